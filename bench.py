@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: stereo frames/s of the point+line front-end on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--frames-per-gpu F]
+  python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--frames-per-gpu F] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the whole per-frame hot path (ORB extract x2, LSD/LBD extract x2, stereo point + line
 matching; with --config 3 also the frame-to-frame track matching) over a batch of synthetic EuRoC-shaped stereo
 frames that are already resident in HBM, followed for N > 1 by the RCCL gather of the per-frame result tables to
-rank 0.  Rank 0 prints ONE JSON line (the driver contract of the task statement).
+rank 0.  Rank 0 prints ONE JSON line (the driver contract of the task statement); `ms_per_step` is one timed step.
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what the headline does not need: the
+per-kernel profile and roofline (a profiled pass of K more steps), the CPU baseline, the parity check of the last timed
+step against the oracle, and the single-pair, host-inclusive and large-batch legs.  --dump-outputs DIR writes the
+records of the last timed step as DIR/<name>.npy (dump_outputs): the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 Workloads (BASELINE.json `configs`):
   default      752x480, 1200 ORB kp + <=100 lines, F frames per GPU per step (weak scaling)
@@ -365,6 +371,76 @@ def dry_tables(args, rank, world):
     return 0 if ok else 1
 
 
+def synth_pair(job):
+    """One seeded synthetic stereo pair (seed, W, H, t) as a (2, H, W) u8 array: a worker of make_images."""
+    from pli_slam_amd import synth
+    seed, W, H, t = job
+    return np.stack(synth.make_stereo_pair(seed, W, H, t=t))
+
+
+def make_images(args, rank, world, nuniq, W, H):
+    """(nuniq, 2, H, W) u8: the distinct stereo pairs of this rank.  Synthetic pairs are made by forked worker processes, at most 16
+    per node shared by its ranks (numpy and scipy hold the GIL for most of a pair: threads barely help), so this runs before the
+    process touches the GPU."""
+    if args.real_images:
+        from pli_slam_amd import realdata
+        return np.stack([np.stack(p) for p in realdata.frames_752x480(nuniq, seed=17 + rank, w=W, h=H)])
+    if args.config == 3:
+        # one scene for all ranks, rank r holds the time slice [r * nuniq, r * nuniq + nuniq): consecutive shards of ONE stream
+        jobs = [(100, W, H, rank * nuniq + t_) for t_ in range(nuniq)]
+    else:
+        jobs = [(s_, W, H, 0) for s_ in range(rank * nuniq, rank * nuniq + nuniq)]
+    nproc = min(len(jobs), max(1, min(16, len(os.sched_getaffinity(0))) // world))
+    if nproc <= 1:
+        return np.stack([synth_pair(j) for j in jobs])
+    import multiprocessing
+    with multiprocessing.get_context("fork").Pool(nproc) as pool:
+        return np.stack(pool.map(synth_pair, jobs))
+
+
+DUMP_FRAMES = 64          # --dump-outputs writes at most this many records ...
+DUMP_BYTES = 64 << 20     # ... and fewer where they could exceed this at full keypoint / keyline capacity
+
+
+def dump_outputs(fe, table, F, track, track_base, out_dir):
+    """--dump-outputs: the records of the last timed step as a caller reads them (Frontend.parse_record), as out_dir/<name>.npy.
+    frames.npy holds the frame indices written: all F frames, or a fixed seeded sample of them (DUMP_FRAMES, DUMP_BYTES), sorted;
+    counts.npy their 8 record counts (keypoints L / R, keylines L / R, ...).  Every other name concatenates the arrays of those
+    frames in that order, split by the counts: kpL / kpR (n x 6: x, y, size, angle, response, octave), descL / descR (n x 32
+    descriptor bytes), klL / klR (m x 17 KeyLine fields), ldescL / ldescR (m x 32), uright and depth (n of the left eye), disp
+    (m x 2) and le (m x 3) of the left keylines; with the frame-to-frame track (config 3, own frame f at record track_base + f of
+    `track`) track_counts (4 per frame), track_best and track_lines.  float32, float64 where the record holds doubles; every
+    integer field is exact."""
+    import torch
+    Y = fe.layout
+    kpc, klc = int(Y.kp_cap), int(Y.kl_cap)
+    per_frame = 4 * (2 * kpc * (6 + 32 + 1) + 2 * klc * (17 + 32 + 1)) + 8 * (3 * klc + 9) + (8 * 4 + 4 * (kpc + klc) if track is not None else 0)
+    k = min(F, DUMP_FRAMES, max(1, DUMP_BYTES // per_frame))
+    frames = np.arange(F) if k == F else np.sort(np.random.default_rng(0).permutation(F)[:k])
+    rec_bytes = int(Y.record_bytes)
+    host = table[:F * rec_bytes].view(F, rec_bytes)[torch.as_tensor(frames, device=table.device)].cpu().numpy().reshape(-1)
+    recs = [fe.parse_record(host, i) for i in range(k)]
+
+    def cat(key, fields=False, dtype=np.float32):
+        if fields:           # structured keypoints / keylines: one float column per field
+            return np.concatenate([np.stack([r[key][n_].astype(dtype) for n_ in r[key].dtype.names], 1) for r in recs])
+        return np.concatenate([r[key] for r in recs]).astype(dtype)
+    out = {"frames": frames.astype(np.float64), "counts": np.stack([r["counts"] for r in recs]).astype(np.float64)}
+    for e in "LR":
+        out["kp" + e], out["desc" + e] = cat("kp" + e, True), cat("desc" + e)
+        out["kl" + e], out["ldesc" + e] = cat("kl" + e, True), cat("ldesc" + e)
+    out.update(uright=cat("uright"), depth=cat("depth"), disp=cat("disp"), le=cat("le", dtype=np.float64))
+    if track is not None:
+        th = track.cpu().numpy()
+        trs = [fe.parse_track(th, track_base + int(f)) for f in frames]
+        out["track_counts"] = np.stack([t["counts"] for t in trs]).astype(np.float64)
+        out["track_best"] = np.concatenate([t["best"] for t in trs]).astype(np.float32)
+        out["track_lines"] = np.concatenate([t["lines"] for t in trs]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -395,6 +471,12 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="all ranks run their kernels on GPU 0 (rehearsal of the multi-rank path on a one-GPU box; needs --backend gloo: "
                          "the tables are staged through the host for the gather and the halo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the per-kernel profile and roofline (a profiled pass of --steps steps "
+                         "after the timed ones), the CPU baseline, the parity check against the oracle, the single-pair, host-inclusive and "
+                         "large-batch legs (--no-cpu-baseline / --no-host-leg / --no-large-batch-leg drop legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -421,6 +503,29 @@ def main():
 
     if args.real_images and (args.config in (3, 5) or (args.width or 752) != 752 or (args.height or 480) != 480):
         sys.exit("--real-images cuts 752x480 windows from the photographs: not with --config 3 / 5 or another --width / --height")
+
+    from pli_slam_amd import capi
+    from pli_slam_amd.sharding import shard_range
+
+    C_ = CONFIGS.get(args.config, CONFIGS[2] if args.config == 0 else None)
+    W, H = args.width or C_["W"], args.height or C_["H"]
+    nfeat, nlines = args.nfeatures or C_["nf"], args.nlines or C_["nl"]
+    if args.config == 2:
+        F = 1
+    elif args.config == 4:
+        F = max(1, args.inflight) * shard_range(BATCH4, rank, world)[1]
+    elif args.config == 5:
+        F = args.frames_per_gpu or 16
+    elif args.config == 3:
+        F = args.frames_per_gpu or 64
+    else:
+        F = args.frames_per_gpu or 256
+    # synthetic stream: up to --unique-frames distinct seeded stereo pairs per rank (seeds disjoint across ranks), cycled to F
+    # frames; config 3: consecutive frames t = 0..nuniq-1 of ONE scene (the motion of synth.make_stereo_pair).  Made before this
+    # process touches the GPU: make_images forks its workers
+    nuniq = min(F, args.unique_frames)
+    images = make_images(args, rank, world, nuniq, W, H)               # (nuniq, 2, H, W) u8
+
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the front-end has no CPU path")
     if args.share_device:
@@ -442,23 +547,10 @@ def main():
             dist.init_process_group(args.backend, rank=rank, world_size=world, device_id=dev)
         assert dist.get_world_size() == args.gpus
 
-    from pli_slam_amd import capi, synth
+    from pli_slam_amd import synth
     from pli_slam_amd.frontend import Frontend
-    from pli_slam_amd.sharding import TableGatherer, shard_range
+    from pli_slam_amd.sharding import TableGatherer
 
-    C_ = CONFIGS.get(args.config, CONFIGS[2] if args.config == 0 else None)
-    W, H = args.width or C_["W"], args.height or C_["H"]
-    nfeat, nlines = args.nfeatures or C_["nf"], args.nlines or C_["nl"]
-    if args.config == 2:
-        F = 1
-    elif args.config == 4:
-        F = max(1, args.inflight) * shard_range(BATCH4, rank, world)[1]
-    elif args.config == 5:
-        F = args.frames_per_gpu or 16
-    elif args.config == 3:
-        F = args.frames_per_gpu or 64
-    else:
-        F = args.frames_per_gpu or 256
     Fmax = F
     if multi:                                         # equal table sizes for the gather (config 4 shards may differ by one)
         t = torch.tensor([F], device=ctl)
@@ -468,20 +560,6 @@ def main():
     cfg = capi.default_config(W, H, orb_nfeatures=nfeat, lsd_nfeatures=nlines, max_frames=Fmax + (1 if (args.config == 3 and multi) else 0),
                               lsd_mode=args.lsd_mode)
     fe = Frontend(cfg, device=local_rank, dev=False)      # (the product library: PLI_USE_DEV_LIB=1 — the tools — swaps in the development build)
-    # synthetic stream: up to --unique-frames distinct seeded stereo pairs per rank (seeds disjoint across ranks), cycled to F
-    # frames; config 3: consecutive frames t = 0..nuniq-1 of ONE scene (the motion of synth.make_stereo_pair)
-    nuniq = min(F, args.unique_frames)
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(min(32, os.cpu_count() or 1)) as ex:
-        if args.config == 3:
-            # one scene for all ranks, rank r holds the time slice [r * nuniq, r * nuniq + nuniq): consecutive shards of ONE stream
-            pairs = list(ex.map(lambda t_: synth.make_stereo_pair(100, W, H, t=rank * nuniq + t_), range(nuniq)))
-        elif args.real_images:
-            from pli_slam_amd import realdata
-            pairs = realdata.frames_752x480(nuniq, seed=17 + rank, w=W, h=H)
-        else:
-            pairs = list(ex.map(lambda s_: synth.make_stereo_pair(s_, W, H), range(rank * nuniq, rank * nuniq + nuniq)))
-    images = np.stack([np.stack(p) for p in pairs])                    # (nuniq, 2, H, W) u8
     d_uniq = torch.from_numpy(images).to(dev)
     d_img = d_uniq[torch.arange(F, device=dev) % nuniq].contiguous()   # (F, 2, H, W) resident in HBM before timing
     d_left, d_right = d_img[:, 0].contiguous(), d_img[:, 1].contiguous()
@@ -542,15 +620,14 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    fe.prof_reset()
-    fe.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
-    fe.prof_enable(False)
-    prof = fe.prof_report()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fe, gath.table(last_slot[0]) if gath else d_table, F, track[2] if track is not None else None,
+                     1 if track is not None and multi else 0, args.dump_outputs)
     frames_done = torch.tensor([float(F * args.steps)], dtype=torch.float64, device=ctl)
     ranks_ev = None
     if multi:
@@ -565,7 +642,7 @@ def main():
     # track of its first frame against the oracle's track over [last frame of the previous shard | own first frame] (config 3:
     # that track exists only through the halo exchange); rank 0 checks records of EVERY rank's gathered shard against the oracle.
     parity_multi = None
-    if multi and not args.no_cpu_baseline:
+    if args.full and multi and not args.no_cpu_baseline:
         counts_r = [shard_range(BATCH4, r_, world)[1] * max(1, args.inflight) if args.config == 4 else F for r_ in range(world)]
 
         real_cache = {}
@@ -591,132 +668,27 @@ def main():
             parity_multi["halo_tracks_checked_against_oracle"] = int(hb[0].item())
             parity_multi["halo_tracks_mismatching"] = int(hb[1].item())
             parity_multi["ok"] = bool(parity_multi["ok"] and hb[1].item() == 0)
+    parity = None
+    if args.full and not multi and not args.no_cpu_baseline:
+        # the table the last timed step left in d_table is the one that is checked
+        parity = parity_check(fe, cfg, d_table, images, F, nuniq, rec_bytes)
+
+    prof = {}
+    if args.full:
+        # per-kernel HIP-event times in a pass of their own after the timed steps (the same step, --steps times): the two events
+        # around every launch stay out of the headline
+        fe.prof_reset()
+        fe.prof_enable(True)
+        for _ in range(args.steps):
+            step()
+        fence()
+        fe.prof_enable(False)
+        prof = fe.prof_report()
 
     rc = 0
     if rank == 0:
         b_frame, g = path_bytes_per_frame(W, H, cfg.orb_nlevels, cfg.orb_scale_factor, nfeat, nlines, cfg.lsd_scale)
         fps = total_frames / dt
-        # dominant kernel by HIP-event time on the stream it ran on.  The ORB chain runs on a side stream beside the (longer) line
-        # chain: the event times of its kernels include the time they wait for compute units behind the line kernels, so they
-        # do not compete (alone — PLI_SIDE_MAX=0 — none of them comes near the growers)
-        orb_chain = ("k_resize_level", "k_fast_cells", "k_octree", "k_blur_orb", "k_describe", "k_kp_counts")
-        cand = {k: v for k, v in prof.items() if k not in orb_chain} or prof
-        dom = max(cand.items(), key=lambda kv: kv[1][1]) if cand else (None, (0, 0.0))
-        name, (calls, total_ms) = dom
-        per_img = kernel_bytes_per_image(name, g, nfeat, nlines, W, H) if name else None
-        # a relaxation grower is launched once per round; ideally the rounds of a step together touch the angle / modgrad planes
-        # once, so the algorithmic bytes of ONE launch are that pass divided by the launches of the step
-        if per_img is not None and name in ("k_tx_grow_sparse", "k_rx_grow", "k_rx_grow_big", "k_rx_grow_wave"):
-            per_img = per_img / max(calls / max(args.steps, 1), 1.0)
-        avg_s = (total_ms / max(calls, 1)) * 1e-3
-        peak = 8000.0
-        achieved = per_img * 2 * F / avg_s / 1e9 if (per_img is not None and avg_s > 0) else None
-        issue = None       # what the dominant kernel is bound by, from the committed SQ passes of the same workload
-        step_traffic = None  # counter traffic of the WHOLE step (every kernel x its launches) against the algorithmic bytes
-        traffic = None     # HBM bytes per launch from the committed PMC passes of the same workload, if any
-        sector = None      # the growers are gather kernels: their ceiling is the rate of random 128-byte line requests the chip
-        counters_note = None   # why a counter-derived field is null, or which committed workload stood in for this one
-        try:               # sustains (tools/probes/gather_rate.hip, profiles/r02_gather_rate_probe.txt: 49 G/s), not the stream peak
-            tpath = [p_ for p_ in (os.path.join(ROOT, "profiles", "r%02d_traffic.json" % n_) for n_ in (6, 5, 4, 3, 2)) if os.path.exists(p_)][0]
-            tr = json.load(open(tpath))
-            wkey = "%dx%d_F%d" % (W, H, F)
-            src_F = F
-            if wkey not in tr["workloads"]:
-                # no counter pass was committed for this batch size (a shard of config 4, another --frames-per-gpu): the nearest committed
-                # workload of the SAME image size stands in, its per-launch counters scaled by the ratio of the batch sizes (the
-                # kernels of the path are per-image work), and the line says so
-                same = sorted((abs(int(k_.split("_F")[1]) - F), k_) for k_ in tr["workloads"] if k_.startswith("%dx%d_F" % (W, H)))
-                if same:
-                    wkey = same[0][1]
-                    src_F = int(wkey.split("_F")[1])
-                    counters_note = "no committed counter pass for F = %d: %s of %s scaled by %d / %d" % (F, wkey, os.path.basename(tpath), F, src_F)
-                else:
-                    counters_note = "no committed counter pass for %dx%d in %s" % (W, H, os.path.basename(tpath))
-            scale_F = F / float(src_F)
-            k = tr["workloads"].get(wkey, {}).get(name)
-            if k and scale_F != 1.0:
-                k = dict(k, fetch_kb=k["fetch_kb"] * scale_F, write_kb=k["write_kb"] * scale_F)
-            # bytes = 2 x FETCH_SIZE + WRITE_SIZE for EVERY kernel: the L2 reads memory in 128-byte lines — streams and the growers'
-            # random 16-byte gathers alike (TCC_EA0_RDREQ_128B = TCC_EA0_RDREQ for each kernel of the step and for the patterns of known
-            # size of tools/probes/read_amp.hip: profiles/r05_counter_calibration.txt) — and FETCH_SIZE tallies a request as 64 bytes.
-            # (Rounds 2-4 and the first round-5 lines counted the growers' requests as 64-byte sectors: their traffic was understated.)
-            wl = tr["workloads"].get(wkey, {})
-            if wl and all("launches" in v_ for v_ in wl.values()):
-                tot = scale_F * sum(v_["launches"] * (2 * v_["fetch_kb"] + v_["write_kb"]) * 1024 for kn_, v_ in wl.items() if "alias_of" not in v_)
-                step_traffic = {"bytes_per_step": tot, "algorithmic_bytes_per_step": b_frame * F, "ratio": tot / (b_frame * F),
-                                "hbm_GBps_at_this_rate": tot / (dt / args.steps) / 1e9, "source": os.path.basename(tpath), "source_workload": wkey,
-                                "note": "sum over the kernels of the committed FETCH_SIZE / WRITE_SIZE passes x their launches per step; "
-                                        "every read request is a 128-byte line (2 x FETCH_SIZE), the growers' gathers included"}
-            iq = tr.get("issue", {}).get(wkey, {}).get(name)
-            if iq and iq["avg_ns"] > 0 and scale_F == 1.0:
-                simd_quads = 1024 * iq["avg_ns"] * 2.4 / 4.0        # quad-cycles all SIMDs of the chip offer during one launch (2.4 GHz)
-                issue = {"valu_issue_frac": iq["active_valu_quad_cycles"] / simd_quads, "valu_wave_instructions": iq["valu"],
-                         "salu_wave_instructions": iq["salu"], "launch_ns_under_profiler": iq["avg_ns"], "source": os.path.basename(tpath),
-                         "note": "SQ_ACTIVE_INST_VALU / (1024 SIMDs x quad-cycles of the launch): the share of the chip's VALU issue "
-                                 "time the kernel uses (profiler run, 2.4 GHz assumed)"}
-            if k:
-                # FETCH_SIZE tallies every read request as 64 bytes on gfx950 (MI355X_MICROARCH.md: x2); the requests are 128-byte lines
-                # for the growers' gathers as well (profiles/r05_counter_calibration.txt)
-                traffic = (2 * k["fetch_kb"] + k["write_kb"]) * 1024
-                if name.startswith(("k_tx_grow", "k_lsd_grow", "k_rx_grow")) and avg_s > 0:
-                    rate = k["fetch_kb"] * 1024 / 64 / avg_s / 1e9      # requests per second (FETCH_SIZE = requests x 64 B)
-                    sector = {"achieved": rate, "peak": 49.0, "unit": "G 128-byte line requests/s (L2 misses)", "frac": rate / 49.0,
-                              "note": "peak measured by tools/probes/gather_rate.hip (random gathers: 49 G lines/s = 6.3 TB/s, the HBM "
-                                      "rate a stream reaches too); requests per launch from the committed FETCH_SIZE pass"}
-        except Exception as e:     # (the headline does not depend on the committed counter files; the line says what went wrong)
-            counters_note = "counter files not usable: %r" % (e,)
-        traffic_rate = (traffic / avg_s / 1e9) if (traffic and avg_s > 0) else None
-        if args.real_images and traffic is not None:
-            # the committed counter passes are of the SYNTHETIC batch: the bytes stand as an upper bound for these (calmer) frames, a rate
-            # formed with this run's launch time would not be a measurement
-            traffic_rate, sector = None, None
-            counters_note = ((counters_note + "; ") if counters_note else "") + "counter passes are of the synthetic batch, not of these frames"
-        # every kernel of the step against the HBM peak: algorithmic bytes per image (table above) x images per step / its time per step
-        # (a kernel of the ORB chain is timed on the side stream, beside the line chain: its fraction is a lower bound)
-        kfrac = {}
-        for kn, (kc, kms) in prof.items():
-            b_img = kernel_bytes_per_image(kn, g, nfeat, nlines, W, H)
-            if kn == "k_resize_level":           # seven launches: level k reads level k - 1 and writes itself
-                lv, sc, b_img = [], np.float32(1.0), 0
-                for l in range(cfg.orb_nlevels):
-                    inv = np.float32(1.0) / sc
-                    lv.append(int(np.rint(np.float32(W) * inv)) * int(np.rint(np.float32(H) * inv)))
-                    sc = np.float32(sc * np.float32(cfg.orb_scale_factor))
-                b_img = sum(lv[l - 1] + lv[l] for l in range(1, len(lv)))
-            if b_img and kms > 0:
-                fr_ = b_img * 2 * F * args.steps / (kms * 1e-3) / 1e9 / peak
-                # (above the peak = the launch did not do that work: the ordered-list kernels in the key mode of the tile relaxation
-                # end at once unless an image is left to the sequential grower)
-                if fr_ <= 1.0:
-                    kfrac[kn] = round(fr_, 4)
-        side = orb_chain + ("k_stereo_points", "k_stereo_median", "k_blur_lbd", "k_sobel")
-        grower = bool(name) and name.startswith(("k_tx_grow", "k_lsd_grow", "k_rx_grow"))
-        # `frac` is against the HBM peak by ALGORITHMIC bytes, as the contract asks.  A region grower is a chain of dependent random
-        # gathers at the occupancy limit of 8 waves per SIMD: `bound` names that category; every 16-byte gather that misses the L2 moves a
-        # 128-byte line, so its MEASURED traffic (`traffic`, `traffic_GBps`) is tens of times its algorithmic bytes and about half of what
-        # the memory system delivers to gathers (`sector_requests`) — `limiter` names the three shares (the measurements behind them:
-        # DESIGN.md 5); `issue`, `sector_requests` and `step_traffic` carry what the committed counter passes of this workload say —
-        # null, with `counters_note`, when there are none
-        roof = {"bound": "latency (wave slots)" if grower else "hbm", "kernel": name, "achieved": achieved, "peak": peak, "unit": "GB/s",
-                "frac": (achieved / peak) if achieved is not None else None, "traffic": traffic, "traffic_GBps": traffic_rate, "sector_requests": sector,
-                "limiter": "VALU issue / dependent trips at 8 waves per SIMD / 128-byte lines for 8-byte gathers (DESIGN.md 5)" if grower else "hbm",
-                "counters_note": counters_note,
-                "issue": issue, "step_traffic": step_traffic,
-                "avg_launch_ms": avg_s * 1e3, "launches": calls,
-                "kernel_launches_per_step": round(sum(v[0] for v in prof.values()) / max(args.steps, 1), 1),
-                "path_achieved": fps / world * b_frame / 1e9, "path_frac": fps / world * b_frame / 1e9 / peak,
-                "kernel_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in
-                                       sorted(prof.items(), key=lambda kv: -kv[1][1]) if k not in side},
-                "side_stream_kernel_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in
-                                                   sorted(prof.items(), key=lambda kv: -kv[1][1]) if k in side},
-                "kernel_hbm_frac": dict(sorted(kfrac.items(), key=lambda kv: -kv[1])),
-                "kernel_ms_note": "HIP-event time between the launch's two events on the stream it ran on, summed per step.  "
-                                  "side_stream_kernel_ms_per_step: the ORB chain, the stereo point matcher and the LBD's blur + Sobel run on a "
-                                  "low-priority side stream beside the line chain: their event times INCLUDE the wait for wave slots behind the "
-                                  "line kernels (alone, PLI_SIDE_MAX=0, 256 frames: k_resize_level 0.7 ms, k_fast_cells 3.0, k_octree 1.5, "
-                                  "k_blur_orb 1.0, k_describe 1.0) and are not comparable with the main stream's; the line chain's kernels are "
-                                  "stretched by them in turn (alone: k_tx_round2 1.8 ms, k_tx_grow_sparse 3.0; the chain forks behind round 2's owner pass of a "
-                                  "large batch).  DESIGN.md 5 / 7 have every kernel alone"}
         what = C_["what"] if args.config else ("752x480 stereo pairs, extract + stereo Hamming match (BASELINE configs[1] shape, "
                                                "batched)")
         out = {
@@ -733,14 +705,16 @@ def main():
                                    "GPU per step" % (world, what, W, H, nfeat, nlines, F),
                        "baseline_config": args.config or None, "frames_per_gpu": F, "bytes_per_frame": b_frame,
                        "parallelism": "frame-batch data parallel, %d rank(s), gather of result tables to rank 0" % world},
-            "roofline": roof,
             "library": os.path.basename(getattr(fe.L, "_name", "?")),
         }
-        rs = fe.lsd_round_stats()
-        out["lsd_arena_words_per_pixel"] = fe.lsd_arena_words() if hasattr(fe.L, "pli_lsd_arena_words") else None
-        out["lsd_rounds"] = {"launched_without_host_look": rs[0], "needed_by_slowest_image": rs[1], "images_redone_by_device_fallback": rs[2],
-                             "note": "relaxation rounds per step; an image that has not settled after the launched rounds is redone on the "
-                                     "device by the sequential grower (exact, slow): needed = -1 would flag it"}
+        if args.full:
+            out["roofline"] = roofline(prof, g, b_frame, fps, dt, W, H, F, nfeat, nlines, world, args.steps, cfg, args.real_images)
+            rs = fe.lsd_round_stats()
+            out["lsd_arena_words_per_pixel"] = fe.lsd_arena_words() if hasattr(fe.L, "pli_lsd_arena_words") else None
+            out["lsd_rounds"] = {"launched_without_host_look": rs[0], "needed_by_slowest_image": rs[1],
+                                 "images_redone_by_device_fallback": rs[2],
+                                 "note": "relaxation rounds per step; an image that has not settled after the launched rounds is redone "
+                                         "on the device by the sequential grower (exact, slow): needed = -1 would flag it"}
         if multi:
             out["gather"] = {"bytes_per_rank_per_step": Fmax * rec_bytes, "bytes_at_root_per_step": world * Fmax * rec_bytes,
                              "backend": args.backend, "staged_through_host": bool(gath.staged)}
@@ -765,11 +739,11 @@ def main():
         if args.config == 4:
             out["config"]["batch_frames"] = BATCH4
             out["config"]["batches_in_flight"] = max(1, args.inflight)
-        if multi and not args.no_cpu_baseline:
+        if args.full and multi and not args.no_cpu_baseline:
             # the multi-rank line carries the CPU baseline too (rule d): rank 0 times the oracle on a sample of ITS shard after the
             # timed region; the other ranks wait at the closing barrier below
             out["cpu_baseline"] = cpu_baseline(images, bytes(cfg), budget_s=args.cpu_baseline_seconds)
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             # BASELINE.json configs[1] (a single stereo pair) beside the batch: latency of one pair through the same library
             if F > 1 and (W, H) == (752, 480):
                 f1 = Frontend(capi.default_config(W, H, orb_nfeatures=nfeat, lsd_nfeatures=nlines, max_frames=1), device=local_rank, dev=False)
@@ -792,8 +766,7 @@ def main():
             if not args.no_host_leg:
                 out["host_inclusive"] = host_inclusive_leg(fe, images, F, nuniq, W, H, rec_bytes, args.steps)
             out["cpu_baseline"] = cpu_baseline(images, bytes(cfg), budget_s=args.cpu_baseline_seconds)
-            # the table the last timed step left in d_table is the one that is checked
-            out["parity"] = parity_check(fe, cfg, d_table, images, F, nuniq, rec_bytes)
+            out["parity"] = parity
             if not out["parity"]["ok"]:
                 out["value"] = None                   # a fast path whose results differ from the reference's is not a result
                 rc = 3
@@ -835,6 +808,133 @@ def large_batch_leg(capi, Frontend, nfeat, nlines, lsd_mode, device, d_uniq, nun
     dt = time.perf_counter() - t0
     return {"frames_per_gpu": F, "value": F * steps / dt, "unit": "stereo frames/s", "ms_per_step": dt / steps * 1e3, "steps": steps,
             "note": "same path and shapes, %d stereo frames per step on one GPU (sequential LSD schedule)" % F}
+
+
+def roofline(prof, g, b_frame, fps, dt, W, H, F, nfeat, nlines, world, steps, cfg, real_images):
+    """The `roofline` object of a --full line: the dominant kernel of the profiled pass against the HBM peak, every kernel's
+    time per step, and what the committed counter passes of the same workload say about it."""
+    # dominant kernel by HIP-event time on the stream it ran on.  The ORB chain runs on a side stream beside the (longer) line
+    # chain: the event times of its kernels include the time they wait for compute units behind the line kernels, so they
+    # do not compete (alone — PLI_SIDE_MAX=0 — none of them comes near the growers, see DESIGN.md §7)
+    orb_chain = ("k_resize_level", "k_fast_cells", "k_octree", "k_blur_orb", "k_describe", "k_kp_counts")
+    cand = {k: v for k, v in prof.items() if k not in orb_chain} or prof
+    dom = max(cand.items(), key=lambda kv: kv[1][1]) if cand else (None, (0, 0.0))
+    name, (calls, total_ms) = dom
+    per_img = kernel_bytes_per_image(name, g, nfeat, nlines, W, H) if name else None
+    # a relaxation grower is launched once per round; ideally the rounds of a step together touch the angle / modgrad planes
+    # once, so the algorithmic bytes of ONE launch are that pass divided by the launches of the step
+    if per_img is not None and name in ("k_tx_grow_sparse", "k_rx_grow", "k_rx_grow_big", "k_rx_grow_wave"):
+        per_img = per_img / max(calls / max(steps, 1), 1.0)
+    avg_s = (total_ms / max(calls, 1)) * 1e-3
+    peak = 8000.0
+    achieved = per_img * 2 * F / avg_s / 1e9 if (per_img is not None and avg_s > 0) else None
+    issue = None       # what the dominant kernel is bound by, from the committed SQ passes of the same workload
+    step_traffic = None  # counter traffic of the WHOLE step (every kernel x its launches) against the algorithmic bytes
+    traffic = None     # HBM bytes per launch from the committed PMC passes of the same workload, if any
+    sector = None      # the growers are gather kernels: their ceiling is the rate of random 128-byte line requests the chip
+    counters_note = None   # why a counter-derived field is null, or which committed workload stood in for this one
+    try:               # sustains (tools/probes/gather_rate.hip, profiles/r02_gather_rate_probe.txt: 49 G/s), not the stream peak
+        tpath = [p_ for p_ in (os.path.join(ROOT, "profiles", "r%02d_traffic.json" % n_) for n_ in (6, 5, 4, 3, 2)) if os.path.exists(p_)][0]
+        tr = json.load(open(tpath))
+        wkey = "%dx%d_F%d" % (W, H, F)
+        src_F = F
+        if wkey not in tr["workloads"]:
+            # no counter pass was committed for this batch size (a shard of config 4, another --frames-per-gpu): the nearest committed
+            # workload of the SAME image size stands in, its per-launch counters scaled by the ratio of the batch sizes (the
+            # kernels of the path are per-image work), and the line says so
+            same = sorted((abs(int(k_.split("_F")[1]) - F), k_) for k_ in tr["workloads"] if k_.startswith("%dx%d_F" % (W, H)))
+            if same:
+                wkey = same[0][1]
+                src_F = int(wkey.split("_F")[1])
+                counters_note = "no committed counter pass for F = %d: %s of %s scaled by %d / %d" % (F, wkey, os.path.basename(tpath), F, src_F)
+            else:
+                counters_note = "no committed counter pass for %dx%d in %s" % (W, H, os.path.basename(tpath))
+        scale_F = F / float(src_F)
+        k = tr["workloads"].get(wkey, {}).get(name)
+        if k and scale_F != 1.0:
+            k = dict(k, fetch_kb=k["fetch_kb"] * scale_F, write_kb=k["write_kb"] * scale_F)
+        # bytes = 2 x FETCH_SIZE + WRITE_SIZE for EVERY kernel: the L2 reads memory in 128-byte lines — streams and the growers'
+        # random 16-byte gathers alike (TCC_EA0_RDREQ_128B = TCC_EA0_RDREQ for each kernel of the step and for the patterns of known
+        # size of tools/probes/read_amp.hip: profiles/r05_counter_calibration.txt) — and FETCH_SIZE tallies a request as 64 bytes.
+        # (Rounds 2-4 and the first round-5 lines counted the growers' requests as 64-byte sectors: their traffic was understated.)
+        wl = tr["workloads"].get(wkey, {})
+        if wl and all("launches" in v_ for v_ in wl.values()):
+            tot = scale_F * sum(v_["launches"] * (2 * v_["fetch_kb"] + v_["write_kb"]) * 1024 for kn_, v_ in wl.items() if "alias_of" not in v_)
+            step_traffic = {"bytes_per_step": tot, "algorithmic_bytes_per_step": b_frame * F, "ratio": tot / (b_frame * F),
+                            "hbm_GBps_at_this_rate": tot / (dt / steps) / 1e9, "source": os.path.basename(tpath), "source_workload": wkey,
+                            "note": "sum over the kernels of the committed FETCH_SIZE / WRITE_SIZE passes x their launches per step; "
+                                    "every read request is a 128-byte line (2 x FETCH_SIZE), the growers' gathers included"}
+        iq = tr.get("issue", {}).get(wkey, {}).get(name)
+        if iq and iq["avg_ns"] > 0 and scale_F == 1.0:
+            simd_quads = 1024 * iq["avg_ns"] * 2.4 / 4.0        # quad-cycles all SIMDs of the chip offer during one launch (2.4 GHz)
+            issue = {"valu_issue_frac": iq["active_valu_quad_cycles"] / simd_quads, "valu_wave_instructions": iq["valu"],
+                     "salu_wave_instructions": iq["salu"], "launch_ns_under_profiler": iq["avg_ns"], "source": os.path.basename(tpath),
+                     "note": "SQ_ACTIVE_INST_VALU / (1024 SIMDs x quad-cycles of the launch): the share of the chip's VALU issue "
+                             "time the kernel uses (profiler run, 2.4 GHz assumed)"}
+        if k:
+            # FETCH_SIZE tallies every read request as 64 bytes on gfx950 (MI355X_MICROARCH.md: x2); the requests are 128-byte lines
+            # for the growers' gathers as well (profiles/r05_counter_calibration.txt)
+            traffic = (2 * k["fetch_kb"] + k["write_kb"]) * 1024
+            if name.startswith(("k_tx_grow", "k_lsd_grow", "k_rx_grow")) and avg_s > 0:
+                rate = k["fetch_kb"] * 1024 / 64 / avg_s / 1e9      # requests per second (FETCH_SIZE = requests x 64 B)
+                sector = {"achieved": rate, "peak": 49.0, "unit": "G 128-byte line requests/s (L2 misses)", "frac": rate / 49.0,
+                          "note": "peak measured by tools/probes/gather_rate.hip (random gathers: 49 G lines/s = 6.3 TB/s, the HBM "
+                                  "rate a stream reaches too); requests per launch from the committed FETCH_SIZE pass"}
+    except Exception as e:     # (the headline does not depend on the committed counter files; the line says what went wrong)
+        counters_note = "counter files not usable: %r" % (e,)
+    traffic_rate = (traffic / avg_s / 1e9) if (traffic and avg_s > 0) else None
+    if real_images and traffic is not None:
+        # the committed counter passes are of the SYNTHETIC batch: the bytes stand as an upper bound for these (calmer) frames, a rate
+        # formed with this run's launch time would not be a measurement
+        traffic_rate, sector = None, None
+        counters_note = ((counters_note + "; ") if counters_note else "") + "counter passes are of the synthetic batch, not of these frames"
+    # every kernel of the step against the HBM peak: algorithmic bytes per image (table above) x images per step / its time per step
+    # (a kernel of the ORB chain is timed on the side stream, beside the line chain: its fraction is a lower bound)
+    kfrac = {}
+    for kn, (kc, kms) in prof.items():
+        b_img = kernel_bytes_per_image(kn, g, nfeat, nlines, W, H)
+        if kn == "k_resize_level":           # seven launches: level k reads level k - 1 and writes itself
+            lv, sc, b_img = [], np.float32(1.0), 0
+            for l in range(cfg.orb_nlevels):
+                inv = np.float32(1.0) / sc
+                lv.append(int(np.rint(np.float32(W) * inv)) * int(np.rint(np.float32(H) * inv)))
+                sc = np.float32(sc * np.float32(cfg.orb_scale_factor))
+            b_img = sum(lv[l - 1] + lv[l] for l in range(1, len(lv)))
+        if b_img and kms > 0:
+            fr_ = b_img * 2 * F * steps / (kms * 1e-3) / 1e9 / peak
+            # (above the peak = the launch did not do that work: the ordered-list kernels in the key mode of the tile relaxation
+            # end at once unless an image is left to the sequential grower)
+            if fr_ <= 1.0:
+                kfrac[kn] = round(fr_, 4)
+    side = orb_chain + ("k_stereo_points", "k_stereo_median", "k_blur_lbd", "k_sobel")
+    grower = bool(name) and name.startswith(("k_tx_grow", "k_lsd_grow", "k_rx_grow"))
+    # `frac` is against the HBM peak by ALGORITHMIC bytes, as the contract asks.  A region grower is a chain of dependent random
+    # gathers at the occupancy limit of 8 waves per SIMD: `bound` names that category; every 16-byte gather that misses the L2 moves a
+    # 128-byte line, so its MEASURED traffic (`traffic`, `traffic_GBps`) is tens of times its algorithmic bytes and about half of what
+    # the memory system delivers to gathers (`sector_requests`) — `limiter` names the three shares (the measurements behind them:
+    # DESIGN.md 5); `issue`, `sector_requests` and `step_traffic` carry what the committed counter passes of this workload say —
+    # null, with `counters_note`, when there are none
+    roof = {"bound": "latency (wave slots)" if grower else "hbm", "kernel": name, "achieved": achieved, "peak": peak, "unit": "GB/s",
+            "frac": (achieved / peak) if achieved is not None else None, "traffic": traffic, "traffic_GBps": traffic_rate, "sector_requests": sector,
+            "limiter": "VALU issue / dependent trips at 8 waves per SIMD / 128-byte lines for 8-byte gathers (DESIGN.md 5)" if grower else "hbm",
+            "counters_note": counters_note,
+            "issue": issue, "step_traffic": step_traffic,
+            "avg_launch_ms": avg_s * 1e3, "launches": calls,
+            "kernel_launches_per_step": round(sum(v[0] for v in prof.values()) / max(steps, 1), 1),
+            "path_achieved": fps / world * b_frame / 1e9, "path_frac": fps / world * b_frame / 1e9 / peak,
+            "kernel_ms_per_step": {k: round(v[1] / steps, 4) for k, v in
+                                   sorted(prof.items(), key=lambda kv: -kv[1][1]) if k not in side},
+            "side_stream_kernel_ms_per_step": {k: round(v[1] / steps, 4) for k, v in
+                                               sorted(prof.items(), key=lambda kv: -kv[1][1]) if k in side},
+            "kernel_hbm_frac": dict(sorted(kfrac.items(), key=lambda kv: -kv[1])),
+            "kernel_ms_note": "HIP-event time between the launch's two events on the stream it ran on, summed per step.  "
+                              "side_stream_kernel_ms_per_step: the ORB chain, the stereo point matcher and the LBD's blur + Sobel run on a "
+                              "low-priority side stream beside the line chain: their event times INCLUDE the wait for wave slots behind the "
+                              "line kernels (alone, PLI_SIDE_MAX=0, 256 frames: k_resize_level 0.7 ms, k_fast_cells 3.0, k_octree 1.5, "
+                              "k_blur_orb 1.0, k_describe 1.0) and are not comparable with the main stream's; the line chain's kernels are "
+                              "stretched by them in turn (alone: k_tx_round2 1.8 ms, k_tx_grow_sparse 3.0; the chain forks behind round 2's owner pass of a "
+                              "large batch).  DESIGN.md 5 / 7 have every kernel alone"}
+    return roof
 
 
 def host_inclusive_leg(fe, images, F, nuniq, W, H, rec_bytes, steps):

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 def run_bench(*extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "2", "--warmup", "1",
-                          "--cpu-baseline-seconds", "3", *extra], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--cpu-baseline-seconds", "3", *extra], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -78,7 +78,7 @@ def run_nccl_one_rank(*extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--backend", "nccl", "--force-dist", "--steps", "2", "--warmup", "1",
-                          "--cpu-baseline-seconds", "3", *extra], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--cpu-baseline-seconds", "3", *extra], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
 

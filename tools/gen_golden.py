@@ -45,6 +45,18 @@ if po.ref() is not None:
     json.dump({"source": "reference src/LineIterator.cpp + src/gridStructure.cpp via oracle/_ref/libpli_ref.so",
                "line_coords": cases, "grid_queries": queries}, open(os.path.join(out, "grid_ref.json"), "w"))
     print("grid_ref.json: %d walks, %d queries" % (len(cases), len(queries)))
+    # grid_ref_live.json: the seeded cases of tests/test_ref_pin.py::test_live_against_reference_build, inputs and the reference's outputs
+    rng = np.random.default_rng(99)
+    walks = rng.uniform(-3, 70, (300, 4))
+    segs = rng.uniform([0, 0, 0, 0], [64, 48, 64, 48], (80, 4))
+    qs = [[int(rng.integers(0, 64)), int(rng.integers(0, 48))] for _ in range(100)]
+    win = [10, 0, 0, 0]
+    json.dump({"source": "reference src/LineIterator.cpp + src/gridStructure.cpp via oracle/_ref/libpli_ref.so",
+               "line_coords": [{"seg": s.tolist(), "cells": po.ref_line_coords(*s).tolist()} for s in walks],
+               "segs": segs.tolist(), "win": win,
+               "grid_queries": [{"q": q, "cand": po.ref_grid_query(segs, 48, 64, q[0], q[1], win).tolist()} for q in qs]},
+              open(os.path.join(out, "grid_ref_live.json"), "w"))
+    print("grid_ref_live.json: %d walks, %d queries" % (len(walks), len(qs)))
 else:
     print("oracle/_ref absent: grid_ref.json not regenerated")
 

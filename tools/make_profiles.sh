@@ -69,26 +69,26 @@ if [[ $WHAT == *markers* ]]; then
 fi
 cd $R
 if [[ $WHAT == *plain* ]]; then
-  timeout 900 python3 bench.py --steps 5 --warmup 1 > $O/bench_default.log 2>&1
+  timeout 900 python3 bench.py --steps 5 --warmup 1 --full > $O/bench_default.log 2>&1
   grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json
   # the other workloads without the profiler attached (the bench_<name>.json beside the kernel stats are runs under rocprofv3)
   for w in "config5_4k --config 5" "config3_720p --config 3" "config2_single_pair --config 2" "f32 --frames-per-gpu 32" "f2048_sequential --frames-per-gpu 2048"; do
     set -- $w; name=$1; shift
-    timeout 900 python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_${name}_plain.json
+    timeout 900 python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline "$@" 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_${name}_plain.json
   done
 fi
 if [[ $WHAT == *sweep4k* ]]; then
   : > $O/sweep_config5_4k.jsonl
   for f in 16 32 64; do
-    timeout 900 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-leg --config 5 --frames-per-gpu $f 2>/dev/null | grep '^{"metric"' | tail -1 >> $O/sweep_config5_4k.jsonl
+    timeout 900 python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-host-leg --config 5 --frames-per-gpu $f 2>/dev/null | grep '^{"metric"' | tail -1 >> $O/sweep_config5_4k.jsonl
   done
 fi
 if [[ $WHAT == *real* ]]; then
-  timeout 900 python3 bench.py --steps 5 --warmup 1 --real-images --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_real_images_f256.json
+  timeout 900 python3 bench.py --steps 5 --warmup 1 --full --real-images --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_real_images_f256.json
 fi
 if [[ $WHAT == *extras* ]]; then
   # the headline batch with every kernel alone and in a row, per-round times (name@round); round 4's real-image workload (64 distinct windows)
-  PLI_USE_DEV_LIB=1 PLI_SIDE_MAX=0 PLI_RX_PROFROUNDS=1 timeout 900 python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_default_f256_alone_per_round.json
-  timeout 900 python3 bench.py --steps 5 --warmup 1 --real-images --unique-frames 64 --no-cpu-baseline --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_real_images_64windows_f256.json
+  PLI_USE_DEV_LIB=1 PLI_SIDE_MAX=0 PLI_RX_PROFROUNDS=1 timeout 900 python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_default_f256_alone_per_round.json
+  timeout 900 python3 bench.py --steps 5 --warmup 1 --full --real-images --unique-frames 64 --no-cpu-baseline --no-host-leg --no-large-batch-leg 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_real_images_64windows_f256.json
 fi
 ls -la $O
