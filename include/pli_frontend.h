@@ -521,6 +521,22 @@ void pli_vocab_destroy(pli_vocab* v);
 pli_status pli_bow_transform(pli_ctx* ctx, const pli_vocab* vocab, const uint8_t* desc, int32_t n, int32_t levelsup,
                              int32_t* word_id, double* weight, int32_t* node_id);
 
+/* ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) ORBmatcher.cc:269-470, F.Nleft == -1 branch (rectified stereo,
+ * RGB-D, mono pinhole), for nkf keyframes against one frame in one call (Tracking::Relocalization's loop, Tracking.cc:4205-4230).
+ * Keyframe k owns rows kf_off[k] .. kf_off[k+1]-1 of kf_desc / kf_angle / kf_node / kf_valid; kf_off[0] = 0, non-decreasing.
+ * *_node[i] = the FeatureVector node that lists feature i, -1 = listed in none (stopped word): pli_bow_transform's node_id where
+ * weight > 0.  kf_valid[i] != 0: the keyframe's map point i is set and not isBad().  kf_angle = pKF->mvKeysUn[i].angle,
+ * f_angle = F.mvKeys[i].angle; with check_orientation every angle must lie in [0, 360) (the angles are not read without it and
+ * may then be NULL).  matches: nkf x nf, the keyframe feature (row within its keyframe) that frame feature i is matched to, or
+ * -1, after the rotation filter; nmatches[k] = the reference's return value.  TH_LOW = 50.
+ * Caps: nf and every keyframe's feature count <= PLI_BOW_MAX_FEATURES (else PLI_ERR_CAPACITY, nothing is truncated); nkf is
+ * bounded by device memory only.  nkf == 0 and nf == 0 are valid (no matches). */
+#define PLI_BOW_MAX_FEATURES 8192
+pli_status pli_search_by_bow(pli_ctx* ctx, int32_t nkf, const int32_t* kf_off, const uint8_t* kf_desc, const float* kf_angle,
+                             const int32_t* kf_node, const uint8_t* kf_valid, const uint8_t* f_desc, const float* f_angle,
+                             const int32_t* f_node, int32_t nf, float nnratio, int32_t check_orientation, int32_t* matches,
+                             int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

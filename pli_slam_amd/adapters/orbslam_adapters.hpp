@@ -8,6 +8,8 @@
 //   ORB_SLAM3::ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono, match12)   include/ORBmatcher.h:51,
 //                                                             src/ORBmatcher.cc:2179-2323 (projection on the host with the
 //                                                             reference's own cv::Mat expressions, window search on the GPU)
+//   ORB_SLAM3::ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches)   include/ORBmatcher.h, src/ORBmatcher.cc:269-470 (F.Nleft == -1;
+//                                                             + a batch form for Tracking::Relocalization's candidate loop)
 //
 // Frame.cc / Tracking.cc keep calling these names unchanged; INTEGRATION.md lists the edits (swap the headers).
 //
@@ -517,6 +519,27 @@ inline int match(const cv::Mat& desc1, const cv::Mat& desc2, float nnr, std::vec
   return fe->matchLines(desc1.data, desc1.rows, desc2.data, desc2.rows, nnr, matches_12);
 }
 
+namespace pli_detail {
+// A DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as one node id per feature, -1 = listed in no node.  DBoW2's
+// transform() lists every feature once, in ascending order within its node; anything else was not built by transform().
+template <class FeatVecT>
+std::vector<int32_t> featureNodes(const FeatVecT& fv, int n, const char* what) {
+  std::vector<int32_t> node((size_t)n, -1);
+  for (const auto& kv : fv) {
+    if ((uint64_t)kv.first > (uint64_t)INT32_MAX) throw std::logic_error(std::string(what) + ": node id beyond 2^31 - 1");
+    for (size_t t = 0; t < kv.second.size(); ++t) {
+      const uint64_t i = kv.second[t];
+      if (i >= (uint64_t)n) throw std::logic_error(std::string(what) + ": feature index beyond N");
+      if (t > 0 && kv.second[t - 1] >= kv.second[t])
+        throw std::logic_error(std::string(what) + ": a node's feature list is not ascending (not built by transform)");
+      if (node[i] != -1) throw std::logic_error(std::string(what) + ": a feature listed in two nodes (not built by transform)");
+      node[i] = (int32_t)kv.first;
+    }
+  }
+  return node;
+}
+}  // namespace pli_detail
+
 // The parts of ORB_SLAM3::ORBmatcher on the hot path.  Template on the tree's Frame / MapPoint so that this header does
 // not need Frame.h; inside the PLI-SLAM tree: `using ORBmatcher = ORB_SLAM3::PliORBmatcher<Frame, MapPoint>;`.
 template <class FrameT, class MapPointT>
@@ -606,6 +629,66 @@ class PliORBmatcher {
         match12.erase(raw[i]);
       }
     return nmatches;
+  }
+
+  // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches), ORBmatcher.cc:269-470, for a frame of
+  // one camera or rectified stereo (F.Nleft == -1) and a keyframe without a second camera: the node walk, TH_LOW, the ratio test,
+  // the rotation histogram and ComputeThreeMaxima run on the GPU.  KeyFrameT needs N, mDescriptors, mvKeysUn, mFeatVec,
+  // mpCamera2 and GetMapPointMatches(); FrameT N, Nleft, mDescriptors, mvKeys and mFeatVec (both FeatureVectors from transform).
+  template <class KeyFrameT>
+  int SearchByBoW(KeyFrameT* pKF, FrameT& F, std::vector<MapPointT*>& vpMapPointMatches) {
+    std::vector<std::vector<MapPointT*>> matches;
+    std::vector<int> nmatches;
+    SearchByBoW(std::vector<KeyFrameT*>(1, pKF), F, matches, nmatches);
+    vpMapPointMatches.swap(matches[0]);
+    return nmatches[0];
+  }
+
+  // (not in the reference) The same for every keyframe of vpKFs in ONE device call: what Tracking::Relocalization's loop over its
+  // candidates (Tracking.cc:4205-4230) computes, one vpMapPointMatches and one return value per keyframe.
+  template <class KeyFrameT>
+  void SearchByBoW(const std::vector<KeyFrameT*>& vpKFs, FrameT& F, std::vector<std::vector<MapPointT*>>& vvpMapPointMatches,
+                   std::vector<int>& vnmatches) {
+    if (F.Nleft != -1) throw std::logic_error("SearchByBoW: a frame of two cameras (F.Nleft != -1) is not supported");
+    const int nf = F.N, nkf = (int)vpKFs.size();
+    const std::vector<int32_t> fNode = pli_detail::featureNodes(F.mFeatVec, nf, "SearchByBoW: F.mFeatVec");
+    std::vector<float> fAngle((size_t)nf);
+    std::vector<uint8_t> fDesc((size_t)nf * 32);
+    for (int i = 0; i < nf; ++i) {
+      fAngle[i] = F.mvKeys[i].angle;
+      std::memcpy(&fDesc[(size_t)i * 32], F.mDescriptors.template ptr<uint8_t>(i), 32);
+    }
+    std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
+    std::vector<int32_t> kfOff(1, 0), kfNode;
+    std::vector<float> kfAngle;
+    std::vector<uint8_t> kfDesc, kfValid;
+    for (int k = 0; k < nkf; ++k) {
+      KeyFrameT* pKF = vpKFs[k];
+      if (pKF->mpCamera2) throw std::logic_error("SearchByBoW: a keyframe of two cameras (mpCamera2 set) is not supported");
+      const int n = pKF->N;
+      kfPoints[k] = pKF->GetMapPointMatches();
+      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, "SearchByBoW: pKF->mFeatVec");
+      kfNode.insert(kfNode.end(), node.begin(), node.end());
+      for (int i = 0; i < n; ++i) {
+        MapPointT* pMP = kfPoints[k][i];
+        kfValid.push_back(pMP && !pMP->isBad() ? 1 : 0);
+        kfAngle.push_back(pKF->mvKeysUn[i].angle);
+        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
+        kfDesc.insert(kfDesc.end(), d, d + 32);
+      }
+      kfOff.push_back(kfOff.back() + n);
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
+    if (!fe) throw std::logic_error("SearchByBoW: no extractor has run yet (no device context)");
+    std::vector<int> matches;
+    fe->searchByBoW(nkf, kfOff.data(), kfDesc.data(), kfAngle.data(), kfNode.data(), kfValid.data(), fDesc.data(), fAngle.data(),
+                    fNode.data(), nf, mfNNratio, mbCheckOrientation, matches, vnmatches);
+    vvpMapPointMatches.assign((size_t)nkf, std::vector<MapPointT*>((size_t)nf, static_cast<MapPointT*>(nullptr)));
+    for (int k = 0; k < nkf; ++k)
+      for (int i = 0; i < nf; ++i) {
+        const int j = matches[(size_t)k * nf + i];
+        if (j >= 0) vvpMapPointMatches[k][i] = kfPoints[k][j];
+      }
   }
 
  protected:

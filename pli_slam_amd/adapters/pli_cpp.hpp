@@ -127,6 +127,17 @@ class Frontend {
                                    rawIdx2 ? rawIdx2->data() : nullptr, &n));
     return n;
   }
+  // ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) ORBmatcher.cc:269-470 (F.Nleft == -1) of nkf keyframes against one frame
+  // (include/pli_frontend.h pli_search_by_bow): matches (nkf x nf) = the keyframe feature each frame feature is matched to or -1,
+  // nmatches[k] = the reference's return value for keyframe k
+  void searchByBoW(int nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle, const int32_t* kfNode,
+                   const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle, const int32_t* fNode, int nf, float nnratio,
+                   bool checkOrientation, std::vector<int>& matches, std::vector<int>& nmatches) {
+    matches.assign((size_t)nkf * nf, -1);
+    nmatches.assign(nkf, 0);
+    check(pli_search_by_bow(ctx_, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, nnratio,
+                            checkOrientation ? 1 : 0, matches.data(), nmatches.data()));
+  }
   // Frame::ComputeStereoFromRGBD(imDepth) Frame.cc:1309 (depth: CV_32F, row stride in floats)
   void computeStereoFromRGBD(const float* depth, int64_t strideFloats, std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
     mvuRight.assign(layout_.kp_cap, -1.f); mvDepth.assign(layout_.kp_cap, -1.f);

@@ -9,6 +9,7 @@
 //   k_knn2, k_ratio, k_mutual           matchNNR / match                   (LineMatcher.cpp:139-229)
 //   k_search_by_projection              ORBmatcher::SearchByProjection(F,F)(ORBmatcher.cc:2179-2323)
 //   k_search_local_map                  ORBmatcher::SearchByProjection(F,MPs)(ORBmatcher.cc:44-143)
+//   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -1224,6 +1225,195 @@ __global__ __launch_bounds__(64) void k_bow_descend(const uint8_t* __restrict__ 
     wordId[i] = nodeWord[cur];
     weight[i] = nodeWeight[cur];
     nodeId[i] = nid;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:269-470, F.Nleft == -1 branch) for a batch of
+// keyframes against one frame (Tracking::Relocalization's loop, Tracking.cc:4205-4230).
+//
+// Why the reference's sequential walk may run in parallel: a feature is listed in ONE node of its FeatureVector (DBoW2's
+// addFeature runs once per feature), and only keyframe features of that same node are compared with it.  The walk's only state
+// besides its outputs is "frame feature already matched in this call" (vpMapPointMatches[realIdxF] set), and a frame feature can
+// only be matched by a keyframe feature of its own node, so that state never crosses a node: the common nodes are independent of
+// each other, the keyframes are independent of each other, and only the keyframe features inside one node must be taken in list
+// order (ascending index).  The rotation histogram and nmatches are sums over the matches: their order does not matter.
+//
+//   k_bow_frame_sort   one workgroup: the frame's features sorted by node id (LDS bitonic sort of (node, index) pairs; the order
+//                      inside a node does not matter, the candidate key below carries the index); unlisted ones (-1) last.
+//   k_search_by_bow    one workgroup per keyframe: its valid features whose node the frame lists become (first position of the
+//                      node in the sorted frame list, index) keys, sorted in LDS: runs of one common node in ascending index.
+//                      The waves take 64-key chunks in turn and walk every run that starts in their chunk, keyframe feature after
+//                      keyframe feature; the lanes hold the node's frame candidates (looping over more than 64).  The reference's
+//                      running best / second best (strict <: ties keep the first listed, the lowest index) are the two smallest
+//                      (distance, frame index) keys.  Which keyframe feature took a frame feature lives in LDS; the 30-bin
+//                      rotation histogram takes LDS atomics, and thread 0 runs ComputeThreeMaxima (:2449-2490) before all
+//                      threads write the row with the filter applied.
+// ---------------------------------------------------------------------------
+constexpr int BOW_TH_LOW = 50, BOW_HISTO = 30;
+
+__device__ __forceinline__ int pow2_ceil(int m) {
+  int n = 1;
+  while (n < m) n <<= 1;
+  return n;
+}
+
+// ascending bitonic sort of n (a power of two) keys in LDS by the whole block; the payload (may be NULL) moves with its key
+__device__ void lds_bitonic_sort(uint32_t* key, uint16_t* val, int n) {
+  for (int k = 2; k <= n; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int l = i ^ j;
+        if (l > i) {
+          const uint32_t a = key[i], b = key[l];
+          if ((a > b) == ((i & k) == 0)) {
+            key[i] = b; key[l] = a;
+            if (val) { const uint16_t t = val[i]; val[i] = val[l]; val[l] = t; }
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+__device__ __forceinline__ int bow_lower_bound(const uint32_t* a, int lo, int hi, uint32_t v) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the histogram bin of a match (ORBmatcher.cc:405-411): rot / 30 lies in [0, 12] for angles in [0, 360), so bins 0..12 only
+__device__ __forceinline__ int bow_rot_bin(float kfAngle, float fAngle) {
+  float rot = __fsub_rn(kfAngle, fAngle);
+  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+  int bin = (int)roundf(__fmul_rn(rot, 1.0f / BOW_HISTO));
+  if (bin == BOW_HISTO) bin = 0;
+  return min(max(bin, 0), BOW_HISTO - 1);       // (the caller checks the angles; this only keeps the LDS index in range)
+}
+
+// nf <= 8192; LDS: pow2_ceil(nf) * 6 bytes
+__global__ __launch_bounds__(1024) void k_bow_frame_sort(const int* __restrict__ fNode, int nf, uint32_t* __restrict__ sNode,
+                                                         uint16_t* __restrict__ sIdx, int* __restrict__ nListed) {
+  extern __shared__ __align__(16) uint32_t bowSortLds[];
+  const int n = pow2_ceil(nf);
+  uint32_t* key = bowSortLds;
+  uint16_t* val = reinterpret_cast<uint16_t*>(key + n);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    key[i] = i < nf ? (uint32_t)fNode[i] : 0xFFFFFFFFu;          // node -1 (listed in no node) sorts last
+    val[i] = (uint16_t)i;
+  }
+  __syncthreads();
+  lds_bitonic_sort(key, val, n);
+  for (int i = threadIdx.x; i < nf; i += blockDim.x) {
+    const bool listed = key[i] != 0xFFFFFFFFu;
+    sNode[i] = key[i];
+    sIdx[i] = val[i];
+    if (listed && (i + 1 == nf || key[i + 1] == 0xFFFFFFFFu)) *nListed = i + 1;
+    if (i == 0 && !listed) *nListed = 0;
+  }
+}
+
+// grid = keyframes; LDS: 48 ints + keyCap keys (a power of two >= every keyframe's feature count) + nf shorts
+__global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
+                                                       const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
+                                                       const uint8_t* __restrict__ kfValid, const uint8_t* __restrict__ fDesc,
+                                                       const float* __restrict__ fAngle, const uint32_t* __restrict__ sNode,
+                                                       const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed, int nf,
+                                                       int keyCap, float nnratio, int checkOri, int* __restrict__ matches,
+                                                       int* __restrict__ nmatchesOut) {
+  extern __shared__ __align__(16) int bowLds[];
+  int* hist = bowLds;                                             // 30 bins (32 ints)
+  int* misc = bowLds + 32;                                        // [0] keys, [1] matches, [2..4] the bins ComputeThreeMaxima keeps
+  uint32_t* key = reinterpret_cast<uint32_t*>(bowLds + 48);
+  short* owner = reinterpret_cast<short*>(key + keyCap);          // per frame feature: the keyframe feature that took it, -1 free
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+  const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base;
+  const int nfl = *nListed;
+  for (int i = tid; i < 48; i += blockDim.x) bowLds[i] = 0;
+  for (int i = tid; i < nf; i += blockDim.x) owner[i] = -1;
+  __syncthreads();
+  // the keyframe features that take part: map point set and not bad, listed in a node the frame lists too
+  for (int j = tid; j < nk; j += blockDim.x) {
+    const int node = kfNode[base + j];
+    if (!kfValid[base + j] || node < 0) continue;
+    const int lo = bow_lower_bound(sNode, 0, nfl, (uint32_t)node);
+    if (lo < nfl && sNode[lo] == (uint32_t)node) key[atomicAdd(&misc[0], 1)] = ((uint32_t)lo << 16) | (uint32_t)j;
+  }
+  __syncthreads();
+  const int m = misc[0], n2 = pow2_ceil(m);
+  for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
+  __syncthreads();
+  lds_bitonic_sort(key, nullptr, n2);
+  int nm = 0;
+  for (int c0 = wave * 64; c0 < m; c0 += nwaves * 64) {
+    const int p = c0 + lane;
+    unsigned long long starts = __builtin_amdgcn_ballot_w64(p < m && (p == 0 || (key[p] >> 16) != (key[p - 1] >> 16)));
+    while (starts) {
+      const int s = c0 + __builtin_ctzll(starts);
+      starts &= starts - 1;
+      const uint32_t lo = key[s] >> 16;
+      const int hi = bow_lower_bound(sNode, (int)lo + 1, nfl, sNode[lo] + 1u);   // (node ids are < 2^31: no wrap)
+      for (int q = s; q < m && (key[q] >> 16) == lo; ++q) {
+        const int j = (int)(key[q] & 0xFFFFu);
+        uint64_t dk[4];
+        load_desc(kfDesc + (int64_t)(base + j) * 32, dk);
+        unsigned long long k1 = ~0ull, k2 = ~0ull;
+        for (int t = (int)lo + lane; t < hi; t += 64) {
+          const int fi = sIdx[t];
+          if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319)
+          uint64_t df[4];
+          load_desc(fDesc + (int64_t)fi * 32, df);
+          const unsigned long long kk = ((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi;
+          if (kk < k1) { k2 = k1; k1 = kk; }
+          else if (kk < k2) k2 = kk;
+        }
+        const unsigned long long m1 = wave_min_u64(k1);
+        const unsigned long long m2 = wave_min_u64(k1 == m1 ? k2 : k1);
+        if (m1 == ~0ull) continue;
+        const int bestDist1 = (int)(m1 >> 32), bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+        if (bestDist1 <= BOW_TH_LOW && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
+          const int fi = (int)(m1 & 0xFFFFFFFFull);
+          owner[fi] = (short)j;                                   // every lane stores the same value
+          ++nm;
+          if (checkOri && lane == 0) atomicAdd(&hist[bow_rot_bin(kfAngle[base + j], fAngle[fi])], 1);
+          __threadfence_block();
+        }
+      }
+    }
+  }
+  if (lane == 0 && nm) atomicAdd(&misc[1], nm);
+  __syncthreads();
+  if (tid == 0) {
+    int total = misc[1], ind1 = -1, ind2 = -1, ind3 = -1;
+    if (checkOri) {
+      int max1 = 0, max2 = 0, max3 = 0;
+      for (int i = 0; i < BOW_HISTO; ++i) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+      }
+      if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+      else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+      for (int i = 0; i < BOW_HISTO; ++i)
+        if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
+    }
+    misc[2] = ind1; misc[3] = ind2; misc[4] = ind3;
+    nmatchesOut[kf] = total;
+  }
+  __syncthreads();
+  const int ind1 = misc[2], ind2 = misc[3], ind3 = misc[4];
+  int* row = matches + (int64_t)kf * nf;
+  for (int i = tid; i < nf; i += blockDim.x) {
+    int j = owner[i];
+    if (j >= 0 && checkOri) {
+      const int b = bow_rot_bin(kfAngle[base + j], fAngle[i]);
+      if (b != ind1 && b != ind2 && b != ind3) j = -1;
+    }
+    row[i] = j;
   }
 }
 

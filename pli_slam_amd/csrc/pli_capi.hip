@@ -2696,6 +2696,79 @@ pli_status pli_bow_transform(pli_ctx* c, const pli_vocab* v, const uint8_t* desc
   return PLI_OK;
 }
 
+pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
+                             const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
+                             const int32_t* fNode, int32_t nf, float nnratio, int32_t checkOri, int32_t* matches, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || nkf < 0 || nf < 0 || (nkf > 0 && (!kfOff || !nmatches)) || (nf > 0 && (!fDesc || !fNode || (checkOri && !fAngle))) ||
+      (nkf > 0 && nf > 0 && !matches)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
+  int maxNk = 0;
+  for (int k = 0; k < nkf; ++k) {
+    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
+    const int nk = kfOff[k + 1] - kfOff[k];
+    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
+    maxNk = std::max(maxNk, nk);
+  }
+  if (nf > PLI_BOW_MAX_FEATURES) { g_err = "the frame has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = kfOff[nkf];
+  if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  for (int64_t i = 0; i < total; ++i)
+    if (kfNode[i] < -1) { g_err = "kf_node: a node id or -1"; return PLI_ERR_INVALID; }
+  for (int i = 0; i < nf; ++i)
+    if (fNode[i] < -1) { g_err = "f_node: a node id or -1"; return PLI_ERR_INVALID; }
+  if (checkOri) {
+    // (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
+    for (int64_t i = 0; i < total; ++i)
+      if (!(kfAngle[i] >= 0.f && kfAngle[i] < 360.f)) { g_err = "kf_angle outside [0, 360)"; return PLI_ERR_INVALID; }
+    for (int i = 0; i < nf; ++i)
+      if (!(fAngle[i] >= 0.f && fAngle[i] < 360.f)) { g_err = "f_angle outside [0, 360)"; return PLI_ERR_INVALID; }
+  }
+  if (nf == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t tot1 = std::max<int64_t>(total, 1);
+  const size_t bo = alignUp((size_t)(nkf + 1) * 4, 256), bkd = alignUp((size_t)tot1 * 32, 256), bka = alignUp((size_t)tot1 * 4, 256);
+  const size_t bkv = alignUp((size_t)tot1, 256), bfd = alignUp((size_t)nf * 32, 256), bf4 = alignUp((size_t)nf * 4, 256);
+  const size_t bf2 = alignUp((size_t)nf * 2, 256), bm = alignUp((size_t)nkf * nf * 4, 256), bn = alignUp((size_t)nkf * 4, 256);
+  pli_status st = ensureScratch(c, bo + bkd + 2 * bka + bkv + bfd + 3 * bf4 + bf2 + bm + bn + 256);
+  if (st != PLI_OK) return st;
+  uint8_t* p = (uint8_t*)c->scratch;
+  int* dOff = (int*)p; p += bo;
+  uint8_t* dKd = p; p += bkd;
+  float* dKa = (float*)p; p += bka;
+  int* dKn = (int*)p; p += bka;
+  uint8_t* dKv = p; p += bkv;
+  uint8_t* dFd = p; p += bfd;
+  float* dFa = (float*)p; p += bf4;
+  int* dFn = (int*)p; p += bf4;
+  uint32_t* dSn = (uint32_t*)p; p += bf4;
+  uint16_t* dSi = (uint16_t*)p; p += bf2;
+  int* dM = (int*)p; p += bm;
+  int* dN = (int*)p; p += bn;
+  int* dListed = (int*)p;
+  HIPCHK(hipMemcpyAsync(dOff, kfOff, (size_t)(nkf + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (total > 0) {
+    HIPCHK(hipMemcpyAsync(dKd, kfDesc, (size_t)total * 32, hipMemcpyHostToDevice, c->stream));
+    if (checkOri) HIPCHK(hipMemcpyAsync(dKa, kfAngle, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dKn, kfNode, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dKv, kfValid, (size_t)total, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(hipMemcpyAsync(dFd, fDesc, (size_t)nf * 32, hipMemcpyHostToDevice, c->stream));
+  if (checkOri) HIPCHK(hipMemcpyAsync(dFa, fAngle, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dFn, fNode, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+  int sortN = 1, keyCap = 1;
+  while (sortN < nf) sortN <<= 1;
+  while (keyCap < maxNk) keyCap <<= 1;
+  LAUNCH(c, "k_bow_frame_sort", k_bow_frame_sort, dim3(1), dim3(1024), (size_t)sortN * 6, dFn, nf, dSn, dSi, dListed);
+  LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16), dOff,
+         dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
+  HIPCHK(hipMemcpyAsync(matches, dM, (size_t)nkf * nf * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(nmatches, dN, (size_t)nkf * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 // ---- measurement -----------------------------------------------------------
 int64_t pli_trace_ranges(void) { return (int64_t)g_roctx.pushed.load(std::memory_order_relaxed); }
 

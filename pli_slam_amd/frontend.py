@@ -178,6 +178,33 @@ class Frontend:
         check(self.L.pli_bow_transform(self.h, vocab, ptr(d), n, levelsup, ptr(word), ptr(weight), ptr(node)))
         return word, weight, node
 
+    def search_by_bow(self, f_desc, f_angle, f_node, kfs, nnratio=0.75, check_orientation=True):
+        """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:269-470, F.Nleft == -1) of every keyframe of `kfs`
+        against one frame, in one call.  kfs: list of (desc, angle, node, valid) per keyframe; node = the FeatureVector node that
+        lists a feature (-1: none), valid = its map point is set and not bad.  Returns (matches[nkf, nf]: the keyframe feature
+        each frame feature is matched to or -1, nmatches[nkf])."""
+        fd = np.ascontiguousarray(f_desc, np.uint8).reshape(-1, 32)
+        nf = fd.shape[0]
+        fa = np.ascontiguousarray(f_angle, np.float32).reshape(nf)
+        fn = np.ascontiguousarray(f_node, np.int32).reshape(nf)
+        nkf = len(kfs)
+        off = np.zeros(nkf + 1, np.int32)
+        for k, kf in enumerate(kfs):
+            off[k + 1] = off[k] + np.asarray(kf[0]).reshape(-1, 32).shape[0]
+
+        def cat(i, dt, shape):
+            parts = [np.asarray(kf[i], dt).reshape(shape) for kf in kfs]
+            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0,) + shape[1:], dt), dt)
+        kd, ka = cat(0, np.uint8, (-1, 32)), cat(1, np.float32, (-1,))
+        kn, kv = cat(2, np.int32, (-1,)), cat(3, np.uint8, (-1,))
+        if not (len(ka) == len(kn) == len(kv) == len(kd)):
+            raise ValueError("every keyframe needs one angle, node and valid flag per descriptor")
+        matches = np.full((nkf, nf), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        check(self.L.pli_search_by_bow(self.h, nkf, ptr(off), ptr(kd), ptr(ka), ptr(kn), ptr(kv), ptr(fd), ptr(fa), ptr(fn), nf,
+                                       nnratio, int(check_orientation), ptr(matches), ptr(nmatches)))
+        return matches, nmatches
+
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""
