@@ -749,7 +749,6 @@ __global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const floa
 // order) takes the smallest key whose keypoint is still free — the reference's running minimum in visiting order —
 // with the owner table in LDS and the next query's keys already in flight.
 // ---------------------------------------------------------------------------
-constexpr int PROJ_K = 64;          // candidates kept per query; more -> that query is rescanned in phase 2
 
 __device__ __forceinline__ bool proj_window(const pli_proj_query& Q, float minX, float maxX, float minY, float maxY,
                                             float gwInv, float ghInv, bool checkBounds, int& c0, int& c1, int& r0, int& r1) {

@@ -3,6 +3,7 @@
 // There is no CPU fallback: without a gfx950 device every compute entry point
 // fails with PLI_ERR_NO_DEVICE.
 #include "kernels.hpp"
+#include "scratch_plan.hpp"
 #include <cmath>
 #include <cfloat>
 #include <algorithm>
@@ -1554,6 +1555,55 @@ pli_status ensureScratch(pli_ctx* c, size_t bytes) {
   return PLI_OK;
 }
 
+// The scratch of one call (scratch_plan.hpp): the context's grow-only buffer takes the plan's total, the plan's blocks point into it.
+pli_status commitScratch(pli_ctx* c, ScratchPlan& plan) {
+  const pli_status st = ensureScratch(c, plan.bytes());
+  if (st == PLI_OK) plan.bind(c->scratch);
+  return st;
+}
+
+// n elements from the host into a scratch block, on the context's stream (nothing when n == 0) ...
+template <typename T>
+hipError_t upload(pli_ctx* c, ScratchBlock<T> dst, const T* src, size_t n) {
+  return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream) : hipSuccess;
+}
+// ... and back (nothing for a null pointer or n == 0)
+template <typename T>
+hipError_t download(pli_ctx* c, T* dst, ScratchBlock<T> src, size_t n) {
+  return dst && n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
+// The tail of the matchers: waits for the stream and hands out the device's match counter.
+pli_status fetchCount(pli_ctx* c, const int* dcount, int32_t* nmatches) {
+  int cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, dcount, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (nmatches) *nmatches = cnt;
+  return PLI_OK;
+}
+
+// The counts block of a record (include/pli_frontend.h: pli_table_layout.off_counts), as the kernels write it.
+struct RecordCounts {
+  int32_t kp[2], kl[2];                   // keypoints / keylines of eye 0, 1
+  int32_t stereoPoints, stereoLines;
+  uint8_t linesCut[2], kpCut[2];          // truncation flags per eye: segments beyond max_lines, keypoints beyond kp_cap
+  int32_t reserved;
+};
+static_assert(sizeof(RecordCounts) == 32 && offsetof(RecordCounts, linesCut) == 24, "the int32[8] at off_counts");
+
+// ... of the context's own record, once the stream has finished
+pli_status readCounts(pli_ctx* c, RecordCounts& rc) {
+  HIPCHK(hipMemcpyAsync(&rc, c->ownTable + c->lay.off_counts, sizeof(rc), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
+// n rows (of `per` elements) of a column of the context's own record to the host; nothing for a null pointer or n <= 0
+template <typename T>
+hipError_t copyColumn(pli_ctx* c, T* dst, int64_t off, int n, int per = 1) {
+  return dst && n > 0 ? hipMemcpy(dst, c->ownTable + off, (size_t)n * per * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+}
+
 pli_status checkImage(pli_ctx* c, const uint8_t* img, int w, int h, int64_t stride) {
   if (!img || w <= 0 || h <= 0) { g_err = "empty image"; return PLI_ERR_EMPTY_IMAGE; }
   if (w != c->cfg.width || h != c->cfg.height) { g_err = "image size differs from the context's"; return PLI_ERR_INVALID; }
@@ -1806,12 +1856,12 @@ pli_status pli_batch_run_host(pli_ctx* c, int32_t nframes, const uint8_t* left, 
   HIPCHK(hipSetDevice(c->device));
   const int W = c->cfg.width, H = c->cfg.height;
   const size_t imgBytes = (size_t)W * H;
-  const size_t imgsBytes = alignUp(2 * imgBytes * nframes, 256);     // the table needs its natural alignment (odd image sizes!)
-  pli_status st = ensureScratch(c, imgsBytes + (size_t)c->lay.record_bytes * nframes);
+  ScratchPlan plan;
+  auto dl = plan.add<uint8_t>(2 * imgBytes * nframes);                  // the left images, then the right ones
+  auto dt = plan.add<uint8_t>((size_t)c->lay.record_bytes * nframes);   // (a block of its own: the table needs its natural alignment)
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* dl = (uint8_t*)c->scratch;
   uint8_t* dr = dl + imgBytes * nframes;
-  uint8_t* dt = dl + imgsBytes;
   for (int f = 0; f < nframes; ++f) {
     HIPCHK(hipMemcpy2DAsync(dl + imgBytes * f, W, left + (int64_t)f * frameStride, stride, W, H, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpy2DAsync(dr + imgBytes * f, W, right + (int64_t)f * frameStride, stride, W, H, hipMemcpyHostToDevice, c->stream));
@@ -1844,16 +1894,16 @@ pli_status pli_frame_extract(pli_ctx* c, const uint8_t* left, const uint8_t* rig
   HIPCHK(hipStreamSynchronize(c->stream));
   std::memcpy(c->hostRec.data(), c->recPinned, (size_t)c->lay.record_bytes);
   std::memcpy(record, c->recPinned, (size_t)c->lay.record_bytes);
-  const int32_t* counts = reinterpret_cast<const int32_t*>(c->hostRec.data() + c->lay.off_counts);
+  RecordCounts rc;
+  std::memcpy(&rc, c->hostRec.data() + c->lay.off_counts, sizeof(rc));
   for (int e = 0; e < 2; ++e) {
     c->orbDone[e] = c->lineDone[e] = true;
-    c->orbCount[e] = c->monoCount[e] = counts[e];
-    c->lineCount[e] = counts[2 + e];
+    c->orbCount[e] = c->monoCount[e] = rc.kp[e];
+    c->lineCount[e] = rc.kl[e];
     c->pyrHostValid[e] = false;
   }
-  const uint8_t* flags = reinterpret_cast<const uint8_t*>(counts + 6);
-  if (flags[0] || flags[1]) { g_err = "more segments pass the length cut than max_lines holds: raise pli_frontend_config.max_lines"; return PLI_ERR_CAPACITY; }
-  if (flags[2] || flags[3]) { g_err = "more keypoints than kp_cap holds"; return PLI_ERR_CAPACITY; }
+  if (rc.linesCut[0] || rc.linesCut[1]) { g_err = "more segments pass the length cut than max_lines holds: raise pli_frontend_config.max_lines"; return PLI_ERR_CAPACITY; }
+  if (rc.kpCut[0] || rc.kpCut[1]) { g_err = "more keypoints than kp_cap holds"; return PLI_ERR_CAPACITY; }
   c->frameFresh = true;
   c->pointsFresh = true;
   return PLI_OK;
@@ -1948,22 +1998,19 @@ pli_status pli_orb_extract(pli_ctx* c, int32_t eye, const uint8_t* img, int32_t 
   if ((st = stageImage(c, eye, img, w, h, stride)) != PLI_OK) return st;
   if ((st = runOrb(c, eye, 1, c->ownTable)) != PLI_OK) return st;
   const pli_table_layout& Y = c->lay;
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int N = counts[eye];
+  RecordCounts rc;
+  if ((st = readCounts(c, rc)) != PLI_OK) return st;
+  const int N = rc.kp[eye];
   c->orbDone[eye] = true;
   c->frameFresh = false;
   c->pyrHostValid[eye] = false;
   c->orbCount[eye] = N;
   c->monoCount[eye] = N;
   *n = N;
-  if (reinterpret_cast<const uint8_t*>(counts + 6)[2 + eye]) { g_err = "more keypoints than kp_cap holds"; return PLI_ERR_CAPACITY; }
+  if (rc.kpCut[eye]) { g_err = "more keypoints than kp_cap holds"; return PLI_ERR_CAPACITY; }
   if (N > cap) { g_err = "keypoint buffer too small"; return PLI_ERR_CAPACITY; }
-  if (N > 0) {
-    if (kp) HIPCHK(hipMemcpy(kp, c->ownTable + Y.off_kp[eye], (size_t)N * sizeof(pli_keypoint), hipMemcpyDeviceToHost));
-    if (desc) HIPCHK(hipMemcpy(desc, c->ownTable + Y.off_desc[eye], (size_t)N * 32, hipMemcpyDeviceToHost));
-  }
+  HIPCHK(copyColumn(c, kp, Y.off_kp[eye], N));
+  HIPCHK(copyColumn(c, desc, Y.off_desc[eye], N, 32));
   return PLI_OK;
 }
 
@@ -2002,23 +2049,20 @@ pli_status pli_line_extract(pli_ctx* c, int32_t eye, const uint8_t* img, int32_t
   if ((st = stageImage(c, eye, img, w, h, stride)) != PLI_OK) return st;
   if ((st = runLines(c, eye, 1, c->ownTable)) != PLI_OK) return st;
   const pli_table_layout& Y = c->lay;
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int N = counts[2 + eye];
+  RecordCounts rc;
+  if ((st = readCounts(c, rc)) != PLI_OK) return st;
+  const int N = rc.kl[eye];
   c->lineDone[eye] = true;
   c->frameFresh = false;
   c->lineCount[eye] = N;
   *n = N;
-  if (reinterpret_cast<const uint8_t*>(counts + 6)[eye]) {
+  if (rc.linesCut[eye]) {
     g_err = "more segments pass the length cut than max_lines holds: raise pli_frontend_config.max_lines";
     return PLI_ERR_CAPACITY;
   }
   if (N > cap) { g_err = "keyline buffer too small"; return PLI_ERR_CAPACITY; }
-  if (N > 0) {
-    if (kl) HIPCHK(hipMemcpy(kl, c->ownTable + Y.off_kl[eye], (size_t)N * sizeof(pli_keyline), hipMemcpyDeviceToHost));
-    if (desc) HIPCHK(hipMemcpy(desc, c->ownTable + Y.off_ldesc[eye], (size_t)N * 32, hipMemcpyDeviceToHost));
-  }
+  HIPCHK(copyColumn(c, kl, Y.off_kl[eye], N));
+  HIPCHK(copyColumn(c, desc, Y.off_ldesc[eye], N, 32));
   return PLI_OK;
 }
 
@@ -2100,20 +2144,17 @@ pli_status pli_stereo_match_points(pli_ctx* c, float* uright, float* depth, int3
   pli_status st = runStereoPoints(c, 1, c->ownTable);
   if (st != PLI_OK) return st;
   const pli_table_layout& Y = c->lay;
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int N = counts[0];
-  if (c->frameFresh && N > 0) {                         // the Frame's cached record follows the rig it was re-matched with
-    HIPCHK(hipMemcpy(c->hostRec.data() + Y.off_uright, c->ownTable + Y.off_uright, (size_t)N * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c->hostRec.data() + Y.off_depth, c->ownTable + Y.off_depth, (size_t)N * 4, hipMemcpyDeviceToHost));
+  RecordCounts rc;
+  if ((st = readCounts(c, rc)) != PLI_OK) return st;
+  const int N = rc.kp[0];
+  if (c->frameFresh) {                                  // the Frame's cached record follows the rig it was re-matched with
+    HIPCHK(copyColumn(c, reinterpret_cast<float*>(c->hostRec.data() + Y.off_uright), Y.off_uright, N));
+    HIPCHK(copyColumn(c, reinterpret_cast<float*>(c->hostRec.data() + Y.off_depth), Y.off_depth, N));
   }
   c->pointsFresh = c->frameFresh;
   if (N > cap) { g_err = "output buffer too small"; return PLI_ERR_CAPACITY; }
-  if (N > 0) {
-    if (uright) HIPCHK(hipMemcpy(uright, c->ownTable + Y.off_uright, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (depth) HIPCHK(hipMemcpy(depth, c->ownTable + Y.off_depth, (size_t)N * 4, hipMemcpyDeviceToHost));
-  }
+  HIPCHK(copyColumn(c, uright, Y.off_uright, N));
+  HIPCHK(copyColumn(c, depth, Y.off_depth, N));
   return PLI_OK;
 }
 
@@ -2129,15 +2170,12 @@ pli_status pli_stereo_from_depth(pli_ctx* c, const float* depth, int64_t strideF
   const pli_table_layout& Y = c->lay;
   LAUNCH(c, "k_stereo_from_depth", k_stereo_from_depth, dim3((c->hp.kpCap + 255) / 256), dim3(256), 0, c->dP, (const float*)c->scratch,
          (int64_t)W, W, H, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_uright, Y.off_depth);
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int N = counts[0];
+  RecordCounts rc;
+  if ((st = readCounts(c, rc)) != PLI_OK) return st;
+  const int N = rc.kp[0];
   if (N > cap) { g_err = "output buffer too small"; return PLI_ERR_CAPACITY; }
-  if (N > 0) {
-    if (uright) HIPCHK(hipMemcpy(uright, c->ownTable + Y.off_uright, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (depthOut) HIPCHK(hipMemcpy(depthOut, c->ownTable + Y.off_depth, (size_t)N * 4, hipMemcpyDeviceToHost));
-  }
+  HIPCHK(copyColumn(c, uright, Y.off_uright, N));
+  HIPCHK(copyColumn(c, depthOut, Y.off_depth, N));
   return PLI_OK;
 }
 
@@ -2156,54 +2194,62 @@ pli_status pli_orb_extract_lapping(pli_ctx* c, int32_t eye, const uint8_t* img, 
   if (N > cap) { g_err = "keypoint buffer too small"; return PLI_ERR_CAPACITY; }
   if (N == 0) return PLI_OK;
   const pli_table_layout& Y = c->lay;
-  const size_t bk = alignUp((size_t)N * sizeof(pli_keypoint), 256), bd = alignUp((size_t)N * 32, 256);
-  if ((st = ensureScratch(c, bk + bd + 256)) != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  pli_keypoint* sk = (pli_keypoint*)p;
-  uint8_t* sd = p + bk;
-  int* dmono = (int*)(p + bk + bd);
+  ScratchPlan plan;
+  auto sk = plan.add<pli_keypoint>(N);
+  auto sd = plan.add<uint8_t>((size_t)N * 32);
+  auto dmono = plan.add<int>(1);
+  if ((st = commitScratch(c, plan)) != PLI_OK) return st;
   pli_keypoint* tk = (pli_keypoint*)(c->ownTable + Y.off_kp[eye]);
   uint8_t* td = c->ownTable + Y.off_desc[eye];
   HIPCHK(hipMemcpyAsync(sk, tk, (size_t)N * sizeof(pli_keypoint), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(sd, td, (size_t)N * 32, hipMemcpyDeviceToDevice, c->stream));
   LAUNCH(c, "k_lapping_order", k_lapping_order, dim3(1), dim3(1024), 0, (const pli_keypoint*)sk, (const uint8_t*)sd, N, (float)lap0,
          (float)lap1, tk, td, dmono);
-  int mono = 0;
-  HIPCHK(hipMemcpyAsync(&mono, dmono, 4, hipMemcpyDeviceToHost, c->stream));
   if (kp) HIPCHK(hipMemcpyAsync(kp, tk, (size_t)N * sizeof(pli_keypoint), hipMemcpyDeviceToHost, c->stream));
   if (desc) HIPCHK(hipMemcpyAsync(desc, td, (size_t)N * 32, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *n_mono = mono;
-  c->monoCount[eye] = mono;
+  if ((st = fetchCount(c, dmono, n_mono)) != PLI_OK) return st;
+  c->monoCount[eye] = *n_mono;
   return PLI_OK;
 }
 
-// Frame::ComputeStereoFishEyeMatches (Frame.cc:1577-1618): tables on the device (kL/dL/kR/dR), results to host buffers.
-// `scratchOff`: bytes of c->scratch already in use by the caller.
-static pli_status fisheyeCore(pli_ctx* c, const pli_keypoint* kL, const uint8_t* dL, int NL, int monoL, const pli_keypoint* kR,
-                              const uint8_t* dR, int NR, int monoR, size_t scratchOff, const pli_kb8_camera* cam1,
+// Frame::ComputeStereoFishEyeMatches (Frame.cc:1577-1618): tables on the device (kL/dL/kR/dR: the context's record) or, with
+// `hostTables`, the caller's, which are staged in blocks of the same plan; results to host buffers.
+static pli_status fisheyeCore(pli_ctx* c, bool hostTables, const pli_keypoint* kL, const uint8_t* dL, int NL, int monoL,
+                              const pli_keypoint* kR, const uint8_t* dR, int NR, int monoR, const pli_kb8_camera* cam1,
                               const pli_kb8_camera* cam2, const float* Rlr, const float* tlr, int32_t* l2r, int32_t* r2l, float* depth,
                               float* p3d, int32_t* nmatches) {
   monoL = std::min(std::max(monoL, 0), NL);
   monoR = std::min(std::max(monoR, 0), NR);
   const int nq = NL - monoL, nt = NR - monoR;
-  const size_t bi = alignUp((size_t)std::max(nq, 1) * 16, 256), bl = alignUp((size_t)std::max(NL, 1) * 4, 256),
-               br = alignUp((size_t)std::max(NR, 1) * 4, 256), bp = alignUp((size_t)std::max(NL, 1) * 12, 256);
-  uint8_t* p = (uint8_t*)c->scratch + scratchOff;
-  int* kidx = (int*)p; int* kdst = kidx + 2 * std::max(nq, 1); p += bi;
-  int* dl2r = (int*)p; p += bl;
-  float* ddepth = (float*)p; p += bl;
-  int* dr2l = (int*)p; p += br;
-  float* dp3 = (float*)p; p += bp;
-  float* dRt = (float*)p; p += 128;
-  float* dsig = (float*)p; p += 128;
-  int* dcnt = (int*)p;
+  ScratchPlan plan;
+  auto kidx = plan.add<int>((size_t)nq * 2);             // k_knn2: two ints per query, the indices ...
+  auto kdst = plan.add<int>((size_t)nq * 2);             // ... and the distances
+  auto dl2r = plan.add<int>(NL);
+  auto ddepth = plan.add<float>(NL);
+  auto dr2l = plan.add<int>(NR);
+  auto dp3 = plan.add<float>((size_t)std::max(NL, 1) * 3);
+  auto dRt = plan.add<float>(12);
+  auto dsig = plan.add<float>(MAX_LEVELS);
+  auto dcnt = plan.add<int>(1);
+  auto skL = plan.add<pli_keypoint>(hostTables ? NL : 0);
+  auto sdL = plan.add<uint8_t>(hostTables ? (size_t)NL * 32 : 0);
+  auto skR = plan.add<pli_keypoint>(hostTables ? NR : 0);
+  auto sdR = plan.add<uint8_t>(hostTables ? (size_t)NR * 32 : 0);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  if (hostTables) {
+    HIPCHK(upload(c, skL, kL, NL));
+    HIPCHK(upload(c, sdL, dL, (size_t)NL * 32));
+    HIPCHK(upload(c, skR, kR, NR));
+    HIPCHK(upload(c, sdR, dR, (size_t)NR * 32));
+    kL = skL; dL = sdL; kR = skR; dR = sdR;
+  }
   float hRt[12], hsig[MAX_LEVELS];
   for (int i = 0; i < 9; ++i) hRt[i] = Rlr[i];
   for (int i = 0; i < 3; ++i) hRt[9 + i] = tlr[i];
   for (int l = 0; l < c->hp.nlevels; ++l) hsig[l] = c->hp.lv[l].scale * c->hp.lv[l].scale;      // mvLevelSigma2, ORBextractor.cc:424
-  HIPCHK(hipMemcpyAsync(dRt, hRt, sizeof(hRt), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dsig, hsig, sizeof(float) * c->hp.nlevels, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(upload(c, dRt, hRt, 12));
+  HIPCHK(upload(c, dsig, hsig, c->hp.nlevels));
   HIPCHK(hipMemsetAsync(dl2r, 0xFF, (size_t)std::max(NL, 1) * 4, c->stream));
   HIPCHK(hipMemsetAsync(dr2l, 0xFF, (size_t)std::max(NR, 1) * 4, c->stream));
   HIPCHK(hipMemsetAsync(dp3, 0, (size_t)std::max(NL, 1) * 12, c->stream));
@@ -2217,19 +2263,11 @@ static pli_status fisheyeCore(pli_ctx* c, const pli_keypoint* kL, const uint8_t*
     LAUNCH(c, "k_fisheye_triangulate", k_fisheye_triangulate, dim3((nq + 63) / 64), dim3(64), 0, kL, kR, (const int*)kidx,
            (const int*)kdst, nq, nt, monoL, monoR, c1, c2, (const float*)dRt, (const float*)dsig, dl2r, dr2l, ddepth, dp3, dcnt);
   }
-  int cnt = 0;
-  if (l2r && NL) HIPCHK(hipMemcpyAsync(l2r, dl2r, (size_t)NL * 4, hipMemcpyDeviceToHost, c->stream));
-  if (r2l && NR) HIPCHK(hipMemcpyAsync(r2l, dr2l, (size_t)NR * 4, hipMemcpyDeviceToHost, c->stream));
-  if (depth && NL) HIPCHK(hipMemcpyAsync(depth, ddepth, (size_t)NL * 4, hipMemcpyDeviceToHost, c->stream));
-  if (p3d && NL) HIPCHK(hipMemcpyAsync(p3d, dp3, (size_t)NL * 12, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&cnt, dcnt, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (nmatches) *nmatches = cnt;
-  return PLI_OK;
-}
-static size_t fisheyeScratch(int NL, int NR) {
-  return alignUp((size_t)std::max(NL, 1) * 16, 256) + 2 * alignUp((size_t)std::max(NL, 1) * 4, 256) +
-         alignUp((size_t)std::max(NR, 1) * 4, 256) + alignUp((size_t)std::max(NL, 1) * 12, 256) + 512;
+  HIPCHK(download(c, l2r, dl2r, NL));
+  HIPCHK(download(c, r2l, dr2l, NR));
+  HIPCHK(download(c, depth, ddepth, NL));
+  HIPCHK(download(c, p3d, dp3, (size_t)NL * 3));
+  return fetchCount(c, dcnt, nmatches);
 }
 
 // ... on the device tables of the last pli_orb_extract_lapping of both eyes
@@ -2241,15 +2279,13 @@ pli_status pli_stereo_fisheye(pli_ctx* c, const pli_kb8_camera* cam1, const pli_
   if (!c->orbDone[0] || !c->orbDone[1]) { g_err = "pli_orb_extract_lapping must run for both eyes first"; return PLI_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
   const pli_table_layout& Y = c->lay;
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int NL = counts[0], NR = counts[1];
-  if (NL > capL || NR > capR) { g_err = "output buffer too small"; return PLI_ERR_CAPACITY; }
-  pli_status st = ensureScratch(c, fisheyeScratch(NL, NR));
+  RecordCounts rc;
+  pli_status st = readCounts(c, rc);
   if (st != PLI_OK) return st;
-  return fisheyeCore(c, (const pli_keypoint*)(c->ownTable + Y.off_kp[0]), c->ownTable + Y.off_desc[0], NL, c->monoCount[0],
-                     (const pli_keypoint*)(c->ownTable + Y.off_kp[1]), c->ownTable + Y.off_desc[1], NR, c->monoCount[1], 0, cam1, cam2,
+  const int NL = rc.kp[0], NR = rc.kp[1];
+  if (NL > capL || NR > capR) { g_err = "output buffer too small"; return PLI_ERR_CAPACITY; }
+  return fisheyeCore(c, false, (const pli_keypoint*)(c->ownTable + Y.off_kp[0]), c->ownTable + Y.off_desc[0], NL, c->monoCount[0],
+                     (const pli_keypoint*)(c->ownTable + Y.off_kp[1]), c->ownTable + Y.off_desc[1], NR, c->monoCount[1], cam1, cam2,
                      Rlr, tlr, l2r, r2l, depth, p3d, nmatches);
 }
 
@@ -2263,22 +2299,8 @@ pli_status pli_stereo_fisheye_tables(pli_ctx* c, const pli_keypoint* kpL, const 
       (nright > 0 && (!kpR || !descR))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nmatches) *nmatches = 0;
   HIPCHK(hipSetDevice(c->device));
-  const size_t bkl = alignUp((size_t)std::max(nleft, 1) * sizeof(pli_keypoint), 256), bdl = alignUp((size_t)std::max(nleft, 1) * 32, 256);
-  const size_t bkr = alignUp((size_t)std::max(nright, 1) * sizeof(pli_keypoint), 256), bdr = alignUp((size_t)std::max(nright, 1) * 32, 256);
-  pli_status st = ensureScratch(c, bkl + bdl + bkr + bdr + fisheyeScratch(nleft, nright));
-  if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  pli_keypoint* kL = (pli_keypoint*)p; uint8_t* dL = p + bkl; pli_keypoint* kR = (pli_keypoint*)(p + bkl + bdl); uint8_t* dR = p + bkl + bdl + bkr;
-  if (nleft) {
-    HIPCHK(hipMemcpyAsync(kL, kpL, (size_t)nleft * sizeof(pli_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dL, descL, (size_t)nleft * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  if (nright) {
-    HIPCHK(hipMemcpyAsync(kR, kpR, (size_t)nright * sizeof(pli_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dR, descR, (size_t)nright * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  return fisheyeCore(c, kL, dL, nleft, monoLeft, kR, dR, nright, monoRight, bkl + bdl + bkr + bdr, cam1, cam2, Rlr, tlr, l2r, r2l, depth,
-                     p3d, nmatches);
+  return fisheyeCore(c, true, kpL, descL, nleft, monoLeft, kpR, descR, nright, monoRight, cam1, cam2, Rlr, tlr, l2r, r2l, depth, p3d,
+                     nmatches);
 }
 
 pli_status pli_stereo_match_lines(pli_ctx* c, float* disp, double* le, int32_t cap) {
@@ -2298,15 +2320,12 @@ pli_status pli_stereo_match_lines(pli_ctx* c, float* disp, double* le, int32_t c
   pli_status st = runStereoLines(c, 1, c->ownTable);
   if (st != PLI_OK) return st;
   const pli_table_layout& Y = c->lay;
-  int counts[8];
-  HIPCHK(hipMemcpyAsync(counts, c->ownTable + Y.off_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const int N = counts[2];
+  RecordCounts rc;
+  if ((st = readCounts(c, rc)) != PLI_OK) return st;
+  const int N = rc.kl[0];
   if (N > cap) { g_err = "output buffer too small"; return PLI_ERR_CAPACITY; }
-  if (N > 0) {
-    if (disp) HIPCHK(hipMemcpy(disp, c->ownTable + Y.off_disp, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (le) HIPCHK(hipMemcpy(le, c->ownTable + Y.off_le, (size_t)N * 24, hipMemcpyDeviceToHost));
-  }
+  HIPCHK(copyColumn(c, disp, Y.off_disp, N, 2));
+  HIPCHK(copyColumn(c, le, Y.off_le, N, 3));
   return PLI_OK;
 }
 
@@ -2315,16 +2334,16 @@ pli_status pli_descriptor_distance(pli_ctx* c, const uint8_t* a, const uint8_t* 
   if (!c || n < 0 || (n > 0 && (!a || !b || !dist))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (n == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
-  const size_t db = (size_t)n * 32;
-  pli_status st = ensureScratch(c, 2 * db + (size_t)n * 4);
+  ScratchPlan plan;
+  auto da = plan.add<uint8_t>((size_t)n * 32);
+  auto db = plan.add<uint8_t>((size_t)n * 32);
+  auto dd = plan.add<int>(n);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* da = (uint8_t*)c->scratch;
-  uint8_t* dbp = da + db;
-  int* dd = (int*)(dbp + db);
-  HIPCHK(hipMemcpyAsync(da, a, db, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dbp, b, db, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_distance", k_distance, dim3((n + 255) / 256), dim3(256), 0, da, dbp, n, dd);
-  HIPCHK(hipMemcpyAsync(dist, dd, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(upload(c, da, a, (size_t)n * 32));
+  HIPCHK(upload(c, db, b, (size_t)n * 32));
+  LAUNCH(c, "k_distance", k_distance, dim3((n + 255) / 256), dim3(256), 0, da, db, n, dd);
+  HIPCHK(download(c, dist, dd, n));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }
@@ -2334,18 +2353,18 @@ pli_status pli_hamming_knn2(pli_ctx* c, const uint8_t* q, int32_t nq, const uint
   if (!c || nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nq == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
-  const size_t qb = alignUp((size_t)nq * 32, 256), tb = alignUp((size_t)std::max(nt, 1) * 32, 256), ob = (size_t)nq * 8;
-  pli_status st = ensureScratch(c, qb + tb + 2 * ob);
+  ScratchPlan plan;
+  auto dq = plan.add<uint8_t>((size_t)nq * 32);
+  auto dt = plan.add<uint8_t>((size_t)nt * 32);
+  auto di = plan.add<int>((size_t)nq * 2);               // k_knn2: two ints per query, the indices ...
+  auto dd = plan.add<int>((size_t)nq * 2);               // ... and the distances
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* dq = (uint8_t*)c->scratch;
-  uint8_t* dt = dq + qb;
-  int* di = (int*)(dt + tb);
-  int* dd = di + 2 * nq;
-  HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-  if (nt > 0) HIPCHK(hipMemcpyAsync(dt, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(upload(c, dq, q, (size_t)nq * 32));
+  HIPCHK(upload(c, dt, t, (size_t)nt * 32));
   LAUNCH(c, "k_knn2", k_knn2, dim3(nq), dim3(64), 0, dq, nq, dt, nt, di, dd);
-  HIPCHK(hipMemcpyAsync(idx, di, ob, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(dist, dd, ob, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(download(c, idx, di, (size_t)nq * 2));
+  HIPCHK(download(c, dist, dd, (size_t)nq * 2));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }
@@ -2356,21 +2375,20 @@ static pli_status matchDescriptors(pli_ctx* c, const uint8_t* d1, int32_t n1, co
   if (nmatches) *nmatches = 0;
   if (n1 == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
-  const size_t b1 = alignUp((size_t)n1 * 32, 256), b2 = alignUp((size_t)std::max(n2, 1) * 32, 256);
-  const size_t k1 = alignUp((size_t)n1 * 16, 256), k2 = alignUp((size_t)std::max(n2, 1) * 16, 256);
-  const size_t mm1 = alignUp((size_t)n1 * 4, 256), mm2 = alignUp((size_t)std::max(n2, 1) * 4, 256);
-  pli_status st = ensureScratch(c, b1 + b2 + k1 + k2 + mm1 + mm2 + 256);
+  ScratchPlan plan;
+  auto dd1 = plan.add<uint8_t>((size_t)n1 * 32);
+  auto dd2 = plan.add<uint8_t>((size_t)n2 * 32);
+  auto i1 = plan.add<int>((size_t)n1 * 2);               // k_knn2: two ints per query, the indices ...
+  auto ds1 = plan.add<int>((size_t)n1 * 2);              // ... and the distances
+  auto i2 = plan.add<int>((size_t)n2 * 2);
+  auto ds2 = plan.add<int>((size_t)n2 * 2);
+  auto dm12 = plan.add<int>(n1);
+  auto dm21 = plan.add<int>(n2);
+  auto dcount = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  uint8_t* dd1 = p; p += b1;
-  uint8_t* dd2 = p; p += b2;
-  int* i1 = (int*)p; int* ds1 = i1 + 2 * n1; p += k1;
-  int* i2 = (int*)p; int* ds2 = i2 + 2 * std::max(n2, 1); p += k2;
-  int* dm12 = (int*)p; p += mm1;
-  int* dm21 = (int*)p; p += mm2;
-  int* dcount = (int*)p;
-  HIPCHK(hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, c->stream));
-  if (n2 > 0) HIPCHK(hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(upload(c, dd1, d1, (size_t)n1 * 32));
+  HIPCHK(upload(c, dd2, d2, (size_t)n2 * 32));
   HIPCHK(hipMemsetAsync(dcount, 0, 4, c->stream));
   LAUNCH(c, "k_knn2", k_knn2, dim3(n1), dim3(64), 0, dd1, n1, dd2, n2, i1, ds1);
   LAUNCH(c, "k_ratio", k_ratio, dim3((n1 + 255) / 256), dim3(256), 0, i1, ds1, n1, n2, nnr, dm12);
@@ -2379,13 +2397,9 @@ static pli_status matchDescriptors(pli_ctx* c, const uint8_t* d1, int32_t n1, co
     LAUNCH(c, "k_knn2", k_knn2, dim3(n2), dim3(64), 0, dd2, n2, dd1, n1, i2, ds2);
     LAUNCH(c, "k_ratio", k_ratio, dim3((n2 + 255) / 256), dim3(256), 0, i2, ds2, n2, n1, nnr, dm21);
   }
-  LAUNCH(c, "k_mutual", k_mutual, dim3((n1 + 255) / 256), dim3(256), 0, dm12, (lr && n2 > 0) ? dm21 : (int*)nullptr, n1, dcount);
-  int cnt = 0;
-  HIPCHK(hipMemcpyAsync(m12, dm12, (size_t)n1 * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&cnt, dcount, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (nmatches) *nmatches = cnt;
-  return PLI_OK;
+  LAUNCH(c, "k_mutual", k_mutual, dim3((n1 + 255) / 256), dim3(256), 0, dm12, (lr && n2 > 0) ? (int*)dm21 : (int*)nullptr, n1, dcount);
+  HIPCHK(download(c, m12, dm12, n1));
+  return fetchCount(c, dcount, nmatches);
 }
 
 pli_status pli_match_lines(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
@@ -2404,7 +2418,6 @@ pli_status pli_match_nnr(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_
 // Frames whose keypoints fit the LDS owner table take the two-phase form (candidates in parallel, then the ordered
 // assignment); larger ones the single-wave kernels that scan the frame per query.
 constexpr int PROJ_LDS_KEYPOINTS = 15360;
-constexpr int PROJ_CAND = 64;                 // PROJ_K of match_kernels.hip
 
 static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
                                    const pli_keypoint* kp, const uint8_t* desc, const float* uright, const uint8_t* occupied,
@@ -2417,37 +2430,31 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
   HIPCHK(hipSetDevice(c->device));
   const int nc = std::max(ncur, 1);
   const bool twoPhase = ncur <= PROJ_LDS_KEYPOINTS;
-  const size_t bq = alignUp((size_t)nq * sizeof(pli_proj_query), 256), bqd = alignUp((size_t)nq * 32, 256);
-  const size_t bk = alignUp((size_t)nc * sizeof(pli_keypoint), 256), bd = alignUp((size_t)nc * 32, 256), bu = alignUp((size_t)nc * 4, 256);
-  const size_t bo = alignUp((size_t)nc * 4, 256), bb = alignUp((size_t)nq * 4, 256), bc = alignUp((size_t)nc, 256);
   for (int i = 0; i < nq; ++i)
     if (mode == 0 && (q[i].valid & ~3)) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
-  const size_t bkeys = twoPhase ? alignUp((size_t)nq * PROJ_CAND * 8, 256) : 0, bcc = twoPhase ? alignUp((size_t)nq * 4, 256) : 0;
-  pli_status st = ensureScratch(c, bq + bqd + bk + bd + bu + bo + 2 * bb + bc + bkeys + bcc + 256);
+  ScratchPlan plan;
+  auto dq = plan.add<pli_proj_query>(nq);
+  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
+  auto dk = plan.add<pli_keypoint>(ncur);
+  auto ddsc = plan.add<uint8_t>((size_t)ncur * 32);
+  auto du = plan.add<float>(ncur);
+  auto down = plan.add<int>(ncur);
+  auto dbest = plan.add<int>(nq);
+  auto draw = plan.add<int>(nq);
+  auto docc = plan.add<uint8_t>(ncur);
+  auto dkeys = plan.add<unsigned long long>(twoPhase ? (size_t)nq * PROJ_K : 0);
+  auto dcc = plan.add<int>(twoPhase ? nq : 0);
+  auto dcnt = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  pli_proj_query* dq = (pli_proj_query*)p; p += bq;
-  uint8_t* dqd = p; p += bqd;
-  pli_keypoint* dk = (pli_keypoint*)p; p += bk;
-  uint8_t* ddsc = p; p += bd;
-  float* du = (float*)p; p += bu;
-  int* down = (int*)p; p += bo;
-  int* dbest = (int*)p; p += bb;
-  int* draw = (int*)p; p += bb;
-  uint8_t* docc = p; p += bc;
-  unsigned long long* dkeys = (unsigned long long*)p; p += bkeys;
-  int* dcc = (int*)p; p += bcc;
-  int* dcnt = (int*)p;
-  HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * sizeof(pli_proj_query), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dqd, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-  if (ncur > 0) {
-    HIPCHK(hipMemcpyAsync(dk, kp, (size_t)ncur * sizeof(pli_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(ddsc, desc, (size_t)ncur * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(du, uright, (size_t)ncur * 4, hipMemcpyHostToDevice, c->stream));
-    if (occupied) HIPCHK(hipMemcpyAsync(docc, occupied, (size_t)ncur, hipMemcpyHostToDevice, c->stream));
-  }
+  HIPCHK(upload(c, dq, q, nq));
+  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
+  HIPCHK(upload(c, dk, kp, ncur));
+  HIPCHK(upload(c, ddsc, desc, (size_t)ncur * 32));
+  HIPCHK(upload(c, du, uright, ncur));
+  if (occupied) HIPCHK(upload(c, docc, occupied, ncur));
   const uint8_t* occ = (occupied && ncur > 0) ? (const uint8_t*)docc : (const uint8_t*)nullptr;
-  int* rawOut = (mode == 0 && raw) ? draw : (int*)nullptr;
+  int* rawOut = (mode == 0 && raw) ? (int*)draw : (int*)nullptr;
   if (twoPhase) {
     // a second-best farther than 100 / nnratio can no longer reject a best of <= 100 (ORBmatcher.cc:124-126)
     int limit = 100;
@@ -2463,13 +2470,9 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
     LAUNCH(c, "k_search_local_map", k_search_local_map, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
            minY, maxY, nnratio, down, dbest, dcnt);
   }
-  int cnt = 0;
-  HIPCHK(hipMemcpyAsync(best, dbest, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  if (rawOut) HIPCHK(hipMemcpyAsync(raw, draw, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&cnt, dcnt, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (nmatches) *nmatches = cnt;
-  return PLI_OK;
+  HIPCHK(download(c, best, dbest, nq));
+  if (rawOut) HIPCHK(download(c, raw, draw, nq));
+  return fetchCount(c, dcnt, nmatches);
 }
 
 pli_status pli_search_by_projection(pli_ctx* c, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
@@ -2509,38 +2512,40 @@ pli_status pli_search_local_map_fisheye(pli_ctx* c, const pli_proj_query* qL, co
   if (nq == 0 || nL + nR == 0) return PLI_OK;
   if (nL + nR > PROJ_LDS_KEYPOINTS) { g_err = "too many keypoints for the LDS slot tables of the fisheye local-map search"; return PLI_ERR_CAPACITY; }
   HIPCHK(hipSetDevice(c->device));
-  const int ncL = std::max(nL, 1), ncR = std::max(nR, 1), ncM = std::max(ncL, ncR);
-  const size_t bq = alignUp((size_t)nq * sizeof(pli_proj_query), 256), bqd = alignUp((size_t)nq * 32, 256);
-  const size_t bkL = alignUp((size_t)ncL * sizeof(pli_keypoint), 256), bdL = alignUp((size_t)ncL * 32, 256), boL = alignUp((size_t)ncL, 256), biL = alignUp((size_t)ncL * 4, 256);
-  const size_t bkR = alignUp((size_t)ncR * sizeof(pli_keypoint), 256), bdR = alignUp((size_t)ncR * 32, 256), boR = alignUp((size_t)ncR, 256), biR = alignUp((size_t)ncR * 4, 256);
-  const size_t bu = alignUp((size_t)ncM * 4, 256), bkeys = alignUp((size_t)nq * PROJ_CAND * 8, 256), bcc = alignUp((size_t)nq * 4, 256);
-  pli_status st = ensureScratch(c, 2 * bq + bqd + bkL + bdL + boL + 2 * biL + bkR + bdR + boR + 2 * biR + bu + 2 * bkeys + 2 * bcc + 256);
+  const int ncM = std::max(std::max(nL, nR), 1);
+  ScratchPlan plan;
+  auto dqL = plan.add<pli_proj_query>(nq);
+  auto dqR = plan.add<pli_proj_query>(nq);
+  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
+  auto dkL = plan.add<pli_keypoint>(nL);
+  auto ddL = plan.add<uint8_t>((size_t)nL * 32);
+  auto doL = plan.add<uint8_t>(nL);
+  auto dl2r = plan.add<int>(nL);
+  auto dmpL = plan.add<int>(nL);
+  auto dkR = plan.add<pli_keypoint>(nR);
+  auto ddR = plan.add<uint8_t>((size_t)nR * 32);
+  auto doR = plan.add<uint8_t>(nR);
+  auto dr2l = plan.add<int>(nR);
+  auto dmpR = plan.add<int>(nR);
+  auto du = plan.add<float>(ncM);
+  auto dkeysL = plan.add<unsigned long long>((size_t)nq * PROJ_K);
+  auto dkeysR = plan.add<unsigned long long>((size_t)nq * PROJ_K);
+  auto dccL = plan.add<int>(nq);
+  auto dccR = plan.add<int>(nq);
+  auto dcnt = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  auto take = [&](size_t b) { uint8_t* r = p; p += b; return r; };
-  pli_proj_query* dqL = (pli_proj_query*)take(bq); pli_proj_query* dqR = (pli_proj_query*)take(bq);
-  uint8_t* dqd = take(bqd);
-  pli_keypoint* dkL = (pli_keypoint*)take(bkL); uint8_t* ddL = take(bdL); uint8_t* doL = take(boL); int* dl2r = (int*)take(biL); int* dmpL = (int*)take(biL);
-  pli_keypoint* dkR = (pli_keypoint*)take(bkR); uint8_t* ddR = take(bdR); uint8_t* doR = take(boR); int* dr2l = (int*)take(biR); int* dmpR = (int*)take(biR);
-  float* du = (float*)take(bu);
-  unsigned long long* dkeysL = (unsigned long long*)take(bkeys); unsigned long long* dkeysR = (unsigned long long*)take(bkeys);
-  int* dccL = (int*)take(bcc); int* dccR = (int*)take(bcc);
-  int* dcnt = (int*)p;
-  HIPCHK(hipMemcpyAsync(dqL, qL, (size_t)nq * sizeof(pli_proj_query), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dqR, qR, (size_t)nq * sizeof(pli_proj_query), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dqd, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-  if (nL > 0) {
-    HIPCHK(hipMemcpyAsync(dkL, kpL, (size_t)nL * sizeof(pli_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(ddL, descL, (size_t)nL * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dl2r, l2r, (size_t)nL * 4, hipMemcpyHostToDevice, c->stream));
-    if (occL) HIPCHK(hipMemcpyAsync(doL, occL, (size_t)nL, hipMemcpyHostToDevice, c->stream));
-  }
-  if (nR > 0) {
-    HIPCHK(hipMemcpyAsync(dkR, kpR, (size_t)nR * sizeof(pli_keypoint), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(ddR, descR, (size_t)nR * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dr2l, r2l, (size_t)nR * 4, hipMemcpyHostToDevice, c->stream));
-    if (occR) HIPCHK(hipMemcpyAsync(doR, occR, (size_t)nR, hipMemcpyHostToDevice, c->stream));
-  }
+  HIPCHK(upload(c, dqL, qL, nq));
+  HIPCHK(upload(c, dqR, qR, nq));
+  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
+  HIPCHK(upload(c, dkL, kpL, nL));
+  HIPCHK(upload(c, ddL, descL, (size_t)nL * 32));
+  HIPCHK(upload(c, dl2r, l2r, nL));
+  if (occL) HIPCHK(upload(c, doL, occL, nL));
+  HIPCHK(upload(c, dkR, kpR, nR));
+  HIPCHK(upload(c, ddR, descR, (size_t)nR * 32));
+  HIPCHK(upload(c, dr2l, r2l, nR));
+  if (occR) HIPCHK(upload(c, doR, occR, nR));
   // (the fisheye branch has no mvuRight gate: a plane of -1 switches it off in the shared candidate kernel)
   LAUNCH(c, "k_fill_f32", k_fill_f32, dim3((ncM + 255) / 256), dim3(256), 0, du, ncM, -1.0f);
   const int limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
@@ -2552,13 +2557,9 @@ pli_status pli_search_local_map_fisheye(pli_ctx* c, const pli_proj_query* qL, co
          (occL && nL > 0) ? (const uint8_t*)doL : (const uint8_t*)nullptr, dl2r, nL, dkR, ddR,
          (occR && nR > 0) ? (const uint8_t*)doR : (const uint8_t*)nullptr, dr2l, nR, du, minX, maxX, minY, maxY, nnratio, dkeysL, dccL,
          dkeysR, dccR, dmpL, dmpR, dcnt);
-  int cnt = 0;
-  if (nL > 0) HIPCHK(hipMemcpyAsync(mpL, dmpL, (size_t)nL * 4, hipMemcpyDeviceToHost, c->stream));
-  if (nR > 0) HIPCHK(hipMemcpyAsync(mpR, dmpR, (size_t)nR * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&cnt, dcnt, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (nmatches) *nmatches = cnt;
-  return PLI_OK;
+  HIPCHK(download(c, mpL, dmpL, nL));
+  HIPCHK(download(c, mpR, dmpR, nR));
+  return fetchCount(c, dcnt, nmatches);
 }
 
 // ---- frame-to-frame track matching of a batch (match_kernels.hip: k_track_*) ------------------------
@@ -2602,15 +2603,13 @@ pli_status pli_batch_track(pli_ctx* c, int32_t nframes, const void* table, const
   tp.offUr = Y.off_uright; tp.offDepth = Y.off_depth; tp.offLd0 = Y.off_ldesc[0];
   tp.trackBytes = TL.record_bytes; tp.toffCounts = TL.off_counts; tp.toffBest = TL.off_best; tp.toffLines = TL.off_lines;
   const size_t NF = (size_t)nframes;
-  const size_t bq = alignUp(NF * P.kpCap * sizeof(pli_proj_query), 256), bk = alignUp(NF * P.kpCap * 64 * 8, 256),
-               bc = alignUp(NF * P.kpCap * 4, 256), bl = alignUp(NF * std::max(P.klCap, 1) * 4, 256);
-  pli_status st = ensureScratch(c, bq + bk + bc + bl);
+  ScratchPlan plan;
+  auto dq = plan.add<pli_proj_query>(NF * P.kpCap);
+  auto dkeys = plan.add<unsigned long long>(NF * P.kpCap * PROJ_K);
+  auto dcc = plan.add<int>(NF * P.kpCap);
+  auto dl = plan.add<int>(NF * std::max(P.klCap, 1));
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  pli_proj_query* dq = (pli_proj_query*)p; p += bq;
-  unsigned long long* dkeys = (unsigned long long*)p; p += bk;
-  int* dcc = (int*)p; p += bc;
-  int* dl = (int*)p;
   const uint8_t* T = (const uint8_t*)table;
   LAUNCH(c, "k_track_queries", k_track_queries, dim3((P.kpCap + 255) / 256, nframes - 1), dim3(256), 0, c->dP, T, poses, tp, dq);
   LAUNCH(c, "k_track_candidates", k_track_candidates, dim3(P.kpCap, nframes - 1), dim3(64), 0, T, tp, dq, dkeys, dcc);
@@ -2678,20 +2677,19 @@ pli_status pli_bow_transform(pli_ctx* c, const pli_vocab* v, const uint8_t* desc
   if (!c || !v || n < 0 || (n > 0 && (!desc || !wordId || !weight || !nodeId))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (n == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
-  const size_t bd = alignUp((size_t)n * 32, 256), bw = alignUp((size_t)n * 4, 256), bf = alignUp((size_t)n * 8, 256);
-  pli_status st = ensureScratch(c, bd + 2 * bw + bf);
+  ScratchPlan plan;
+  auto dd = plan.add<uint8_t>((size_t)n * 32);
+  auto dwt = plan.add<double>(n);
+  auto dword = plan.add<int>(n);
+  auto dnode = plan.add<int>(n);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  uint8_t* dd = p; p += bd;
-  double* dwt = (double*)p; p += bf;
-  int* dword = (int*)p; p += bw;
-  int* dnode = (int*)p;
-  HIPCHK(hipMemcpyAsync(dd, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(upload(c, dd, desc, (size_t)n * 32));
   LAUNCH(c, "k_bow_descend", k_bow_descend, dim3(n), dim3(64), 0, dd, n, v->childOff, v->childList, v->desc, v->word, v->weight,
          v->L - levelsup, dword, dwt, dnode);
-  HIPCHK(hipMemcpyAsync(wordId, dword, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(weight, dwt, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(nodeId, dnode, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(download(c, wordId, dword, n));
+  HIPCHK(download(c, weight, dwt, n));
+  HIPCHK(download(c, nodeId, dnode, n));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }
@@ -2727,44 +2725,38 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   }
   if (nf == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
   HIPCHK(hipSetDevice(c->device));
-  const int64_t tot1 = std::max<int64_t>(total, 1);
-  const size_t bo = alignUp((size_t)(nkf + 1) * 4, 256), bkd = alignUp((size_t)tot1 * 32, 256), bka = alignUp((size_t)tot1 * 4, 256);
-  const size_t bkv = alignUp((size_t)tot1, 256), bfd = alignUp((size_t)nf * 32, 256), bf4 = alignUp((size_t)nf * 4, 256);
-  const size_t bf2 = alignUp((size_t)nf * 2, 256), bm = alignUp((size_t)nkf * nf * 4, 256), bn = alignUp((size_t)nkf * 4, 256);
-  pli_status st = ensureScratch(c, bo + bkd + 2 * bka + bkv + bfd + 3 * bf4 + bf2 + bm + bn + 256);
+  ScratchPlan plan;
+  auto dOff = plan.add<int>((size_t)nkf + 1);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dKa = plan.add<float>(total);
+  auto dKn = plan.add<int>(total);
+  auto dKv = plan.add<uint8_t>(total);
+  auto dFd = plan.add<uint8_t>((size_t)nf * 32);
+  auto dFa = plan.add<float>(nf);
+  auto dFn = plan.add<int>(nf);
+  auto dSn = plan.add<uint32_t>(nf);
+  auto dSi = plan.add<uint16_t>(nf);
+  auto dM = plan.add<int>((size_t)nkf * nf);
+  auto dN = plan.add<int>(nkf);
+  auto dListed = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  uint8_t* p = (uint8_t*)c->scratch;
-  int* dOff = (int*)p; p += bo;
-  uint8_t* dKd = p; p += bkd;
-  float* dKa = (float*)p; p += bka;
-  int* dKn = (int*)p; p += bka;
-  uint8_t* dKv = p; p += bkv;
-  uint8_t* dFd = p; p += bfd;
-  float* dFa = (float*)p; p += bf4;
-  int* dFn = (int*)p; p += bf4;
-  uint32_t* dSn = (uint32_t*)p; p += bf4;
-  uint16_t* dSi = (uint16_t*)p; p += bf2;
-  int* dM = (int*)p; p += bm;
-  int* dN = (int*)p; p += bn;
-  int* dListed = (int*)p;
-  HIPCHK(hipMemcpyAsync(dOff, kfOff, (size_t)(nkf + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (total > 0) {
-    HIPCHK(hipMemcpyAsync(dKd, kfDesc, (size_t)total * 32, hipMemcpyHostToDevice, c->stream));
-    if (checkOri) HIPCHK(hipMemcpyAsync(dKa, kfAngle, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dKn, kfNode, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dKv, kfValid, (size_t)total, hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(hipMemcpyAsync(dFd, fDesc, (size_t)nf * 32, hipMemcpyHostToDevice, c->stream));
-  if (checkOri) HIPCHK(hipMemcpyAsync(dFa, fAngle, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dFn, fNode, (size_t)nf * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  if (checkOri) HIPCHK(upload(c, dKa, kfAngle, total));
+  HIPCHK(upload(c, dKn, kfNode, total));
+  HIPCHK(upload(c, dKv, kfValid, total));
+  HIPCHK(upload(c, dFd, fDesc, (size_t)nf * 32));
+  if (checkOri) HIPCHK(upload(c, dFa, fAngle, nf));
+  HIPCHK(upload(c, dFn, fNode, nf));
   int sortN = 1, keyCap = 1;
   while (sortN < nf) sortN <<= 1;
   while (keyCap < maxNk) keyCap <<= 1;
   LAUNCH(c, "k_bow_frame_sort", k_bow_frame_sort, dim3(1), dim3(1024), (size_t)sortN * 6, dFn, nf, dSn, dSi, dListed);
   LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16), dOff,
          dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
-  HIPCHK(hipMemcpyAsync(matches, dM, (size_t)nkf * nf * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(nmatches, dN, (size_t)nkf * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(download(c, matches, dM, (size_t)nkf * nf));
+  HIPCHK(download(c, nmatches, dN, nkf));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }
