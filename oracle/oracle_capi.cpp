@@ -332,6 +332,44 @@ int orc_stereo_lines_tables(const pli_frontend_config* cfg, const pli_keyline* k
   if (matches) std::memcpy(matches, M.data(), M.size() * 4);
   return n1;
 }
+// Stereo point matching on caller tables and caller pyramids (levels packed one after the other, each w*h bytes, rows
+// contiguous).  computeStereoMatches indexes its row table with (int)vL unchecked, as the reference does: a table with a
+// keypoint row outside level 0, an octave outside the pyramid or a non-finite coordinate is refused (-1), never indexed.
+int orc_stereo_points_tables(const pli_frontend_config* cfg, const pli_keypoint* kl, const uint8_t* dl, int n1,
+                             const pli_keypoint* kr, const uint8_t* dr, int n2, const uint8_t* pyrL, const uint8_t* pyrR,
+                             const int* lw, const int* lh, int nlevels, float* uright, float* depth, int* bestIdx, int* sad) {
+  if (nlevels <= 0 || nlevels != cfg->orb_nlevels) return -1;
+  for (int e = 0; e < 2; ++e) {
+    const pli_keypoint* k = e ? kr : kl;
+    const int n = e ? n2 : n1;
+    for (int i = 0; i < n; ++i) {
+      if (!std::isfinite(k[i].x) || !std::isfinite(k[i].y)) return -1;
+      if (k[i].octave < 0 || k[i].octave >= nlevels) return -1;
+      if (!(k[i].y >= 0.f) || (int)k[i].y >= lh[0]) return -1;
+    }
+  }
+  std::vector<Img8> PL, PR;
+  size_t off = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    PL.push_back(wrap(pyrL + off, lw[l], lh[l], lw[l]));
+    PR.push_back(wrap(pyrR + off, lw[l], lh[l], lw[l]));
+    off += (size_t)lw[l] * lh[l];
+  }
+  // mvScaleFactor / mvInvScaleFactor as ORBextractor's constructor builds them
+  OrbExtractor ex(cfg->orb_nfeatures, cfg->orb_scale_factor, cfg->orb_nlevels, cfg->orb_ini_th_fast, cfg->orb_min_th_fast);
+  const float maxD = cfg->stereo_maxd_inf ? std::numeric_limits<float>::infinity() : cfg->bf / (cfg->bf / cfg->fx);
+  std::vector<pli_keypoint> KL(kl, kl + n1), KR(kr, kr + n2);
+  std::vector<float> U, D;
+  std::vector<int> B, S;
+  computeStereoMatches(KL, dl, KR, dr, PL, PR, ex.mvScaleFactor, ex.mvInvScaleFactor, cfg->bf, maxD, U, D, &B, &S);
+  if (n1) {
+    std::memcpy(uright, U.data(), (size_t)n1 * 4);
+    std::memcpy(depth, D.data(), (size_t)n1 * 4);
+    std::memcpy(bestIdx, B.data(), (size_t)n1 * 4);
+    std::memcpy(sad, S.data(), (size_t)n1 * 4);
+  }
+  return n1;
+}
 // Bresenham cell walk (pinned against oracle/_ref).
 int orc_line_coords(double x1, double y1, double x2, double y2, int* out, int cap) {
   std::vector<std::pair<int, int>> lc;

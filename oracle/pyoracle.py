@@ -472,6 +472,26 @@ def stereo_lines_tables(cfg, kl, dl, kr, dr, w, h):
     return disp, le, m
 
 
+def stereo_points_tables(cfg, kpL, descL, kpR, descR, pyrL, pyrR):
+    """Frame::ComputeStereoMatches on caller tables; pyrL / pyrR: one uint8 (h, w) array per pyramid level.
+    Raises ValueError for a table the oracle would have to index out of range with (see orc_stereo_points_tables)."""
+    kl, kr = np.ascontiguousarray(kpL, KEYPOINT_DT), np.ascontiguousarray(kpR, KEYPOINT_DT)
+    dl, dr = np.ascontiguousarray(descL, np.uint8), np.ascontiguousarray(descR, np.uint8)
+    assert len(pyrL) == len(pyrR) and all(a.shape == b.shape for a, b in zip(pyrL, pyrR))
+    lw = np.array([a.shape[1] for a in pyrL], np.int32)
+    lh = np.array([a.shape[0] for a in pyrL], np.int32)
+    pl = np.concatenate([_u8(a).ravel() for a in pyrL])
+    pr = np.concatenate([_u8(a).ravel() for a in pyrR])
+    n1 = kl.shape[0]
+    ur, dp = np.zeros(n1, np.float32), np.zeros(n1, np.float32)
+    bi, sad = np.zeros(n1, np.int32), np.zeros(n1, np.int32)
+    r = lib().orc_stereo_points_tables(C.byref(cfg), _p(kl), _p(dl), n1, _p(kr), _p(dr), kr.shape[0], _p(pl), _p(pr),
+                                       _p(lw), _p(lh), len(pyrL), _p(ur), _p(dp), _p(bi), _p(sad))
+    if r < 0:
+        raise ValueError("stereo_points_tables: keypoint row / octave / coordinate outside what ComputeStereoMatches may index")
+    return ur, dp, bi, sad
+
+
 def _coords(fn, x1, y1, x2, y2):
     buf = np.zeros((4096, 2), np.int32)
     n = fn(C.c_double(x1), C.c_double(y1), C.c_double(x2), C.c_double(y2), _p(buf), 4096)

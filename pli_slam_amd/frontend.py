@@ -342,6 +342,17 @@ class Frontend:
 
     def batch_run_device(self, nframes, dev_left, dev_right, stride, frame_stride, dev_table, stages=capi.RUN_ALL):
         """Asynchronous: device pointers (ints) in, device table out; sync() to wait."""
+        # The stereo stages read their inputs from the table: counts[0..3], keypoints, descriptors, keylines and line
+        # descriptors of each record, and the pyramids the context holds.  So the stereo kernels can be run on tables of
+        # the caller's making: (1) stages=RUN_ALL on the images, which leaves every pyramid level in the context; (2)
+        # overwrite those columns of the records on the device (offsets: pli_ctx_layout); (3) stages=RUN_STEREO_POINTS |
+        # RUN_STEREO_LINES with the same images -- the ingest rewrites level 0 with the same bytes, levels 1.. stay --
+        # and read uright, depth, disp, le, counts[4], counts[5] (with debug_enable: DBG_STEREO_SAD per frame).  The
+        # tables must keep what the kernels assume (they index the per-level tables by octave and turn coordinates into
+        # ints without a guard): tests/helpers_matchers.py validate_tables is the authority on that list -- counts within
+        # kp_cap / kl_cap, (n, 32) uint8 descriptors, octave in [0, nlevels), finite coordinates, keypoint rows inside the
+        # image and columns within one width of it, line end points within one image size of it.
+        # tests/test_independent_matchers_gpu.py runs this route.
         check(self.L.pli_batch_run(self.h, nframes, C.c_void_p(dev_left), C.c_void_p(dev_right), stride, frame_stride,
                                    stages, C.c_void_p(dev_table)))
 

@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+import helpers_matchers
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
@@ -302,24 +304,7 @@ def test_local_map_search_ties_and_levels(gpu):
     """Second-best / same-level ratio rule of ORBmatcher.cc:118-138 on engineered tables with many equal distances."""
     g = gpu
     fe = g.Frontend(g.capi.default_config(128, 128))
-    rng = np.random.default_rng(11)
-    ncur, nq = 700, 500
-    kp = np.zeros(ncur, g.capi.KEYPOINT_DT)
-    kp["x"] = rng.uniform(0, 640, ncur).astype(np.float32); kp["y"] = rng.uniform(0, 480, ncur).astype(np.float32)
-    kp["octave"] = rng.integers(0, 4, ncur)
-    desc = (rng.integers(0, 2, (ncur, 32)) * 255).astype(np.uint8)       # distances are multiples of 8
-    ur = np.where(rng.random(ncur) < 0.5, kp["x"] - rng.uniform(0, 30, ncur), -1).astype(np.float32)
-    q = np.zeros(nq, g.capi.PROJ_QUERY_DT)
-    src = rng.integers(0, ncur, nq)
-    q["u"] = kp["x"][src] + rng.uniform(-4, 4, nq).astype(np.float32); q["v"] = kp["y"][src] + rng.uniform(-4, 4, nq).astype(np.float32)
-    q["radius"] = rng.uniform(10, 60, nq).astype(np.float32)
-    q["ur"] = q["u"] - rng.uniform(0, 30, nq).astype(np.float32)
-    q["min_level"] = rng.integers(-1, 3, nq); q["max_level"] = q["min_level"] + rng.integers(0, 3, nq)
-    q["valid"] = rng.random(nq) < 0.9
-    qd = desc[src].copy()
-    flip = rng.random((nq, 32)) < 0.25
-    qd[flip] ^= 255
-    bounds = (0.0, 640.0, 0.0, 480.0)
+    q, qd, kp, desc, ur, bounds = helpers_matchers.local_map_ties_tables(11, 700, 500)    # (shared with test_independent_matchers*.py)
     tot = 0
     for nnratio in (0.8, 0.5, 1.0):
         n, best = fe.search_local_map(q, qd, kp, desc, ur, bounds, nnratio)
@@ -348,25 +333,7 @@ def test_projection_searches_dense_windows(gpu, ncur, nq):
     (rescanned in the ordered phase) and, at 17000 keypoints, the frame too large for the LDS owner table."""
     g = gpu
     fe = g.Frontend(g.capi.default_config(128, 128))
-    rng = np.random.default_rng(ncur)
-    kp = np.zeros(ncur, g.capi.KEYPOINT_DT)
-    kp["x"] = rng.uniform(0, 640, ncur).astype(np.float32); kp["y"] = rng.uniform(0, 480, ncur).astype(np.float32)
-    kp["octave"] = rng.integers(0, 8, ncur); kp["angle"] = rng.uniform(0, 360, ncur).astype(np.float32)
-    desc = rng.integers(0, 256, (ncur, 32), dtype=np.uint8)
-    desc[:, 8:] = desc[0, 8:]                                            # close descriptors: most candidates pass the limit
-    ur = np.where(rng.random(ncur) < 0.5, kp["x"] - rng.uniform(0, 30, ncur), -1).astype(np.float32)
-    occ = (rng.random(ncur) < 0.2).astype(np.uint8)
-    q = np.zeros(nq, g.capi.PROJ_QUERY_DT)
-    src = rng.integers(0, ncur, nq)
-    q["u"] = kp["x"][src] + rng.uniform(-4, 4, nq).astype(np.float32); q["v"] = kp["y"][src] + rng.uniform(-4, 4, nq).astype(np.float32)
-    q["radius"] = np.where(rng.random(nq) < 0.5, rng.uniform(5, 30, nq), rng.uniform(60, 200, nq)).astype(np.float32)
-    q["ur"] = q["u"] - rng.uniform(0, 30, nq).astype(np.float32)
-    q["min_level"] = rng.integers(-1, 3, nq); q["max_level"] = np.where(rng.random(nq) < 0.3, -1, q["min_level"] + rng.integers(0, 6, nq))
-    q["angle"] = (kp["angle"][src] + rng.choice([0.0, 0.0, 0.0, 90.0, 200.0], nq)).astype(np.float32) % 360
-    q["valid"] = rng.random(nq) < 0.95
-    qd = desc[src].copy()
-    qd[:, :3] ^= rng.integers(0, 256, (nq, 3), dtype=np.uint8)
-    bounds = (0.0, 640.0, 0.0, 480.0)
+    q, qd, kp, desc, ur, occ, bounds, rng = helpers_matchers.dense_window_tables(ncur, nq)    # (shared with test_independent_matchers*.py)
     for nnratio in (0.8, 0.3):
         n, best = fe.search_local_map(q, qd, kp, desc, ur, bounds, nnratio, cur_occupied=occ)
         on, obest = g.po.search_local_map(q, qd, kp, desc, ur, occ, bounds, nnratio)
@@ -454,11 +421,7 @@ def test_local_map_search_two_fisheye_cameras(gpu, nl, nr, nq):
 def test_matchers_random_and_ties(gpu):
     g = gpu
     fe = g.Frontend(g.capi.default_config(128, 128))
-    rng = np.random.default_rng(7)
-    a = rng.integers(0, 256, (333, 32), dtype=np.uint8)
-    b = rng.integers(0, 256, (257, 32), dtype=np.uint8)
-    b[100:110] = a[5]                   # exact ties at distance 0
-    b[200] = a[6]; b[201] = a[6]; b[201, 0] ^= 1
+    a, b, c, d = helpers_matchers.descriptor_tables_random_and_ties(7)    # (shared with test_independent_matchers*.py)
     assert np.array_equal(fe.descriptor_distance(a[:257], b), g.po.descriptor_distance(a[:257], b))
     idx, dist = fe.knn2(a, b)
     oidx, odist = g.po.knn2(a, b)
@@ -468,8 +431,6 @@ def test_matchers_random_and_ties(gpu):
         on, om = g.po.match_lines(a, b, nnr, True)
         assert n == on and np.array_equal(m, om)
     # low-entropy descriptors: many equal distances
-    c = (rng.integers(0, 2, (90, 32)) * 255).astype(np.uint8)
-    d = (rng.integers(0, 2, (70, 32)) * 255).astype(np.uint8)
     n, m = fe.match(c, d, 0.9)
     on, om = g.po.match_lines(c, d, 0.9, True)
     assert n == on and np.array_equal(m, om)
@@ -482,7 +443,9 @@ def test_matchers_random_and_ties(gpu):
 
 
 def test_stereo_lines_engineered_tables(gpu):
-    """matchGrid prefix-min / mutual rule and the geometric filters on hand-made line tables, through the batch record."""
+    """The oracle's table entry point for stereo lines against the batch record, on the tables the pipeline itself extracts from
+    one synthetic pair (not hand-made ones).  Constructed line tables -- the prefix-min / mutual rule, the geometric filters
+    and their edges -- go through the stereo kernels in test_independent_matchers_gpu.py."""
     g = gpu
     W, H = 752, 480
     cfg = g.capi.default_config(W, H, lsd_nfeatures=100)
