@@ -537,6 +537,31 @@ pli_status pli_search_by_bow(pli_ctx* ctx, int32_t nkf, const int32_t* kf_off, c
                              const int32_t* f_node, int32_t nf, float nnratio, int32_t check_orientation, int32_t* matches,
                              int32_t* nmatches);
 
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206, the branch
+ * without second cameras (mpCamera2 == nullptr on both sides, NLeft == -1, keypoints = mvKeysUn), for one keyframe pKF1 against
+ * nkf neighbours pKF2[k] in one call (LocalMapping::CreateNewMapPoints' loop, LocalMapping.cc:343-423; Tracking.cc:4705).
+ * kp1 / desc1 / node1 / has_mp1 / stereo1: n1 rows of pKF1 - mvKeysUn (pt, octave, angle are read), mDescriptors, the
+ * FeatureVector node that lists the feature (-1 = none, as for pli_search_by_bow), GetMapPoint(i) != nullptr (isBad() is not
+ * asked), mvuRight[i] >= 0.  Neighbour k owns rows kf_off[k] .. kf_off[k+1]-1 of the five kf_* tables; kf_off[0] = 0,
+ * non-decreasing.  F12: nkf x 9 floats, row major, the matrix Pinhole::epipolarConstrain forms from R12, t12 and the two K
+ * (Pinhole.cpp:124-127; the F12 argument of the reference's overload is not read by it); ep: nkf x 2, the epipole
+ * pKF2->mpCamera->project(R2w * Cw + t2w) (:972-977).  Both are host arithmetic (PliORBmatcher computes them); the device
+ * evaluates Pinhole.cpp:130-143 (float, the comparison dsqr < 3.84 * unc in double) and the epipole gate :1089-1097 on them.
+ * mvScaleFactors / mvLevelSigma2 are the context's (every keyframe comes from the same extractor): octaves index them and must
+ * lie in [0, orb_nlevels).  coarse = bCoarse: the epipolar expression does not decide, the other gates do.  With
+ * check_orientation (mbCheckOrientation) every angle must lie in [0, 360).
+ * matches12: nkf x n1, vMatches12 after the rotation filter (the row of pKF2[k] that feature i of pKF1 is matched to, -1 = none;
+ * vMatchedPairs is the row read in index order); nmatches[k] = the reference's return value.  A feature of pKF2 may be matched
+ * by several features of pKF1 (vbMatched2 is never set in the reference); of equally distant candidates the last listed wins.
+ * Caps: n1 and every neighbour's feature count <= PLI_BOW_MAX_FEATURES (else PLI_ERR_CAPACITY, nothing is truncated); nkf is
+ * bounded by device memory only.  nkf == 0 and empty tables are valid (no matches). */
+pli_status pli_search_for_triangulation(pli_ctx* ctx, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                        const uint8_t* has_mp1, const uint8_t* stereo1, int32_t n1, int32_t nkf,
+                                        const int32_t* kf_off, const pli_keypoint* kf_kp, const uint8_t* kf_desc,
+                                        const int32_t* kf_node, const uint8_t* kf_has_mp, const uint8_t* kf_stereo,
+                                        const float* F12, const float* ep, int32_t only_stereo, int32_t coarse,
+                                        int32_t check_orientation, int32_t* matches12, int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

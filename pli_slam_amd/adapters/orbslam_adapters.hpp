@@ -10,6 +10,9 @@
 //                                                             reference's own cv::Mat expressions, window search on the GPU)
 //   ORB_SLAM3::ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches)   include/ORBmatcher.h, src/ORBmatcher.cc:269-470 (F.Nleft == -1;
 //                                                             + a batch form for Tracking::Relocalization's candidate loop)
+//   ORB_SLAM3::ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse)   include/ORBmatcher.h,
+//                                                             src/ORBmatcher.cc:965-1206 (no second cameras; + a batch form for
+//                                                             LocalMapping::CreateNewMapPoints' neighbour loop)
 //
 // Frame.cc / Tracking.cc keep calling these names unchanged; INTEGRATION.md lists the edits (swap the headers).
 //
@@ -34,6 +37,8 @@
 #include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <string>
+#include <utility>
 #include <vector>
 #include "pli_cpp.hpp"
 #ifndef PLI_ADAPTER_NO_KEYLINE_HEADER
@@ -538,6 +543,60 @@ std::vector<int32_t> featureNodes(const FeatVecT& fv, int n, const char* what) {
   }
   return node;
 }
+
+// The host geometry of ORBmatcher::SearchForTriangulation for keyframes of one pinhole camera each: the epipole
+// ep = pKF2->mpCamera->project(R2w * Cw + t2w) (ORBmatcher.cc:972-977, Pinhole.cpp:30-33), R12 = R1w * R2w.t(),
+// t12 = -R1w * R2w.t() * t2w + t1w (:991-992) and F12 = K1.t().inv() * t12x * R12 * K2.inv() (Pinhole.cpp:124-127).
+// R*: 3 x 3 row major, K*: fx, fy, cx, cy.
+// Arithmetic convention (PARITY UNPINNED: OpenCV's own arithmetic, no OpenCV here to compare with): every cv::Mat product is one
+// CV_32F gemm by the convention DESIGN.md §9 lists - products and sum in double, `+ C` inside the same sum, one rounding to float
+// per element - and a chain A * B * C materialises (A * B) as float first; -R1w * R2w.t() is the gemm with alpha = -1; inv() of a
+// 3 x 3 CV_32F matrix is OpenCV's closed form: the determinant and the cofactors in double, each element (float)(cofactor * (1 /
+// det)), all zeros for det == 0.  project() is the reference's float expression fx * x / z + cx, left to right.
+inline void triangulationGeometry(const float R1w[9], const float t1w[3], const float Cw[3], const float K1[4], const float R2w[9],
+                                  const float t2w[3], const float K2[4], float F12[9], float ep[2]) {
+  auto gemm = [](const float* A, bool transA, double alpha, const float* B, bool transB, int cols, const float* C, float* out) {
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < cols; ++j) {
+        double d = 0.0;
+        for (int k = 0; k < 3; ++k)
+          d += (double)(transA ? A[k * 3 + i] : A[i * 3 + k]) * (double)(transB ? B[j * 3 + k] : B[k * cols + j]);
+        out[i * cols + j] = (float)(alpha * d + (C ? (double)C[i * cols + j] : 0.0));
+      }
+  };
+  auto inv3 = [](const float* S, float* out) {
+    const double det = S[0] * ((double)S[4] * S[8] - (double)S[5] * S[7]) - S[1] * ((double)S[3] * S[8] - (double)S[5] * S[6]) +
+                       S[2] * ((double)S[3] * S[7] - (double)S[4] * S[6]);
+    if (det == 0.0) { for (int i = 0; i < 9; ++i) out[i] = 0.f; return; }
+    const double d = 1.0 / det;
+    out[0] = (float)(((double)S[4] * S[8] - (double)S[5] * S[7]) * d);
+    out[1] = (float)(((double)S[2] * S[7] - (double)S[1] * S[8]) * d);
+    out[2] = (float)(((double)S[1] * S[5] - (double)S[2] * S[4]) * d);
+    out[3] = (float)(((double)S[5] * S[6] - (double)S[3] * S[8]) * d);
+    out[4] = (float)(((double)S[0] * S[8] - (double)S[2] * S[6]) * d);
+    out[5] = (float)(((double)S[2] * S[3] - (double)S[0] * S[5]) * d);
+    out[6] = (float)(((double)S[3] * S[7] - (double)S[4] * S[6]) * d);
+    out[7] = (float)(((double)S[1] * S[6] - (double)S[0] * S[7]) * d);
+    out[8] = (float)(((double)S[0] * S[4] - (double)S[1] * S[3]) * d);
+  };
+  float C2[3];
+  gemm(R2w, false, 1.0, Cw, false, 1, t2w, C2);
+  ep[0] = K2[0] * C2[0] / C2[2] + K2[2];
+  ep[1] = K2[1] * C2[1] / C2[2] + K2[3];
+  float R12[9], negR12[9], t12[3];
+  gemm(R1w, false, 1.0, R2w, true, 3, nullptr, R12);
+  gemm(R1w, false, -1.0, R2w, true, 3, nullptr, negR12);
+  gemm(negR12, false, 1.0, t2w, false, 1, t1w, t12);
+  const float t12x[9] = {0.f, -t12[2], t12[1], t12[2], 0.f, -t12[0], -t12[1], t12[0], 0.f};      // SkewSymmetricMatrix
+  const float K1t[9] = {K1[0], 0.f, 0.f, 0.f, K1[1], 0.f, K1[2], K1[3], 1.f};
+  const float K2m[9] = {K2[0], 0.f, K2[2], 0.f, K2[1], K2[3], 0.f, 0.f, 1.f};
+  float K1ti[9], K2i[9], A[9], B[9];
+  inv3(K1t, K1ti);
+  inv3(K2m, K2i);
+  gemm(K1ti, false, 1.0, t12x, false, 3, nullptr, A);
+  gemm(A, false, 1.0, R12, false, 3, nullptr, B);
+  gemm(B, false, 1.0, K2i, false, 3, nullptr, F12);
+}
 }  // namespace pli_detail
 
 // The parts of ORB_SLAM3::ORBmatcher on the hot path.  Template on the tree's Frame / MapPoint so that this header does
@@ -689,6 +748,85 @@ class PliORBmatcher {
         const int j = matches[(size_t)k * nf + i];
         if (j >= 0) vvpMapPointMatches[k][i] = kfPoints[k][j];
       }
+  }
+
+  // ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
+  // const bool bOnlyStereo, const bool bCoarse), ORBmatcher.cc:965-1206, for keyframes of one pinhole camera each (mpCamera2 ==
+  // nullptr, NLeft == -1).  F12 is ignored, as the reference ignores it: its gate is mpCamera->epipolarConstrain, which forms its
+  // own matrix from the two poses (pli_detail::triangulationGeometry here).  KeyFrameT needs N, NLeft, mDescriptors, mvKeysUn,
+  // mvuRight, mFeatVec (from transform), mpCamera (with toK()), mpCamera2, GetMapPoint(i), GetRotation(), GetTranslation() and
+  // GetCameraCenter().
+  template <class KeyFrameT>
+  int SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat /*F12*/, std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
+                             const bool bOnlyStereo, const bool bCoarse = false) {
+    std::vector<std::vector<std::pair<size_t, size_t>>> pairs;
+    std::vector<int> nmatches;
+    SearchForTriangulation(pKF1, std::vector<KeyFrameT*>(1, pKF2), pairs, nmatches, bOnlyStereo, bCoarse);
+    vMatchedPairs.swap(pairs[0]);
+    return nmatches[0];
+  }
+
+  // (not in the reference) The same for every neighbour of vpKF2 in ONE device call: what the loop of
+  // LocalMapping::CreateNewMapPoints (LocalMapping.cc:343-423) computes, one vMatchedPairs and one return value per neighbour.
+  template <class KeyFrameT>
+  void SearchForTriangulation(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2,
+                              std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, std::vector<int>& vnmatches,
+                              const bool bOnlyStereo, const bool bCoarse = false) {
+    struct Table {
+      std::vector<pli_keypoint> kp;
+      std::vector<uint8_t> desc, hasMp, stereo;
+      std::vector<int32_t> node;
+      float R[9], t[3], K[4];
+    };
+    auto gather = [](KeyFrameT* pKF, Table& T, const char* what) {
+      if (pKF->mpCamera2 || pKF->NLeft != -1)
+        throw std::logic_error("SearchForTriangulation: a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
+      const int n = pKF->N;
+      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, what);
+      T.node.insert(T.node.end(), node.begin(), node.end());
+      for (int i = 0; i < n; ++i) {
+        const cv::KeyPoint& k = pKF->mvKeysUn[i];
+        T.kp.push_back(pli_keypoint{k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave});
+        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
+        T.desc.insert(T.desc.end(), d, d + 32);
+        T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
+        T.stereo.push_back(pKF->mvuRight[i] >= 0 ? 1 : 0);
+      }
+      const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), K = pKF->mpCamera->toK();
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) T.R[i * 3 + j] = R.template at<float>(i, j);
+        T.t[i] = t.template at<float>(i);
+      }
+      T.K[0] = K.template at<float>(0, 0); T.K[1] = K.template at<float>(1, 1);
+      T.K[2] = K.template at<float>(0, 2); T.K[3] = K.template at<float>(1, 2);
+    };
+    const int nkf = (int)vpKF2.size();
+    Table T1, T2;
+    gather(pKF1, T1, "SearchForTriangulation: pKF1->mFeatVec");
+    const int n1 = pKF1->N;
+    const cv::Mat Cw = pKF1->GetCameraCenter();
+    const float cw[3] = {Cw.template at<float>(0), Cw.template at<float>(1), Cw.template at<float>(2)};
+    std::vector<int32_t> kfOff(1, 0);
+    std::vector<float> F12((size_t)nkf * 9 + 1), ep((size_t)nkf * 2 + 1);
+    for (int k = 0; k < nkf; ++k) {
+      gather(vpKF2[k], T2, "SearchForTriangulation: pKF2->mFeatVec");
+      kfOff.push_back(kfOff.back() + vpKF2[k]->N);
+      pli_detail::triangulationGeometry(T1.R, T1.t, cw, T1.K, T2.R, T2.t, T2.K, &F12[(size_t)k * 9], &ep[(size_t)k * 2]);
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
+    if (!fe) throw std::logic_error("SearchForTriangulation: no extractor has run yet (no device context)");
+    std::vector<int> matches;
+    fe->searchForTriangulation(T1.kp.data(), T1.desc.data(), T1.node.data(), T1.hasMp.data(), T1.stereo.data(), n1, nkf, kfOff.data(),
+                               T2.kp.data(), T2.desc.data(), T2.node.data(), T2.hasMp.data(), T2.stereo.data(), F12.data(), ep.data(),
+                               bOnlyStereo, bCoarse, mbCheckOrientation, matches, vnmatches);
+    vvMatchedPairs.assign((size_t)nkf, std::vector<std::pair<size_t, size_t>>());
+    for (int k = 0; k < nkf; ++k) {
+      vvMatchedPairs[k].reserve(vnmatches[k]);
+      for (int i = 0; i < n1; ++i) {                                    // vMatches12 read in index order (:1198-1203)
+        const int j = matches[(size_t)k * n1 + i];
+        if (j >= 0) vvMatchedPairs[k].push_back(std::make_pair((size_t)i, (size_t)j));
+      }
+    }
   }
 
  protected:

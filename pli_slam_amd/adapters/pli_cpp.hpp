@@ -138,6 +138,20 @@ class Frontend {
     check(pli_search_by_bow(ctx_, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, nnratio,
                             checkOrientation ? 1 : 0, matches.data(), nmatches.data()));
   }
+  // ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206 (no second
+  // cameras) of one keyframe against nkf neighbours (include/pli_frontend.h pli_search_for_triangulation): matches12 (nkf x n1) =
+  // the neighbour's feature each feature of pKF1 is matched to or -1, nmatches[k] = the reference's return value for neighbour k
+  void searchForTriangulation(const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1, const uint8_t* hasMp1,
+                              const uint8_t* stereo1, int n1, int nkf, const int32_t* kfOff, const pli_keypoint* kfKp,
+                              const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp, const uint8_t* kfStereo,
+                              const float* F12, const float* ep, bool onlyStereo, bool coarse, bool checkOrientation,
+                              std::vector<int>& matches12, std::vector<int>& nmatches) {
+    matches12.assign((size_t)nkf * n1, -1);
+    nmatches.assign(nkf, 0);
+    check(pli_search_for_triangulation(ctx_, kp1, desc1, node1, hasMp1, stereo1, n1, nkf, kfOff, kfKp, kfDesc, kfNode, kfHasMp,
+                                       kfStereo, F12, ep, onlyStereo ? 1 : 0, coarse ? 1 : 0, checkOrientation ? 1 : 0,
+                                       matches12.data(), nmatches.data()));
+  }
   // Frame::ComputeStereoFromRGBD(imDepth) Frame.cc:1309 (depth: CV_32F, row stride in floats)
   void computeStereoFromRGBD(const float* depth, int64_t strideFloats, std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
     mvuRight.assign(layout_.kp_cap, -1.f); mvDepth.assign(layout_.kp_cap, -1.f);

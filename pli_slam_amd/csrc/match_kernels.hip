@@ -10,6 +10,7 @@
 //   k_search_by_projection              ORBmatcher::SearchByProjection(F,F)(ORBmatcher.cc:2179-2323)
 //   k_search_local_map                  ORBmatcher::SearchByProjection(F,MPs)(ORBmatcher.cc:44-143)
 //   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
+//   k_tri_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -1413,6 +1414,162 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
       if (b != ind1 && b != ind2 && b != ind3) j = -1;
     }
     row[i] = j;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:965-1206, the branch
+// without second cameras: NLeft == -1, mvKeysUn) for one keyframe against a batch of neighbours (LocalMapping::CreateNewMapPoints'
+// loop, LocalMapping.cc:343-423).
+//
+// Why every feature of pKF1 may go alone: vbMatched2 (:1011) is read at :1067 and never set, so nothing a feature of pKF1 does is
+// seen by another.  For one idx1 the loop of :1060-1137 keeps a candidate when dist <= TH_LOW, dist <= bestDist and the gates pass,
+// and no gate reads bestDist: the result is, among the candidates of idx1's node that pass every gate, the smallest distance and,
+// of equal distances, the LAST listed (a node lists its features in ascending index: the largest idx2).  That is the minimum of
+// the key (distance << 32) | (0xffffffff - idx2); the order in which the candidates are visited does not matter.
+//
+//   k_tri_sort     one workgroup per neighbour: its features that may be taken (listed in a node, no map point, stereo when
+//                  bOnlyStereo) sorted by node id (LDS bitonic sort of (node, index)), the others last; also clears the
+//                  neighbour's histogram and counter.
+//   k_tri_match    grid (slices of pKF1, neighbours), one wave per idx1: a binary search finds the node's run in the neighbour's
+//                  sorted list, the lanes stride over it (Hamming distance, TH_LOW, the epipole gate :1089-1097, the epipolar
+//                  gate Pinhole.cpp:130-143 on the host's F12), a wave minimum of the key picks the winner; lane 0 writes
+//                  vMatches12[idx1] and adds to the neighbour's 30-bin rotation histogram and counter (global atomics).
+//   k_tri_finish   (mbCheckOrientation only) one workgroup per neighbour: ComputeThreeMaxima (:2449-2490) on the histogram, then
+//                  the row is filtered (a match's bin is recomputed from the two angles) and the return value corrected.
+// ---------------------------------------------------------------------------
+constexpr int TRI_STAT = 32;                                     // ints per neighbour: 30 bins, [30] the match counter
+
+// grid = neighbours; keyCap = a power of two >= every neighbour's feature count (<= 8192); LDS: keyCap * 6 bytes
+__global__ __launch_bounds__(1024) void k_tri_sort(const int* __restrict__ kfOff, const int* __restrict__ kfNode,
+                                                   const uint8_t* __restrict__ kfHasMp, const uint8_t* __restrict__ kfStereo,
+                                                   int onlyStereo, int keyCap, uint32_t* __restrict__ sNode,
+                                                   uint16_t* __restrict__ sIdx, int* __restrict__ nListed, int* __restrict__ stat) {
+  extern __shared__ __align__(16) uint32_t triSortLds[];
+  const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base;
+  const int n = min(pow2_ceil(max(nk, 1)), keyCap);
+  uint32_t* key = triSortLds;
+  uint16_t* val = reinterpret_cast<uint16_t*>(key + keyCap);
+  for (int i = threadIdx.x; i < TRI_STAT; i += blockDim.x) stat[kf * TRI_STAT + i] = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    uint32_t k = 0xFFFFFFFFu;
+    if (i < nk) {
+      const int node = kfNode[base + i];
+      if (node >= 0 && !kfHasMp[base + i] && (!onlyStereo || kfStereo[base + i])) k = (uint32_t)node;
+    }
+    key[i] = k;
+    val[i] = (uint16_t)i;
+  }
+  if (threadIdx.x == 0) nListed[kf] = 0;
+  __syncthreads();
+  lds_bitonic_sort(key, val, n);
+  for (int i = threadIdx.x; i < nk; i += blockDim.x) {
+    sNode[base + i] = key[i];
+    sIdx[base + i] = val[i];
+    if (key[i] != 0xFFFFFFFFu && (i + 1 == nk || key[i + 1] == 0xFFFFFFFFu)) nListed[kf] = i + 1;
+  }
+}
+
+// grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours)
+constexpr int TRI_PER_WAVE = 4;
+__global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
+                                                   const int* __restrict__ node1, const uint8_t* __restrict__ hasMp1,
+                                                   const uint8_t* __restrict__ stereo1, int n1, const int* __restrict__ kfOff,
+                                                   const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                   const uint8_t* __restrict__ kfStereo, const uint32_t* __restrict__ sNode,
+                                                   const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
+                                                   const float* __restrict__ F12, const float* __restrict__ ep,
+                                                   const float* __restrict__ scaleFactor, const float* __restrict__ sigma2,
+                                                   int onlyStereo, int coarse, int checkOri, int* __restrict__ matches12,
+                                                   int* __restrict__ stat) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int kf = blockIdx.y, base = kfOff[kf], nl = nListed[kf];
+  const float* F = F12 + kf * 9;
+  const float epx = ep[kf * 2], epy = ep[kf * 2 + 1];
+  const uint32_t* sn = sNode + base;
+  const uint16_t* si = sIdx + base;
+  const int first = (blockIdx.x * nwaves + wave) * TRI_PER_WAVE;
+  for (int idx1 = first; idx1 < min(first + TRI_PER_WAVE, n1); ++idx1) {
+    int best = -1;
+    const int node = node1[idx1];
+    const bool st1 = stereo1[idx1] != 0;
+    if (node >= 0 && !hasMp1[idx1] && (!onlyStereo || st1)) {       // :1036-1045 (a feature in no node is never visited)
+      const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
+      if (lo < nl && sn[lo] == (uint32_t)node) {
+        const int hi = bow_lower_bound(sn, lo + 1, nl, (uint32_t)node + 1u);
+        const pli_keypoint k1 = kp1[idx1];
+        // the epipolar line in the second image, l = x1' F12 = [a b c] (Pinhole.cpp:130-132)
+        const float a = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[0]), __fmul_rn(k1.y, F[3])), F[6]);
+        const float b = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[1]), __fmul_rn(k1.y, F[4])), F[7]);
+        const float c = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[2]), __fmul_rn(k1.y, F[5])), F[8]);
+        const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+        uint64_t d1[4];
+        load_desc(desc1 + (int64_t)idx1 * 32, d1);
+        unsigned long long k = ~0ull;
+        for (int t = lo + lane; t < hi; t += 64) {
+          const int idx2 = si[t];
+          uint64_t d2[4];
+          load_desc(kfDesc + (int64_t)(base + idx2) * 32, d2);
+          const int dist = hamming256(d1, d2);
+          if (dist > BOW_TH_LOW) continue;                         // :1080 (dist > bestDist: the key's minimum)
+          const pli_keypoint k2 = kfKp[base + idx2];
+          if (!st1 && !kfStereo[base + idx2]) {                    // :1089-1097
+            const float ex = __fsub_rn(epx, k2.x), ey = __fsub_rn(epy, k2.y);
+            if (__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)) < __fmul_rn(100.0f, scaleFactor[k2.octave])) continue;
+          }
+          if (!coarse) {                                           // Pinhole.cpp:134-143
+            const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, k2.x), __fmul_rn(b, k2.y)), c);
+            if (den == 0.0f) continue;
+            const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
+            if (!((double)dsqr < 3.84 * (double)sigma2[k2.octave])) continue;
+          }
+          const unsigned long long kk = ((unsigned long long)dist << 32) | (0xFFFFFFFFu - (unsigned)idx2);
+          k = kk < k ? kk : k;
+        }
+        k = wave_min_u64(k);
+        if (k != ~0ull) best = (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
+      }
+    }
+    if (lane == 0) {
+      matches12[(int64_t)kf * n1 + idx1] = best;
+      if (best >= 0) {
+        atomicAdd(&stat[kf * TRI_STAT + 30], 1);
+        if (checkOri) atomicAdd(&stat[kf * TRI_STAT + bow_rot_bin(kp1[idx1].angle, kfKp[base + best].angle)], 1);
+      }
+    }
+  }
+}
+
+// grid = neighbours (mbCheckOrientation only)
+__global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restrict__ kp1, int n1, const int* __restrict__ kfOff,
+                                                    const pli_keypoint* __restrict__ kfKp, int* __restrict__ matches12,
+                                                    int* __restrict__ stat) {
+  __shared__ int keep[3];
+  const int kf = blockIdx.x, base = kfOff[kf];
+  int* hist = stat + kf * TRI_STAT;
+  if (threadIdx.x == 0) {
+    int total = hist[30], ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+    for (int i = 0; i < BOW_HISTO; ++i) {
+      const int s = hist[i];
+      if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+      else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+      else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+    for (int i = 0; i < BOW_HISTO; ++i)
+      if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
+    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+    hist[30] = total;
+  }
+  __syncthreads();
+  const int ind1 = keep[0], ind2 = keep[1], ind3 = keep[2];
+  int* row = matches12 + (int64_t)kf * n1;
+  for (int i = threadIdx.x; i < n1; i += blockDim.x) {
+    const int j = row[i];
+    if (j < 0) continue;
+    const int b = bow_rot_bin(kp1[i].angle, kfKp[base + j].angle);
+    if (b != ind1 && b != ind2 && b != ind3) row[i] = -1;
   }
 }
 

@@ -2761,6 +2761,97 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   return PLI_OK;
 }
 
+pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                        const uint8_t* hasMp1, const uint8_t* stereo1, int32_t n1, int32_t nkf, const int32_t* kfOff,
+                                        const pli_keypoint* kfKp, const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
+                                        const uint8_t* kfStereo, const float* F12, const float* ep, int32_t onlyStereo, int32_t coarse,
+                                        int32_t checkOri, int32_t* matches12, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1 || !stereo1)) ||
+      (nkf > 0 && (!kfOff || !F12 || !ep || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
+  int maxNk = 0;
+  for (int k = 0; k < nkf; ++k) {
+    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
+    const int nk = kfOff[k + 1] - kfOff[k];
+    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a neighbour has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
+    maxNk = std::max(maxNk, nk);
+  }
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = kfOff[nkf];
+  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp || !kfStereo)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  // (the octaves index the level tables, the angles the rotation histogram: outside their ranges the reference reads past a vector / asserts)
+  const int nlevels = c->hp.nlevels;
+  auto tableOk = [&](const pli_keypoint* kp, const int32_t* node, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+      if (node[i] < -1) { g_err = "node: a node id or -1"; return false; }
+      if (kp[i].octave < 0 || kp[i].octave >= nlevels) { g_err = "octave outside the context's levels"; return false; }
+      if (checkOri && !(kp[i].angle >= 0.f && kp[i].angle < 360.f)) { g_err = "angle outside [0, 360)"; return false; }
+    }
+    return true;
+  };
+  if (!tableOk(kp1, node1, n1) || !tableOk(kfKp, kfNode, total)) return PLI_ERR_INVALID;
+  if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto dK1 = plan.add<pli_keypoint>(n1);
+  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
+  auto dN1 = plan.add<int>(n1);
+  auto dM1 = plan.add<uint8_t>(n1);
+  auto dS1 = plan.add<uint8_t>(n1);
+  auto dOff = plan.add<int>((size_t)nkf + 1);
+  auto dKk = plan.add<pli_keypoint>(total);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dKn = plan.add<int>(total);
+  auto dKm = plan.add<uint8_t>(total);
+  auto dKs = plan.add<uint8_t>(total);
+  auto dSn = plan.add<uint32_t>(total);
+  auto dSi = plan.add<uint16_t>(total);
+  auto dListed = plan.add<int>(nkf);
+  auto dF = plan.add<float>((size_t)nkf * 9);
+  auto dEp = plan.add<float>((size_t)nkf * 2);
+  auto dLv = plan.add<float>(2 * MAX_LEVELS);              // mvScaleFactors, then mvLevelSigma2
+  auto dStat = plan.add<int>((size_t)nkf * 32);            // per neighbour: 30 histogram bins, [30] the match counter
+  auto dM = plan.add<int>((size_t)nkf * n1);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  float hlv[2 * MAX_LEVELS] = {};
+  for (int l = 0; l < nlevels; ++l) {
+    hlv[l] = c->hp.lv[l].scale;                                          // mvScaleFactors, ORBextractor.cc:420
+    hlv[MAX_LEVELS + l] = c->hp.lv[l].scale * c->hp.lv[l].scale;         // mvLevelSigma2, ORBextractor.cc:424
+  }
+  HIPCHK(upload(c, dK1, kp1, n1));
+  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
+  HIPCHK(upload(c, dN1, node1, n1));
+  HIPCHK(upload(c, dM1, hasMp1, n1));
+  HIPCHK(upload(c, dS1, stereo1, n1));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
+  HIPCHK(upload(c, dKk, kfKp, total));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  HIPCHK(upload(c, dKn, kfNode, total));
+  HIPCHK(upload(c, dKm, kfHasMp, total));
+  HIPCHK(upload(c, dKs, kfStereo, total));
+  HIPCHK(upload(c, dF, F12, (size_t)nkf * 9));
+  HIPCHK(upload(c, dEp, ep, (size_t)nkf * 2));
+  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
+  int keyCap = 1;
+  while (keyCap < maxNk) keyCap <<= 1;
+  const int perBlock = 4 * 4;                                            // k_tri_match: 4 waves x TRI_PER_WAVE features of pKF1
+  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, dKn, dKm, dKs, onlyStereo ? 1 : 0, keyCap, dSn, dSi,
+         dListed, dStat);
+  LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1, dS1, n1, dOff, dKk,
+         dKd, dKs, dSn, dSi, dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS, onlyStereo ? 1 : 0, coarse ? 1 : 0,
+         checkOri ? 1 : 0, dM, dStat);
+  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
+  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
+  std::vector<int> hstat((size_t)nkf * 32);
+  HIPCHK(download(c, hstat.data(), dStat, (size_t)nkf * 32));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
+  return PLI_OK;
+}
+
 // ---- measurement -----------------------------------------------------------
 int64_t pli_trace_ranges(void) { return (int64_t)g_roctx.pushed.load(std::memory_order_relaxed); }
 

@@ -205,6 +205,43 @@ class Frontend:
                                        nnratio, int(check_orientation), ptr(matches), ptr(nmatches)))
         return matches, nmatches
 
+    def search_for_triangulation(self, kf1, kfs, only_stereo=False, coarse=False, check_orientation=False):
+        """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:965-1206, no
+        second cameras) of keyframe `kf1` against every neighbour of `kfs`, in one call.  kf1: (kp, desc, node, has_mp, stereo) -
+        mvKeysUn as KEYPOINT_DT rows, descriptors, the FeatureVector node that lists a feature (-1: none), map point set,
+        mvuRight >= 0; kfs: list of (kp, desc, node, has_mp, stereo, F12, ep) per neighbour, F12 = the 3 x 3 matrix of
+        Pinhole::epipolarConstrain, ep = the epipole in the neighbour's image.  Returns (matches12[nkf, n1]: the neighbour's
+        feature that feature i of kf1 is matched to or -1, nmatches[nkf])."""
+        def table(t):
+            d = np.ascontiguousarray(t[1], np.uint8).reshape(-1, 32)
+            n = d.shape[0]
+            cols = (np.ascontiguousarray(t[0], capi.KEYPOINT_DT).reshape(-1), d, np.ascontiguousarray(t[2], np.int32).reshape(-1),
+                    np.ascontiguousarray(t[3], np.uint8).reshape(-1), np.ascontiguousarray(t[4], np.uint8).reshape(-1))
+            if any(len(col) != n for col in cols):
+                raise ValueError("every feature needs one keypoint, descriptor, node, has_mp and stereo flag")
+            return cols
+        k1, d1, n1, m1, s1 = table(kf1)
+        tabs = [table(kf) for kf in kfs]
+        nkf = len(kfs)
+        off = np.zeros(nkf + 1, np.int32)
+        for k, t in enumerate(tabs):
+            off[k + 1] = off[k] + len(t[2])
+
+        def cat(i, dt, shape):
+            parts = [t[i] for t in tabs]
+            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
+        kk, kd = cat(0, capi.KEYPOINT_DT, (0,)), cat(1, np.uint8, (0, 32))
+        kn, km, ks = cat(2, np.int32, (0,)), cat(3, np.uint8, (0,)), cat(4, np.uint8, (0,))
+        f12 = np.ascontiguousarray([np.asarray(kf[5], np.float32).reshape(9) for kf in kfs], np.float32).reshape(nkf, 9)
+        ep = np.ascontiguousarray([np.asarray(kf[6], np.float32).reshape(2) for kf in kfs], np.float32).reshape(nkf, 2)
+        matches = np.full((nkf, len(n1)), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        check(self.L.pli_search_for_triangulation(self.h, ptr(k1), ptr(d1), ptr(n1), ptr(m1), ptr(s1), len(n1), nkf, ptr(off),
+                                                  ptr(kk), ptr(kd), ptr(kn), ptr(km), ptr(ks), ptr(f12), ptr(ep),
+                                                  int(only_stereo), int(coarse), int(check_orientation), ptr(matches),
+                                                  ptr(nmatches)))
+        return matches, nmatches
+
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""

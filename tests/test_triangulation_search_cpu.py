@@ -1,0 +1,550 @@
+"""ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:965-1206, the branch
+without second cameras: NLeft == -1, mvKeysUn) with Pinhole::epipolarConstrain (Pinhole.cpp:122-144), restated in Python: the
+checker of pli_search_for_triangulation (tests/test_triangulation_search_gpu.py, tests/test_cpp_triangulation_search.py).
+Here, without a device: the scalar restatement (the reference's control flow, literally) against a second, vectorised one that
+uses the closed form the kernel relies on, hand-worked known answers, the exits of the inner loop counted over the seeded
+cases, and a syntax check of the SearchForTriangulation adapters against stub KeyFrame types.
+
+Two properties of the reference's text carry the device design, and test_scalar_and_closed_form_restatements_agree is their
+test: vbMatched2 (:1011) is read at :1067 and never set, so the features of pKF1 do not see each other; and the loop keeps a
+candidate when dist <= bestDist and every gate passes while no gate reads bestDist, so the winner of idx1 is the smallest
+distance among the candidates that pass every gate and, of equal distances, the LAST listed one.
+
+F12 (the matrix epipolarConstrain forms, Pinhole.cpp:124-127) and ep (the epipole, ORBmatcher.cc:972-977) are inputs here, as
+they are for the device entry point: both are host arithmetic of the adapter.
+"""
+import bisect
+import os
+import subprocess
+import tempfile
+from collections import Counter, namedtuple
+
+import numpy as np
+
+from test_bow_search_cpu import POP8, desc_with_bits, distance, feature_vector, rot_bin, three_maxima
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TH_LOW, HISTO_LENGTH = 50, 30
+F32 = np.float32
+NLEVELS = 8
+# mvScaleFactor[i] = mvScaleFactor[i-1] * scaleFactor, mvLevelSigma2[i] = mvScaleFactor[i]^2, in float (ORBextractor.cc:417-425)
+SCALE = np.ones(NLEVELS, np.float32)
+for _l in range(1, NLEVELS):
+    SCALE[_l] = F32(SCALE[_l - 1] * F32(1.2))
+SIGMA2 = (SCALE * SCALE).astype(np.float32)
+
+# one keyframe's tables: mvKeysUn (pt.x, pt.y, octave, angle), mDescriptors, the FeatureVector node that lists a feature (-1: none),
+# GetMapPoint(i) != nullptr, mvuRight[i] >= 0
+Table = namedtuple("Table", "x y octave angle desc node has_mp stereo")
+
+
+def make_table(rows):
+    """rows: (x, y, octave, angle, desc, node[, has_mp[, stereo]]) per feature."""
+    g = lambda i, dt, dflt=None: np.array([r[i] if len(r) > i else dflt for r in rows], dt)
+    return Table(g(0, np.float32), g(1, np.float32), g(2, np.int32), g(3, np.float32),
+                 np.array([r[4] for r in rows], np.uint8).reshape(-1, 32), g(5, np.int32), g(6, np.uint8, 0), g(7, np.uint8, 0))
+
+
+def epipolar_constrain(x1, y1, x2, y2, F, unc):
+    """Pinhole.cpp:130-143 on the given F12: float left to right, den == 0 rejects, the comparison in double."""
+    x1, y1, x2, y2 = F32(x1), F32(y1), F32(x2), F32(y2)
+    a = F32(F32(F32(x1 * F[0, 0]) + F32(y1 * F[1, 0])) + F[2, 0])
+    b = F32(F32(F32(x1 * F[0, 1]) + F32(y1 * F[1, 1])) + F[2, 1])
+    c = F32(F32(F32(x1 * F[0, 2]) + F32(y1 * F[1, 2])) + F[2, 2])
+    num = F32(F32(F32(a * x2) + F32(b * y2)) + c)
+    den = F32(F32(a * a) + F32(b * b))
+    if den == 0:
+        return None
+    with np.errstate(all="ignore"):
+        dsqr = F32(F32(num * num) / den)
+    return bool(float(dsqr) < 3.84 * float(unc))
+
+
+def search_for_triangulation(t1, t2, F12, ep, only_stereo=False, coarse=False, check_orientation=False, exits=None):
+    """The reference's control flow, scalar: returns (vMatches12[n1] after the rotation filter, nmatches).  `exits` (a Counter)
+    takes one count per exit of the loops."""
+    ex = exits if exits is not None else Counter()
+    F = np.asarray(F12, np.float32).reshape(3, 3)
+    epx, epy = F32(ep[0]), F32(ep[1])
+    n1, n2 = len(t1.node), len(t2.node)
+    fv1, fv2 = feature_vector(t1.node), feature_vector(t2.node)
+    keys1, keys2 = sorted(fv1), sorted(fv2)
+    nmatches = 0
+    matched2 = [False] * n2                       # vbMatched2: tested below, never set (as in the reference)
+    matches12 = [-1] * n1
+    rot_hist = [[] for _ in range(HISTO_LENGTH)]
+    i, j = 0, 0
+    while i < len(keys1) and j < len(keys2):
+        if keys1[i] == keys2[j]:
+            ex["node_common"] += 1
+            for idx1 in fv1[keys1[i]]:
+                if t1.has_mp[idx1]:
+                    ex["has_mp1"] += 1
+                    continue
+                stereo1 = bool(t1.stereo[idx1])
+                if only_stereo and not stereo1:
+                    ex["only_stereo1"] += 1
+                    continue
+                best_dist, best_idx2 = TH_LOW, -1
+                rejected_by_line = 256            # the smallest distance the epipolar gate alone turned away
+                for idx2 in fv2[keys2[j]]:
+                    if matched2[idx2] or t2.has_mp[idx2]:
+                        ex["has_mp2"] += 1
+                        continue
+                    stereo2 = bool(t2.stereo[idx2])
+                    if only_stereo and not stereo2:
+                        ex["only_stereo2"] += 1
+                        continue
+                    dist = distance(t1.desc[idx1], t2.desc[idx2])
+                    if dist > TH_LOW or dist > best_dist:
+                        ex["th_low" if dist > TH_LOW else "worse_than_best"] += 1
+                        continue
+                    if not stereo1 and not stereo2:
+                        distex = F32(epx - t2.x[idx2])
+                        distey = F32(epy - t2.y[idx2])
+                        if F32(F32(distex * distex) + F32(distey * distey)) < F32(F32(100) * SCALE[t2.octave[idx2]]):
+                            ex["epipole"] += 1
+                            continue
+                    ok = epipolar_constrain(t1.x[idx1], t1.y[idx1], t2.x[idx2], t2.y[idx2], F, SIGMA2[t2.octave[idx2]])
+                    if ok is None:
+                        ex["den_zero"] += 1
+                    if ok or coarse:
+                        ex["replaced" if best_idx2 >= 0 else "taken"] += 1
+                        if dist == best_dist and best_idx2 >= 0:
+                            ex["tie_later_wins"] += 1
+                        best_idx2, best_dist = idx2, dist
+                    else:
+                        if ok is not None:
+                            ex["off_line"] += 1
+                        rejected_by_line = min(rejected_by_line, dist)
+                if best_idx2 >= 0:
+                    matches12[idx1] = best_idx2
+                    nmatches += 1
+                    if rejected_by_line < best_dist:
+                        ex["line_decided"] += 1   # a closer descriptor lost to the epipolar gate
+                    if check_orientation:
+                        rot_hist[rot_bin(t1.angle[idx1], t2.angle[best_idx2])].append(idx1)
+                else:
+                    ex["no_match"] += 1
+            i += 1
+            j += 1
+        elif keys1[i] < keys2[j]:
+            ex["node_only_in_1"] += 1
+            i = bisect.bisect_left(keys1, keys2[j], i)
+        else:
+            ex["node_only_in_2"] += 1
+            j = bisect.bisect_left(keys2, keys1[i], j)
+    if check_orientation:
+        keep = three_maxima([len(h) for h in rot_hist])
+        for b in range(HISTO_LENGTH):
+            if b in keep:
+                continue
+            for idx1 in rot_hist[b]:
+                matches12[idx1] = -1
+                nmatches -= 1
+                ex["rotation_filtered"] += 1
+    return np.array(matches12, np.int32), nmatches
+
+
+def search_for_triangulation_fast(t1, t2, F12, ep, only_stereo=False, coarse=False, check_orientation=False):
+    """The closed form, numpy per node: for every idx1 the minimum of (distance, -position) over the candidates that pass every
+    gate.  float32 arrays: every numpy operation rounds once, like the scalar statement."""
+    F = np.asarray(F12, np.float32).reshape(3, 3)
+    epx, epy = F32(ep[0]), F32(ep[1])
+    n1 = len(t1.node)
+    matches = np.full(n1, -1, np.int32)
+    fv1, fv2 = feature_vector(t1.node), feature_vector(t2.node)
+    d1all, d2all = np.asarray(t1.desc, np.uint8), np.asarray(t2.desc, np.uint8)
+    with np.errstate(all="ignore"):
+        for node in sorted(set(fv1) & set(fv2)):
+            i1 = np.array([i for i in fv1[node] if not t1.has_mp[i] and (not only_stereo or t1.stereo[i])], np.int64)
+            i2 = np.array([i for i in fv2[node] if not t2.has_mp[i] and (not only_stereo or t2.stereo[i])], np.int64)
+            if len(i1) == 0 or len(i2) == 0:
+                continue
+            D = POP8[np.bitwise_xor(d1all[i1][:, None, :], d2all[i2][None, :, :])].sum(-1, dtype=np.int64)
+            ok = D <= TH_LOW
+            ex, ey = epx - t2.x[i2], epy - t2.y[i2]
+            near = (ex * ex + ey * ey) < (F32(100) * SCALE[t2.octave[i2]])
+            mono = (t1.stereo[i1] == 0)[:, None] & (t2.stereo[i2] == 0)[None, :]
+            ok &= ~(mono & near[None, :])
+            if not coarse:
+                x1, y1 = t1.x[i1], t1.y[i1]
+                a = ((x1 * F[0, 0] + y1 * F[1, 0]) + F[2, 0])[:, None]
+                b = ((x1 * F[0, 1] + y1 * F[1, 1]) + F[2, 1])[:, None]
+                c = ((x1 * F[0, 2] + y1 * F[1, 2]) + F[2, 2])[:, None]
+                num = (a * t2.x[i2][None, :] + b * t2.y[i2][None, :]) + c
+                den = a * a + b * b
+                dsqr = (num * num) / den
+                assert dsqr.dtype == np.float32
+                ok &= (den != 0) & (dsqr.astype(np.float64) < 3.84 * SIGMA2[t2.octave[i2]].astype(np.float64)[None, :])
+            pos = np.arange(len(i2), dtype=np.int64)
+            key = np.where(ok, D * (1 << 20) + ((1 << 20) - 1 - pos)[None, :], 1 << 40)
+            best = key.min(axis=1)
+            hit = best < (1 << 40)
+            matches[i1[hit]] = i2[(1 << 20) - 1 - (best[hit] & ((1 << 20) - 1))]
+    nmatches = int((matches >= 0).sum())
+    if check_orientation:
+        hist = [[] for _ in range(HISTO_LENGTH)]
+        for idx1 in np.nonzero(matches >= 0)[0]:
+            hist[rot_bin(t1.angle[idx1], t2.angle[matches[idx1]])].append(int(idx1))
+        keep = three_maxima([len(h) for h in hist])
+        for b in range(HISTO_LENGTH):
+            if b not in keep:
+                matches[hist[b]] = -1
+                nmatches -= len(hist[b])
+    return matches, nmatches
+
+
+# ---- constructed two-view geometry ----------------------------------------------------------------------------------------
+
+K_EUROC = (458.654, 457.296, 367.215, 248.375)          # fx, fy, cx, cy (752 x 480)
+
+
+def rot_xyz(rx, ry, rz):
+    cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def geometry_np(R1w, t1w, R2w, t2w, K1=K_EUROC, K2=K_EUROC):
+    """F12 = K1^-T [t12]x R12 K2^-1 and the epipole of camera 1 in image 2, in double, rounded to float at the end (a helper of
+    the tests: any F12 / ep serve for parity; these make the true pairs lie on their lines)."""
+    R12 = R1w @ R2w.T
+    t12 = -R1w @ R2w.T @ t2w + t1w
+    tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+    Km = lambda k: np.array([[k[0], 0, k[2]], [0, k[1], k[3]], [0, 0, 1.0]])
+    F = np.linalg.inv(Km(K1).T) @ tx @ R12 @ np.linalg.inv(Km(K2))
+    C2 = R2w @ (-R1w.T @ t1w) + t2w
+    with np.errstate(all="ignore"):
+        ep = np.array([K2[0] * C2[0] / C2[2] + K2[2], K2[1] * C2[1] / C2[2] + K2[3]])
+    return F.astype(np.float32), ep.astype(np.float32)
+
+
+def flip_bits(rng, d, n):
+    d = d.copy()
+    for b in rng.choice(256, n, replace=False):
+        d[b >> 3] ^= np.uint8(1 << (b & 7))
+    return d
+
+
+def two_view_case(rng, nkf, npts, nnodes=12, K=K_EUROC, poses=None):
+    """One keyframe and nkf neighbours that see the same random 3D points.  Returns (t1, [(t2, F12, ep, truth)]): truth[idx1] =
+    the neighbour's feature that shows the same point, or -1.  Built so that the restatement ALONE takes every exit of its loops:
+      * decoys in the neighbour: the keyframe's descriptor exactly (distance 0, closer than the true feature), same node, placed
+        away from the epipolar line - the epipolar gate, not the distance, must decide;
+      * twins: the true feature twice (equal distance, both on the line) - the later one wins;
+      * features right at the epipole (mono on both sides: gated; stereo: not gated), the neighbours move forward so that the
+        epipole lies in the image;
+      * corners the keyframe holds twice: both take the same feature of the neighbour (vbMatched2 is never set);
+      * map points on either side, mono / stereo mixed, nodes changed, dropped (-1) or listed by one side only, points seen by
+        one side only;
+      * neighbour 3 (when present) gets F12 = 0: den == 0 for every pair.
+    `poses` (a list) takes (R1w, t1w, R2w, t2w) per neighbour."""
+    fx, fy, cx, cy = K
+    P = np.stack([rng.uniform(-4, 4, npts), rng.uniform(-2.5, 2.5, npts), rng.uniform(3, 12, npts)], 1)
+    base_desc = rng.integers(0, 256, (npts, 32), dtype=np.uint8)
+    base_node = rng.integers(0, nnodes, npts)
+    base_angle = rng.uniform(0, 360, npts)
+
+    def project(R, t, X):
+        Xc = X @ R.T + t
+        return fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy
+
+    R1w, t1w = rot_xyz(*rng.normal(0, 0.02, 3)), rng.normal(0, 0.05, 3)
+    u1, v1 = project(R1w, t1w, P)
+    rows1, point1 = [], []
+    for p in range(npts):
+        if rng.random() < 0.1:
+            continue                                                    # not seen by the keyframe
+        r = rng.random()                                                # (even ids past nnodes: nodes only the keyframe lists)
+        node = int(base_node[p]) if r > 0.09 else (-1 if r < 0.05 else nnodes + 2 * int(rng.integers(0, 5)))
+        rows1.append((u1[p] + rng.normal(0, 0.2), v1[p] + rng.normal(0, 0.2), int(rng.integers(0, NLEVELS)), base_angle[p],
+                      flip_bits(rng, base_desc[p], int(rng.integers(0, 8))), node, int(rng.random() < 0.15), int(rng.random() < 0.5)))
+        point1.append(p)
+        if rng.random() < 0.08:                                         # the same corner again on another level
+            rows1.append(rows1[-1][:2] + (int(rng.integers(0, NLEVELS)),) + rows1[-1][3:6] + (0, rows1[-1][7]))
+            point1.append(p)
+    t1 = make_table(rows1)
+    idx1_of = {p: i for i, p in enumerate(point1)}
+    out = []
+    for k in range(nkf):
+        R2w = rot_xyz(*rng.normal(0, 0.03, 3))
+        t2w = np.array([rng.normal(0, 0.15), rng.normal(0, 0.05), -rng.uniform(0.3, 0.8)])       # the camera moves forward
+        F12, ep = geometry_np(R1w, t1w, R2w, t2w, K, K)
+        u2, v2 = project(R2w, t2w, P)
+        turn = rng.uniform(0, 360)
+        rows2, point2 = [], []
+        for p in range(npts):
+            if rng.random() < 0.1:
+                continue
+            r = rng.random()
+            # (odd ids past nnodes: nodes only the neighbour lists)
+            node = int(base_node[p]) if r > 0.1 else (-1 if r < 0.03 else int(rng.integers(0, nnodes)) if r < 0.07 else
+                                                     nnodes + 1 + 2 * int(rng.integers(0, 5)))
+            ang = (base_angle[p] + turn + rng.normal(0, 6)) % 360 if rng.random() < 0.85 else rng.uniform(0, 360)
+            d2 = flip_bits(rng, base_desc[p], int(rng.integers(0, 8)))
+            row = (u2[p] + rng.normal(0, 0.2), v2[p] + rng.normal(0, 0.2), int(rng.integers(0, NLEVELS)), ang, d2, node,
+                   int(rng.random() < 0.15), int(rng.random() < 0.5))
+            rows2.append(row)
+            point2.append(p)
+            i1 = idx1_of.get(p)
+            r = rng.random()
+            if i1 is not None and r < 0.15:           # decoy: the keyframe's own descriptor, off the line
+                rows2.append((rng.uniform(0, 752), rng.uniform(0, 480), int(rng.integers(0, NLEVELS)), ang, t1.desc[i1].copy(),
+                              node, 0, row[7]))
+                point2.append(-1)
+            elif r < 0.25:                            # twin: the same feature again
+                rows2.append(row[:6] + (0, row[7]))
+                point2.append(p)
+            elif i1 is not None and r < 0.32:         # a copy at the epipole (gated when both sides are mono)
+                rows2.append((float(ep[0]) + rng.normal(0, 2), float(ep[1]) + rng.normal(0, 2), 0, ang, t1.desc[i1].copy(), node, 0,
+                              int(rng.random() < 0.3)))
+                point2.append(-1)
+        order = rng.permutation(len(rows2))
+        t2 = make_table([rows2[i] for i in order])
+        ang = t2.angle.copy()
+        ang[ang >= 360.0] = 0.0
+        t2 = t2._replace(angle=ang)
+        truth = np.full(len(t1.node), -1, np.int32)
+        for new, old in enumerate(order):               # (of twins the later index stays: the one the reference keeps)
+            p = point2[old]
+            if p >= 0:
+                truth[[i for i, q in enumerate(point1) if q == p]] = new
+        if k == 3:
+            F12 = np.zeros((3, 3), np.float32)
+        if poses is not None:
+            poses.append((R1w, t1w, R2w, t2w))
+        out.append((t2, F12, ep, truth))
+    return t1, out
+
+
+EXITS = ("node_common", "node_only_in_1", "node_only_in_2", "has_mp1", "only_stereo1", "has_mp2", "only_stereo2", "th_low",
+         "worse_than_best", "epipole", "den_zero", "off_line", "taken", "replaced", "tie_later_wins", "no_match", "line_decided",
+         "rotation_filtered")
+SETTINGS = [(os_, co, ori) for os_ in (False, True) for co in (False, True) for ori in (False, True)]
+
+
+def test_scalar_and_closed_form_restatements_agree_and_every_exit_is_taken():
+    rng = np.random.default_rng(11)
+    total = Counter()
+    for it in range(6):
+        t1, nbrs = two_view_case(rng, 4, int(rng.integers(40, 160)), nnodes=int(rng.choice([1, 4, 12])))
+        for only_stereo, coarse, ori in SETTINGS:
+            batch_line_decided = 0
+            for k, (t2, F12, ep, truth) in enumerate(nbrs):
+                ex = Counter()
+                m1, n1 = search_for_triangulation(t1, t2, F12, ep, only_stereo, coarse, ori, ex)
+                m2, n2 = search_for_triangulation_fast(t1, t2, F12, ep, only_stereo, coarse, ori)
+                assert np.array_equal(m1, m2) and n1 == n2, (it, k, only_stereo, coarse, ori)
+                assert n1 == int((m1 >= 0).sum())
+                batch_line_decided += ex["line_decided"]
+                total.update(ex)
+            # in every batch the epipolar gate, not the distance, decides at least one winner (it cannot under bCoarse)
+            assert coarse or batch_line_decided > 0, (it, only_stereo, ori)
+    for name in EXITS:
+        assert total[name] > 0, (name, dict(total))
+
+
+def test_a_feature_of_the_neighbour_is_matched_by_several_of_the_keyframe_in_seeded_cases():
+    rng = np.random.default_rng(12)
+    t1, nbrs = two_view_case(rng, 2, 150, nnodes=2)
+    shared = 0
+    for t2, F12, ep, truth in nbrs:
+        m, _ = search_for_triangulation(t1, t2, F12, ep)
+        taken = m[m >= 0]
+        shared += len(taken) - len(set(taken.tolist()))
+    assert shared > 0
+
+
+# ---- hand-worked cases ----------------------------------------------------------------------------------------------------
+
+Z = np.zeros(32, np.uint8)
+# F12 of a pure sideways motion (t12 along x, R12 = I, K = I): the epipolar line of (x1, y1) is y2 = y1 -> a = 0, b = -1, c = y1
+F_ROWS = np.array([[0, 0, 0], [0, 0, 1], [0, -1, 0]], np.float32)
+FAR = (1e6, 1e6)                                      # an epipole far from every keypoint
+
+
+def run(rows1, rows2, F12=F_ROWS, ep=FAR, **kw):
+    t1, t2 = make_table(rows1), make_table(rows2)
+    m, n = search_for_triangulation(t1, t2, F12, ep, **kw)
+    m2, n2 = search_for_triangulation_fast(t1, t2, F12, ep, **kw)
+    assert np.array_equal(m, m2) and n == n2
+    return m.tolist(), n
+
+
+def test_equal_distances_the_later_one_wins():
+    kf2 = [(5, 10, 0, 0, desc_with_bits(10), 7), (9, 10, 0, 0, desc_with_bits(10, offset=100), 7), (3, 10, 0, 0, desc_with_bits(11), 7)]
+    assert run([(0, 10, 0, 0, Z, 7)], kf2) == ([1], 1)
+    assert run([(0, 10, 0, 0, Z, 7)], kf2[::-1]) == ([2], 1)
+
+
+def test_th_low_is_inclusive():
+    assert run([(0, 10, 0, 0, Z, 1)], [(5, 10, 0, 0, desc_with_bits(50), 1)]) == ([0], 1)
+    assert run([(0, 10, 0, 0, Z, 1)], [(5, 10, 0, 0, desc_with_bits(51), 1)]) == ([-1], 0)
+
+
+def test_a_neighbour_feature_is_matched_by_two_keyframe_features():
+    # vbMatched2 is never set: both features of pKF1 take feature 0 of pKF2
+    kf1 = [(0, 10, 0, 0, Z, 4), (2, 10, 0, 0, desc_with_bits(1), 4)]
+    assert run(kf1, [(5, 10, 0, 0, desc_with_bits(2, offset=8), 4)]) == ([0, 0], 2)
+
+
+def test_zero_denominator_rejects_unless_coarse():
+    zero = np.zeros((3, 3), np.float32)
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 10, 0, 0, Z, 4)], F12=zero) == ([-1], 0)
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 10, 0, 0, Z, 4)], F12=zero, coarse=True) == ([0], 1)
+
+
+def find_float_double_split():
+    """A level and a float dsqr for which `dsqr < 3.84 * sigma2` differs between double (the reference: 3.84 is a double
+    literal) and float (3.84f * sigma2 rounded).  Searches the 8-level, 1.2-factor table; returns (level, dsqr, in_double,
+    in_float) or None."""
+    for lvl in range(NLEVELS):
+        bound64 = 3.84 * float(SIGMA2[lvl])
+        bound32 = F32(F32(3.84) * SIGMA2[lvl])
+        lo = F32(bound64)
+        for cand in (np.nextafter(lo, F32(0)), lo, np.nextafter(lo, F32(np.inf)), bound32, np.nextafter(bound32, F32(0))):
+            in_double, in_float = bool(float(cand) < bound64), bool(cand < bound32)
+            if in_double != in_float:
+                return lvl, F32(cand), in_double, in_float
+    return None
+
+
+def test_the_comparison_is_in_double_on_either_side_of_the_bound():
+    """dsqr just below and just above 3.84 * sigma2 for every level; and the float / double split: ONE WAS FOUND - at level 0
+    (sigma2 = 1) dsqr = 3.84f = 3.8399999141... is accepted by the reference (3.8399999 < 3.84 in double) where a float
+    comparison (3.84f < 3.84f * 1.0f) would reject it; the search below asserts that such a level exists."""
+    # with F_ROWS: a = 0, b = -1, c = y1: num = y1 - y2, den = 1, dsqr = (y1 - y2)^2 exactly for small integers / dyadic values
+    for lvl in range(NLEVELS):
+        bound = 3.84 * float(SIGMA2[lvl])
+        # the largest dyadic step below / above sqrt(bound) on a 1/64 grid keeps num * num exact in float
+        s = np.floor(np.sqrt(bound) * 64) / 64
+        for dy, want in ((s, 1), (s + 1 / 64, 0)):
+            assert (float(F32(dy) * F32(dy)) < bound) == bool(want)
+            assert run([(0, 0, 0, 0, Z, 1)], [(5, dy, lvl, 0, Z, 1)])[1] == want, (lvl, dy)
+    split = find_float_double_split()
+    assert split is not None
+    lvl, dsqr, in_double, in_float = split
+    # a pair whose dsqr is exactly that float: F12 = [[0,0,0],[0,0,1],[0,-1,0]] scaled so that den = 1 and num = sqrt is not exact
+    # in general, so the split is checked on the gate's own expression: a = 0, b = -1 (den = 1), num * num = dsqr via c
+    # (x1 = 0, y1 = 0, F[2,2] = c = num, y2 = 0): dsqr = fl(num * num) / 1
+    num = F32(np.sqrt(np.float64(dsqr)))
+    for cand in (np.nextafter(num, F32(0)), num, np.nextafter(num, F32(np.inf))):
+        d = F32(cand * cand)
+        F = np.array([[0, 0, 0], [0, 0, 0], [0, -1, cand]], np.float32)
+        want = int(float(d) < 3.84 * float(SIGMA2[lvl]))
+        assert run([(0, 0, 0, 0, Z, 1)], [(5, 0, lvl, 0, Z, 1)], F12=F)[1] == want
+        if d == dsqr:
+            assert bool(want) == in_double and in_double != in_float
+
+
+def test_the_epipole_gate_applies_to_mono_mono_only():
+    # the neighbour's feature sits 5 px from the epipole: 25 < 100 * 1.0 -> skipped, unless either side is stereo
+    kf1 = lambda st: [(0, 10, 0, 0, Z, 4, 0, st)]
+    kf2 = lambda st, octave=0, x=5: [(x, 10, octave, 0, Z, 4, 0, st)]
+    assert run(kf1(0), kf2(0), ep=(0, 10)) == ([-1], 0)
+    assert run(kf1(1), kf2(0), ep=(0, 10)) == ([0], 1)
+    assert run(kf1(0), kf2(1), ep=(0, 10)) == ([0], 1)
+    assert run(kf1(1), kf2(1), ep=(0, 10)) == ([0], 1)
+    # the radius grows with the level of kp2: 10 px away: 100 < 100 * 1.0 false (taken), 100 < 100 * 1.2 true (skipped)
+    assert run(kf1(0), kf2(0, 0, 10), ep=(0, 10)) == ([0], 1)
+    assert run(kf1(0), kf2(0, 1, 10), ep=(0, 10)) == ([-1], 0)
+    assert run(kf1(0), kf2(0), ep=(0, 10), coarse=True) == ([-1], 0)       # bCoarse does not lift this gate
+
+
+def test_only_stereo_and_coarse():
+    kf1 = [(0, 10, 0, 0, Z, 4, 0, 1), (0, 20, 0, 0, Z, 5, 0, 0)]
+    kf2 = [(5, 10, 0, 0, Z, 4, 0, 0), (6, 10, 0, 0, desc_with_bits(3), 4, 0, 1), (5, 20, 0, 0, Z, 5, 0, 1)]
+    assert run(kf1, kf2) == ([0, 2], 2)
+    assert run(kf1, kf2, only_stereo=True) == ([1, -1], 1)
+    # off the line (y differs by 3: 9 > 3.84): rejected, taken under bCoarse; TH_LOW still holds under bCoarse
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 13, 0, 0, Z, 4)]) == ([-1], 0)
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 13, 0, 0, Z, 4)], coarse=True) == ([0], 1)
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 13, 0, 0, desc_with_bits(51), 4)], coarse=True) == ([-1], 0)
+    # the closer descriptor lies off the line: the farther one on the line wins
+    assert run([(0, 10, 0, 0, Z, 4)], [(5, 10, 0, 0, desc_with_bits(30), 4), (5, 14, 0, 0, Z, 4)]) == ([0], 1)
+
+
+def test_nodes_and_map_points():
+    kf2 = [(5, 10, 0, 0, Z, 4), (5, 10, 0, 0, Z, 9)]
+    assert run([(0, 10, 0, 0, Z, 5)], kf2) == ([-1], 0)                        # a node present on one side only
+    assert run([(0, 10, 0, 0, Z, -1)], [(5, 10, 0, 0, Z, -1)]) == ([-1], 0)    # listed in no node
+    assert run([(0, 10, 0, 0, Z, 9)], kf2) == ([1], 1)
+    assert run([(0, 10, 0, 0, Z, 9, 1)], kf2) == ([-1], 0)                     # pKF1's feature has a map point
+    assert run([(0, 10, 0, 0, Z, 9)], [(5, 10, 0, 0, Z, 9, 1), (5, 10, 0, 0, desc_with_bits(9), 9)]) == ([1], 1)   # pKF2's has one
+    assert run([], kf2) == ([], 0) and run([(0, 10, 0, 0, Z, 4)], []) == ([-1], 0)
+
+
+def test_orientation_filter_holds_idx1():
+    # rotations 0 (x11, bin 0), 60, 90, 120: 1 < 0.1f * 11 drops all three other bins
+    kf1, kf2 = [], []
+    for i in range(14):
+        d = desc_with_bits(3, offset=(i * 17) % 250)
+        ang = 0.0 if i < 11 else (60.0, 90.0, 120.0)[i - 11]
+        kf1.append((0, 10 + i, 0, ang, d, 100 + i))
+        kf2.append((5, 10 + i, 0, 0.0, d, 100 + i))
+    m, n = run(kf1, kf2[::-1], check_orientation=True)
+    assert n == 11 and m == [13 - i for i in range(11)] + [-1] * 3
+    assert run(kf1, kf2, check_orientation=False)[1] == 14
+
+
+# ---- the adapters ---------------------------------------------------------------------------------------------------------
+
+STUB_SRC = r'''
+#define PLI_ADAPTER_NO_KEYLINE_HEADER
+#define PLI_ADAPTER_KEYLINE_TYPE StubKeyLine
+#include <opencv2/core/core.hpp>
+struct StubKeyLine { float angle; int class_id; int octave; cv::Point2f pt; float response; float size; float startPointX,
+  startPointY, endPointX, endPointY, sPointInOctaveX, sPointInOctaveY, ePointInOctaveX, ePointInOctaveY, lineLength; int numOfPixels; };
+#include "pli_slam_amd/adapters/orbslam_adapters.hpp"
+#include <map>
+#include <utility>
+#include <vector>
+// the members SearchForTriangulation reads (include/KeyFrame.h, CameraModels/GeometricCamera.h; DBoW2::FeatureVector is a std::map)
+typedef std::map<unsigned int, std::vector<unsigned int>> FeatureVector;
+struct StubMapPoint { bool isBad(); cv::Mat GetWorldPos(); cv::Mat GetDescriptor(); int Observations(); };
+struct StubCamera { cv::Mat toK(); };
+struct StubFrame {
+  cv::Mat mTcw, mDescriptors; float mb, mbf, fx, fy, cx, cy, mnMinX, mnMaxX, mnMinY, mnMaxY; int N, Nleft;
+  std::vector<StubMapPoint*> mvpMapPoints; std::vector<bool> mvbOutlier; std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
+  std::vector<float> mvScaleFactors, mvuRight; FeatureVector mFeatVec;
+};
+struct StubKeyFrame {
+  int N, NLeft; cv::Mat mDescriptors; std::vector<cv::KeyPoint> mvKeysUn; std::vector<float> mvuRight; FeatureVector mFeatVec;
+  StubCamera *mpCamera, *mpCamera2;
+  StubMapPoint* GetMapPoint(const size_t& idx);
+  cv::Mat GetRotation(); cv::Mat GetTranslation(); cv::Mat GetCameraCenter();
+};
+int use(StubKeyFrame* kf1, StubKeyFrame* kf2, std::vector<StubKeyFrame*>& neighbours, cv::Mat F12) {
+  typedef ORB_SLAM3::PliORBmatcher<StubFrame, StubMapPoint> ORBmatcher;
+  ORBmatcher matcher(0.6f, false);
+  std::vector<std::pair<size_t, size_t>> vMatchedPairs;
+  int n = matcher.SearchForTriangulation(kf1, kf2, F12, vMatchedPairs, false);
+  n += matcher.SearchForTriangulation(kf1, kf2, F12, vMatchedPairs, true, true);
+  std::vector<std::vector<std::pair<size_t, size_t>>> vvMatchedPairs;
+  std::vector<int> vn;
+  matcher.SearchForTriangulation(kf1, neighbours, vvMatchedPairs, vn, false);
+  float F[9], ep[2];
+  const float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t1[3] = {0, 0, 0}, t2[3] = {1, 0, 0}, K[4] = {458, 457, 367, 248};
+  ORB_SLAM3::pli_detail::triangulationGeometry(R, t1, t1, K, R, t2, K, F, ep);
+  return n + (int)vn.size();
+}
+'''
+
+
+def test_search_for_triangulation_adapters_are_valid_cpp_against_stub_types():
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "a.cpp")
+        open(src, "w").write(STUB_SRC)
+        r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", ROOT, "-I", os.path.join(ROOT, "tests", "stubs"), src],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_the_header_declares_search_for_triangulation():
+    src = open(os.path.join(ROOT, "include", "pli_frontend.h")).read()
+    assert "pli_status pli_search_for_triangulation(" in src
+    from pli_slam_amd import capi
+    assert "pli_search_for_triangulation" in capi._PROTOS
