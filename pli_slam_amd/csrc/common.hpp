@@ -122,6 +122,9 @@ struct TxDirtyLists {
                                // list), (1 << pixbits) - 1 when they are KEYS (gradient bin << pixbits | seed pixel, k_tx_sort): the seed pixel
   const int* perm = nullptr;   // round 1: workgroup -> (image, tile) in order of decreasing work (k_tx_order), or null: the grid order
   int xcdAffine = 0;           // round 1: all tiles of an image on ONE XCD (workgroups go to the 8 XCDs round robin)
+  int stamp = 0;               // the call's stamp base: round t stamps the per-region planes (rgDirty, rgLost) with stamp + t.  The base moves
+                               // up with every call of a context past every round number a call can write, so what earlier calls left in the
+                               // planes matches no round of this one and the planes need no clear per call (pli_capi.hip: lineStampBase)
 };
 
 // "no rank / no id": what the rank plane (k_lsd_scatter) and the id plane (k_tx_sort, key mode) hold for a pixel without a level-line
@@ -142,8 +145,6 @@ struct TxKeys {
   int nBins, pixbits;
   int* idPlane;                     // out: own id of every pixel (TX_INF: undefined)
   float4* recPack = nullptr;        // packed round 1 (lsd_tile.hip): the pixel records, whose fourth word is owner_1 during round 1
-  int* zeroA = nullptr;             // planes of one word per pixel index that the sort clears on its way (rgDirty, rgLost), or null
-  int* zeroB = nullptr;
   int lazyMargin = 8;               // LAZY ids: units of the 2^-22 fixed point around a bin boundary that the double plane decides (>= 4; test switch)
   int2* hot = nullptr;              // round 6: round 1's words live in 8-byte hot records {angle, owner word} instead (lsd_tile.hip "HOT RECORDS")
   const float2* cold = nullptr;     // ... and the records' exact {cos, sin} in a plane of their own when the 16-byte records are not written

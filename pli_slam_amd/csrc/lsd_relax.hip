@@ -272,8 +272,9 @@ __global__ __launch_bounds__(1024) void k_rx_seed(RxCtl* __restrict__ ctl, int2*
 __device__ __forceinline__ void rx_mark_dirty(int o, bool withBox, int t, int* __restrict__ rgDirty,
                                               const int2* __restrict__ rgBox, int* __restrict__ tileAct, int TW, int TH,
                                               const TxDirtyLists& DL, int img) {
-  if (rgDirty[o] == t) return;
-  if (atomicExch(&rgDirty[o], t) == t) return;      // one marker per region activates the tiles
+  const int st = DL.stamp + t;                      // (the call's stamp base: 0 in the lane relaxation, whose planes are filled per call)
+  if (rgDirty[o] == st) return;
+  if (atomicExch(&rgDirty[o], st) == st) return;    // one marker per region activates the tiles
   tx_dirty_append(DL, img, o);
   if (!withBox) return;
   const int2 b = rgBox[o];
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(256) void k_rx_mark(RxCtl* __restrict__ ctl, const 
           const int op = ci ? op2.x : op2.y;           // owner_{t-1} of the neighbour
           if (op == INT_MAX || op == lastOp) continue;
           lastOp = op;
-          if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + op] == t - 1)
+          if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + op] == DL.stamp + t - 1)
             rx_mark_dirty(op, true, t, rgDirty, rgBox, tileAct, TW, TH, DL, img);
         }
       }

@@ -265,10 +265,8 @@ __device__ __forceinline__ void tx_sort_tile(const int* __restrict__ rankAll, co
       // owner_0 = the trivial map, written for EVERY pixel of the tile (an undefined pixel is nobody's: INT_MAX in both components):
       // the front pass does not initialise the plane for this schedule.  Packed round 1: owner_1's start value into the pixel
       // record instead, with the "unclaimed" bit (k_tx_round2 writes the owner plane); LAZY ids: the front pass has written the word
-      // (the two stamp planes of the relaxation — one word per pixel index each — start every call at zero: cleared here, beside the id
-      // plane's store, instead of by a fill kernel of their own)
-      if (keys.zeroA) keys.zeroA[img * npix + y * W + x] = 0;
-      if (keys.zeroB) keys.zeroB[img * npix + y * W + x] = 0;
+      // (the two stamp planes of the relaxation — one word per pixel index each — are NOT cleared, here or anywhere else on a call's path:
+      // their words are round stamps above a base that moves up with every call, TxDirtyLists::stamp)
       if (keys.pack == 1) {
         if (r != TX_INF) {
           if (keys.hot) keys.hot[img * npix + y * W + x].y = (int)(TX_UNCLAIMED | (unsigned)r);
@@ -342,8 +340,9 @@ __device__ __forceinline__ void tx_mark_dirty(int o, int t, int* __restrict__ rg
                                               int* __restrict__ tileAct, int TW, int TH, const TxDirtyLists& DL, int img,
                                               bool withBox = true) {
   const int oi = o & DL.rmask;                          // (the region's slot in the per-region planes)
-  if (rgDirty[oi] == t) return;
-  if (atomicExch(&rgDirty[oi], t) == t) return;
+  const int st = DL.stamp + t;                          // (the region planes carry the call's stamp base, the cell tables the plain round)
+  if (rgDirty[oi] == st) return;
+  if (atomicExch(&rgDirty[oi], st) == st) return;
   tx_dirty_append(DL, img, o);
   if (!withBox) return;
   const int2 b = rgBox[oi];
@@ -388,7 +387,7 @@ __global__ __launch_bounds__(256) void k_tx_diff2(RxCtl* __restrict__ ctl, const
         // by its rightful lower owner as well, and a pixel it was wrongly refused would have to be held by a lower region that
         // does not hold it in the end — which is then a change of the later rounds' kind.  tools/sim/sim_tile_relax.cpp replays
         // the rule: SIM_CARRY=1 SIM_LOST=1.)
-        if (rgLostAll[base + (o & DL.rmask)] != 0)
+        if (rgLostAll[base + (o & DL.rmask)] == DL.stamp + 1)      // (stamped in round 1 of THIS call)
           tx_mark_dirty(o, t, rgDirtyAll + base, rgBoxAll + base, tileActAll + (int64_t)img * TW * TH, TW, TH, DL, img);
       } else {                                          // conservative rule: does its box (+1) leave the tile?
         const int2 b = rgBoxAll[base + (o & DL.rmask)];
@@ -494,7 +493,7 @@ __device__ __forceinline__ void tx_round2_block(RxCtl* __restrict__ ctl, int2* _
     }
     // (p is o's seed: o holds it, so o is alive)
     const bool dead = sp[i] != p && (ci ? so[i].x : so[i].y) != o[i];
-    const bool dirty = dead || lost[i] != 0;
+    const bool dirty = dead || lost[i] == DL.stamp + 1;      // (lost a claim in round 1 of THIS call; 0 = no owner, never a stamp)
     if (dirty) tx_mark_dirty(o[i], t, rgDirtyAll + base, rgBoxAll + base, tileActAll + (int64_t)img * TW * TH, TW, TH, DL, img);
     // (a pixel that falls back to its own rank makes its cell differ between owner_1 and owner_2: noted for round 3's diff)
     if (dirty && tileTouchAll) tileTouchAll[(int64_t)img * TW * TH + (y >> 3) * TW + (x >> 3)] = t;
@@ -591,7 +590,7 @@ __global__ __launch_bounds__(256) void k_tx_mark(RxCtl* __restrict__ ctl, const 
       const int2 op2 = ownAll[base + py * W + px];
       const int op = ci ? op2.x : op2.y;               // owner_{t-1} of the neighbour
       if (op == INT_MAX) continue;
-      if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == t - 1)
+      if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == DL.stamp + t - 1)
         tx_mark_dirty(op, t, rgDirty, rgBox, tileAct, TW, TH, DL, img);
     }
   }
@@ -671,7 +670,7 @@ __device__ __forceinline__ void tx_diffmark_block(RxCtl* ctl, const int2* ownAll
       const int2 op2 = ownAll[base + py * W + px];
       const int op = ci ? op2.x : op2.y;               // owner_{t-1} of the neighbour
       if (op == INT_MAX) continue;
-      if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == t - 1)
+      if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == DL.stamp + t - 1)
         tx_mark_dirty(op, t, rgDirty, rgBox, tileAct, TW, TH, DL, img);
     }
   }
@@ -695,7 +694,7 @@ __global__ __launch_bounds__(256) void k_tx_diffmark(RxCtl* __restrict__ ctl, co
 // that is per wave)
 __device__ __forceinline__ void tx_prep_block(RxCtl* ctl, int2* ownAll, const int* rankAll, const int* rgDirtyAll,
                                               const int* tileActAll, int W, int H, int TW, int TH, int t, int bx, int by, int img,
-                                              int full, int* tileTouchAll, int rmask) {
+                                              int full, int* tileTouchAll, int rmask, int stamp) {
   __shared__ int s_act;
   __shared__ int s_cell[4][4];
   RxCtl& c = ctl[img];
@@ -744,7 +743,7 @@ __device__ __forceinline__ void tx_prep_block(RxCtl* ctl, int2* ownAll, const in
     if (r[i] == TX_INF) continue;
     const int y = by * 32 + i * 8 + (tid >> 5);
     const int prevv = ci ? o[i].x : o[i].y;
-    const int cur = dirtyAt[i] != t ? prevv : r[i];
+    const int cur = dirtyAt[i] != stamp + t ? prevv : r[i];
     if (cur != (ci ? o[i].y : o[i].x)) {
       if (ci) o[i].y = cur; else o[i].x = cur;
       ownAll[base + y * W + x] = o[i];
@@ -755,8 +754,8 @@ __device__ __forceinline__ void tx_prep_block(RxCtl* ctl, int2* ownAll, const in
 __global__ __launch_bounds__(256) void k_tx_prep(RxCtl* __restrict__ ctl, int2* __restrict__ ownAll,
                                                  const int* __restrict__ rankAll, const int* __restrict__ rgDirtyAll,
                                                  const int* __restrict__ tileActAll, int W, int H, int TW, int TH, int t, int img0,
-                                                 int full, int* __restrict__ tileTouchAll, int rmask) {
-  tx_prep_block(ctl, ownAll, rankAll, rgDirtyAll, tileActAll, W, H, TW, TH, t, blockIdx.x, blockIdx.y, blockIdx.z + img0, full, tileTouchAll, rmask);
+                                                 int full, int* __restrict__ tileTouchAll, int rmask, int stamp) {
+  tx_prep_block(ctl, ownAll, rankAll, rgDirtyAll, tileActAll, W, H, TW, TH, t, blockIdx.x, blockIdx.y, blockIdx.z + img0, full, tileTouchAll, rmask, stamp);
 }
 
 // ---------------------------------------------------------------------------
@@ -911,7 +910,7 @@ __global__ __launch_bounds__(64) void k_tx_diffmark_cells(RxCtl* __restrict__ ct
           const int2 op2 = ownAll[base + py * W + px];
           const int op = ci ? op2.x : op2.y;             // owner_{t-1} of the neighbour
           if (op == INT_MAX) continue;
-          if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == t - 1)
+          if ((prev2 < op && prevv > op) || (prev2 == op && prevv < op) || rgLostAll[base + (op & DL.rmask)] == DL.stamp + t - 1)
             tx_mark_dirty(op, t, rgDirty, rgBox, tileAct, TW, TH, DL, img);
         }
       }
@@ -923,7 +922,7 @@ __global__ __launch_bounds__(64) void k_tx_diffmark_cells(RxCtl* __restrict__ ct
 // one wave per listed cell, four cells at a time: owner_t of the cells' pixels (k_tx_prep's rule)
 __global__ __launch_bounds__(64) void k_tx_prep_cells(const RxCtl* __restrict__ ctl, int2* __restrict__ ownAll, const int* __restrict__ rankAll,
                                                        const int* __restrict__ rgDirtyAll, int W, int H, int TW, int TH, int t, int img0, int rmask,
-                                                       const int* __restrict__ list, const int* __restrict__ cnt) {
+                                                       const int* __restrict__ list, const int* __restrict__ cnt, int stamp) {
   constexpr int U = 4;
   const int lane = threadIdx.x & 63;
   const int il = blockIdx.y, ncell = TW * TH;
@@ -956,7 +955,7 @@ __global__ __launch_bounds__(64) void k_tx_prep_cells(const RxCtl* __restrict__ 
     for (int u = 0; u < U; ++u) {
       if (r[u] == TX_INF) continue;
       const int prevv = ci ? o[u].x : o[u].y;
-      const int cur = dirtyAt[u] != t ? prevv : r[u];
+      const int cur = dirtyAt[u] != stamp + t ? prevv : r[u];
       if (cur != (ci ? o[u].y : o[u].x)) {
         if (ci) o[u].y = cur; else o[u].x = cur;
         ownAll[base + p[u]] = o[u];
@@ -1175,6 +1174,7 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
   int* tileTouch = tileTouchAll ? tileTouchAll + (int64_t)img * TW * TH : nullptr;
   RxRect* rects = rectAll + (int64_t)img * rectCap;
   const int ci = t & 1;                                   // owner_t lives in component ci, owner_{t-1} in the other
+  const int st = DL.stamp + t;                            // what this round stamps the per-region planes with (uniform: one scalar add per wave)
   const double prec = P.prec;
   const int minReg = P.minRegSize;
   const float alignLo = P.alignLo, alignHi = P.alignHi;
@@ -1420,14 +1420,14 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
           // a higher one has just lost it)
           // (a claim never finds the region's own id: the accept loop takes a pixel once)
           if (__builtin_amdgcn_ballot_w64(pendOld >= 0) != 0ull) {
-            if (pendOld >= 0) rgLost[max(pendOld, r) & DL.rmask] = t;
+            if (pendOld >= 0) rgLost[max(pendOld, r) & DL.rmask] = st;
           }
           pendOld = -1;
           return;
         } else if (noteLost) {
           if (__builtin_amdgcn_ballot_w64(pendOld != pendRank) != 0ull) {
             const bool contested = pendOld < r || (pendOld != r && pendOld != pendRank);
-            if (contested) rgLost[(pendOld < r ? r : pendOld) & DL.rmask] = t;
+            if (contested) rgLost[(pendOld < r ? r : pendOld) & DL.rmask] = st;
           }
         }
         pendOld = r;
@@ -1869,8 +1869,8 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
                 for (int i = 1; i < CAP; ++i) {
                   if (i >= cnt) continue;
                   const int pv = ci ? ow[i].x : ow[i].y;       // round 1: owner_0 is the trivial map, i.e. the pixel's own rank
-                  if (olds[i] < r) rgLost[r & DL.rmask] = t;                              // a lower rank slipped in between the look and the claim
-                  else if (olds[i] != r && olds[i] != pv) rgLost[olds[i] & DL.rmask] = t; // a higher rank held it: it has just lost the pixel
+                  if (olds[i] < r) rgLost[r & DL.rmask] = st;                             // a lower rank slipped in between the look and the claim
+                  else if (olds[i] != r && olds[i] != pv) rgLost[olds[i] & DL.rmask] = st; // a higher rank held it: it has just lost the pixel
                 }
               }
             }
@@ -1939,7 +1939,7 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
       if (valid) se = seedEntry(base + lane);
     }
     bool d = valid;
-    if (SPARSE && !useDirty) d = valid && rgDirty[se.x & DL.rmask] == t;
+    if (SPARSE && !useDirty) d = valid && rgDirty[se.x & DL.rmask] == st;
     float4 srec = make_float4(TX_NOTDEF, 0.f, 0.f, 0.f);
     int2 so = make_int2(0, 0);
     if (PACK) {
@@ -2490,7 +2490,7 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
       for (int i = 0; i < n; ++i) {
         const int64_t va = base + (int64_t)s_list[i] * G;
         const int il = (int)(va / (nbx * nbyB)), rem = (int)(va - (int64_t)il * (nbx * nbyB));
-        tx_prep_block(A.ctl, A.own, A.rank, A.rgDirty, A.tileAct, W, H, A.TW, A.TH, t, rem % nbx, rem / nbx, A.img0 + il, 0, A.tileTouch, A.DL.rmask);
+        tx_prep_block(A.ctl, A.own, A.rank, A.rgDirty, A.tileAct, W, H, A.TW, A.TH, t, rem % nbx, rem / nbx, A.img0 + il, 0, A.tileTouch, A.DL.rmask, A.DL.stamp);
         __syncthreads();
       }
     }

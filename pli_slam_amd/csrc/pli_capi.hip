@@ -114,6 +114,12 @@ struct pli_ctx {
   int2* own = nullptr; RxSeed* smallSeeds = nullptr; RxSeed* bigSeeds = nullptr; int bigCap = 0;
   RxHand* hand = nullptr; int handCap = 0; RxRect* rects = nullptr; int rectCap = 0; int* rankOf = nullptr; int2* rgBox = nullptr; float4* rgSeg = nullptr; uint8_t* rgClean = nullptr;
   int* rgLost = nullptr;                     // tile relaxation: round in which a region last lost a contested claim (per rank)
+  // rgDirty and rgLost hold ROUND STAMPS, and a stamp is only ever compared with a round of the call that reads it.  So the planes are not
+  // cleared per call: every call of the tile relaxation stamps with lineStampNext + t and leaves lineStampNext above everything it could
+  // have written (runLines).  Words of earlier calls, under whatever pixels, are below the base and match no round.  One counter per
+  // context (the planes are indexed by image slot; calls are ordered by the context's lock and the stream).  Zeroed when allocated and
+  // when the counter would pass INT_MAX.  Dev switch PLI_TX_STAMP0: where the counter starts.
+  int lineStampNext = 0;
   int* tileTouch = nullptr;                  // tile relaxation: round in which a grower last claimed a pixel of the 8x8 cell
   int* tileMin = nullptr; int* tileAct = nullptr; int* rgDirty = nullptr; int tilesW = 0, tilesH = 0; int* rxChunkCnt = nullptr; int rxChunks = 0;
   int* lastSize = nullptr; int* arena = nullptr; int arenaCap = 0; int arenaFactor = 0;    // (arena words per scaled pixel the context got)
@@ -676,6 +682,11 @@ pli_status allocAll(pli_ctx* c) {
     A(c->tileTouch, (size_t)c->tilesW * c->tilesH * NR);
     A(c->rgDirty, npix * NR);
     A(c->rgLost, npix * NR);
+    // (round stamps above a per-call base, pli_ctx::lineStampNext: cleared here, once, and not per call)
+    HIPCHK(hipMemset(c->rgDirty, 0, sizeof(int) * npix * NR));
+    HIPCHK(hipMemset(c->rgLost, 0, sizeof(int) * npix * NR));
+    HIPCHK(hipDeviceSynchronize());
+    if (const char* e = DEVENV("PLI_TX_STAMP0")) c->lineStampNext = std::max(0, atoi(e));     // test switch: a start next to the overflow
     c->rxChunks = (int)((npix + 2047) / 2048);
     A(c->rxChunkCnt, (size_t)c->rxChunks * NR);
     // pixel lists for region2rect (<= npix per round) + queue overflow blocks; the lane growers also park hand-overs here
@@ -1066,15 +1077,16 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     int bigThresh = RX_HAND;
     if (const char* e = DEVENV("PLI_JR_BIG")) bigThresh = atoi(e);
     int maxRounds = 96;
-    if (const char* e = DEVENV("PLI_RX_MAXROUNDS")) maxRounds = std::max(1, atoi(e));
+    if (const char* e = DEVENV("PLI_RX_MAXROUNDS")) maxRounds = std::max(1, std::min(1 << 20, atoi(e)));
     const float precDeg = (float)(P.prec * 180.0 / 3.14159265358979323846);
     (void)growBlocks; (void)bigBlocks; (void)bigThresh; (void)precDeg;     // (the lane relaxation's: development build)
     if (c->rgClean) HIPCHK(hipMemsetAsync(c->rgClean + (int64_t)img0 * npix, 0, npix64 * nimg, c->stream));   // round stamps
     const bool lostRule = c->lsdMode != 1 && DEVENV("PLI_TX_BOXRULE") == nullptr;     // dev switch: the conservative round-2 rule
     {
-      // everything the relaxation wants zeroed at the start of a call, in one launch (k_zero_ranges): control blocks, the stamp planes,
-      // the cell tables, and the tile relaxation's per-tile dirty counters (cleared by their consumers from then on), the barrier words
-      // of k_tx_tail and the candidate counters of k_tx_collect
+      // everything the relaxation wants zeroed at the start of a call, in one launch (k_zero_ranges): control blocks, the cell tables,
+      // the tile relaxation's per-tile dirty counters (cleared by their consumers from then on), the barrier words of k_tx_tail and the
+      // candidate counters of k_tx_collect.  NOT the two per-pixel stamp planes (rgDirty, rgLost) of the tile relaxation, whatever its
+      // dev switches: their stamps sit above a base that moves with every call (pli_ctx::lineStampNext), nobody clears them per call.
       const int64_t cells = (int64_t)c->tilesW * c->tilesH;
       const int64_t ntile64 = (int64_t)c->txNtx * c->txNty;
       static_assert(sizeof(RxCtl) % 4 == 0, "RxCtl is cleared as words");
@@ -1088,11 +1100,10 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
         Z.p[zr] = (uint32_t*)p; Z.words[zr] = words; ++zr;
       };
       add(c->jrCtl + img0, (int64_t)(sizeof(RxCtl) / 4) * nimg);
-      // (tile relaxation: k_tx_sort clears the two per-pixel stamp planes while it writes the id plane)
-      if (c->lsdMode == 1 || DEVENV("PLI_TX_ZERO_BY_FILL")) {
-        add(c->rgDirty + (int64_t)img0 * npix, npix64 * nimg);
-        if (lostRule) add(c->rgLost + (int64_t)img0 * npix, npix64 * nimg);
-      }
+      // (the lane relaxation — development build, lsd_mode 1 — keeps its fill and stamps with the plain round: k_rx_seed_sparse and the byte
+      // plane rgClean beside it compare with t, the schedule is a cross-check and not a speed item, and a context has one mode for life,
+      // so its planes never meet the other schedules' stamps)
+      if (c->lsdMode == 1) add(c->rgDirty + (int64_t)img0 * npix, npix64 * nimg);
       add(c->tileTouch + (int64_t)img0 * cells, cells * nimg);
       add(c->tileAct + (int64_t)img0 * cells, cells * nimg);
       if (c->txDirtyCnt) add(c->txDirtyCnt + (int64_t)img0 * ntile64, ntile64 * nimg);
@@ -1125,8 +1136,23 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
                               !DEVENV("PLI_TX_NOFUSEDM") && !DEVENV("PLI_TX_NODIRTYLIST");
     const bool blocking = !tailPossible && (c->rxLastRounds == 0 || trace || DEVENV("PLI_RX_BLOCKING") != nullptr);
     if (!blocking && !tailPossible) maxRounds = std::min(maxRounds, c->rxLastRounds + c->rxMargin);
-    if (!blocking) if (const char* e = DEVENV("PLI_RX_PLAN")) maxRounds = std::max(1, atoi(e));   // dev / test: a plan that is too short
+    if (!blocking) if (const char* e = DEVENV("PLI_RX_PLAN")) maxRounds = std::max(1, std::min(1 << 20, atoi(e)));   // dev / test: a plan that is too short
     c->rxPlanned = blocking ? 0 : (tailPossible ? -1 : maxRounds);
+    // The call's stamp base (pli_ctx::lineStampNext).  No round of this call is above maxRounds — the host loop below and k_tx_tail, which
+    // counts its own rounds, both end there — so the next call starts maxRounds + 1 higher.  Before the counter would pass INT_MAX (once in
+    // some 10^7 calls) both planes are zeroed whole, in stream order behind every earlier call, and the counter starts again.
+    // (That order holds because every kernel that reads or writes the two planes runs on c->stream.  Round 1's region2rect pass, the one
+    // kernel of the line chain on another stream — aux / aux2 —, touches neither; a kernel that did would need an event before this fill.)
+    int stampBase = 0;
+    if (tile) {
+      if ((int64_t)c->lineStampNext + maxRounds + 1 > (int64_t)INT_MAX) {
+        HIPCHK(hipMemsetAsync(c->rgDirty, 0, sizeof(int) * (size_t)npix * c->rxImages, c->stream));
+        HIPCHK(hipMemsetAsync(c->rgLost, 0, sizeof(int) * (size_t)npix * c->rxImages, c->stream));
+        c->lineStampNext = 0;
+      }
+      stampBase = c->lineStampNext;
+      c->lineStampNext += maxRounds + 1;
+    }
     const int firstLook = c->rxLastRounds > 0 ? std::max(4, c->rxLastRounds) : 4;
     auto look = [&](int t) -> pli_status {
       // the host looks at the state every second round, starting where the previous call on this context ended (a
@@ -1152,7 +1178,6 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       if (keyMode) keys = TxKeys{c->mg, c->maxMg, P.rho, P.nBins, c->txPixBits, c->rankOf};
       const bool pack1 = packMode != 0;
       if (pack1) { keys.recPack = c->rec; keys.pack = packMode; keys.hot = hotPlane; keys.cold = coldPlane; }
-      if (!DEVENV("PLI_TX_ZERO_BY_FILL")) { keys.zeroA = c->rgDirty; keys.zeroB = lostRule ? c->rgLost : (int*)nullptr; }
       // (test switch: a wide margin sends every unclaimed pixel of the LAZY form through the double plane; the results must not change)
       if (const char* e = DEVENV("PLI_TX_LAZY_MARGIN")) keys.lazyMargin = std::max(4, std::min(0x3FFFFFFF, atoi(e)));
 #ifdef PLI_DEV
@@ -1167,6 +1192,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       const size_t txPad = DEVENV("PLI_TX_LDSPAD") ? (size_t)atoi(DEVENV("PLI_TX_LDSPAD")) : 0;   // dev: occupancy cap of the tile growers
       TxDirtyLists DL{c->txDirtyList, c->txDirtyCnt, c->order, ts, c->txNtx, c->txNty, P.LW, npix64};
       if (keyMode) DL.rmask = (1 << c->txPixBits) - 1;
+      DL.stamp = stampBase;
       if (DEVENV("PLI_TX_NODIRTYLIST")) DL.list = nullptr;             // dev: every active tile walks its whole seed list
       TxDirtyLists noDL = DL; noDL.list = nullptr;
       // rounds >= 3: k_rx_diff + k_tx_mark as one kernel (k_tx_diffmark; the dev rules keep the separate passes)
@@ -1265,7 +1291,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
               c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)c->rgLost, DL, (const int*)lst, (const int*)cntA);
           TRL(c, "k_tx_cells", k_tx_cells, lg, dim3(256), 0, c->jrCtl, (const int*)c->tileAct, c->tileTouch, ncell, nimg, img0, t, 1, lst, cntB);
           TRL(c, "k_tx_prep", k_tx_prep_cells, wg, dim3(64), 0, (const RxCtl*)c->jrCtl, c->own, (const int*)c->rankOf, (const int*)c->rgDirty, P.LW,
-              P.LH, c->tilesW, c->tilesH, t, img0, DL.rmask, (const int*)lst, (const int*)cntB);
+              P.LH, c->tilesW, c->tilesH, t, img0, DL.rmask, (const int*)lst, (const int*)cntB, DL.stamp);
           cellsDone = true;
         } else if (t >= 3 && fusedDM)
           TRL(c, "k_tx_diffmark", k_tx_diffmark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf,
@@ -1295,7 +1321,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
 #endif
           if (!fused2 && !cellsDone)
           TRL(c, "k_tx_prep", k_tx_prep, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf,
-              c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, t == 2 ? 1 : 0, fusedDM ? c->tileTouch : (int*)nullptr, DL.rmask);
+              c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, t == 2 ? 1 : 0, fusedDM ? c->tileTouch : (int*)nullptr, DL.rmask, DL.stamp);
           if (hotLater)
           TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse_h, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
               c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
