@@ -62,6 +62,17 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   }
   return v;
 }
+// the two smallest 64-bit keys of a wave: every lane pushes its keys; min1() gives all lanes the smallest key pushed by any lane,
+// min2(min1()) the second smallest (~0ull where there is none; the keys of a wave are distinct: they carry an index)
+struct WaveTop2 {
+  unsigned long long k1 = ~0ull, k2 = ~0ull;
+  __device__ __forceinline__ void push(unsigned long long key) {
+    if (key < k1) { k2 = k1; k1 = key; }
+    else if (key < k2) k2 = key;
+  }
+  __device__ __forceinline__ unsigned long long min1() const { return wave_min_u64(k1); }
+  __device__ __forceinline__ unsigned long long min2(unsigned long long m1) const { return wave_min_u64(k1 == m1 ? k2 : k1); }
+};
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -7,8 +7,10 @@
 //                                       + GridStructure/LineIterator (gridStructure.cpp, LineIterator.cpp)
 //   k_distance                          ORBmatcher::DescriptorDistance     (ORBmatcher.cc:2495-2511)
 //   k_knn2, k_ratio, k_mutual           matchNNR / match                   (LineMatcher.cpp:139-229)
-//   k_search_by_projection              ORBmatcher::SearchByProjection(F,F)(ORBmatcher.cc:2179-2323)
-//   k_search_local_map                  ORBmatcher::SearchByProjection(F,MPs)(ORBmatcher.cc:44-143)
+//   k_proj_candidates + k_proj_assign   ORBmatcher::SearchByProjection(F,F)(ORBmatcher.cc:2179-2323) and
+//   (k_proj_assign_scan: large frames)  ORBmatcher::SearchByProjection(F,MPs)(ORBmatcher.cc:44-143)
+//   k_proj_assign_fisheye               the same (F,MPs) for a frame of two fisheye cameras (ORBmatcher.cc:44-214)
+//   k_track_queries/candidates/assign/lines   frame-to-frame track matching of a batch (pli_batch_track)
 //   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 //   k_tri_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
 #include "kernels.hpp"
@@ -20,6 +22,37 @@ namespace pli {
 __device__ __forceinline__ void load_desc(const uint8_t* p, uint64_t d[4]) {
   const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
   d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3];
+}
+
+// ---------------------------------------------------------------------------
+// Rotation consistency (mbCheckOrientation), shared by the projection, BoW and triangulation searches: a match votes for the
+// bin of the angle between its two keypoints; matches outside the three fullest bins are dropped.
+// ---------------------------------------------------------------------------
+constexpr int HISTO_LENGTH = 30;
+
+// the raw bin of the reference expression (ORBmatcher.cc:2286-2291; :391-396 in SearchByBoW): 0..12 for angles in [0, 360); other floats may
+// give any int, and each search family states below what it does with a bin outside 0..HISTO_LENGTH-1
+__device__ __forceinline__ int rot_bin(float a, float b) {
+  float rot = __fsub_rn(a, b);
+  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+  int bin = (int)roundf(__fmul_rn(rot, 1.0f / HISTO_LENGTH));
+  if (bin == HISTO_LENGTH) bin = 0;
+  return bin;
+}
+
+// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2449-2490) on a histogram of HISTO_LENGTH counts: the three fullest bins, the
+// second and third only if they hold at least 10 % of the first (-1: none)
+__device__ __forceinline__ void three_maxima(const int* hist, int& ind1, int& ind2, int& ind3) {
+  int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+  for (int i = 0; i < HISTO_LENGTH; i++) {
+    const int s = hist[i];
+    if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+    else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+    else if (s > max3) { max3 = s; i3 = i; }
+  }
+  if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
+  else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) i3 = -1;
+  ind1 = i1; ind2 = i2; ind3 = i3;
 }
 
 // ---------------------------------------------------------------------------
@@ -462,17 +495,13 @@ __global__ __launch_bounds__(64) void k_knn2(const uint8_t* __restrict__ q, int 
   if (i >= nq) return;
   uint64_t dq[4];
   load_desc(q + (int64_t)i * 32, dq);
-  unsigned long long k1 = ~0ull, k2 = ~0ull;
+  WaveTop2 top;
   for (int j = lane; j < nt; j += 64) {
     uint64_t dt[4];
     load_desc(t + (int64_t)j * 32, dt);
-    unsigned long long key = ((unsigned long long)hamming256(dq, dt) << 32) | (unsigned)j;
-    if (key < k1) { k2 = k1; k1 = key; }
-    else if (key < k2) k2 = key;
+    top.push(((unsigned long long)hamming256(dq, dt) << 32) | (unsigned)j);
   }
-  const unsigned long long m1 = wave_min_u64(k1);
-  const unsigned long long c2 = (k1 == m1) ? k2 : k1;
-  const unsigned long long m2 = wave_min_u64(c2);
+  const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
   if (lane == 0) {
     idx[2 * i] = m1 == ~0ull ? -1 : (int)(m1 & 0xFFFFFFFFu);
     dist[2 * i] = m1 == ~0ull ? INT_MAX : (int)(m1 >> 32);
@@ -504,223 +533,6 @@ __global__ void k_mutual(int* __restrict__ m12, const int* __restrict__ m21, int
 }
 
 // ---------------------------------------------------------------------------
-// SearchByProjection(CurrentFrame, LastFrame): the queries are consumed in
-// order by one wave because a current keypoint taken by an earlier query is
-// not available to later ones; the 64 lanes scan the current keypoints.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_search_by_projection(const pli_proj_query* __restrict__ q,
-                                                             const uint8_t* __restrict__ qdesc, int nq,
-                                                             const pli_keypoint* __restrict__ kp,
-                                                             const uint8_t* __restrict__ desc,
-                                                             const float* __restrict__ uright, int ncur, float minX,
-                                                             float maxX, float minY, float maxY, int checkOri,
-                                                             int* __restrict__ owner /* ncur */,
-                                                             int* __restrict__ bestIdx2 /* nq */,
-                                                             int* __restrict__ nmatchesOut,
-                                                             const uint8_t* __restrict__ occupied /* ncur or null */,
-                                                             int* __restrict__ rawIdx2 /* nq or null: the matches before the rotation filter */) {
-  __shared__ int hist[30];
-  __shared__ int keep[30];
-  const int lane = threadIdx.x;
-  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX));
-  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(maxY, minY));
-  // (a keypoint that holds a map point with observations before the call is not available, ORBmatcher.cc:2259-2261; a match made in
-  // this call takes its keypoint away from the later queries only if ITS map point has observations — PLI_PROJ_NO_OBSERVATIONS, bit 1 of
-  // `valid`, marks the queries whose map point has none: Tracking::UpdateLastFrame's temporal points in localisation mode)
-  for (int i = lane; i < ncur; i += 64) owner[i] = (occupied && occupied[i]) ? INT_MAX : -1;
-  for (int i = lane; i < nq; i += 64) bestIdx2[i] = -1;
-  if (lane < 30) hist[lane] = 0;
-  __syncthreads();
-  int nmatches = 0;
-  for (int i = 0; i < nq; ++i) {
-    const pli_proj_query Q = q[i];
-    if (!Q.valid) continue;
-    const float u = Q.u, v = Q.v, radius = Q.radius;
-    if (u < minX || u > maxX) continue;
-    if (v < minY || v > maxY) continue;
-    const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, minX), radius), gwInv)));
-    if (nMinCellX >= GRID_COLS) continue;
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, minX), radius), gwInv)));
-    if (nMaxCellX < 0) continue;
-    const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, minY), radius), ghInv)));
-    if (nMinCellY >= GRID_ROWS) continue;
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, minY), radius), ghInv)));
-    if (nMaxCellY < 0) continue;
-    const bool bCheckLevels = (Q.min_level > 0) || (Q.max_level >= 0);
-    uint64_t dq[4];
-    load_desc(qdesc + (int64_t)i * 32, dq);
-    unsigned long long best = ~0ull;
-    for (int i2 = lane; i2 < ncur; i2 += 64) {
-      const pli_keypoint k = kp[i2];
-      const int px = (int)roundf(__fmul_rn(__fsub_rn(k.x, minX), gwInv));
-      const int py = (int)roundf(__fmul_rn(__fsub_rn(k.y, minY), ghInv));
-      if (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) continue;   // PosInGrid
-      if (px < nMinCellX || px > nMaxCellX || py < nMinCellY || py > nMaxCellY) continue;
-      if (bCheckLevels) {
-        if (k.octave < Q.min_level) continue;
-        if (Q.max_level >= 0 && k.octave > Q.max_level) continue;
-      }
-      const float distx = __fsub_rn(k.x, u), disty = __fsub_rn(k.y, v);
-      if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-      if (owner[i2] >= 0) continue;
-      const float ur2 = uright[i2];
-      if (ur2 > 0) {
-        const float er = fabsf(__fsub_rn(Q.ur, ur2));
-        if (er > radius) continue;
-      }
-      uint64_t d2[4];
-      load_desc(desc + (int64_t)i2 * 32, d2);
-      const int dist = hamming256(dq, d2);
-      if (dist < 256) {
-        // first minimum in the reference's visiting order: cells ix asc, iy asc, then insertion order
-        unsigned long long key = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) |
-                                 ((unsigned long long)py << 28) | (unsigned long long)i2;
-        best = key < best ? key : best;
-      }
-    }
-    best = wave_min_u64(best);
-    if (best != ~0ull && (int)(best >> 40) <= 100) {
-      const int b2 = (int)(best & 0xFFFFFFFull);
-      if (lane == 0) {
-        if (!(Q.valid & 2)) owner[b2] = i;
-        bestIdx2[i] = b2;
-        if (checkOri) {
-          float rot = __fsub_rn(Q.angle, kp[b2].angle);
-          if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-          int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-          if (bin == 30) bin = 0;
-          if (bin >= 0 && bin < 30) hist[bin]++;
-        }
-      }
-      ++nmatches;
-      __threadfence_block();
-    }
-    __syncthreads();
-  }
-  if (checkOri) {
-    if (lane == 0) {
-      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-      for (int i = 0; i < 30; i++) {
-        const int s = hist[i];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-      }
-      if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-      else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-      for (int i = 0; i < 30; ++i) keep[i] = (i == ind1 || i == ind2 || i == ind3);
-    }
-    __syncthreads();
-  }
-  // the rotation filter, per accepted query (:2303-2320: every entry of a rejected bin takes one off nmatches)
-  __syncthreads();
-  int removed = 0;
-  for (int i = lane; i < nq; i += 64) {
-    const int b = bestIdx2[i];
-    if (rawIdx2) rawIdx2[i] = b;
-    if (b < 0 || !checkOri) continue;
-    float rot = __fsub_rn(q[i].angle, kp[b].angle);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-    if (bin == 30) bin = 0;
-    if (!(bin >= 0 && bin < 30 && keep[bin])) { bestIdx2[i] = -1; ++removed; }
-  }
-  removed = wave_sum_i32(removed);
-  nmatches -= removed;
-  if (lane == 0) *nmatchesOut = nmatches;
-}
-
-// ---------------------------------------------------------------------------
-// Local-map search (ORBmatcher.cc:44-143, rectified stereo branch).  One wave walks the
-// map points in order (the assignment of a keypoint is visible to the following points);
-// the lanes share the scan over the frame's keypoints.  The reference's running
-// best / second-best pair is the two smallest (distance, visiting order) keys.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_search_local_map(const pli_proj_query* __restrict__ q,
-                                                         const uint8_t* __restrict__ qdesc, int nq,
-                                                         const pli_keypoint* __restrict__ kp,
-                                                         const uint8_t* __restrict__ desc,
-                                                         const float* __restrict__ uright,
-                                                         const uint8_t* __restrict__ occupied, int ncur, float minX,
-                                                         float maxX, float minY, float maxY, float nnratio,
-                                                         int* __restrict__ owner /* ncur */,
-                                                         int* __restrict__ bestIdx2 /* nq */,
-                                                         int* __restrict__ nmatchesOut) {
-  const int lane = threadIdx.x;
-  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX));
-  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(maxY, minY));
-  for (int i = lane; i < ncur; i += 64) owner[i] = (occupied && occupied[i]) ? INT_MAX : -1;
-  for (int i = lane; i < nq; i += 64) bestIdx2[i] = -1;
-  __syncthreads();
-  int nmatches = 0;
-  for (int i = 0; i < nq; ++i) {
-    const pli_proj_query Q = q[i];
-    if (!Q.valid) continue;
-    const float u = Q.u, v = Q.v, radius = Q.radius;
-    const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, minX), radius), gwInv)));
-    if (nMinCellX >= GRID_COLS) continue;
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, minX), radius), gwInv)));
-    if (nMaxCellX < 0) continue;
-    const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, minY), radius), ghInv)));
-    if (nMinCellY >= GRID_ROWS) continue;
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, minY), radius), ghInv)));
-    if (nMaxCellY < 0) continue;
-    const bool bCheckLevels = (Q.min_level > 0) || (Q.max_level >= 0);
-    uint64_t dq[4];
-    load_desc(qdesc + (int64_t)i * 32, dq);
-    unsigned long long k1 = ~0ull, k2 = ~0ull;
-    for (int i2 = lane; i2 < ncur; i2 += 64) {
-      const pli_keypoint k = kp[i2];
-      const int px = (int)roundf(__fmul_rn(__fsub_rn(k.x, minX), gwInv));
-      const int py = (int)roundf(__fmul_rn(__fsub_rn(k.y, minY), ghInv));
-      if (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) continue;   // PosInGrid
-      if (px < nMinCellX || px > nMaxCellX || py < nMinCellY || py > nMaxCellY) continue;
-      if (bCheckLevels) {
-        if (k.octave < Q.min_level) continue;
-        if (Q.max_level >= 0 && k.octave > Q.max_level) continue;
-      }
-      const float distx = __fsub_rn(k.x, u), disty = __fsub_rn(k.y, v);
-      if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-      if (owner[i2] >= 0) continue;
-      const float ur2 = uright[i2];
-      if (ur2 > 0) {
-        const float er = fabsf(__fsub_rn(Q.ur, ur2));
-        if (er > radius) continue;
-      }
-      uint64_t d2[4];
-      load_desc(desc + (int64_t)i2 * 32, d2);
-      const int dist = hamming256(dq, d2);
-      if (dist < 256) {
-        const unsigned long long key = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) |
-                                       ((unsigned long long)py << 28) | (unsigned long long)i2;
-        if (key < k1) { k2 = k1; k1 = key; }
-        else if (key < k2) k2 = key;
-      }
-    }
-    const unsigned long long m1 = wave_min_u64(k1);
-    const unsigned long long c2 = (k1 == m1) ? k2 : k1;
-    const unsigned long long m2 = wave_min_u64(c2);
-    if (m1 != ~0ull && (int)(m1 >> 40) <= 100) {
-      const int b1 = (int)(m1 & 0xFFFFFFFull);
-      const int bestDist = (int)(m1 >> 40);
-      const int bestLevel = kp[b1].octave;
-      int bestDist2 = 256, bestLevel2 = -1;
-      if (m2 != ~0ull) { bestDist2 = (int)(m2 >> 40); bestLevel2 = kp[(int)(m2 & 0xFFFFFFFull)].octave; }
-      const bool reject = bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2);
-      if (!reject) {
-        // every lane stores the same value (lane 0 need not be active in a divergent wave)
-        owner[b1] = i;
-        bestIdx2[i] = b1;
-        ++nmatches;
-        __threadfence_block();
-      }
-    }
-    __syncthreads();
-  }
-  if (lane == 0) *nmatchesOut = nmatches;
-}
-
-// ---------------------------------------------------------------------------
 // Frame::ComputeStereoFromRGBD (Frame.cc:1309-1331): depth of every left keypoint from a registered float
 // depth image, mvuRight = x - bf / d.  (cv::Mat::at<float>(v, u) with float arguments truncates them.)
 // ---------------------------------------------------------------------------
@@ -743,12 +555,15 @@ __global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const floa
 }
 
 // ---------------------------------------------------------------------------
-// Two-phase form of the two projection searches (used when the frame's keypoints fit the LDS owner table).
+// The two projection searches: SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:2179-2323) and
+// SearchByProjection(Frame, MapPoints) (:44-143, rectified stereo branch).
 // Which keypoints a query may take (grid window, pyramid levels, radius, uRight gate) and their Hamming distances do
 // not depend on the other queries; only "already taken" does.  Phase 1 (one wave per query, all queries in parallel)
 // lists the candidates of every query as (distance, visiting order, index) keys; phase 2 (one wave, queries in
-// order) takes the smallest key whose keypoint is still free — the reference's running minimum in visiting order —
-// with the owner table in LDS and the next query's keys already in flight.
+// order, because a keypoint taken by an earlier query is not available to later ones) takes the smallest key whose
+// keypoint is still free — the reference's running minimum in visiting order — with the owner table in LDS and the
+// next query's keys already in flight.  A frame whose keypoints do not fit the LDS owner table runs phase 2 alone,
+// with the owner table in global memory and one scan of the frame per query (proj_assign_dev).
 // ---------------------------------------------------------------------------
 
 __device__ __forceinline__ bool proj_window(const pli_proj_query& Q, float minX, float maxX, float minY, float maxY,
@@ -828,8 +643,19 @@ __global__ __launch_bounds__(64) void k_proj_candidates(const pli_proj_query* __
                       candKeys, candCount);
 }
 
-// mode 0: SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:2179-2323); mode 1: (Frame, MapPoints) (:44-143)
-// owner: ncur ints of LDS: -1 free, else the query that took the keypoint (INT_MAX: occupied before)
+// The projection searches keep a match out of the rotation histogram, and reject it in the filter, when its bin lies outside
+// 0..HISTO_LENGTH-1 (angles outside [0, 360)): -1
+__device__ __forceinline__ int proj_rot_bin(float qAngle, float kpAngle) {
+  const int bin = rot_bin(qAngle, kpAngle);
+  return (bin >= 0 && bin < HISTO_LENGTH) ? bin : -1;
+}
+
+// The ordered phase of both searches, one wave.  mode 0: SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:2179-2323);
+// mode 1: (Frame, MapPoints) (:44-143).
+// owner: ncur ints: -1 free, else the query that took the keypoint (INT_MAX: occupied before).  kOwnerInLds says where the caller
+// keeps them; the only difference is the fence that orders a query's owner store before the next query's owner loads.
+// candCount null: no candidate lists, every query scans the frame.
+template <bool kOwnerInLds>
 __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_proj_query* __restrict__ q,
                                                 const uint8_t* __restrict__ qdesc, int nq,
                                                 const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc,
@@ -838,49 +664,48 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
                                                 int checkOri, float nnratio, const unsigned long long* __restrict__ candKeys,
                                                 const int* __restrict__ candCount, int* __restrict__ bestIdx2,
                                                 int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2 /* mode 0, or null */) {
-  __shared__ int hist[30];
-  __shared__ int keep[30];
+  __shared__ int hist[HISTO_LENGTH];
+  __shared__ int keep[HISTO_LENGTH];
   const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX));
   const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(maxY, minY));
   for (int i = lane; i < ncur; i += 64) owner[i] = (occupied && occupied[i]) ? INT_MAX : -1;
   for (int i = lane; i < nq; i += 64) bestIdx2[i] = -1;
-  if (lane < 30) hist[lane] = 0;
+  if (lane < HISTO_LENGTH) hist[lane] = 0;
   __syncthreads();
   int nmatches = 0;
-  int cntNext = nq > 0 ? candCount[0] : 0;
+  int cntNext = !candCount ? -1 : nq > 0 ? candCount[0] : 0;
   unsigned long long keyNext = (nq > 0 && lane < cntNext) ? candKeys[lane] : ~0ull;
   for (int i = 0; i < nq; ++i) {
     const int cnt = cntNext;
     unsigned long long key = keyNext;
-    if (i + 1 < nq) {                                   // the next query's keys travel while this one is decided
+    if (candCount && i + 1 < nq) {                      // the next query's keys travel while this one is decided
       cntNext = candCount[i + 1];
       keyNext = lane < cntNext ? candKeys[(int64_t)(i + 1) * PROJ_K + lane] : ~0ull;
     }
-    unsigned long long k1 = ~0ull, k2 = ~0ull;
+    WaveTop2 top;
     if (cnt >= 0) {
       if (key != ~0ull && owner[(int)(key & 0xFFFFFFFull)] >= 0) key = ~0ull;
-      k1 = key;
-    } else {                                            // more than PROJ_K candidates: scan the frame for this query
+      top.push(key);
+    } else {                                            // no list, or more than PROJ_K candidates: scan the frame for this query
       const pli_proj_query Q = q[i];
       int c0, c1, r0, r1;
       if (proj_window(Q, minX, maxX, minY, maxY, gwInv, ghInv, mode == 0, c0, c1, r0, r1)) {
         uint64_t dq[4];
         load_desc(qdesc + (int64_t)i * 32, dq);
         for (int i2 = lane; i2 < ncur; i2 += 64) {
-          if (owner[i2] >= 0) continue;
           const unsigned long long kk = proj_key(Q, dq, i2, kp, desc, uright, minX, minY, gwInv, ghInv, c0, c1, r0, r1);
-          if (kk < k1) { k2 = k1; k1 = kk; }
-          else if (kk < k2) k2 = kk;
+          // not a candidate (~0), or all 256 bits differ: never below the reference's initial bestDist = bestDist2 = 256
+          if ((int)(kk >> 40) >= 256 || owner[i2] >= 0) continue;
+          top.push(kk);
         }
       }
     }
-    const unsigned long long m1 = wave_min_u64(k1);
+    const unsigned long long m1 = top.min1();
     if (m1 != ~0ull && (int)(m1 >> 40) <= 100) {
       const int b1 = (int)(m1 & 0xFFFFFFFull);
       bool accept = true;
       if (mode == 1) {
-        const unsigned long long c2 = (k1 == m1) ? k2 : k1;
-        const unsigned long long m2 = wave_min_u64(c2);
+        const unsigned long long m2 = top.min2(m1);
         const int bestDist = (int)(m1 >> 40), bestLevel = kp[b1].octave;
         int bestDist2 = 256, bestLevel2 = -1;
         if (m2 != ~0ull) { bestDist2 = (int)(m2 >> 40); bestLevel2 = kp[(int)(m2 & 0xFFFFFFFull)].octave; }
@@ -892,31 +717,26 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
         if (mode == 1 || !(q[i].valid & 2)) owner[b1] = i;
         bestIdx2[i] = b1;
         if (mode == 0 && checkOri && lane == 0) {
-          float rot = __fsub_rn(q[i].angle, kp[b1].angle);
-          if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-          int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-          if (bin == 30) bin = 0;
-          if (bin >= 0 && bin < 30) hist[bin]++;
+          const int bin = proj_rot_bin(q[i].angle, kp[b1].angle);
+          if (bin >= 0) hist[bin]++;
         }
         ++nmatches;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // single wave: LDS is executed in order
+    if (kOwnerInLds) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // single wave: LDS is executed in order
+    } else {
+      __threadfence_block();                                   // global memory: the store is visible before the next query's loads
+      __syncthreads();
+    }
   }
   __syncthreads();
   if (mode == 0) {
     if (checkOri) {
       if (lane == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-          const int s = hist[i];
-          if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-          else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-          else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-        for (int i = 0; i < 30; ++i) keep[i] = (i == ind1 || i == ind2 || i == ind3);
+        int ind1, ind2, ind3;
+        three_maxima(hist, ind1, ind2, ind3);
+        for (int i = 0; i < HISTO_LENGTH; ++i) keep[i] = (i == ind1 || i == ind2 || i == ind3);
       }
       __syncthreads();
     }
@@ -926,11 +746,8 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
       const int b = bestIdx2[i];
       if (rawIdx2) rawIdx2[i] = b;
       if (b < 0 || !checkOri) continue;
-      float rot = __fsub_rn(q[i].angle, kp[b].angle);
-      if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-      int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-      if (bin == 30) bin = 0;
-      if (!(bin >= 0 && bin < 30 && keep[bin])) { bestIdx2[i] = -1; ++removed; }
+      const int bin = proj_rot_bin(q[i].angle, kp[b].angle);
+      if (bin < 0 || !keep[bin]) { bestIdx2[i] = -1; ++removed; }
     }
     removed = wave_sum_i32(removed);
     nmatches -= removed;
@@ -938,6 +755,7 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
   if (lane == 0) *nmatchesOut = nmatches;
 }
 
+// frames of up to PROJ_LDS_KEYPOINTS keypoints, after k_proj_candidates; LDS: ncur ints
 __global__ __launch_bounds__(64) void k_proj_assign(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq,
                                                     const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc,
                                                     const float* __restrict__ uright, const uint8_t* __restrict__ occupied,
@@ -946,8 +764,20 @@ __global__ __launch_bounds__(64) void k_proj_assign(const pli_proj_query* __rest
                                                     const int* __restrict__ candCount, int* __restrict__ bestIdx2,
                                                     int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2) {
   extern __shared__ int owner[];
-  proj_assign_dev(threadIdx.x, owner, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, mode, checkOri, nnratio,
-                  candKeys, candCount, bestIdx2, nmatchesOut, rawIdx2);
+  proj_assign_dev<true>(threadIdx.x, owner, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, mode, checkOri,
+                        nnratio, candKeys, candCount, bestIdx2, nmatchesOut, rawIdx2);
+}
+
+// larger frames: no candidate lists, the owner table in global memory
+__global__ __launch_bounds__(64) void k_proj_assign_scan(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc,
+                                                         int nq, const pli_keypoint* __restrict__ kp,
+                                                         const uint8_t* __restrict__ desc, const float* __restrict__ uright,
+                                                         const uint8_t* __restrict__ occupied, int ncur, float minX, float maxX,
+                                                         float minY, float maxY, int mode, int checkOri, float nnratio,
+                                                         int* __restrict__ owner /* ncur */, int* __restrict__ bestIdx2,
+                                                         int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2) {
+  proj_assign_dev<false>(threadIdx.x, owner, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, mode, checkOri,
+                         nnratio, nullptr, nullptr, bestIdx2, nmatchesOut, rawIdx2);
 }
 
 // ---------------------------------------------------------------------------
@@ -982,11 +812,11 @@ __global__ __launch_bounds__(64) void k_proj_assign_fisheye(
   auto search = [&](int i, const pli_proj_query* q, const pli_keypoint* kp, const uint8_t* desc, int ncur, const int* own,
                     const unsigned long long* keys, const int* cnts, int& b1) -> int {
     const int cnt = cnts[i];
-    unsigned long long k1 = ~0ull, k2 = ~0ull;
+    WaveTop2 top;
     if (cnt >= 0) {
       unsigned long long key = lane < cnt ? keys[(int64_t)i * PROJ_K + lane] : ~0ull;
       if (key != ~0ull && own[(int)(key & 0xFFFFFFFull)] >= 0) key = ~0ull;
-      k1 = key;
+      top.push(key);
     } else {                                             // more than PROJ_K candidates: scan the camera for this query
       const pli_proj_query Q = q[i];
       int c0, c1, r0, r1;
@@ -995,17 +825,14 @@ __global__ __launch_bounds__(64) void k_proj_assign_fisheye(
         load_desc(qdesc + (int64_t)i * 32, dq);
         for (int i2 = lane; i2 < ncur; i2 += 64) {
           if (own[i2] >= 0) continue;
-          const unsigned long long kk = proj_key(Q, dq, i2, kp, desc, noUright, minX, minY, gwInv, ghInv, c0, c1, r0, r1);
-          if (kk < k1) { k2 = k1; k1 = kk; }
-          else if (kk < k2) k2 = kk;
+          top.push(proj_key(Q, dq, i2, kp, desc, noUright, minX, minY, gwInv, ghInv, c0, c1, r0, r1));
         }
       }
     }
-    const unsigned long long m1 = wave_min_u64(k1);
+    const unsigned long long m1 = top.min1();
     if (m1 == ~0ull || (int)(m1 >> 40) > 100) return 0;
     b1 = (int)(m1 & 0xFFFFFFFull);
-    const unsigned long long c2 = (k1 == m1) ? k2 : k1;
-    const unsigned long long m2 = wave_min_u64(c2);
+    const unsigned long long m2 = top.min2(m1);
     const int bestDist = (int)(m1 >> 40), bestLevel = kp[b1].octave;
     int bestDist2 = 256, bestLevel2 = -1;
     if (m2 != ~0ull) { bestDist2 = (int)(m2 >> 40); bestLevel2 = kp[(int)(m2 & 0xFFFFFFFull)].octave; }
@@ -1128,7 +955,7 @@ __global__ __launch_bounds__(64) void k_track_assign(const uint8_t* __restrict__
   const int nq = reinterpret_cast<const int*>(last + tp.offCounts)[0], ncur = reinterpret_cast<const int*>(cur + tp.offCounts)[0];
   int* counts = reinterpret_cast<int*>(out + tp.toffCounts);
   if (threadIdx.x == 0) counts[0] = nq;
-  proj_assign_dev(threadIdx.x, owner, qAll + (int64_t)frame * tp.kpCap, last + tp.offDesc0, nq,
+  proj_assign_dev<true>(threadIdx.x, owner, qAll + (int64_t)frame * tp.kpCap, last + tp.offDesc0, nq,
                   reinterpret_cast<const pli_keypoint*>(cur + tp.offKp0), cur + tp.offDesc0,
                   reinterpret_cast<const float*>(cur + tp.offUr), nullptr, ncur, tp.minX, tp.maxX, tp.minY, tp.maxY, 0, tp.checkOri, 0.f,
                   candKeysAll + (int64_t)frame * tp.kpCap * PROJ_K, candCountAll + (int64_t)frame * tp.kpCap,
@@ -1157,17 +984,13 @@ __global__ __launch_bounds__(256) void k_track_lines(const uint8_t* __restrict__
     for (int i = wv; i < nq; i += 4) {
       uint64_t dq[4];
       load_desc(q + (int64_t)i * 32, dq);
-      unsigned long long k1 = ~0ull, k2 = ~0ull;
+      WaveTop2 top;
       for (int j = lane; j < nt; j += 64) {
         uint64_t dt[4];
         load_desc(t + (int64_t)j * 32, dt);
-        const unsigned long long key = ((unsigned long long)hamming256(dq, dt) << 32) | (unsigned)j;
-        if (key < k1) { k2 = k1; k1 = key; }
-        else if (key < k2) k2 = key;
+        top.push(((unsigned long long)hamming256(dq, dt) << 32) | (unsigned)j);
       }
-      const unsigned long long m1 = wave_min_u64(k1);
-      const unsigned long long c2 = (k1 == m1) ? k2 : k1;
-      const unsigned long long m2 = wave_min_u64(c2);
+      const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
       if (lane == 0) {
         int r = -1;
         if (nt >= 2 && (float)(int)(m1 >> 32) < __fmul_rn((float)(int)(m2 >> 32), tp.nnrLines)) r = (int)(m1 & 0xFFFFFFFFu);
@@ -1247,10 +1070,10 @@ __global__ __launch_bounds__(64) void k_bow_descend(const uint8_t* __restrict__ 
 //                      keyframe feature; the lanes hold the node's frame candidates (looping over more than 64).  The reference's
 //                      running best / second best (strict <: ties keep the first listed, the lowest index) are the two smallest
 //                      (distance, frame index) keys.  Which keyframe feature took a frame feature lives in LDS; the 30-bin
-//                      rotation histogram takes LDS atomics, and thread 0 runs ComputeThreeMaxima (:2449-2490) before all
+//                      rotation histogram takes LDS atomics, and thread 0 runs three_maxima before all
 //                      threads write the row with the filter applied.
 // ---------------------------------------------------------------------------
-constexpr int BOW_TH_LOW = 50, BOW_HISTO = 30;
+constexpr int BOW_TH_LOW = 50;
 
 __device__ __forceinline__ int pow2_ceil(int m) {
   int n = 1;
@@ -1285,13 +1108,10 @@ __device__ __forceinline__ int bow_lower_bound(const uint32_t* a, int lo, int hi
   return lo;
 }
 
-// the histogram bin of a match (ORBmatcher.cc:405-411): rot / 30 lies in [0, 12] for angles in [0, 360), so bins 0..12 only
+// SearchByBoW and SearchForTriangulation clamp a bin outside 0..HISTO_LENGTH-1 (the caller checks the angles; this only keeps
+// the histogram index in range)
 __device__ __forceinline__ int bow_rot_bin(float kfAngle, float fAngle) {
-  float rot = __fsub_rn(kfAngle, fAngle);
-  if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-  int bin = (int)roundf(__fmul_rn(rot, 1.0f / BOW_HISTO));
-  if (bin == BOW_HISTO) bin = 0;
-  return min(max(bin, 0), BOW_HISTO - 1);       // (the caller checks the angles; this only keeps the LDS index in range)
+  return min(max(rot_bin(kfAngle, fAngle), 0), HISTO_LENGTH - 1);
 }
 
 // nf <= 8192; LDS: pow2_ceil(nf) * 6 bytes
@@ -1360,18 +1180,15 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
         const int j = (int)(key[q] & 0xFFFFu);
         uint64_t dk[4];
         load_desc(kfDesc + (int64_t)(base + j) * 32, dk);
-        unsigned long long k1 = ~0ull, k2 = ~0ull;
+        WaveTop2 top;
         for (int t = (int)lo + lane; t < hi; t += 64) {
           const int fi = sIdx[t];
           if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319)
           uint64_t df[4];
           load_desc(fDesc + (int64_t)fi * 32, df);
-          const unsigned long long kk = ((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi;
-          if (kk < k1) { k2 = k1; k1 = kk; }
-          else if (kk < k2) k2 = kk;
+          top.push(((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi);
         }
-        const unsigned long long m1 = wave_min_u64(k1);
-        const unsigned long long m2 = wave_min_u64(k1 == m1 ? k2 : k1);
+        const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
         if (m1 == ~0ull) continue;
         const int bestDist1 = (int)(m1 >> 32), bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
         if (bestDist1 <= BOW_TH_LOW && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
@@ -1389,16 +1206,8 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
   if (tid == 0) {
     int total = misc[1], ind1 = -1, ind2 = -1, ind3 = -1;
     if (checkOri) {
-      int max1 = 0, max2 = 0, max3 = 0;
-      for (int i = 0; i < BOW_HISTO; ++i) {
-        const int s = hist[i];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-      }
-      if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-      else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-      for (int i = 0; i < BOW_HISTO; ++i)
+      three_maxima(hist, ind1, ind2, ind3);
+      for (int i = 0; i < HISTO_LENGTH; ++i)
         if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
     }
     misc[2] = ind1; misc[3] = ind2; misc[4] = ind3;
@@ -1435,7 +1244,7 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
 //                  sorted list, the lanes stride over it (Hamming distance, TH_LOW, the epipole gate :1089-1097, the epipolar
 //                  gate Pinhole.cpp:130-143 on the host's F12), a wave minimum of the key picks the winner; lane 0 writes
 //                  vMatches12[idx1] and adds to the neighbour's 30-bin rotation histogram and counter (global atomics).
-//   k_tri_finish   (mbCheckOrientation only) one workgroup per neighbour: ComputeThreeMaxima (:2449-2490) on the histogram, then
+//   k_tri_finish   (mbCheckOrientation only) one workgroup per neighbour: three_maxima on the histogram, then
 //                  the row is filtered (a match's bin is recomputed from the two angles) and the return value corrected.
 // ---------------------------------------------------------------------------
 constexpr int TRI_STAT = 32;                                     // ints per neighbour: 30 bins, [30] the match counter
@@ -1548,16 +1357,9 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
   const int kf = blockIdx.x, base = kfOff[kf];
   int* hist = stat + kf * TRI_STAT;
   if (threadIdx.x == 0) {
-    int total = hist[30], ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < BOW_HISTO; ++i) {
-      const int s = hist[i];
-      if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-      else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-      else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-    for (int i = 0; i < BOW_HISTO; ++i)
+    int total = hist[30], ind1, ind2, ind3;
+    three_maxima(hist, ind1, ind2, ind3);
+    for (int i = 0; i < HISTO_LENGTH; ++i)
       if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
     keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
     hist[30] = total;
@@ -1573,10 +1375,6 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
   }
 }
 
-}  // namespace pli
-
-namespace pli {
-
 // ---------------------------------------------------------------------------
 // SURVEY §8(f) row 4, fisheye stereo.
 // Frame::ComputeStereoFishEyeMatches (Frame.cc:1577-1618): after knnMatch(k = 2) of the lapping-area descriptors (k_knn2),
@@ -1588,11 +1386,6 @@ namespace pli {
 // hypot as sqrt(p*p + beta*beta)), libm calls on floats in double and rounded.  Same statement as the checker's
 // (match_oracle.hpp kb8TriangulateMatches), operation for operation.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float mat_dot3(const float* a, int sa, const float* b, double alpha, double c) {
-  const double d = (double)a[0] * (double)b[0] + (double)a[sa] * (double)b[1] + (double)a[2 * sa] * (double)b[2];
-  return (float)(alpha * d + c);
-}
-
 __device__ __forceinline__ void kb8_unproject(const Kb8& c, float u, float v, float r[3]) {
   const float pwx = (u - c.cx) / c.fx, pwy = (v - c.cy) / c.fy;
   float scale = 1.f;
@@ -1711,7 +1504,7 @@ __global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* 
   float r1[3], r2[3], r21[3];
   kb8_unproject(c1, k1.x, k1.y, r1);
   kb8_unproject(c2, k2.x, k2.y, r2);
-  for (int a = 0; a < 3; ++a) r21[a] = mat_dot3(R12 + 3 * a, 1, r2, 1.0, 0.0);
+  for (int a = 0; a < 3; ++a) r21[a] = cvmat_dot3(R12 + 3 * a, 1, r2, 1.0, 0.0);
   const double dot = (double)r1[0] * r21[0] + (double)r1[1] * r21[1] + (double)r1[2] * r21[2];
   const double n1 = sqrt((double)r1[0] * r1[0] + (double)r1[1] * r1[1] + (double)r1[2] * r1[2]);
   const double n2 = sqrt((double)r21[0] * r21[0] + (double)r21[1] * r21[1] + (double)r21[2] * r21[2]);
@@ -1720,7 +1513,7 @@ __global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* 
   // Tcw1 = [I | 0], Tcw2 = [R21 | t21] with R21 = R12^T, t21 = -R21 t12
   float R21[9], t21[3];
   for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) R21[3 * a + b] = R12[3 * b + a];
-  for (int a = 0; a < 3; ++a) t21[a] = mat_dot3(R21 + 3 * a, 1, t12, -1.0, 0.0);
+  for (int a = 0; a < 3; ++a) t21[a] = cvmat_dot3(R21 + 3 * a, 1, t12, -1.0, 0.0);
   const float T1[3][4] = {{1.f, 0.f, 0.f, 0.f}, {0.f, 1.f, 0.f, 0.f}, {0.f, 0.f, 1.f, 0.f}};
   float T2[3][4];
   for (int a = 0; a < 3; ++a) { T2[a][0] = R21[3 * a]; T2[a][1] = R21[3 * a + 1]; T2[a][2] = R21[3 * a + 2]; T2[a][3] = t21[a]; }
@@ -1744,7 +1537,7 @@ __global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* 
   const float ex1 = u1 - k1.x, ey1 = v1 - k1.y;
   if ((double)(ex1 * ex1 + ey1 * ey1) > 5.991 * (double)sigma2[k1.octave]) return;
   float x32[3];
-  for (int a = 0; a < 3; ++a) x32[a] = mat_dot3(R21 + 3 * a, 1, x3, 1.0, (double)t21[a]);
+  for (int a = 0; a < 3; ++a) x32[a] = cvmat_dot3(R21 + 3 * a, 1, x3, 1.0, (double)t21[a]);
   float u2, v2;
   kb8_project(c2, x32, u2, v2);
   const float ex2 = u2 - k2.x, ey2 = v2 - k2.y;

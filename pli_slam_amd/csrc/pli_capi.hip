@@ -2442,7 +2442,7 @@ pli_status pli_match_nnr(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_
 
 // Both projection searches: mode 0 frame-to-frame (ORBmatcher.cc:2179-2323), mode 1 local map (:44-143).
 // Frames whose keypoints fit the LDS owner table take the two-phase form (candidates in parallel, then the ordered
-// assignment); larger ones the single-wave kernels that scan the frame per query.
+// assignment); larger ones the ordered assignment alone, owner table in global memory, which scans the frame per query.
 constexpr int PROJ_LDS_KEYPOINTS = 15360;
 
 static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
@@ -2455,7 +2455,7 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
   if (ncur >= (1 << 28)) { g_err = "too many keypoints"; return PLI_ERR_INVALID; }
   HIPCHK(hipSetDevice(c->device));
   const int nc = std::max(ncur, 1);
-  const bool twoPhase = ncur <= PROJ_LDS_KEYPOINTS;
+  const bool ownerInLds = ncur <= PROJ_LDS_KEYPOINTS;
   for (int i = 0; i < nq; ++i)
     if (mode == 0 && (q[i].valid & ~3)) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
   ScratchPlan plan;
@@ -2464,12 +2464,12 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
   auto dk = plan.add<pli_keypoint>(ncur);
   auto ddsc = plan.add<uint8_t>((size_t)ncur * 32);
   auto du = plan.add<float>(ncur);
-  auto down = plan.add<int>(ncur);
+  auto down = plan.add<int>(ownerInLds ? 0 : ncur);
   auto dbest = plan.add<int>(nq);
   auto draw = plan.add<int>(nq);
   auto docc = plan.add<uint8_t>(ncur);
-  auto dkeys = plan.add<unsigned long long>(twoPhase ? (size_t)nq * PROJ_K : 0);
-  auto dcc = plan.add<int>(twoPhase ? nq : 0);
+  auto dkeys = plan.add<unsigned long long>(ownerInLds ? (size_t)nq * PROJ_K : 0);
+  auto dcc = plan.add<int>(ownerInLds ? nq : 0);
   auto dcnt = plan.add<int>(1);
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
@@ -2481,7 +2481,7 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
   if (occupied) HIPCHK(upload(c, docc, occupied, ncur));
   const uint8_t* occ = (occupied && ncur > 0) ? (const uint8_t*)docc : (const uint8_t*)nullptr;
   int* rawOut = (mode == 0 && raw) ? (int*)draw : (int*)nullptr;
-  if (twoPhase) {
+  if (ownerInLds) {
     // a second-best farther than 100 / nnratio can no longer reject a best of <= 100 (ORBmatcher.cc:124-126)
     int limit = 100;
     if (mode == 1) limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
@@ -2489,12 +2489,9 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
            mode == 0 ? 1 : 0, limit, dkeys, dcc);
     LAUNCH(c, "k_proj_assign", k_proj_assign, dim3(1), dim3(64), (size_t)nc * 4, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
            minY, maxY, mode, checkOri, nnratio, dkeys, dcc, dbest, dcnt, rawOut);
-  } else if (mode == 0) {
-    LAUNCH(c, "k_search_by_projection", k_search_by_projection, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, ncur, minX, maxX,
-           minY, maxY, checkOri, down, dbest, dcnt, occ, rawOut);
   } else {
-    LAUNCH(c, "k_search_local_map", k_search_local_map, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
-           minY, maxY, nnratio, down, dbest, dcnt);
+    LAUNCH(c, "k_proj_assign_scan", k_proj_assign_scan, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
+           minY, maxY, mode, checkOri, nnratio, down, dbest, dcnt, rawOut);
   }
   HIPCHK(download(c, best, dbest, nq));
   if (rawOut) HIPCHK(download(c, raw, draw, nq));
