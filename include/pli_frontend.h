@@ -562,6 +562,56 @@ pli_status pli_search_for_triangulation(pli_ctx* ctx, const pli_keypoint* kp1, c
                                         const float* F12, const float* ep, int32_t only_stereo, int32_t coarse,
                                         int32_t check_orientation, int32_t* matches12, int32_t* nmatches);
 
+/* The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) ORBmatcher.cc:1399-1609 (the branch bRight == false,
+ * NLeft == -1, keypoints = mvKeysUn) and of the Sim3 overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) :1611-1733, for nmp map
+ * points against nkf keyframes in one call (LocalMapping::SearchInNeighbors, LocalMapping.cc:743-749 and :776;
+ * LoopClosing::SearchAndFuse, LoopClosing.cc:2097-2165).  The projection runs on the device, with the cv::Mat conventions of the
+ * reference's expressions (a matrix product: double accumulation, one rounding; cv::norm and Mat::dot in double; the rest float,
+ * in the written order, nothing fused).  What follows the search in the reference (Replace / AddObservation / AddMapPoint
+ * :1572-1594, and the gates isBad() and IsInKeyFrame at the time a point's turn comes) is sequential and stays with the caller:
+ * PliORBmatcher::Fuse replays it. */
+typedef struct pli_fuse_point {   /* 40 bytes */
+  float pos[3];        /* GetWorldPos() :1435 */
+  float normal[3];     /* GetNormal() :1490 */
+  float min_dist_inv;  /* GetMinDistanceInvariance() :1478 */
+  float max_dist_inv;  /* GetMaxDistanceInvariance() :1477 */
+  float max_dist;      /* mfMaxDistance, read by PredictScale (MapPoint.cc:449-464); finite and > 0 where valid */
+  int32_t valid;       /* 0 = skip for every keyframe (!pMP :1424, isBad() :1432); also a point whose max_dist is not finite
+                          and positive (the reference converts a NaN to int there) */
+} pli_fuse_point;
+
+typedef struct pli_fuse_camera {
+  float fx, fy, cx, cy; /* pKF->fx .. cy :1419-1422 (Pinhole::project, Pinhole.cpp:30-33) */
+  float bf;             /* pKF->mbf :1423 */
+  float min_x, max_x, min_y, max_y; /* mnMinX .. mnMaxY: KeyFrame::IsInImage (KeyFrame.cc:927-930) and the 64 x 48 grid */
+} pli_fuse_camera;
+
+/* mp / mp_desc: nmp points and their GetDescriptor() rows (32 bytes each).  Keyframe k owns rows kf_off[k] .. kf_off[k+1]-1 of
+ * kf_kp (mvKeysUn: pt and octave are read), kf_desc (mDescriptors) and kf_uright (mvuRight; read only with reproj_gate, may be
+ * NULL without); kf_off[0] = 0, non-decreasing.  kf_pose: nkf x 15 floats - Rcw row major (GetRotation()), tcw
+ * (GetTranslation()), Ow (GetCameraCenter(): the stored value, not recomputed).  skip: nkf x nmp, may be NULL; != 0 leaves the
+ * pair out (IsInKeyFrame(pKF) :1437, spAlreadyFound.count(pMP) :1639).  cam: every keyframe of a call shares it, as every
+ * keyframe shares the context's mvScaleFactors / mvInvLevelSigma2 (octaves index them and must lie in [0, orb_nlevels)).
+ * th: the radius is th * mvScaleFactors[level] :1502.
+ * level_ratio: orb_nlevels - 1 floats, non-decreasing.  MapPoint::PredictScale's ceil(log(ratio) / mfLogScaleFactor) leaves the
+ * overload of log(float) to the integrator's toolchain, and a device logarithm is not the host's; so the host supplies, for
+ * n = 0 .. orb_nlevels-2, the largest float ratio for which ITS expression (with its clamps) gives a level <= n (found by
+ * bisection over float bit patterns; pli_cpp.hpp fuseLevelRatio), and the device's level is the number of n with
+ * ratio > level_ratio[n].
+ * reproj_gate != 0: the chi-square gate :1533-1557 (7.8 where kf_uright >= 0, 5.99 otherwise) of the first overload; 0: the Sim3
+ * overload, which has none.
+ * best_idx: nkf x nmp, bestIdx where bestDist <= TH_LOW (50), else -1: the row within the keyframe; the strict minimum in the
+ * visiting order of KeyFrame::GetFeaturesInArea (KeyFrame.cc:881-925).  best_dist (may be NULL): bestDist, 256 where no candidate
+ * passed the gates.
+ * Errors: PLI_ERR_INVALID for null pointers, an octave outside [0, orb_nlevels), a decreasing kf_off, a decreasing or NaN
+ * level_ratio; PLI_ERR_CAPACITY for a keyframe with more than PLI_BOW_MAX_FEATURES rows (nothing is truncated).  nmp and nkf are
+ * bounded by device memory only; nkf == 0, nmp == 0 and empty keyframes are valid.  The number of kernel launches does not depend
+ * on nkf or nmp. */
+pli_status pli_fuse_search(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t* mp_desc, int32_t nmp, int32_t nkf,
+                           const int32_t* kf_off, const pli_keypoint* kf_kp, const uint8_t* kf_desc, const float* kf_uright,
+                           const float* kf_pose, const uint8_t* skip, const pli_fuse_camera* cam, float th,
+                           const float* level_ratio, int32_t reproj_gate, int32_t* best_idx, int32_t* best_dist);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

@@ -13,6 +13,9 @@
 //   ORB_SLAM3::ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse)   include/ORBmatcher.h,
 //                                                             src/ORBmatcher.cc:965-1206 (no second cameras; + a batch form for
 //                                                             LocalMapping::CreateNewMapPoints' neighbour loop)
+//   ORB_SLAM3::ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)   include/ORBmatcher.h,
+//                                                             src/ORBmatcher.cc:1399-1609, :1611-1733 (no second cameras; + a batch
+//                                                             form for LocalMapping::SearchInNeighbors' loop over target keyframes)
 //
 // Frame.cc / Tracking.cc keep calling these names unchanged; INTEGRATION.md lists the edits (swap the headers).
 //
@@ -829,9 +832,247 @@ class PliORBmatcher {
     }
   }
 
+  // ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight), ORBmatcher.cc:
+  // 1399-1609, for a keyframe of one pinhole camera (bRight == false, NLeft == -1): the projection and the window search run on
+  // the device (pli_fuse_search), :1572-1594 (Replace / AddObservation / AddMapPoint) and the gates isBad() / IsInKeyFrame here.
+  // KeyFrameT needs N, NLeft, mvKeysUn, mvuRight, mDescriptors, fx, fy, cx, cy, mbf, mnMinX, mnMaxX, mnMinY, mnMaxY,
+  // mnScaleLevels, mfLogScaleFactor, GetRotation(), GetTranslation(), GetCameraCenter(), GetMapPoint(idx), AddMapPoint(pMP, idx)
+  // (and GetMapPoints() for the Sim3 form); MapPointT needs isBad(), IsInKeyFrame(pKF), GetWorldPos(), GetNormal(),
+  // GetMinDistanceInvariance(), GetMaxDistanceInvariance(), GetDescriptor(), Observations(), Replace(pMP), AddObservation(pKF,
+  // idx) and GetMaxDistance(): mfMaxDistance is protected in the reference's MapPoint, INTEGRATION.md gives the one-line accessor.
+  template <class KeyFrameT>
+  int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0, const bool bRight = false) {
+    if (bRight) throw std::logic_error("Fuse: the right camera of a two-camera keyframe (bRight) is not supported");
+    std::vector<int> nFused;
+    Fuse(std::vector<KeyFrameT*>(1, pKF), vpMapPoints, th, nFused);
+    return nFused[0];
+  }
+
+  // (not in the reference) The loop of LocalMapping::SearchInNeighbors, LocalMapping.cc:743-749 - Fuse(pKFi, vpMapPointMatches)
+  // for every target keyframe - with ONE device search for all targets.  nFused[k] and every side effect equal the reference's
+  // keyframe-after-keyframe loop exactly, although Fuse(KF_k) changes state that Fuse(KF_k+1) reads:
+  //   * the device searches with the state at entry; the keyframes are then replayed in order on the host, running :1572-1594;
+  //   * isBad() and IsInKeyFrame(pKF) are evaluated at replay time, when the point's turn comes, not taken from the uploaded
+  //     skip table (which only saves work: inside Fuse a good point never leaves a keyframe and a bad one never recovers);
+  //   * the point that survives a Replace has had ComputeDistinctiveDescriptors() run on it (MapPoint.cc:268), so its descriptor
+  //     may differ from the one that was searched: the 32 bytes are compared before and after every Replace performed here, and
+  //     before keyframe k is replayed every list point whose descriptor changed is searched again, in one call, against the
+  //     keyframes k..end.  (Inside keyframe k itself such a point is in the keyframe, so its result there is never read.)
+  //     Position, normal and the distances do not change inside Fuse.
+  // pnResearch (may be null): the number of such repeated searches.
+  template <class KeyFrameT>
+  void Fuse(const std::vector<KeyFrameT*>& vpTargetKFs, const std::vector<MapPointT*>& vpMapPoints, const float th,
+            std::vector<int>& nFused, int* pnResearch = nullptr) {
+    const int nkf = (int)vpTargetKFs.size(), nmp = (int)vpMapPoints.size();
+    nFused.assign(nkf, 0);
+    if (pnResearch) *pnResearch = 0;
+    if (nkf == 0) return;
+    FuseTables T;
+    for (int k = 0; k < nkf; ++k) {
+      KeyFrameT* pKF = vpTargetKFs[k];
+      const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
+      float pose[15];
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) pose[i * 3 + j] = R.template at<float>(i, j);
+        pose[9 + i] = t.template at<float>(i);
+        pose[12 + i] = Ow.template at<float>(i);
+      }
+      fuseGatherKeyFrame(pKF, pose, T);
+    }
+    std::vector<pli_fuse_point> pts(nmp);
+    std::vector<uint8_t> desc((size_t)nmp * 32, 0), skip((size_t)nkf * nmp, 0);
+    for (int i = 0; i < nmp; ++i) {
+      MapPointT* pMP = vpMapPoints[i];
+      pts[i] = fusePoint(pMP);
+      if (!pts[i].valid) continue;
+      std::memcpy(&desc[(size_t)i * 32], pMP->GetDescriptor().template ptr<uint8_t>(), 32);
+      for (int k = 0; k < nkf; ++k) skip[(size_t)k * nmp + i] = pMP->IsInKeyFrame(vpTargetKFs[k]) ? 1 : 0;
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
+    if (!fe) throw std::logic_error("Fuse: no extractor has run yet (no device context)");
+    const std::vector<float>& levelRatio = fuseLevelRatio(vpTargetKFs[0]);
+    std::vector<int> best;
+    fe->fuseSearch(pts.data(), desc.data(), nmp, nkf, T.off.data(), T.kp.data(), T.desc.data(), T.uright.data(), T.pose.data(),
+                   skip.data(), T.cam, th, levelRatio, true, best);
+    std::vector<uint8_t> changed(nmp, 0);
+    bool anyChanged = false;
+    for (int k = 0; k < nkf; ++k) {
+      KeyFrameT* pKF = vpTargetKFs[k];
+      if (anyChanged) {                         // the points whose descriptor a Replace changed, against the keyframes k..end
+        std::vector<int> which;
+        std::vector<pli_fuse_point> p2;
+        std::vector<uint8_t> d2;
+        for (int i = 0; i < nmp; ++i)
+          if (changed[i]) {
+            which.push_back(i);
+            p2.push_back(fusePoint(vpMapPoints[i]));
+            const size_t at = d2.size();
+            d2.resize(at + 32, 0);
+            if (p2.back().valid) std::memcpy(&d2[at], vpMapPoints[i]->GetDescriptor().template ptr<uint8_t>(), 32);
+            changed[i] = 0;
+          }
+        std::vector<int32_t> off2(T.off.begin() + k, T.off.end());
+        for (size_t j = off2.size(); j-- > 0;) off2[j] -= off2[0];
+        const size_t row0 = (size_t)T.off[k];
+        std::vector<int> b2;
+        fe->fuseSearch(p2.data(), d2.data(), (int)which.size(), nkf - k, off2.data(), T.kp.data() + row0, T.desc.data() + row0 * 32,
+                       T.uright.data() + row0, T.pose.data() + (size_t)k * 15, nullptr, T.cam, th, levelRatio, true, b2);
+        for (int kk = k; kk < nkf; ++kk)
+          for (size_t j = 0; j < which.size(); ++j) best[(size_t)kk * nmp + which[j]] = b2[(size_t)(kk - k) * which.size() + j];
+        anyChanged = false;
+        if (pnResearch) ++*pnResearch;
+      }
+      int n = 0;
+      for (int i = 0; i < nmp; ++i) {
+        MapPointT* pMP = vpMapPoints[i];
+        if (!pMP) continue;                                                  // :1424
+        if (pMP->isBad()) continue;                                          // :1432
+        if (pMP->IsInKeyFrame(pKF)) continue;                                // :1437
+        const int bestIdx = best[(size_t)k * nmp + i];
+        if (bestIdx < 0) continue;                                           // every other exit, and bestDist > TH_LOW
+        MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);                      // :1572-1594
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) {
+            MapPointT* survivor = pMPinKF->Observations() > pMP->Observations() ? pMPinKF : pMP;
+            uint8_t before[32];
+            std::memcpy(before, survivor->GetDescriptor().template ptr<uint8_t>(), 32);
+            if (survivor == pMPinKF) pMP->Replace(pMPinKF);
+            else pMPinKF->Replace(pMP);
+            if (std::memcmp(before, survivor->GetDescriptor().template ptr<uint8_t>(), 32) != 0)
+              for (int j = 0; j < nmp; ++j)
+                if (vpMapPoints[j] == survivor) { changed[j] = 1; anyChanged = true; }
+          }
+        } else {
+          pMP->AddObservation(pKF, bestIdx);
+          pKF->AddMapPoint(pMP, bestIdx);
+        }
+        n++;
+      }
+      nFused[k] = n;
+    }
+  }
+
+  // ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint),
+  // ORBmatcher.cc:1611-1733 (LoopClosing::SearchAndFuse).  The Sim3 decomposition :1620-1624 runs here (PARITY UNPINNED: OpenCV's
+  // arithmetic, by the conventions DESIGN.md §9 lists - Mat::dot sums in double, sqrt of that double rounded to float; Mat / s is
+  // (float)(x * (1.0 / s)); -Rcw.t() * tcw is one gemm with alpha = -1, one rounding).  No chi-square gate in this overload.
+  // Not batched over keyframes: the caller's own Replace runs between them.
+  template <class KeyFrameT>
+  int Fuse(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
+    double dd = 0.0;
+    for (int j = 0; j < 3; ++j) dd += (double)Scw.template at<float>(0, j) * (double)Scw.template at<float>(0, j);
+    const float scw = (float)std::sqrt(dd);
+    const double inv = 1.0 / (double)scw;
+    float pose[15];
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) pose[i * 3 + j] = (float)((double)Scw.template at<float>(i, j) * inv);
+      pose[9 + i] = (float)((double)Scw.template at<float>(i, 3) * inv);
+    }
+    for (int i = 0; i < 3; ++i)
+      pose[12 + i] = (float)(-1.0 * ((double)pose[i] * (double)pose[9] + (double)pose[3 + i] * (double)pose[10] + (double)pose[6 + i] * (double)pose[11]));
+    FuseTables T;
+    fuseGatherKeyFrame(pKF, pose, T);
+    const auto spAlreadyFound = pKF->GetMapPoints();
+    const int nmp = (int)vpPoints.size();
+    std::vector<pli_fuse_point> pts(nmp);
+    std::vector<uint8_t> desc((size_t)nmp * 32, 0), skip(nmp, 0);
+    for (int i = 0; i < nmp; ++i) {
+      pts[i] = fusePoint(vpPoints[i]);
+      if (!pts[i].valid) continue;
+      std::memcpy(&desc[(size_t)i * 32], vpPoints[i]->GetDescriptor().template ptr<uint8_t>(), 32);
+      skip[i] = spAlreadyFound.count(vpPoints[i]) ? 1 : 0;                  // :1639
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
+    if (!fe) throw std::logic_error("Fuse: no extractor has run yet (no device context)");
+    std::vector<int> best;
+    fe->fuseSearch(pts.data(), desc.data(), nmp, 1, T.off.data(), T.kp.data(), T.desc.data(), T.uright.data(), T.pose.data(), skip.data(),
+                   T.cam, th, fuseLevelRatio(pKF), false, best);
+    int nFused = 0;
+    for (int i = 0; i < nmp; ++i) {
+      const int bestIdx = best[i];
+      if (bestIdx < 0) continue;
+      MapPointT* pMP = vpPoints[i];
+      MapPointT* pMPinKF = pKF->GetMapPoint(bestIdx);                        // :1717-1728
+      if (pMPinKF) {
+        if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
+      } else {
+        pMP->AddObservation(pKF, bestIdx);
+        pKF->AddMapPoint(pMP, bestIdx);
+      }
+      nFused++;
+    }
+    return nFused;
+  }
+
+  // the level_ratio table the Fuse adapters hand to pli_fuse_search (tests read it)
+  template <class KeyFrameT>
+  const std::vector<float>& fuseLevelRatio(KeyFrameT* pKF) {
+    const int nlevels = pKF->mnScaleLevels;
+    const float logSf = pKF->mfLogScaleFactor;
+    if (mvFuseLevelRatio.empty() || mnFuseLevels != nlevels || mfFuseLogSf != logSf) {
+      // MapPoint::PredictScale, MapPoint.cc:457-461, as MapPoint.cc compiles it (it is `using namespace std`, so log(float) is
+      // whichever overload this toolchain selects there)
+      mvFuseLevelRatio = pli::Frontend::fuseLevelRatio(nlevels, [nlevels, logSf](float ratio) {
+        using namespace std;
+        if (!(ratio > 0.0f)) return 0;
+        if (std::isinf(ratio)) return nlevels - 1;
+        int nScale = ceil(log(ratio) / logSf);
+        if (nScale < 0) nScale = 0;
+        else if (nScale >= nlevels) nScale = nlevels - 1;
+        return nScale;
+      });
+      mnFuseLevels = nlevels;
+      mfFuseLogSf = logSf;
+    }
+    return mvFuseLevelRatio;
+  }
+
  protected:
+  struct FuseTables {
+    std::vector<int32_t> off = std::vector<int32_t>(1, 0);
+    std::vector<pli_keypoint> kp;
+    std::vector<uint8_t> desc;
+    std::vector<float> uright, pose;
+    pli_fuse_camera cam;
+    bool haveCam = false;
+  };
+  template <class KeyFrameT>
+  static void fuseGatherKeyFrame(KeyFrameT* pKF, const float pose[15], FuseTables& T) {
+    if (pKF->NLeft != -1) throw std::logic_error("Fuse: a keyframe of two cameras (NLeft != -1) is not supported");
+    const pli_fuse_camera cam = {pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, (float)pKF->mnMinX, (float)pKF->mnMaxX, (float)pKF->mnMinY,
+                                 (float)pKF->mnMaxY};
+    if (T.haveCam && std::memcmp(&cam, &T.cam, sizeof cam) != 0)
+      throw std::logic_error("Fuse: the target keyframes of one call must share the camera and the image bounds");
+    T.cam = cam;
+    T.haveCam = true;
+    const int n = pKF->N;
+    for (int i = 0; i < n; ++i) {
+      const cv::KeyPoint& k = pKF->mvKeysUn[i];
+      T.kp.push_back(pli_keypoint{k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave});
+      const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
+      T.desc.insert(T.desc.end(), d, d + 32);
+      T.uright.push_back(pKF->mvuRight[i]);
+    }
+    T.off.push_back(T.off.back() + n);
+    T.pose.insert(T.pose.end(), pose, pose + 15);
+  }
+  static pli_fuse_point fusePoint(MapPointT* pMP) {
+    pli_fuse_point P = {};
+    if (!pMP || pMP->isBad()) return P;
+    const cv::Mat p = pMP->GetWorldPos(), nrm = pMP->GetNormal();
+    for (int i = 0; i < 3; ++i) { P.pos[i] = p.template at<float>(i); P.normal[i] = nrm.template at<float>(i); }
+    P.min_dist_inv = pMP->GetMinDistanceInvariance();
+    P.max_dist_inv = pMP->GetMaxDistanceInvariance();
+    P.max_dist = pMP->GetMaxDistance();
+    P.valid = (std::isfinite(P.max_dist) && P.max_dist > 0.f) ? 1 : 0;      // (the reference converts a NaN to int there)
+    return P;
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
+  std::vector<float> mvFuseLevelRatio;
+  int mnFuseLevels = 0;
+  float mfFuseLogSf = 0.f;
 };
 
 }  // namespace ORB_SLAM3

@@ -152,6 +152,35 @@ class Frontend {
                                        kfStereo, F12, ep, onlyStereo ? 1 : 0, coarse ? 1 : 0, checkOrientation ? 1 : 0,
                                        matches12.data(), nmatches.data()));
   }
+  // The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reprojGate = false: the Sim3 overload
+  // :1611-1733) of nmp map points against nkf keyframes (include/pli_frontend.h pli_fuse_search): bestIdx (nkf x nmp) = the
+  // keyframe's row or -1.  levelRatio: fuseLevelRatio() of the extractor's configuration.
+  void fuseSearch(const pli_fuse_point* mp, const uint8_t* mpDesc, int nmp, int nkf, const int32_t* kfOff, const pli_keypoint* kfKp,
+                  const uint8_t* kfDesc, const float* kfUright, const float* kfPose, const uint8_t* skip, const pli_fuse_camera& cam,
+                  float th, const std::vector<float>& levelRatio, bool reprojGate, std::vector<int>& bestIdx) {
+    bestIdx.assign((size_t)nkf * nmp, -1);
+    check(pli_fuse_search(ctx_, mp, mpDesc, nmp, nkf, kfOff, kfKp, kfDesc, kfUright, kfPose, skip, &cam, th, levelRatio.data(),
+                          reprojGate ? 1 : 0, bestIdx.data(), nullptr));
+  }
+  // level_ratio of pli_fuse_search from the HOST's own MapPoint::PredictScale expression: levelOf(ratio) must be the tree's
+  // expression compiled by the tree's compiler (ceil(log(ratio) / mfLogScaleFactor) with its clamps), so that whichever overload
+  // of log its toolchain selects is the one the thresholds describe.  For n = 0 .. nlevels-2 the largest float for which
+  // levelOf gives a level <= n, by bisection over the bit patterns of the positive floats.
+  template <class LevelOf>
+  static std::vector<float> fuseLevelRatio(int nlevels, LevelOf levelOf) {
+    std::vector<float> out(nlevels > 1 ? nlevels - 1 : 0);
+    for (int n = 0; n + 1 < nlevels; ++n) {
+      uint32_t lo = 1u, hi = 0x7F800000u;                 // the smallest subnormal: level 0; +inf: the top level
+      while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        float r;
+        std::memcpy(&r, &mid, 4);
+        if (levelOf(r) <= n) lo = mid; else hi = mid;
+      }
+      std::memcpy(&out[n], &lo, 4);
+    }
+    return out;
+  }
   // Frame::ComputeStereoFromRGBD(imDepth) Frame.cc:1309 (depth: CV_32F, row stride in floats)
   void computeStereoFromRGBD(const float* depth, int64_t strideFloats, std::vector<float>& mvuRight, std::vector<float>& mvDepth) {
     mvuRight.assign(layout_.kp_cap, -1.f); mvDepth.assign(layout_.kp_cap, -1.f);

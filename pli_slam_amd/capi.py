@@ -29,6 +29,9 @@ KEYLINE_DT = np.dtype([("angle", "<f4"), ("class_id", "<i4"), ("octave", "<i4"),
 PROJ_QUERY_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("ur", "<f4"),
                           ("min_level", "<i4"), ("max_level", "<i4"), ("angle", "<f4"), ("valid", "<i4")])
 
+FUSE_POINT_DT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist_inv", "<f4"), ("max_dist_inv", "<f4"),
+                          ("max_dist", "<f4"), ("valid", "<i4")])
+
 PLI_OK = 0
 ERRORS = {-1: "PLI_ERR_INVALID", -2: "PLI_ERR_EMPTY_IMAGE", -3: "PLI_ERR_CAPACITY", -4: "PLI_ERR_HIP",
           -5: "PLI_ERR_NO_DEVICE", -6: "PLI_ERR_STATE"}
@@ -72,6 +75,12 @@ class TrackParams(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
                 ("th", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
                 ("mono", C.c_int32), ("check_orientation", C.c_int32), ("nnr_lines", C.c_float), ("reserved", C.c_int32)]
+
+
+class FuseCamera(C.Structure):
+    """pli_fuse_camera."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
 class TrackLayout(C.Structure):
@@ -163,6 +172,9 @@ _PROTOS = {
                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                  C.c_int32, C.c_void_p, C.c_void_p]),
+    "pli_fuse_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FuseCamera), C.c_float, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p]),
     "pli_prof_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "pli_prof_reset": (C.c_int32, [C.c_void_p]),
     "pli_prof_report": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int64]),

@@ -13,6 +13,7 @@
 //   k_track_queries/candidates/assign/lines   frame-to-frame track matching of a batch (pli_batch_track)
 //   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 //   k_tri_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
+//   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -1374,6 +1375,228 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
     if (b != ind1 && b != ind2 && b != ind3) row[i] = -1;
   }
 }
+
+// ---------------------------------------------------------------------------
+// The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, the branch bRight == false, NLeft == -1, keypoints = mvKeysUn;
+// and the Sim3 overload :1611-1733, which has no chi-square gate) for nmp map points against a batch of keyframes
+// (LocalMapping::SearchInNeighbors, LocalMapping.cc:743-749 and :776; LoopClosing::SearchAndFuse).
+//
+// No map point's bestIdx reads another's, so every (keyframe, point) pair goes alone.  Its result is the strict minimum of the
+// Hamming distance in the visiting order of KeyFrame::GetFeaturesInArea (KeyFrame.cc:881-925: cell columns, then cell rows, then
+// the cell's list in ascending index): the minimum of the key (distance, column, row, index), proj_key's order.  What follows the
+// search (Replace / AddObservation / AddMapPoint, isBad(), IsInKeyFrame) is sequential and stays on the host.
+//
+//   k_fuse_grid     one workgroup per keyframe: a counting sort of its features by grid cell (Frame::PosInGrid), the cells in the
+//                   order column * 48 + row, so that the rows r0..r1 of one column are ONE run of the index list.
+//   k_fuse_project  one thread per (keyframe, point): Rcw * p + tcw as cv::Mat arithmetic (cvmat_dot3), the depth, image, distance
+//                   and viewing-angle gates, PredictScale as comparisons against the host's level_ratio table (no device
+//                   logarithm), the radius.  Survivors go to a compact list (ballot + popcount, one atomic per wave); every pair
+//                   gets -1 / 256 here.
+//   k_fuse_match    FUSE_LANES lanes per survivor (a 3 px window holds a handful of keypoints: a whole wave per query would idle
+//                   most lanes), a fixed grid striding over the list: the lanes stride over each column's run, apply the window,
+//                   the level gate [level - 1, level], the chi-square gate :1533-1557 and take the group minimum of the key by
+//                   cross-lane shuffles.  TH_LOW decides the result.
+// Three launches per call, whatever nkf and nmp.
+// ---------------------------------------------------------------------------
+constexpr int FUSE_CELLS = GRID_COLS * GRID_ROWS;
+constexpr int FUSE_TH_LOW = 50;                                  // ORBmatcher::TH_LOW
+
+__device__ __forceinline__ int fuse_cell(const pli_keypoint& k, float minX, float minY, float gwInv, float ghInv, int& px, int& py) {
+  px = (int)roundf(__fmul_rn(__fsub_rn(k.x, minX), gwInv));
+  py = (int)roundf(__fmul_rn(__fsub_rn(k.y, minY), ghInv));
+  if (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) return -1;                  // PosInGrid
+  return px * GRID_ROWS + py;
+}
+
+// grid = keyframes, 256 threads; cellStart: nkf x (FUSE_CELLS + 1), sIdx: one uint16 per feature (the listed ones first)
+__global__ __launch_bounds__(256) void k_fuse_grid(const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
+                                                   pli_fuse_camera cam, int* __restrict__ cellStart,
+                                                   uint16_t* __restrict__ sIdx) {
+  __shared__ int cnt[FUSE_CELLS];
+  __shared__ int part[256];
+  const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base, t = threadIdx.x;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int i = t; i < FUSE_CELLS; i += 256) cnt[i] = 0;
+  __syncthreads();
+  for (int i = t; i < nk; i += 256) {
+    int px, py;
+    const int cell = fuse_cell(kfKp[base + i], cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+    if (cell >= 0) atomicAdd(&cnt[cell], 1);
+  }
+  __syncthreads();
+  // exclusive scan of the 3072 counts: 12 cells per thread, then the 256 partial sums
+  constexpr int PER = FUSE_CELLS / 256;
+  int s = 0;
+  for (int j = 0; j < PER; ++j) s += cnt[t * PER + j];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = part[t] - s;
+  int* cs = cellStart + (int64_t)kf * (FUSE_CELLS + 1);
+  for (int j = 0; j < PER; ++j) {
+    const int c = cnt[t * PER + j];
+    cs[t * PER + j] = run;
+    cnt[t * PER + j] = run;                                      // from here on: the cell's write cursor
+    run += c;
+  }
+  if (t == 255) cs[FUSE_CELLS] = run;
+  __syncthreads();
+  for (int i = t; i < nk; i += 256) {
+    int px, py;
+    const int cell = fuse_cell(kfKp[base + i], cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+    if (cell >= 0) sIdx[base + atomicAdd(&cnt[cell], 1)] = (uint16_t)i;      // (the order inside a cell is free: the key decides)
+  }
+}
+
+static_assert(sizeof(FuseSurvivor) == 32, "FuseSurvivor layout");
+
+// grid = ceil(nkf * nmp / 256)
+__global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __restrict__ mp, int nmp, int nkf,
+                                                      const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
+                                                      pli_fuse_camera cam, float th, const float* __restrict__ levelRatio,
+                                                      int nlevels, const float* __restrict__ scaleFactor,
+                                                      FuseSurvivor* __restrict__ surv, int* __restrict__ nSurv,
+                                                      int* __restrict__ bestIdx, int* __restrict__ bestDist) {
+  const int64_t pair = (int64_t)blockIdx.x * 256 + threadIdx.x, npairs = (int64_t)nkf * nmp;
+  bool keep = false;
+  FuseSurvivor S;
+  if (pair < npairs) {
+    const int kf = (int)(pair / nmp), i = (int)(pair - (int64_t)kf * nmp);
+    S.kf = kf; S.mp = i; S.pad = 0;
+    bestIdx[pair] = -1;
+    if (bestDist) bestDist[pair] = 256;
+    const pli_fuse_point P = mp[i];
+    if (P.valid && !(skip && skip[pair])) {                      // !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound
+      const float* T = kfPose + (int64_t)kf * 15;                // Rcw row major, tcw, Ow
+      float pc[3];
+      for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);      // Rcw*p3Dw + tcw
+      const float x = pc[0], y = pc[1], z = pc[2];
+      if (!(z < 0.0f)) {                                         // :1448
+        const float invz = __fdiv_rn(1.0f, z);
+        S.u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);         // Pinhole::project, Pinhole.cpp:30-33
+        S.v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+        if (S.u >= cam.min_x && S.u < cam.max_x && S.v >= cam.min_y && S.v < cam.max_y) {      // KeyFrame::IsInImage
+          S.ur = __fsub_rn(S.u, __fmul_rn(cam.bf, invz));
+          const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
+          // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) and PO.dot(Pn) (double)
+          const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
+          const float dist3D = (float)sqrt(n2);
+          const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
+          if (!(dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) && !(dot < 0.5 * (double)dist3D)) {
+            const float ratio = __fdiv_rn(P.max_dist, dist3D);   // MapPoint::PredictScale, MapPoint.cc:449-464
+            int level = 0;
+            for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
+            S.level = level;
+            S.radius = __fmul_rn(th, scaleFactor[level]);
+            keep = true;
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+  if (bal) {
+    const int lane = threadIdx.x & 63;
+    int first = 0;
+    if (lane == 0) first = atomicAdd(nSurv, __popcll(bal));
+    first = __shfl(first, 0, 64);
+    if (keep) surv[first + __popcll(bal & ((1ull << lane) - 1ull))] = S;
+  }
+}
+
+// the minimum of a key over the G lanes of a group (G a power of two <= 64; all lanes of the wave take part)
+template <int G>
+__device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
+// a fixed grid of 256-thread blocks; G lanes per survivor
+template <int G>
+__global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restrict__ surv, const int* __restrict__ nSurv, int nmp,
+                                                    const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
+                                                    const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                    const float* __restrict__ kfUright, const int* __restrict__ cellStart,
+                                                    const uint16_t* __restrict__ sIdx, pli_fuse_camera cam,
+                                                    const float* __restrict__ invSigma2, int reprojGate,
+                                                    int* __restrict__ bestIdx, int* __restrict__ bestDist) {
+  const int ns = *nSurv, sub = threadIdx.x & (G - 1);
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  constexpr int PER_BLOCK = 256 / G;
+  // (the loop bound is the same for every lane of a wave: the shuffles below are executed by whole waves)
+  for (int64_t b0 = (int64_t)blockIdx.x * PER_BLOCK; b0 < ns; b0 += (int64_t)gridDim.x * PER_BLOCK) {
+    const int64_t s = b0 + threadIdx.x / G;
+    unsigned long long key = ~0ull;
+    FuseSurvivor S;
+    S.kf = 0; S.mp = 0;
+    if (s < ns) {
+      S = surv[s];
+      const float u = S.u, v = S.v, radius = S.radius;
+      // KeyFrame::GetFeaturesInArea, KeyFrame.cc:889-903
+      const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
+      const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
+      const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
+      const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
+      if (c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1) {
+        const int base = kfOff[S.kf];
+        const int* cs = cellStart + (int64_t)S.kf * (FUSE_CELLS + 1);
+        uint64_t dq[4];
+        load_desc(mpDesc + (int64_t)S.mp * 32, dq);
+        for (int cx = c0; cx <= c1; ++cx) {
+          const int lo = cs[cx * GRID_ROWS + r0], hi = cs[cx * GRID_ROWS + r1 + 1];
+          for (int t = lo + sub; t < hi; t += G) {
+            const int i2 = sIdx[base + t];
+            const pli_keypoint k = kfKp[base + i2];
+            const float dx = __fsub_rn(k.x, u), dy = __fsub_rn(k.y, v);
+            if (!(fabsf(dx) < radius && fabsf(dy) < radius)) continue;                     // KeyFrame.cc:918
+            if (k.octave < S.level - 1 || k.octave > S.level) continue;                    // :1524
+            if (reprojGate) {                                                              // :1533-1557
+              const float ex = __fsub_rn(u, k.x), ey = __fsub_rn(v, k.y);
+              const float kr = kfUright[base + i2];
+              float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+              double lim = 5.99;
+              if (kr >= 0) {
+                const float er = __fsub_rn(S.ur, kr);
+                e2 = __fadd_rn(e2, __fmul_rn(er, er));
+                lim = 7.8;
+              }
+              if ((double)__fmul_rn(e2, invSigma2[k.octave]) > lim) continue;
+            }
+            uint64_t d2[4];
+            load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
+            const int dist = hamming256(dq, d2);
+            int px, py;
+            fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+            const unsigned long long kk = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) |
+                                          ((unsigned long long)py << 28) | (unsigned long long)i2;
+            key = kk < key ? kk : key;
+          }
+        }
+      }
+    }
+    key = group_min_u64<G>(key);
+    if (s < ns && sub == 0 && key != ~0ull) {
+      const int dist = (int)(key >> 40);
+      const int64_t pair = (int64_t)S.kf * nmp + S.mp;
+      if (bestDist) bestDist[pair] = dist;
+      if (dist <= FUSE_TH_LOW) bestIdx[pair] = (int)(key & 0xFFFFFFFull);
+    }
+  }
+}
+template __global__ void k_fuse_match<8>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<16>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<64>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
 
 // ---------------------------------------------------------------------------
 // SURVEY §8(f) row 4, fisheye stereo.

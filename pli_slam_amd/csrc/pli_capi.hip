@@ -2875,6 +2875,88 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   return PLI_OK;
 }
 
+pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf, const int32_t* kfOff,
+                           const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfUright, const float* kfPose,
+                           const uint8_t* skip, const pli_fuse_camera* cam, float th, const float* levelRatio, int32_t reprojGate,
+                           int32_t* bestIdx, int32_t* bestDist) {
+  CtxGuard guard__(c);
+  if (!c || nmp < 0 || nkf < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (nkf > 0 && (!kfOff || !kfPose)) ||
+      (nkf > 0 && nmp > 0 && !bestIdx)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  const int nlevels = c->hp.nlevels;
+  for (int n = 0; n < nlevels - 1; ++n)
+    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
+  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
+  for (int k = 0; k < nkf; ++k) {
+    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
+    if (kfOff[k + 1] - kfOff[k] > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the Fuse cap"; return PLI_ERR_CAPACITY; }
+  }
+  const int64_t total = kfOff[nkf];
+  if (total > 0 && (!kfKp || !kfDesc || (reprojGate && !kfUright))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  for (int64_t i = 0; i < total; ++i)      // (the octaves index the level tables: outside them the reference reads past a vector)
+    if (kfKp[i].octave < 0 || kfKp[i].octave >= nlevels) { g_err = "octave outside the context's levels"; return PLI_ERR_INVALID; }
+  if (nmp == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t npairs = (size_t)nkf * nmp;
+  ScratchPlan plan;
+  auto dMp = plan.add<pli_fuse_point>(nmp);
+  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
+  auto dOff = plan.add<int>((size_t)nkf + 1);
+  auto dKk = plan.add<pli_keypoint>(total);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dKu = plan.add<float>(total);
+  auto dPose = plan.add<float>((size_t)nkf * 15);
+  auto dSkip = plan.add<uint8_t>(skip ? npairs : 0);
+  auto dLv = plan.add<float>(3 * MAX_LEVELS);               // level_ratio, mvScaleFactors, mvInvLevelSigma2
+  auto dCell = plan.add<int>((size_t)nkf * (GRID_COLS * GRID_ROWS + 1));
+  auto dSi = plan.add<uint16_t>(total);
+  auto dSurv = plan.add<FuseSurvivor>(npairs);
+  auto dNs = plan.add<int>(1);
+  auto dBi = plan.add<int>(npairs);
+  auto dBd = plan.add<int>(bestDist ? npairs : 0);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  float hlv[3 * MAX_LEVELS] = {};
+  for (int l = 0; l < nlevels; ++l) {
+    if (l < nlevels - 1) hlv[l] = levelRatio[l];
+    const float s = c->hp.lv[l].scale;
+    hlv[MAX_LEVELS + l] = s;                                 // mvScaleFactors, ORBextractor.cc:420
+    hlv[2 * MAX_LEVELS + l] = 1.0f / (s * s);                // mvInvLevelSigma2 = 1.0f / mvLevelSigma2, ORBextractor.cc:424-431
+  }
+  HIPCHK(upload(c, dMp, mp, nmp));
+  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
+  HIPCHK(upload(c, dKk, kfKp, total));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  if (reprojGate) HIPCHK(upload(c, dKu, kfUright, total));
+  HIPCHK(upload(c, dPose, kfPose, (size_t)nkf * 15));
+  if (skip) HIPCHK(upload(c, dSkip, skip, npairs));
+  HIPCHK(upload(c, dLv, (const float*)hlv, 3 * MAX_LEVELS));
+  HIPCHK(hipMemsetAsync(dNs, 0, sizeof(int), c->stream));
+  const uint8_t* dSkipPtr = skip ? (const uint8_t*)dSkip : nullptr;
+  int* dBdPtr = bestDist ? (int*)dBd : nullptr;
+  const float* lv = dLv;
+  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(nkf), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
+  LAUNCH(c, "k_fuse_project", k_fuse_project, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose, dSkipPtr, *cam, th,
+         lv, nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBdPtr);
+  // lanes per surviving pair (Fuse: 8 measured best; the development build can run the other widths)
+  int lanes = 8;
+  if (const char* e = DEVENV("PLI_FUSE_LANES")) lanes = atoi(e);
+  const dim3 mgrid(1024);
+#define FUSE_MATCH(G)                                                                                                              \
+  LAUNCH(c, "k_fuse_match", k_fuse_match<G>, mgrid, dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd, dKu, dCell, dSi, *cam,     \
+         lv + 2 * MAX_LEVELS, reprojGate ? 1 : 0, dBi, dBdPtr)
+  if (lanes == 16) FUSE_MATCH(16);
+  else if (lanes == 64) FUSE_MATCH(64);
+  else FUSE_MATCH(8);
+#undef FUSE_MATCH
+  HIPCHK(download(c, bestIdx, dBi, npairs));
+  if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 // ---- measurement -----------------------------------------------------------
 int64_t pli_trace_ranges(void) { return (int64_t)g_roctx.pushed.load(std::memory_order_relaxed); }
 

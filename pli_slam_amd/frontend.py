@@ -39,6 +39,41 @@ def needs_dev_library(cfg):
     return cfg.lsd_mode == 1 or any(k.startswith("PLI_") and k not in PRODUCT_ENV + PYTHON_ENV for k in os.environ)
 
 
+def predict_scale(ratio, nlevels, scale_factor):
+    """MapPoint::PredictScale (MapPoint.cc:449-464) on ratio = mfMaxDistance / currentDist, a float: ceil(log(ratio) /
+    mfLogScaleFactor) with mfLogScaleFactor = (float)log(mfScaleFactor) and the clamps to [0, nlevels).  The logarithm is the
+    host's (math.log of the float, in double): the expression an integrator's compiler builds may select logf instead, which is
+    why pli_fuse_search takes the thresholds as a table (fuse_level_ratio) and does not evaluate a logarithm itself."""
+    import math
+    ratio = float(np.float32(ratio))
+    if not ratio > 0.0:
+        return 0
+    if math.isinf(ratio):
+        return nlevels - 1
+    log_sf = float(np.float32(math.log(float(np.float32(scale_factor)))))
+    n = math.ceil(math.log(ratio) / log_sf)
+    return 0 if n < 0 else nlevels - 1 if n >= nlevels else int(n)
+
+
+def fuse_level_ratio(nlevels, scale_factor, level_fn=None):
+    """level_ratio of pli_fuse_search: for n = 0 .. nlevels-2 the largest float r for which the host's PredictScale expression
+    (level_fn(r), default predict_scale) gives a level <= n, by bisection over the bit patterns of the positive floats (the
+    expression does not decrease with r).  The level of a ratio is then the number of n with ratio > level_ratio[n]."""
+    fn = level_fn or (lambda r: predict_scale(r, nlevels, scale_factor))
+    as_float = lambda bits: np.array([bits], np.uint32).view(np.float32)[0]
+    out = np.zeros(max(nlevels - 1, 0), np.float32)
+    for n in range(nlevels - 1):
+        lo, hi = 1, 0x7F800000                      # the smallest subnormal: level 0; +inf: the top level
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if fn(as_float(mid)) <= n:
+                lo = mid
+            else:
+                hi = mid
+        out[n] = as_float(lo)
+    return out
+
+
 class Frontend:
     """One pli_ctx: device buffers + stream for up to `max_frames` stereo frames."""
 
@@ -241,6 +276,54 @@ class Frontend:
                                                   int(only_stereo), int(coarse), int(check_orientation), ptr(matches),
                                                   ptr(nmatches)))
         return matches, nmatches
+
+    def fuse_search(self, points, descs, keyframes, cam, th=3.0, reproj_gate=True, skip=None, level_ratio=None):
+        """The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reproj_gate=False: the Sim3
+        overload :1611-1733) of the map points `points` (capi.FUSE_POINT_DT rows) with descriptors `descs` against every keyframe
+        of `keyframes`, in one call.  keyframes: list of (kp, desc, uright, pose) - mvKeysUn as KEYPOINT_DT rows, mDescriptors,
+        mvuRight, pose = 15 floats (Rcw row major, tcw, Ow); cam: capi.FuseCamera or its 9 values; skip: nkf x nmp, != 0 leaves a
+        pair out (IsInKeyFrame).  Returns (best_idx[nkf, nmp]: the keyframe's row or -1, best_dist[nkf, nmp])."""
+        pts = np.ascontiguousarray(points, capi.FUSE_POINT_DT).reshape(-1)
+        d = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        if len(d) != len(pts):
+            raise ValueError("every map point needs one descriptor")
+        nkf, nmp = len(keyframes), len(pts)
+        tabs = []
+        for kf in keyframes:
+            kd = np.ascontiguousarray(kf[1], np.uint8).reshape(-1, 32)
+            cols = (np.ascontiguousarray(kf[0], KEYPOINT_DT).reshape(-1), kd, np.ascontiguousarray(kf[2], np.float32).reshape(-1),
+                    np.ascontiguousarray(kf[3], np.float32).reshape(15))
+            if len(cols[0]) != len(kd) or len(cols[2]) != len(kd):
+                raise ValueError("every feature needs one keypoint, descriptor and uright")
+            tabs.append(cols)
+        off = np.zeros(nkf + 1, np.int32)
+        for k, t in enumerate(tabs):
+            off[k + 1] = off[k] + len(t[1])
+
+        def cat(i, dt, shape):
+            parts = [t[i] for t in tabs]
+            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
+        kk, kd, ku = cat(0, KEYPOINT_DT, (0,)), cat(1, np.uint8, (0, 32)), cat(2, np.float32, (0,))
+        pose = np.ascontiguousarray([t[3] for t in tabs], np.float32).reshape(nkf, 15)
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint8)
+            if skip.shape != (nkf, nmp):
+                raise ValueError("skip: nkf x nmp")
+        if level_ratio is None:
+            if getattr(self, "_fuse_level_ratio", None) is None:
+                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
+            level_ratio = self._fuse_level_ratio
+        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
+        if len(level_ratio) != self.cfg.orb_nlevels - 1:
+            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        best_idx = np.full((nkf, nmp), -1, np.int32)
+        best_dist = np.full((nkf, nmp), 256, np.int32)
+        check(self.L.pli_fuse_search(self.h, ptr(pts), ptr(d), nmp, nkf, ptr(off), ptr(kk), ptr(kd), ptr(ku), ptr(pose),
+                                     ptr(skip), C.byref(cam), float(th), ptr(level_ratio), int(reproj_gate), ptr(best_idx),
+                                     ptr(best_dist)))
+        return best_idx, best_dist
 
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
