@@ -6,7 +6,7 @@
 //   k_lsd_grow      region_grow + region2rect, refine = NONE
 //   k_keylines      LSDDetectorC::detectImpl KeyLine fill + Lineextractor top-N
 //                   (LSDDetector_custom.cpp:264-308, LineExtractor.cc:53-65)
-//   k_sobel         cv::Sobel 3x3 dx/dy -> i16            (binary_descriptor_custom.cpp:395-396)
+//   k_sobel         GaussianBlur 5x5 + cv::Sobel 3x3 dx/dy -> i16 (binary_descriptor_custom.cpp:358,395-396)
 //   k_lbd           BinaryDescriptor::computeLBD + binaryConversion
 //                   (binary_descriptor_custom.cpp:1026-1340, 401-412, 662-666)
 #include "kernels.hpp"
@@ -1546,53 +1546,141 @@ __global__ __launch_bounds__(256) void k_keylines(const DevParams* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// k_sobel: 3x3 Sobel dx, dy (CV_16S) with REFLECT_101 on the blurred image.
+// k_sobel: BinaryDescriptor::compute's GaussianBlur 5x5 and 3x3 Sobel dx, dy (CV_16S) of level 0 in one pass: the blurred
+// image exists only as a tile in LDS.  A workgroup makes a 64 x 32 tile of (dx, dy): it stages the source tile with a halo of
+// LBD_BLUR_R + 1 (aligned 4-byte loads, REFLECT_101 on the source like k_blur), blurs it with k_blur's arithmetic (jobLbd's
+// coefficients, 32-bit sums, (s + 2^15) >> 16, saturate) into a tile with a halo of 1, and takes the Sobel from that tile with
+// REFLECT_101 of the BLURRED image at the image border: only blurred pixels inside the image are read.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sobel(const uint8_t* __restrict__ in, int64_t imgStride, int W, int H,
-                                               int pitch, short2* __restrict__ dxy, int img0) {
-  // 4 adjacent pixels per thread: ONE aligned dword of each of the three rows per thread — the byte on its left and the byte on its
-  // right come from the neighbouring lanes' dwords (the first and the last lane of a wave load theirs), where the earlier form
-  // issued 18 byte loads per thread — and one 16-byte store of interleaved (dx, dy).  (Rows are pitch = align64(W) bytes: a dword at
-  // x0 < W is inside the row.)
-  const int img = blockIdx.z + img0, y = blockIdx.y, x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  const int lane = threadIdx.x & 63;
-  const uint8_t* base = in + (int64_t)img * imgStride;
-  const uint8_t* rows[3] = {base + (int64_t)reflect101(y - 1, H) * pitch, base + (int64_t)y * pitch, base + (int64_t)reflect101(y + 1, H) * pitch};
-  const bool live = x0 < W;
-  int v[3][6];
+constexpr int SB_H = LBD_BLUR_R + 1;          // halo of the source tile (3: the staging below loads one dword left of the tile)
+constexpr int SB_SR = 32 + 2 * SB_H;          // source rows (38)
+constexpr int SB_SD = 18;                     // dwords of a source row: columns x0 - 4 .. x0 + 67
+constexpr int SB_BR = 34;                     // blurred rows y0 - 1 .. y0 + 32
+constexpr int SB_BD = 17;                     // dwords of a blurred row: columns x0 - 1 .. x0 + 66 (x0 + 64 is the last one used)
+static_assert(SB_H <= 4 && LBD_BLUR_R <= 3, "the source tile starts one dword left of the output tile");
+
+__global__ __launch_bounds__(256) void k_sobel(const BlurJob* __restrict__ Jp, const uint8_t* __restrict__ in, int64_t inImgStride,
+                                               short2* __restrict__ dxy, int img0) {
+  __shared__ uint32_t t8[SB_SR * SB_SD + 2];            // (+ the dwords a sum of the unused columns x0 + 65, x0 + 66 may touch)
+  __shared__ __attribute__((aligned(16))) int hs[SB_SR * 4 * SB_BD];
+  __shared__ uint32_t bt[SB_BR * SB_BD];
+  const BlurJob& J = *Jp;
+  const BlurPlane& PL = J.pl[0];
+  const int W = PL.w, H = PL.h;
+  const int img = blockIdx.y + img0;
+  const int ty = blockIdx.x / PL.tilesX, tx = blockIdx.x - ty * PL.tilesX;
+  const int x0 = tx * 64, y0 = ty * 32;
+  constexpr int R = LBD_BLUR_R;
+  const uint8_t* src = in + (int64_t)img * inImgStride + PL.offIn;
+  const int tid = threadIdx.x;
+  int kc[7];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    unsigned cur = 0u;
-    if (live) cur = *reinterpret_cast<const unsigned*>(rows[r] + x0);
-    unsigned prev = (unsigned)__shfl_up((int)cur, 1, 64), next = (unsigned)__shfl_down((int)cur, 1, 64);
-    if (lane == 0 && live && x0 >= 4) prev = *reinterpret_cast<const unsigned*>(rows[r] + x0 - 4);
-    if (lane == 63 && x0 + 4 < W) next = *reinterpret_cast<const unsigned*>(rows[r] + x0 + 4);
-    v[r][1] = cur & 0xFF; v[r][2] = (cur >> 8) & 0xFF; v[r][3] = (cur >> 16) & 0xFF; v[r][4] = cur >> 24;
-    v[r][0] = x0 == 0 ? v[r][2] : (int)(prev >> 24);              // REFLECT_101: column -1 is column 1
-    v[r][5] = (int)(next & 0xFF);
+  for (int k = 0; k < 7; ++k) kc[k] = k <= 2 * R ? J.k[k] : 0;
+  const bool narrow = (kc[0] | kc[1] | kc[2] | kc[3] | kc[4] | kc[5] | kc[6]) < 256;
+  const uint32_t kLo = (uint32_t)kc[0] | ((uint32_t)kc[1] << 8) | ((uint32_t)kc[2] << 16) | ((uint32_t)kc[3] << 24);
+  const uint32_t kHi = (uint32_t)kc[4] | ((uint32_t)kc[5] << 8) | ((uint32_t)kc[6] << 16);
+  // stage rows y0 - 3 .. y0 + 34, columns x0 - 4 .. x0 + 67 (byte b of a row = column x0 - 4 + b), as k_blur does
+  for (int i = tid; i < SB_SR * SB_SD; i += 256) {
+    const int y = (int)(((float)i + 0.5f) * (1.0f / SB_SD)), d = i - y * SB_SD;     // exact for i < 38 * 18
+    const uint8_t* row = src + (int64_t)reflect101(y0 + y - SB_H, H) * PL.pitchIn;
+    const int px = x0 - 4 + 4 * d;
+    uint32_t v;
+    if (px >= 0 && px + 3 < W) {
+      v = *reinterpret_cast<const uint32_t*>(row + px);
+    } else {
+      v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // (columns further than the halo outside the image are never used by a stored output: clamped to keep the reflection single)
+        const int xx = reflect101(min(max(px + k, -SB_H), W - 1 + SB_H), W);
+        v |= (uint32_t)row[xx] << (8 * k);
+      }
+    }
+    t8[i] = v;
   }
-  if (!live) return;
-  if (x0 + 4 >= W) {
-    // the thread that holds the last column(s): columns past the image are not stored, column W is column W - 2
+  if (tid < 2) t8[SB_SR * SB_SD + tid] = 0u;
+  __syncthreads();
+  // horizontal pass, 4 adjacent sums per task: blurred column x0 - 1 + 4j + i takes the bytes 4j + i + (3 - R) + k, k = 0..2R
+  for (int t = tid; t < SB_SR * SB_BD; t += 256) {
+    const int y = (int)(((float)t + 0.5f) * (1.0f / SB_BD)), j = t - y * SB_BD;     // exact for t < 38 * 17
+    const uint32_t* w = &t8[y * SB_SD + j];
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+    int s[4];
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
+    for (int i = 0; i < 4; ++i) {
+      constexpr int base = 3 - R;                        // 1
+      const int off = i + base;                          // 1..4
+      const bool q = off >= 4;
+      const uint32_t a0 = q ? w1 : w0, a1 = q ? w2 : w1, a2 = q ? w3 : w2;
+      const uint32_t lo = __builtin_amdgcn_alignbyte(a1, a0, off & 3);
+      const uint32_t hi = __builtin_amdgcn_alignbyte(a2, a1, off & 3);
+      if (narrow) {
+        s[i] = (int)__builtin_amdgcn_udot4(hi, kHi, __builtin_amdgcn_udot4(lo, kLo, 0u, false), false);
+      } else {                                           // a coefficient of 256 (a sigma so small that the kernel is a delta)
+        s[i] = 0;
 #pragma unroll
-      for (int k = 1; k < 6; ++k)
-        if (x0 + k - 1 >= W) v[r][k] = rows[r][reflect101(min(x0 + k - 1, W), W)];
+        for (int k = 0; k < 4; ++k) s[i] += kc[k] * (int)((lo >> (8 * k)) & 255u);
+#pragma unroll
+        for (int k = 4; k < 7; ++k) s[i] += kc[k] * (int)((hi >> (8 * (k - 4))) & 255u);
+      }
+    }
+    *reinterpret_cast<int4*>(&hs[(y * SB_BD + j) * 4]) = make_int4(s[0], s[1], s[2], s[3]);
   }
-  short2 o[4];
+  __syncthreads();
+  // vertical pass: blurred row y0 - 1 + r from the sums of the source rows r .. r + 2R of the tile
+  for (int t = tid; t < SB_BR * SB_BD; t += 256) {
+    const int r = (int)(((float)t + 0.5f) * (1.0f / SB_BD)), j = t - r * SB_BD;
+    int s[4] = {0, 0, 0, 0};
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int gx = (v[0][k + 2] - v[0][k]) + 2 * (v[1][k + 2] - v[1][k]) + (v[2][k + 2] - v[2][k]);
-    const int gy = (v[2][k] - v[0][k]) + 2 * (v[2][k + 1] - v[0][k + 1]) + (v[2][k + 2] - v[0][k + 2]);
-    o[k] = make_short2((short)gx, (short)gy);      // interleaved: k_lbd gathers both with one 4-byte load
+    for (int k = 0; k <= 2 * R; ++k) {
+      const int4 v = *reinterpret_cast<const int4*>(&hs[((r + k) * SB_BD + j) * 4]);
+      s[0] += kc[k] * v.x; s[1] += kc[k] * v.y; s[2] += kc[k] * v.z; s[3] += kc[k] * v.w;
+    }
+    // (s + 2^15) >> 16 and the saturate: the sums are never negative (pixels and coefficients are not), so the saturate is the upper clamp
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o |= min((uint32_t)(s[i] + (1 << 15)) >> 16, 255u) << (8 * i);
+    bt[t] = o;
   }
-  short2* dst = dxy + (int64_t)img * W * H + (int64_t)y * W + x0;
-  if (x0 + 3 < W && (((int64_t)y * W + x0) & 3) == 0 && ((int64_t)W * H & 3) == 0) {
-    *reinterpret_cast<int4*>(dst) = make_int4(*reinterpret_cast<int*>(&o[0]), *reinterpret_cast<int*>(&o[1]),
-                                              *reinterpret_cast<int*>(&o[2]), *reinterpret_cast<int*>(&o[3]));
-  } else {
-    for (int k = 0; k < 4 && x0 + k < W; ++k) dst[k] = o[k];
+  __syncthreads();
+  // Sobel, 4 adjacent pixels per task: the columns x - 1 .. x + 4 of three blurred rows are two dwords of each; one 16-byte store
+  const uint8_t* btb = reinterpret_cast<const uint8_t*>(bt);
+  for (int t = tid; t < 32 * 16; t += 256) {
+    const int yy = t >> 4, j = t & 15;
+    const int y = y0 + yy, x = x0 + 4 * j;
+    if (y >= H || x >= W) continue;
+    // rows of the blurred tile (row 0 = image row y0 - 1); REFLECT_101: row -1 is row 1, row H is row H - 2
+    const int rr[3] = {reflect101(y - 1, H) - y0 + 1, yy + 1, reflect101(y + 1, H) - y0 + 1};
+    int v[3][6];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const uint32_t lo = bt[rr[r] * SB_BD + j], hi = bt[rr[r] * SB_BD + j + 1];
+      v[r][0] = lo & 0xFF; v[r][1] = (lo >> 8) & 0xFF; v[r][2] = (lo >> 16) & 0xFF; v[r][3] = lo >> 24;
+      v[r][4] = hi & 0xFF; v[r][5] = (hi >> 8) & 0xFF;
+      if (x == 0) v[r][0] = v[r][2];                     // column -1 is column 1
+    }
+    if (x + 4 >= W) {
+      // the task that holds the last column(s): columns past the image are not stored, column W is column W - 2
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 1; k < 6; ++k)
+          if (x + k - 1 >= W) v[r][k] = btb[rr[r] * (4 * SB_BD) + reflect101(min(x + k - 1, W), W) - x0 + 1];
+    }
+    short2 o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int gx = (v[0][k + 2] - v[0][k]) + 2 * (v[1][k + 2] - v[1][k]) + (v[2][k + 2] - v[2][k]);
+      const int gy = (v[2][k] - v[0][k]) + 2 * (v[2][k + 1] - v[0][k + 1]) + (v[2][k + 2] - v[0][k + 2]);
+      o[k] = make_short2((short)gx, (short)gy);      // interleaved: k_lbd gathers both with one 4-byte load
+    }
+    short2* dst = dxy + (int64_t)img * W * H + (int64_t)y * W + x;
+    if (x + 3 < W && (((int64_t)y * W + x) & 3) == 0 && ((int64_t)W * H & 3) == 0) {
+      *reinterpret_cast<int4*>(dst) = make_int4(*reinterpret_cast<int*>(&o[0]), *reinterpret_cast<int*>(&o[1]),
+                                                *reinterpret_cast<int*>(&o[2]), *reinterpret_cast<int*>(&o[3]));
+    } else {
+      for (int k = 0; k < 4 && x + k < W; ++k) dst[k] = o[k];
+    }
   }
 }
 

@@ -4,8 +4,8 @@
 //   k_resize_level  ORBextractor::ComputePyramid            (ORBextractor.cc:1152-1177)
 //   k_fast_cells    per-cell cv::FAST x2 thresholds + NMS   (ORBextractor.cc:787-854)
 //   k_octree        ORBextractor::DistributeOctTree         (ORBextractor.cc:479-761)
-//   k_blur          cv::GaussianBlur u8 fixed point         (ORBextractor.cc:1115, also LSD/LBD)
-//   k_describe      IC_Angle + computeOrbDescriptor + table (ORBextractor.cc:75-145,1105-1147)
+//   k_blur          cv::GaussianBlur u8 fixed point         (the CV_8U LSD pre-filter; ORBextractor.cc:1115 as a plane: debug contexts)
+//   k_describe      GaussianBlur of the keypoint's window + IC_Angle + computeOrbDescriptor + table (ORBextractor.cc:75-145,1105-1147)
 //
 // All arithmetic that decides a result is integer or explicitly ordered IEEE
 // float (see device_prims.hpp); the library is built with -ffp-contract=off.
@@ -837,12 +837,35 @@ __global__ __launch_bounds__(256) void k_blur(const BlurJob* __restrict__ Jp, co
 // k_describe: one wave per selected keypoint slot: IC_Angle on the level image,
 // steered rBRIEF on the blurred level (ballot -> 4 x u64), and the final
 // level-major tables (ORBextractor.cc:1105-1147) straight into the frame record.
+//
+// The blurred level is not a plane in memory: the wave stages the unblurred window of its keypoint in LDS (aligned 4-byte
+// loads, REFLECT_101 at the level's border like k_blur), runs k_blur's two passes on it — the same 8-bit coefficients, 32-bit
+// sums, (s + 2^15) >> 16 and the saturate, so every blurred byte is the byte the plane pass makes — and reads the 512 steered
+// taps, and IC_Angle's disc, from LDS.  A keypoint lies 19 pixels from the border and a tap reaches ORB_REACH = 18 pixels: the
+// blurred pixels a tap can touch are inside the level, the source pixels under the blur kernel are not always.
 // ---------------------------------------------------------------------------
+constexpr int DW_R = (ORB_REACH + ORB_BLUR_R > ORB_HALF_PATCH ? ORB_REACH + ORB_BLUR_R : ORB_HALF_PATCH);   // staged window: radius
+constexpr int DW_S = 2 * DW_R + 1;                         // ... and side (43)
+constexpr int DW_SD = (DW_S + 3 + 3) / 4;                  // dwords of a staged row: the side plus the window's misalignment (0..3)
+constexpr int DW_O = DW_R - ORB_REACH - ORB_BLUR_R;        // first staged row / column under the blur of the first blurred one
+constexpr int DW_B = 2 * ORB_REACH + 1;                    // blurred window: side (37)
+constexpr int DW_BG = (DW_B + 3) / 4;                      // ... in groups of 4 columns
+constexpr int DW_BP = 4 * DW_BG;                           // ... and its row pitch
+constexpr int DW_HR = DW_B + 2 * ORB_BLUR_R;               // rows of horizontal sums
+static_assert(DW_R >= ORB_REACH + ORB_BLUR_R && DW_R >= ORB_HALF_PATCH, "the staged window covers the blur of every tap and IC_Angle's disc");
+static_assert(DW_O + DW_HR <= DW_S && 3 + DW_O + DW_B - 1 + 2 * ORB_BLUR_R < 4 * DW_SD, "the blur passes stay inside the staged window");
+static_assert(DW_BP % 4 == 0 && ORB_BLUR_R == 3 && DW_O <= 1, "four sums per lane and step; two v_dot4 on the dwords j..j+3 per 7-tap sum");
+
 __global__ __launch_bounds__(64) void k_describe(const DevParams* __restrict__ Pp, const uint8_t* __restrict__ pyr,
-                                                 const uint8_t* __restrict__ blur, const uint32_t* __restrict__ kpSel,
+                                                 const BlurJob* __restrict__ Jp, const uint32_t* __restrict__ kpSel,
                                                  const int* __restrict__ kpSelCount, uint8_t* __restrict__ table,
                                                  int64_t recordBytes, int64_t offCounts, int64_t offKp0,
                                                  int64_t offKp1, int64_t offDesc0, int64_t offDesc1, int img0) {
+  // the unblurred window (byte b of a row = column kx - DW_R - ox + b, ox = the misalignment of the window's first column) + the
+  // dwords that the sums of the unused columns DW_B..DW_BP-1 may touch past the last row
+  __shared__ uint32_t s_src[DW_S * DW_SD + 2];
+  __shared__ __attribute__((aligned(8))) unsigned short s_hs[DW_HR * DW_BP];     // horizontal sums: at most 255 * 256, 16 bits
+  __shared__ uint32_t s_bl[DW_B * DW_BG];                                         // the blurred window
   const DevParams& P = *Pp;
   const int img = blockIdx.y + img0, slot = blockIdx.x;
   int lvl = 0;
@@ -869,28 +892,80 @@ __global__ __launch_bounds__(64) void k_describe(const DevParams* __restrict__ P
   const int kx = (int)((cv >> 8) & 0xFFF) + G.minBX, ky = (int)(cv >> 20) + G.minBY;
   const int resp = (int)(cv & 0xFF);
   const uint8_t* im = pyr + (int64_t)img * P.pyrBlock + G.offset;
-  // IC_Angle: moments over the radius-15 disc.  The disc rows (umax) go through LDS so that the 16 pixel loads of a lane
-  // do not each wait for a table load: they are issued together.
   __shared__ int s_umax[16];
   if (lane < 16) s_umax[lane] = P.umax[lane];
+  // stage the window: a dword inside the level is one aligned load (the rows of a level start 64-byte aligned), a dword across the
+  // left or right border is put together from REFLECT_101 bytes; rows above and below the level are its reflected rows
+  const int wy0 = ky - DW_R, ox = (kx - DW_R) & 3, bx = (kx - DW_R) - ox;
+  for (int i = lane; i < DW_S * DW_SD; i += 64) {
+    const int y = i / DW_SD, d = i - y * DW_SD;
+    const uint8_t* row = im + (int64_t)reflect101(wy0 + y, G.h) * G.pitch;
+    const int px = bx + 4 * d;
+    uint32_t v;
+    if (px >= 0 && px + 3 < G.w) {
+      v = *reinterpret_cast<const uint32_t*>(row + px);
+    } else {
+      v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v |= (uint32_t)row[reflect101(px + k, G.w)] << (8 * k);
+    }
+    s_src[i] = v;
+  }
+  if (lane < 2) s_src[DW_S * DW_SD + lane] = 0u;
   __syncthreads();
+  const uint8_t* srcb = reinterpret_cast<const uint8_t*>(s_src);
+  // IC_Angle: moments over the radius-15 disc of the unblurred window
   int m10 = 0, m01 = 0;
-  int val[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     const int i = lane + 64 * k;
     const int r = (i * 2115) >> 16;                // i / 31, exact for i < 1024
     const int v = r - 15, u = (i - r * 31) - 15;
     const int av = v < 0 ? -v : v, au = u < 0 ? -u : u;
-    val[k] = 0;
-    if (i < 31 * 31 && au <= s_umax[av]) val[k] = im[(int64_t)(ky + v) * G.pitch + kx + u];
+    int val = 0;
+    if (i < 31 * 31 && au <= s_umax[av]) val = srcb[(DW_R + v) * (4 * DW_SD) + ox + DW_R + u];
+    m10 += u * val;
+    m01 += v * val;
   }
+  // horizontal pass, four adjacent sums per lane and step: blurred column c takes the bytes ox + DW_O + c + k, k = 0..6, of its row
+  const BlurJob& J = *Jp;
+  int kc[7];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int i = lane + 64 * k;
-    const int r = (i * 2115) >> 16;
-    m10 += ((i - r * 31) - 15) * val[k];
-    m01 += (r - 15) * val[k];
+  for (int k = 0; k < 7; ++k) kc[k] = J.k[k];
+  const uint32_t kLo = (uint32_t)kc[0] | ((uint32_t)kc[1] << 8) | ((uint32_t)kc[2] << 16) | ((uint32_t)kc[3] << 24);
+  const uint32_t kHi = (uint32_t)kc[4] | ((uint32_t)kc[5] << 8) | ((uint32_t)kc[6] << 16);
+  for (int t = lane; t < DW_HR * DW_BG; t += 64) {
+    const int y = t / DW_BG, j = t - y * DW_BG;
+    const uint32_t* w = &s_src[(DW_O + y) * DW_SD + j];
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+    uint32_t s[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int off = ox + DW_O + i;                     // 0..6 (+ DW_O), the same in every lane
+      const bool q = off >= 4;
+      const uint32_t a0 = q ? w1 : w0, a1 = q ? w2 : w1, a2 = q ? w3 : w2;
+      const uint32_t lo = __builtin_amdgcn_alignbyte(a1, a0, off & 3);
+      const uint32_t hi = __builtin_amdgcn_alignbyte(a2, a1, off & 3);
+      s[i] = __builtin_amdgcn_udot4(hi, kHi, __builtin_amdgcn_udot4(lo, kLo, 0u, false), false);
+    }
+    *reinterpret_cast<uint2*>(&s_hs[y * DW_BP + 4 * j]) = make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
+  }
+  __syncthreads();
+  // vertical pass
+  for (int t = lane; t < DW_B * DW_BG; t += 64) {
+    const int y = t / DW_BG, j = t - y * DW_BG;
+    int s[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      const uint2 v = *reinterpret_cast<const uint2*>(&s_hs[(y + k) * DW_BP + 4 * j]);
+      s[0] += kc[k] * (int)(v.x & 0xFFFFu); s[1] += kc[k] * (int)(v.x >> 16);
+      s[2] += kc[k] * (int)(v.y & 0xFFFFu); s[3] += kc[k] * (int)(v.y >> 16);
+    }
+    // (s + 2^15) >> 16 and the saturate: the sums are never negative (pixels and coefficients are not), so the saturate is the upper clamp
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o |= min((uint32_t)(s[i] + (1 << 15)) >> 16, 255u) << (8 * i);
+    s_bl[t] = o;
   }
   m10 = wave_sum_i32(m10);
   m01 = wave_sum_i32(m01);
@@ -900,8 +975,8 @@ __global__ __launch_bounds__(64) void k_describe(const DevParams* __restrict__ P
   const float ang = __fmul_rn(angle, factorPI);
   float a, b;                                          // a = cos, b = sin (ORBextractor.cc:111)
   sincos_of_float(ang, (P.parityFlags & PLI_PARITY_TRIG_F32_ORB) != 0, &b, &a);
-  const uint8_t* bl = blur + (int64_t)img * P.pyrBlock + G.offset;
-  const uint8_t* center = bl + (int64_t)ky * G.pitch + kx;
+  __syncthreads();
+  const uint8_t* center = reinterpret_cast<const uint8_t*>(s_bl) + ORB_REACH * DW_BP + ORB_REACH;
   unsigned long long words[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -911,8 +986,8 @@ __global__ __launch_bounds__(64) void k_describe(const DevParams* __restrict__ P
     int c0 = cv_round_f(__fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b)));
     int r1 = cv_round_f(__fadd_rn(__fmul_rn(x1, b), __fmul_rn(y1, a)));
     int c1 = cv_round_f(__fsub_rn(__fmul_rn(x1, a), __fmul_rn(y1, b)));
-    int t0 = center[(int64_t)r0 * G.pitch + c0];
-    int t1 = center[(int64_t)r1 * G.pitch + c1];
+    int t0 = center[r0 * DW_BP + c0];
+    int t1 = center[r1 * DW_BP + c1];
     words[j] = __ballot(t0 < t1);
   }
   if (lane == 0) {

@@ -520,7 +520,6 @@ pli_status allocAll(pli_ctx* c) {
   A(c->dP, 1);
   HIPCHK(hipMemcpy(c->dP, &c->hp, sizeof(DevParams), hipMemcpyHostToDevice));
   A(c->pyr, (size_t)P.pyrBlock * NI);
-  A(c->blur, (size_t)P.pyrBlock * NI);
   for (int l = 1; l < P.nlevels; ++l) {
     const LevelGeom &S = P.lv[l - 1], &D = P.lv[l];
     std::vector<int> t = buildResizeTab(S.w, S.h, D.w, D.h, 1. / ((double)D.w / S.w), 1. / ((double)D.h / S.h));
@@ -539,8 +538,14 @@ pli_status allocAll(pli_ctx* c) {
     BlurJob J;
     std::memset(&J, 0, sizeof(J));
     J.nplanes = P.nlevels;
-    J.radius = 3;
-    gaussKernelFixed8(7, 2.0, J.k);
+    J.radius = ORB_BLUR_R;
+    gaussKernelFixed8(2 * ORB_BLUR_R + 1, 2.0, J.k);
+    {
+      // k_describe keeps the horizontal sums of its window in 16 bits and takes them with v_dot4
+      int ksum = 0, kmax = 0;
+      for (int i = 0; i < 2 * ORB_BLUR_R + 1; ++i) { ksum += J.k[i]; kmax = std::max(kmax, J.k[i]); }
+      if (ksum * 255 > 65535 || kmax > 255) { g_err = "ORB blur coefficients do not fit k_describe's 16-bit sums"; return PLI_ERR_INVALID; }
+    }
     int tb = 0;
     for (int l = 0; l < P.nlevels; ++l) {
       BlurPlane& p = J.pl[l];
@@ -570,9 +575,9 @@ pli_status allocAll(pli_ctx* c) {
     A(c->jobLsd, 1);
     HIPCHK(hipMemcpy(c->jobLsd, &J, sizeof(J), hipMemcpyHostToDevice));
     // LBD: 5x5 sigma 1 (binary_descriptor_custom.cpp:358)
-    J.radius = 2;
+    J.radius = LBD_BLUR_R;
     std::memset(J.k, 0, sizeof(J.k));
-    gaussKernelFixed8(5, 1.0, J.k);
+    gaussKernelFixed8(2 * LBD_BLUR_R + 1, 1.0, J.k);
     A(c->jobLbd, 1);
     HIPCHK(hipMemcpy(c->jobLbd, &J, sizeof(J), hipMemcpyHostToDevice));
   }
@@ -887,10 +892,12 @@ pli_status runOrb(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     else { if (wide) OCTREE_LAUNCH(k_octree_w); else OCTREE_LAUNCH(k_octree); }
 #undef OCTREE_LAUNCH
   }
-  LAUNCH(c, "k_blur_orb", k_blur, dim3(c->orbTiles, nimg), dim3(256), 0, c->jobOrb, c->pyr, P.pyrBlock, c->blur, P.pyrBlock, img0);
+  // the blurred pyramid is a debug item only (PLI_DBG_BLUR_LEVEL): k_describe blurs the window of each keypoint itself
+  if (c->debug && c->blur)
+    LAUNCH(c, "k_blur_orb", k_blur, dim3(c->orbTiles, nimg), dim3(256), 0, c->jobOrb, c->pyr, P.pyrBlock, c->blur, P.pyrBlock, img0);
   LAUNCH(c, "k_kp_counts", k_kp_counts, dim3((nimg + 63) / 64), dim3(64), 0, c->dP, c->kpSelCount, table, Y.record_bytes,
          Y.off_counts, nimg, img0);
-  LAUNCH(c, "k_describe", k_describe, dim3(P.kpSlotsPerImage, nimg), dim3(64), 0, c->dP, c->pyr, c->blur, c->kpSel,
+  LAUNCH(c, "k_describe", k_describe, dim3(P.kpSlotsPerImage, nimg), dim3(64), 0, c->dP, c->pyr, c->jobOrb, c->kpSel,
          c->kpSelCount, table, Y.record_bytes, Y.off_counts, Y.off_kp[0], Y.off_kp[1], Y.off_desc[0], Y.off_desc[1], img0);
   return PLI_OK;
 }
@@ -911,9 +918,7 @@ pli_status runOrb(pli_ctx* c, int img0, int nimg, uint8_t* table) {
 pli_status runLbdPre(pli_ctx* c, int img0, int nimg) {
   TraceRange range__("pli:lbd blur+sobel");
   const DevParams& P = c->hp;
-  LAUNCH(c, "k_blur_lbd", k_blur, dim3(c->l0Tiles, nimg), dim3(256), 0, c->jobLbd, c->pyr, P.pyrBlock, c->tmp8, c->tmp8Stride, img0);
-  dim3 g((P.W + 1023) / 1024, P.H, nimg);
-  LAUNCH(c, "k_sobel", k_sobel, g, dim3(256), 0, c->tmp8, c->tmp8Stride, P.W, P.H, c->tmpPitch, c->dxy, img0);
+  LAUNCH(c, "k_sobel", k_sobel, dim3(c->l0Tiles, nimg), dim3(256), 0, c->jobLbd, c->pyr, P.pyrBlock, c->dxy, img0);
   return PLI_OK;
 }
 
@@ -3005,6 +3010,7 @@ pli_status pli_debug_enable(pli_ctx* c, int32_t on) {
   HIPCHK(hipStreamSynchronize(c->stream));
   if (on && !c->angDbg) {
     pli_status st;
+    if ((st = c->dalloc(&c->blur, (size_t)c->hp.pyrBlock * c->NI)) != PLI_OK) return st;
     if ((st = c->dalloc(&c->angDbg, (size_t)c->hp.LW * c->hp.LH * c->NI)) != PLI_OK) return st;
     if ((st = c->dalloc(&c->lbdFloat, (size_t)c->NI * c->hp.klCap * 72)) != PLI_OK) return st;
     if (c->lsdF64 && (st = c->dalloc(&c->scaled64Dbg, (size_t)c->hp.LW * c->hp.LH * c->NI)) != PLI_OK) return st;
@@ -3025,6 +3031,7 @@ pli_status pli_debug_fetch(pli_ctx* c, int32_t image, int32_t what, int32_t arg,
     case PLI_DBG_BLUR_LEVEL: {
       if (arg < 0 || arg >= P.nlevels) return PLI_ERR_INVALID;
       const LevelGeom& G = P.lv[arg];
+      if (what == PLI_DBG_BLUR_LEVEL && !c->blur) { g_err = "pli_debug_enable was not on during the run"; return PLI_ERR_STATE; }
       if (!need((int64_t)G.w * G.h)) return dst ? PLI_ERR_CAPACITY : PLI_OK;
       const uint8_t* base = (what == PLI_DBG_PYRAMID_LEVEL ? c->pyr : c->blur) + (int64_t)image * P.pyrBlock + G.offset;
       HIPCHK(hipMemcpy2D(dst, G.w, base, G.pitch, G.w, G.h, hipMemcpyDeviceToHost));
@@ -3152,3 +3159,8 @@ pli_status pli_debug_fetch(pli_ctx* c, int32_t image, int32_t what, int32_t arg,
 }
 
 }  // extern "C"
+
+#ifdef PLI_DEV
+// development build: the reach k_describe's window is sized for (kernels.hpp, ORB_REACH), for the test that recomputes it from the pattern
+extern "C" int32_t pli_dev_orb_window_reach(void) { return ORB_REACH; }
+#endif
