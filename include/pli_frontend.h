@@ -537,6 +537,24 @@ pli_status pli_search_by_bow(pli_ctx* ctx, int32_t nkf, const int32_t* kf_off, c
                              const int32_t* f_node, int32_t nf, float nnratio, int32_t check_orientation, int32_t* matches,
                              int32_t* nmatches);
 
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) ORBmatcher.cc:823-963 (NLeft == -1 on both sides: the
+ * two-camera guards :858, :878 are not provided), for one keyframe pKF1 against nkf keyframes pKF2[k] in one call
+ * (LoopClosing::DetectCommonRegionsFromBoW's loop, LoopClosing.cc:528-540).
+ * desc1 / angle1 / node1 / valid1: n1 rows of pKF1 - mDescriptors, mvKeysUn[i].angle, the FeatureVector node that lists the
+ * feature (-1 = none, as for pli_search_by_bow), GetMapPointMatches()[i] set and not isBad().  Keyframe k owns rows
+ * kf_off[k] .. kf_off[k+1]-1 of kf_desc / kf_angle / kf_node / kf_valid (the same four of pKF2[k]); kf_off[0] = 0, non-decreasing.
+ * pKF1's features are walked in the reference's order (nodes ascending, a node's list ascending); a feature of pKF2[k] taken by an
+ * accepted match (vbMatched2) is no candidate for the later ones.  The distance test is strict: bestDist1 < TH_LOW = 50.  With
+ * check_orientation every angle must lie in [0, 360) (the angles are not read without it and may then be NULL).
+ * matches12: nkf x n1, the row within keyframe k that feature i of pKF1 is matched to, or -1, after the rotation filter
+ * (vpMatches12 as indices); nmatches[k] = the reference's return value.
+ * Caps: n1 and every keyframe's feature count <= PLI_BOW_MAX_FEATURES (else PLI_ERR_CAPACITY, nothing is truncated); nkf is
+ * bounded by device memory only.  nkf == 0, n1 == 0 and empty keyframes are valid (no matches). */
+pli_status pli_search_by_bow_kf(pli_ctx* ctx, const uint8_t* desc1, const float* angle1, const int32_t* node1,
+                                const uint8_t* valid1, int32_t n1, int32_t nkf, const int32_t* kf_off, const uint8_t* kf_desc,
+                                const float* kf_angle, const int32_t* kf_node, const uint8_t* kf_valid, float nnratio,
+                                int32_t check_orientation, int32_t* matches12, int32_t* nmatches);
+
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206, the branch
  * without second cameras (mpCamera2 == nullptr on both sides, NLeft == -1, keypoints = mvKeysUn), for one keyframe pKF1 against
  * nkf neighbours pKF2[k] in one call (LocalMapping::CreateNewMapPoints' loop, LocalMapping.cc:343-423; Tracking.cc:4705).

@@ -753,6 +753,68 @@ class PliORBmatcher {
       }
   }
 
+  // ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), ORBmatcher.cc:823-963, for keyframes
+  // of one camera each (NLeft == -1, mpCamera2 == nullptr): the node walk in pKF1's order, vbMatched2, bestDist1 < TH_LOW, the ratio
+  // test, the rotation histogram and ComputeThreeMaxima run on the GPU.  KeyFrameT needs N, NLeft, mDescriptors, mvKeysUn, mFeatVec
+  // (from transform), mpCamera2 and GetMapPointMatches().
+  template <class KeyFrameT>
+  int SearchByBoW(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12) {
+    std::vector<std::vector<MapPointT*>> matches;
+    std::vector<int> nmatches;
+    SearchByBoW(pKF1, std::vector<KeyFrameT*>(1, pKF2), matches, nmatches);
+    vpMatches12.swap(matches[0]);
+    return nmatches[0];
+  }
+
+  // (not in the reference) The same for every keyframe of vpKF2 in ONE device call: what the loop of
+  // LoopClosing::DetectCommonRegionsFromBoW over a candidate's covisible keyframes (LoopClosing.cc:528-540) computes, one
+  // vpMatches12 and one return value per keyframe.  GetMapPointMatches() is taken once per keyframe, at entry.
+  template <class KeyFrameT>
+  void SearchByBoW(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, std::vector<std::vector<MapPointT*>>& vvpMatches12,
+                   std::vector<int>& vnmatches) {
+    struct Table {
+      std::vector<int32_t> node;
+      std::vector<float> angle;
+      std::vector<uint8_t> desc, valid;
+    };
+    auto gather = [](KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, Table& T, const char* what) {
+      if (pKF->mpCamera2 || pKF->NLeft != -1)
+        throw std::logic_error("SearchByBoW: a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
+      const int n = pKF->N;
+      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, what);
+      T.node.insert(T.node.end(), node.begin(), node.end());
+      for (int i = 0; i < n; ++i) {
+        MapPointT* pMP = vpMapPoints[i];
+        T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);               // :862-866, :882-888
+        T.angle.push_back(pKF->mvKeysUn[i].angle);
+        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
+        T.desc.insert(T.desc.end(), d, d + 32);
+      }
+    };
+    const int nkf = (int)vpKF2.size(), n1 = pKF1->N;
+    Table T1, T2;
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    gather(pKF1, vpMapPoints1, T1, "SearchByBoW: pKF1->mFeatVec");
+    std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
+    std::vector<int32_t> kfOff(1, 0);
+    for (int k = 0; k < nkf; ++k) {
+      kfPoints[k] = vpKF2[k]->GetMapPointMatches();
+      gather(vpKF2[k], kfPoints[k], T2, "SearchByBoW: pKF2->mFeatVec");
+      kfOff.push_back(kfOff.back() + vpKF2[k]->N);
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
+    if (!fe) throw std::logic_error("SearchByBoW: no extractor has run yet (no device context)");
+    std::vector<int> matches;
+    fe->searchByBoWKF(T1.desc.data(), T1.angle.data(), T1.node.data(), T1.valid.data(), n1, nkf, kfOff.data(), T2.desc.data(),
+                      T2.angle.data(), T2.node.data(), T2.valid.data(), mfNNratio, mbCheckOrientation, matches, vnmatches);
+    vvpMatches12.assign((size_t)nkf, std::vector<MapPointT*>(vpMapPoints1.size(), static_cast<MapPointT*>(nullptr)));
+    for (int k = 0; k < nkf; ++k)
+      for (int i = 0; i < n1; ++i) {
+        const int j = matches[(size_t)k * n1 + i];
+        if (j >= 0) vvpMatches12[k][i] = kfPoints[k][j];               // :910
+      }
+  }
+
   // ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
   // const bool bOnlyStereo, const bool bCoarse), ORBmatcher.cc:965-1206, for keyframes of one pinhole camera each (mpCamera2 ==
   // nullptr, NLeft == -1).  F12 is ignored, as the reference ignores it: its gate is mpCamera->epipolarConstrain, which forms its

@@ -138,6 +138,17 @@ class Frontend {
     check(pli_search_by_bow(ctx_, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, nnratio,
                             checkOrientation ? 1 : 0, matches.data(), nmatches.data()));
   }
+  // ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) ORBmatcher.cc:823-963 (NLeft == -1) of one keyframe against nkf keyframes
+  // (include/pli_frontend.h pli_search_by_bow_kf): matches12 (nkf x n1) = the row of keyframe k each feature of pKF1 is matched to
+  // or -1, nmatches[k] = the reference's return value for keyframe k
+  void searchByBoWKF(const uint8_t* desc1, const float* angle1, const int32_t* node1, const uint8_t* valid1, int n1, int nkf,
+                     const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle, const int32_t* kfNode, const uint8_t* kfValid,
+                     float nnratio, bool checkOrientation, std::vector<int>& matches12, std::vector<int>& nmatches) {
+    matches12.assign((size_t)nkf * n1, -1);
+    nmatches.assign(nkf, 0);
+    check(pli_search_by_bow_kf(ctx_, desc1, angle1, node1, valid1, n1, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, nnratio,
+                               checkOrientation ? 1 : 0, matches12.data(), nmatches.data()));
+  }
   // ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206 (no second
   // cameras) of one keyframe against nkf neighbours (include/pli_frontend.h pli_search_for_triangulation): matches12 (nkf x n1) =
   // the neighbour's feature each feature of pKF1 is matched to or -1, nmatches[k] = the reference's return value for neighbour k

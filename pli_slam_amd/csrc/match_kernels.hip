@@ -13,6 +13,7 @@
 //   k_track_queries/candidates/assign/lines   frame-to-frame track matching of a batch (pli_batch_track)
 //   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 //   k_tri_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
+//   k_tri_sort + k_search_by_bow_kf     ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 #include "kernels.hpp"
 #include "device_prims.hpp"
@@ -1137,6 +1138,55 @@ __global__ __launch_bounds__(1024) void k_bow_frame_sort(const int* __restrict__
   }
 }
 
+// The ordered walk of both SearchByBoW kernels, by the whole block: key[0..m) (LDS, sorted) holds (first position of a common node in
+// the candidate side's sorted list << 16 | walking feature), so a run of equal upper halves is one node's walking features in
+// ascending index.  The waves take 64-key chunks in turn and walk every run that starts in their chunk, feature after feature; the
+// lanes hold the node's candidates sIdx[lo..hi) (looping over more than 64).  The reference's running best / second best (strict <:
+// ties keep the first listed, the lowest index) are the two smallest (distance, candidate index) keys.  owner[candidate] (LDS,
+// -1 = free) takes the walking feature of an accepted match (bestDist1 <= maxDist and the ratio test); hist takes its rotation
+// bin.  wDesc / wAngle and cDesc / cAngle are the walking and the candidate side's tables.  Returns this wave's accepted matches.
+__device__ __forceinline__ int bow_walk(const uint32_t* key, int m, const uint8_t* __restrict__ wDesc, const float* __restrict__ wAngle,
+                                        const uint32_t* __restrict__ sNode, const uint16_t* __restrict__ sIdx, int nListed,
+                                        const uint8_t* __restrict__ cDesc, const float* __restrict__ cAngle, short* owner, int* hist,
+                                        int maxDist, float nnratio, int checkOri) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  int nm = 0;
+  for (int c0 = wave * 64; c0 < m; c0 += nwaves * 64) {
+    const int p = c0 + lane;
+    unsigned long long starts = __builtin_amdgcn_ballot_w64(p < m && (p == 0 || (key[p] >> 16) != (key[p - 1] >> 16)));
+    while (starts) {
+      const int s = c0 + __builtin_ctzll(starts);
+      starts &= starts - 1;
+      const uint32_t lo = key[s] >> 16;
+      const int hi = bow_lower_bound(sNode, (int)lo + 1, nListed, sNode[lo] + 1u);   // (node ids are < 2^31: no wrap)
+      for (int q = s; q < m && (key[q] >> 16) == lo; ++q) {
+        const int j = (int)(key[q] & 0xFFFFu);
+        uint64_t dk[4];
+        load_desc(wDesc + (int64_t)j * 32, dk);
+        WaveTop2 top;
+        for (int t = (int)lo + lane; t < hi; t += 64) {
+          const int fi = sIdx[t];
+          if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319, :884)
+          uint64_t df[4];
+          load_desc(cDesc + (int64_t)fi * 32, df);
+          top.push(((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi);
+        }
+        const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
+        if (m1 == ~0ull) continue;
+        const int bestDist1 = (int)(m1 >> 32), bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
+        if (bestDist1 <= maxDist && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
+          const int fi = (int)(m1 & 0xFFFFFFFFull);
+          owner[fi] = (short)j;                                   // every lane stores the same value
+          ++nm;
+          if (checkOri && lane == 0) atomicAdd(&hist[bow_rot_bin(wAngle[j], cAngle[fi])], 1);
+          __threadfence_block();
+        }
+      }
+    }
+  }
+  return nm;
+}
+
 // grid = keyframes; LDS: 48 ints + keyCap keys (a power of two >= every keyframe's feature count) + nf shorts
 __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
                                                        const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
@@ -1150,7 +1200,7 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
   int* misc = bowLds + 32;                                        // [0] keys, [1] matches, [2..4] the bins ComputeThreeMaxima keeps
   uint32_t* key = reinterpret_cast<uint32_t*>(bowLds + 48);
   short* owner = reinterpret_cast<short*>(key + keyCap);          // per frame feature: the keyframe feature that took it, -1 free
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base;
   const int nfl = *nListed;
   for (int i = tid; i < 48; i += blockDim.x) bowLds[i] = 0;
@@ -1168,40 +1218,8 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
   for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
   __syncthreads();
   lds_bitonic_sort(key, nullptr, n2);
-  int nm = 0;
-  for (int c0 = wave * 64; c0 < m; c0 += nwaves * 64) {
-    const int p = c0 + lane;
-    unsigned long long starts = __builtin_amdgcn_ballot_w64(p < m && (p == 0 || (key[p] >> 16) != (key[p - 1] >> 16)));
-    while (starts) {
-      const int s = c0 + __builtin_ctzll(starts);
-      starts &= starts - 1;
-      const uint32_t lo = key[s] >> 16;
-      const int hi = bow_lower_bound(sNode, (int)lo + 1, nfl, sNode[lo] + 1u);   // (node ids are < 2^31: no wrap)
-      for (int q = s; q < m && (key[q] >> 16) == lo; ++q) {
-        const int j = (int)(key[q] & 0xFFFFu);
-        uint64_t dk[4];
-        load_desc(kfDesc + (int64_t)(base + j) * 32, dk);
-        WaveTop2 top;
-        for (int t = (int)lo + lane; t < hi; t += 64) {
-          const int fi = sIdx[t];
-          if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319)
-          uint64_t df[4];
-          load_desc(fDesc + (int64_t)fi * 32, df);
-          top.push(((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi);
-        }
-        const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
-        if (m1 == ~0ull) continue;
-        const int bestDist1 = (int)(m1 >> 32), bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-        if (bestDist1 <= BOW_TH_LOW && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
-          const int fi = (int)(m1 & 0xFFFFFFFFull);
-          owner[fi] = (short)j;                                   // every lane stores the same value
-          ++nm;
-          if (checkOri && lane == 0) atomicAdd(&hist[bow_rot_bin(kfAngle[base + j], fAngle[fi])], 1);
-          __threadfence_block();
-        }
-      }
-    }
-  }
+  const int nm = bow_walk(key, m, kfDesc + (int64_t)base * 32, kfAngle + base, sNode, sIdx, nfl, fDesc, fAngle, owner, hist, BOW_TH_LOW,
+                          nnratio, checkOri);
   if (lane == 0 && nm) atomicAdd(&misc[1], nm);
   __syncthreads();
   if (tid == 0) {
@@ -1250,22 +1268,26 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
 // ---------------------------------------------------------------------------
 constexpr int TRI_STAT = 32;                                     // ints per neighbour: 30 bins, [30] the match counter
 
-// grid = neighbours; keyCap = a power of two >= every neighbour's feature count (<= 8192); LDS: keyCap * 6 bytes
+// grid = neighbours; keyCap = a power of two >= every neighbour's feature count (<= 8192); LDS: keyCap * 6 bytes.  A feature may
+// be taken when (kfFlag != 0) == (flagWanted != 0): SearchForTriangulation passes "has a map point" and 0, SearchByBoW(KF, KF)
+// passes "map point set and not bad" and 1 (no stereo table, no stat: NULL).
 __global__ __launch_bounds__(1024) void k_tri_sort(const int* __restrict__ kfOff, const int* __restrict__ kfNode,
-                                                   const uint8_t* __restrict__ kfHasMp, const uint8_t* __restrict__ kfStereo,
-                                                   int onlyStereo, int keyCap, uint32_t* __restrict__ sNode,
-                                                   uint16_t* __restrict__ sIdx, int* __restrict__ nListed, int* __restrict__ stat) {
+                                                   const uint8_t* __restrict__ kfFlag, int flagWanted,
+                                                   const uint8_t* __restrict__ kfStereo, int onlyStereo, int keyCap,
+                                                   uint32_t* __restrict__ sNode, uint16_t* __restrict__ sIdx,
+                                                   int* __restrict__ nListed, int* __restrict__ stat) {
   extern __shared__ __align__(16) uint32_t triSortLds[];
   const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base;
   const int n = min(pow2_ceil(max(nk, 1)), keyCap);
   uint32_t* key = triSortLds;
   uint16_t* val = reinterpret_cast<uint16_t*>(key + keyCap);
-  for (int i = threadIdx.x; i < TRI_STAT; i += blockDim.x) stat[kf * TRI_STAT + i] = 0;
+  if (stat)
+    for (int i = threadIdx.x; i < TRI_STAT; i += blockDim.x) stat[kf * TRI_STAT + i] = 0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     uint32_t k = 0xFFFFFFFFu;
     if (i < nk) {
       const int node = kfNode[base + i];
-      if (node >= 0 && !kfHasMp[base + i] && (!onlyStereo || kfStereo[base + i])) k = (uint32_t)node;
+      if (node >= 0 && (kfFlag[base + i] != 0) == (flagWanted != 0) && (!onlyStereo || kfStereo[base + i])) k = (uint32_t)node;
     }
     key[i] = k;
     val[i] = (uint16_t)i;
@@ -1374,6 +1396,90 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
     const int b = bow_rot_bin(kp1[i].angle, kfKp[base + j].angle);
     if (b != ind1 && b != ind2 && b != ind3) row[i] = -1;
   }
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (ORBmatcher.cc:823-963, NLeft == -1 on both sides) for one
+// keyframe pKF1 against a batch of keyframes pKF2[k] (LoopClosing::DetectCommonRegionsFromBoW's loop, LoopClosing.cc:528-540).
+//
+// Against SearchByBoW(KF, Frame) the sides swap: pKF1 is walked in list order and pKF2's features are the ones taken away
+// (vbMatched2), both sides carry the map-point gate, the distance test is strict (bestDist1 < TH_LOW) and the result is indexed by
+// pKF1's feature.
+//
+// Why the reference's sequential walk may run in parallel: a feature is listed in ONE node of its FeatureVector, and
+// vbMatched2[idx2] is only read and written while the node that lists idx2 is walked, that is by pKF1's features of that node.  So
+// the common nodes are independent of each other, the pairs (pKF1, pKF2[k]) are independent of each other (vbMatched2 is per call),
+// and only pKF1's features inside one node must be taken in list order (ascending index).  The rotation histogram and nmatches are
+// sums over the matches; vbMatched2 is not given back by the rotation filter and is not read after it.
+//
+//   k_tri_sort          one workgroup per pKF2[k]: its valid features sorted by node id (the candidate list differs per pair).
+//   k_search_by_bow_kf  one workgroup per pair: pKF1's valid features whose node k lists (with a valid feature: a node without one
+//                       has no candidate) become (first position of the node in k's sorted list, idx1) keys, 13 bits each, sorted
+//                       in LDS; bow_walk takes the runs.  owner[idx2] (LDS) is vbMatched2 with the idx1 that took it; thread 0
+//                       runs three_maxima; the owner table is inverted in LDS with the filter applied and written as the row.
+// Two launches per call, whatever nkf.
+// ---------------------------------------------------------------------------
+// grid = pairs; keyCap = a power of two >= n1, ownerCap >= every pKF2's feature count; LDS: 48 ints + keyCap keys + ownerCap shorts
+__global__ __launch_bounds__(512) void k_search_by_bow_kf(const uint8_t* __restrict__ desc1, const float* __restrict__ angle1,
+                                                          const int* __restrict__ node1, const uint8_t* __restrict__ valid1, int n1,
+                                                          const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
+                                                          const float* __restrict__ kfAngle, const uint32_t* __restrict__ sNode,
+                                                          const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
+                                                          int keyCap, float nnratio, int checkOri, int* __restrict__ matches12,
+                                                          int* __restrict__ nmatchesOut) {
+  extern __shared__ __align__(16) int bowKfLds[];
+  int* hist = bowKfLds;                                           // 30 bins (32 ints)
+  int* misc = bowKfLds + 32;                                      // [0] keys, [1] matches, [2..4] the bins ComputeThreeMaxima keeps
+  uint32_t* key = reinterpret_cast<uint32_t*>(bowKfLds + 48);
+  short* owner = reinterpret_cast<short*>(key + keyCap);          // per feature of pKF2: the feature of pKF1 that took it, -1 free
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base, nl = nListed[kf];
+  const uint32_t* sn = sNode + base;
+  const uint16_t* si = sIdx + base;
+  int* row = matches12 + (int64_t)kf * n1;
+  for (int i = tid; i < 48; i += blockDim.x) bowKfLds[i] = 0;
+  for (int i = tid; i < nk; i += blockDim.x) owner[i] = -1;
+  __syncthreads();
+  for (int i = tid; i < n1; i += blockDim.x) {
+    const int node = node1[i];
+    if (!valid1[i] || node < 0) continue;                         // :862-866 (a feature in no node is never visited)
+    const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
+    if (lo < nl && sn[lo] == (uint32_t)node) key[atomicAdd(&misc[0], 1)] = ((uint32_t)lo << 16) | (uint32_t)i;
+  }
+  __syncthreads();
+  const int m = misc[0], n2 = pow2_ceil(m);
+  for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
+  __syncthreads();
+  lds_bitonic_sort(key, nullptr, n2);
+  const int nm = bow_walk(key, m, desc1, angle1, sn, si, nl, kfDesc + (int64_t)base * 32, kfAngle + base, owner, hist, BOW_TH_LOW - 1,
+                          nnratio, checkOri);                     // bestDist1 < TH_LOW :906
+  if (lane == 0 && nm) atomicAdd(&misc[1], nm);
+  __syncthreads();
+  if (tid == 0) {
+    int total = misc[1], ind1 = -1, ind2 = -1, ind3 = -1;
+    if (checkOri) {
+      three_maxima(hist, ind1, ind2, ind3);
+      for (int i = 0; i < HISTO_LENGTH; ++i)
+        if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
+    }
+    misc[2] = ind1; misc[3] = ind2; misc[4] = ind3;
+    nmatchesOut[kf] = total;
+  }
+  int* inv = reinterpret_cast<int*>(key);                         // the keys are done: vpMatches12 as indices, n1 <= keyCap
+  for (int i = tid; i < n1; i += blockDim.x) inv[i] = -1;
+  __syncthreads();
+  const int ind1 = misc[2], ind2 = misc[3], ind3 = misc[4];
+  for (int i2 = tid; i2 < nk; i2 += blockDim.x) {
+    const int i = owner[i2];
+    if (i < 0) continue;
+    if (checkOri) {
+      const int b = bow_rot_bin(angle1[i], kfAngle[base + i2]);
+      if (b != ind1 && b != ind2 && b != ind3) continue;
+    }
+    inv[i] = i2;
+  }
+  __syncthreads();
+  for (int i = tid; i < n1; i += blockDim.x) row[i] = inv[i];
 }
 
 // ---------------------------------------------------------------------------

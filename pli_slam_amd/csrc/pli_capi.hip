@@ -2789,6 +2789,77 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   return PLI_OK;
 }
 
+pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* angle1, const int32_t* node1, const uint8_t* valid1,
+                                int32_t n1, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
+                                const int32_t* kfNode, const uint8_t* kfValid, float nnratio, int32_t checkOri, int32_t* matches12,
+                                int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!desc1 || !node1 || !valid1 || (checkOri && !angle1))) ||
+      (nkf > 0 && (!kfOff || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
+  int maxNk = 0;
+  for (int k = 0; k < nkf; ++k) {
+    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
+    const int nk = kfOff[k + 1] - kfOff[k];
+    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
+    maxNk = std::max(maxNk, nk);
+  }
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = kfOff[nkf];
+  if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  for (int64_t i = 0; i < total; ++i)
+    if (kfNode[i] < -1) { g_err = "kf_node: a node id or -1"; return PLI_ERR_INVALID; }
+  for (int i = 0; i < n1; ++i)
+    if (node1[i] < -1) { g_err = "node1: a node id or -1"; return PLI_ERR_INVALID; }
+  if (checkOri) {
+    // (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
+    for (int64_t i = 0; i < total; ++i)
+      if (!(kfAngle[i] >= 0.f && kfAngle[i] < 360.f)) { g_err = "kf_angle outside [0, 360)"; return PLI_ERR_INVALID; }
+    for (int i = 0; i < n1; ++i)
+      if (!(angle1[i] >= 0.f && angle1[i] < 360.f)) { g_err = "angle1 outside [0, 360)"; return PLI_ERR_INVALID; }
+  }
+  if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
+  auto dA1 = plan.add<float>(n1);
+  auto dN1 = plan.add<int>(n1);
+  auto dV1 = plan.add<uint8_t>(n1);
+  auto dOff = plan.add<int>((size_t)nkf + 1);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dKa = plan.add<float>(total);
+  auto dKn = plan.add<int>(total);
+  auto dKv = plan.add<uint8_t>(total);
+  auto dSn = plan.add<uint32_t>(total);
+  auto dSi = plan.add<uint16_t>(total);
+  auto dListed = plan.add<int>(nkf);
+  auto dM = plan.add<int>((size_t)nkf * n1);
+  auto dN = plan.add<int>(nkf);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
+  if (checkOri) HIPCHK(upload(c, dA1, angle1, n1));
+  HIPCHK(upload(c, dN1, node1, n1));
+  HIPCHK(upload(c, dV1, valid1, n1));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  if (checkOri) HIPCHK(upload(c, dKa, kfAngle, total));
+  HIPCHK(upload(c, dKn, kfNode, total));
+  HIPCHK(upload(c, dKv, kfValid, total));
+  int sortCap = 1, keyCap = 1;
+  while (sortCap < maxNk) sortCap <<= 1;
+  while (keyCap < n1) keyCap <<= 1;
+  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)sortCap * 6, dOff, dKn, dKv, 1, (const uint8_t*)nullptr, 0, sortCap,
+         dSn, dSi, dListed, (int*)nullptr);
+  LAUNCH(c, "k_search_by_bow_kf", k_search_by_bow_kf, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)maxNk * 2, 16),
+         dD1, dA1, dN1, dV1, n1, dOff, dKd, dKa, dSn, dSi, dListed, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
+  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
+  HIPCHK(download(c, nmatches, dN, nkf));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
                                         const uint8_t* hasMp1, const uint8_t* stereo1, int32_t n1, int32_t nkf, const int32_t* kfOff,
                                         const pli_keypoint* kfKp, const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
@@ -2866,8 +2937,8 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   int keyCap = 1;
   while (keyCap < maxNk) keyCap <<= 1;
   const int perBlock = 4 * 4;                                            // k_tri_match: 4 waves x TRI_PER_WAVE features of pKF1
-  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, dKn, dKm, dKs, onlyStereo ? 1 : 0, keyCap, dSn, dSi,
-         dListed, dStat);
+  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, dKn, dKm, 0, dKs, onlyStereo ? 1 : 0, keyCap, dSn,
+         dSi, dListed, dStat);
   LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1, dS1, n1, dOff, dKk,
          dKd, dKs, dSn, dSi, dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS, onlyStereo ? 1 : 0, coarse ? 1 : 0,
          checkOri ? 1 : 0, dM, dStat);

@@ -240,6 +240,34 @@ class Frontend:
                                        nnratio, int(check_orientation), ptr(matches), ptr(nmatches)))
         return matches, nmatches
 
+    def search_by_bow_kf(self, desc1, angle1, node1, valid1, kfs, nnratio=0.75, check_orientation=True):
+        """ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:823-963, NLeft == -1) of keyframe 1 against every
+        keyframe of `kfs`, in one call (loop closing).  desc1 / angle1 / node1 / valid1 and each (desc, angle, node, valid) of
+        kfs as in search_by_bow; the map-point gate holds on both sides.  Returns (matches12[nkf, n1]: the row of keyframe k that
+        feature i of keyframe 1 is matched to or -1, nmatches[nkf])."""
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        n1 = d1.shape[0]
+        a1 = np.ascontiguousarray(angle1, np.float32).reshape(n1)
+        nd1 = np.ascontiguousarray(node1, np.int32).reshape(n1)
+        v1 = np.ascontiguousarray(valid1, np.uint8).reshape(n1)
+        nkf = len(kfs)
+        off = np.zeros(nkf + 1, np.int32)
+        for k, kf in enumerate(kfs):
+            off[k + 1] = off[k] + np.asarray(kf[0]).reshape(-1, 32).shape[0]
+
+        def cat(i, dt, shape):
+            parts = [np.asarray(kf[i], dt).reshape(shape) for kf in kfs]
+            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0,) + shape[1:], dt), dt)
+        kd, ka = cat(0, np.uint8, (-1, 32)), cat(1, np.float32, (-1,))
+        kn, kv = cat(2, np.int32, (-1,)), cat(3, np.uint8, (-1,))
+        if not (len(ka) == len(kn) == len(kv) == len(kd)):
+            raise ValueError("every keyframe needs one angle, node and valid flag per descriptor")
+        matches = np.full((nkf, n1), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        check(self.L.pli_search_by_bow_kf(self.h, ptr(d1), ptr(a1), ptr(nd1), ptr(v1), n1, nkf, ptr(off), ptr(kd), ptr(ka), ptr(kn),
+                                          ptr(kv), nnratio, int(check_orientation), ptr(matches), ptr(nmatches)))
+        return matches, nmatches
+
     def search_for_triangulation(self, kf1, kfs, only_stereo=False, coarse=False, check_orientation=False):
         """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:965-1206, no
         second cameras) of keyframe `kf1` against every neighbour of `kfs`, in one call.  kf1: (kp, desc, node, has_mp, stereo) -
