@@ -547,6 +547,46 @@ std::vector<int32_t> featureNodes(const FeatVecT& fv, int n, const char* what) {
   return node;
 }
 
+// ---- what the searches against a batch of keyframes (SearchByBoW, SearchForTriangulation, Fuse) share on the host ----
+// The device context the extractors created; `who` names the caller in the message.
+inline std::shared_ptr<pli::Frontend> deviceContext(const char* who) {
+  std::shared_ptr<pli::Frontend> fe = Registry::get().any();
+  if (!fe) throw std::logic_error(std::string(who) + ": no extractor has run yet (no device context)");
+  return fe;
+}
+
+inline pli_keypoint keypoint(const cv::KeyPoint& k) { return pli_keypoint{k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave}; }
+
+// The flat tables of a batch: keyframe k is rows off[k] .. off[k + 1].  A matcher derives from it and adds its own columns.
+struct KfTable {
+  std::vector<int32_t> off = std::vector<int32_t>(1, 0), node;
+  std::vector<uint8_t> desc;
+};
+// appends the n rows of a keyframe's (or frame's) mDescriptors and closes its row range
+template <class MatT>
+void appendDescriptors(KfTable& T, const MatT& descriptors, int n) {
+  for (int i = 0; i < n; ++i) {
+    const uint8_t* d = descriptors.template ptr<uint8_t>(i);
+    T.desc.insert(T.desc.end(), d, d + 32);
+  }
+  T.off.push_back(T.off.back() + n);
+}
+// appends the node of each of its n features (featureNodes; `what` names the FeatureVector in its messages)
+template <class FeatVecT>
+void appendNodes(KfTable& T, const FeatVecT& fv, int n, const char* what) {
+  const std::vector<int32_t> node = featureNodes(fv, n, what);
+  T.node.insert(T.node.end(), node.begin(), node.end());
+}
+// The nkf x n table of indices a batched search returns: fn(k, i, j) for every match j >= 0 of item i in keyframe k, in index order.
+template <class Fn>
+void forEachMatch(const std::vector<int>& matches, int nkf, int n, Fn fn) {
+  for (int k = 0; k < nkf; ++k)
+    for (int i = 0; i < n; ++i) {
+      const int j = matches[(size_t)k * n + i];
+      if (j >= 0) fn(k, i, j);
+    }
+}
+
 // The host geometry of ORBmatcher::SearchForTriangulation for keyframes of one pinhole camera each: the epipole
 // ep = pKF2->mpCamera->project(R2w * Cw + t2w) (ORBmatcher.cc:972-977, Pinhole.cpp:30-33), R12 = R1w * R2w.t(),
 // t12 = -R1w * R2w.t() * t2w + t1w (:991-992) and F12 = K1.t().inv() * t12x * R12 * K2.inv() (Pinhole.cpp:124-127).
@@ -713,44 +753,24 @@ class PliORBmatcher {
                    std::vector<int>& vnmatches) {
     if (F.Nleft != -1) throw std::logic_error("SearchByBoW: a frame of two cameras (F.Nleft != -1) is not supported");
     const int nf = F.N, nkf = (int)vpKFs.size();
-    const std::vector<int32_t> fNode = pli_detail::featureNodes(F.mFeatVec, nf, "SearchByBoW: F.mFeatVec");
+    pli_detail::KfTable TF;
+    pli_detail::appendNodes(TF, F.mFeatVec, nf, "SearchByBoW: F.mFeatVec");
+    pli_detail::appendDescriptors(TF, F.mDescriptors, nf);
     std::vector<float> fAngle((size_t)nf);
-    std::vector<uint8_t> fDesc((size_t)nf * 32);
-    for (int i = 0; i < nf; ++i) {
-      fAngle[i] = F.mvKeys[i].angle;
-      std::memcpy(&fDesc[(size_t)i * 32], F.mDescriptors.template ptr<uint8_t>(i), 32);
-    }
+    for (int i = 0; i < nf; ++i) fAngle[i] = F.mvKeys[i].angle;
     std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
-    std::vector<int32_t> kfOff(1, 0), kfNode;
-    std::vector<float> kfAngle;
-    std::vector<uint8_t> kfDesc, kfValid;
+    BowTable T;
     for (int k = 0; k < nkf; ++k) {
-      KeyFrameT* pKF = vpKFs[k];
-      if (pKF->mpCamera2) throw std::logic_error("SearchByBoW: a keyframe of two cameras (mpCamera2 set) is not supported");
-      const int n = pKF->N;
-      kfPoints[k] = pKF->GetMapPointMatches();
-      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, "SearchByBoW: pKF->mFeatVec");
-      kfNode.insert(kfNode.end(), node.begin(), node.end());
-      for (int i = 0; i < n; ++i) {
-        MapPointT* pMP = kfPoints[k][i];
-        kfValid.push_back(pMP && !pMP->isBad() ? 1 : 0);
-        kfAngle.push_back(pKF->mvKeysUn[i].angle);
-        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
-        kfDesc.insert(kfDesc.end(), d, d + 32);
-      }
-      kfOff.push_back(kfOff.back() + n);
+      if (vpKFs[k]->mpCamera2) throw std::logic_error("SearchByBoW: a keyframe of two cameras (mpCamera2 set) is not supported");
+      kfPoints[k] = vpKFs[k]->GetMapPointMatches();
+      bowGatherKeyFrame(vpKFs[k], kfPoints[k], "SearchByBoW: pKF->mFeatVec", T);
     }
-    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
-    if (!fe) throw std::logic_error("SearchByBoW: no extractor has run yet (no device context)");
     std::vector<int> matches;
-    fe->searchByBoW(nkf, kfOff.data(), kfDesc.data(), kfAngle.data(), kfNode.data(), kfValid.data(), fDesc.data(), fAngle.data(),
-                    fNode.data(), nf, mfNNratio, mbCheckOrientation, matches, vnmatches);
+    pli_detail::deviceContext("SearchByBoW")->searchByBoW(nkf, T.off.data(), T.desc.data(), T.angle.data(), T.node.data(), T.valid.data(),
+                                                         TF.desc.data(), fAngle.data(), TF.node.data(), nf, mfNNratio,
+                                                         mbCheckOrientation, matches, vnmatches);
     vvpMapPointMatches.assign((size_t)nkf, std::vector<MapPointT*>((size_t)nf, static_cast<MapPointT*>(nullptr)));
-    for (int k = 0; k < nkf; ++k)
-      for (int i = 0; i < nf; ++i) {
-        const int j = matches[(size_t)k * nf + i];
-        if (j >= 0) vvpMapPointMatches[k][i] = kfPoints[k][j];
-      }
+    pli_detail::forEachMatch(matches, nkf, nf, [&](int k, int i, int j) { vvpMapPointMatches[k][i] = kfPoints[k][j]; });
   }
 
   // ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), ORBmatcher.cc:823-963, for keyframes
@@ -772,47 +792,26 @@ class PliORBmatcher {
   template <class KeyFrameT>
   void SearchByBoW(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, std::vector<std::vector<MapPointT*>>& vvpMatches12,
                    std::vector<int>& vnmatches) {
-    struct Table {
-      std::vector<int32_t> node;
-      std::vector<float> angle;
-      std::vector<uint8_t> desc, valid;
-    };
-    auto gather = [](KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, Table& T, const char* what) {
+    auto gather = [](KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const char* what, BowTable& T) {
       if (pKF->mpCamera2 || pKF->NLeft != -1)
         throw std::logic_error("SearchByBoW: a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
-      const int n = pKF->N;
-      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, what);
-      T.node.insert(T.node.end(), node.begin(), node.end());
-      for (int i = 0; i < n; ++i) {
-        MapPointT* pMP = vpMapPoints[i];
-        T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);               // :862-866, :882-888
-        T.angle.push_back(pKF->mvKeysUn[i].angle);
-        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
-        T.desc.insert(T.desc.end(), d, d + 32);
-      }
+      bowGatherKeyFrame(pKF, vpMapPoints, what, T);                    // :862-866, :882-888
     };
     const int nkf = (int)vpKF2.size(), n1 = pKF1->N;
-    Table T1, T2;
+    BowTable T1, T2;
     const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
-    gather(pKF1, vpMapPoints1, T1, "SearchByBoW: pKF1->mFeatVec");
+    gather(pKF1, vpMapPoints1, "SearchByBoW: pKF1->mFeatVec", T1);
     std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
-    std::vector<int32_t> kfOff(1, 0);
     for (int k = 0; k < nkf; ++k) {
       kfPoints[k] = vpKF2[k]->GetMapPointMatches();
-      gather(vpKF2[k], kfPoints[k], T2, "SearchByBoW: pKF2->mFeatVec");
-      kfOff.push_back(kfOff.back() + vpKF2[k]->N);
+      gather(vpKF2[k], kfPoints[k], "SearchByBoW: pKF2->mFeatVec", T2);
     }
-    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
-    if (!fe) throw std::logic_error("SearchByBoW: no extractor has run yet (no device context)");
     std::vector<int> matches;
-    fe->searchByBoWKF(T1.desc.data(), T1.angle.data(), T1.node.data(), T1.valid.data(), n1, nkf, kfOff.data(), T2.desc.data(),
-                      T2.angle.data(), T2.node.data(), T2.valid.data(), mfNNratio, mbCheckOrientation, matches, vnmatches);
+    pli_detail::deviceContext("SearchByBoW")->searchByBoWKF(T1.desc.data(), T1.angle.data(), T1.node.data(), T1.valid.data(), n1, nkf,
+                                                           T2.off.data(), T2.desc.data(), T2.angle.data(), T2.node.data(),
+                                                           T2.valid.data(), mfNNratio, mbCheckOrientation, matches, vnmatches);
     vvpMatches12.assign((size_t)nkf, std::vector<MapPointT*>(vpMapPoints1.size(), static_cast<MapPointT*>(nullptr)));
-    for (int k = 0; k < nkf; ++k)
-      for (int i = 0; i < n1; ++i) {
-        const int j = matches[(size_t)k * n1 + i];
-        if (j >= 0) vvpMatches12[k][i] = kfPoints[k][j];               // :910
-      }
+    pli_detail::forEachMatch(matches, nkf, n1, [&](int k, int i, int j) { vvpMatches12[k][i] = kfPoints[k][j]; });   // :910
   }
 
   // ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
@@ -837,23 +836,19 @@ class PliORBmatcher {
   void SearchForTriangulation(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2,
                               std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, std::vector<int>& vnmatches,
                               const bool bOnlyStereo, const bool bCoarse = false) {
-    struct Table {
+    struct Table : pli_detail::KfTable {
       std::vector<pli_keypoint> kp;
-      std::vector<uint8_t> desc, hasMp, stereo;
-      std::vector<int32_t> node;
+      std::vector<uint8_t> hasMp, stereo;
       float R[9], t[3], K[4];
     };
     auto gather = [](KeyFrameT* pKF, Table& T, const char* what) {
       if (pKF->mpCamera2 || pKF->NLeft != -1)
         throw std::logic_error("SearchForTriangulation: a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
       const int n = pKF->N;
-      const std::vector<int32_t> node = pli_detail::featureNodes(pKF->mFeatVec, n, what);
-      T.node.insert(T.node.end(), node.begin(), node.end());
+      pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
+      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
       for (int i = 0; i < n; ++i) {
-        const cv::KeyPoint& k = pKF->mvKeysUn[i];
-        T.kp.push_back(pli_keypoint{k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave});
-        const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
-        T.desc.insert(T.desc.end(), d, d + 32);
+        T.kp.push_back(pli_detail::keypoint(pKF->mvKeysUn[i]));
         T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
         T.stereo.push_back(pKF->mvuRight[i] >= 0 ? 1 : 0);
       }
@@ -871,27 +866,21 @@ class PliORBmatcher {
     const int n1 = pKF1->N;
     const cv::Mat Cw = pKF1->GetCameraCenter();
     const float cw[3] = {Cw.template at<float>(0), Cw.template at<float>(1), Cw.template at<float>(2)};
-    std::vector<int32_t> kfOff(1, 0);
     std::vector<float> F12((size_t)nkf * 9 + 1), ep((size_t)nkf * 2 + 1);
     for (int k = 0; k < nkf; ++k) {
       gather(vpKF2[k], T2, "SearchForTriangulation: pKF2->mFeatVec");
-      kfOff.push_back(kfOff.back() + vpKF2[k]->N);
       pli_detail::triangulationGeometry(T1.R, T1.t, cw, T1.K, T2.R, T2.t, T2.K, &F12[(size_t)k * 9], &ep[(size_t)k * 2]);
     }
-    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
-    if (!fe) throw std::logic_error("SearchForTriangulation: no extractor has run yet (no device context)");
     std::vector<int> matches;
-    fe->searchForTriangulation(T1.kp.data(), T1.desc.data(), T1.node.data(), T1.hasMp.data(), T1.stereo.data(), n1, nkf, kfOff.data(),
-                               T2.kp.data(), T2.desc.data(), T2.node.data(), T2.hasMp.data(), T2.stereo.data(), F12.data(), ep.data(),
-                               bOnlyStereo, bCoarse, mbCheckOrientation, matches, vnmatches);
+    pli_detail::deviceContext("SearchForTriangulation")
+        ->searchForTriangulation(T1.kp.data(), T1.desc.data(), T1.node.data(), T1.hasMp.data(), T1.stereo.data(), n1, nkf, T2.off.data(),
+                                 T2.kp.data(), T2.desc.data(), T2.node.data(), T2.hasMp.data(), T2.stereo.data(), F12.data(), ep.data(),
+                                 bOnlyStereo, bCoarse, mbCheckOrientation, matches, vnmatches);
     vvMatchedPairs.assign((size_t)nkf, std::vector<std::pair<size_t, size_t>>());
-    for (int k = 0; k < nkf; ++k) {
-      vvMatchedPairs[k].reserve(vnmatches[k]);
-      for (int i = 0; i < n1; ++i) {                                    // vMatches12 read in index order (:1198-1203)
-        const int j = matches[(size_t)k * n1 + i];
-        if (j >= 0) vvMatchedPairs[k].push_back(std::make_pair((size_t)i, (size_t)j));
-      }
-    }
+    for (int k = 0; k < nkf; ++k) vvMatchedPairs[k].reserve(vnmatches[k]);
+    pli_detail::forEachMatch(matches, nkf, n1, [&](int k, int i, int j) {      // vMatches12 read in index order (:1198-1203)
+      vvMatchedPairs[k].push_back(std::make_pair((size_t)i, (size_t)j));
+    });
   }
 
   // ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight), ORBmatcher.cc:
@@ -950,8 +939,7 @@ class PliORBmatcher {
       std::memcpy(&desc[(size_t)i * 32], pMP->GetDescriptor().template ptr<uint8_t>(), 32);
       for (int k = 0; k < nkf; ++k) skip[(size_t)k * nmp + i] = pMP->IsInKeyFrame(vpTargetKFs[k]) ? 1 : 0;
     }
-    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
-    if (!fe) throw std::logic_error("Fuse: no extractor has run yet (no device context)");
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("Fuse");
     const std::vector<float>& levelRatio = fuseLevelRatio(vpTargetKFs[0]);
     std::vector<int> best;
     fe->fuseSearch(pts.data(), desc.data(), nmp, nkf, T.off.data(), T.kp.data(), T.desc.data(), T.uright.data(), T.pose.data(),
@@ -1044,8 +1032,7 @@ class PliORBmatcher {
       std::memcpy(&desc[(size_t)i * 32], vpPoints[i]->GetDescriptor().template ptr<uint8_t>(), 32);
       skip[i] = spAlreadyFound.count(vpPoints[i]) ? 1 : 0;                  // :1639
     }
-    std::shared_ptr<pli::Frontend> fe = pli_detail::Registry::get().any();
-    if (!fe) throw std::logic_error("Fuse: no extractor has run yet (no device context)");
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("Fuse");
     std::vector<int> best;
     fe->fuseSearch(pts.data(), desc.data(), nmp, 1, T.off.data(), T.kp.data(), T.desc.data(), T.uright.data(), T.pose.data(), skip.data(),
                    T.cam, th, fuseLevelRatio(pKF), false, best);
@@ -1090,10 +1077,24 @@ class PliORBmatcher {
   }
 
  protected:
-  struct FuseTables {
-    std::vector<int32_t> off = std::vector<int32_t>(1, 0);
+  // the keyframe side of both SearchByBoW forms; valid = the map point is set and not bad
+  struct BowTable : pli_detail::KfTable {
+    std::vector<float> angle;
+    std::vector<uint8_t> valid;
+  };
+  template <class KeyFrameT>
+  static void bowGatherKeyFrame(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const char* what, BowTable& T) {
+    const int n = pKF->N;
+    pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
+    pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
+    for (int i = 0; i < n; ++i) {
+      MapPointT* pMP = vpMapPoints[i];
+      T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);
+      T.angle.push_back(pKF->mvKeysUn[i].angle);
+    }
+  }
+  struct FuseTables : pli_detail::KfTable {
     std::vector<pli_keypoint> kp;
-    std::vector<uint8_t> desc;
     std::vector<float> uright, pose;
     pli_fuse_camera cam;
     bool haveCam = false;
@@ -1108,14 +1109,11 @@ class PliORBmatcher {
     T.cam = cam;
     T.haveCam = true;
     const int n = pKF->N;
+    pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
     for (int i = 0; i < n; ++i) {
-      const cv::KeyPoint& k = pKF->mvKeysUn[i];
-      T.kp.push_back(pli_keypoint{k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave});
-      const uint8_t* d = pKF->mDescriptors.template ptr<uint8_t>(i);
-      T.desc.insert(T.desc.end(), d, d + 32);
+      T.kp.push_back(pli_detail::keypoint(pKF->mvKeysUn[i]));
       T.uright.push_back(pKF->mvuRight[i]);
     }
-    T.off.push_back(T.off.back() + n);
     T.pose.insert(T.pose.end(), pose, pose + 15);
   }
   static pli_fuse_point fusePoint(MapPointT* pMP) {

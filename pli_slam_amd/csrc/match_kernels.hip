@@ -11,9 +11,9 @@
 //   (k_proj_assign_scan: large frames)  ORBmatcher::SearchByProjection(F,MPs)(ORBmatcher.cc:44-143)
 //   k_proj_assign_fisheye               the same (F,MPs) for a frame of two fisheye cameras (ORBmatcher.cc:44-214)
 //   k_track_queries/candidates/assign/lines   frame-to-frame track matching of a batch (pli_batch_track)
-//   k_bow_frame_sort + k_search_by_bow  ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
-//   k_tri_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
-//   k_tri_sort + k_search_by_bow_kf     ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
+//   k_node_sort + k_search_by_bow       ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
+//   k_node_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
+//   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 #include "kernels.hpp"
 #include "device_prims.hpp"
@@ -1064,8 +1064,8 @@ __global__ __launch_bounds__(64) void k_bow_descend(const uint8_t* __restrict__ 
 // each other, the keyframes are independent of each other, and only the keyframe features inside one node must be taken in list
 // order (ascending index).  The rotation histogram and nmatches are sums over the matches: their order does not matter.
 //
-//   k_bow_frame_sort   one workgroup: the frame's features sorted by node id (LDS bitonic sort of (node, index) pairs; the order
-//                      inside a node does not matter, the candidate key below carries the index); unlisted ones (-1) last.
+//   k_node_sort        (below, shared by the three node searches) one workgroup: the frame's features sorted by node id; the
+//                      order inside a node does not matter, the candidate key below carries the index; unlisted ones (-1) last.
 //   k_search_by_bow    one workgroup per keyframe: its valid features whose node the frame lists become (first position of the
 //                      node in the sorted frame list, index) keys, sorted in LDS: runs of one common node in ascending index.
 //                      The waves take 64-key chunks in turn and walk every run that starts in their chunk, keyframe feature after
@@ -1076,6 +1076,7 @@ __global__ __launch_bounds__(64) void k_bow_descend(const uint8_t* __restrict__ 
 //                      threads write the row with the filter applied.
 // ---------------------------------------------------------------------------
 constexpr int BOW_TH_LOW = 50;
+constexpr int TRI_STAT = 32;                                     // SearchForTriangulation, ints per neighbour: 30 bins, [30] the match counter
 
 __device__ __forceinline__ int pow2_ceil(int m) {
   int n = 1;
@@ -1116,25 +1117,41 @@ __device__ __forceinline__ int bow_rot_bin(float kfAngle, float fAngle) {
   return min(max(rot_bin(kfAngle, fAngle), 0), HISTO_LENGTH - 1);
 }
 
-// nf <= 8192; LDS: pow2_ceil(nf) * 6 bytes
-__global__ __launch_bounds__(1024) void k_bow_frame_sort(const int* __restrict__ fNode, int nf, uint32_t* __restrict__ sNode,
-                                                         uint16_t* __restrict__ sIdx, int* __restrict__ nListed) {
-  extern __shared__ __align__(16) uint32_t bowSortLds[];
-  const int n = pow2_ceil(nf);
-  uint32_t* key = bowSortLds;
-  uint16_t* val = reinterpret_cast<uint16_t*>(key + n);
+// The candidate side of SearchByBoW(KF, F), SearchByBoW(KF, KF) and SearchForTriangulation: one workgroup per table (grid =
+// tables), its features that may be taken sorted by node id (LDS bitonic sort of (node, index) pairs), the others last
+// (0xFFFFFFFF); nListed = how many may be taken, 0 when none.  Table t is rows kfOff[t] .. kfOff[t + 1]; kfOff == NULL: one table,
+// rows 0 .. nkOne (the frame of SearchByBoW(KF, F)).  A feature may be taken when it is listed in a node (node >= 0), (kfFlag != 0)
+// == (flagWanted != 0) and, with onlyStereo, kfStereo is set; kfFlag == NULL: every listed feature.  SearchForTriangulation passes
+// "has a map point" and 0, SearchByBoW(KF, KF) "map point set and not bad" and 1; stat (NULL: none) is SearchForTriangulation's
+// histogram and counter, cleared here.  keyCap = a power of two >= every table's feature count (<= 8192); LDS: keyCap * 6 bytes.
+__global__ __launch_bounds__(1024) void k_node_sort(const int* __restrict__ kfOff, int nkOne, const int* __restrict__ kfNode,
+                                                    const uint8_t* __restrict__ kfFlag, int flagWanted,
+                                                    const uint8_t* __restrict__ kfStereo, int onlyStereo, int keyCap,
+                                                    uint32_t* __restrict__ sNode, uint16_t* __restrict__ sIdx,
+                                                    int* __restrict__ nListed, int* __restrict__ stat) {
+  extern __shared__ __align__(16) uint32_t nodeSortLds[];
+  const int kf = blockIdx.x, base = kfOff ? kfOff[kf] : 0, nk = kfOff ? kfOff[kf + 1] - base : nkOne;
+  const int n = min(pow2_ceil(max(nk, 1)), keyCap);
+  uint32_t* key = nodeSortLds;
+  uint16_t* val = reinterpret_cast<uint16_t*>(key + keyCap);
+  if (stat)
+    for (int i = threadIdx.x; i < TRI_STAT; i += blockDim.x) stat[kf * TRI_STAT + i] = 0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    key[i] = i < nf ? (uint32_t)fNode[i] : 0xFFFFFFFFu;          // node -1 (listed in no node) sorts last
+    uint32_t k = 0xFFFFFFFFu;
+    if (i < nk) {
+      const int node = kfNode[base + i];
+      if (node >= 0 && (!kfFlag || (kfFlag[base + i] != 0) == (flagWanted != 0)) && (!onlyStereo || kfStereo[base + i])) k = (uint32_t)node;
+    }
+    key[i] = k;
     val[i] = (uint16_t)i;
   }
+  if (threadIdx.x == 0) nListed[kf] = 0;
   __syncthreads();
   lds_bitonic_sort(key, val, n);
-  for (int i = threadIdx.x; i < nf; i += blockDim.x) {
-    const bool listed = key[i] != 0xFFFFFFFFu;
-    sNode[i] = key[i];
-    sIdx[i] = val[i];
-    if (listed && (i + 1 == nf || key[i + 1] == 0xFFFFFFFFu)) *nListed = i + 1;
-    if (i == 0 && !listed) *nListed = 0;
+  for (int i = threadIdx.x; i < nk; i += blockDim.x) {
+    sNode[base + i] = key[i];
+    sIdx[base + i] = val[i];
+    if (key[i] != 0xFFFFFFFFu && (i + 1 == nk || key[i + 1] == 0xFFFFFFFFu)) nListed[kf] = i + 1;
   }
 }
 
@@ -1187,6 +1204,39 @@ __device__ __forceinline__ int bow_walk(const uint32_t* key, int m, const uint8_
   return nm;
 }
 
+// The key collection of both SearchByBoW kernels, by the whole block: the walking side's features that take part (valid, and
+// listed in a node that the candidate side's sorted list sNode[0..nListed) holds too) become (first position of the node in that
+// list << 16 | index) keys, sorted in LDS and padded to a power of two for it.  *count (LDS, 0 at entry) counts them.  Returns m.
+__device__ __forceinline__ int bow_collect_keys(const int* __restrict__ wNode, const uint8_t* __restrict__ wValid, int nw,
+                                                const uint32_t* __restrict__ sNode, int nListed, uint32_t* key, int* count) {
+  const int tid = threadIdx.x;
+  for (int j = tid; j < nw; j += blockDim.x) {
+    const int node = wNode[j];
+    if (!wValid[j] || node < 0) continue;                         // (a feature in no node is never visited)
+    const int lo = bow_lower_bound(sNode, 0, nListed, (uint32_t)node);
+    if (lo < nListed && sNode[lo] == (uint32_t)node) key[atomicAdd(count, 1)] = ((uint32_t)lo << 16) | (uint32_t)j;
+  }
+  __syncthreads();
+  const int m = *count, n2 = pow2_ceil(m);
+  for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
+  __syncthreads();
+  lds_bitonic_sort(key, nullptr, n2);
+  return m;
+}
+
+// The rotation filter's decision, by ONE thread: keep[0..2] = the bins ComputeThreeMaxima keeps (-1: none; all -1 without
+// checkOri, where nothing is filtered); returns total less the matches of the dropped bins.
+__device__ __forceinline__ int bow_keep_bins(const int* hist, int total, int checkOri, int* keep) {
+  int ind1 = -1, ind2 = -1, ind3 = -1;
+  if (checkOri) {
+    three_maxima(hist, ind1, ind2, ind3);
+    for (int i = 0; i < HISTO_LENGTH; ++i)
+      if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
+  }
+  keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+  return total;
+}
+
 // grid = keyframes; LDS: 48 ints + keyCap keys (a power of two >= every keyframe's feature count) + nf shorts
 __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
                                                        const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
@@ -1207,31 +1257,12 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
   for (int i = tid; i < nf; i += blockDim.x) owner[i] = -1;
   __syncthreads();
   // the keyframe features that take part: map point set and not bad, listed in a node the frame lists too
-  for (int j = tid; j < nk; j += blockDim.x) {
-    const int node = kfNode[base + j];
-    if (!kfValid[base + j] || node < 0) continue;
-    const int lo = bow_lower_bound(sNode, 0, nfl, (uint32_t)node);
-    if (lo < nfl && sNode[lo] == (uint32_t)node) key[atomicAdd(&misc[0], 1)] = ((uint32_t)lo << 16) | (uint32_t)j;
-  }
-  __syncthreads();
-  const int m = misc[0], n2 = pow2_ceil(m);
-  for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
-  __syncthreads();
-  lds_bitonic_sort(key, nullptr, n2);
+  const int m = bow_collect_keys(kfNode + base, kfValid + base, nk, sNode, nfl, key, &misc[0]);
   const int nm = bow_walk(key, m, kfDesc + (int64_t)base * 32, kfAngle + base, sNode, sIdx, nfl, fDesc, fAngle, owner, hist, BOW_TH_LOW,
                           nnratio, checkOri);
   if (lane == 0 && nm) atomicAdd(&misc[1], nm);
   __syncthreads();
-  if (tid == 0) {
-    int total = misc[1], ind1 = -1, ind2 = -1, ind3 = -1;
-    if (checkOri) {
-      three_maxima(hist, ind1, ind2, ind3);
-      for (int i = 0; i < HISTO_LENGTH; ++i)
-        if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
-    }
-    misc[2] = ind1; misc[3] = ind2; misc[4] = ind3;
-    nmatchesOut[kf] = total;
-  }
+  if (tid == 0) nmatchesOut[kf] = bow_keep_bins(hist, misc[1], checkOri, misc + 2);
   __syncthreads();
   const int ind1 = misc[2], ind2 = misc[3], ind3 = misc[4];
   int* row = matches + (int64_t)kf * nf;
@@ -1256,9 +1287,8 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
 // of equal distances, the LAST listed (a node lists its features in ascending index: the largest idx2).  That is the minimum of
 // the key (distance << 32) | (0xffffffff - idx2); the order in which the candidates are visited does not matter.
 //
-//   k_tri_sort     one workgroup per neighbour: its features that may be taken (listed in a node, no map point, stereo when
-//                  bOnlyStereo) sorted by node id (LDS bitonic sort of (node, index)), the others last; also clears the
-//                  neighbour's histogram and counter.
+//   k_node_sort    (above) one workgroup per neighbour: its features that may be taken (listed in a node, no map point, stereo
+//                  when bOnlyStereo) sorted by node id, the others last; also clears the neighbour's histogram and counter.
 //   k_tri_match    grid (slices of pKF1, neighbours), one wave per idx1: a binary search finds the node's run in the neighbour's
 //                  sorted list, the lanes stride over it (Hamming distance, TH_LOW, the epipole gate :1089-1097, the epipolar
 //                  gate Pinhole.cpp:130-143 on the host's F12), a wave minimum of the key picks the winner; lane 0 writes
@@ -1266,42 +1296,6 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
 //   k_tri_finish   (mbCheckOrientation only) one workgroup per neighbour: three_maxima on the histogram, then
 //                  the row is filtered (a match's bin is recomputed from the two angles) and the return value corrected.
 // ---------------------------------------------------------------------------
-constexpr int TRI_STAT = 32;                                     // ints per neighbour: 30 bins, [30] the match counter
-
-// grid = neighbours; keyCap = a power of two >= every neighbour's feature count (<= 8192); LDS: keyCap * 6 bytes.  A feature may
-// be taken when (kfFlag != 0) == (flagWanted != 0): SearchForTriangulation passes "has a map point" and 0, SearchByBoW(KF, KF)
-// passes "map point set and not bad" and 1 (no stereo table, no stat: NULL).
-__global__ __launch_bounds__(1024) void k_tri_sort(const int* __restrict__ kfOff, const int* __restrict__ kfNode,
-                                                   const uint8_t* __restrict__ kfFlag, int flagWanted,
-                                                   const uint8_t* __restrict__ kfStereo, int onlyStereo, int keyCap,
-                                                   uint32_t* __restrict__ sNode, uint16_t* __restrict__ sIdx,
-                                                   int* __restrict__ nListed, int* __restrict__ stat) {
-  extern __shared__ __align__(16) uint32_t triSortLds[];
-  const int kf = blockIdx.x, base = kfOff[kf], nk = kfOff[kf + 1] - base;
-  const int n = min(pow2_ceil(max(nk, 1)), keyCap);
-  uint32_t* key = triSortLds;
-  uint16_t* val = reinterpret_cast<uint16_t*>(key + keyCap);
-  if (stat)
-    for (int i = threadIdx.x; i < TRI_STAT; i += blockDim.x) stat[kf * TRI_STAT + i] = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    uint32_t k = 0xFFFFFFFFu;
-    if (i < nk) {
-      const int node = kfNode[base + i];
-      if (node >= 0 && (kfFlag[base + i] != 0) == (flagWanted != 0) && (!onlyStereo || kfStereo[base + i])) k = (uint32_t)node;
-    }
-    key[i] = k;
-    val[i] = (uint16_t)i;
-  }
-  if (threadIdx.x == 0) nListed[kf] = 0;
-  __syncthreads();
-  lds_bitonic_sort(key, val, n);
-  for (int i = threadIdx.x; i < nk; i += blockDim.x) {
-    sNode[base + i] = key[i];
-    sIdx[base + i] = val[i];
-    if (key[i] != 0xFFFFFFFFu && (i + 1 == nk || key[i + 1] == 0xFFFFFFFFu)) nListed[kf] = i + 1;
-  }
-}
-
 // grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours)
 constexpr int TRI_PER_WAVE = 4;
 __global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
@@ -1379,14 +1373,7 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
   __shared__ int keep[3];
   const int kf = blockIdx.x, base = kfOff[kf];
   int* hist = stat + kf * TRI_STAT;
-  if (threadIdx.x == 0) {
-    int total = hist[30], ind1, ind2, ind3;
-    three_maxima(hist, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; ++i)
-      if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
-    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-    hist[30] = total;
-  }
+  if (threadIdx.x == 0) hist[30] = bow_keep_bins(hist, hist[30], 1, keep);
   __syncthreads();
   const int ind1 = keep[0], ind2 = keep[1], ind3 = keep[2];
   int* row = matches12 + (int64_t)kf * n1;
@@ -1412,7 +1399,7 @@ __global__ __launch_bounds__(256) void k_tri_finish(const pli_keypoint* __restri
 // and only pKF1's features inside one node must be taken in list order (ascending index).  The rotation histogram and nmatches are
 // sums over the matches; vbMatched2 is not given back by the rotation filter and is not read after it.
 //
-//   k_tri_sort          one workgroup per pKF2[k]: its valid features sorted by node id (the candidate list differs per pair).
+//   k_node_sort         (above) one workgroup per pKF2[k]: its valid features sorted by node id (the candidate list differs per pair).
 //   k_search_by_bow_kf  one workgroup per pair: pKF1's valid features whose node k lists (with a valid feature: a node without one
 //                       has no candidate) become (first position of the node in k's sorted list, idx1) keys, 13 bits each, sorted
 //                       in LDS; bow_walk takes the runs.  owner[idx2] (LDS) is vbMatched2 with the idx1 that took it; thread 0
@@ -1440,31 +1427,12 @@ __global__ __launch_bounds__(512) void k_search_by_bow_kf(const uint8_t* __restr
   for (int i = tid; i < 48; i += blockDim.x) bowKfLds[i] = 0;
   for (int i = tid; i < nk; i += blockDim.x) owner[i] = -1;
   __syncthreads();
-  for (int i = tid; i < n1; i += blockDim.x) {
-    const int node = node1[i];
-    if (!valid1[i] || node < 0) continue;                         // :862-866 (a feature in no node is never visited)
-    const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
-    if (lo < nl && sn[lo] == (uint32_t)node) key[atomicAdd(&misc[0], 1)] = ((uint32_t)lo << 16) | (uint32_t)i;
-  }
-  __syncthreads();
-  const int m = misc[0], n2 = pow2_ceil(m);
-  for (int i = m + tid; i < n2; i += blockDim.x) key[i] = 0xFFFFFFFFu;
-  __syncthreads();
-  lds_bitonic_sort(key, nullptr, n2);
+  const int m = bow_collect_keys(node1, valid1, n1, sn, nl, key, &misc[0]);   // :862-866
   const int nm = bow_walk(key, m, desc1, angle1, sn, si, nl, kfDesc + (int64_t)base * 32, kfAngle + base, owner, hist, BOW_TH_LOW - 1,
                           nnratio, checkOri);                     // bestDist1 < TH_LOW :906
   if (lane == 0 && nm) atomicAdd(&misc[1], nm);
   __syncthreads();
-  if (tid == 0) {
-    int total = misc[1], ind1 = -1, ind2 = -1, ind3 = -1;
-    if (checkOri) {
-      three_maxima(hist, ind1, ind2, ind3);
-      for (int i = 0; i < HISTO_LENGTH; ++i)
-        if (i != ind1 && i != ind2 && i != ind3) total -= hist[i];
-    }
-    misc[2] = ind1; misc[3] = ind2; misc[4] = ind3;
-    nmatchesOut[kf] = total;
-  }
+  if (tid == 0) nmatchesOut[kf] = bow_keep_bins(hist, misc[1], checkOri, misc + 2);
   int* inv = reinterpret_cast<int*>(key);                         // the keys are done: vpMatches12 as indices, n1 <= keyCap
   for (int i = tid; i < n1; i += blockDim.x) inv[i] = -1;
   __syncthreads();

@@ -1647,6 +1647,71 @@ pli_status stageImage(pli_ctx* c, int eye, const uint8_t* img, int w, int h, int
   return runIngest(c, c->inStage[0], c->inStage[1], w, 0, eye, 1);
 }
 
+// ---- the searches of one item against a batch of keyframes ------------------------
+// pli_search_by_bow, pli_search_by_bow_kf, pli_search_for_triangulation and pli_fuse_search take their keyframes as flat tables:
+// keyframe k is rows kf_off[k] .. kf_off[k + 1].  What they share on the host is here; every entry point checks in the same order:
+// null / negative arguments, nkf == 0 (OK), kf_off and the per-keyframe cap (kfBatch), the other side's cap, null tables for
+// total > 0, the values, the empty other side (OK, zeroed counts).
+struct KfBatch {
+  int nkf = 0;
+  const int32_t* off = nullptr;
+  int64_t total = 0;                                        // rows of all keyframes
+  int maxNk = 0;                                            // rows of the largest keyframe
+};
+
+// PLI_ERR_INVALID for a kf_off that does not start at 0 or decreases, PLI_ERR_CAPACITY (capMsg) for a keyframe above the cap
+pli_status kfBatch(int32_t nkf, const int32_t* kfOff, const char* capMsg, KfBatch& B) {
+  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
+  B.nkf = nkf; B.off = kfOff; B.maxNk = 0;
+  for (int k = 0; k < nkf; ++k) {
+    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
+    const int nk = kfOff[k + 1] - kfOff[k];
+    if (nk > PLI_BOW_MAX_FEATURES) { g_err = capMsg; return PLI_ERR_CAPACITY; }
+    B.maxNk = std::max(B.maxNk, nk);
+  }
+  B.total = kfOff[nkf];
+  return PLI_OK;
+}
+
+bool nodesOk(const int32_t* node, int64_t n, const char* what) {
+  for (int64_t i = 0; i < n; ++i)
+    if (node[i] < -1) { g_err = std::string(what) + ": a node id or -1"; return false; }
+  return true;
+}
+
+// (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
+inline float angleOf(float a) { return a; }
+inline float angleOf(const pli_keypoint& k) { return k.angle; }
+template <class T>
+bool anglesOk(const T* p, int64_t n, const char* what) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!(angleOf(p[i]) >= 0.f && angleOf(p[i]) < 360.f)) { g_err = std::string(what) + " outside [0, 360)"; return false; }
+  return true;
+}
+
+// (the octaves index the level tables: outside them the reference reads past a vector)
+bool octavesOk(const pli_ctx* c, const pli_keypoint* kp, int64_t n, const char* what) {
+  for (int64_t i = 0; i < n; ++i)
+    if (kp[i].octave < 0 || kp[i].octave >= c->hp.nlevels) { g_err = std::string(what) + ": octave outside the context's levels"; return false; }
+  return true;
+}
+
+int pow2Ceil(int m) {
+  int n = 1;
+  while (n < m) n <<= 1;
+  return n;
+}
+
+// mvScaleFactors, mvLevelSigma2 and mvInvLevelSigma2 = 1.0f / mvLevelSigma2 (ORBextractor.cc:420-431) as the device compares
+// against them; each a table of MAX_LEVELS floats or NULL
+void levelTables(const pli_ctx* c, float* scale, float* sigma2, float* invSigma2) {
+  for (int l = 0; l < c->hp.nlevels; ++l) {
+    const float s = c->hp.lv[l].scale;
+    if (scale) scale[l] = s;
+    if (sigma2) sigma2[l] = s * s;
+    if (invSigma2) invSigma2[l] = 1.0f / (s * s);
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -2722,6 +2787,7 @@ pli_status pli_bow_transform(pli_ctx* c, const pli_vocab* v, const uint8_t* desc
   return PLI_OK;
 }
 
+// ---- the searches of one item against a batch of keyframes (shared host part: KfBatch and the checks above) ----
 pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
                              const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
                              const int32_t* fNode, int32_t nf, float nnratio, int32_t checkOri, int32_t* matches, int32_t* nmatches) {
@@ -2729,28 +2795,14 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   if (!c || nkf < 0 || nf < 0 || (nkf > 0 && (!kfOff || !nmatches)) || (nf > 0 && (!fDesc || !fNode || (checkOri && !fAngle))) ||
       (nkf > 0 && nf > 0 && !matches)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nkf == 0) return PLI_OK;
-  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
-  int maxNk = 0;
-  for (int k = 0; k < nkf; ++k) {
-    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
-    const int nk = kfOff[k + 1] - kfOff[k];
-    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-    maxNk = std::max(maxNk, nk);
-  }
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the SearchByBoW cap", B);
+  if (st != PLI_OK) return st;
   if (nf > PLI_BOW_MAX_FEATURES) { g_err = "the frame has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = kfOff[nkf];
+  const int64_t total = B.total;
   if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  for (int64_t i = 0; i < total; ++i)
-    if (kfNode[i] < -1) { g_err = "kf_node: a node id or -1"; return PLI_ERR_INVALID; }
-  for (int i = 0; i < nf; ++i)
-    if (fNode[i] < -1) { g_err = "f_node: a node id or -1"; return PLI_ERR_INVALID; }
-  if (checkOri) {
-    // (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
-    for (int64_t i = 0; i < total; ++i)
-      if (!(kfAngle[i] >= 0.f && kfAngle[i] < 360.f)) { g_err = "kf_angle outside [0, 360)"; return PLI_ERR_INVALID; }
-    for (int i = 0; i < nf; ++i)
-      if (!(fAngle[i] >= 0.f && fAngle[i] < 360.f)) { g_err = "f_angle outside [0, 360)"; return PLI_ERR_INVALID; }
-  }
+  if (!nodesOk(kfNode, total, "kf_node") || !nodesOk(fNode, nf, "f_node")) return PLI_ERR_INVALID;
+  if (checkOri && (!anglesOk(kfAngle, total, "kf_angle") || !anglesOk(fAngle, nf, "f_angle"))) return PLI_ERR_INVALID;
   if (nf == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
   HIPCHK(hipSetDevice(c->device));
   ScratchPlan plan;
@@ -2767,7 +2819,7 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   auto dM = plan.add<int>((size_t)nkf * nf);
   auto dN = plan.add<int>(nkf);
   auto dListed = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
+  st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
   HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
@@ -2777,10 +2829,10 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   HIPCHK(upload(c, dFd, fDesc, (size_t)nf * 32));
   if (checkOri) HIPCHK(upload(c, dFa, fAngle, nf));
   HIPCHK(upload(c, dFn, fNode, nf));
-  int sortN = 1, keyCap = 1;
-  while (sortN < nf) sortN <<= 1;
-  while (keyCap < maxNk) keyCap <<= 1;
-  LAUNCH(c, "k_bow_frame_sort", k_bow_frame_sort, dim3(1), dim3(1024), (size_t)sortN * 6, dFn, nf, dSn, dSi, dListed);
+  const int sortN = pow2Ceil(nf), keyCap = pow2Ceil(B.maxNk);
+  // the frame is one table without an offset list: every feature listed in a node (no flag, no stereo table, no stat)
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(1), dim3(1024), (size_t)sortN * 6, (const int*)nullptr, nf, dFn, (const uint8_t*)nullptr, 0,
+         (const uint8_t*)nullptr, 0, sortN, dSn, dSi, dListed, (int*)nullptr);
   LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16), dOff,
          dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
   HIPCHK(download(c, matches, dM, (size_t)nkf * nf));
@@ -2797,28 +2849,14 @@ pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* a
   if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!desc1 || !node1 || !valid1 || (checkOri && !angle1))) ||
       (nkf > 0 && (!kfOff || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nkf == 0) return PLI_OK;
-  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
-  int maxNk = 0;
-  for (int k = 0; k < nkf; ++k) {
-    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
-    const int nk = kfOff[k + 1] - kfOff[k];
-    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-    maxNk = std::max(maxNk, nk);
-  }
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the SearchByBoW cap", B);
+  if (st != PLI_OK) return st;
   if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = kfOff[nkf];
+  const int64_t total = B.total;
   if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  for (int64_t i = 0; i < total; ++i)
-    if (kfNode[i] < -1) { g_err = "kf_node: a node id or -1"; return PLI_ERR_INVALID; }
-  for (int i = 0; i < n1; ++i)
-    if (node1[i] < -1) { g_err = "node1: a node id or -1"; return PLI_ERR_INVALID; }
-  if (checkOri) {
-    // (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
-    for (int64_t i = 0; i < total; ++i)
-      if (!(kfAngle[i] >= 0.f && kfAngle[i] < 360.f)) { g_err = "kf_angle outside [0, 360)"; return PLI_ERR_INVALID; }
-    for (int i = 0; i < n1; ++i)
-      if (!(angle1[i] >= 0.f && angle1[i] < 360.f)) { g_err = "angle1 outside [0, 360)"; return PLI_ERR_INVALID; }
-  }
+  if (!nodesOk(kfNode, total, "kf_node") || !nodesOk(node1, n1, "node1")) return PLI_ERR_INVALID;
+  if (checkOri && (!anglesOk(kfAngle, total, "kf_angle") || !anglesOk(angle1, n1, "angle1"))) return PLI_ERR_INVALID;
   if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
   HIPCHK(hipSetDevice(c->device));
   ScratchPlan plan;
@@ -2836,7 +2874,7 @@ pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* a
   auto dListed = plan.add<int>(nkf);
   auto dM = plan.add<int>((size_t)nkf * n1);
   auto dN = plan.add<int>(nkf);
-  pli_status st = commitScratch(c, plan);
+  st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
   if (checkOri) HIPCHK(upload(c, dA1, angle1, n1));
@@ -2847,12 +2885,10 @@ pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* a
   if (checkOri) HIPCHK(upload(c, dKa, kfAngle, total));
   HIPCHK(upload(c, dKn, kfNode, total));
   HIPCHK(upload(c, dKv, kfValid, total));
-  int sortCap = 1, keyCap = 1;
-  while (sortCap < maxNk) sortCap <<= 1;
-  while (keyCap < n1) keyCap <<= 1;
-  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)sortCap * 6, dOff, dKn, dKv, 1, (const uint8_t*)nullptr, 0, sortCap,
+  const int sortCap = pow2Ceil(B.maxNk), keyCap = pow2Ceil(n1);
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)sortCap * 6, dOff, 0, dKn, dKv, 1, (const uint8_t*)nullptr, 0, sortCap,
          dSn, dSi, dListed, (int*)nullptr);
-  LAUNCH(c, "k_search_by_bow_kf", k_search_by_bow_kf, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)maxNk * 2, 16),
+  LAUNCH(c, "k_search_by_bow_kf", k_search_by_bow_kf, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)B.maxNk * 2, 16),
          dD1, dA1, dN1, dV1, n1, dOff, dKd, dKa, dSn, dSi, dListed, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
   HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
   HIPCHK(download(c, nmatches, dN, nkf));
@@ -2869,28 +2905,15 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1 || !stereo1)) ||
       (nkf > 0 && (!kfOff || !F12 || !ep || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nkf == 0) return PLI_OK;
-  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
-  int maxNk = 0;
-  for (int k = 0; k < nkf; ++k) {
-    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
-    const int nk = kfOff[k + 1] - kfOff[k];
-    if (nk > PLI_BOW_MAX_FEATURES) { g_err = "a neighbour has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
-    maxNk = std::max(maxNk, nk);
-  }
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the SearchForTriangulation cap", B);
+  if (st != PLI_OK) return st;
   if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = kfOff[nkf];
+  const int64_t total = B.total;
   if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp || !kfStereo)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  // (the octaves index the level tables, the angles the rotation histogram: outside their ranges the reference reads past a vector / asserts)
-  const int nlevels = c->hp.nlevels;
-  auto tableOk = [&](const pli_keypoint* kp, const int32_t* node, int64_t n) {
-    for (int64_t i = 0; i < n; ++i) {
-      if (node[i] < -1) { g_err = "node: a node id or -1"; return false; }
-      if (kp[i].octave < 0 || kp[i].octave >= nlevels) { g_err = "octave outside the context's levels"; return false; }
-      if (checkOri && !(kp[i].angle >= 0.f && kp[i].angle < 360.f)) { g_err = "angle outside [0, 360)"; return false; }
-    }
-    return true;
-  };
-  if (!tableOk(kp1, node1, n1) || !tableOk(kfKp, kfNode, total)) return PLI_ERR_INVALID;
+  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || (checkOri && !anglesOk(kp1, n1, "kp1: angle"))) return PLI_ERR_INVALID;
+  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || (checkOri && !anglesOk(kfKp, total, "kf_kp: angle")))
+    return PLI_ERR_INVALID;
   if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
   HIPCHK(hipSetDevice(c->device));
   ScratchPlan plan;
@@ -2913,13 +2936,10 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   auto dLv = plan.add<float>(2 * MAX_LEVELS);              // mvScaleFactors, then mvLevelSigma2
   auto dStat = plan.add<int>((size_t)nkf * 32);            // per neighbour: 30 histogram bins, [30] the match counter
   auto dM = plan.add<int>((size_t)nkf * n1);
-  pli_status st = commitScratch(c, plan);
+  st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   float hlv[2 * MAX_LEVELS] = {};
-  for (int l = 0; l < nlevels; ++l) {
-    hlv[l] = c->hp.lv[l].scale;                                          // mvScaleFactors, ORBextractor.cc:420
-    hlv[MAX_LEVELS + l] = c->hp.lv[l].scale * c->hp.lv[l].scale;         // mvLevelSigma2, ORBextractor.cc:424
-  }
+  levelTables(c, hlv, hlv + MAX_LEVELS, nullptr);
   HIPCHK(upload(c, dK1, kp1, n1));
   HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
   HIPCHK(upload(c, dN1, node1, n1));
@@ -2934,11 +2954,10 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   HIPCHK(upload(c, dF, F12, (size_t)nkf * 9));
   HIPCHK(upload(c, dEp, ep, (size_t)nkf * 2));
   HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
-  int keyCap = 1;
-  while (keyCap < maxNk) keyCap <<= 1;
+  const int keyCap = pow2Ceil(B.maxNk);
   const int perBlock = 4 * 4;                                            // k_tri_match: 4 waves x TRI_PER_WAVE features of pKF1
-  LAUNCH(c, "k_tri_sort", k_tri_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, dKn, dKm, 0, dKs, onlyStereo ? 1 : 0, keyCap, dSn,
-         dSi, dListed, dStat);
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, 0, dKn, dKm, 0, dKs, onlyStereo ? 1 : 0, keyCap,
+         dSn, dSi, dListed, dStat);
   LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1, dS1, n1, dOff, dKk,
          dKd, dKs, dSn, dSi, dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS, onlyStereo ? 1 : 0, coarse ? 1 : 0,
          checkOri ? 1 : 0, dM, dStat);
@@ -2963,15 +2982,12 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
     if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
   if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
   if (nkf == 0) return PLI_OK;
-  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
-  for (int k = 0; k < nkf; ++k) {
-    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
-    if (kfOff[k + 1] - kfOff[k] > PLI_BOW_MAX_FEATURES) { g_err = "a keyframe has more features than the Fuse cap"; return PLI_ERR_CAPACITY; }
-  }
-  const int64_t total = kfOff[nkf];
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the Fuse cap", B);
+  if (st != PLI_OK) return st;
+  const int64_t total = B.total;
   if (total > 0 && (!kfKp || !kfDesc || (reprojGate && !kfUright))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  for (int64_t i = 0; i < total; ++i)      // (the octaves index the level tables: outside them the reference reads past a vector)
-    if (kfKp[i].octave < 0 || kfKp[i].octave >= nlevels) { g_err = "octave outside the context's levels"; return PLI_ERR_INVALID; }
+  if (!octavesOk(c, kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
   if (nmp == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
   const size_t npairs = (size_t)nkf * nmp;
@@ -2991,15 +3007,11 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   auto dNs = plan.add<int>(1);
   auto dBi = plan.add<int>(npairs);
   auto dBd = plan.add<int>(bestDist ? npairs : 0);
-  pli_status st = commitScratch(c, plan);
+  st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   float hlv[3 * MAX_LEVELS] = {};
-  for (int l = 0; l < nlevels; ++l) {
-    if (l < nlevels - 1) hlv[l] = levelRatio[l];
-    const float s = c->hp.lv[l].scale;
-    hlv[MAX_LEVELS + l] = s;                                 // mvScaleFactors, ORBextractor.cc:420
-    hlv[2 * MAX_LEVELS + l] = 1.0f / (s * s);                // mvInvLevelSigma2 = 1.0f / mvLevelSigma2, ORBextractor.cc:424-431
-  }
+  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
+  levelTables(c, hlv + MAX_LEVELS, nullptr, hlv + 2 * MAX_LEVELS);
   HIPCHK(upload(c, dMp, mp, nmp));
   HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
   HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));

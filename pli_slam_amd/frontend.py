@@ -74,6 +74,29 @@ def fuse_level_ratio(nlevels, scale_factor, level_fn=None):
     return out
 
 
+def pack_keyframes(kfs, spec, what):
+    """The flat per-feature tables of a batch of keyframes, as the batched searches take them.  kfs: one tuple per keyframe;
+    spec: (position in the tuple, dtype, trailing shape) of each per-feature column.  Returns (off, columns): keyframe k is rows
+    off[k] .. off[k + 1] (int32, off[0] = 0) of every column, each C-contiguous of shape (total,) + trailing shape.  A keyframe
+    whose columns disagree in length raises ValueError(what)."""
+    off = np.zeros(len(kfs) + 1, np.int32)
+    parts = [[] for _ in spec]
+    for k, kf in enumerate(kfs):
+        cols = [np.asarray(kf[i], dt).reshape((-1,) + tuple(tail)) for i, dt, tail in spec]
+        if any(len(col) != len(cols[0]) for col in cols):
+            raise ValueError(what)
+        off[k + 1] = off[k] + len(cols[0])
+        for p, col in zip(parts, cols):
+            p.append(col)
+    return off, [np.ascontiguousarray(np.concatenate(p) if p else np.zeros((0,) + tuple(tail), dt), dt)
+                 for p, (_, dt, tail) in zip(parts, spec)]
+
+
+BOW_COLUMNS = ((0, np.uint8, (32,)), (1, np.float32, ()), (2, np.int32, ()), (3, np.uint8, ()))      # desc, angle, node, valid
+TRI_COLUMNS = ((0, KEYPOINT_DT, ()), (1, np.uint8, (32,)), (2, np.int32, ()), (3, np.uint8, ()), (4, np.uint8, ()))
+FUSE_COLUMNS = ((0, KEYPOINT_DT, ()), (1, np.uint8, (32,)), (2, np.float32, ()))                     # kp, desc, uright
+
+
 class Frontend:
     """One pli_ctx: device buffers + stream for up to `max_frames` stereo frames."""
 
@@ -223,17 +246,7 @@ class Frontend:
         fa = np.ascontiguousarray(f_angle, np.float32).reshape(nf)
         fn = np.ascontiguousarray(f_node, np.int32).reshape(nf)
         nkf = len(kfs)
-        off = np.zeros(nkf + 1, np.int32)
-        for k, kf in enumerate(kfs):
-            off[k + 1] = off[k] + np.asarray(kf[0]).reshape(-1, 32).shape[0]
-
-        def cat(i, dt, shape):
-            parts = [np.asarray(kf[i], dt).reshape(shape) for kf in kfs]
-            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0,) + shape[1:], dt), dt)
-        kd, ka = cat(0, np.uint8, (-1, 32)), cat(1, np.float32, (-1,))
-        kn, kv = cat(2, np.int32, (-1,)), cat(3, np.uint8, (-1,))
-        if not (len(ka) == len(kn) == len(kv) == len(kd)):
-            raise ValueError("every keyframe needs one angle, node and valid flag per descriptor")
+        off, (kd, ka, kn, kv) = pack_keyframes(kfs, BOW_COLUMNS, "every keyframe needs one angle, node and valid flag per descriptor")
         matches = np.full((nkf, nf), -1, np.int32)
         nmatches = np.zeros(nkf, np.int32)
         check(self.L.pli_search_by_bow(self.h, nkf, ptr(off), ptr(kd), ptr(ka), ptr(kn), ptr(kv), ptr(fd), ptr(fa), ptr(fn), nf,
@@ -251,17 +264,7 @@ class Frontend:
         nd1 = np.ascontiguousarray(node1, np.int32).reshape(n1)
         v1 = np.ascontiguousarray(valid1, np.uint8).reshape(n1)
         nkf = len(kfs)
-        off = np.zeros(nkf + 1, np.int32)
-        for k, kf in enumerate(kfs):
-            off[k + 1] = off[k] + np.asarray(kf[0]).reshape(-1, 32).shape[0]
-
-        def cat(i, dt, shape):
-            parts = [np.asarray(kf[i], dt).reshape(shape) for kf in kfs]
-            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0,) + shape[1:], dt), dt)
-        kd, ka = cat(0, np.uint8, (-1, 32)), cat(1, np.float32, (-1,))
-        kn, kv = cat(2, np.int32, (-1,)), cat(3, np.uint8, (-1,))
-        if not (len(ka) == len(kn) == len(kv) == len(kd)):
-            raise ValueError("every keyframe needs one angle, node and valid flag per descriptor")
+        off, (kd, ka, kn, kv) = pack_keyframes(kfs, BOW_COLUMNS, "every keyframe needs one angle, node and valid flag per descriptor")
         matches = np.full((nkf, n1), -1, np.int32)
         nmatches = np.zeros(nkf, np.int32)
         check(self.L.pli_search_by_bow_kf(self.h, ptr(d1), ptr(a1), ptr(nd1), ptr(v1), n1, nkf, ptr(off), ptr(kd), ptr(ka), ptr(kn),
@@ -275,26 +278,10 @@ class Frontend:
         mvuRight >= 0; kfs: list of (kp, desc, node, has_mp, stereo, F12, ep) per neighbour, F12 = the 3 x 3 matrix of
         Pinhole::epipolarConstrain, ep = the epipole in the neighbour's image.  Returns (matches12[nkf, n1]: the neighbour's
         feature that feature i of kf1 is matched to or -1, nmatches[nkf])."""
-        def table(t):
-            d = np.ascontiguousarray(t[1], np.uint8).reshape(-1, 32)
-            n = d.shape[0]
-            cols = (np.ascontiguousarray(t[0], capi.KEYPOINT_DT).reshape(-1), d, np.ascontiguousarray(t[2], np.int32).reshape(-1),
-                    np.ascontiguousarray(t[3], np.uint8).reshape(-1), np.ascontiguousarray(t[4], np.uint8).reshape(-1))
-            if any(len(col) != n for col in cols):
-                raise ValueError("every feature needs one keypoint, descriptor, node, has_mp and stereo flag")
-            return cols
-        k1, d1, n1, m1, s1 = table(kf1)
-        tabs = [table(kf) for kf in kfs]
+        what = "every feature needs one keypoint, descriptor, node, has_mp and stereo flag"
+        k1, d1, n1, m1, s1 = pack_keyframes([kf1], TRI_COLUMNS, what)[1]
         nkf = len(kfs)
-        off = np.zeros(nkf + 1, np.int32)
-        for k, t in enumerate(tabs):
-            off[k + 1] = off[k] + len(t[2])
-
-        def cat(i, dt, shape):
-            parts = [t[i] for t in tabs]
-            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
-        kk, kd = cat(0, capi.KEYPOINT_DT, (0,)), cat(1, np.uint8, (0, 32))
-        kn, km, ks = cat(2, np.int32, (0,)), cat(3, np.uint8, (0,)), cat(4, np.uint8, (0,))
+        off, (kk, kd, kn, km, ks) = pack_keyframes(kfs, TRI_COLUMNS, what)
         f12 = np.ascontiguousarray([np.asarray(kf[5], np.float32).reshape(9) for kf in kfs], np.float32).reshape(nkf, 9)
         ep = np.ascontiguousarray([np.asarray(kf[6], np.float32).reshape(2) for kf in kfs], np.float32).reshape(nkf, 2)
         matches = np.full((nkf, len(n1)), -1, np.int32)
@@ -316,23 +303,8 @@ class Frontend:
         if len(d) != len(pts):
             raise ValueError("every map point needs one descriptor")
         nkf, nmp = len(keyframes), len(pts)
-        tabs = []
-        for kf in keyframes:
-            kd = np.ascontiguousarray(kf[1], np.uint8).reshape(-1, 32)
-            cols = (np.ascontiguousarray(kf[0], KEYPOINT_DT).reshape(-1), kd, np.ascontiguousarray(kf[2], np.float32).reshape(-1),
-                    np.ascontiguousarray(kf[3], np.float32).reshape(15))
-            if len(cols[0]) != len(kd) or len(cols[2]) != len(kd):
-                raise ValueError("every feature needs one keypoint, descriptor and uright")
-            tabs.append(cols)
-        off = np.zeros(nkf + 1, np.int32)
-        for k, t in enumerate(tabs):
-            off[k + 1] = off[k] + len(t[1])
-
-        def cat(i, dt, shape):
-            parts = [t[i] for t in tabs]
-            return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape, dt), dt)
-        kk, kd, ku = cat(0, KEYPOINT_DT, (0,)), cat(1, np.uint8, (0, 32)), cat(2, np.float32, (0,))
-        pose = np.ascontiguousarray([t[3] for t in tabs], np.float32).reshape(nkf, 15)
+        off, (kk, kd, ku) = pack_keyframes(keyframes, FUSE_COLUMNS, "every feature needs one keypoint, descriptor and uright")
+        pose = np.ascontiguousarray([np.asarray(kf[3], np.float32).reshape(15) for kf in keyframes], np.float32).reshape(nkf, 15)
         if not isinstance(cam, capi.FuseCamera):
             cam = capi.FuseCamera(*[float(v) for v in cam])
         if skip is not None:

@@ -206,3 +206,55 @@ def test_the_scalar_restatement_on_one_device_case(fe):
     for k, (kd, ka, kn, kv) in enumerate(kfs):
         want_m, want_n = search_by_bow(kd, ka, kn, kv, *f, 0.75, True)
         assert np.array_equal(m[k], want_m) and n[k] == want_n
+
+
+def check_scalar(fe, frame, kfs):
+    """Exact equality with the scalar restatement, with and without the rotation filter."""
+    for ori in (True, False):
+        m, n = fe.search_by_bow(*frame, kfs, 0.75, ori)
+        assert m.shape == (len(kfs), len(frame[2])) and n.shape == (len(kfs),)
+        for k, (kd, ka, kn, kv) in enumerate(kfs):
+            want_m, want_n = search_by_bow(kd, ka, kn, kv, *frame, 0.75, ori)
+            assert np.array_equal(m[k], want_m) and n[k] == want_n, (ori, k, n[k], want_n)
+    return m, n
+
+
+@pytest.fixture(scope="module")
+def small_scene():
+    """A 65-feature frame in 4 nodes (every feature listed) and two keyframes of 65 features that see it."""
+    rng = np.random.default_rng(65)
+    _, _, _, _, fd, fa, fn = random_case(rng, 1, 65, 4, ndup=0.5)
+    fn = np.abs(fn).astype(np.int32)                    # -1 -> 1: every feature listed
+    kfs = [keyframe_of(rng, (fd, fa, fn), 65, invalid=0.1, nnodes=4) for _ in range(2)]
+    return (fd, fa, fn), kfs
+
+
+@pytest.mark.parametrize("nf", [1, 2, 63, 64, 65])
+def test_frame_sizes_around_a_wave_and_a_power_of_two(fe, small_scene, nf):
+    """The frame's sort runs in the batch sort kernel as one table without an offset list: one feature, one wave less one, a whole
+    wave (a power of two), one more."""
+    (fd, fa, fn), kfs = small_scene
+    m, n = check_scalar(fe, (fd[:nf], fa[:nf], fn[:nf]), kfs)
+    if nf >= 63:
+        assert n.min() > 0
+
+
+def test_a_frame_listed_in_no_node(fe, small_scene):
+    (fd, fa, fn), kfs = small_scene
+    m, n = check_scalar(fe, (fd, fa, np.full(len(fn), -1, np.int32)), kfs)
+    assert (m == -1).all() and (n == 0).all()
+
+
+def test_only_frame_feature_0_unlisted(fe, small_scene):
+    (fd, fa, fn), kfs = small_scene
+    fn = fn.copy()
+    fn[0] = -1
+    m, n = check_scalar(fe, (fd, fa, fn), kfs)
+    assert (m[:, 0] == -1).all() and n.min() > 0
+
+
+def test_a_batch_whose_first_and_last_keyframe_are_empty(fe, small_scene):
+    frame, kfs = small_scene
+    e = (np.zeros((0, 32), np.uint8), np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(0, np.uint8))
+    m, n = check_scalar(fe, frame, [e, kfs[0], kfs[1], e])
+    assert n[0] == 0 and n[3] == 0 and n[1] > 0 and n[2] > 0
