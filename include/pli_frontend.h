@@ -630,6 +630,39 @@ pli_status pli_fuse_search(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t
                            const float* kf_pose, const uint8_t* skip, const pli_fuse_camera* cam, float th,
                            const float* level_ratio, int32_t reproj_gate, int32_t* best_idx, int32_t* best_dist);
 
+/* Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) ORBmatcher.cc:473-586 and the
+ * overload with vpPointsKFs / vpMatchedKF :588-704 (LoopClosing.cc:631, :656, :852), for ONE list of nmp map points against npair
+ * (keyframe, Scw) pairs in one call.  Unlike Fuse this search is sequential across the points of a pair: vpMatched[bestIdx] = pMP
+ * (:579 / :696) takes the keypoint away from every later point (:558 / :675).  Points are decided in list order; the pairs are
+ * independent of each other, each with its own owner state, also when the same keyframe appears in two pairs.  A point listed
+ * twice is two entries (the reference's spAlreadyFound is fixed at entry, :490).
+ * Tables as pli_fuse_search: mp (max_dist / valid as there), mp_desc, kf_off, kf_kp, kf_desc, cam (bf is not read), th,
+ * level_ratio; kf_pose: 15 floats per pair - Rcw, tcw, Ow decomposed from Scw on the host exactly as :483-487; skip: npair x nmp,
+ * may be NULL, != 0 = spAlreadyFound.count(pMP) :501.
+ * occupied: one byte per keyframe row (ragged by kf_off), may be NULL: != 0 = vpMatched[idx] != NULL at entry (:558).
+ * Gates in the reference's order: valid / skip :501; z < 0 :511; the projection; KeyFrame::IsInImage :522; the distance range
+ * :531; PO.dot(Pn) < 0.5*dist :537; PredictScale :540 through level_ratio; radius = th * mvScaleFactors[level] :543; an empty
+ * window :547.  project_form selects the projection's arithmetic, which rounds differently: 0 = Pinhole::project, fx*x/z + cx
+ * (:519); 1 = invz = 1/z; x*invz; fx*x + cx (:631-636).  Every operation is float, in the written order, nothing contracted.
+ * Candidates :555-575: the rows of KeyFrame::GetFeaturesInArea, without the owned ones (occupied at entry, or taken by an earlier
+ * point of this pair), octave in [level-1, level]; the strict minimum of the Hamming distance in visiting order = the minimum of
+ * the key (distance, cell column, cell row, index), as in pli_fuse_search.
+ * Acceptance :577: bestDist <= TH_LOW*ratioHamming is the float comparison (float)bestDist <= 50.0f * ratio_hamming (one
+ * rounding).  With no candidate the reference holds bestDist = 256 and bestIdx = -1 and would write vpMatched[-1] if the product
+ * reached 256: ratio_hamming must be finite, > 0 and 50.0f * ratio_hamming < 256, else PLI_ERR_INVALID.
+ * row_point: one int per keyframe row: the index of the point that took the row in this call (vpMatched[row] = vpPoints[i]), -1
+ * otherwise; rows occupied at entry stay -1.  best_idx (may be NULL): npair x nmp, the row a point took or -1.  nmatches[npair]:
+ * the reference's return value.
+ * Errors: PLI_ERR_INVALID for null pointers, project_form outside {0, 1}, an octave outside [0, orb_nlevels), a decreasing
+ * kf_off, a decreasing or NaN level_ratio; PLI_ERR_CAPACITY for a keyframe with more than PLI_BOW_MAX_FEATURES rows (nothing is
+ * truncated).  npair == 0, nmp == 0 and empty keyframes are valid.  The number of kernel launches does not depend on npair or
+ * nmp. */
+pli_status pli_search_by_projection_sim3(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t* mp_desc, int32_t nmp, int32_t npair,
+                                         const int32_t* kf_off, const pli_keypoint* kf_kp, const uint8_t* kf_desc,
+                                         const float* kf_pose, const uint8_t* skip, const uint8_t* occupied,
+                                         const pli_fuse_camera* cam, float th, const float* level_ratio, float ratio_hamming,
+                                         int32_t project_form, int32_t* row_point, int32_t* best_idx, int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

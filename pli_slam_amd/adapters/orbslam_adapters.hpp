@@ -16,6 +16,10 @@
 //   ORB_SLAM3::ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)   include/ORBmatcher.h,
 //                                                             src/ORBmatcher.cc:1399-1609, :1611-1733 (no second cameras; + a batch
 //                                                             form for LocalMapping::SearchInNeighbors' loop over target keyframes)
+//   ORB_SLAM3::ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) and (pKF, Scw, vpPoints, vpPointsKFs,
+//                                                             vpMatched, vpMatchedKF, th, ratioHamming)   include/ORBmatcher.h,
+//                                                             src/ORBmatcher.cc:473-586, :588-704 (no second cameras; + a batch
+//                                                             form for LoopClosing's loop over covisible keyframes)
 //
 // Frame.cc / Tracking.cc keep calling these names unchanged; INTEGRATION.md lists the edits (swap the headers).
 //
@@ -39,6 +43,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -1009,17 +1014,8 @@ class PliORBmatcher {
   // Not batched over keyframes: the caller's own Replace runs between them.
   template <class KeyFrameT>
   int Fuse(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
-    double dd = 0.0;
-    for (int j = 0; j < 3; ++j) dd += (double)Scw.template at<float>(0, j) * (double)Scw.template at<float>(0, j);
-    const float scw = (float)std::sqrt(dd);
-    const double inv = 1.0 / (double)scw;
     float pose[15];
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) pose[i * 3 + j] = (float)((double)Scw.template at<float>(i, j) * inv);
-      pose[9 + i] = (float)((double)Scw.template at<float>(i, 3) * inv);
-    }
-    for (int i = 0; i < 3; ++i)
-      pose[12 + i] = (float)(-1.0 * ((double)pose[i] * (double)pose[9] + (double)pose[3 + i] * (double)pose[10] + (double)pose[6 + i] * (double)pose[11]));
+    sim3Pose(Scw, pose);
     FuseTables T;
     fuseGatherKeyFrame(pKF, pose, T);
     const auto spAlreadyFound = pKF->GetMapPoints();
@@ -1053,6 +1049,61 @@ class PliORBmatcher {
     return nFused;
   }
 
+  // ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched,
+  // int th, float ratioHamming), ORBmatcher.cc:473-586 (LoopClosing.cc:656 and :852): the whole loop runs on the device
+  // (pli_search_by_projection_sim3, Pinhole::project's arithmetic :519); the decomposition of Scw :483-487 runs here, as in the
+  // Sim3 Fuse above.  vpMatched[row] = vpPoints[i] for every row a point took; the return value is the reference's.
+  template <class KeyFrameT>
+  int SearchByProjection(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched, int th,
+                         float ratioHamming = 1.0) {
+    std::vector<std::vector<MapPointT*>> vvpMatched(1);
+    vvpMatched[0].swap(vpMatched);
+    std::vector<int> vnmatches;
+    try {
+      sim3Projection(std::vector<KeyFrameT*>(1, pKF), std::vector<cv::Mat>(1, Scw), vpPoints, vvpMatched, th, ratioHamming, 0, vnmatches,
+                     [](int, int, int) {});
+    } catch (...) {
+      vpMatched.swap(vvpMatched[0]);
+      throw;
+    }
+    vpMatched.swap(vvpMatched[0]);
+    return vnmatches[0];
+  }
+
+  // ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, const vector<KeyFrame*>&
+  // vpPointsKFs, vector<MapPoint*>& vpMatched, vector<KeyFrame*>& vpMatchedKF, int th, float ratioHamming), ORBmatcher.cc:588-704
+  // (LoopClosing.cc:631): the same search with the projection written out as :631-636 (invz = 1/z; x*invz; fx*x + cx), which rounds
+  // differently from Pinhole::project; vpMatchedKF[row] = vpPointsKFs[i] beside vpMatched[row] = vpPoints[i] (:696-697).
+  template <class KeyFrameT>
+  int SearchByProjection(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>& vpPoints, const std::vector<KeyFrameT*>& vpPointsKFs,
+                         std::vector<MapPointT*>& vpMatched, std::vector<KeyFrameT*>& vpMatchedKF, int th, float ratioHamming = 1.0) {
+    if (vpPointsKFs.size() < vpPoints.size() || vpMatchedKF.size() < vpMatched.size())
+      throw std::logic_error("SearchByProjection: vpPointsKFs / vpMatchedKF are shorter than vpPoints / vpMatched");
+    std::vector<std::vector<MapPointT*>> vvpMatched(1);
+    vvpMatched[0].swap(vpMatched);
+    std::vector<int> vnmatches;
+    try {
+      sim3Projection(std::vector<KeyFrameT*>(1, pKF), std::vector<cv::Mat>(1, Scw), vpPoints, vvpMatched, th, ratioHamming, 1, vnmatches,
+                     [&](int, int row, int i) { vpMatchedKF[row] = vpPointsKFs[i]; });
+    } catch (...) {
+      vpMatched.swap(vvpMatched[0]);
+      throw;
+    }
+    vpMatched.swap(vvpMatched[0]);
+    return vnmatches[0];
+  }
+
+  // (not in the reference) The loop of LoopClosing.cc:698-730 - FindMatchesByProjection (:852: th = 3, ratio = 1.5) for up to five
+  // covisibles of the current keyframe, each with its own Scw, against ONE list of points - with ONE device search.  vvpMatched[k]
+  // is keyframe k's vpMatched (sized by the caller, as :851 does; non-null entries are occupied rows and already-found points),
+  // vnmatches[k] the reference's return value.  The pairs do not share state, so every result equals the single call's.  The
+  // reference's loop stops after three valid keyframes; this form has searched all of them by then.
+  template <class KeyFrameT>
+  void SearchByProjection(const std::vector<KeyFrameT*>& vpKFs, const std::vector<cv::Mat>& vScw, const std::vector<MapPointT*>& vpPoints,
+                          std::vector<std::vector<MapPointT*>>& vvpMatched, int th, float ratioHamming, std::vector<int>& vnmatches) {
+    sim3Projection(vpKFs, vScw, vpPoints, vvpMatched, th, ratioHamming, 0, vnmatches, [](int, int, int) {});
+  }
+
   // the level_ratio table the Fuse adapters hand to pli_fuse_search (tests read it)
   template <class KeyFrameT>
   const std::vector<float>& fuseLevelRatio(KeyFrameT* pKF) {
@@ -1076,6 +1127,22 @@ class PliORBmatcher {
     return mvFuseLevelRatio;
   }
 
+  // The decomposition of a Sim3 matrix, ORBmatcher.cc:483-487 / :1620-1624, into Rcw (row major), tcw, Ow; tests read it (PARITY UNPINNED:
+  // OpenCV's arithmetic, by the conventions DESIGN.md §9 lists - Mat::dot sums in double, sqrt of that double rounded to float;
+  // Mat / s is (float)(x * (1.0 / s)); -Rcw.t() * tcw is one gemm with alpha = -1, one rounding)
+  static void sim3Pose(const cv::Mat& Scw, float pose[15]) {
+    double dd = 0.0;
+    for (int j = 0; j < 3; ++j) dd += (double)Scw.template at<float>(0, j) * (double)Scw.template at<float>(0, j);
+    const float scw = (float)std::sqrt(dd);
+    const double inv = 1.0 / (double)scw;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) pose[i * 3 + j] = (float)((double)Scw.template at<float>(i, j) * inv);
+      pose[9 + i] = (float)((double)Scw.template at<float>(i, 3) * inv);
+    }
+    for (int i = 0; i < 3; ++i)
+      pose[12 + i] = (float)(-1.0 * ((double)pose[i] * (double)pose[9] + (double)pose[3 + i] * (double)pose[10] + (double)pose[6 + i] * (double)pose[11]));
+  }
+
  protected:
   // the keyframe side of both SearchByBoW forms; valid = the map point is set and not bad
   struct BowTable : pli_detail::KfTable {
@@ -1092,6 +1159,51 @@ class PliORBmatcher {
       T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);
       T.angle.push_back(pKF->mvKeysUn[i].angle);
     }
+  }
+  // What the three SearchByProjection(KeyFrame, Scw, ...) forms share: the tables, one device search, vpMatched written from
+  // row_point.  onMatch(pair, row, point) runs for every row taken.
+  template <class KeyFrameT, class OnMatch>
+  void sim3Projection(const std::vector<KeyFrameT*>& vpKFs, const std::vector<cv::Mat>& vScw, const std::vector<MapPointT*>& vpPoints,
+                      std::vector<std::vector<MapPointT*>>& vvpMatched, int th, float ratioHamming, int projectForm,
+                      std::vector<int>& vnmatches, OnMatch onMatch) {
+    const int npair = (int)vpKFs.size(), nmp = (int)vpPoints.size();
+    if (vScw.size() != vpKFs.size() || vvpMatched.size() != vpKFs.size())
+      throw std::logic_error("SearchByProjection: one Scw and one vpMatched per keyframe");
+    vnmatches.assign(npair, 0);
+    if (npair == 0) return;
+    FuseTables T;
+    std::vector<uint8_t> occupied, skip((size_t)npair * nmp, 0);
+    std::vector<pli_fuse_point> pts(nmp);
+    std::vector<uint8_t> desc((size_t)nmp * 32, 0);
+    for (int i = 0; i < nmp; ++i) {
+      pts[i] = fusePoint(vpPoints[i]);                                       // isBad() :501
+      if (pts[i].valid) std::memcpy(&desc[(size_t)i * 32], vpPoints[i]->GetDescriptor().template ptr<uint8_t>(), 32);
+    }
+    for (int k = 0; k < npair; ++k) {
+      KeyFrameT* pKF = vpKFs[k];
+      if (pKF->NLeft != -1) throw std::logic_error("SearchByProjection: a keyframe of two cameras (NLeft != -1) is not supported");
+      if (pKF->mpCamera2) throw std::logic_error("SearchByProjection: a keyframe with mpCamera2 is not supported");
+      if ((int)vvpMatched[k].size() < pKF->N) throw std::logic_error("SearchByProjection: vpMatched is shorter than the keyframe");
+      float pose[15];
+      sim3Pose(vScw[k], pose);
+      fuseGatherKeyFrame(pKF, pose, T);
+      const std::set<MapPointT*> spAlreadyFound(vvpMatched[k].begin(), vvpMatched[k].end());      // :490-491
+      for (int i = 0; i < pKF->N; ++i) occupied.push_back(vvpMatched[k][i] ? 1 : 0);
+      for (int i = 0; i < nmp; ++i)
+        if (vpPoints[i] && spAlreadyFound.count(vpPoints[i])) skip[(size_t)k * nmp + i] = 1;
+    }
+    std::vector<int> rowPoint;
+    pli_detail::deviceContext("SearchByProjection")
+        ->searchByProjectionSim3(pts.data(), desc.data(), nmp, npair, T.off.data(), T.kp.data(), T.desc.data(), T.pose.data(), skip.data(),
+                                 occupied.data(), T.cam, (float)th, fuseLevelRatio(vpKFs[0]), ratioHamming, projectForm, rowPoint,
+                                 vnmatches);
+    for (int k = 0; k < npair; ++k)
+      for (int r = T.off[k]; r < T.off[k + 1]; ++r) {
+        const int i = rowPoint[r];
+        if (i < 0) continue;
+        vvpMatched[k][r - T.off[k]] = vpPoints[i];                            // :579 / :696
+        onMatch(k, r - T.off[k], i);
+      }
   }
   struct FuseTables : pli_detail::KfTable {
     std::vector<pli_keypoint> kp;

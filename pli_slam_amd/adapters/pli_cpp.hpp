@@ -173,6 +173,19 @@ class Frontend {
     check(pli_fuse_search(ctx_, mp, mpDesc, nmp, nkf, kfOff, kfKp, kfDesc, kfUright, kfPose, skip, &cam, th, levelRatio.data(),
                           reprojGate ? 1 : 0, bestIdx.data(), nullptr));
   }
+  // Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
+  // ORBmatcher.cc:473-704 of nmp map points against npair (keyframe, Scw) pairs (include/pli_frontend.h
+  // pli_search_by_projection_sim3): rowPoint (one per keyframe row) = the point that took the row in this call or -1,
+  // nmatches[k] = the reference's return value for pair k.  projectForm: 0 = Pinhole::project (:519), 1 = :631-636.
+  void searchByProjectionSim3(const pli_fuse_point* mp, const uint8_t* mpDesc, int nmp, int npair, const int32_t* kfOff,
+                              const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfPose, const uint8_t* skip,
+                              const uint8_t* occupied, const pli_fuse_camera& cam, float th, const std::vector<float>& levelRatio,
+                              float ratioHamming, int projectForm, std::vector<int>& rowPoint, std::vector<int>& nmatches) {
+    rowPoint.assign(npair > 0 ? (size_t)kfOff[npair] : 0, -1);
+    nmatches.assign(npair, 0);
+    check(pli_search_by_projection_sim3(ctx_, mp, mpDesc, nmp, npair, kfOff, kfKp, kfDesc, kfPose, skip, occupied, &cam, th,
+                                        levelRatio.data(), ratioHamming, projectForm, rowPoint.data(), nullptr, nmatches.data()));
+  }
   // level_ratio of pli_fuse_search from the HOST's own MapPoint::PredictScale expression: levelOf(ratio) must be the tree's
   // expression compiled by the tree's compiler (ceil(log(ratio) / mfLogScaleFactor) with its clamps), so that whichever overload
   // of log its toolchain selects is the one the thresholds describe.  For n = 0 .. nlevels-2 the largest float for which

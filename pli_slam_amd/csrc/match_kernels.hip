@@ -15,6 +15,7 @@
 //   k_node_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
+//   k_fuse_grid, k_sim3_project, k_sim3_candidates, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -1530,6 +1531,41 @@ __global__ __launch_bounds__(256) void k_fuse_grid(const int* __restrict__ kfOff
 
 static_assert(sizeof(FuseSurvivor) == 32, "FuseSurvivor layout");
 
+// One (keyframe, point) pair up to the window search: the gates :1432-1500 (Sim3 searches: :501-543) in the reference's order.  true: S
+// holds the projection, the level and the radius (S.ur only for kForm 0).  kForm 0: Pinhole::project (Pinhole.cpp:30-33, fx*x/z + cx),
+// what Fuse and ORBmatcher.cc:519 call; kForm 1: ORBmatcher.cc:631-636 (invz = 1/z; x*invz; fx*x + cx), which rounds differently.
+template <int kForm>
+__device__ __forceinline__ bool fuse_project_point(const pli_fuse_point& P, const float* __restrict__ T /* Rcw row major, tcw, Ow */,
+                                                   const pli_fuse_camera& cam, float th, const float* __restrict__ levelRatio,
+                                                   int nlevels, const float* __restrict__ scaleFactor, FuseSurvivor& S) {
+  float pc[3];
+  for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);      // Rcw*p3Dw + tcw
+  const float x = pc[0], y = pc[1], z = pc[2];
+  if (z < 0.0f) return false;                                    // :1448
+  const float invz = __fdiv_rn(1.0f, z);
+  if (kForm == 0) {
+    S.u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);             // Pinhole::project, Pinhole.cpp:30-33
+    S.v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+  } else {
+    S.u = __fadd_rn(__fmul_rn(cam.fx, __fmul_rn(x, invz)), cam.cx);          // ORBmatcher.cc:631-636
+    S.v = __fadd_rn(__fmul_rn(cam.fy, __fmul_rn(y, invz)), cam.cy);
+  }
+  if (!(S.u >= cam.min_x && S.u < cam.max_x && S.v >= cam.min_y && S.v < cam.max_y)) return false;      // KeyFrame::IsInImage
+  S.ur = __fsub_rn(S.u, __fmul_rn(cam.bf, invz));
+  const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
+  // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) and PO.dot(Pn) (double)
+  const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
+  const float dist3D = (float)sqrt(n2);
+  const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
+  if ((dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) || dot < 0.5 * (double)dist3D) return false;
+  const float ratio = __fdiv_rn(P.max_dist, dist3D);             // MapPoint::PredictScale, MapPoint.cc:449-464
+  int level = 0;
+  for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
+  S.level = level;
+  S.radius = __fmul_rn(th, scaleFactor[level]);
+  return true;
+}
+
 // grid = ceil(nkf * nmp / 256)
 __global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __restrict__ mp, int nmp, int nkf,
                                                       const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
@@ -1546,33 +1582,8 @@ __global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __re
     bestIdx[pair] = -1;
     if (bestDist) bestDist[pair] = 256;
     const pli_fuse_point P = mp[i];
-    if (P.valid && !(skip && skip[pair])) {                      // !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound
-      const float* T = kfPose + (int64_t)kf * 15;                // Rcw row major, tcw, Ow
-      float pc[3];
-      for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);      // Rcw*p3Dw + tcw
-      const float x = pc[0], y = pc[1], z = pc[2];
-      if (!(z < 0.0f)) {                                         // :1448
-        const float invz = __fdiv_rn(1.0f, z);
-        S.u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);         // Pinhole::project, Pinhole.cpp:30-33
-        S.v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
-        if (S.u >= cam.min_x && S.u < cam.max_x && S.v >= cam.min_y && S.v < cam.max_y) {      // KeyFrame::IsInImage
-          S.ur = __fsub_rn(S.u, __fmul_rn(cam.bf, invz));
-          const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
-          // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) and PO.dot(Pn) (double)
-          const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
-          const float dist3D = (float)sqrt(n2);
-          const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
-          if (!(dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) && !(dot < 0.5 * (double)dist3D)) {
-            const float ratio = __fdiv_rn(P.max_dist, dist3D);   // MapPoint::PredictScale, MapPoint.cc:449-464
-            int level = 0;
-            for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
-            S.level = level;
-            S.radius = __fmul_rn(th, scaleFactor[level]);
-            keep = true;
-          }
-        }
-      }
-    }
+    if (P.valid && !(skip && skip[pair]))                        // !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound
+      keep = fuse_project_point<0>(P, kfPose + (int64_t)kf * 15, cam, th, levelRatio, nlevels, scaleFactor, S);
   }
   const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
   if (bal) {
@@ -1671,6 +1682,184 @@ __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restri
 template __global__ void k_fuse_match<8>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
 template __global__ void k_fuse_match<16>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
 template __global__ void k_fuse_match<64>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+
+// ---------------------------------------------------------------------------
+// Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
+// (ORBmatcher.cc:473-586 and :588-704) for one list of nmp map points against npair (keyframe, Scw) pairs.
+//
+// Unlike Fuse this search is sequential across the map points of a pair: vpMatched[bestIdx] = pMP (:579 / :696) takes the keypoint
+// away from every later point (:558 / :675).  What a point may take apart from that (gates, window, levels, distances) does not
+// depend on the other points, so:
+//
+//   k_fuse_grid        (unchanged) the cell sort of every pair's keyframe.
+//   k_sim3_project     one thread per (pair, point), fuse_project_point<form>: the survivor record goes to the DENSE slot
+//                      pair * nmp + point (level -1: the point left at a gate), so a pair's survivors stay in point order; the
+//                      slot's candidate count and best_idx are reset here.
+//   k_sim3_candidates  SIM3_LANES lanes per slot, a fixed grid striding over the slots: the window walk of k_fuse_match; every key
+//                      (distance, cell column, cell row, index) that passes the window and the level gate with a distance within
+//                      the limit goes to the slot's list of `width` keys (their order in the list is free: the minimum decides).
+//                      The count keeps counting past the width: count > width marks the query as overflowed.
+//   k_sim3_assign      one wave per pair, the owner table (-1 free, INT_MAX occupied at entry, else the point) in LDS: the wave
+//                      reads 64 counts at a time, walks the slots with candidates in point order (the next one's keys already in
+//                      flight), drops owned keys, takes the wave minimum = the reference's strict minimum in visiting order among
+//                      the free rows, stores the owner.  An overflowed query walks its window again through the cell runs.
+// The limit: bestDist <= TH_LOW * ratioHamming (:577) is a float comparison of an integer below 256, so it equals
+// dist <= floor(50.0f * ratio) (the host computes it); a key above the limit can never be accepted, whichever rows are owned.
+// Four launches per call, whatever npair and nmp.
+// ---------------------------------------------------------------------------
+constexpr int SIM3_LANES = 8;
+
+// grid = ceil(npair * nmp / 256)
+__global__ __launch_bounds__(256) void k_sim3_project(const pli_fuse_point* __restrict__ mp, int nmp, int npair,
+                                                      const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
+                                                      pli_fuse_camera cam, float th, const float* __restrict__ levelRatio,
+                                                      int nlevels, const float* __restrict__ scaleFactor, int form,
+                                                      FuseSurvivor* __restrict__ surv, int* __restrict__ candCount,
+                                                      int* __restrict__ bestIdx) {
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot >= (int64_t)npair * nmp) return;
+  const int kf = (int)(slot / nmp), i = (int)(slot - (int64_t)kf * nmp);
+  FuseSurvivor S;
+  S.kf = kf; S.mp = i; S.u = 0.f; S.v = 0.f; S.ur = 0.f; S.radius = 0.f; S.level = -1; S.pad = 0;
+  const pli_fuse_point P = mp[i];
+  if (P.valid && !(skip && skip[slot])) {                        // isBad(), spAlreadyFound.count(pMP) :501
+    const float* T = kfPose + (int64_t)kf * 15;
+    const bool keep = form ? fuse_project_point<1>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S)
+                           : fuse_project_point<0>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S);
+    if (!keep) S.level = -1;
+  }
+  surv[slot] = S;
+  candCount[slot] = 0;
+  if (bestIdx) bestIdx[slot] = -1;
+}
+
+// The window of survivor S in its keyframe's cell runs (KeyFrame::GetFeaturesInArea, KeyFrame.cc:881-925), `stride` lanes of
+// which this is lane `sub`: emit(key) for every row inside the window whose octave lies in [level - 1, level] (:563) and whose
+// distance is <= distLimit.
+template <class Emit>
+__device__ __forceinline__ void sim3_window(const FuseSurvivor& S, int sub, int stride, const uint8_t* __restrict__ mpDesc,
+                                            const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
+                                            const uint8_t* __restrict__ kfDesc, const int* __restrict__ cellStart,
+                                            const uint16_t* __restrict__ sIdx, const pli_fuse_camera& cam, float gwInv, float ghInv,
+                                            int distLimit, Emit emit) {
+  const float u = S.u, v = S.v, radius = S.radius;
+  const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
+  const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
+  const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
+  const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
+  if (!(c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1)) return;
+  const int base = kfOff[S.kf];
+  const int* cs = cellStart + (int64_t)S.kf * (FUSE_CELLS + 1);
+  uint64_t dq[4];
+  load_desc(mpDesc + (int64_t)S.mp * 32, dq);
+  for (int cx = c0; cx <= c1; ++cx) {
+    const int lo = cs[cx * GRID_ROWS + r0], hi = cs[cx * GRID_ROWS + r1 + 1];
+    for (int t = lo + sub; t < hi; t += stride) {
+      const int i2 = sIdx[base + t];
+      const pli_keypoint k = kfKp[base + i2];
+      if (!(fabsf(__fsub_rn(k.x, u)) < radius && fabsf(__fsub_rn(k.y, v)) < radius)) continue;        // KeyFrame.cc:918
+      if (k.octave < S.level - 1 || k.octave > S.level) continue;                                      // :563
+      uint64_t d2[4];
+      load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
+      const int dist = hamming256(dq, d2);
+      if (dist > distLimit) continue;
+      int px, py;
+      fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+      emit(((unsigned long long)dist << 40) | ((unsigned long long)px << 34) | ((unsigned long long)py << 28) | (unsigned long long)i2);
+    }
+  }
+}
+
+// a fixed grid of 256-thread blocks; SIM3_LANES lanes per slot.  candCount: zeroed by k_sim3_project
+__global__ __launch_bounds__(256) void k_sim3_candidates(const FuseSurvivor* __restrict__ surv, int64_t nslot,
+                                                         const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
+                                                         const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                         const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                         pli_fuse_camera cam, int distLimit, int width,
+                                                         unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
+  constexpr int PER_BLOCK = 256 / SIM3_LANES;
+  const int sub = threadIdx.x & (SIM3_LANES - 1);
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int64_t s = (int64_t)blockIdx.x * PER_BLOCK + threadIdx.x / SIM3_LANES; s < nslot; s += (int64_t)gridDim.x * PER_BLOCK) {
+    const FuseSurvivor S = surv[s];
+    if (S.level < 0) continue;
+    unsigned long long* keys = candKeys + s * width;
+    int* count = candCount + s;
+    sim3_window(S, sub, SIM3_LANES, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                [=](unsigned long long key) {
+                  const int pos = atomicAdd(count, 1);
+                  if (pos < width) keys[pos] = key;
+                });
+  }
+}
+
+// grid = pairs, one wave; LDS: the pair's rows as ints (the owner table)
+__global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restrict__ surv, int nmp, const uint8_t* __restrict__ mpDesc,
+                                                    const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
+                                                    const uint8_t* __restrict__ kfDesc, const uint8_t* __restrict__ occupied,
+                                                    const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                    pli_fuse_camera cam, int distLimit, int width,
+                                                    const unsigned long long* __restrict__ candKeys,
+                                                    const int* __restrict__ candCount, int* __restrict__ rowPoint,
+                                                    int* __restrict__ bestIdx, int* __restrict__ nmatchesOut) {
+  extern __shared__ int owner[];
+  const int pair = blockIdx.x, lane = threadIdx.x, base = kfOff[pair], nk = kfOff[pair + 1] - base;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int r = lane; r < nk; r += 64) owner[r] = (occupied && occupied[base + r]) ? INT_MAX : -1;      // vpMatched[idx] at entry
+  __syncthreads();
+  const int64_t slot0 = (int64_t)pair * nmp;
+  const int* cnts = candCount + slot0;
+  // the walk over the slots that have candidates, in point order: 64 counts per load, one bit per slot
+  int chunk = -64, cntLane = 0;
+  unsigned long long todo = 0;
+  int iNext = -1, cntNext = 0;
+  unsigned long long keyNext = ~0ull;
+  auto advance = [&]() {                                         // -> iNext (nmp: none is left), cntNext, keyNext
+    while (todo == 0) {
+      chunk += 64;
+      if (chunk >= nmp) { iNext = nmp; return; }
+      cntLane = chunk + lane < nmp ? cnts[chunk + lane] : 0;
+      todo = __builtin_amdgcn_ballot_w64(cntLane != 0);
+    }
+    const int bit = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    iNext = chunk + bit;
+    cntNext = __shfl(cntLane, bit, 64);
+    keyNext = (cntNext <= width && lane < cntNext) ? candKeys[(slot0 + iNext) * width + lane] : ~0ull;
+  };
+  advance();
+  int nmatches = 0;
+  while (iNext < nmp) {
+    const int i = iNext, cnt = cntNext;
+    unsigned long long key = keyNext;
+    advance();                                                   // the next query's keys travel while this one is decided
+    if (cnt <= width) {
+      if (key != ~0ull && owner[(int)(key & 0xFFFFFFFull)] != -1) key = ~0ull;             // :558
+    } else {                                                     // more candidates than the list holds: the window again
+      key = ~0ull;
+      sim3_window(surv[slot0 + i], lane, 64, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                  [&](unsigned long long kk) {
+                    if (owner[(int)(kk & 0xFFFFFFFull)] == -1 && kk < key) key = kk;
+                  });
+    }
+    const unsigned long long m = wave_min_u64(key);
+    if (m != ~0ull) {                                            // :577 (the limit is already applied)
+      const int b = (int)(m & 0xFFFFFFFull);
+      owner[b] = i;                                              // :579 (every lane stores the same value)
+      if (lane == 0 && bestIdx) bestIdx[slot0 + i] = b;
+      ++nmatches;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // single wave: LDS is executed in order
+  }
+  __syncthreads();
+  for (int r = lane; r < nk; r += 64) {
+    const int o = owner[r];
+    rowPoint[base + r] = (o >= 0 && o != INT_MAX) ? o : -1;
+  }
+  if (lane == 0) nmatchesOut[pair] = nmatches;
+}
 
 // ---------------------------------------------------------------------------
 // SURVEY §8(f) row 4, fisheye stereo.

@@ -1648,7 +1648,8 @@ pli_status stageImage(pli_ctx* c, int eye, const uint8_t* img, int w, int h, int
 }
 
 // ---- the searches of one item against a batch of keyframes ------------------------
-// pli_search_by_bow, pli_search_by_bow_kf, pli_search_for_triangulation and pli_fuse_search take their keyframes as flat tables:
+// pli_search_by_bow, pli_search_by_bow_kf, pli_search_for_triangulation, pli_fuse_search and pli_search_by_projection_sim3 take their
+// keyframes as flat tables:
 // keyframe k is rows kf_off[k] .. kf_off[k + 1].  What they share on the host is here; every entry point checks in the same order:
 // null / negative arguments, nkf == 0 (OK), kf_off and the per-keyframe cap (kfBatch), the other side's cap, null tables for
 // total > 0, the values, the empty other side (OK, zeroed counts).
@@ -3041,6 +3042,97 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
 #undef FUSE_MATCH
   HIPCHK(download(c, bestIdx, dBi, npairs));
   if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
+// the candidate list of one (pair, point) slot of pli_search_by_projection_sim3: 16 keys (DESIGN.md §9, Sim3 projection; the
+// ordered wave reads a list with one load, so 64 is the most; the development build can run the other widths)
+constexpr int SIM3_LIST_WIDTH = 16;
+
+pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t npair,
+                                         const int32_t* kfOff, const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfPose,
+                                         const uint8_t* skip, const uint8_t* occupied, const pli_fuse_camera* cam, float th,
+                                         const float* levelRatio, float ratioHamming, int32_t projectForm, int32_t* rowPoint,
+                                         int32_t* bestIdx, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || nmp < 0 || npair < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (npair > 0 && (!kfOff || !kfPose || !nmatches)) ||
+      (projectForm != 0 && projectForm != 1)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  const int nlevels = c->hp.nlevels;
+  for (int n = 0; n < nlevels - 1; ++n)
+    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
+  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  // bestDist <= TH_LOW * ratioHamming (ORBmatcher.cc:577): a float product, one rounding.  With no candidate the reference holds
+  // bestDist = 256, bestIdx = -1 and would write vpMatched[-1] if the product reached 256
+  const float limit = 50.0f * ratioHamming;
+  if (!std::isfinite(ratioHamming) || !(ratioHamming > 0.f) || !(limit < 256.0f)) {
+    g_err = "ratio_hamming must be finite, > 0 and 50 * ratio_hamming < 256";
+    return PLI_ERR_INVALID;
+  }
+  const int distLimit = (int)std::floor(limit);             // (float)d <= limit  <=>  d <= floor(limit) for the integers d < 256
+  if (npair == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(npair, kfOff, "a keyframe has more features than the projection search cap", B);
+  if (st != PLI_OK) return st;
+  const int64_t total = B.total;
+  if (total > 0 && (!kfKp || !kfDesc || !rowPoint)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (!octavesOk(c, kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
+  std::fill(nmatches, nmatches + npair, 0);
+  if (nmp == 0 || total == 0) {
+    if (total > 0) std::fill(rowPoint, rowPoint + total, -1);
+    if (bestIdx) std::fill(bestIdx, bestIdx + (size_t)npair * nmp, -1);
+    return PLI_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  int width = SIM3_LIST_WIDTH;
+  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) width = std::min(64, std::max(1, atoi(e)));
+  const size_t nslot = (size_t)npair * nmp;
+  ScratchPlan plan;
+  auto dMp = plan.add<pli_fuse_point>(nmp);
+  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
+  auto dOff = plan.add<int>((size_t)npair + 1);
+  auto dKk = plan.add<pli_keypoint>(total);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dPose = plan.add<float>((size_t)npair * 15);
+  auto dSkip = plan.add<uint8_t>(skip ? nslot : 0);
+  auto dOcc = plan.add<uint8_t>(occupied ? total : 0);
+  auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
+  auto dCell = plan.add<int>((size_t)npair * (GRID_COLS * GRID_ROWS + 1));
+  auto dSi = plan.add<uint16_t>(total);
+  auto dSurv = plan.add<FuseSurvivor>(nslot);
+  auto dKeys = plan.add<unsigned long long>(nslot * width);
+  auto dCnt = plan.add<int>(nslot);
+  auto dRow = plan.add<int>(total);
+  auto dBi = plan.add<int>(bestIdx ? nslot : 0);
+  auto dNm = plan.add<int>(npair);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  float hlv[2 * MAX_LEVELS] = {};
+  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
+  levelTables(c, hlv + MAX_LEVELS, nullptr, nullptr);
+  HIPCHK(upload(c, dMp, mp, nmp));
+  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)npair + 1));
+  HIPCHK(upload(c, dKk, kfKp, total));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  HIPCHK(upload(c, dPose, kfPose, (size_t)npair * 15));
+  if (skip) HIPCHK(upload(c, dSkip, skip, nslot));
+  if (occupied) HIPCHK(upload(c, dOcc, occupied, total));
+  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
+  const uint8_t* dSkipPtr = skip ? (const uint8_t*)dSkip : nullptr;
+  const uint8_t* dOccPtr = occupied ? (const uint8_t*)dOcc : nullptr;
+  int* dBiPtr = bestIdx ? (int*)dBi : nullptr;
+  const float* lv = dLv;
+  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(npair), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
+  LAUNCH(c, "k_sim3_project", k_sim3_project, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, dMp, nmp, npair, dPose, dSkipPtr, *cam,
+         th, lv, nlevels, lv + MAX_LEVELS, projectForm, dSurv, dCnt, dBiPtr);
+  LAUNCH(c, "k_sim3_candidates", k_sim3_candidates, dim3(1024), dim3(256), 0, dSurv, (int64_t)nslot, dMd, dOff, dKk, dKd, dCell, dSi, *cam,
+         distLimit, width, dKeys, dCnt);
+  LAUNCH(c, "k_sim3_assign", k_sim3_assign, dim3(npair), dim3(64), (size_t)B.maxNk * sizeof(int), dSurv, nmp, dMd, dOff, dKk, dKd, dOccPtr,
+         dCell, dSi, *cam, distLimit, width, dKeys, dCnt, dRow, dBiPtr, dNm);
+  HIPCHK(download(c, rowPoint, dRow, total));
+  if (bestIdx) HIPCHK(download(c, bestIdx, dBi, nslot));
+  HIPCHK(download(c, nmatches, dNm, npair));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }

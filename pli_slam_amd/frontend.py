@@ -325,6 +325,55 @@ class Frontend:
                                      ptr(best_dist)))
         return best_idx, best_dist
 
+    def search_by_projection_sim3(self, points, descs, pairs, cam, th=3.0, ratio_hamming=1.0, project_form=0, skip=None,
+                                  level_ratio=None):
+        """Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th,
+        ratioHamming) (ORBmatcher.cc:473-704) of ONE list of map points `points` (capi.FUSE_POINT_DT rows, descriptors `descs`)
+        against every (keyframe, Scw) pair of `pairs`, in one call; the points of a pair are decided in list order and a row taken
+        by one is closed to the later ones.  pairs: list of (kp, desc, pose[, occupied]) - mvKeysUn as KEYPOINT_DT rows,
+        mDescriptors, pose = 15 floats (Rcw row major, tcw, Ow, decomposed from Scw), occupied = one flag per row (vpMatched[idx]
+        != NULL at entry; absent or None: none).  cam: capi.FuseCamera or its 9 values; skip: npair x nmp, != 0 leaves a point out
+        of a pair (spAlreadyFound); project_form: 0 = Pinhole::project (:519), 1 = the inverse-depth form (:631-636).
+        Returns (row_point: one int32 array per pair, the point that took each row or -1; best_idx[npair, nmp]: the row a point
+        took or -1; nmatches[npair])."""
+        pts = np.ascontiguousarray(points, capi.FUSE_POINT_DT).reshape(-1)
+        d = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        if len(d) != len(pts):
+            raise ValueError("every map point needs one descriptor")
+        npair, nmp = len(pairs), len(pts)
+        off, (kk, kd) = pack_keyframes(pairs, FUSE_COLUMNS[:2], "every feature needs one keypoint and one descriptor")
+        pose = np.ascontiguousarray([np.asarray(p[2], np.float32).reshape(15) for p in pairs], np.float32).reshape(npair, 15)
+        occ = None
+        if any(len(p) > 3 and p[3] is not None for p in pairs):
+            occ = np.zeros(int(off[-1]), np.uint8)
+            for k, p in enumerate(pairs):
+                if len(p) > 3 and p[3] is not None:
+                    o = np.asarray(p[3]).reshape(-1)
+                    if len(o) != off[k + 1] - off[k]:
+                        raise ValueError("occupied: one flag per keyframe row")
+                    occ[off[k]:off[k + 1]] = o != 0
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint8)
+            if skip.shape != (npair, nmp):
+                raise ValueError("skip: npair x nmp")
+        if level_ratio is None:
+            if getattr(self, "_fuse_level_ratio", None) is None:
+                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
+            level_ratio = self._fuse_level_ratio
+        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
+        if len(level_ratio) != self.cfg.orb_nlevels - 1:
+            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        rows = np.full(int(off[-1]), -1, np.int32)
+        best_idx = np.full((npair, nmp), -1, np.int32)
+        nmatches = np.zeros(npair, np.int32)
+        check(self.L.pli_search_by_projection_sim3(self.h, ptr(pts), ptr(d), nmp, npair, ptr(off), ptr(kk), ptr(kd), ptr(pose),
+                                                   ptr(skip), ptr(occ), C.byref(cam), float(th), ptr(level_ratio),
+                                                   float(ratio_hamming), int(project_form), ptr(rows), ptr(best_idx),
+                                                   ptr(nmatches)))
+        return [rows[off[k]:off[k + 1]] for k in range(npair)], best_idx, nmatches
+
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""
