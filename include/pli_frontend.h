@@ -663,6 +663,51 @@ pli_status pli_search_by_projection_sim3(pli_ctx* ctx, const pli_fuse_point* mp,
                                          const pli_fuse_camera* cam, float th, const float* level_ratio, float ratio_hamming,
                                          int32_t project_form, int32_t* row_point, int32_t* best_idx, int32_t* nmatches);
 
+/* Relocalisation's ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) ORBmatcher.cc:2325-2447
+ * (Tracking.cc:4290 with th 10, ORBdist 100 and :4304 with 3, 64), for ONE frame table against ncand candidates in one call.  The
+ * roles are those of pli_search_by_projection_sim3 turned round: the searched table is the frame (f_kp = mvKeysUn: pt, octave and,
+ * with check_orientation, angle are read; f_desc = mDescriptors; nf rows), the point lists belong to the candidates.  The search
+ * is sequential across the points of a candidate: CurrentFrame.mvpMapPoints[bestIdx2] = pMP (:2405) closes the row to every later
+ * point (:2389).  Points are decided in list order; the candidates are independent of each other, each with its own owner state,
+ * also when two of them list the same points.
+ * Candidate c owns rows mp_off[c] .. mp_off[c+1]-1 of mp, mp_desc and mp_angle (pKF->GetMapPointMatches() in index order, :2339):
+ * mp as pli_fuse_search (normal is not read), valid = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP) (:2345-2347: the lists are
+ * per candidate, so there is no skip table); mp_desc = GetDescriptor(); mp_angle = pKF->mvKeysUn[i].angle, may be NULL when
+ * check_orientation == 0.  pose: ncand x 15 floats - Rcw row major, tcw (of CurrentFrame.mTcw as set for that candidate) and
+ * Ow = -Rcw.t()*tcw (:2329-2331), computed on the host.  occupied: ncand x nf bytes, may be NULL: != 0 =
+ * CurrentFrame.mvpMapPoints[i2] != NULL at entry (:2389).  cam, th, level_ratio as pli_fuse_search (bf is not read).
+ * Gates in the reference's order, which are NOT those of the Sim3 search: valid; NO z < 0 gate (a point behind the camera whose
+ * projection falls into the image is searched like any other); Pinhole::project, fx*x/z + cx (:2353); the image gate :2355-2358,
+ * closed on both sides (not IsInImage's half-open one); the distance range :2368; NO viewing-normal gate;
+ * MapPoint::PredictScale(dist3D, &CurrentFrame) :2371 through level_ratio; radius = th * mvScaleFactors[level] :2374; an empty
+ * window :2378.  Every operation is float, in the written order, nothing contracted (the matrix product and cv::norm as
+ * pli_fuse_search).
+ * One deviation: the reference's gate lets a NaN projection through and then converts NaN to int, which is undefined.  Here a point
+ * is admitted only when u >= min_x && u <= max_x && v >= min_y && v <= max_y: for every non-NaN u, v this is the reference's gate,
+ * a NaN leaves.
+ * Candidates :2386-2401: the rows of Frame::GetFeaturesInArea(u, v, radius, level-1, level+1) (Frame.cc:774-843: the cells and
+ * the visiting order of KeyFrame::GetFeaturesInArea, octave in [level-1, level+1]) without the owned ones (occupied at entry, or
+ * taken by an earlier point of this candidate); the strict minimum of the Hamming distance in visiting order = the minimum of the
+ * key (distance, cell column, cell row, index).  Acceptance :2403: bestDist <= orb_dist, integers.  With no candidate the
+ * reference holds bestDist = 256 and bestIdx2 = -1 and would write mvpMapPoints[-1] at orb_dist = 256: orb_dist must lie in
+ * [0, 255].
+ * check_orientation (mbCheckOrientation, :2408-2444): the bin of pKF->mvKeysUn[i].angle - CurrentFrame.mvKeysUn[bestIdx2].angle
+ * as in pli_search_by_bow (every angle in [0, 360)), ComputeThreeMaxima after the walk, every match in another bin set back to
+ * NULL and nmatches decremented.  A row that the filter gives back was still closed during the walk.
+ * row_point: ncand x nf, the index WITHIN the candidate's own list of the point that holds the row after the rotation filter
+ * (CurrentFrame.mvpMapPoints[row] = vpMPs[i]), -1 otherwise; rows occupied at entry stay -1.  best_idx (may be NULL):
+ * mp_off[ncand] entries, the row a point took BEFORE the filter or -1.  nmatches[ncand]: the reference's return value.
+ * Errors: PLI_ERR_INVALID for null pointers, mp_off[0] != 0 or a decreasing mp_off, an octave outside [0, orb_nlevels), a
+ * decreasing or NaN level_ratio, orb_dist outside [0, 255], with check_orientation an angle outside [0, 360); PLI_ERR_CAPACITY
+ * for nf > PLI_BOW_MAX_FEATURES (the owner table is nf ints in LDS) or a list with more than PLI_BOW_MAX_FEATURES points (a
+ * keyframe has no more rows than that); nothing is truncated.  ncand == 0, empty point lists and nf == 0 are valid.  The number of
+ * kernel launches does not depend on ncand or on the number of points. */
+pli_status pli_search_by_projection_reloc(pli_ctx* ctx, int32_t ncand, const int32_t* mp_off, const pli_fuse_point* mp,
+                                          const uint8_t* mp_desc, const float* mp_angle, const float* pose,
+                                          const pli_keypoint* f_kp, const uint8_t* f_desc, int32_t nf, const uint8_t* occupied,
+                                          const pli_fuse_camera* cam, float th, const float* level_ratio, int32_t orb_dist,
+                                          int32_t check_orientation, int32_t* row_point, int32_t* best_idx, int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

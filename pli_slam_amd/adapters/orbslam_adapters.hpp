@@ -20,6 +20,9 @@
 //                                                             vpMatched, vpMatchedKF, th, ratioHamming)   include/ORBmatcher.h,
 //                                                             src/ORBmatcher.cc:473-586, :588-704 (no second cameras; + a batch
 //                                                             form for LoopClosing's loop over covisible keyframes)
+//   ORB_SLAM3::ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)   include/ORBmatcher.h,
+//                                                             src/ORBmatcher.cc:2325-2447 (relocalisation, Tracking.cc:4290 and :4304;
+//                                                             no second cameras; + a batch form over the candidate keyframes)
 //
 // Frame.cc / Tracking.cc keep calling these names unchanged; INTEGRATION.md lists the edits (swap the headers).
 //
@@ -1104,6 +1107,43 @@ class PliORBmatcher {
     sim3Projection(vpKFs, vScw, vpPoints, vvpMatched, th, ratioHamming, 0, vnmatches, [](int, int, int) {});
   }
 
+  // ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, const float th, const
+  // int ORBdist), ORBmatcher.cc:2325-2447 (Tracking::Relocalization, Tracking.cc:4290 and :4304): the whole loop, the rotation
+  // histogram and ComputeThreeMaxima run on the device (pli_search_by_projection_reloc); Rcw, tcw and Ow = -Rcw.t()*tcw (:2329-2331)
+  // are the reference's own cv::Mat expressions, run here.  CurrentFrame.mvpMapPoints[row] = vpMPs[i] for every row a point holds
+  // after the rotation filter; the return value is the reference's.  FrameT needs mTcw, N, Nleft, mvKeysUn, mDescriptors,
+  // mvpMapPoints, fx, fy, cx, cy, mbf, mnMinX .. mnMaxY, mnScaleLevels and mfLogScaleFactor; KeyFrameT mpCamera2, mvKeysUn and
+  // GetMapPointMatches().
+  template <class KeyFrameT>
+  int SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const std::set<MapPointT*>& sAlreadyFound, const float th, const int ORBdist) {
+    std::vector<std::vector<MapPointT*>> vvpMapPoints;
+    std::vector<int> vnmatches;
+    relocProjection(CurrentFrame, std::vector<KeyFrameT*>(1, pKF), std::vector<cv::Mat>(1, CurrentFrame.mTcw),
+                    std::vector<const std::set<MapPointT*>*>(1, &sAlreadyFound),
+                    std::vector<const std::vector<MapPointT*>*>(1, &CurrentFrame.mvpMapPoints), th, ORBdist, vvpMapPoints, vnmatches);
+    CurrentFrame.mvpMapPoints.swap(vvpMapPoints[0]);                         // :2405, :2439
+    return vnmatches[0];
+  }
+
+  // (not in the reference) The same search for several candidates of Tracking::Relocalization with ONE device call, for an
+  // integrator who runs PnP and the pose optimisation for every candidate first: candidate k has its own pose vTcw[k] (what
+  // CurrentFrame.mTcw would be at :4290), its own sAlreadyFound and its own state of mvpMapPoints at entry (vvpEntry[k], N
+  // entries).  vvpMapPoints[k] is what CurrentFrame.mvpMapPoints would hold after the single call, vnmatches[k] its return value;
+  // CurrentFrame itself is not written.  The candidates do not share state, so every result equals the single call's.  The
+  // reference's loop stops at the first candidate with enough inliers (bMatch); this form has searched the later ones by then.
+  template <class KeyFrameT>
+  void SearchByProjection(const FrameT& CurrentFrame, const std::vector<KeyFrameT*>& vpKFs, const std::vector<cv::Mat>& vTcw,
+                          const std::vector<std::set<MapPointT*>>& vsAlreadyFound, const std::vector<std::vector<MapPointT*>>& vvpEntry,
+                          const float th, const int ORBdist, std::vector<std::vector<MapPointT*>>& vvpMapPoints,
+                          std::vector<int>& vnmatches) {
+    if (vsAlreadyFound.size() != vpKFs.size() || vvpEntry.size() != vpKFs.size())
+      throw std::logic_error("SearchByProjection: one sAlreadyFound and one state of mvpMapPoints per candidate");
+    std::vector<const std::set<MapPointT*>*> found;
+    std::vector<const std::vector<MapPointT*>*> entry;
+    for (size_t k = 0; k < vpKFs.size(); ++k) { found.push_back(&vsAlreadyFound[k]); entry.push_back(&vvpEntry[k]); }
+    relocProjection(CurrentFrame, vpKFs, vTcw, found, entry, th, ORBdist, vvpMapPoints, vnmatches);
+  }
+
   // the level_ratio table the Fuse adapters hand to pli_fuse_search (tests read it)
   template <class KeyFrameT>
   const std::vector<float>& fuseLevelRatio(KeyFrameT* pKF) {
@@ -1125,6 +1165,17 @@ class PliORBmatcher {
       mfFuseLogSf = logSf;
     }
     return mvFuseLevelRatio;
+  }
+
+  // Rcw (row major), tcw and Ow = -Rcw.t()*tcw of a frame pose, the reference's own cv::Mat expressions ORBmatcher.cc:2329-2331;
+  // tests read it
+  static void relocPose(const cv::Mat& Tcw, float pose[15]) {
+    const cv::Mat Rcw = Tcw.rowRange(0, 3).colRange(0, 3);
+    const cv::Mat tcw = Tcw.rowRange(0, 3).col(3);
+    const cv::Mat Ow = -Rcw.t() * tcw;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) pose[i * 3 + j] = Rcw.template at<float>(i, j);
+    for (int i = 0; i < 3; ++i) { pose[9 + i] = tcw.template at<float>(i); pose[12 + i] = Ow.template at<float>(i); }
   }
 
   // The decomposition of a Sim3 matrix, ORBmatcher.cc:483-487 / :1620-1624, into Rcw (row major), tcw, Ow; tests read it (PARITY UNPINNED:
@@ -1204,6 +1255,61 @@ class PliORBmatcher {
         vvpMatched[k][r - T.off[k]] = vpPoints[i];                            // :579 / :696
         onMatch(k, r - T.off[k], i);
       }
+  }
+  // What the two SearchByProjection(Frame, KeyFrame, sAlreadyFound, ...) forms share: the candidates' point lists, the frame's
+  // table, one device search; vvpMapPoints[k] = the entry state with the rows candidate k's points hold written over it.
+  template <class KeyFrameT>
+  void relocProjection(const FrameT& F, const std::vector<KeyFrameT*>& vpKFs, const std::vector<cv::Mat>& vTcw,
+                       const std::vector<const std::set<MapPointT*>*>& vsFound,
+                       const std::vector<const std::vector<MapPointT*>*>& vEntry, float th, int ORBdist,
+                       std::vector<std::vector<MapPointT*>>& vvpMapPoints, std::vector<int>& vnmatches) {
+    const int ncand = (int)vpKFs.size(), nf = F.N;
+    if (vTcw.size() != vpKFs.size()) throw std::logic_error("SearchByProjection: one Tcw per candidate");
+    if (F.Nleft != -1) throw std::logic_error("SearchByProjection: a frame of two cameras (Nleft != -1) is not supported");
+    vnmatches.assign(ncand, 0);
+    vvpMapPoints.assign(ncand, std::vector<MapPointT*>());
+    if (ncand == 0) return;
+    std::vector<std::vector<MapPointT*>> vvpMPs(ncand);
+    std::vector<int32_t> off(1, 0);
+    std::vector<pli_fuse_point> pts;
+    std::vector<uint8_t> desc, occupied((size_t)ncand * nf, 0);
+    std::vector<float> angle, pose;
+    for (int k = 0; k < ncand; ++k) {
+      KeyFrameT* pKF = vpKFs[k];
+      if (pKF->mpCamera2) throw std::logic_error("SearchByProjection: a keyframe with mpCamera2 is not supported");
+      if ((int)vEntry[k]->size() < nf) throw std::logic_error("SearchByProjection: mvpMapPoints is shorter than the frame");
+      float T[15];
+      relocPose(vTcw[k], T);
+      pose.insert(pose.end(), T, T + 15);
+      vvpMPs[k] = pKF->GetMapPointMatches();                                 // :2339
+      const std::vector<MapPointT*>& vpMPs = vvpMPs[k];
+      if (vpMPs.size() > pKF->mvKeysUn.size()) throw std::logic_error("SearchByProjection: more map points than keypoints in a keyframe");
+      for (size_t i = 0; i < vpMPs.size(); ++i) {
+        pli_fuse_point P = fusePoint(vpMPs[i]);                              // pMP, !isBad() :2345-2347
+        if (P.valid && vsFound[k]->count(vpMPs[i])) P.valid = 0;             // !sAlreadyFound.count(pMP)
+        pts.push_back(P);
+        desc.insert(desc.end(), 32, (uint8_t)0);
+        if (P.valid) std::memcpy(&desc[desc.size() - 32], vpMPs[i]->GetDescriptor().template ptr<uint8_t>(), 32);
+        angle.push_back(pKF->mvKeysUn[i].angle);                             // :2410
+      }
+      off.push_back((int32_t)pts.size());
+      for (int j = 0; j < nf; ++j) occupied[(size_t)k * nf + j] = (*vEntry[k])[j] ? 1 : 0;      // :2389
+    }
+    std::vector<pli_keypoint> kp((size_t)nf);
+    for (int j = 0; j < nf; ++j) kp[j] = pli_detail::keypoint(F.mvKeysUn[j]);
+    const pli_fuse_camera cam = {F.fx, F.fy, F.cx, F.cy, F.mbf, (float)F.mnMinX, (float)F.mnMaxX, (float)F.mnMinY, (float)F.mnMaxY};
+    std::vector<int> rowPoint;
+    pli_detail::deviceContext("SearchByProjection")
+        ->searchByProjectionReloc(ncand, off.data(), pts.data(), desc.data(), angle.data(), pose.data(), kp.data(),
+                                  nf > 0 ? F.mDescriptors.template ptr<uint8_t>() : nullptr, nf, occupied.data(), cam, th,
+                                  fuseLevelRatio(&F), ORBdist, mbCheckOrientation, rowPoint, vnmatches);
+    for (int k = 0; k < ncand; ++k) {
+      vvpMapPoints[k] = *vEntry[k];
+      for (int r = 0; r < nf; ++r) {
+        const int i = rowPoint[(size_t)k * nf + r];
+        if (i >= 0) vvpMapPoints[k][r] = vvpMPs[k][i];                       // :2405, less the rows :2439 gives back
+      }
+    }
   }
   struct FuseTables : pli_detail::KfTable {
     std::vector<pli_keypoint> kp;

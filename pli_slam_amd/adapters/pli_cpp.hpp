@@ -186,6 +186,20 @@ class Frontend {
     check(pli_search_by_projection_sim3(ctx_, mp, mpDesc, nmp, npair, kfOff, kfKp, kfDesc, kfPose, skip, occupied, &cam, th,
                                         levelRatio.data(), ratioHamming, projectForm, rowPoint.data(), nullptr, nmatches.data()));
   }
+  // Relocalisation's ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) ORBmatcher.cc:2325-2447 of one
+  // frame table (nf rows) against ncand candidates, candidate c owning rows mpOff[c] .. mpOff[c + 1] of mp / mpDesc / mpAngle
+  // (include/pli_frontend.h pli_search_by_projection_reloc): rowPoint (ncand x nf) = the index within the candidate's list of the
+  // point that holds the row after the rotation filter or -1, nmatches[c] = the reference's return value for candidate c.
+  void searchByProjectionReloc(int ncand, const int32_t* mpOff, const pli_fuse_point* mp, const uint8_t* mpDesc, const float* mpAngle,
+                               const float* pose, const pli_keypoint* fKp, const uint8_t* fDesc, int nf, const uint8_t* occupied,
+                               const pli_fuse_camera& cam, float th, const std::vector<float>& levelRatio, int orbDist,
+                               bool checkOrientation, std::vector<int>& rowPoint, std::vector<int>& nmatches) {
+    rowPoint.assign((size_t)ncand * nf, -1);
+    nmatches.assign(ncand, 0);
+    check(pli_search_by_projection_reloc(ctx_, ncand, mpOff, mp, mpDesc, mpAngle, pose, fKp, fDesc, nf, occupied, &cam, th,
+                                         levelRatio.data(), orbDist, checkOrientation ? 1 : 0, rowPoint.data(), nullptr,
+                                         nmatches.data()));
+  }
   // level_ratio of pli_fuse_search from the HOST's own MapPoint::PredictScale expression: levelOf(ratio) must be the tree's
   // expression compiled by the tree's compiler (ceil(log(ratio) / mfLogScaleFactor) with its clamps), so that whichever overload
   // of log its toolchain selects is the one the thresholds describe.  For n = 0 .. nlevels-2 the largest float for which

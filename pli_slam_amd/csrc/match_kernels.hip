@@ -16,6 +16,7 @@
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 //   k_fuse_grid, k_sim3_project, k_sim3_candidates, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
+//   k_fuse_grid, k_reloc_project, k_reloc_candidates, k_reloc_assign  ORBmatcher::SearchByProjection(Frame, KF, sAlreadyFound, ...) (ORBmatcher.cc:2325-2447)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -1734,9 +1735,10 @@ __global__ __launch_bounds__(256) void k_sim3_project(const pli_fuse_point* __re
 }
 
 // The window of survivor S in its keyframe's cell runs (KeyFrame::GetFeaturesInArea, KeyFrame.cc:881-925), `stride` lanes of
-// which this is lane `sub`: emit(key) for every row inside the window whose octave lies in [level - 1, level] (:563) and whose
+// which this is lane `sub`: emit(key) for every row inside the window whose octave lies in [level - 1, level + kUp] (kUp 0: :563;
+// kUp 1: Frame::GetFeaturesInArea(..., level - 1, level + 1) of ORBmatcher.cc:2376, the same cells in the same order) and whose
 // distance is <= distLimit.
-template <class Emit>
+template <int kUp, class Emit>
 __device__ __forceinline__ void sim3_window(const FuseSurvivor& S, int sub, int stride, const uint8_t* __restrict__ mpDesc,
                                             const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
                                             const uint8_t* __restrict__ kfDesc, const int* __restrict__ cellStart,
@@ -1758,7 +1760,7 @@ __device__ __forceinline__ void sim3_window(const FuseSurvivor& S, int sub, int 
       const int i2 = sIdx[base + t];
       const pli_keypoint k = kfKp[base + i2];
       if (!(fabsf(__fsub_rn(k.x, u)) < radius && fabsf(__fsub_rn(k.y, v)) < radius)) continue;        // KeyFrame.cc:918
-      if (k.octave < S.level - 1 || k.octave > S.level) continue;                                      // :563
+      if (k.octave < S.level - 1 || k.octave > S.level + kUp) continue;                                // :563 / :2376
       uint64_t d2[4];
       load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
       const int dist = hamming256(dq, d2);
@@ -1786,30 +1788,25 @@ __global__ __launch_bounds__(256) void k_sim3_candidates(const FuseSurvivor* __r
     if (S.level < 0) continue;
     unsigned long long* keys = candKeys + s * width;
     int* count = candCount + s;
-    sim3_window(S, sub, SIM3_LANES, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
-                [=](unsigned long long key) {
-                  const int pos = atomicAdd(count, 1);
-                  if (pos < width) keys[pos] = key;
-                });
+    sim3_window<0>(S, sub, SIM3_LANES, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                   [=](unsigned long long key) {
+                     const int pos = atomicAdd(count, 1);
+                     if (pos < width) keys[pos] = key;
+                   });
   }
 }
 
-// grid = pairs, one wave; LDS: the pair's rows as ints (the owner table)
-__global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restrict__ surv, int nmp, const uint8_t* __restrict__ mpDesc,
-                                                    const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
-                                                    const uint8_t* __restrict__ kfDesc, const uint8_t* __restrict__ occupied,
-                                                    const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
-                                                    pli_fuse_camera cam, int distLimit, int width,
-                                                    const unsigned long long* __restrict__ candKeys,
-                                                    const int* __restrict__ candCount, int* __restrict__ rowPoint,
-                                                    int* __restrict__ bestIdx, int* __restrict__ nmatchesOut) {
-  extern __shared__ int owner[];
-  const int pair = blockIdx.x, lane = threadIdx.x, base = kfOff[pair], nk = kfOff[pair + 1] - base;
-  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
-  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
-  for (int r = lane; r < nk; r += 64) owner[r] = (occupied && occupied[base + r]) ? INT_MAX : -1;      // vpMatched[idx] at entry
-  __syncthreads();
-  const int64_t slot0 = (int64_t)pair * nmp;
+// The ordered walk of one wave over the slots slot0 .. slot0 + nmp (one pair's, or one candidate's, points in list order) against
+// the owner table in LDS (-1 free, INT_MAX occupied at entry, else the point): 64 counts per load, one bit per slot with
+// candidates; the next slot's keys travel while this one is decided.  Returns the number of rows taken.  kUp as sim3_window.
+template <int kUp>
+__device__ __forceinline__ int sim3_ordered_walk(int* owner, int lane, const FuseSurvivor* __restrict__ surv, int64_t slot0, int nmp,
+                                                 const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
+                                                 const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                 const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                 const pli_fuse_camera& cam, float gwInv, float ghInv, int distLimit, int width,
+                                                 const unsigned long long* __restrict__ candKeys,
+                                                 const int* __restrict__ candCount, int* __restrict__ bestIdx) {
   const int* cnts = candCount + slot0;
   // the walk over the slots that have candidates, in point order: 64 counts per load, one bit per slot
   int chunk = -64, cntLane = 0;
@@ -1839,10 +1836,10 @@ __global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restri
       if (key != ~0ull && owner[(int)(key & 0xFFFFFFFull)] != -1) key = ~0ull;             // :558
     } else {                                                     // more candidates than the list holds: the window again
       key = ~0ull;
-      sim3_window(surv[slot0 + i], lane, 64, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
-                  [&](unsigned long long kk) {
-                    if (owner[(int)(kk & 0xFFFFFFFull)] == -1 && kk < key) key = kk;
-                  });
+      sim3_window<kUp>(surv[slot0 + i], lane, 64, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                       [&](unsigned long long kk) {
+                         if (owner[(int)(kk & 0xFFFFFFFull)] == -1 && kk < key) key = kk;
+                       });
     }
     const unsigned long long m = wave_min_u64(key);
     if (m != ~0ull) {                                            // :577 (the limit is already applied)
@@ -1853,12 +1850,173 @@ __global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restri
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // single wave: LDS is executed in order
   }
+  return nmatches;
+}
+
+// grid = pairs, one wave; LDS: the pair's rows as ints (the owner table)
+__global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restrict__ surv, int nmp, const uint8_t* __restrict__ mpDesc,
+                                                    const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
+                                                    const uint8_t* __restrict__ kfDesc, const uint8_t* __restrict__ occupied,
+                                                    const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                    pli_fuse_camera cam, int distLimit, int width,
+                                                    const unsigned long long* __restrict__ candKeys,
+                                                    const int* __restrict__ candCount, int* __restrict__ rowPoint,
+                                                    int* __restrict__ bestIdx, int* __restrict__ nmatchesOut) {
+  extern __shared__ int owner[];
+  const int pair = blockIdx.x, lane = threadIdx.x, base = kfOff[pair], nk = kfOff[pair + 1] - base;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int r = lane; r < nk; r += 64) owner[r] = (occupied && occupied[base + r]) ? INT_MAX : -1;      // vpMatched[idx] at entry
+  __syncthreads();
+  const int nmatches = sim3_ordered_walk<0>(owner, lane, surv, (int64_t)pair * nmp, nmp, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx,
+                                            cam, gwInv, ghInv, distLimit, width, candKeys, candCount, bestIdx);
   __syncthreads();
   for (int r = lane; r < nk; r += 64) {
     const int o = owner[r];
     rowPoint[base + r] = (o >= 0 && o != INT_MAX) ? o : -1;
   }
   if (lane == 0) nmatchesOut[pair] = nmatches;
+}
+
+// ---------------------------------------------------------------------------
+// Relocalisation's ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:2325-2447;
+// Tracking.cc:4290, :4304) of ONE frame table against ncand candidates, each with its own point list (rows mpOff[c] .. mpOff[c + 1]
+// of mp / mpDesc / mpAngle), its own pose (the frame's Tcw after that candidate's PnP) and its own occupied rows.
+//
+// The roles are those of the Sim3 search turned round: the searched table is the frame (one "keyframe" for k_fuse_grid, kfOff =
+// {0, nf}), the lists belong to the candidates.  The search is ordered in the same way: mvpMapPoints[bestIdx2] = pMP (:2405) closes
+// the row to every later point (:2389).
+//
+//   k_fuse_grid         (unchanged) the cell sort of the frame's table, once for all candidates.
+//   k_reloc_project     one thread per point, the DENSE slot = the point's row in the ragged list; reloc_project_point: the gates of
+//                       :2351-2374, which are NOT those of fuse_project_point (no z < 0 gate, the image gate closed on both sides,
+//                       no viewing-normal gate).
+//   k_reloc_candidates  k_sim3_candidates over sim3_window<1>: octaves in [level - 1, level + 1] (:2376), keys within ORBdist (:2403).
+//   k_reloc_assign      one wave per candidate: the owner table of nf ints in LDS, sim3_ordered_walk<1>, then (mbCheckOrientation,
+//                       :2408-2444) the 30-bin histogram over the rows taken, ComputeThreeMaxima, the filter and the corrected
+//                       count.  A row that the filter gives back was closed during the whole walk, as in the reference.
+// Four launches per call, whatever ncand and the lists.
+// ---------------------------------------------------------------------------
+
+// One point up to the window search, :2351-2374 in the reference's order.  true: S holds the projection, the level and the radius.
+__device__ __forceinline__ bool reloc_project_point(const pli_fuse_point& P, const float* __restrict__ T /* Rcw row major, tcw, Ow */,
+                                                    const pli_fuse_camera& cam, float th, const float* __restrict__ levelRatio,
+                                                    int nlevels, const float* __restrict__ scaleFactor, FuseSurvivor& S) {
+  float pc[3];
+  for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);      // Rcw*x3Dw + tcw :2351
+  const float x = pc[0], y = pc[1], z = pc[2];                   // no z < 0 gate: a point behind the camera is searched too
+  S.u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);   // Pinhole::project, Pinhole.cpp:30-33
+  S.v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+  // :2355-2358, closed on both sides; written so that a NaN leaves (the reference would convert it to int: undefined)
+  if (!(S.u >= cam.min_x && S.u <= cam.max_x && S.v >= cam.min_y && S.v <= cam.max_y)) return false;
+  const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
+  // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) :2362
+  const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
+  const float dist3D = (float)sqrt(n2);
+  if (dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) return false;        // :2368; no viewing-normal gate
+  const float ratio = __fdiv_rn(P.max_dist, dist3D);             // MapPoint::PredictScale(dist, Frame*), MapPoint.cc:466-482
+  int level = 0;
+  for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
+  S.level = level;
+  S.radius = __fmul_rn(th, scaleFactor[level]);                  // :2374
+  return true;
+}
+
+// grid = ceil(npts / 256), npts = mpOff[ncand]
+__global__ __launch_bounds__(256) void k_reloc_project(const pli_fuse_point* __restrict__ mp, const int* __restrict__ mpOff, int ncand,
+                                                       const float* __restrict__ pose, pli_fuse_camera cam, float th,
+                                                       const float* __restrict__ levelRatio, int nlevels,
+                                                       const float* __restrict__ scaleFactor, FuseSurvivor* __restrict__ surv,
+                                                       int* __restrict__ candCount, int* __restrict__ bestIdx) {
+  const int slot = blockIdx.x * 256 + threadIdx.x;
+  if (slot >= mpOff[ncand]) return;
+  int lo = 0, hi = ncand;                                        // the candidate: the last c with mpOff[c] <= slot
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (mpOff[mid] <= slot) lo = mid;
+    else hi = mid;
+  }
+  FuseSurvivor S;
+  S.kf = 0; S.mp = slot; S.u = 0.f; S.v = 0.f; S.ur = 0.f; S.radius = 0.f; S.level = -1; S.pad = 0;      // kf 0: the frame's table
+  const pli_fuse_point P = mp[slot];
+  if (P.valid) {                                                 // pMP, !isBad(), !sAlreadyFound.count(pMP) :2345-2347
+    if (!reloc_project_point(P, pose + (int64_t)lo * 15, cam, th, levelRatio, nlevels, scaleFactor, S)) S.level = -1;
+  }
+  surv[slot] = S;
+  candCount[slot] = 0;
+  if (bestIdx) bestIdx[slot] = -1;
+}
+
+// k_sim3_candidates with the octave window [level - 1, level + 1] (a kernel of its own, so that the other's code stays as it is); a
+// fixed grid of 256-thread blocks, SIM3_LANES lanes per slot.  candCount: zeroed by k_reloc_project.  fOff = {0, nf}
+__global__ __launch_bounds__(256) void k_reloc_candidates(const FuseSurvivor* __restrict__ surv, int64_t nslot,
+                                                          const uint8_t* __restrict__ mpDesc, const int* __restrict__ fOff,
+                                                          const pli_keypoint* __restrict__ fKp, const uint8_t* __restrict__ fDesc,
+                                                          const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                          pli_fuse_camera cam, int distLimit, int width,
+                                                          unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
+  constexpr int PER_BLOCK = 256 / SIM3_LANES;
+  const int sub = threadIdx.x & (SIM3_LANES - 1);
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int64_t s = (int64_t)blockIdx.x * PER_BLOCK + threadIdx.x / SIM3_LANES; s < nslot; s += (int64_t)gridDim.x * PER_BLOCK) {
+    const FuseSurvivor S = surv[s];
+    if (S.level < 0) continue;
+    unsigned long long* keys = candKeys + s * width;
+    int* count = candCount + s;
+    sim3_window<1>(S, sub, SIM3_LANES, mpDesc, fOff, fKp, fDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                   [=](unsigned long long key) {             // keys within ORBdist :2403
+                     const int pos = atomicAdd(count, 1);
+                     if (pos < width) keys[pos] = key;
+                   });
+  }
+}
+
+// grid = candidates, one wave; LDS: nf ints (the owner table) and 48 ints (the histogram and ComputeThreeMaxima's bins)
+__global__ __launch_bounds__(64) void k_reloc_assign(const FuseSurvivor* __restrict__ surv, const int* __restrict__ mpOff,
+                                                     const uint8_t* __restrict__ mpDesc, const float* __restrict__ mpAngle,
+                                                     const int* __restrict__ fOff, const pli_keypoint* __restrict__ fKp,
+                                                     const uint8_t* __restrict__ fDesc, int nf, const uint8_t* __restrict__ occupied,
+                                                     const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                     pli_fuse_camera cam, int distLimit, int width, int checkOri,
+                                                     const unsigned long long* __restrict__ candKeys,
+                                                     const int* __restrict__ candCount, int* __restrict__ rowPoint,
+                                                     int* __restrict__ bestIdx, int* __restrict__ nmatchesOut) {
+  extern __shared__ int relocLds[];
+  int* hist = relocLds;                                          // 30 bins (32 ints)
+  int* keep = relocLds + 32;                                     // the bins ComputeThreeMaxima keeps
+  int* owner = relocLds + 48;
+  const int cand = blockIdx.x, lane = threadIdx.x;
+  const int slot0 = mpOff[cand], nmp = mpOff[cand + 1] - slot0;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  const uint8_t* occ = occupied ? occupied + (int64_t)cand * nf : nullptr;
+  if (lane < 48) relocLds[lane] = 0;
+  for (int r = lane; r < nf; r += 64) owner[r] = (occ && occ[r]) ? INT_MAX : -1;           // mvpMapPoints[i2] at entry :2389
+  __syncthreads();
+  const int taken = sim3_ordered_walk<1>(owner, lane, surv, (int64_t)slot0, nmp, mpDesc, fOff, fKp, fDesc, cellStart, sIdx, cam, gwInv,
+                                         ghInv, distLimit, width, candKeys, candCount, bestIdx);
+  __syncthreads();
+  if (checkOri) {                                                // :2408-2418, over the rows taken (the order of the votes is free)
+    for (int r = lane; r < nf; r += 64) {
+      const int o = owner[r];
+      if (o >= 0 && o != INT_MAX) atomicAdd(&hist[bow_rot_bin(mpAngle[slot0 + o], fKp[r].angle)], 1);
+    }
+    __syncthreads();
+  }
+  if (lane == 0) nmatchesOut[cand] = bow_keep_bins(hist, taken, checkOri, keep);           // :2425-2444
+  __syncthreads();
+  const int ind1 = keep[0], ind2 = keep[1], ind3 = keep[2];
+  int* row = rowPoint + (int64_t)cand * nf;
+  for (int r = lane; r < nf; r += 64) {
+    int o = owner[r];
+    if (o < 0 || o == INT_MAX) o = -1;
+    else if (checkOri) {
+      const int b = bow_rot_bin(mpAngle[slot0 + o], fKp[r].angle);
+      if (b != ind1 && b != ind2 && b != ind3) o = -1;           // :2439
+    }
+    row[r] = o;
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -1649,7 +1649,7 @@ pli_status stageImage(pli_ctx* c, int eye, const uint8_t* img, int w, int h, int
 
 // ---- the searches of one item against a batch of keyframes ------------------------
 // pli_search_by_bow, pli_search_by_bow_kf, pli_search_for_triangulation, pli_fuse_search and pli_search_by_projection_sim3 take their
-// keyframes as flat tables:
+// keyframes as flat tables (pli_search_by_projection_reloc: its candidates' point lists, mp_off):
 // keyframe k is rows kf_off[k] .. kf_off[k + 1].  What they share on the host is here; every entry point checks in the same order:
 // null / negative arguments, nkf == 0 (OK), kf_off and the per-keyframe cap (kfBatch), the other side's cap, null tables for
 // total > 0, the values, the empty other side (OK, zeroed counts).
@@ -3133,6 +3133,93 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
   HIPCHK(download(c, rowPoint, dRow, total));
   if (bestIdx) HIPCHK(download(c, bestIdx, dBi, nslot));
   HIPCHK(download(c, nmatches, dNm, npair));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
+pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32_t* mpOff, const pli_fuse_point* mp,
+                                          const uint8_t* mpDesc, const float* mpAngle, const float* pose, const pli_keypoint* fKp,
+                                          const uint8_t* fDesc, int32_t nf, const uint8_t* occupied, const pli_fuse_camera* cam,
+                                          float th, const float* levelRatio, int32_t orbDist, int32_t checkOri, int32_t* rowPoint,
+                                          int32_t* bestIdx, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || ncand < 0 || nf < 0 || !cam || !levelRatio || (ncand > 0 && (!mpOff || !pose || !nmatches)) || (nf > 0 && (!fKp || !fDesc)) ||
+      (ncand > 0 && nf > 0 && !rowPoint)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  const int nlevels = c->hp.nlevels;
+  for (int n = 0; n < nlevels - 1; ++n)
+    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
+  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  // bestDist <= ORBdist (ORBmatcher.cc:2403): with no candidate the reference holds bestDist = 256, bestIdx2 = -1 and would write
+  // mvpMapPoints[-1] at 256
+  if (orbDist < 0 || orbDist > 255) { g_err = "orb_dist must lie in [0, 255]"; return PLI_ERR_INVALID; }
+  if (ncand == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(ncand, mpOff, "a candidate lists more points than the projection search cap", B);
+  if (st != PLI_OK) return st;
+  if (nf > PLI_BOW_MAX_FEATURES) { g_err = "the frame has more features than the projection search cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = B.total;
+  if (total > 0 && (!mp || !mpDesc || (checkOri && !mpAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (!octavesOk(c, fKp, nf, "f_kp")) return PLI_ERR_INVALID;
+  if (checkOri && (!anglesOk(mpAngle, total, "mp_angle") || !anglesOk(fKp, nf, "f_kp angle"))) return PLI_ERR_INVALID;
+  std::fill(nmatches, nmatches + ncand, 0);
+  if (total == 0 || nf == 0) {
+    if (nf > 0) std::fill(rowPoint, rowPoint + (size_t)ncand * nf, -1);
+    if (bestIdx) std::fill(bestIdx, bestIdx + total, -1);
+    return PLI_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  int width = SIM3_LIST_WIDTH;                              // the list of one point, as pli_search_by_projection_sim3
+  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) width = std::min(64, std::max(1, atoi(e)));
+  const size_t nrow = (size_t)ncand * nf;
+  ScratchPlan plan;
+  auto dOff = plan.add<int>((size_t)ncand + 1);
+  auto dMp = plan.add<pli_fuse_point>(total);
+  auto dMd = plan.add<uint8_t>((size_t)total * 32);
+  auto dMa = plan.add<float>(checkOri ? total : 0);
+  auto dPose = plan.add<float>((size_t)ncand * 15);
+  auto dFoff = plan.add<int>(2);                            // the frame as the one table of k_fuse_grid: {0, nf}
+  auto dKk = plan.add<pli_keypoint>(nf);
+  auto dKd = plan.add<uint8_t>((size_t)nf * 32);
+  auto dOcc = plan.add<uint8_t>(occupied ? nrow : 0);
+  auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
+  auto dCell = plan.add<int>(GRID_COLS * GRID_ROWS + 1);
+  auto dSi = plan.add<uint16_t>(nf);
+  auto dSurv = plan.add<FuseSurvivor>(total);
+  auto dKeys = plan.add<unsigned long long>((size_t)total * width);
+  auto dCnt = plan.add<int>(total);
+  auto dRow = plan.add<int>(nrow);
+  auto dBi = plan.add<int>(bestIdx ? total : 0);
+  auto dNm = plan.add<int>(ncand);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  float hlv[2 * MAX_LEVELS] = {};
+  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
+  levelTables(c, hlv + MAX_LEVELS, nullptr, nullptr);
+  const int fOff[2] = {0, nf};
+  HIPCHK(upload(c, dOff, mpOff, (size_t)ncand + 1));
+  HIPCHK(upload(c, dMp, mp, total));
+  HIPCHK(upload(c, dMd, mpDesc, (size_t)total * 32));
+  if (checkOri) HIPCHK(upload(c, dMa, mpAngle, total));
+  HIPCHK(upload(c, dPose, pose, (size_t)ncand * 15));
+  HIPCHK(upload(c, dFoff, (const int*)fOff, 2));
+  HIPCHK(upload(c, dKk, fKp, nf));
+  HIPCHK(upload(c, dKd, fDesc, (size_t)nf * 32));
+  if (occupied) HIPCHK(upload(c, dOcc, occupied, nrow));
+  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
+  const float* dMaPtr = checkOri ? (const float*)dMa : nullptr;
+  const uint8_t* dOccPtr = occupied ? (const uint8_t*)dOcc : nullptr;
+  int* dBiPtr = bestIdx ? (int*)dBi : nullptr;
+  const float* lv = dLv;
+  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dFoff, dKk, *cam, dCell, dSi);
+  LAUNCH(c, "k_reloc_project", k_reloc_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dMp, dOff, ncand, dPose, *cam, th, lv,
+         nlevels, lv + MAX_LEVELS, dSurv, dCnt, dBiPtr);
+  LAUNCH(c, "k_reloc_candidates", k_reloc_candidates, dim3(1024), dim3(256), 0, dSurv, (int64_t)total, dMd, dFoff, dKk, dKd, dCell, dSi,
+         *cam, orbDist, width, dKeys, dCnt);
+  LAUNCH(c, "k_reloc_assign", k_reloc_assign, dim3(ncand), dim3(64), (size_t)(48 + nf) * sizeof(int), dSurv, dOff, dMd, dMaPtr, dFoff, dKk,
+         dKd, nf, dOccPtr, dCell, dSi, *cam, orbDist, width, checkOri ? 1 : 0, dKeys, dCnt, dRow, dBiPtr, dNm);
+  HIPCHK(download(c, rowPoint, dRow, nrow));
+  if (bestIdx) HIPCHK(download(c, bestIdx, dBi, total));
+  HIPCHK(download(c, nmatches, dNm, ncand));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }

@@ -374,6 +374,58 @@ class Frontend:
                                                    ptr(nmatches)))
         return [rows[off[k]:off[k + 1]] for k in range(npair)], best_idx, nmatches
 
+    def search_by_projection_reloc(self, cands, frame_kp, frame_desc, cam, th=10.0, orb_dist=100, check_orientation=True,
+                                   level_ratio=None):
+        """Relocalisation's ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:2325-2447;
+        Tracking.cc:4290, :4304) of ONE frame table (frame_kp: mvKeysUn as KEYPOINT_DT rows, frame_desc: mDescriptors) against
+        every candidate of `cands`, in one call; the points of a candidate are decided in list order and a row taken by one is
+        closed to the later ones.  cands: list of (points, descs, angles, pose, occupied_or_None) - pKF->GetMapPointMatches() as
+        capi.FUSE_POINT_DT rows (valid = set, not bad and not in sAlreadyFound; normal is not read), GetDescriptor() rows,
+        pKF->mvKeysUn[i].angle (None without check_orientation), pose = 15 floats (Rcw row major, tcw, Ow = -Rcw.t()*tcw of the
+        frame's Tcw for this candidate), occupied = one flag per frame row (mvpMapPoints[i2] != NULL at entry; None: none).
+        cam: capi.FuseCamera or its 9 values.
+        Returns (row_point[ncand, nf]: the index within the candidate's own list of the point that holds the row after the
+        rotation filter or -1; best_idx: one int32 array per candidate, the row a point took before the filter or -1;
+        nmatches[ncand])."""
+        kk = np.ascontiguousarray(frame_kp, KEYPOINT_DT).reshape(-1)
+        kd = np.ascontiguousarray(frame_desc, np.uint8).reshape(-1, 32)
+        if len(kk) != len(kd):
+            raise ValueError("every frame feature needs one keypoint and one descriptor")
+        ncand, nf = len(cands), len(kk)
+        check_orientation = bool(check_orientation)
+        if check_orientation and any(cd[2] is None for cd in cands):
+            raise ValueError("check_orientation needs every candidate's angles")
+        lists = [(cd[0], cd[1], cd[2] if check_orientation else np.zeros(len(np.asarray(cd[0]).reshape(-1)), np.float32)) for cd in cands]
+        off, (pts, d, ang) = pack_keyframes(lists, ((0, capi.FUSE_POINT_DT, ()), (1, np.uint8, (32,)), (2, np.float32, ())),
+                                            "every map point needs one descriptor and one angle")
+        pose = np.ascontiguousarray([np.asarray(cd[3], np.float32).reshape(15) for cd in cands], np.float32).reshape(ncand, 15)
+        occ = None
+        if any(len(cd) > 4 and cd[4] is not None for cd in cands):
+            occ = np.zeros((ncand, nf), np.uint8)
+            for k, cd in enumerate(cands):
+                if len(cd) > 4 and cd[4] is not None:
+                    o = np.asarray(cd[4]).reshape(-1)
+                    if len(o) != nf:
+                        raise ValueError("occupied: one flag per frame row")
+                    occ[k] = o != 0
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        if level_ratio is None:
+            if getattr(self, "_fuse_level_ratio", None) is None:
+                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
+            level_ratio = self._fuse_level_ratio
+        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
+        if len(level_ratio) != self.cfg.orb_nlevels - 1:
+            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        rows = np.full((ncand, nf), -1, np.int32)
+        best_idx = np.full(int(off[-1]), -1, np.int32)
+        nmatches = np.zeros(ncand, np.int32)
+        check(self.L.pli_search_by_projection_reloc(self.h, ncand, ptr(off), ptr(pts), ptr(d), ptr(ang) if check_orientation else None,
+                                                    ptr(pose), ptr(kk), ptr(kd), nf, ptr(occ), C.byref(cam), float(th),
+                                                    ptr(level_ratio), int(orb_dist), int(check_orientation), ptr(rows),
+                                                    ptr(best_idx), ptr(nmatches)))
+        return rows, [best_idx[off[k]:off[k + 1]] for k in range(ncand)], nmatches
+
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""
