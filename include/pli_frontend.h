@@ -708,6 +708,36 @@ pli_status pli_search_by_projection_reloc(pli_ctx* ctx, int32_t ncand, const int
                                           const pli_fuse_camera* cam, float th, const float* level_ratio, int32_t orb_dist,
                                           int32_t check_orientation, int32_t* row_point, int32_t* best_idx, int32_t* nmatches);
 
+/* Monocular initialisation's ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+ * ORBmatcher.cc:706-821 (Tracking.cc:2109-2110: matcher (0.9, true), window 100) of one table against one table.  kp1 / desc1 =
+ * F1.mvKeysUn / mDescriptors (n1 rows: octave and, with check_orientation, angle are read), prev_matched = vbPrevMatched as n1 x
+ * (x, y), READ ONLY: the update :816-818, vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt for the matches that are left, is
+ * the caller's, from matches12 and kp2 (each call's windows come from the previous call's result, so there is no batch form).
+ * kp2 / desc2 = F2.mvKeysUn / mDescriptors (n2 rows: pt, octave, angle); min_x .. max_y = mnMinX .. mnMaxY of the 64 x 48 grid.
+ * Only F1 keypoints with octave == 0 search (:723).  Candidates: Frame::GetFeaturesInArea(x, y, window_size, 0, 0)
+ * (Frame.cc:774-843): the cells column by column and row by row, a cell's keypoints in index order, octave == 0 only, the window
+ * strict (fabs(dx) < r && fabs(dy) < r); a keypoint that PosInGrid (:845-855) puts outside the grid is in no cell.
+ * The walk over i1 is ordered, and a row of F2 is NOT closed once taken.  Its state is vMatchedDistance[i2] (INT_MAX at entry) and
+ * vnMatches21[i2]: candidate i2 is left out for i1 when vMatchedDistance[i2] <= dist (:745) and is then neither best nor
+ * second-best; a later i1 with a strictly smaller distance takes the row again and evicts the earlier owner (:764-768), an equal
+ * distance does not.  Best = the first strict minimum in visiting order = the minimum of the key (distance, cell column, cell row,
+ * index); bestDist2 = the second-smallest distance among the candidates not left out (equal to the best on a tie, INT_MAX with
+ * fewer than two).  Acceptance :760-762: bestDist <= TH_LOW (50) and bestDist < (float)bestDist2 * nnratio in float (45 against a
+ * second-best of 50 at 0.9f is rejected: 50 * 0.9f == 45.0f).
+ * check_orientation (mbCheckOrientation, :774-813): the bin of F1's angle minus F2's as in pli_search_by_bow (every angle in
+ * [0, 360)); rotHist records EVERY acceptance, also those evicted later, so ComputeThreeMaxima sees bin sizes that count evicted
+ * i1; the filter clears only entries that still hold a match (:805).
+ * matches12[n1] = vnMatches12 after the filter; raw12[n1] (may be NULL) = vnMatches12 after the walk and before the filter, the
+ * evictions applied; *nmatches = the return value.
+ * Errors: PLI_ERR_INVALID for null pointers, window_size < 0, nnratio not finite or <= 0, empty image bounds, an octave outside
+ * [0, orb_nlevels), with check_orientation an angle outside [0, 360), a NaN in prev_matched; PLI_ERR_CAPACITY for n1 or n2 above
+ * PLI_BOW_MAX_FEATURES (the row state and vnMatches12 live in LDS); nothing is truncated.  n1 == 0 and n2 == 0 are valid.  The
+ * number of kernel launches does not depend on n1 or n2. */
+pli_status pli_search_for_initialization(pli_ctx* ctx, const pli_keypoint* kp1, const uint8_t* desc1, int32_t n1,
+                                         const float* prev_matched, const pli_keypoint* kp2, const uint8_t* desc2, int32_t n2,
+                                         float min_x, float max_x, float min_y, float max_y, int32_t window_size, float nnratio,
+                                         int32_t check_orientation, int32_t* matches12, int32_t* raw12, int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

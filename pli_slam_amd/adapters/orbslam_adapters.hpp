@@ -1144,6 +1144,88 @@ class PliORBmatcher {
     relocProjection(CurrentFrame, vpKFs, vTcw, found, entry, th, ORBdist, vvpMapPoints, vnmatches);
   }
 
+  // ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>& vbPrevMatched, vector<int>& vnMatches12, int
+  // windowSize), ORBmatcher.cc:706-821 (Tracking::MonocularInitialization, Tracking.cc:2109-2110): the windows, the ordered walk
+  // with its evictions, the rotation histogram and ComputeThreeMaxima run on the device (pli_search_for_initialization);
+  // vnMatches12 is the reference's, vbPrevMatched gets the update :816-818, the return value is the reference's.  Frames of one
+  // camera only (Nleft == -1).  FrameT needs Nleft, mvKeysUn, mDescriptors and mnMinX .. mnMaxY.
+  int SearchForInitialization(FrameT& F1, FrameT& F2, std::vector<cv::Point2f>& vbPrevMatched, std::vector<int>& vnMatches12,
+                              int windowSize = 10) {
+    if (F1.Nleft != -1 || F2.Nleft != -1) throw std::logic_error("SearchForInitialization: frames of two cameras are not covered");
+    const size_t n1 = F1.mvKeysUn.size(), n2 = F2.mvKeysUn.size();
+    if (vbPrevMatched.size() != n1) throw std::logic_error("SearchForInitialization: vbPrevMatched needs one point per keypoint of F1");
+    std::vector<pli_keypoint> kp1(n1), kp2(n2);
+    std::vector<float> prev(2 * n1);
+    for (size_t i = 0; i < n1; ++i) {
+      kp1[i] = pli_detail::keypoint(F1.mvKeysUn[i]);
+      prev[2 * i] = vbPrevMatched[i].x;
+      prev[2 * i + 1] = vbPrevMatched[i].y;
+    }
+    for (size_t i = 0; i < n2; ++i) kp2[i] = pli_detail::keypoint(F2.mvKeysUn[i]);
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("SearchForInitialization");
+    const int nmatches = fe->searchForInitialization(kp1, F1.mDescriptors.data, prev.data(), kp2, F2.mDescriptors.data, F2.mnMinX,
+                                                     F2.mnMaxX, F2.mnMinY, F2.mnMaxY, windowSize, mfNNratio,
+                                                     mbCheckOrientation, vnMatches12);
+    for (size_t i1 = 0; i1 < n1; ++i1)                                       // :816-818
+      if (vnMatches12[i1] >= 0) vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt;
+    return nmatches;
+  }
+
+  // ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float th, const bool bFarPoints, const
+  // float thFarPoints), ORBmatcher.cc:44-143 for a frame of one camera or rectified stereo (F.Nleft == -1;
+  // Tracking::SearchLocalPoints, Tracking.cc:3854): the gates :53-62, RadiusByViewingCos (:216-222) and the window radius are the
+  // reference's own expressions, run here; the windows, best and second-best, TH_HIGH and the ratio test run on the device
+  // (pli_search_local_map).  F.mvpMapPoints[bestIdx] = pMP for every row taken; the return value is the reference's.
+  // One case is refused: a point in view that is not bad and has Observations() == 0.  The reference would not close the row such
+  // a point takes (:89-91 reads Observations() of the row's point), the device closes every row taken.
+  // FrameT needs N, Nleft, mvKeysUn, mDescriptors, mvuRight, mvpMapPoints, mvScaleFactors and mnMinX .. mnMaxY;
+  // MapPointT mbTrackInView, mTrackDepth, isBad(), mnTrackScaleLevel, mTrackViewCos, mTrackProjX / Y / XR, GetDescriptor() and
+  // Observations().
+  int SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpMapPoints, const float th = 3, const bool bFarPoints = false,
+                         const float thFarPoints = 50.0f) {
+    if (F.Nleft != -1) throw std::logic_error("SearchByProjection(F, vpMapPoints): frames of two cameras are not covered");
+    const bool bFactor = th != 1.0;
+    const size_t nq = vpMapPoints.size();
+    std::vector<pli_proj_query> q(nq);
+    std::vector<uint8_t> qdesc(nq * 32, 0);
+    for (size_t iMP = 0; iMP < nq; ++iMP) {
+      pli_proj_query& Q = q[iMP];
+      std::memset(&Q, 0, sizeof(Q));
+      MapPointT* pMP = vpMapPoints[iMP];
+      if (!pMP->mbTrackInView) continue;                                     // :53, :62 (no right camera)
+      if (bFarPoints && pMP->mTrackDepth > thFarPoints) continue;            // :56
+      if (pMP->isBad()) continue;                                            // :59
+      if (pMP->Observations() <= 0)
+        throw std::logic_error("SearchByProjection(F, vpMapPoints): a point in view without observations is not covered");
+      const int nPredictedLevel = pMP->mnTrackScaleLevel;
+      float r = pMP->mTrackViewCos > 0.998 ? 2.5 : 4.0;                      // RadiusByViewingCos :216-222
+      if (bFactor) r *= th;
+      Q.u = pMP->mTrackProjX;
+      Q.v = pMP->mTrackProjY;
+      Q.radius = r * F.mvScaleFactors[nPredictedLevel];                      // :73, :96
+      Q.ur = pMP->mTrackProjXR;
+      Q.min_level = nPredictedLevel - 1;
+      Q.max_level = nPredictedLevel;
+      Q.valid = 1;
+      const cv::Mat dMP = pMP->GetDescriptor();
+      std::memcpy(&qdesc[iMP * 32], dMP.ptr<uint8_t>(), 32);
+    }
+    const int M = F.N;
+    std::vector<pli_keypoint> kp((size_t)M);
+    std::vector<uint8_t> occupied((size_t)M, 0);
+    for (int j = 0; j < M; ++j) {
+      kp[j] = pli_detail::keypoint(F.mvKeysUn[j]);
+      if (F.mvpMapPoints[j] && F.mvpMapPoints[j]->Observations() > 0) occupied[j] = 1;      // :89-91
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("SearchByProjection(F, vpMapPoints)");
+    std::vector<int> best;
+    const int nmatches = fe->searchLocalMap(q, qdesc.data(), kp, F.mDescriptors.data, F.mvuRight.data(), occupied.data(), F.mnMinX,
+                                            F.mnMaxX, F.mnMinY, F.mnMaxY, mfNNratio, best);
+    for (size_t iMP = 0; iMP < nq; ++iMP)
+      if (best[iMP] >= 0) F.mvpMapPoints[best[iMP]] = vpMapPoints[iMP];      // :130
+    return nmatches;
+  }
+
   // the level_ratio table the Fuse adapters hand to pli_fuse_search (tests read it)
   template <class KeyFrameT>
   const std::vector<float>& fuseLevelRatio(KeyFrameT* pKF) {

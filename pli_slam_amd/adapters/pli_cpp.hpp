@@ -200,6 +200,21 @@ class Frontend {
                                          levelRatio.data(), orbDist, checkOrientation ? 1 : 0, rowPoint.data(), nullptr,
                                          nmatches.data()));
   }
+  // Monocular initialisation's ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+  // ORBmatcher.cc:706-821 (include/pli_frontend.h pli_search_for_initialization): matches12 = vnMatches12 after the rotation
+  // filter; prevMatched (n1 x 2: x, y) is read, the update :816-818 is the caller's.  Returns the reference's return value.
+  int searchForInitialization(const std::vector<pli_keypoint>& kp1, const uint8_t* desc1, const float* prevMatched,
+                              const std::vector<pli_keypoint>& kp2, const uint8_t* desc2, float minX, float maxX, float minY,
+                              float maxY, int windowSize, float nnratio, bool checkOrientation, std::vector<int>& matches12,
+                              std::vector<int>* raw12 = nullptr) {
+    matches12.assign(kp1.size(), -1);
+    if (raw12) raw12->assign(kp1.size(), -1);
+    int32_t n = 0;
+    check(pli_search_for_initialization(ctx_, kp1.data(), desc1, (int)kp1.size(), prevMatched, kp2.data(), desc2, (int)kp2.size(), minX,
+                                        maxX, minY, maxY, windowSize, nnratio, checkOrientation ? 1 : 0, matches12.data(),
+                                        raw12 ? raw12->data() : nullptr, &n));
+    return n;
+  }
   // level_ratio of pli_fuse_search from the HOST's own MapPoint::PredictScale expression: levelOf(ratio) must be the tree's
   // expression compiled by the tree's compiler (ceil(log(ratio) / mfLogScaleFactor) with its clamps), so that whichever overload
   // of log its toolchain selects is the one the thresholds describe.  For n = 0 .. nlevels-2 the largest float for which

@@ -184,6 +184,9 @@ _PROTOS = {
     "pli_search_by_projection_reloc": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(FuseCamera), C.c_float,
                                                    C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pli_search_for_initialization": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_float,
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pli_prof_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "pli_prof_reset": (C.c_int32, [C.c_void_p]),
     "pli_prof_report": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int64]),

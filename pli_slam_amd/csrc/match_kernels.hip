@@ -17,6 +17,7 @@
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 //   k_fuse_grid, k_sim3_project, k_sim3_candidates, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
 //   k_fuse_grid, k_reloc_project, k_reloc_candidates, k_reloc_assign  ORBmatcher::SearchByProjection(Frame, KF, sAlreadyFound, ...) (ORBmatcher.cc:2325-2447)
+//   k_fuse_grid, k_init_candidates, k_init_assign  ORBmatcher::SearchForInitialization (ORBmatcher.cc:706-821)
 #include "kernels.hpp"
 #include "device_prims.hpp"
 #include <climits>
@@ -2017,6 +2018,184 @@ __global__ __launch_bounds__(64) void k_reloc_assign(const FuseSurvivor* __restr
     }
     row[r] = o;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Monocular initialisation's ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+// (ORBmatcher.cc:706-821; Tracking.cc:2109-2110) of one F1 table against one F2 table.
+//
+// The walk over i1 is ordered, but a row of F2 is not closed once taken: its state is (vMatchedDistance, vnMatches21), a candidate is
+// left out for i1 when vMatchedDistance[i2] <= dist (:745), and a later i1 with a strictly smaller distance takes the row again and
+// evicts the earlier owner (:764-768).  The windows and the Hamming distances do not depend on that state, so:
+//
+//   k_fuse_grid        (unchanged) the cell sort of F2's table (one "keyframe", {0, n2}).
+//   k_init_candidates  one wave per i1 with octave 0 (:723), a fixed grid striding over i1: the window of
+//                      Frame::GetFeaturesInArea(x, y, r, 0, 0) (Frame.cc:774-843) around vbPrevMatched[i1] in the cell runs, 64 rows
+//                      per step; the keys (distance, cell column, cell row, index) within the limit go to the list of i1 (`width`
+//                      keys, in visiting order, placed by ballot and popcount: no atomics, nothing to clear) and are counted; the
+//                      count keeps counting past the width, count > width marks the list as overflowed.
+//   k_init_assign      ONE wave, the per-row state (distance << 16 | owner, all ones: INT_MAX / -1) and vnMatches12 (shorts) in LDS:
+//                      walks the i1 that have candidates in order (the next one's keys in flight), drops the left-out keys, takes
+//                      the two smallest keys of the wave = bestDist / bestIdx2 (the first strict minimum in visiting order) and
+//                      bestDist2, applies :760-762 in float, evicts, stores.  An overflowed list walks its window again.  The
+//                      histogram counts every acceptance, also those evicted later (:774-784: nothing leaves rotHist), and
+//                      ComputeThreeMaxima sees those sizes; the filter clears only the entries that still hold a match (:805).
+// The limit of the lists is the host's (pli_search_for_initialization, where the argument is written down).
+// Three launches per call, whatever n1 and n2.
+// ---------------------------------------------------------------------------
+constexpr unsigned INIT_NO_OWNER = 0xFFFFu;
+
+// The window of (x, y, r) in F2's cell runs by a whole wave in uniform steps: every lane calls visit(key) the same number of
+// times, key = ~0ull where the lane has no row, the row is outside the window (strict, Frame.cc:836), not at octave 0 or its
+// distance is above distLimit.
+template <class Visit>
+__device__ __forceinline__ void init_window(float x, float y, float r, const uint64_t dq[4], int lane,
+                                            const pli_keypoint* __restrict__ kp2, const uint8_t* __restrict__ desc2,
+                                            const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                            const pli_fuse_camera& cam, float gwInv, float ghInv, int distLimit, Visit visit) {
+  const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, cam.min_x), r), gwInv)));
+  const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, cam.min_x), r), gwInv)));
+  const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, cam.min_y), r), ghInv)));
+  const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, cam.min_y), r), ghInv)));
+  if (!(c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1)) return;
+  for (int cx = c0; cx <= c1; ++cx) {
+    const int lo = cellStart[cx * GRID_ROWS + r0], hi = cellStart[cx * GRID_ROWS + r1 + 1];
+    for (int t0 = lo; t0 < hi; t0 += 64) {
+      unsigned long long key = ~0ull;
+      if (t0 + lane < hi) {
+        const int i2 = sIdx[t0 + lane];
+        const pli_keypoint k = kp2[i2];
+        if (k.octave == 0 && fabsf(__fsub_rn(k.x, x)) < r && fabsf(__fsub_rn(k.y, y)) < r) {           // Frame.cc:826-837
+          uint64_t d2[4];
+          load_desc(desc2 + (int64_t)i2 * 32, d2);
+          const int dist = hamming256(dq, d2);
+          if (dist <= distLimit) {
+            int px, py;
+            fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+            key = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) | ((unsigned long long)py << 28) | (unsigned long long)i2;
+          }
+        }
+      }
+      visit(key);
+    }
+  }
+}
+
+// a fixed grid of 256-thread blocks, one wave per i1.  candKeys: n1 x width, candCount: n1 (every entry is written)
+__global__ __launch_bounds__(256) void k_init_candidates(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1, int n1,
+                                                         const float* __restrict__ prevMatched, const pli_keypoint* __restrict__ kp2,
+                                                         const uint8_t* __restrict__ desc2, const int* __restrict__ cellStart,
+                                                         const uint16_t* __restrict__ sIdx, pli_fuse_camera cam, float radius,
+                                                         int distLimit, int width, unsigned long long* __restrict__ candKeys,
+                                                         int* __restrict__ candCount) {
+  const int lane = threadIdx.x & 63, wavesPerBlock = 256 / 64;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  for (int i1 = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6); i1 < n1; i1 += gridDim.x * wavesPerBlock) {
+    int count = 0;
+    if (kp1[i1].octave == 0) {                                   // :723 (the octaves are checked: none is negative)
+      uint64_t dq[4];
+      load_desc(desc1 + (int64_t)i1 * 32, dq);
+      unsigned long long* keys = candKeys + (int64_t)i1 * width;
+      init_window(prevMatched[2 * i1], prevMatched[2 * i1 + 1], radius, dq, lane, kp2, desc2, cellStart, sIdx, cam, gwInv, ghInv,
+                  distLimit, [&](unsigned long long key) {
+                    const unsigned long long pass = __builtin_amdgcn_ballot_w64(key != ~0ull);
+                    const int pos = count + __popcll(pass & ((1ull << lane) - 1ull));
+                    if (key != ~0ull && pos < width) keys[pos] = key;
+                    count += __popcll(pass);
+                  });
+    }
+    if (lane == 0) candCount[i1] = count;
+  }
+}
+
+// grid = 1, one wave; LDS: 48 ints (the histogram and ComputeThreeMaxima's bins), n2 words (the row state), n1 shorts (vnMatches12)
+__global__ __launch_bounds__(64) void k_init_assign(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1, int n1,
+                                                    const float* __restrict__ prevMatched, const pli_keypoint* __restrict__ kp2,
+                                                    const uint8_t* __restrict__ desc2, int n2, const int* __restrict__ cellStart,
+                                                    const uint16_t* __restrict__ sIdx, pli_fuse_camera cam, float radius,
+                                                    int distLimit, int width, float nnratio, int checkOri,
+                                                    const unsigned long long* __restrict__ candKeys,
+                                                    const int* __restrict__ candCount, int* __restrict__ matches12,
+                                                    int* __restrict__ raw12, int* __restrict__ nmatchesOut) {
+  extern __shared__ int initLds[];
+  int* hist = initLds;                                           // 30 bins (32 ints)
+  int* keep = initLds + 32;                                      // the bins ComputeThreeMaxima keeps
+  unsigned* state = reinterpret_cast<unsigned*>(initLds + 48);   // vMatchedDistance[i2] << 16 | vnMatches21[i2]
+  short* m12 = reinterpret_cast<short*>(state + n2);             // vnMatches12 (n2 <= 8192)
+  const int lane = threadIdx.x;
+  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
+  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
+  if (lane < 48) initLds[lane] = 0;
+  for (int r = lane; r < n2; r += 64) state[r] = ~0u;            // INT_MAX, -1 :716-717
+  for (int i = lane; i < n1; i += 64) m12[i] = -1;               // :709
+  __syncthreads();
+  // the walk over the i1 that have candidates, in order: 64 counts per load, one bit per i1 (as sim3_ordered_walk)
+  int chunk = -64, cntLane = 0;
+  unsigned long long todo = 0;
+  int iNext = -1, cntNext = 0;
+  unsigned long long keyNext = ~0ull;
+  auto advance = [&]() {                                         // -> iNext (n1: none is left), cntNext, keyNext
+    while (todo == 0) {
+      chunk += 64;
+      if (chunk >= n1) { iNext = n1; return; }
+      cntLane = chunk + lane < n1 ? candCount[chunk + lane] : 0;
+      todo = __builtin_amdgcn_ballot_w64(cntLane != 0);
+    }
+    const int bit = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    iNext = chunk + bit;
+    cntNext = __shfl(cntLane, bit, 64);
+    keyNext = (cntNext <= width && lane < cntNext) ? candKeys[(int64_t)iNext * width + lane] : ~0ull;
+  };
+  advance();
+  while (iNext < n1) {
+    const int i1 = iNext, cnt = cntNext;
+    const unsigned long long key = keyNext;
+    advance();                                                   // the next i1's keys travel while this one is decided
+    WaveTop2 top;
+    if (cnt <= width) {
+      if (key != ~0ull && (state[(int)(key & 0xFFFFFFFull)] >> 16) > (unsigned)(key >> 40)) top.push(key);      // :745
+    } else {                                                     // more candidates than the list holds: the window again
+      uint64_t dq[4];
+      load_desc(desc1 + (int64_t)i1 * 32, dq);
+      init_window(prevMatched[2 * i1], prevMatched[2 * i1 + 1], radius, dq, lane, kp2, desc2, cellStart, sIdx, cam, gwInv, ghInv,
+                  distLimit, [&](unsigned long long kk) {
+                    if (kk != ~0ull && (state[(int)(kk & 0xFFFFFFFull)] >> 16) > (unsigned)(kk >> 40)) top.push(kk);
+                  });
+    }
+    const unsigned long long k1 = top.min1();
+    if (k1 != ~0ull) {
+      const unsigned long long k2 = top.min2(k1);
+      const int bestDist = (int)(k1 >> 40), bestDist2 = k2 != ~0ull ? (int)(k2 >> 40) : INT_MAX;
+      if (bestDist <= FUSE_TH_LOW && (float)bestDist < __fmul_rn((float)bestDist2, nnratio)) {         // :760-762
+        const int b = (int)(k1 & 0xFFFFFFFull);
+        const unsigned old = state[b] & 0xFFFFu;                 // (every lane reads and stores the same values)
+        if (old != INIT_NO_OWNER) m12[old] = -1;                 // :764-768
+        m12[i1] = (short)b;
+        state[b] = ((unsigned)bestDist << 16) | (unsigned)i1;    // :770-771
+        if (checkOri && lane == 0) ++hist[bow_rot_bin(kp1[i1].angle, kp2[b].angle)];       // :774-784, never taken back
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // single wave: LDS is executed in order
+  }
+  __syncthreads();
+  if (lane == 0) bow_keep_bins(hist, 0, checkOri, keep);         // :796 (the count comes from the entries that are left)
+  __syncthreads();
+  const int ind1 = keep[0], ind2 = keep[1], ind3 = keep[2];
+  int left = 0;
+  for (int i1 = lane; i1 < n1; i1 += 64) {
+    int m = m12[i1];
+    if (raw12) raw12[i1] = m;
+    if (m >= 0 && checkOri) {
+      const int bin = bow_rot_bin(kp1[i1].angle, kp2[m].angle);
+      if (bin != ind1 && bin != ind2 && bin != ind3) m = -1;     // :798-811, only where a match is still held (:805)
+    }
+    matches12[i1] = m;
+    left += m >= 0 ? 1 : 0;
+  }
+  left = wave_sum_i32(left);                                     // nmatches: ++ :772, -- :767 and :808 = the entries left
+  if (lane == 0) nmatchesOut[0] = left;
 }
 
 // ---------------------------------------------------------------------------

@@ -3224,6 +3224,81 @@ pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32
   return PLI_OK;
 }
 
+constexpr int INIT_LIST_WIDTH = 16;
+
+pli_status pli_search_for_initialization(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, int32_t n1,
+                                         const float* prevMatched, const pli_keypoint* kp2, const uint8_t* desc2, int32_t n2,
+                                         float minX, float maxX, float minY, float maxY, int32_t windowSize, float nnratio,
+                                         int32_t checkOri, int32_t* matches12, int32_t* raw12, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || n2 < 0 || !nmatches || (n1 > 0 && (!kp1 || !desc1 || !prevMatched || !matches12)) || (n2 > 0 && (!kp2 || !desc2))) {
+    g_err = "bad argument"; return PLI_ERR_INVALID;
+  }
+  if (windowSize < 0) { g_err = "window_size must not be negative"; return PLI_ERR_INVALID; }
+  if (!std::isfinite(nnratio) || !(nnratio > 0.f)) { g_err = "nnratio must be finite and positive"; return PLI_ERR_INVALID; }
+  if (!(maxX > minX) || !(maxY > minY)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "F1 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
+  if (n2 > PLI_BOW_MAX_FEATURES) { g_err = "F2 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
+  if (!octavesOk(c, kp1, n1, "kp1") || !octavesOk(c, kp2, n2, "kp2")) return PLI_ERR_INVALID;
+  if (checkOri && (!anglesOk(kp1, n1, "kp1 angle") || !anglesOk(kp2, n2, "kp2 angle"))) return PLI_ERR_INVALID;
+  for (int64_t i = 0; i < 2 * (int64_t)n1; ++i)
+    if (std::isnan(prevMatched[i])) { g_err = "prev_matched holds a NaN"; return PLI_ERR_INVALID; }
+  *nmatches = 0;
+  if (n1 == 0 || n2 == 0) {
+    std::fill(matches12, matches12 + n1, -1);
+    if (raw12) std::fill(raw12, raw12 + n1, -1);
+    return PLI_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  // The limit of the per-i1 candidate lists.  A candidate at distance d can bear on a decision in two ways only.  As a best: :760
+  // needs d <= TH_LOW.  As a second-best that rejects a best b <= TH_LOW: :762 rejects when b >= (float)d * nnratio, and with
+  // b <= 50 that needs (float)d * nnratio <= 50.0f, which is monotone in d for nnratio > 0.  A candidate above both bounds is
+  // never a best that is accepted (if it were the minimum, every other candidate would be above TH_LOW too) and as a second-best
+  // it behaves like INT_MAX: (float)d * nnratio > 50.0f >= b accepts, as does a missing second-best.  Whether it is left out by
+  // vMatchedDistance (:745) changes nothing either, and it never enters vMatchedDistance, which only holds accepted distances.
+  // So the lists keep d <= max(TH_LOW, the largest d with (float)d * nnratio <= 50.0f): 55 for 0.9.
+  int distLimit = 50;
+  while (distLimit < 256 && (float)(distLimit + 1) * nnratio <= 50.0f) ++distLimit;
+  const int width = INIT_LIST_WIDTH;
+  ScratchPlan plan;
+  auto dOff = plan.add<int>(2);                             // F2 as the one table of k_fuse_grid: {0, n2}
+  auto dK1 = plan.add<pli_keypoint>(n1);
+  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
+  auto dPrev = plan.add<float>((size_t)n1 * 2);
+  auto dK2 = plan.add<pli_keypoint>(n2);
+  auto dD2 = plan.add<uint8_t>((size_t)n2 * 32);
+  auto dCell = plan.add<int>(GRID_COLS * GRID_ROWS + 1);
+  auto dSi = plan.add<uint16_t>(n2);
+  auto dKeys = plan.add<unsigned long long>((size_t)n1 * width);
+  auto dCnt = plan.add<int>(n1);
+  auto dM12 = plan.add<int>(n1);
+  auto dRaw = plan.add<int>(raw12 ? n1 : 0);
+  auto dNm = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  pli_fuse_camera cam = {};                                 // only the bounds are read (the 64 x 48 grid)
+  cam.min_x = minX; cam.max_x = maxX; cam.min_y = minY; cam.max_y = maxY;
+  const int off2[2] = {0, n2};
+  HIPCHK(upload(c, dOff, (const int*)off2, 2));
+  HIPCHK(upload(c, dK1, kp1, n1));
+  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
+  HIPCHK(upload(c, dPrev, prevMatched, (size_t)n1 * 2));
+  HIPCHK(upload(c, dK2, kp2, n2));
+  HIPCHK(upload(c, dD2, desc2, (size_t)n2 * 32));
+  int* dRawPtr = raw12 ? (int*)dRaw : nullptr;
+  const float radius = (float)windowSize;                   // const float& r of GetFeaturesInArea takes the int (:726)
+  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dOff, dK2, cam, dCell, dSi);
+  LAUNCH(c, "k_init_candidates", k_init_candidates, dim3((unsigned)std::min(1024, (n1 + 3) / 4)), dim3(256), 0, dK1, dD1, n1, dPrev, dK2, dD2,
+         dCell, dSi, cam, radius, distLimit, width, dKeys, dCnt);
+  LAUNCH(c, "k_init_assign", k_init_assign, dim3(1), dim3(64), (size_t)(48 + n2) * sizeof(int) + (size_t)n1 * sizeof(short), dK1, dD1, n1,
+         dPrev, dK2, dD2, n2, dCell, dSi, cam, radius, distLimit, width, nnratio, checkOri ? 1 : 0, dKeys, dCnt, dM12, dRawPtr, dNm);
+  HIPCHK(download(c, matches12, dM12, n1));
+  if (raw12) HIPCHK(download(c, raw12, dRaw, n1));
+  HIPCHK(download(c, nmatches, dNm, 1));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 // ---- measurement -----------------------------------------------------------
 int64_t pli_trace_ranges(void) { return (int64_t)g_roctx.pushed.load(std::memory_order_relaxed); }
 

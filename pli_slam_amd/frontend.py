@@ -426,6 +426,36 @@ class Frontend:
                                                     ptr(best_idx), ptr(nmatches)))
         return rows, [best_idx[off[k]:off[k + 1]] for k in range(ncand)], nmatches
 
+    def search_for_initialization(self, kp1, desc1, prev_matched, kp2, desc2, bounds, window_size=10, nnratio=0.9,
+                                  check_orientation=True):
+        """Monocular initialisation's ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+        (ORBmatcher.cc:706-821; Tracking.cc:2109-2110 with window 100) - see pli_search_for_initialization.  kp1 / kp2: mvKeysUn
+        of F1 / F2 as KEYPOINT_DT rows, desc1 / desc2: mDescriptors, prev_matched: vbPrevMatched as n1 x (x, y) (not written),
+        bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY).
+        Returns (nmatches, matches12: vnMatches12 after the rotation filter, raw12: before it with the evictions applied,
+        new_prev_matched: a copy of prev_matched with the update :816-818 for the matches that are left)."""
+        k1 = np.ascontiguousarray(kp1, KEYPOINT_DT).reshape(-1)
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        k2 = np.ascontiguousarray(kp2, KEYPOINT_DT).reshape(-1)
+        d2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        pm = np.ascontiguousarray(prev_matched, np.float32).reshape(-1, 2)
+        if len(k1) != len(d1) or len(k2) != len(d2):
+            raise ValueError("every feature needs one keypoint and one descriptor")
+        if len(pm) != len(k1):
+            raise ValueError("prev_matched: one point per F1 keypoint")
+        n1, n2 = len(k1), len(k2)
+        m12 = np.full(n1, -1, np.int32)
+        raw = np.full(n1, -1, np.int32)
+        n = C.c_int32()
+        check(self.L.pli_search_for_initialization(self.h, ptr(k1), ptr(d1), n1, ptr(pm), ptr(k2), ptr(d2), n2, float(bounds[0]),
+                                                   float(bounds[1]), float(bounds[2]), float(bounds[3]), int(window_size),
+                                                   float(nnratio), int(bool(check_orientation)), ptr(m12), ptr(raw), C.byref(n)))
+        new_pm = pm.copy()
+        hit = m12 >= 0
+        new_pm[hit, 0] = k2["x"][m12[hit]]
+        new_pm[hit, 1] = k2["y"][m12[hit]]
+        return n.value, m12, raw, new_pm
+
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""
