@@ -390,6 +390,9 @@ pli_status pli_search_by_projection(pli_ctx* ctx,
  * prediction for the current frame, the optimised pose for the last.  dev_track: nframes records of pli_track_layout
  * (record 0 is left untouched): counts = {nq = last N, point matches, n1 = last line count, line matches},
  * best_idx2[j] = current keypoint matched to last keypoint j or -1, matches_12[i] = current line of last line i or -1.
+ * A last keypoint whose point lies in the current camera's plane (x3Dc.z == 0: invzc = +inf is not `< 0`) projects to +-inf, which
+ * the image gate refuses, or to NaN, which it does not (ORBmatcher.cc:2225-2228 compare false); a NaN projection takes no
+ * keypoint, because every distance test against it is false: best_idx2[j] = -1, as for the reference's loop.
  * Asynchronous on the context stream. */
 typedef struct pli_track_params {
   float fx, fy, cx, cy, bf;          /* Camera.fx/fy/cx/cy/bf (EuRoC.yaml:9-28)                        */
@@ -455,7 +458,9 @@ pli_status pli_stereo_fisheye(pli_ctx* ctx, const pli_kb8_camera* cam1, const pl
                               float* depth, float* p3d, int32_t* nmatches);
 
 /* The same on caller tables: kp_left / desc_left = mvKeys / mDescriptors (Nleft rows, lapping-area keypoints from row
- * mono_left on), kp_right / desc_right = mvKeysRight / mDescriptorsRight; octaves index the context's mvLevelSigma2. */
+ * mono_left on), kp_right / desc_right = mvKeysRight / mDescriptorsRight; octaves index the context's mvLevelSigma2.
+ * Every row of both tables must have 0 <= octave < orb_nlevels and finite x, y: otherwise PLI_ERR_INVALID, before anything is
+ * launched; the output arrays are left untouched and *nmatches is 0. */
 pli_status pli_stereo_fisheye_tables(pli_ctx* ctx, const pli_keypoint* kp_left, const uint8_t* desc_left, int32_t nleft,
                                      int32_t mono_left, const pli_keypoint* kp_right, const uint8_t* desc_right,
                                      int32_t nright, int32_t mono_right,

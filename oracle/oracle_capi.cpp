@@ -394,6 +394,18 @@ int orc_grid_query(const double* segs, int nseg, int rows, int cols, int qx, int
   return n;
 }
 // OpenCV-primitive restatements, exposed for known-answer tests.
+// Caller tables of orc_stereo_fisheye: -1 for a row whose octave is outside sigma2[0 .. nlevels) or whose coordinates are not
+// finite, as pli_stereo_fisheye_tables refuses it.  pyoracle.stereo_fisheye asks this before anything is indexed (a function
+// of its own: orc_stereo_fisheye keeps its arguments).
+int orc_fisheye_tables_valid(const pli_keypoint* kpL, int nleft, const pli_keypoint* kpR, int nright, int nlevels) {
+  for (int e = 0; e < 2; ++e) {
+    const pli_keypoint* k = e ? kpR : kpL;
+    const int n = e ? nright : nleft;
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(k[i].x) || !std::isfinite(k[i].y) || k[i].octave < 0 || k[i].octave >= nlevels) return -1;
+  }
+  return 0;
+}
 int orc_stereo_fisheye(const pli_keypoint* kpL, const uint8_t* descL, int nleft, int monoLeft, const pli_keypoint* kpR,
                        const uint8_t* descR, int nright, int monoRight, const float* cam1, const float* cam2, const float* Rlr,
                        const float* tlr, const float* sigma2, int* l2r, int* r2l, float* depth, float* p3d) {

@@ -434,7 +434,8 @@ def lapping_order(kp, lap0, lap1):
 
 
 def stereo_fisheye(kpL, descL, mono_left, kpR, descR, mono_right, cam1, cam2, Rlr, tlr, sigma2):
-    """Frame::ComputeStereoFishEyeMatches (Frame.cc:1577-1618) on tables in lapping order."""
+    """Frame::ComputeStereoFishEyeMatches (Frame.cc:1577-1618) on tables in lapping order.
+    Raises ValueError for a row whose octave is outside sigma2 or whose coordinates are not finite (orc_fisheye_tables_valid)."""
     kpL, kpR = np.ascontiguousarray(kpL, KEYPOINT_DT), np.ascontiguousarray(kpR, KEYPOINT_DT)
     descL, descR = np.ascontiguousarray(descL, np.uint8), np.ascontiguousarray(descR, np.uint8)
     c1, c2 = np.ascontiguousarray(cam1, np.float32), np.ascontiguousarray(cam2, np.float32)
@@ -443,6 +444,8 @@ def stereo_fisheye(kpL, descL, mono_left, kpR, descR, mono_right, cam1, cam2, Rl
     nl, nr = kpL.shape[0], kpR.shape[0]
     l2r, r2l = np.zeros(nl, np.int32), np.zeros(nr, np.int32)
     depth, p3d = np.zeros(nl, np.float32), np.zeros((nl, 3), np.float32)
+    if lib().orc_fisheye_tables_valid(_p(kpL), nl, _p(kpR), nr, s2.shape[0]) < 0:
+        raise ValueError("stereo_fisheye: octave outside mvLevelSigma2 or a non-finite keypoint coordinate")
     n = lib().orc_stereo_fisheye(_p(kpL), _p(descL), nl, int(mono_left), _p(kpR), _p(descR), nr, int(mono_right), _p(c1), _p(c2),
                                  _p(R), _p(t), _p(s2), _p(l2r), _p(r2l), _p(depth), _p(p3d))
     return n, l2r, r2l, depth, p3d

@@ -2318,6 +2318,19 @@ static pli_status fisheyeCore(pli_ctx* c, bool hostTables, const pli_keypoint* k
   monoL = std::min(std::max(monoL, 0), NL);
   monoR = std::min(std::max(monoR, 0), NR);
   const int nq = NL - monoL, nt = NR - monoR;
+  if (hostTables) {
+    // k_fisheye_triangulate indexes mvLevelSigma2 by the octave of both keypoints and projects with their coordinates: the
+    // caller's rows are checked here, before anything is allocated or launched (the oracle's orc_fisheye_tables_valid is the same list)
+    for (int e = 0; e < 2; ++e) {
+      const pli_keypoint* k = e ? kR : kL;
+      const int n = e ? NR : NL;
+      for (int i = 0; i < n; ++i)
+        if (!std::isfinite(k[i].x) || !std::isfinite(k[i].y) || k[i].octave < 0 || k[i].octave >= c->hp.nlevels) {
+          g_err = "pli_stereo_fisheye_tables: a keypoint's octave is outside 0 .. nlevels-1 or its coordinates are not finite";
+          return PLI_ERR_INVALID;
+        }
+    }
+  }
   ScratchPlan plan;
   auto kidx = plan.add<int>((size_t)nq * 2);             // k_knn2: two ints per query, the indices ...
   auto kdst = plan.add<int>((size_t)nq * 2);             // ... and the distances
