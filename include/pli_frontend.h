@@ -502,6 +502,38 @@ pli_status pli_search_local_map_fisheye(pli_ctx* ctx, const pli_proj_query* q_le
                                         float min_x, float max_x, float min_y, float max_y, float nnratio,
                                         int32_t* mp_left, int32_t* mp_right, int32_t* nmatches);
 
+/* --- Frame-to-frame tracking of a two-camera frame (Tracking::TrackWithMotionModel, Tracking.cc:2961,2969) ---
+ * Core of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) ORBmatcher.cc:1961-2177 for a current frame of two
+ * cameras (CurrentFrame.Nleft != -1), whose mvpMapPoints has Nleft + Nright slots.  The caller projects, as for
+ * pli_search_by_projection.  Per LastFrame row i, in order:
+ *   q_left[i]:  everything as for pli_search_by_projection — (u,v) = mpCamera->project(x3Dc), radius = th*mvScaleFactors[nLastOctave],
+ *               the octave window, angle = the last frame's keypoint angle (mvKeys / mvKeysRight by i < LastFrame.Nleft), valid =
+ *               0 (no map point / outlier / invzc < 0), 1, or 1 | PLI_PROJ_NO_OBSERVATIONS.  The image gate :2004-2007 and
+ *               GetFeaturesInArea on mGrid / mvKeys (kp_left) apply; this branch has no mvuRight gate (:2040).
+ *   q_right[i]: only u, v, radius, min_level and max_level are read — (u,v) = mpCamera->project(Trl*x3Dc) (:2084-2086), the same
+ *               radius and window; valid and angle are those of q_left[i]; `ur` is read on neither side.  No image gate and no
+ *               invz test (:2086); GetFeaturesInArea on mGridRight / mvKeysRight (kp_right).
+ * The right camera of row i is searched only if the left projection passed the image gate AND the left GetFeaturesInArea
+ * returned at least one keypoint (the `continue`s of :2004-2007 and :2024 leave both cameras) — judged on the window and the level
+ * gate alone, before availability and before any distance: a left window whose keypoints are all taken, or all farther than TH_HIGH,
+ * does not close the right camera.
+ * occ_left[k] / occ_right[k] != 0 (may be NULL): slot k / Nleft + k holds a map point with Observations() > 0 before the call; a
+ * match takes its keypoint away from the rows behind it on that camera unless valid has PLI_PROJ_NO_OBSERVATIONS, on both
+ * cameras.  One 30-bin rotation histogram and one ComputeThreeMaxima for both cameras (:2154-2174).
+ * best_left[i] / best_right[i] = the keypoint of that camera (index within the camera) row i holds after the rotation filter, or
+ * -1; raw_left / raw_right (may be NULL) = the same before it: a maintainer replays :2061 / :2128 from them in row order, left
+ * then right, and :2169 for the entries with raw >= 0 > best.  *nmatches = the reference's return value.
+ * A NaN projection takes no keypoint (every distance test against it is false) and, on the left, leaves the right camera
+ * unsearched as an empty window does; an infinite right projection falls outside the grid and takes none either.
+ * nleft + nright <= 15360: more is PLI_ERR_CAPACITY, nothing is truncated.  nq, nleft and nright may be 0. */
+pli_status pli_search_by_projection_two_cameras(pli_ctx* ctx,
+                                                const pli_proj_query* q_left, const pli_proj_query* q_right, const uint8_t* qdesc, int32_t nq,
+                                                const pli_keypoint* kp_left, const uint8_t* desc_left, const uint8_t* occ_left, int32_t nleft,
+                                                const pli_keypoint* kp_right, const uint8_t* desc_right, const uint8_t* occ_right, int32_t nright,
+                                                float min_x, float max_x, float min_y, float max_y, int32_t check_orientation,
+                                                int32_t* best_left, int32_t* best_right, int32_t* raw_left, int32_t* raw_right,
+                                                int32_t* nmatches);
+
 /* int match(const vector<MapLine*>&, Frame&, nnr, matches_12) LineMatcher.cpp:161-171: one-directional matchNNR
  * of the local map lines' descriptors against the frame's (the reference returns before its mutual check). */
 pli_status pli_match_nnr(pli_ctx* ctx, const uint8_t* desc1, int32_t n1, const uint8_t* desc2, int32_t n2, float nnr,

@@ -266,6 +266,26 @@ class Frontend {
                                        mpRight.data(), &n));
     return n;
   }
+  // core of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for a current frame of two cameras
+  // (CurrentFrame.Nleft != -1), ORBmatcher.cc:1961-2177 (include/pli_frontend.h pli_search_by_projection_two_cameras): bestLeft[i] /
+  // bestRight[i] = the keypoint of that camera row i holds after the rotation filter or -1, rawLeft / rawRight the same before it
+  int searchByProjectionTwoCameras(const std::vector<pli_proj_query>& qLeft, const std::vector<pli_proj_query>& qRight,
+                                   const uint8_t* qdesc, const std::vector<pli_keypoint>& kpLeft, const uint8_t* descLeft,
+                                   const uint8_t* occLeft, const std::vector<pli_keypoint>& kpRight, const uint8_t* descRight,
+                                   const uint8_t* occRight, float minX, float maxX, float minY, float maxY, bool checkOrientation,
+                                   std::vector<int>& bestLeft, std::vector<int>& bestRight, std::vector<int>* rawLeft = nullptr,
+                                   std::vector<int>* rawRight = nullptr) {
+    if (qLeft.size() != qRight.size()) throw std::logic_error("searchByProjectionTwoCameras: one right query per left query");
+    bestLeft.assign(qLeft.size(), -1); bestRight.assign(qLeft.size(), -1);
+    if (rawLeft) rawLeft->assign(qLeft.size(), -1);
+    if (rawRight) rawRight->assign(qLeft.size(), -1);
+    int32_t n = 0;
+    check(pli_search_by_projection_two_cameras(ctx_, qLeft.data(), qRight.data(), qdesc, (int)qLeft.size(), kpLeft.data(), descLeft,
+                                               occLeft, (int)kpLeft.size(), kpRight.data(), descRight, occRight, (int)kpRight.size(),
+                                               minX, maxX, minY, maxY, checkOrientation ? 1 : 0, bestLeft.data(), bestRight.data(),
+                                               rawLeft ? rawLeft->data() : nullptr, rawRight ? rawRight->data() : nullptr, &n));
+    return n;
+  }
   // int match(const vector<MapLine*>&, Frame&, nnr, matches_12) LineMatcher.cpp:161 on the descriptor tables
   int matchNNR(const uint8_t* desc1, int n1, const uint8_t* desc2, int n2, float nnr, std::vector<int>& matches12) {
     matches12.assign(n1, -1);

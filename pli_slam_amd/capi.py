@@ -178,6 +178,11 @@ _PROTOS = {
     "pli_fuse_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FuseCamera), C.c_float, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p]),
+    "pli_search_by_projection_two_cameras": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                         C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "pli_search_by_projection_sim3": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FuseCamera), C.c_float,
                                                   C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -614,13 +614,15 @@ __device__ __forceinline__ void proj_candidates_dev(int i, int lane, const pli_p
                                                     const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc,
                                                     const float* __restrict__ uright, int ncur, float minX, float maxX,
                                                     float minY, float maxY, int checkBounds, int distLimit,
-                                                    unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
+                                                    unsigned long long* __restrict__ candKeys, int* __restrict__ candCount,
+                                                    int* __restrict__ windowOpen = nullptr /* nq, or null */) {
   if (i >= nq) return;
   const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX));
   const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(maxY, minY));
   const pli_proj_query Q = q[i];
   int c0, c1, r0, r1;
   int count = 0;
+  bool open = false;                                    // GetFeaturesInArea returns something: before "taken" and before any distance
   if (proj_window(Q, minX, maxX, minY, maxY, gwInv, ghInv, checkBounds != 0, c0, c1, r0, r1)) {
     uint64_t dq[4];
     load_desc(qdesc + (int64_t)i * 32, dq);
@@ -629,6 +631,7 @@ __device__ __forceinline__ void proj_candidates_dev(int i, int lane, const pli_p
       unsigned long long key = ~0ull;
       if (i2 < ncur) key = proj_key(Q, dq, i2, kp, desc, uright, minX, minY, gwInv, ghInv, c0, c1, r0, r1);
       const bool keep = key != ~0ull && (int)(key >> 40) <= distLimit;
+      if (windowOpen) open = open || __builtin_amdgcn_ballot_w64(key != ~0ull) != 0ull;
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
       const int pos = count + __popcll(bal & ((1ull << lane) - 1ull));
       if (keep && pos < PROJ_K) candKeys[(int64_t)i * PROJ_K + pos] = key;
@@ -636,6 +639,7 @@ __device__ __forceinline__ void proj_candidates_dev(int i, int lane, const pli_p
     }
   }
   if (lane == 0) candCount[i] = count <= PROJ_K ? count : -1;
+  if (windowOpen && lane == 0) windowOpen[i] = open ? 1 : 0;
 }
 
 __global__ __launch_bounds__(64) void k_proj_candidates(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc,
@@ -660,7 +664,11 @@ __device__ __forceinline__ int proj_rot_bin(float qAngle, float kpAngle) {
 // owner: ncur ints: -1 free, else the query that took the keypoint (INT_MAX: occupied before).  kOwnerInLds says where the caller
 // keeps them; the only difference is the fence that orders a query's owner store before the next query's owner loads.
 // candCount null: no candidate lists, every query scans the frame.
-template <bool kOwnerInLds>
+// kCamera (mode 0) 1 / 2: the walk of the left / right camera of a two-camera frame (k_proj2_assign below).  The right walk leaves
+// out the queries whose skipUnless[i] is 0 and has no image gate (ORBmatcher.cc:2086); the rotation filter waits for the other
+// camera, so either walk leaves its histogram in histOut[HISTO_LENGTH], the matches before the filter in bestIdx2 and their
+// number in *nmatchesOut.
+template <bool kOwnerInLds, int kCamera = 0>
 __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_proj_query* __restrict__ q,
                                                 const uint8_t* __restrict__ qdesc, int nq,
                                                 const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc,
@@ -668,7 +676,8 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
                                                 int ncur, float minX, float maxX, float minY, float maxY, int mode,
                                                 int checkOri, float nnratio, const unsigned long long* __restrict__ candKeys,
                                                 const int* __restrict__ candCount, int* __restrict__ bestIdx2,
-                                                int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2 /* mode 0, or null */) {
+                                                int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2 /* mode 0, or null */,
+                                                const int* __restrict__ skipUnless = nullptr, int* __restrict__ histOut = nullptr) {
   __shared__ int hist[HISTO_LENGTH];
   __shared__ int keep[HISTO_LENGTH];
   const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(maxX, minX));
@@ -687,6 +696,7 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
       cntNext = candCount[i + 1];
       keyNext = lane < cntNext ? candKeys[(int64_t)(i + 1) * PROJ_K + lane] : ~0ull;
     }
+    if (kCamera == 2 && !skipUnless[i]) continue;                   // (nothing was stored: no fence needed)
     WaveTop2 top;
     if (cnt >= 0) {
       if (key != ~0ull && owner[(int)(key & 0xFFFFFFFull)] >= 0) key = ~0ull;
@@ -694,7 +704,7 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
     } else {                                            // no list, or more than PROJ_K candidates: scan the frame for this query
       const pli_proj_query Q = q[i];
       int c0, c1, r0, r1;
-      if (proj_window(Q, minX, maxX, minY, maxY, gwInv, ghInv, mode == 0, c0, c1, r0, r1)) {
+      if (proj_window(Q, minX, maxX, minY, maxY, gwInv, ghInv, mode == 0 && kCamera != 2, c0, c1, r0, r1)) {
         uint64_t dq[4];
         load_desc(qdesc + (int64_t)i * 32, dq);
         for (int i2 = lane; i2 < ncur; i2 += 64) {
@@ -736,7 +746,9 @@ __device__ __forceinline__ void proj_assign_dev(int lane, int* owner, const pli_
     }
   }
   __syncthreads();
-  if (mode == 0) {
+  if (kCamera != 0) {
+    if (lane < HISTO_LENGTH) histOut[lane] = hist[lane];
+  } else if (mode == 0) {
     if (checkOri) {
       if (lane == 0) {
         int ind1, ind2, ind3;
@@ -783,6 +795,82 @@ __global__ __launch_bounds__(64) void k_proj_assign_scan(const pli_proj_query* _
                                                          int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2) {
   proj_assign_dev<false>(threadIdx.x, owner, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, mode, checkOri,
                          nnratio, nullptr, nullptr, bestIdx2, nmatchesOut, rawIdx2);
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for a current frame of two cameras (ORBmatcher.cc:1961-2177
+// with CurrentFrame.Nleft != -1).  The left search reads and writes only the left half of CurrentFrame.mvpMapPoints and the right
+// search only the right half, so the two ordered walks never see each other's writes.  What couples them is (a) the left
+// `continue`s of :2004-2007 and :2024, which leave the right camera unsearched too and depend on the geometry alone — the
+// windowOpen flag of the left candidates — and (b) the one rotation histogram.  So: candidates of every (query, camera) in
+// parallel, the two walks side by side (one wave each, owner table in LDS), then one wave that adds the histograms and filters.
+//   q: [2][nq] (left, then right with valid and angle of the left), keys [2][nq][PROJ_K], cnt / best / raw [2][nq],
+//   hist [2][HISTO_LENGTH], accepts [2]; noUright: max(nL, nR) floats of -1 (this branch has no mvuRight gate, :2040)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_proj2_candidates(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq,
+                                                         const pli_keypoint* __restrict__ kpL, const uint8_t* __restrict__ descL, int nL,
+                                                         const pli_keypoint* __restrict__ kpR, const uint8_t* __restrict__ descR, int nR,
+                                                         const float* __restrict__ noUright, float minX, float maxX, float minY,
+                                                         float maxY, unsigned long long* __restrict__ candKeys,
+                                                         int* __restrict__ candCount, int* __restrict__ leftOpen) {
+  const int cam = blockIdx.y;
+  // (the image gate :2004-2007 is the left projection's; the right projection has none, :2086)
+  proj_candidates_dev(blockIdx.x, threadIdx.x, q + (int64_t)cam * nq, qdesc, nq, cam ? kpR : kpL, cam ? descR : descL, noUright,
+                      cam ? nR : nL, minX, maxX, minY, maxY, cam ? 0 : 1, 100, candKeys + (int64_t)cam * nq * PROJ_K,
+                      candCount + (int64_t)cam * nq, cam ? nullptr : leftOpen);
+}
+
+// grid 2: block = camera; LDS: max(nL, nR) ints
+__global__ __launch_bounds__(64) void k_proj2_assign(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq,
+                                                     const pli_keypoint* __restrict__ kpL, const uint8_t* __restrict__ descL,
+                                                     const uint8_t* __restrict__ occL, int nL, const pli_keypoint* __restrict__ kpR,
+                                                     const uint8_t* __restrict__ descR, const uint8_t* __restrict__ occR, int nR,
+                                                     const float* __restrict__ noUright, float minX, float maxX, float minY, float maxY,
+                                                     int checkOri, const unsigned long long* __restrict__ candKeys,
+                                                     const int* __restrict__ candCount, const int* __restrict__ leftOpen,
+                                                     int* __restrict__ rawIdx2, int* __restrict__ hist, int* __restrict__ accepts) {
+  extern __shared__ int owner[];
+  const int cam = blockIdx.x;
+  if (cam == 0)
+    proj_assign_dev<true, 1>(threadIdx.x, owner, q, qdesc, nq, kpL, descL, noUright, occL, nL, minX, maxX, minY, maxY, 0, checkOri, 0.0f,
+                             candKeys, candCount, rawIdx2, accepts, nullptr, nullptr, hist);
+  else
+    proj_assign_dev<true, 2>(threadIdx.x, owner, q + nq, qdesc, nq, kpR, descR, noUright, occR, nR, minX, maxX, minY, maxY, 0, checkOri,
+                             0.0f, candKeys + (int64_t)nq * PROJ_K, candCount + nq, rawIdx2 + nq, accepts + 1, nullptr, leftOpen,
+                             hist + HISTO_LENGTH);
+}
+
+// one wave: ComputeThreeMaxima on the joint histogram, then the filter :2163-2173 over both cameras' matches
+__global__ __launch_bounds__(64) void k_proj2_finish(const pli_proj_query* __restrict__ q, int nq, const pli_keypoint* __restrict__ kpL,
+                                                     const pli_keypoint* __restrict__ kpR, int checkOri,
+                                                     const int* __restrict__ rawIdx2, const int* __restrict__ hist,
+                                                     const int* __restrict__ accepts, int* __restrict__ bestIdx2,
+                                                     int* __restrict__ nmatchesOut) {
+  __shared__ int joint[HISTO_LENGTH];
+  __shared__ int keep[HISTO_LENGTH];
+  const int lane = threadIdx.x;
+  if (lane < HISTO_LENGTH) joint[lane] = hist[lane] + hist[HISTO_LENGTH + lane];
+  __syncthreads();
+  if (checkOri && lane == 0) {
+    int ind1, ind2, ind3;
+    three_maxima(joint, ind1, ind2, ind3);
+    for (int i = 0; i < HISTO_LENGTH; ++i) keep[i] = (i == ind1 || i == ind2 || i == ind3);
+  }
+  __syncthreads();
+  int removed = 0;
+  for (int cam = 0; cam < 2; ++cam) {
+    const pli_keypoint* kp = cam ? kpR : kpL;
+    for (int i = lane; i < nq; i += 64) {
+      int b = rawIdx2[(int64_t)cam * nq + i];
+      if (b >= 0 && checkOri) {
+        const int bin = proj_rot_bin(q[i].angle, kp[b].angle);
+        if (bin < 0 || !keep[bin]) { b = -1; ++removed; }
+      }
+      bestIdx2[(int64_t)cam * nq + i] = b;
+    }
+  }
+  removed = wave_sum_i32(removed);
+  if (lane == 0) *nmatchesOut = accepts[0] + accepts[1] - removed;
 }
 
 // ---------------------------------------------------------------------------

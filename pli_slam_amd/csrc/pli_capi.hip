@@ -2669,6 +2669,74 @@ pli_status pli_search_local_map_fisheye(pli_ctx* c, const pli_proj_query* qL, co
   return fetchCount(c, dcnt, nmatches);
 }
 
+// SearchByProjection(CurrentFrame, LastFrame) for a current frame of two cameras (match_kernels.hip: k_proj2_*)
+pli_status pli_search_by_projection_two_cameras(pli_ctx* c, const pli_proj_query* qL, const pli_proj_query* qR, const uint8_t* qdesc,
+                                                int32_t nq, const pli_keypoint* kpL, const uint8_t* descL, const uint8_t* occL,
+                                                int32_t nL, const pli_keypoint* kpR, const uint8_t* descR, const uint8_t* occR,
+                                                int32_t nR, float minX, float maxX, float minY, float maxY, int32_t checkOri,
+                                                int32_t* bestL, int32_t* bestR, int32_t* rawL, int32_t* rawR, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || nq < 0 || nL < 0 || nR < 0 || (nq > 0 && (!qL || !qR || !qdesc || !bestL || !bestR)) || (nL > 0 && (!kpL || !descL)) ||
+      (nR > 0 && (!kpR || !descR))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nmatches) *nmatches = 0;
+  for (int i = 0; i < nq; ++i)
+    if (qL[i].valid & ~3) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
+  if ((int64_t)nL + nR > PROJ_LDS_KEYPOINTS) { g_err = "too many keypoints for the LDS owner tables of the two-camera projection search"; return PLI_ERR_CAPACITY; }
+  if (nq == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const int ncM = std::max(std::max(nL, nR), 1);
+  // both cameras' queries in one block: the left as given, then the right with the left's valid and angle (the only fields the
+  // reference takes from the last frame's row for both cameras); q2 lives until the synchronisation in fetchCount
+  std::vector<pli_proj_query> q2((size_t)2 * nq);
+  for (int i = 0; i < nq; ++i) {
+    q2[i] = qL[i];
+    pli_proj_query r = qR[i];
+    r.ur = 0.0f; r.angle = qL[i].angle; r.valid = qL[i].valid;
+    q2[(size_t)nq + i] = r;
+  }
+  ScratchPlan plan;
+  auto dq = plan.add<pli_proj_query>((size_t)2 * nq);
+  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
+  auto dkL = plan.add<pli_keypoint>(nL);
+  auto ddL = plan.add<uint8_t>((size_t)nL * 32);
+  auto doL = plan.add<uint8_t>(nL);
+  auto dkR = plan.add<pli_keypoint>(nR);
+  auto ddR = plan.add<uint8_t>((size_t)nR * 32);
+  auto doR = plan.add<uint8_t>(nR);
+  auto du = plan.add<float>(ncM);
+  auto dkeys = plan.add<unsigned long long>((size_t)2 * nq * PROJ_K);
+  auto dcc = plan.add<int>((size_t)2 * nq);
+  auto dopen = plan.add<int>(nq);
+  auto draw = plan.add<int>((size_t)2 * nq);
+  auto dbest = plan.add<int>((size_t)2 * nq);
+  auto dhist = plan.add<int>(2 * 30);                    // [2][HISTO_LENGTH]
+  auto dacc = plan.add<int>(2);
+  auto dcnt = plan.add<int>(1);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  HIPCHK(upload(c, dq, q2.data(), (size_t)2 * nq));
+  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
+  HIPCHK(upload(c, dkL, kpL, nL));
+  HIPCHK(upload(c, ddL, descL, (size_t)nL * 32));
+  if (occL) HIPCHK(upload(c, doL, occL, nL));
+  HIPCHK(upload(c, dkR, kpR, nR));
+  HIPCHK(upload(c, ddR, descR, (size_t)nR * 32));
+  if (occR) HIPCHK(upload(c, doR, occR, nR));
+  LAUNCH(c, "k_fill_f32", k_fill_f32, dim3((ncM + 255) / 256), dim3(256), 0, du, ncM, -1.0f);
+  LAUNCH(c, "k_proj2_candidates", k_proj2_candidates, dim3(nq, 2), dim3(64), 0, dq, dqd, nq, dkL, ddL, nL, dkR, ddR, nR, du, minX, maxX,
+         minY, maxY, dkeys, dcc, dopen);
+  LAUNCH(c, "k_proj2_assign", k_proj2_assign, dim3(2), dim3(64), (size_t)ncM * 4, dq, dqd, nq, dkL, ddL,
+         (occL && nL > 0) ? (const uint8_t*)doL : (const uint8_t*)nullptr, nL, dkR, ddR,
+         (occR && nR > 0) ? (const uint8_t*)doR : (const uint8_t*)nullptr, nR, du, minX, maxX, minY, maxY, checkOri, dkeys, dcc, dopen,
+         draw, dhist, dacc);
+  LAUNCH(c, "k_proj2_finish", k_proj2_finish, dim3(1), dim3(64), 0, dq, nq, dkL, dkR, checkOri, draw, dhist, dacc, dbest, dcnt);
+  HIPCHK(download(c, bestL, dbest, nq));
+  HIPCHK(hipMemcpyAsync(bestR, (int*)dbest + nq, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(download(c, rawL, draw, nq));
+  if (rawR) HIPCHK(hipMemcpyAsync(rawR, (int*)draw + nq, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+  return fetchCount(c, dcnt, nmatches);
+}
+
 // ---- frame-to-frame track matching of a batch (match_kernels.hip: k_track_*) ------------------------
 static void trackLayout(const pli_ctx* c, pli_track_layout& L) {
   int64_t o = 0;

@@ -549,6 +549,30 @@ class Frontend:
                                                   bounds[2], bounds[3], nnratio, ptr(mpl), ptr(mpr), C.byref(n)))
         return n.value, mpl, mpr
 
+    def search_by_projection_two_cameras(self, q_left, q_right, qdesc, kp_left, desc_left, kp_right, desc_right, bounds,
+                                         check_orientation=True, occ_left=None, occ_right=None, with_raw=False):
+        """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for a current frame of two cameras,
+        ORBmatcher.cc:1961-2177 — see pli_search_by_projection_two_cameras.  Returns (nmatches, best_left, best_right), with_raw:
+        (nmatches, best_left, best_right, raw_left, raw_right)."""
+        ql = np.ascontiguousarray(q_left, PROJ_QUERY_DT)
+        qr = np.ascontiguousarray(q_right, PROJ_QUERY_DT)
+        if ql.shape != qr.shape:
+            raise ValueError("q_left and q_right: one row per query each")
+        qd = np.ascontiguousarray(qdesc, np.uint8)
+        kl, kr = np.ascontiguousarray(kp_left, KEYPOINT_DT), np.ascontiguousarray(kp_right, KEYPOINT_DT)
+        dl, dr = np.ascontiguousarray(desc_left, np.uint8), np.ascontiguousarray(desc_right, np.uint8)
+        ol = None if occ_left is None else np.ascontiguousarray(occ_left, np.uint8)
+        orr = None if occ_right is None else np.ascontiguousarray(occ_right, np.uint8)
+        nq = ql.shape[0]
+        bl, br = np.full(nq, -1, np.int32), np.full(nq, -1, np.int32)
+        rl, rr = (np.full(nq, -1, np.int32), np.full(nq, -1, np.int32)) if with_raw else (None, None)
+        n = C.c_int32()
+        check(self.L.pli_search_by_projection_two_cameras(self.h, ptr(ql), ptr(qr), ptr(qd), nq, ptr(kl), ptr(dl), ptr(ol),
+                                                          kl.shape[0], ptr(kr), ptr(dr), ptr(orr), kr.shape[0], bounds[0],
+                                                          bounds[1], bounds[2], bounds[3], int(check_orientation), ptr(bl), ptr(br),
+                                                          ptr(rl), ptr(rr), C.byref(n)))
+        return (n.value, bl, br, rl, rr) if with_raw else (n.value, bl, br)
+
     def match_nnr(self, desc1, desc2, nnr):
         """match(vpLocalMapLines, CurrentFrame, nnr, matches_12) LineMatcher.cpp:161 (one-way matchNNR)."""
         d1, d2 = np.ascontiguousarray(desc1, np.uint8), np.ascontiguousarray(desc2, np.uint8)
