@@ -125,6 +125,14 @@ int orc_get_level_points(void* h, int eye, int level, int which, int* dst, int c
   return n;
 }
 
+// Coverage counters of the last orb extract (OrbCoverage in orb_oracle.hpp): COV_COUNT ints; returns COV_COUNT.
+int orc_get_level_coverage(void* h, int eye, int level, int* dst, int cap) {
+  const OrbLevelDebug& d = ((Frame*)h)->eye[eye].orb->dbg[level];
+  for (int i = 0; i < COV_COUNT && i < cap; ++i) dst[i] = d.cov[i];
+  return COV_COUNT;
+}
+const char* orc_coverage_name(int i) { return i >= 0 && i < COV_COUNT ? kOrbCoverageNames[i] : nullptr; }
+
 int orc_line_extract(void* h, int eye, const uint8_t* img, int w, int hgt, int64_t stride) {
   Frame* f = (Frame*)h;
   Eye& E = f->eye[eye];

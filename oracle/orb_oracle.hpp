@@ -1,11 +1,28 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (never linked into the product library).
 //
 // CPU restatement of ORB_SLAM3::ORBextractor (reference src/ORBextractor.cc),
-// OpenCV primitives from ocv_prims.hpp.  PARITY UNPINNED: the reference has no
-// tests or golden vectors for this path and cannot be built here
-// (OpenCV absent); this file follows the reference source line by line in
-// behaviour, citing file:line, and defines the two things the reference leaves
-// implementation-defined (see DistributeOctTree below).
+// OpenCV primitives from ocv_prims.hpp; follows the reference source line by
+// line in behaviour, citing file:line.
+//
+// PINNED to the reference's own translation unit: oracle/Makefile compiles
+// src/ORBextractor.cc where it lies against ref_recipe/cv_shim/ and
+// ref_recipe/ref_orb_main.cpp (oracle/_ref/pli_ref_orb); its recorded outputs
+// (tests/golden/orb_ref) equal this file's byte for byte on every keypoint row,
+// descriptor and pyramid level of the corpus (tests/test_ref_pin_orb.py).
+//  * Pinned: control flow, geometry and arithmetic -- cell geometry, the
+//    two-threshold fallback, the quotas, DistributeOctTree with its list order
+//    and sort, the rescale, IC_Angle, the steered BRIEF, the lapping order --
+//    over ocv_prims.hpp's restatement of cv::FAST / GaussianBlur / resize /
+//    copyMakeBorder / fastAtan2.
+//  * Not pinned: OpenCV's own bit conventions inside those primitives
+//    (tools/pin/run_pin.sh).
+//  * The order among equal node sizes at the octree's sort (:682, by heap
+//    address in the reference) is the reference's under a monotone heap; under
+//    glibc's heap the reference differs from itself.
+//  * Inputs outside the pin, which the reference leaves undefined and this
+//    file goes on defining: a level with nIni == 0 (portrait images; the
+//    reference indexes an empty vector) and a level without cells (division by
+//    zero).
 #pragma once
 #include "ocv_prims.hpp"
 #include "../include/pli_frontend.h"
@@ -24,9 +41,37 @@ static const int EDGE_THRESHOLD = 19;    // :72
 
 struct OrbCand { int x, y, score; };     // coordinates relative to (minBorderX, minBorderY)
 
+// Which branches of ComputeKeyPointsOctTree / DistributeOctTree a level went through.  Counted so that
+// tests/test_ref_pin_orb.py can assert that its corpus reaches every one of them; nothing reads them otherwise.
+// kOrbCoverageNames (same order) are the labels oracle/pyoracle.py reports.
+enum OrbCoverage {
+  COV_NINI,                 // nIni of the level (a value, not a count)
+  COV_STOP_QUOTA_EXPAND,    // the loop ended in the first expansion phase: lNodes.size() >= N after a full pass (:669)
+  COV_STOP_QUOTA_BREAK,     // ... at the `break` inside the sorted phase (:727)
+  COV_STOP_ALL_SINGLE,      // ... with the quota never reached: size == prevSize, every node single (:669 or :732)
+  COV_SORT_TIES,            // adjacent equal sizes in a sorted vPrevSizeAndPointerToNode (:682)
+  COV_TIE_SPLIT_AT_BREAK,   // the `break` fell inside a group of equal sizes: the next node in line had the size of the last expanded
+  COV_KEYS_ON_SPLIT_LINE,   // DivideNode saw a key with x == n1.UR.x or y == n1.BR.y
+  COV_KEYS_ON_INI_BOUNDARY, // with a non-integer hX: a key on the first integer column of an initial node i >= 1
+  COV_EQUAL_MAXIMA,         // final nodes whose maximal response occurs more than once (first in list order wins)
+  COV_FALLBACK_CELLS,       // cells whose corners are all below iniThFAST: the cv::FAST(minThFAST) result is taken
+  COV_MIXED_CELLS,          // cells with corners of both kinds: the sub-iniThFAST ones are dropped
+  COV_CLIPPED_CELLS,        // cells cut by maxBorderX / maxBorderY
+  COV_SKIPPED_CELLS,        // cells skipped by iniX >= maxBorderX - 6 / iniY >= maxBorderY - 3
+  COV_NARROW_CELLS,         // cells whose sub-image is under 7 px in either direction: cv::FAST returns nothing
+  COV_SEVEN_PX_CELLS,       // cells whose sub-image is exactly 7 px in a direction: one row / column of pixels is searched
+  COV_SEAM_PAIRS,           // 8-neighbour pairs of kept corners that lie in different cells (NMS is per cell)
+  COV_COUNT
+};
+static const char* const kOrbCoverageNames[COV_COUNT] = {
+    "nIni", "stop_quota_expand", "stop_quota_break", "stop_all_single", "sort_ties", "tie_split_at_break", "keys_on_split_line",
+    "keys_on_ini_boundary", "equal_maxima", "fallback_cells", "mixed_cells", "clipped_cells", "skipped_cells", "narrow_cells",
+    "seven_px_cells", "seam_pairs"};
+
 struct OrbLevelDebug {
   std::vector<OrbCand> candidates;       // vToDistributeKeys, reference order
   std::vector<OrbCand> selected;         // after DistributeOctTree, list order
+  int cov[COV_COUNT] = {};
 };
 
 struct OrbExtractor {
@@ -151,7 +196,7 @@ struct OrbExtractor {
     std::list<Node>::iterator lit;
   };
 
-  static void DivideNode(const Node& n, const std::vector<OrbCand>& K, Node& n1, Node& n2, Node& n3, Node& n4) {
+  static void DivideNode(const Node& n, const std::vector<OrbCand>& K, Node& n1, Node& n2, Node& n3, Node& n4, int* cov = nullptr) {
     const int halfX = (int)std::ceil(static_cast<float>(n.URx - n.ULx) / 2);
     const int halfY = (int)std::ceil(static_cast<float>(n.BRy - n.ULy) / 2);
     n1.ULx = n.ULx; n1.ULy = n.ULy;
@@ -172,6 +217,7 @@ struct OrbExtractor {
     n4.BRx = n.BRx; n4.BRy = n.BRy;
     for (size_t i = 0; i < n.keys.size(); i++) {
       const OrbCand& kp = K[n.keys[i]];
+      if (cov && (kp.x == n1.URx || kp.y == n1.BRy)) cov[COV_KEYS_ON_SPLIT_LINE]++;
       if ((float)kp.x < n1.URx) {
         if ((float)kp.y < n1.BRy) n1.keys.push_back(n.keys[i]);
         else n3.keys.push_back(n.keys[i]);
@@ -184,17 +230,22 @@ struct OrbExtractor {
     if (n4.keys.size() == 1) n4.bNoMore = true;
   }
 
-  // Two reference behaviours are implementation-defined and are fixed here:
+  // One reference behaviour is implementation-defined and is fixed here:
   //  * :682 sorts pair<int, ExtractorNode*>: equal sizes are ordered by heap
   //    address.  Oracle: by creation order (`seq`), i.e. among equal sizes the
-  //    most recently created node is expanded first.
+  //    most recently created node is expanded first -- which is exactly the
+  //    reference under a heap that hands out growing addresses (pinned so).
   //  * nothing else: list order, push_front order, first-max-wins are as written.
   static std::vector<int> DistributeOctTree(const std::vector<OrbCand>& K, int minX, int maxX, int minY,
-                                            int maxY, int N) {
+                                            int maxY, int N, int* cov = nullptr) {
     std::vector<int> result;
+    int covLocal[COV_COUNT] = {};
+    if (!cov) cov = covLocal;
     const int nIni = (int)std::round(static_cast<float>(maxX - minX) / (maxY - minY));
-    if (nIni <= 0) return result;     // degenerate aspect (reference divides by zero)
+    cov[COV_NINI] = nIni;
+    if (nIni <= 0) return result;     // degenerate aspect (the reference indexes an empty vector); outside the pin
     const float hX = static_cast<float>(maxX - minX) / nIni;
+    const bool hXInteger = hX == (float)(int)hX;
     std::list<Node> lNodes;
     std::vector<Node*> vpIniNodes(nIni);
     long seq = 0;
@@ -211,6 +262,7 @@ struct OrbExtractor {
     for (size_t i = 0; i < K.size(); i++) {
       int idx = (int)((float)K[i].x / hX);
       if (idx >= nIni) idx = nIni - 1;   // cannot happen for in-range keys; guards the oracle only
+      if (!hXInteger && idx > 0 && (int)((float)(K[i].x - 1) / hX) != idx) cov[COV_KEYS_ON_INI_BOUNDARY]++;
       vpIniNodes[idx]->keys.push_back((int)i);
     }
     auto lit = lNodes.begin();
@@ -245,28 +297,38 @@ struct OrbExtractor {
       while (lit != lNodes.end()) {
         if (lit->bNoMore) { lit++; continue; }
         Node n1, n2, n3, n4;
-        DivideNode(*lit, K, n1, n2, n3, n4);
+        DivideNode(*lit, K, n1, n2, n3, n4, cov);
         pushChild(n1, nToExpand); pushChild(n2, nToExpand);
         pushChild(n3, nToExpand); pushChild(n4, nToExpand);
         lit = lNodes.erase(lit);
       }
       if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) {
         bFinish = true;
+        cov[(int)lNodes.size() >= N ? COV_STOP_QUOTA_EXPAND : COV_STOP_ALL_SINGLE]++;
       } else if (((int)lNodes.size() + nToExpand * 3) > N) {
         while (!bFinish) {
           prevSize = (int)lNodes.size();
           std::vector<SP> vPrev = vSizeAndPointerToNode;
           vSizeAndPointerToNode.clear();
           std::sort(vPrev.begin(), vPrev.end(), cmp);
+          for (size_t j = 1; j < vPrev.size(); j++) cov[COV_SORT_TIES] += vPrev[j].first == vPrev[j - 1].first;
+          bool bBreak = false;
           for (int j = (int)vPrev.size() - 1; j >= 0; j--) {
             Node n1, n2, n3, n4;
-            DivideNode(*vPrev[j].second, K, n1, n2, n3, n4);
+            DivideNode(*vPrev[j].second, K, n1, n2, n3, n4, cov);
             int dummy = 0;
             pushChild(n1, dummy); pushChild(n2, dummy); pushChild(n3, dummy); pushChild(n4, dummy);
             lNodes.erase(vPrev[j].second->lit);
-            if ((int)lNodes.size() >= N) break;
+            if ((int)lNodes.size() >= N) {
+              bBreak = true;
+              if (j > 0 && vPrev[j - 1].first == vPrev[j].first) cov[COV_TIE_SPLIT_AT_BREAK]++;
+              break;
+            }
           }
-          if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) bFinish = true;
+          if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) {
+            bFinish = true;
+            cov[bBreak ? COV_STOP_QUOTA_BREAK : COV_STOP_ALL_SINGLE]++;
+          }
         }
       }
     }
@@ -278,6 +340,9 @@ struct OrbExtractor {
       for (size_t k = 1; k < vk.size(); k++) {
         if (K[vk[k]].score > maxResponse) { best = vk[k]; maxResponse = K[vk[k]].score; }
       }
+      int nMax = 0;
+      for (size_t k = 0; k < vk.size(); k++) nMax += K[vk[k]].score == maxResponse;
+      cov[COV_EQUAL_MAXIMA] += nMax > 1;
       result.push_back(best);
     }
     return result;
@@ -289,9 +354,13 @@ struct OrbExtractor {
   // strictly greater than their 8 neighbours INSIDE the evaluated interior of
   // the cell sub-image (rows/cols 3..dim-4); pixels outside count as 0.
   static void fastCell(const Img8& im, int x0, int y0, int x1, int y1, int iniTh, int minTh,
-                       std::vector<OrbCand>& out /* coords relative to the cell sub-image */) {
+                       std::vector<OrbCand>& out /* coords relative to the cell sub-image */, int* cov = nullptr) {
     int cw = x1 - x0, ch = y1 - y0;
-    if (cw < 7 || ch < 7) return;
+    if (cw < 7 || ch < 7) {
+      if (cov) cov[COV_NARROW_CELLS]++;
+      return;
+    }
+    if (cov && (cw == 7 || ch == 7)) cov[COV_SEVEN_PX_CELLS]++;
     int iw = cw - 6, ih = ch - 6;      // interior
     std::vector<int> sc((size_t)iw * ih);
     for (int y = 0; y < ih; ++y)
@@ -312,8 +381,15 @@ struct OrbExtractor {
           if (s >= iniTh) anyIni = true;       // arc > iniTh  <=>  score >= iniTh
         }
       }
-    for (const OrbCand& c : nms)
+    bool anySub = false;
+    for (const OrbCand& c : nms) {
       if (!anyIni || c.score >= iniTh) out.push_back(c);
+      else anySub = true;
+    }
+    if (cov && !nms.empty()) {
+      if (!anyIni) cov[COV_FALLBACK_CELLS]++;
+      else if (anySub) cov[COV_MIXED_CELLS]++;
+    }
   }
 
   struct KP { float x, y, size, angle, response; int octave; int lx, ly; };
@@ -330,6 +406,8 @@ struct OrbExtractor {
       const int maxBorderX = im.w - EDGE_THRESHOLD + 3;
       const int maxBorderY = im.h - EDGE_THRESHOLD + 3;
       std::vector<OrbCand> vToDistributeKeys;
+      int* cov = dbg[level].cov;
+      std::vector<int> cellOf((size_t)im.w * im.h, -1);   // coverage only: the cell that kept a corner at this pixel
       const float width = (float)(maxBorderX - minBorderX);
       const float height = (float)(maxBorderY - minBorderY);
       const int nCols = (int)(width / W);
@@ -340,24 +418,34 @@ struct OrbExtractor {
       for (int i = 0; i < nRows; i++) {
         const float iniY = (float)(minBorderY + i * hCell);
         float maxY = iniY + hCell + 6;
-        if (iniY >= maxBorderY - 3) continue;
-        if (maxY > maxBorderY) maxY = (float)maxBorderY;
+        if (iniY >= maxBorderY - 3) { cov[COV_SKIPPED_CELLS] += nCols; continue; }
+        bool clippedY = false;
+        if (maxY > maxBorderY) { maxY = (float)maxBorderY; clippedY = true; }
         for (int j = 0; j < nCols; j++) {
           const float iniX = (float)(minBorderX + j * wCell);
           float maxX = iniX + wCell + 6;
-          if (iniX >= maxBorderX - 6) continue;
-          if (maxX > maxBorderX) maxX = (float)maxBorderX;
+          if (iniX >= maxBorderX - 6) { cov[COV_SKIPPED_CELLS]++; continue; }
+          bool clipped = clippedY;
+          if (maxX > maxBorderX) { maxX = (float)maxBorderX; clipped = true; }
+          cov[COV_CLIPPED_CELLS] += clipped;
           std::vector<OrbCand> vKeysCell;
-          fastCell(im, (int)iniX, (int)iniY, (int)maxX, (int)maxY, iniThFAST, minThFAST, vKeysCell);
+          fastCell(im, (int)iniX, (int)iniY, (int)maxX, (int)maxY, iniThFAST, minThFAST, vKeysCell, cov);
           for (OrbCand c : vKeysCell) {
             c.x += j * wCell;
             c.y += i * hCell;
             vToDistributeKeys.push_back(c);
+            const int px = c.x + minBorderX, py = c.y + minBorderY, cell = i * nCols + j;
+            for (int dy = -1; dy <= 1; ++dy)
+              for (int dx = -1; dx <= 1; ++dx) {
+                const int o = cellOf[(size_t)(py + dy) * im.w + px + dx];
+                cov[COV_SEAM_PAIRS] += o >= 0 && o != cell;
+              }
+            cellOf[(size_t)py * im.w + px] = cell;
           }
         }
       }
       std::vector<int> sel = DistributeOctTree(vToDistributeKeys, minBorderX, maxBorderX, minBorderY,
-                                               maxBorderY, mnFeaturesPerLevel[level]);
+                                               maxBorderY, mnFeaturesPerLevel[level], cov);
       dbg[level].candidates = vToDistributeKeys;
       const int scaledPatchSize = (int)(PATCH_SIZE * mvScaleFactor[level]);
       for (int idx : sel) {

@@ -192,6 +192,20 @@ class Frame:
             self.L.orc_get_pyramid(self.h, eye, level, int(blurred), _p(out), C.byref(w), C.byref(h))
         return out
 
+    def orb_extract_lapping(self, eye, img, lapping):
+        """ORBextractor::operator() with vLappingArea = lapping: (n, mono count, keypoints, descriptors) in the mono-first /
+        lapping-from-the-back order of ORBextractor.cc:1135-1144."""
+        n, kp, desc = self.orb_extract(eye, img)
+        order, mono = lapping_order(kp, lapping[0], lapping[1])
+        return n, mono, kp[order], desc[order]
+
+    def level_coverage(self, eye, level):
+        """Branch counters of the last orb_extract for one level (OrbCoverage in orb_oracle.hpp), as {label: value}."""
+        self.L.orc_coverage_name.restype = C.c_char_p
+        out = np.zeros(64, np.int32)
+        n = self.L.orc_get_level_coverage(self.h, eye, level, _p(out), out.size)
+        return {self.L.orc_coverage_name(i).decode(): int(out[i]) for i in range(n)}
+
     def level_points(self, eye, level, selected=False):
         n = self.L.orc_get_level_points(self.h, eye, level, int(selected), None, 0)
         out = np.zeros((n, 3), np.int32)

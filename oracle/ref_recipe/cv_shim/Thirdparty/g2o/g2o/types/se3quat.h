@@ -1,0 +1,1 @@
+#include "pli_cv_shim.hpp"
