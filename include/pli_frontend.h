@@ -617,6 +617,37 @@ pli_status pli_search_for_triangulation(pli_ctx* ctx, const pli_keypoint* kp1, c
                                         const float* F12, const float* ep, int32_t only_stereo, int32_t coarse,
                                         int32_t check_orientation, int32_t* matches12, int32_t* nmatches);
 
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206, the branch
+ * pKF1->mpCamera2 && pKF2->mpCamera2 (a rig of two KannalaBrandt8 cameras, NLeft != -1), for one keyframe pKF1 against nkf
+ * neighbours pKF2[k] in one call.  A keyframe has N = NLeft + NRight features, the left camera's first: kp1 / desc1 / node1 /
+ * has_mp1 are n1 = N rows of pKF1 - mvKeys[i] for i < n1_left = NLeft, else mvKeysRight[i - NLeft] (:1048-1053; pt, octave, angle
+ * are read; NOT mvKeysUn), mDescriptors, the FeatureVector node that lists the feature (-1 = none), GetMapPoint(i) != nullptr.
+ * Neighbour k owns rows kf_off[k] .. kf_off[k+1]-1 of the four kf_* tables, laid out the same way with kf_nleft[k] = its NLeft.
+ * cam_left / cam_right: mpCamera / mpCamera2, shared by every keyframe of the call as the level tables are.  rel: nkf x 4 x 12
+ * floats, per neighbour the relative poses ll, lr, rl, rr of :995-1003 (host arithmetic), each R12 row major then t12; for a
+ * candidate pair (bRight1, bRight2) = (idx1 >= NLeft1, idx2 >= NLeft2) picks the pose and the two cameras (:1099-1129) and the
+ * gate is KannalaBrandt8::epipolarConstrain = TriangulateMatches(...) > 0.0001f (KannalaBrandt8.cpp:235-238, 334-403) with
+ * mvLevelSigma2 of the two octaves, evaluated on the device with the cv::Mat conventions of pli_stereo_fisheye.  There are no
+ * stereo tables, no F12 and no epipole: bStereo1 / bStereo2 are false whenever mpCamera2 is set (:1041, :1070) and the epipole
+ * gate is skipped (:1089).  For the same reason only_stereo != 0 matches nothing (:1043-1045 skips every feature of pKF1): every
+ * row is -1, every count 0, and nothing is launched.  coarse = bCoarse: the triangulation does not decide.  With
+ * check_orientation every angle must lie in [0, 360).
+ * matches12: nkf x n1, vMatches12 after the rotation filter, indices over the neighbour's N; nmatches[k] = the reference's return
+ * value.  Of equally distant candidates the last listed wins, as for pli_search_for_triangulation.
+ * Checked before anything is launched, PLI_ERR_INVALID: null pointers, n1_left outside [0, n1], kf_nleft[k] outside [0, n_k], a
+ * decreasing kf_off, an octave outside [0, orb_nlevels), a keypoint coordinate that is not finite, a value of rel that is not
+ * finite, with check_orientation an angle outside [0, 360).  PLI_ERR_CAPACITY for more than PLI_BOW_MAX_FEATURES rows in n1 or
+ * in a neighbour (nothing is truncated).  nkf == 0, n1 == 0, empty neighbours, n1_left == 0 and n1_left == n1 are valid.  The
+ * number of kernel launches does not depend on nkf. */
+pli_status pli_search_for_triangulation_two_cameras(pli_ctx* ctx, const pli_keypoint* kp1, const uint8_t* desc1,
+                                                    const int32_t* node1, const uint8_t* has_mp1, int32_t n1, int32_t n1_left,
+                                                    int32_t nkf, const int32_t* kf_off, const int32_t* kf_nleft,
+                                                    const pli_keypoint* kf_kp, const uint8_t* kf_desc, const int32_t* kf_node,
+                                                    const uint8_t* kf_has_mp, const pli_kb8_camera* cam_left,
+                                                    const pli_kb8_camera* cam_right, const float* rel, int32_t only_stereo,
+                                                    int32_t coarse, int32_t check_orientation, int32_t* matches12,
+                                                    int32_t* nmatches);
+
 /* The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) ORBmatcher.cc:1399-1609 (the branch bRight == false,
  * NLeft == -1, keypoints = mvKeysUn) and of the Sim3 overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) :1611-1733, for nmp map
  * points against nkf keyframes in one call (LocalMapping::SearchInNeighbors, LocalMapping.cc:743-749 and :776;

@@ -1,12 +1,15 @@
 // The two SearchByProjection forms of ORB_SLAM3::ORBmatcher that run on every tracked frame, for a frame of two cameras
-// (Frame::Nleft != -1, the fisheye-stereo rig): a matcher that is PliORBmatcher in everything else.
+// (Frame::Nleft != -1, the fisheye-stereo rig), and SearchForTriangulation for keyframes of two cameras (mpCamera2 set,
+// NLeft != -1): a matcher that is PliORBmatcher in everything else.
 //
 //   inside the PLI-SLAM tree:  using ORBmatcher = ORB_SLAM3::PliORBmatcherTwoCameras<Frame, MapPoint>;
 //
-// PliORBmatcher itself keeps refusing such frames (its users' Frame types need no second-camera members); this class hides
-// exactly two of its members and forwards both to it when the frame has one camera.
+// PliORBmatcher itself keeps refusing such frames and keyframes (its users' types need no second-camera members); this class
+// hides the members below and forwards each to it when the frame or every keyframe of the call has one camera.
 #pragma once
 #include "orbslam_adapters.hpp"
+#include <cstring>
+#include <utility>
 
 namespace ORB_SLAM3 {
 
@@ -22,6 +25,7 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
   PliORBmatcherTwoCameras(float nnratio = 0.6, bool checkOri = true) : Base(nnratio, checkOri) {}
 
   using Base::SearchByProjection;            // every other form stays visible; the two below hide theirs
+  using Base::SearchForTriangulation;        // likewise: both forms below hide theirs and forward to them
 
   // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono),
   // ORBmatcher.cc:1961-2177 (Tracking::TrackWithMotionModel, Tracking.cc:2961, :2969).  For CurrentFrame.Nleft != -1 the two
@@ -149,6 +153,104 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
     for (int k = 0; k < F.Nright; ++k)
       if (mpR[k] >= 0) F.mvpMapPoints[k + F.Nleft] = vpMapPoints[mpR[k]];    // :133, :206
     return nmatches;
+  }
+
+  // ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, vector<pair<size_t, size_t>>& vMatchedPairs,
+  // const bool bOnlyStereo, const bool bCoarse), ORBmatcher.cc:965-1206 (LocalMapping::CreateNewMapPoints, LocalMapping.cc:387-423;
+  // Tracking.cc:4705).  For keyframes with mpCamera2 the four relative poses of :995-1003 are the reference's own cv::Mat
+  // expressions, run here; the BoW-node walk and KannalaBrandt8::epipolarConstrain per candidate run on the device
+  // (pli_search_for_triangulation_two_cameras).  F12 is not read, as the reference does not read it.  KeyFrameT needs, beyond
+  // what PliORBmatcher::SearchForTriangulation reads when it is forwarded to: mvKeys, mvKeysRight, GetRightRotation(),
+  // GetRightTranslation(), and cameras with getParameter(i) and size() (GeometricCamera.h:77-80), the 8 KannalaBrandt8 parameters.
+  template <class KeyFrameT>
+  int SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat /*F12*/, std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
+                             const bool bOnlyStereo, const bool bCoarse = false) {
+    std::vector<std::vector<std::pair<size_t, size_t>>> pairs;
+    std::vector<int> nmatches;
+    SearchForTriangulation(pKF1, std::vector<KeyFrameT*>(1, pKF2), pairs, nmatches, bOnlyStereo, bCoarse);
+    vMatchedPairs.swap(pairs[0]);
+    return nmatches[0];
+  }
+
+  // (not in the reference) The same for every neighbour of vpKF2 in ONE device call, as the base's batch form.  Every keyframe
+  // of the call has two cameras with the same parameters, or none has (then the base's form runs); anything else throws.
+  template <class KeyFrameT>
+  void SearchForTriangulation(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2,
+                              std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, std::vector<int>& vnmatches,
+                              const bool bOnlyStereo, const bool bCoarse = false) {
+    const int nkf = (int)vpKF2.size();
+    int two = pKF1->mpCamera2 ? 1 : 0;
+    for (KeyFrameT* pKF2 : vpKF2) two += pKF2->mpCamera2 ? 1 : 0;
+    if (two == 0) {
+      Base::SearchForTriangulation(pKF1, vpKF2, vvMatchedPairs, vnmatches, bOnlyStereo, bCoarse);
+      return;
+    }
+    if (two != nkf + 1)     // (the reference multiplies by an empty R12 for such a pair)
+      throw std::logic_error("SearchForTriangulation: keyframes with and without mpCamera2 in one call are not supported");
+    struct Table : pli_detail::KfTable {
+      std::vector<pli_keypoint> kp;
+      std::vector<uint8_t> hasMp;
+      std::vector<int32_t> nleft;
+    };
+    auto cameras = [](KeyFrameT* pKF, pli_kb8_camera cam[2]) {
+      if (pKF->mpCamera->size() != 8 || pKF->mpCamera2->size() != 8)
+        throw std::logic_error("SearchForTriangulation: a keyframe of two cameras needs two KannalaBrandt8 cameras (8 parameters each)");
+      for (int e = 0; e < 2; ++e) {
+        float v[8];
+        for (int i = 0; i < 8; ++i) v[i] = e ? pKF->mpCamera2->getParameter(i) : pKF->mpCamera->getParameter(i);
+        cam[e] = pli_kb8_camera{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+      }
+    };
+    pli_kb8_camera cam[2];
+    cameras(pKF1, cam);
+    auto gather = [&](KeyFrameT* pKF, Table& T, const char* what) {
+      const int n = pKF->N, nl = pKF->NLeft;
+      if (nl < 0 || nl > n || (int)pKF->mvKeys.size() < nl || (int)pKF->mvKeysRight.size() < n - nl || pKF->mDescriptors.rows < n)
+        throw std::logic_error("SearchForTriangulation: a keyframe's tables do not hold NLeft + NRight rows");
+      pli_kb8_camera own[2];
+      cameras(pKF, own);
+      if (std::memcmp(own, cam, sizeof(own)) != 0)
+        throw std::logic_error("SearchForTriangulation: the keyframes of one call must share their camera parameters");
+      pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
+      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
+      for (int i = 0; i < n; ++i) {
+        T.kp.push_back(pli_detail::keypoint(i < nl ? pKF->mvKeys[i] : pKF->mvKeysRight[i - nl]));      // :1048-1050, :1083-1085
+        T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
+      }
+      T.nleft.push_back(nl);
+    };
+    Table T1, T2;
+    gather(pKF1, T1, "SearchForTriangulation: pKF1->mFeatVec");
+    const int n1 = pKF1->N;
+    std::vector<float> rel((size_t)nkf * 48 + 1);
+    for (int k = 0; k < nkf; ++k) {
+      KeyFrameT* pKF2 = vpKF2[k];
+      gather(pKF2, T2, "SearchForTriangulation: pKF2->mFeatVec");
+      const cv::Mat R[4] = {pKF1->GetRotation() * pKF2->GetRotation().t(), pKF1->GetRotation() * pKF2->GetRightRotation().t(),        // :995-998
+                            pKF1->GetRightRotation() * pKF2->GetRotation().t(), pKF1->GetRightRotation() * pKF2->GetRightRotation().t()};
+      const cv::Mat t[4] = {                                                                                                           // :1000-1003
+          pKF1->GetRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetTranslation(),
+          pKF1->GetRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetTranslation(),
+          pKF1->GetRightRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetRightTranslation(),
+          pKF1->GetRightRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetRightTranslation()};
+      for (int p = 0; p < 4; ++p) {
+        float* out = &rel[((size_t)k * 4 + p) * 12];
+        for (int i = 0; i < 3; ++i) {
+          for (int j = 0; j < 3; ++j) out[i * 3 + j] = R[p].template at<float>(i, j);
+          out[9 + i] = t[p].template at<float>(i);
+        }
+      }
+    }
+    std::vector<int> matches;
+    pli_detail::deviceContext("SearchForTriangulation")
+        ->searchForTriangulationTwoCameras(T1.kp.data(), T1.desc.data(), T1.node.data(), T1.hasMp.data(), n1, pKF1->NLeft, nkf,
+                                           T2.off.data(), T2.nleft.data(), T2.kp.data(), T2.desc.data(), T2.node.data(), T2.hasMp.data(),
+                                           cam[0], cam[1], rel.data(), bOnlyStereo, bCoarse, this->mbCheckOrientation, matches, vnmatches);
+    vvMatchedPairs.assign((size_t)nkf, std::vector<std::pair<size_t, size_t>>());
+    for (int k = 0; k < nkf; ++k) vvMatchedPairs[k].reserve(vnmatches[k]);
+    pli_detail::forEachMatch(matches, nkf, n1, [&](int k, int i, int j) {      // vMatches12 read in index order (:1198-1203)
+      vvMatchedPairs[k].push_back(std::make_pair((size_t)i, (size_t)j));
+    });
   }
 
  private:

@@ -163,6 +163,22 @@ class Frontend {
                                        kfStereo, F12, ep, onlyStereo ? 1 : 0, coarse ? 1 : 0, checkOrientation ? 1 : 0,
                                        matches12.data(), nmatches.data()));
   }
+  // ORBmatcher::SearchForTriangulation ORBmatcher.cc:965-1206, the branch of keyframes with two KannalaBrandt8 cameras, of one
+  // keyframe against nkf neighbours (include/pli_frontend.h pli_search_for_triangulation_two_cameras): the tables hold the left
+  // camera's features first (n1Left / kfNleft = NLeft), rel = nkf x 4 x 12 floats (ll, lr, rl, rr: R12 row major, then t12);
+  // matches12 (nkf x n1) = the neighbour's feature, over its N, each feature of pKF1 is matched to or -1
+  void searchForTriangulationTwoCameras(const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1, const uint8_t* hasMp1,
+                                        int n1, int n1Left, int nkf, const int32_t* kfOff, const int32_t* kfNleft,
+                                        const pli_keypoint* kfKp, const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
+                                        const pli_kb8_camera& camLeft, const pli_kb8_camera& camRight, const float* rel,
+                                        bool onlyStereo, bool coarse, bool checkOrientation, std::vector<int>& matches12,
+                                        std::vector<int>& nmatches) {
+    matches12.assign((size_t)nkf * n1, -1);
+    nmatches.assign(nkf, 0);
+    check(pli_search_for_triangulation_two_cameras(ctx_, kp1, desc1, node1, hasMp1, n1, n1Left, nkf, kfOff, kfNleft, kfKp, kfDesc,
+                                                   kfNode, kfHasMp, &camLeft, &camRight, rel, onlyStereo ? 1 : 0, coarse ? 1 : 0,
+                                                   checkOrientation ? 1 : 0, matches12.data(), nmatches.data()));
+  }
   // The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reprojGate = false: the Sim3 overload
   // :1611-1733) of nmp map points against nkf keyframes (include/pli_frontend.h pli_fuse_search): bestIdx (nkf x nmp) = the
   // keyframe's row or -1.  levelRatio: fuseLevelRatio() of the extractor's configuration.

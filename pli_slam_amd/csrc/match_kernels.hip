@@ -13,6 +13,7 @@
 //   k_track_queries/candidates/assign/lines   frame-to-frame track matching of a batch (pli_batch_track)
 //   k_node_sort + k_search_by_bow       ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 //   k_node_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
+//   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_tri_finish  the same for keyframes of two KannalaBrandt8 cameras (mpCamera2)
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 //   k_fuse_grid, k_sim3_project, k_sim3_candidates, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
@@ -2400,27 +2401,20 @@ __device__ __forceinline__ void jacobi_svd_last_vt4(float At[4][4], float out[4]
       for (int k = 0; k < 4; k++) out[k] = Vt[r][k];
 }
 
-__global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* __restrict__ kpL, const pli_keypoint* __restrict__ kpR,
-                                                            const int* __restrict__ knnIdx, const int* __restrict__ knnDist, int nl, int nr,
-                                                            int monoL, int monoR, Kb8 c1, Kb8 c2, const float* __restrict__ R12t12,
-                                                            const float* __restrict__ sigma2, int* __restrict__ l2r, int* __restrict__ r2l,
-                                                            float* __restrict__ depth, float* __restrict__ p3d, int* __restrict__ nmatches) {
-  const int i = blockIdx.x * 64 + threadIdx.x;          // index into the lapping-area (stereo) part of the left table
-  if (i >= nl || nr < 2) return;                        // (*it).size() >= 2
-  const int d0 = knnDist[2 * i], d1 = knnDist[2 * i + 1], j = knnIdx[2 * i];
-  if (!((double)(float)d0 < (double)(float)d1 * 0.7)) return;
-  const pli_keypoint k1 = kpL[monoL + i], k2 = kpR[monoR + j];
-  const float* R12 = R12t12;
-  const float* t12 = R12t12 + 9;
-  float r1[3], r2[3], r21[3];
-  kb8_unproject(c1, k1.x, k1.y, r1);
-  kb8_unproject(c2, k2.x, k2.y, r2);
+// KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:338-402) from the two unprojected rays on: the parallax test, the linear
+// triangulation, both depths and both reprojection gates, the same operations in the same order for every caller.  (x1, y1) and
+// (x2, y2) are the keypoints' coordinates, sigmaLevel / unc their mvLevelSigma2.  Returns z1 and x3 = x3D, or -1 as the reference
+// does (x3 is then not meaningful); the caller applies its own floor on the depth (Frame.cc:1609, KannalaBrandt8.cpp:237).
+__device__ __forceinline__ float kb8_triangulate_rays(const Kb8& c1, const Kb8& c2, const float r1[3], const float r2[3], float x1,
+                                                      float y1, float x2, float y2, const float* __restrict__ R12,
+                                                      const float* __restrict__ t12, float sigmaLevel, float unc, float x3[3]) {
+  float r21[3];
   for (int a = 0; a < 3; ++a) r21[a] = cvmat_dot3(R12 + 3 * a, 1, r2, 1.0, 0.0);
   const double dot = (double)r1[0] * r21[0] + (double)r1[1] * r21[1] + (double)r1[2] * r21[2];
   const double n1 = sqrt((double)r1[0] * r1[0] + (double)r1[1] * r1[1] + (double)r1[2] * r1[2]);
   const double n2 = sqrt((double)r21[0] * r21[0] + (double)r21[1] * r21[1] + (double)r21[2] * r21[2]);
   const float cosPar = (float)(dot / (n1 * n2));
-  if ((double)cosPar > 0.9998) return;
+  if ((double)cosPar > 0.9998) return -1.f;
   // Tcw1 = [I | 0], Tcw2 = [R21 | t21] with R21 = R12^T, t21 = -R21 t12
   float R21[9], t21[3];
   for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) R21[3 * a + b] = R12[3 * b + a];
@@ -2438,27 +2432,157 @@ __global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* 
   float vh[4];
   jacobi_svd_last_vt4(At, vh);
   const float inv = (float)(1.0 / (double)vh[3]);
-  const float x3[3] = {vh[0] * inv + 0.f, vh[1] * inv + 0.f, vh[2] * inv + 0.f};
+  x3[0] = vh[0] * inv + 0.f; x3[1] = vh[1] * inv + 0.f; x3[2] = vh[2] * inv + 0.f;
   const float z1 = x3[2];
-  if (!(z1 > 0)) return;                                // z1 <= 0 (or NaN: `depth > 0.0001f` fails for it below in the reference)
+  if (!(z1 > 0)) return -1.f;                           // z1 <= 0 (or NaN: the callers' `depth > 0.0001f` fails for it in the reference)
   const float z2 = (float)(((double)R21[6] * x3[0] + (double)R21[7] * x3[1] + (double)R21[8] * x3[2]) + (double)t21[2]);
-  if (z2 <= 0) return;
+  if (z2 <= 0) return -1.f;
   float u1, v1;
   kb8_project(c1, x3, u1, v1);
-  const float ex1 = u1 - k1.x, ey1 = v1 - k1.y;
-  if ((double)(ex1 * ex1 + ey1 * ey1) > 5.991 * (double)sigma2[k1.octave]) return;
+  const float ex1 = u1 - x1, ey1 = v1 - y1;
+  if ((double)(ex1 * ex1 + ey1 * ey1) > 5.991 * (double)sigmaLevel) return -1.f;
   float x32[3];
   for (int a = 0; a < 3; ++a) x32[a] = cvmat_dot3(R21 + 3 * a, 1, x3, 1.0, (double)t21[a]);
   float u2, v2;
   kb8_project(c2, x32, u2, v2);
-  const float ex2 = u2 - k2.x, ey2 = v2 - k2.y;
-  if ((double)(ex2 * ex2 + ey2 * ey2) > 5.991 * (double)sigma2[k2.octave]) return;
+  const float ex2 = u2 - x2, ey2 = v2 - y2;
+  if ((double)(ex2 * ex2 + ey2 * ey2) > 5.991 * (double)unc) return -1.f;
+  return z1;
+}
+
+__global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* __restrict__ kpL, const pli_keypoint* __restrict__ kpR,
+                                                            const int* __restrict__ knnIdx, const int* __restrict__ knnDist, int nl, int nr,
+                                                            int monoL, int monoR, Kb8 c1, Kb8 c2, const float* __restrict__ R12t12,
+                                                            const float* __restrict__ sigma2, int* __restrict__ l2r, int* __restrict__ r2l,
+                                                            float* __restrict__ depth, float* __restrict__ p3d, int* __restrict__ nmatches) {
+  const int i = blockIdx.x * 64 + threadIdx.x;          // index into the lapping-area (stereo) part of the left table
+  if (i >= nl || nr < 2) return;                        // (*it).size() >= 2
+  const int d0 = knnDist[2 * i], d1 = knnDist[2 * i + 1], j = knnIdx[2 * i];
+  if (!((double)(float)d0 < (double)(float)d1 * 0.7)) return;
+  const pli_keypoint k1 = kpL[monoL + i], k2 = kpR[monoR + j];
+  float r1[3], r2[3], x3[3];
+  kb8_unproject(c1, k1.x, k1.y, r1);
+  kb8_unproject(c2, k2.x, k2.y, r2);
+  const float z1 = kb8_triangulate_rays(c1, c2, r1, r2, k1.x, k1.y, k2.x, k2.y, R12t12, R12t12 + 9, sigma2[k1.octave], sigma2[k2.octave],
+                                        x3);
   if (!(z1 > 0.0001f)) return;
   l2r[monoL + i] = monoR + j;
   atomicMax(&r2l[monoR + j], monoL + i);        // the reference's loop overwrites: the LAST left keypoint that takes a right one stays
   depth[monoL + i] = z1;
   p3d[3 * (monoL + i)] = x3[0]; p3d[3 * (monoL + i) + 1] = x3[1]; p3d[3 * (monoL + i) + 2] = x3[2];
   atomicAdd(nmatches, 1);
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206), the branch pKF1->mpCamera2 && pKF2->mpCamera2 (a rig of two
+// KannalaBrandt8 cameras, NLeft != -1): a keyframe's N = NLeft + NRight features are the left camera's first, their keypoints
+// mvKeys / mvKeysRight (:1048-1053, :1083-1087), and the gate of a candidate pair is KannalaBrandt8::epipolarConstrain
+// (KannalaBrandt8.cpp:235-238) = TriangulateMatches(...) > 0.0001f with the relative pose and the two cameras that
+// (bRight1, bRight2) pick (:1099-1129).  bStereo1 / bStereo2 are false (:1041, :1070) and the epipole gate is skipped (:1089).
+// What k_tri_match's header says about vbMatched2 and the key holds unchanged.
+//
+//   k_kb8_rays          one thread per feature of pKF1 and of every neighbour: its ray, KannalaBrandt8::unproject with the camera
+//                       of its side.  The ray depends on the keypoint and its own camera only, so the Newton steps and the tan
+//                       leave the candidate loop; the stored floats are the ones TriangulateMatches would compute again.
+//   k_node_sort         (above) as for k_tri_match, without the stereo flag.
+//   k_tri_match_kb8     k_tri_match's shape: one wave per idx1, the lanes stride over the node's run; Hamming distance and TH_LOW
+//                       first (:1080), then, in the lane that holds the survivor, the gate; the wave minimum of the key.
+//   k_tri_finish        (above) unchanged.
+// ---------------------------------------------------------------------------
+// grid = ceil((n1 + total) / 256): item i < n1 is feature i of pKF1, the others the neighbours' rows in table order
+__global__ __launch_bounds__(256) void k_kb8_rays(const pli_keypoint* __restrict__ kp1, int n1, int n1Left,
+                                                  const pli_keypoint* __restrict__ kfKp, const int* __restrict__ kfOff,
+                                                  const int* __restrict__ kfNleft, int nkf, Kb8 camL, Kb8 camR,
+                                                  float2* __restrict__ ray1, float2* __restrict__ kfRay) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int total = kfOff[nkf];
+  if (i >= n1 + total) return;
+  pli_keypoint k;
+  bool right;
+  if (i < n1) {
+    k = kp1[i];
+    right = i >= n1Left;
+  } else {
+    const int row = i - n1;
+    int lo = 0, hi = nkf;                                // the neighbour that owns the row: the last k with kfOff[k] <= row
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (kfOff[mid] <= row) lo = mid;
+      else hi = mid;
+    }
+    k = kfKp[row];
+    right = row - kfOff[lo] >= kfNleft[lo];
+  }
+  float r[3];
+  if (right) kb8_unproject(camR, k.x, k.y, r);
+  else kb8_unproject(camL, k.x, k.y, r);
+  if (i < n1) ray1[i] = make_float2(r[0], r[1]);
+  else kfRay[i - n1] = make_float2(r[0], r[1]);
+}
+
+// grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours); rel: per neighbour ll, lr, rl, rr, each R12 row major then t12
+__global__ __launch_bounds__(256) void k_tri_match_kb8(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
+                                                       const int* __restrict__ node1, const uint8_t* __restrict__ hasMp1,
+                                                       const float2* __restrict__ ray1, int n1, int n1Left,
+                                                       const int* __restrict__ kfOff, const int* __restrict__ kfNleft,
+                                                       const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                       const float2* __restrict__ kfRay, const uint32_t* __restrict__ sNode,
+                                                       const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
+                                                       const float* __restrict__ rel, Kb8 camL, Kb8 camR,
+                                                       const float* __restrict__ sigma2, int coarse, int checkOri,
+                                                       int* __restrict__ matches12, int* __restrict__ stat) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int kf = blockIdx.y, base = kfOff[kf], nl = nListed[kf], nleft2 = kfNleft[kf];
+  const uint32_t* sn = sNode + base;
+  const uint16_t* si = sIdx + base;
+  const int first = (blockIdx.x * nwaves + wave) * TRI_PER_WAVE;
+  for (int idx1 = first; idx1 < min(first + TRI_PER_WAVE, n1); ++idx1) {
+    int best = -1;
+    const int node = node1[idx1];
+    if (node >= 0 && !hasMp1[idx1]) {                              // :1036-1039 (a feature in no node is never visited)
+      const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
+      if (lo < nl && sn[lo] == (uint32_t)node) {
+        const int hi = bow_lower_bound(sn, lo + 1, nl, (uint32_t)node + 1u);
+        const pli_keypoint k1 = kp1[idx1];
+        const bool right1 = idx1 >= n1Left;                        // :1052
+        const float2 q1 = ray1[idx1];
+        const float r1[3] = {q1.x, q1.y, 1.f};
+        const float s1 = sigma2[k1.octave];
+        uint64_t d1[4];
+        load_desc(desc1 + (int64_t)idx1 * 32, d1);
+        unsigned long long k = ~0ull;
+        for (int t = lo + lane; t < hi; t += 64) {
+          const int idx2 = si[t];
+          uint64_t d2[4];
+          load_desc(kfDesc + (int64_t)(base + idx2) * 32, d2);
+          const int dist = hamming256(d1, d2);
+          if (dist > BOW_TH_LOW) continue;                         // :1080 (dist > bestDist: the key's minimum)
+          if (!coarse) {                                           // :1099-1132
+            const pli_keypoint k2 = kfKp[base + idx2];
+            const bool right2 = idx2 >= nleft2;                    // :1086
+            const float2 q2 = kfRay[base + idx2];
+            const float r2[3] = {q2.x, q2.y, 1.f};
+            const float* Rt = rel + ((int64_t)kf * 4 + (right1 ? 2 : 0) + (right2 ? 1 : 0)) * 12;
+            float x3[3];
+            const float z1 = kb8_triangulate_rays(right1 ? camR : camL, right2 ? camR : camL, r1, r2, k1.x, k1.y, k2.x, k2.y, Rt, Rt + 9,
+                                                  s1, sigma2[k2.octave], x3);
+            if (!(z1 > 0.0001f)) continue;                         // KannalaBrandt8.cpp:237
+          }
+          const unsigned long long kk = ((unsigned long long)dist << 32) | (0xFFFFFFFFu - (unsigned)idx2);
+          k = kk < k ? kk : k;
+        }
+        k = wave_min_u64(k);
+        if (k != ~0ull) best = (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
+      }
+    }
+    if (lane == 0) {
+      matches12[(int64_t)kf * n1 + idx1] = best;
+      if (best >= 0) {
+        atomicAdd(&stat[kf * TRI_STAT + 30], 1);
+        if (checkOri) atomicAdd(&stat[kf * TRI_STAT + bow_rot_bin(kp1[idx1].angle, kfKp[base + best].angle)], 1);
+      }
+    }
+  }
 }
 
 __global__ void k_fill_f32(float* __restrict__ dst, int n, float v) {

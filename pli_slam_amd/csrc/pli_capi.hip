@@ -3052,6 +3052,106 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   return PLI_OK;
 }
 
+pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                                    const uint8_t* hasMp1, int32_t n1, int32_t n1Left, int32_t nkf,
+                                                    const int32_t* kfOff, const int32_t* kfNleft, const pli_keypoint* kfKp,
+                                                    const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
+                                                    const pli_kb8_camera* camLeft, const pli_kb8_camera* camRight, const float* rel,
+                                                    int32_t onlyStereo, int32_t coarse, int32_t checkOri, int32_t* matches12,
+                                                    int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || nkf < 0 || !camLeft || !camRight || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1)) ||
+      (nkf > 0 && (!kfOff || !kfNleft || !rel || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (n1Left < 0 || n1Left > n1) { g_err = "n1_left outside [0, n1]"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the SearchForTriangulation cap", B);
+  if (st != PLI_OK) return st;
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = B.total;
+  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  for (int k = 0; k < nkf; ++k)
+    if (kfNleft[k] < 0 || kfNleft[k] > kfOff[k + 1] - kfOff[k]) { g_err = "kf_nleft outside [0, the neighbour's rows]"; return PLI_ERR_INVALID; }
+  // the gate projects with the coordinates and indexes mvLevelSigma2 by the octaves: the rule of pli_stereo_fisheye_tables
+  auto finiteOk = [](const pli_keypoint* kp, int64_t n, const char* what) {
+    for (int64_t i = 0; i < n; ++i)
+      if (!std::isfinite(kp[i].x) || !std::isfinite(kp[i].y)) { g_err = std::string(what) + ": a keypoint's coordinates are not finite"; return false; }
+    return true;
+  };
+  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || !finiteOk(kp1, n1, "kp1") ||
+      (checkOri && !anglesOk(kp1, n1, "kp1: angle")))
+    return PLI_ERR_INVALID;
+  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp") ||
+      (checkOri && !anglesOk(kfKp, total, "kf_kp: angle")))
+    return PLI_ERR_INVALID;
+  for (int64_t i = 0; i < (int64_t)nkf * 48; ++i)
+    if (!std::isfinite(rel[i])) { g_err = "rel: a relative pose is not finite"; return PLI_ERR_INVALID; }
+  std::fill(nmatches, nmatches + nkf, 0);
+  if (n1 == 0) return PLI_OK;
+  if (onlyStereo) {                                         // bStereo1 is false for every feature (:1041): :1043-1045 skips them all
+    std::fill(matches12, matches12 + (size_t)nkf * n1, -1);
+    return PLI_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto dK1 = plan.add<pli_keypoint>(n1);
+  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
+  auto dN1 = plan.add<int>(n1);
+  auto dM1 = plan.add<uint8_t>(n1);
+  auto dR1 = plan.add<float2>(n1);
+  auto dOff = plan.add<int>((size_t)nkf + 1);
+  auto dNl = plan.add<int>(nkf);
+  auto dKk = plan.add<pli_keypoint>(total);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dKn = plan.add<int>(total);
+  auto dKm = plan.add<uint8_t>(total);
+  auto dKr = plan.add<float2>(total);
+  auto dSn = plan.add<uint32_t>(total);
+  auto dSi = plan.add<uint16_t>(total);
+  auto dListed = plan.add<int>(nkf);
+  auto dRel = plan.add<float>((size_t)nkf * 48);
+  auto dLv = plan.add<float>(MAX_LEVELS);                  // mvLevelSigma2
+  auto dStat = plan.add<int>((size_t)nkf * 32);            // per neighbour: 30 histogram bins, [30] the match counter
+  auto dM = plan.add<int>((size_t)nkf * n1);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  float hlv[MAX_LEVELS] = {};
+  levelTables(c, nullptr, hlv, nullptr);
+  HIPCHK(upload(c, dK1, kp1, n1));
+  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
+  HIPCHK(upload(c, dN1, node1, n1));
+  HIPCHK(upload(c, dM1, hasMp1, n1));
+  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
+  HIPCHK(upload(c, dNl, kfNleft, nkf));
+  HIPCHK(upload(c, dKk, kfKp, total));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  HIPCHK(upload(c, dKn, kfNode, total));
+  HIPCHK(upload(c, dKm, kfHasMp, total));
+  HIPCHK(upload(c, dRel, rel, (size_t)nkf * 48));
+  HIPCHK(upload(c, dLv, (const float*)hlv, MAX_LEVELS));
+  Kb8 cl, cr;
+  memcpy(&cl, camLeft, sizeof(cl));
+  memcpy(&cr, camRight, sizeof(cr));
+  const int keyCap = pow2Ceil(B.maxNk);
+  const int perBlock = 4 * 4;                                            // k_tri_match_kb8: 4 waves x TRI_PER_WAVE features of pKF1
+  const int64_t nray = (int64_t)n1 + total;
+  if (!coarse)                                                           // (bCoarse: the gate, the only reader of the rays, does not run)
+    LAUNCH(c, "k_kb8_rays", k_kb8_rays, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, (const pli_keypoint*)dK1, n1, n1Left,
+           (const pli_keypoint*)dKk, (const int*)dOff, (const int*)dNl, nkf, cl, cr, (float2*)dR1, (float2*)dKr);
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, 0, dKn, dKm, 0, (const uint8_t*)nullptr, 0, keyCap,
+         dSn, dSi, dListed, dStat);
+  LAUNCH(c, "k_tri_match_kb8", k_tri_match_kb8, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1,
+         (const float2*)dR1, n1, n1Left, dOff, (const int*)dNl, dKk, dKd, (const float2*)dKr, dSn, dSi, dListed, (const float*)dRel, cl, cr,
+         (const float*)dLv, coarse ? 1 : 0, checkOri ? 1 : 0, dM, dStat);
+  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
+  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
+  std::vector<int> hstat((size_t)nkf * 32);
+  HIPCHK(download(c, hstat.data(), dStat, (size_t)nkf * 32));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
+  return PLI_OK;
+}
+
 pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf, const int32_t* kfOff,
                            const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfUright, const float* kfPose,
                            const uint8_t* skip, const pli_fuse_camera* cam, float th, const float* levelRatio, int32_t reprojGate,

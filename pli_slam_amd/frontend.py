@@ -292,6 +292,30 @@ class Frontend:
                                                   ptr(nmatches)))
         return matches, nmatches
 
+    def search_for_triangulation_two_cameras(self, kf1, kfs, cam_left, cam_right, coarse=False, check_orientation=False,
+                                             only_stereo=False):
+        """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206), the branch of keyframes with two KannalaBrandt8 cameras
+        (mpCamera2 set, NLeft != -1), of keyframe `kf1` against every neighbour of `kfs`, in one call.  kf1: (kp, desc, node,
+        has_mp, nleft) - mvKeys then mvKeysRight as KEYPOINT_DT rows, mDescriptors, the FeatureVector node that lists a feature
+        (-1: none), map point set, NLeft; kfs: list of (kp, desc, node, has_mp, nleft, rel[4, 12]) per neighbour, rel = the
+        relative poses ll, lr, rl, rr (R12 row major, then t12).  cam_left / cam_right: the 8 KannalaBrandt8 parameters of
+        mpCamera / mpCamera2.  Returns (matches12[nkf, n1]: the neighbour's feature, over its N, that feature i of kf1 is matched
+        to or -1, nmatches[nkf])."""
+        what = "every feature needs one keypoint, descriptor, node and has_mp flag"
+        k1, d1, n1, m1 = pack_keyframes([kf1], TRI_COLUMNS[:4], what)[1]
+        nkf = len(kfs)
+        off, (kk, kd, kn, km) = pack_keyframes(kfs, TRI_COLUMNS[:4], what)
+        nleft = np.ascontiguousarray([int(kf[4]) for kf in kfs], np.int32).reshape(nkf)
+        rel = np.ascontiguousarray([np.asarray(kf[5], np.float32).reshape(48) for kf in kfs], np.float32).reshape(nkf, 48)
+        cl, cr = np.ascontiguousarray(cam_left, np.float32).reshape(8), np.ascontiguousarray(cam_right, np.float32).reshape(8)
+        matches = np.full((nkf, len(n1)), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        check(self.L.pli_search_for_triangulation_two_cameras(self.h, ptr(k1), ptr(d1), ptr(n1), ptr(m1), len(n1), int(kf1[4]), nkf,
+                                                              ptr(off), ptr(nleft), ptr(kk), ptr(kd), ptr(kn), ptr(km), ptr(cl),
+                                                              ptr(cr), ptr(rel), int(only_stereo), int(coarse),
+                                                              int(check_orientation), ptr(matches), ptr(nmatches)))
+        return matches, nmatches
+
     def fuse_search(self, points, descs, keyframes, cam, th=3.0, reproj_gate=True, skip=None, level_ratio=None):
         """The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reproj_gate=False: the Sim3
         overload :1611-1733) of the map points `points` (capi.FUSE_POINT_DT rows) with descriptors `descs` against every keyframe
