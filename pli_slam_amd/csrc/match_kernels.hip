@@ -16,8 +16,8 @@
 //   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_tri_finish  the same for keyframes of two KannalaBrandt8 cameras (mpCamera2)
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
-//   k_fuse_grid, k_sim3_project, k_sim3_candidates, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
-//   k_fuse_grid, k_reloc_project, k_reloc_candidates, k_reloc_assign  ORBmatcher::SearchByProjection(Frame, KF, sAlreadyFound, ...) (ORBmatcher.cc:2325-2447)
+//   k_fuse_grid, k_sim3_project, k_window_candidates<0>, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
+//   k_fuse_grid, k_reloc_project, k_window_candidates<1>, k_reloc_assign  ORBmatcher::SearchByProjection(Frame, KF, sAlreadyFound, ...) (ORBmatcher.cc:2325-2447)
 //   k_fuse_grid, k_init_candidates, k_init_assign  ORBmatcher::SearchForInitialization (ORBmatcher.cc:706-821)
 #include "kernels.hpp"
 #include "device_prims.hpp"
@@ -1381,46 +1381,42 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
 //
 //   k_node_sort    (above) one workgroup per neighbour: its features that may be taken (listed in a node, no map point, stereo
 //                  when bOnlyStereo) sorted by node id, the others last; also clears the neighbour's histogram and counter.
-//   k_tri_match    grid (slices of pKF1, neighbours), one wave per idx1: a binary search finds the node's run in the neighbour's
-//                  sorted list, the lanes stride over it (Hamming distance, TH_LOW, the epipole gate :1089-1097, the epipolar
-//                  gate Pinhole.cpp:130-143 on the host's F12), a wave minimum of the key picks the winner; lane 0 writes
-//                  vMatches12[idx1] and adds to the neighbour's 30-bin rotation histogram and counter (global atomics).
+//   k_tri_match    grid (slices of pKF1, neighbours), one wave per idx1, tri_match_body: a binary search finds the node's run in
+//                  the neighbour's sorted list, the lanes stride over it (Hamming distance, TH_LOW, then TriPinholeGate: the
+//                  epipole gate :1089-1097, the epipolar gate Pinhole.cpp:130-143 on the host's F12), a wave minimum of the key
+//                  picks the winner; lane 0 writes vMatches12[idx1] and adds to the neighbour's 30-bin rotation histogram and
+//                  counter (global atomics).
 //   k_tri_finish   (mbCheckOrientation only) one workgroup per neighbour: three_maxima on the histogram, then
 //                  the row is filtered (a match's bin is recomputed from the two angles) and the return value corrected.
 // ---------------------------------------------------------------------------
-// grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours)
 constexpr int TRI_PER_WAVE = 4;
-__global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
-                                                   const int* __restrict__ node1, const uint8_t* __restrict__ hasMp1,
-                                                   const uint8_t* __restrict__ stereo1, int n1, const int* __restrict__ kfOff,
-                                                   const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
-                                                   const uint8_t* __restrict__ kfStereo, const uint32_t* __restrict__ sNode,
-                                                   const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
-                                                   const float* __restrict__ F12, const float* __restrict__ ep,
-                                                   const float* __restrict__ scaleFactor, const float* __restrict__ sigma2,
-                                                   int onlyStereo, int coarse, int checkOri, int* __restrict__ matches12,
-                                                   int* __restrict__ stat) {
+
+// What k_tri_match and k_tri_match_kb8 share: one wave per idx1 of pKF1 against neighbour blockIdx.y (rows base ..), the node's
+// run in the neighbour's sorted list, the lanes striding over it, Hamming distance and TH_LOW first (:1080), the wave minimum of the
+// key, and lane 0's epilogue (vMatches12[idx1], the neighbour's counter and rotation histogram).  The gate is the kernel's own:
+//   gate.admits(idx1)      whether idx1 is searched at all (:1036-1045),
+//   gate.begin(idx1, k1)   what depends on idx1 only,
+//   gate.keeps(idx2)       whether the candidate idx2 of the neighbour, already within TH_LOW, stays.
+template <class Gate>
+__device__ __forceinline__ void tri_match_body(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
+                                               const int* __restrict__ node1, int n1, int base,
+                                               const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                               const uint32_t* __restrict__ sNode, const uint16_t* __restrict__ sIdx,
+                                               const int* __restrict__ nListed, int checkOri, int* __restrict__ matches12,
+                                               int* __restrict__ stat, Gate& gate) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const int kf = blockIdx.y, base = kfOff[kf], nl = nListed[kf];
-  const float* F = F12 + kf * 9;
-  const float epx = ep[kf * 2], epy = ep[kf * 2 + 1];
+  const int kf = blockIdx.y, nl = nListed[kf];
   const uint32_t* sn = sNode + base;
   const uint16_t* si = sIdx + base;
   const int first = (blockIdx.x * nwaves + wave) * TRI_PER_WAVE;
   for (int idx1 = first; idx1 < min(first + TRI_PER_WAVE, n1); ++idx1) {
     int best = -1;
     const int node = node1[idx1];
-    const bool st1 = stereo1[idx1] != 0;
-    if (node >= 0 && !hasMp1[idx1] && (!onlyStereo || st1)) {       // :1036-1045 (a feature in no node is never visited)
+    if (node >= 0 && gate.admits(idx1)) {                          // (a feature in no node is never visited)
       const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
       if (lo < nl && sn[lo] == (uint32_t)node) {
         const int hi = bow_lower_bound(sn, lo + 1, nl, (uint32_t)node + 1u);
-        const pli_keypoint k1 = kp1[idx1];
-        // the epipolar line in the second image, l = x1' F12 = [a b c] (Pinhole.cpp:130-132)
-        const float a = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[0]), __fmul_rn(k1.y, F[3])), F[6]);
-        const float b = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[1]), __fmul_rn(k1.y, F[4])), F[7]);
-        const float c = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[2]), __fmul_rn(k1.y, F[5])), F[8]);
-        const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+        gate.begin(idx1, kp1[idx1]);
         uint64_t d1[4];
         load_desc(desc1 + (int64_t)idx1 * 32, d1);
         unsigned long long k = ~0ull;
@@ -1430,17 +1426,7 @@ __global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restric
           load_desc(kfDesc + (int64_t)(base + idx2) * 32, d2);
           const int dist = hamming256(d1, d2);
           if (dist > BOW_TH_LOW) continue;                         // :1080 (dist > bestDist: the key's minimum)
-          const pli_keypoint k2 = kfKp[base + idx2];
-          if (!st1 && !kfStereo[base + idx2]) {                    // :1089-1097
-            const float ex = __fsub_rn(epx, k2.x), ey = __fsub_rn(epy, k2.y);
-            if (__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)) < __fmul_rn(100.0f, scaleFactor[k2.octave])) continue;
-          }
-          if (!coarse) {                                           // Pinhole.cpp:134-143
-            const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, k2.x), __fmul_rn(b, k2.y)), c);
-            if (den == 0.0f) continue;
-            const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-            if (!((double)dsqr < 3.84 * (double)sigma2[k2.octave])) continue;
-          }
+          if (!gate.keeps(idx2)) continue;
           const unsigned long long kk = ((unsigned long long)dist << 32) | (0xFFFFFFFFu - (unsigned)idx2);
           k = kk < k ? kk : k;
         }
@@ -1456,6 +1442,59 @@ __global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restric
       }
     }
   }
+}
+
+// the pinhole gates: bOnlyStereo (:1043-1045), the epipole gate :1089-1097, the epipolar gate Pinhole.cpp:130-143 on the host's F12
+struct TriPinholeGate {
+  const uint8_t *__restrict__ hasMp1, *__restrict__ stereo1, *__restrict__ kfStereo;
+  const pli_keypoint* __restrict__ kfKp;
+  const float *__restrict__ F, *__restrict__ scaleFactor, *__restrict__ sigma2;
+  float epx, epy;
+  int base, onlyStereo, coarse;
+  bool st1;                                                        // of idx1 (admits, begin):
+  float a, b, c, den;
+  __device__ __forceinline__ bool admits(int idx1) {
+    st1 = stereo1[idx1] != 0;
+    return !hasMp1[idx1] && (!onlyStereo || st1);                  // :1036-1045
+  }
+  __device__ __forceinline__ void begin(int, const pli_keypoint& k1) {
+    // the epipolar line in the second image, l = x1' F12 = [a b c] (Pinhole.cpp:130-132)
+    a = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[0]), __fmul_rn(k1.y, F[3])), F[6]);
+    b = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[1]), __fmul_rn(k1.y, F[4])), F[7]);
+    c = __fadd_rn(__fadd_rn(__fmul_rn(k1.x, F[2]), __fmul_rn(k1.y, F[5])), F[8]);
+    den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+  }
+  __device__ __forceinline__ bool keeps(int idx2) const {
+    const pli_keypoint k2 = kfKp[base + idx2];
+    if (!st1 && !kfStereo[base + idx2]) {                          // :1089-1097
+      const float ex = __fsub_rn(epx, k2.x), ey = __fsub_rn(epy, k2.y);
+      if (__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)) < __fmul_rn(100.0f, scaleFactor[k2.octave])) return false;
+    }
+    if (!coarse) {                                                 // Pinhole.cpp:134-143
+      const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, k2.x), __fmul_rn(b, k2.y)), c);
+      if (den == 0.0f) return false;
+      const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
+      if (!((double)dsqr < 3.84 * (double)sigma2[k2.octave])) return false;
+    }
+    return true;
+  }
+};
+
+// grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours)
+__global__ __launch_bounds__(256) void k_tri_match(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
+                                                   const int* __restrict__ node1, const uint8_t* __restrict__ hasMp1,
+                                                   const uint8_t* __restrict__ stereo1, int n1, const int* __restrict__ kfOff,
+                                                   const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                   const uint8_t* __restrict__ kfStereo, const uint32_t* __restrict__ sNode,
+                                                   const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
+                                                   const float* __restrict__ F12, const float* __restrict__ ep,
+                                                   const float* __restrict__ scaleFactor, const float* __restrict__ sigma2,
+                                                   int onlyStereo, int coarse, int checkOri, int* __restrict__ matches12,
+                                                   int* __restrict__ stat) {
+  const int kf = blockIdx.y, base = kfOff[kf];
+  TriPinholeGate gate{hasMp1, stereo1, kfStereo, kfKp, F12 + kf * 9, scaleFactor, sigma2, ep[kf * 2], ep[kf * 2 + 1], base, onlyStereo,
+                      coarse};
+  tri_match_body(kp1, desc1, node1, n1, base, kfKp, kfDesc, sNode, sIdx, nListed, checkOri, matches12, stat, gate);
 }
 
 // grid = neighbours (mbCheckOrientation only)
@@ -1559,9 +1598,9 @@ __global__ __launch_bounds__(512) void k_search_by_bow_kf(const uint8_t* __restr
 //                   logarithm), the radius.  Survivors go to a compact list (ballot + popcount, one atomic per wave); every pair
 //                   gets -1 / 256 here.
 //   k_fuse_match    FUSE_LANES lanes per survivor (a 3 px window holds a handful of keypoints: a whole wave per query would idle
-//                   most lanes), a fixed grid striding over the list: the lanes stride over each column's run, apply the window,
-//                   the level gate [level - 1, level], the chi-square gate :1533-1557 and take the group minimum of the key by
-//                   cross-lane shuffles.  TH_LOW decides the result.
+//                   most lanes), a fixed grid striding over the list: cell_window_walk (the lanes stride over each column's run,
+//                   apply the window and the level gate [level - 1, level]) with the chi-square gate :1533-1557 as its row gate,
+//                   and the group minimum of the key by cross-lane shuffles.  TH_LOW decides the result.
 // Three launches per call, whatever nkf and nmp.
 // ---------------------------------------------------------------------------
 constexpr int FUSE_CELLS = GRID_COLS * GRID_ROWS;
@@ -1573,6 +1612,29 @@ __device__ __forceinline__ int fuse_cell(const pli_keypoint& k, float minX, floa
   if (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) return -1;                  // PosInGrid
   return px * GRID_ROWS + py;
 }
+
+// The cells that GetFeaturesInArea visits for the window (u, v, radius) (KeyFrame.cc:889-903, Frame.cc:781-806): columns c0..c1,
+// rows r0..r1, clamped to the grid.  Shared by every walk over the cell runs.
+struct CellWindow {
+  int c0, c1, r0, r1;
+  __device__ __forceinline__ CellWindow(float u, float v, float radius, const pli_fuse_camera& cam, float gwInv, float ghInv)
+      : c0(max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, cam.min_x), radius), gwInv)))),
+        c1(min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, cam.min_x), radius), gwInv)))),
+        r0(max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, cam.min_y), radius), ghInv)))),
+        r1(min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, cam.min_y), radius), ghInv)))) {}
+  __device__ __forceinline__ bool empty() const { return !(c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1); }
+};
+
+// The key of row i2 (keypoint k) at Hamming distance dist: (distance, cell column, cell row, index), the visiting order of
+// GetFeaturesInArea among equal distances.  key_row / key_dist take it apart again.
+__device__ __forceinline__ unsigned long long cell_key(int dist, const pli_keypoint& k, const pli_fuse_camera& cam, float gwInv,
+                                                       float ghInv, int i2) {
+  int px, py;
+  fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
+  return ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) | ((unsigned long long)py << 28) | (unsigned long long)i2;
+}
+__device__ __forceinline__ int key_row(unsigned long long key) { return (int)(key & 0xFFFFFFFull); }
+__device__ __forceinline__ int key_dist(unsigned long long key) { return (int)(key >> 40); }
 
 // grid = keyframes, 256 threads; cellStart: nkf x (FUSE_CELLS + 1), sIdx: one uint16 per feature (the listed ones first)
 __global__ __launch_bounds__(256) void k_fuse_grid(const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
@@ -1622,6 +1684,29 @@ __global__ __launch_bounds__(256) void k_fuse_grid(const int* __restrict__ kfOff
 
 static_assert(sizeof(FuseSurvivor) == 32, "FuseSurvivor layout");
 
+// What the projection gates of Fuse / Sim3 and of relocalisation (:2360-2374) share once the point is inside the image:
+// PO, the distance-range gate, (kNormalGate: Fuse and Sim3 only) the viewing-normal gate, PredictScale and the radius.
+template <bool kNormalGate>
+__device__ __forceinline__ bool project_point_tail(const pli_fuse_point& P, const float* __restrict__ T, float th,
+                                                   const float* __restrict__ levelRatio, int nlevels,
+                                                   const float* __restrict__ scaleFactor, FuseSurvivor& S) {
+  const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
+  // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) and PO.dot(Pn) (double)
+  const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
+  const float dist3D = (float)sqrt(n2);
+  if (dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) return false;                    // reloc: :2368
+  if (kNormalGate) {
+    const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
+    if (dot < 0.5 * (double)dist3D) return false;
+  }
+  const float ratio = __fdiv_rn(P.max_dist, dist3D);             // MapPoint::PredictScale, MapPoint.cc:449-464 / :466-482
+  int level = 0;
+  for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
+  S.level = level;
+  S.radius = __fmul_rn(th, scaleFactor[level]);                  // reloc: :2374
+  return true;
+}
+
 // One (keyframe, point) pair up to the window search: the gates :1432-1500 (Sim3 searches: :501-543) in the reference's order.  true: S
 // holds the projection, the level and the radius (S.ur only for kForm 0).  kForm 0: Pinhole::project (Pinhole.cpp:30-33, fx*x/z + cx),
 // what Fuse and ORBmatcher.cc:519 call; kForm 1: ORBmatcher.cc:631-636 (invz = 1/z; x*invz; fx*x + cx), which rounds differently.
@@ -1643,18 +1728,7 @@ __device__ __forceinline__ bool fuse_project_point(const pli_fuse_point& P, cons
   }
   if (!(S.u >= cam.min_x && S.u < cam.max_x && S.v >= cam.min_y && S.v < cam.max_y)) return false;      // KeyFrame::IsInImage
   S.ur = __fsub_rn(S.u, __fmul_rn(cam.bf, invz));
-  const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
-  // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) and PO.dot(Pn) (double)
-  const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
-  const float dist3D = (float)sqrt(n2);
-  const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
-  if ((dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) || dot < 0.5 * (double)dist3D) return false;
-  const float ratio = __fdiv_rn(P.max_dist, dist3D);             // MapPoint::PredictScale, MapPoint.cc:449-464
-  int level = 0;
-  for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
-  S.level = level;
-  S.radius = __fmul_rn(th, scaleFactor[level]);
-  return true;
+  return project_point_tail<true>(P, T, th, levelRatio, nlevels, scaleFactor, S);
 }
 
 // grid = ceil(nkf * nmp / 256)
@@ -1697,6 +1771,44 @@ __device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v
   return v;
 }
 
+// The window of survivor S in its keyframe's cell runs (KeyFrame::GetFeaturesInArea, KeyFrame.cc:881-925), `stride` lanes of which
+// this is lane `sub`: emit(key) for every row inside the window whose octave lies in [level - 1, level + kUp] (kUp 0: :1524 / :563;
+// kUp 1: Frame::GetFeaturesInArea(..., level - 1, level + 1) of ORBmatcher.cc:2376, the same cells in the same order), that
+// rowGate(keypoint, row in the flat table) keeps (asked before the descriptor is loaded) and whose distance is <= distLimit (256,
+// the largest Hamming distance: no limit).  The one walk of Fuse, the Sim3 search and relocalisation.
+struct NoRowGate {
+  __device__ __forceinline__ bool operator()(const pli_keypoint&, int) const { return true; }
+};
+template <int kUp, class RowGate, class Emit>
+__device__ __forceinline__ void cell_window_walk(const FuseSurvivor& S, int sub, int stride, const uint8_t* __restrict__ mpDesc,
+                                                 const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
+                                                 const uint8_t* __restrict__ kfDesc, const int* __restrict__ cellStart,
+                                                 const uint16_t* __restrict__ sIdx, const pli_fuse_camera& cam, float gwInv, float ghInv,
+                                                 int distLimit, RowGate rowGate, Emit emit) {
+  const float u = S.u, v = S.v, radius = S.radius;
+  const CellWindow w(u, v, radius, cam, gwInv, ghInv);
+  if (w.empty()) return;
+  const int base = kfOff[S.kf];
+  const int* cs = cellStart + (int64_t)S.kf * (FUSE_CELLS + 1);
+  uint64_t dq[4];
+  load_desc(mpDesc + (int64_t)S.mp * 32, dq);
+  for (int cx = w.c0; cx <= w.c1; ++cx) {
+    const int lo = cs[cx * GRID_ROWS + w.r0], hi = cs[cx * GRID_ROWS + w.r1 + 1];
+    for (int t = lo + sub; t < hi; t += stride) {
+      const int i2 = sIdx[base + t];
+      const pli_keypoint k = kfKp[base + i2];
+      if (!(fabsf(__fsub_rn(k.x, u)) < radius && fabsf(__fsub_rn(k.y, v)) < radius)) continue;        // KeyFrame.cc:918
+      if (k.octave < S.level - 1 || k.octave > S.level + kUp) continue;                                // :1524 / :563 / :2376
+      if (!rowGate(k, base + i2)) continue;
+      uint64_t d2[4];
+      load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
+      const int dist = hamming256(dq, d2);
+      if (dist > distLimit) continue;
+      emit(cell_key(dist, k, cam, gwInv, ghInv, i2));
+    }
+  }
+}
+
 // a fixed grid of 256-thread blocks; G lanes per survivor
 template <int G>
 __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restrict__ surv, const int* __restrict__ nSurv, int nmp,
@@ -1718,55 +1830,28 @@ __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restri
     S.kf = 0; S.mp = 0;
     if (s < ns) {
       S = surv[s];
-      const float u = S.u, v = S.v, radius = S.radius;
-      // KeyFrame::GetFeaturesInArea, KeyFrame.cc:889-903
-      const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
-      const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
-      const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
-      const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
-      if (c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1) {
-        const int base = kfOff[S.kf];
-        const int* cs = cellStart + (int64_t)S.kf * (FUSE_CELLS + 1);
-        uint64_t dq[4];
-        load_desc(mpDesc + (int64_t)S.mp * 32, dq);
-        for (int cx = c0; cx <= c1; ++cx) {
-          const int lo = cs[cx * GRID_ROWS + r0], hi = cs[cx * GRID_ROWS + r1 + 1];
-          for (int t = lo + sub; t < hi; t += G) {
-            const int i2 = sIdx[base + t];
-            const pli_keypoint k = kfKp[base + i2];
-            const float dx = __fsub_rn(k.x, u), dy = __fsub_rn(k.y, v);
-            if (!(fabsf(dx) < radius && fabsf(dy) < radius)) continue;                     // KeyFrame.cc:918
-            if (k.octave < S.level - 1 || k.octave > S.level) continue;                    // :1524
-            if (reprojGate) {                                                              // :1533-1557
-              const float ex = __fsub_rn(u, k.x), ey = __fsub_rn(v, k.y);
-              const float kr = kfUright[base + i2];
-              float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-              double lim = 5.99;
-              if (kr >= 0) {
-                const float er = __fsub_rn(S.ur, kr);
-                e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                lim = 7.8;
-              }
-              if ((double)__fmul_rn(e2, invSigma2[k.octave]) > lim) continue;
-            }
-            uint64_t d2[4];
-            load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
-            const int dist = hamming256(dq, d2);
-            int px, py;
-            fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
-            const unsigned long long kk = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) |
-                                          ((unsigned long long)py << 28) | (unsigned long long)i2;
-            key = kk < key ? kk : key;
-          }
-        }
-      }
+      cell_window_walk<0>(S, sub, G, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, 256,
+                          [&](const pli_keypoint& k, int row) {  // the chi-square gate :1533-1557
+                            if (!reprojGate) return true;
+                            const float ex = __fsub_rn(S.u, k.x), ey = __fsub_rn(S.v, k.y);
+                            const float kr = kfUright[row];
+                            float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                            double lim = 5.99;
+                            if (kr >= 0) {
+                              const float er = __fsub_rn(S.ur, kr);
+                              e2 = __fadd_rn(e2, __fmul_rn(er, er));
+                              lim = 7.8;
+                            }
+                            return !((double)__fmul_rn(e2, invSigma2[k.octave]) > lim);
+                          },
+                          [&](unsigned long long kk) { key = kk < key ? kk : key; });
     }
     key = group_min_u64<G>(key);
     if (s < ns && sub == 0 && key != ~0ull) {
-      const int dist = (int)(key >> 40);
+      const int dist = key_dist(key);
       const int64_t pair = (int64_t)S.kf * nmp + S.mp;
       if (bestDist) bestDist[pair] = dist;
-      if (dist <= FUSE_TH_LOW) bestIdx[pair] = (int)(key & 0xFFFFFFFull);
+      if (dist <= FUSE_TH_LOW) bestIdx[pair] = key_row(key);
     }
   }
 }
@@ -1786,7 +1871,8 @@ template __global__ void k_fuse_match<64>(const FuseSurvivor*, const int*, int, 
 //   k_sim3_project     one thread per (pair, point), fuse_project_point<form>: the survivor record goes to the DENSE slot
 //                      pair * nmp + point (level -1: the point left at a gate), so a pair's survivors stay in point order; the
 //                      slot's candidate count and best_idx are reset here.
-//   k_sim3_candidates  SIM3_LANES lanes per slot, a fixed grid striding over the slots: the window walk of k_fuse_match; every key
+//   k_sim3_candidates  (k_window_candidates<0>) SIM3_LANES lanes per slot, a fixed grid striding over the slots:
+//                      cell_window_walk, the window walk of k_fuse_match; every key
 //                      (distance, cell column, cell row, index) that passes the window and the level gate with a distance within
 //                      the limit goes to the slot's list of `width` keys (their order in the list is free: the minimum decides).
 //                      The count keeps counting past the width: count > width marks the query as overflowed.
@@ -1800,6 +1886,31 @@ template __global__ void k_fuse_match<64>(const FuseSurvivor*, const int*, int, 
 // ---------------------------------------------------------------------------
 constexpr int SIM3_LANES = 8;
 
+// The dense slot of one point: the survivor record (level -1: the point left at a gate, or is not `live`), the slot's candidate
+// count and best_idx reset.  project(S) runs the gates of a live point and fills S.
+template <class Project>
+__device__ __forceinline__ void dense_slot_store(int64_t slot, int kf, int mp, bool live, Project project,
+                                                 FuseSurvivor* __restrict__ surv, int* __restrict__ candCount,
+                                                 int* __restrict__ bestIdx) {
+  FuseSurvivor S;
+  S.kf = kf; S.mp = mp; S.u = 0.f; S.v = 0.f; S.ur = 0.f; S.radius = 0.f; S.level = -1; S.pad = 0;
+  if (live && !project(S)) S.level = -1;
+  surv[slot] = S;
+  candCount[slot] = 0;
+  if (bestIdx) bestIdx[slot] = -1;
+}
+
+// the table that owns `row` of a flat batch: the last t < n with off[t] <= row
+__device__ __forceinline__ int owning_table(const int* __restrict__ off, int n, int row) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 // grid = ceil(npair * nmp / 256)
 __global__ __launch_bounds__(256) void k_sim3_project(const pli_fuse_point* __restrict__ mp, int nmp, int npair,
                                                       const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
@@ -1810,65 +1921,26 @@ __global__ __launch_bounds__(256) void k_sim3_project(const pli_fuse_point* __re
   const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (slot >= (int64_t)npair * nmp) return;
   const int kf = (int)(slot / nmp), i = (int)(slot - (int64_t)kf * nmp);
-  FuseSurvivor S;
-  S.kf = kf; S.mp = i; S.u = 0.f; S.v = 0.f; S.ur = 0.f; S.radius = 0.f; S.level = -1; S.pad = 0;
   const pli_fuse_point P = mp[i];
-  if (P.valid && !(skip && skip[slot])) {                        // isBad(), spAlreadyFound.count(pMP) :501
-    const float* T = kfPose + (int64_t)kf * 15;
-    const bool keep = form ? fuse_project_point<1>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S)
-                           : fuse_project_point<0>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S);
-    if (!keep) S.level = -1;
-  }
-  surv[slot] = S;
-  candCount[slot] = 0;
-  if (bestIdx) bestIdx[slot] = -1;
+  const float* T = kfPose + (int64_t)kf * 15;
+  dense_slot_store(slot, kf, i, P.valid && !(skip && skip[slot]),                         // isBad(), spAlreadyFound.count(pMP) :501
+                   [&](FuseSurvivor& S) {
+                     return form ? fuse_project_point<1>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S)
+                                 : fuse_project_point<0>(P, T, cam, th, levelRatio, nlevels, scaleFactor, S);
+                   },
+                   surv, candCount, bestIdx);
 }
 
-// The window of survivor S in its keyframe's cell runs (KeyFrame::GetFeaturesInArea, KeyFrame.cc:881-925), `stride` lanes of
-// which this is lane `sub`: emit(key) for every row inside the window whose octave lies in [level - 1, level + kUp] (kUp 0: :563;
-// kUp 1: Frame::GetFeaturesInArea(..., level - 1, level + 1) of ORBmatcher.cc:2376, the same cells in the same order) and whose
-// distance is <= distLimit.
-template <int kUp, class Emit>
-__device__ __forceinline__ void sim3_window(const FuseSurvivor& S, int sub, int stride, const uint8_t* __restrict__ mpDesc,
-                                            const int* __restrict__ kfOff, const pli_keypoint* __restrict__ kfKp,
-                                            const uint8_t* __restrict__ kfDesc, const int* __restrict__ cellStart,
-                                            const uint16_t* __restrict__ sIdx, const pli_fuse_camera& cam, float gwInv, float ghInv,
-                                            int distLimit, Emit emit) {
-  const float u = S.u, v = S.v, radius = S.radius;
-  const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
-  const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, cam.min_x), radius), gwInv)));
-  const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
-  const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, cam.min_y), radius), ghInv)));
-  if (!(c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1)) return;
-  const int base = kfOff[S.kf];
-  const int* cs = cellStart + (int64_t)S.kf * (FUSE_CELLS + 1);
-  uint64_t dq[4];
-  load_desc(mpDesc + (int64_t)S.mp * 32, dq);
-  for (int cx = c0; cx <= c1; ++cx) {
-    const int lo = cs[cx * GRID_ROWS + r0], hi = cs[cx * GRID_ROWS + r1 + 1];
-    for (int t = lo + sub; t < hi; t += stride) {
-      const int i2 = sIdx[base + t];
-      const pli_keypoint k = kfKp[base + i2];
-      if (!(fabsf(__fsub_rn(k.x, u)) < radius && fabsf(__fsub_rn(k.y, v)) < radius)) continue;        // KeyFrame.cc:918
-      if (k.octave < S.level - 1 || k.octave > S.level + kUp) continue;                                // :563 / :2376
-      uint64_t d2[4];
-      load_desc(kfDesc + (int64_t)(base + i2) * 32, d2);
-      const int dist = hamming256(dq, d2);
-      if (dist > distLimit) continue;
-      int px, py;
-      fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
-      emit(((unsigned long long)dist << 40) | ((unsigned long long)px << 34) | ((unsigned long long)py << 28) | (unsigned long long)i2);
-    }
-  }
-}
-
-// a fixed grid of 256-thread blocks; SIM3_LANES lanes per slot.  candCount: zeroed by k_sim3_project
-__global__ __launch_bounds__(256) void k_sim3_candidates(const FuseSurvivor* __restrict__ surv, int64_t nslot,
-                                                         const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
-                                                         const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
-                                                         const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
-                                                         pli_fuse_camera cam, int distLimit, int width,
-                                                         unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
+// The candidate lists of the Sim3 search (kUp 0, launched as "k_sim3_candidates") and of relocalisation (kUp 1,
+// "k_reloc_candidates": the searched table is the frame, kfOff = {0, nf}, and distLimit is ORBdist :2403).  A fixed grid of
+// 256-thread blocks; SIM3_LANES lanes per slot.  candCount: zeroed by k_sim3_project / k_reloc_project
+template <int kUp>
+__global__ __launch_bounds__(256) void k_window_candidates(const FuseSurvivor* __restrict__ surv, int64_t nslot,
+                                                           const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
+                                                           const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
+                                                           const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
+                                                           pli_fuse_camera cam, int distLimit, int width,
+                                                           unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
   constexpr int PER_BLOCK = 256 / SIM3_LANES;
   const int sub = threadIdx.x & (SIM3_LANES - 1);
   const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
@@ -1878,17 +1950,47 @@ __global__ __launch_bounds__(256) void k_sim3_candidates(const FuseSurvivor* __r
     if (S.level < 0) continue;
     unsigned long long* keys = candKeys + s * width;
     int* count = candCount + s;
-    sim3_window<0>(S, sub, SIM3_LANES, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
-                   [=](unsigned long long key) {
-                     const int pos = atomicAdd(count, 1);
-                     if (pos < width) keys[pos] = key;
-                   });
+    cell_window_walk<kUp>(S, sub, SIM3_LANES, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit, NoRowGate(),
+                          [=](unsigned long long key) {
+                            const int pos = atomicAdd(count, 1);
+                            if (pos < width) keys[pos] = key;
+                          });
   }
 }
+template __global__ void k_window_candidates<0>(const FuseSurvivor*, int64_t, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const int*, const uint16_t*, pli_fuse_camera, int, int, unsigned long long*, int*);
+template __global__ void k_window_candidates<1>(const FuseSurvivor*, int64_t, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const int*, const uint16_t*, pli_fuse_camera, int, int, unsigned long long*, int*);
+
+// The cursor of one wave over the n slots of a list that have candidates, in order: 64 counts per load, one bit per slot with
+// candidates, and the next slot's keys (keys: n x width) already in flight.  A caller takes i / cnt / key for itself and calls
+// advance() BEFORE it decides that slot, so that the next slot's keys travel meanwhile.  i == n: none is left.
+struct OrderedCursor {
+  const int* __restrict__ cnts;
+  const unsigned long long* __restrict__ keys;
+  int n, width, lane;
+  int chunk = -64, cntLane = 0;
+  unsigned long long todo = 0;
+  int i = -1, cnt = 0;
+  unsigned long long key = ~0ull;                                // lane's key of slot i (~0ull: none, or the list overflowed)
+  __device__ __forceinline__ OrderedCursor(const int* cnts, const unsigned long long* keys, int n, int width, int lane)
+      : cnts(cnts), keys(keys), n(n), width(width), lane(lane) { advance(); }
+  __device__ __forceinline__ void advance() {
+    while (todo == 0) {
+      chunk += 64;
+      if (chunk >= n) { i = n; return; }
+      cntLane = chunk + lane < n ? cnts[chunk + lane] : 0;
+      todo = __builtin_amdgcn_ballot_w64(cntLane != 0);
+    }
+    const int bit = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    i = chunk + bit;
+    cnt = __shfl(cntLane, bit, 64);
+    key = (cnt <= width && lane < cnt) ? keys[(int64_t)i * width + lane] : ~0ull;
+  }
+};
 
 // The ordered walk of one wave over the slots slot0 .. slot0 + nmp (one pair's, or one candidate's, points in list order) against
-// the owner table in LDS (-1 free, INT_MAX occupied at entry, else the point): 64 counts per load, one bit per slot with
-// candidates; the next slot's keys travel while this one is decided.  Returns the number of rows taken.  kUp as sim3_window.
+// the owner table in LDS (-1 free, INT_MAX occupied at entry, else the point).  Returns the number of rows taken.  kUp as
+// cell_window_walk.
 template <int kUp>
 __device__ __forceinline__ int sim3_ordered_walk(int* owner, int lane, const FuseSurvivor* __restrict__ surv, int64_t slot0, int nmp,
                                                  const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
@@ -1897,43 +1999,24 @@ __device__ __forceinline__ int sim3_ordered_walk(int* owner, int lane, const Fus
                                                  const pli_fuse_camera& cam, float gwInv, float ghInv, int distLimit, int width,
                                                  const unsigned long long* __restrict__ candKeys,
                                                  const int* __restrict__ candCount, int* __restrict__ bestIdx) {
-  const int* cnts = candCount + slot0;
-  // the walk over the slots that have candidates, in point order: 64 counts per load, one bit per slot
-  int chunk = -64, cntLane = 0;
-  unsigned long long todo = 0;
-  int iNext = -1, cntNext = 0;
-  unsigned long long keyNext = ~0ull;
-  auto advance = [&]() {                                         // -> iNext (nmp: none is left), cntNext, keyNext
-    while (todo == 0) {
-      chunk += 64;
-      if (chunk >= nmp) { iNext = nmp; return; }
-      cntLane = chunk + lane < nmp ? cnts[chunk + lane] : 0;
-      todo = __builtin_amdgcn_ballot_w64(cntLane != 0);
-    }
-    const int bit = __builtin_ctzll(todo);
-    todo &= todo - 1;
-    iNext = chunk + bit;
-    cntNext = __shfl(cntLane, bit, 64);
-    keyNext = (cntNext <= width && lane < cntNext) ? candKeys[(slot0 + iNext) * width + lane] : ~0ull;
-  };
-  advance();
+  OrderedCursor cur(candCount + slot0, candKeys + slot0 * width, nmp, width, lane);
   int nmatches = 0;
-  while (iNext < nmp) {
-    const int i = iNext, cnt = cntNext;
-    unsigned long long key = keyNext;
-    advance();                                                   // the next query's keys travel while this one is decided
+  while (cur.i < nmp) {
+    const int i = cur.i, cnt = cur.cnt;
+    unsigned long long key = cur.key;
+    cur.advance();                                               // the next query's keys travel while this one is decided
     if (cnt <= width) {
-      if (key != ~0ull && owner[(int)(key & 0xFFFFFFFull)] != -1) key = ~0ull;             // :558
+      if (key != ~0ull && owner[key_row(key)] != -1) key = ~0ull;                          // :558
     } else {                                                     // more candidates than the list holds: the window again
       key = ~0ull;
-      sim3_window<kUp>(surv[slot0 + i], lane, 64, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
-                       [&](unsigned long long kk) {
-                         if (owner[(int)(kk & 0xFFFFFFFull)] == -1 && kk < key) key = kk;
-                       });
+      cell_window_walk<kUp>(surv[slot0 + i], lane, 64, mpDesc, kfOff, kfKp, kfDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
+                            NoRowGate(), [&](unsigned long long kk) {
+                              if (owner[key_row(kk)] == -1 && kk < key) key = kk;
+                            });
     }
     const unsigned long long m = wave_min_u64(key);
     if (m != ~0ull) {                                            // :577 (the limit is already applied)
-      const int b = (int)(m & 0xFFFFFFFull);
+      const int b = key_row(m);
       owner[b] = i;                                              // :579 (every lane stores the same value)
       if (lane == 0 && bestIdx) bestIdx[slot0 + i] = b;
       ++nmatches;
@@ -1981,7 +2064,7 @@ __global__ __launch_bounds__(64) void k_sim3_assign(const FuseSurvivor* __restri
 //   k_reloc_project     one thread per point, the DENSE slot = the point's row in the ragged list; reloc_project_point: the gates of
 //                       :2351-2374, which are NOT those of fuse_project_point (no z < 0 gate, the image gate closed on both sides,
 //                       no viewing-normal gate).
-//   k_reloc_candidates  k_sim3_candidates over sim3_window<1>: octaves in [level - 1, level + 1] (:2376), keys within ORBdist (:2403).
+//   k_reloc_candidates  k_window_candidates<1>: octaves in [level - 1, level + 1] (:2376), keys within ORBdist (:2403).
 //   k_reloc_assign      one wave per candidate: the owner table of nf ints in LDS, sim3_ordered_walk<1>, then (mbCheckOrientation,
 //                       :2408-2444) the 30-bin histogram over the rows taken, ComputeThreeMaxima, the filter and the corrected
 //                       count.  A row that the filter gives back was closed during the whole walk, as in the reference.
@@ -1999,17 +2082,7 @@ __device__ __forceinline__ bool reloc_project_point(const pli_fuse_point& P, con
   S.v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
   // :2355-2358, closed on both sides; written so that a NaN leaves (the reference would convert it to int: undefined)
   if (!(S.u >= cam.min_x && S.u <= cam.max_x && S.v >= cam.min_y && S.v <= cam.max_y)) return false;
-  const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
-  // cv::norm(PO) (NORM_L2 of CV_32F: the squares summed in double) :2362
-  const double n2 = (double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2];
-  const float dist3D = (float)sqrt(n2);
-  if (dist3D < P.min_dist_inv || dist3D > P.max_dist_inv) return false;        // :2368; no viewing-normal gate
-  const float ratio = __fdiv_rn(P.max_dist, dist3D);             // MapPoint::PredictScale(dist, Frame*), MapPoint.cc:466-482
-  int level = 0;
-  for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
-  S.level = level;
-  S.radius = __fmul_rn(th, scaleFactor[level]);                  // :2374
-  return true;
+  return project_point_tail<false>(P, T, th, levelRatio, nlevels, scaleFactor, S);         // :2360-2374; no viewing-normal gate
 }
 
 // grid = ceil(npts / 256), npts = mpOff[ncand]
@@ -2020,46 +2093,11 @@ __global__ __launch_bounds__(256) void k_reloc_project(const pli_fuse_point* __r
                                                        int* __restrict__ candCount, int* __restrict__ bestIdx) {
   const int slot = blockIdx.x * 256 + threadIdx.x;
   if (slot >= mpOff[ncand]) return;
-  int lo = 0, hi = ncand;                                        // the candidate: the last c with mpOff[c] <= slot
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (mpOff[mid] <= slot) lo = mid;
-    else hi = mid;
-  }
-  FuseSurvivor S;
-  S.kf = 0; S.mp = slot; S.u = 0.f; S.v = 0.f; S.ur = 0.f; S.radius = 0.f; S.level = -1; S.pad = 0;      // kf 0: the frame's table
+  const float* T = pose + (int64_t)owning_table(mpOff, ncand, slot) * 15;                  // the pose of the point's candidate
   const pli_fuse_point P = mp[slot];
-  if (P.valid) {                                                 // pMP, !isBad(), !sAlreadyFound.count(pMP) :2345-2347
-    if (!reloc_project_point(P, pose + (int64_t)lo * 15, cam, th, levelRatio, nlevels, scaleFactor, S)) S.level = -1;
-  }
-  surv[slot] = S;
-  candCount[slot] = 0;
-  if (bestIdx) bestIdx[slot] = -1;
-}
-
-// k_sim3_candidates with the octave window [level - 1, level + 1] (a kernel of its own, so that the other's code stays as it is); a
-// fixed grid of 256-thread blocks, SIM3_LANES lanes per slot.  candCount: zeroed by k_reloc_project.  fOff = {0, nf}
-__global__ __launch_bounds__(256) void k_reloc_candidates(const FuseSurvivor* __restrict__ surv, int64_t nslot,
-                                                          const uint8_t* __restrict__ mpDesc, const int* __restrict__ fOff,
-                                                          const pli_keypoint* __restrict__ fKp, const uint8_t* __restrict__ fDesc,
-                                                          const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
-                                                          pli_fuse_camera cam, int distLimit, int width,
-                                                          unsigned long long* __restrict__ candKeys, int* __restrict__ candCount) {
-  constexpr int PER_BLOCK = 256 / SIM3_LANES;
-  const int sub = threadIdx.x & (SIM3_LANES - 1);
-  const float gwInv = __fdiv_rn((float)GRID_COLS, __fsub_rn(cam.max_x, cam.min_x));
-  const float ghInv = __fdiv_rn((float)GRID_ROWS, __fsub_rn(cam.max_y, cam.min_y));
-  for (int64_t s = (int64_t)blockIdx.x * PER_BLOCK + threadIdx.x / SIM3_LANES; s < nslot; s += (int64_t)gridDim.x * PER_BLOCK) {
-    const FuseSurvivor S = surv[s];
-    if (S.level < 0) continue;
-    unsigned long long* keys = candKeys + s * width;
-    int* count = candCount + s;
-    sim3_window<1>(S, sub, SIM3_LANES, mpDesc, fOff, fKp, fDesc, cellStart, sIdx, cam, gwInv, ghInv, distLimit,
-                   [=](unsigned long long key) {             // keys within ORBdist :2403
-                     const int pos = atomicAdd(count, 1);
-                     if (pos < width) keys[pos] = key;
-                   });
-  }
+  dense_slot_store(slot, 0, slot, P.valid != 0,                  // kf 0: the frame's table; pMP, !isBad(), !sAlreadyFound :2345-2347
+                   [&](FuseSurvivor& S) { return reloc_project_point(P, T, cam, th, levelRatio, nlevels, scaleFactor, S); }, surv,
+                   candCount, bestIdx);
 }
 
 // grid = candidates, one wave; LDS: nf ints (the owner table) and 48 ints (the histogram and ComputeThreeMaxima's bins)
@@ -2142,13 +2180,10 @@ __device__ __forceinline__ void init_window(float x, float y, float r, const uin
                                             const pli_keypoint* __restrict__ kp2, const uint8_t* __restrict__ desc2,
                                             const int* __restrict__ cellStart, const uint16_t* __restrict__ sIdx,
                                             const pli_fuse_camera& cam, float gwInv, float ghInv, int distLimit, Visit visit) {
-  const int c0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, cam.min_x), r), gwInv)));
-  const int c1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, cam.min_x), r), gwInv)));
-  const int r0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, cam.min_y), r), ghInv)));
-  const int r1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, cam.min_y), r), ghInv)));
-  if (!(c0 < GRID_COLS && c1 >= 0 && r0 < GRID_ROWS && r1 >= 0 && r0 <= r1)) return;
-  for (int cx = c0; cx <= c1; ++cx) {
-    const int lo = cellStart[cx * GRID_ROWS + r0], hi = cellStart[cx * GRID_ROWS + r1 + 1];
+  const CellWindow w(x, y, r, cam, gwInv, ghInv);
+  if (w.empty()) return;
+  for (int cx = w.c0; cx <= w.c1; ++cx) {
+    const int lo = cellStart[cx * GRID_ROWS + w.r0], hi = cellStart[cx * GRID_ROWS + w.r1 + 1];
     for (int t0 = lo; t0 < hi; t0 += 64) {
       unsigned long long key = ~0ull;
       if (t0 + lane < hi) {
@@ -2158,11 +2193,7 @@ __device__ __forceinline__ void init_window(float x, float y, float r, const uin
           uint64_t d2[4];
           load_desc(desc2 + (int64_t)i2 * 32, d2);
           const int dist = hamming256(dq, d2);
-          if (dist <= distLimit) {
-            int px, py;
-            fuse_cell(k, cam.min_x, cam.min_y, gwInv, ghInv, px, py);
-            key = ((unsigned long long)dist << 40) | ((unsigned long long)px << 34) | ((unsigned long long)py << 28) | (unsigned long long)i2;
-          }
+          if (dist <= distLimit) key = cell_key(dist, k, cam, gwInv, ghInv, i2);
         }
       }
       visit(key);
@@ -2219,46 +2250,28 @@ __global__ __launch_bounds__(64) void k_init_assign(const pli_keypoint* __restri
   for (int r = lane; r < n2; r += 64) state[r] = ~0u;            // INT_MAX, -1 :716-717
   for (int i = lane; i < n1; i += 64) m12[i] = -1;               // :709
   __syncthreads();
-  // the walk over the i1 that have candidates, in order: 64 counts per load, one bit per i1 (as sim3_ordered_walk)
-  int chunk = -64, cntLane = 0;
-  unsigned long long todo = 0;
-  int iNext = -1, cntNext = 0;
-  unsigned long long keyNext = ~0ull;
-  auto advance = [&]() {                                         // -> iNext (n1: none is left), cntNext, keyNext
-    while (todo == 0) {
-      chunk += 64;
-      if (chunk >= n1) { iNext = n1; return; }
-      cntLane = chunk + lane < n1 ? candCount[chunk + lane] : 0;
-      todo = __builtin_amdgcn_ballot_w64(cntLane != 0);
-    }
-    const int bit = __builtin_ctzll(todo);
-    todo &= todo - 1;
-    iNext = chunk + bit;
-    cntNext = __shfl(cntLane, bit, 64);
-    keyNext = (cntNext <= width && lane < cntNext) ? candKeys[(int64_t)iNext * width + lane] : ~0ull;
-  };
-  advance();
-  while (iNext < n1) {
-    const int i1 = iNext, cnt = cntNext;
-    const unsigned long long key = keyNext;
-    advance();                                                   // the next i1's keys travel while this one is decided
+  OrderedCursor cur(candCount, candKeys, n1, width, lane);       // the i1 that have candidates, in order
+  while (cur.i < n1) {
+    const int i1 = cur.i, cnt = cur.cnt;
+    const unsigned long long key = cur.key;
+    cur.advance();                                               // the next i1's keys travel while this one is decided
     WaveTop2 top;
     if (cnt <= width) {
-      if (key != ~0ull && (state[(int)(key & 0xFFFFFFFull)] >> 16) > (unsigned)(key >> 40)) top.push(key);      // :745
+      if (key != ~0ull && (state[key_row(key)] >> 16) > (unsigned)key_dist(key)) top.push(key);                 // :745
     } else {                                                     // more candidates than the list holds: the window again
       uint64_t dq[4];
       load_desc(desc1 + (int64_t)i1 * 32, dq);
       init_window(prevMatched[2 * i1], prevMatched[2 * i1 + 1], radius, dq, lane, kp2, desc2, cellStart, sIdx, cam, gwInv, ghInv,
                   distLimit, [&](unsigned long long kk) {
-                    if (kk != ~0ull && (state[(int)(kk & 0xFFFFFFFull)] >> 16) > (unsigned)(kk >> 40)) top.push(kk);
+                    if (kk != ~0ull && (state[key_row(kk)] >> 16) > (unsigned)key_dist(kk)) top.push(kk);
                   });
     }
     const unsigned long long k1 = top.min1();
     if (k1 != ~0ull) {
       const unsigned long long k2 = top.min2(k1);
-      const int bestDist = (int)(k1 >> 40), bestDist2 = k2 != ~0ull ? (int)(k2 >> 40) : INT_MAX;
+      const int bestDist = key_dist(k1), bestDist2 = k2 != ~0ull ? key_dist(k2) : INT_MAX;
       if (bestDist <= FUSE_TH_LOW && (float)bestDist < __fmul_rn((float)bestDist2, nnratio)) {         // :760-762
-        const int b = (int)(k1 & 0xFFFFFFFull);
+        const int b = key_row(k1);
         const unsigned old = state[b] & 0xFFFFu;                 // (every lane reads and stores the same values)
         if (old != INIT_NO_OWNER) m12[old] = -1;                 // :764-768
         m12[i1] = (short)b;
@@ -2485,8 +2498,8 @@ __global__ __launch_bounds__(64) void k_fisheye_triangulate(const pli_keypoint* 
 //                       of its side.  The ray depends on the keypoint and its own camera only, so the Newton steps and the tan
 //                       leave the candidate loop; the stored floats are the ones TriangulateMatches would compute again.
 //   k_node_sort         (above) as for k_tri_match, without the stereo flag.
-//   k_tri_match_kb8     k_tri_match's shape: one wave per idx1, the lanes stride over the node's run; Hamming distance and TH_LOW
-//                       first (:1080), then, in the lane that holds the survivor, the gate; the wave minimum of the key.
+//   k_tri_match_kb8     tri_match_body with TriKb8Gate, a kernel of its own because the gate needs five times k_tri_match's
+//                       registers: Hamming distance and TH_LOW first (:1080), then, in the lane that holds the survivor, the gate.
 //   k_tri_finish        (above) unchanged.
 // ---------------------------------------------------------------------------
 // grid = ceil((n1 + total) / 256): item i < n1 is feature i of pKF1, the others the neighbours' rows in table order
@@ -2504,14 +2517,9 @@ __global__ __launch_bounds__(256) void k_kb8_rays(const pli_keypoint* __restrict
     right = i >= n1Left;
   } else {
     const int row = i - n1;
-    int lo = 0, hi = nkf;                                // the neighbour that owns the row: the last k with kfOff[k] <= row
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (kfOff[mid] <= row) lo = mid;
-      else hi = mid;
-    }
+    const int nb = owning_table(kfOff, nkf, row);        // the neighbour that owns the row
     k = kfKp[row];
-    right = row - kfOff[lo] >= kfNleft[lo];
+    right = row - kfOff[nb] >= kfNleft[nb];
   }
   float r[3];
   if (right) kb8_unproject(camR, k.x, k.y, r);
@@ -2519,6 +2527,40 @@ __global__ __launch_bounds__(256) void k_kb8_rays(const pli_keypoint* __restrict
   if (i < n1) ray1[i] = make_float2(r[0], r[1]);
   else kfRay[i - n1] = make_float2(r[0], r[1]);
 }
+
+// the two-camera gate: KannalaBrandt8::epipolarConstrain with the relative pose and the cameras that (bRight1, bRight2) pick
+// (:1099-1132); no stereo features and no epipole gate (:1041, :1070, :1089)
+struct TriKb8Gate {
+  const uint8_t* __restrict__ hasMp1;
+  const pli_keypoint* __restrict__ kfKp;
+  const float2 *__restrict__ ray1, *__restrict__ kfRay;
+  const float *__restrict__ rel, *__restrict__ sigma2;             // rel: the neighbour's ll, lr, rl, rr
+  const Kb8 &camL, &camR;
+  int n1Left, nleft2, base, coarse;
+  pli_keypoint k1;                                                 // of idx1 (begin):
+  bool right1;
+  float r1[3], s1;
+  __device__ __forceinline__ bool admits(int idx1) const { return !hasMp1[idx1]; }         // :1036-1039
+  __device__ __forceinline__ void begin(int idx1, const pli_keypoint& k) {
+    k1 = k;
+    right1 = idx1 >= n1Left;                                       // :1052
+    const float2 q1 = ray1[idx1];
+    r1[0] = q1.x; r1[1] = q1.y; r1[2] = 1.f;
+    s1 = sigma2[k1.octave];
+  }
+  __device__ __forceinline__ bool keeps(int idx2) const {
+    if (coarse) return true;                                       // :1099-1132
+    const pli_keypoint k2 = kfKp[base + idx2];
+    const bool right2 = idx2 >= nleft2;                            // :1086
+    const float2 q2 = kfRay[base + idx2];
+    const float r2[3] = {q2.x, q2.y, 1.f};
+    const float* Rt = rel + ((right1 ? 2 : 0) + (right2 ? 1 : 0)) * 12;
+    float x3[3];
+    const float z1 = kb8_triangulate_rays(right1 ? camR : camL, right2 ? camR : camL, r1, r2, k1.x, k1.y, k2.x, k2.y, Rt, Rt + 9, s1,
+                                          sigma2[k2.octave], x3);
+    return z1 > 0.0001f;                                           // KannalaBrandt8.cpp:237
+  }
+};
 
 // grid = (ceil(n1 / (waves per block * TRI_PER_WAVE)), neighbours); rel: per neighbour ll, lr, rl, rr, each R12 row major then t12
 __global__ __launch_bounds__(256) void k_tri_match_kb8(const pli_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
@@ -2531,58 +2573,9 @@ __global__ __launch_bounds__(256) void k_tri_match_kb8(const pli_keypoint* __res
                                                        const float* __restrict__ rel, Kb8 camL, Kb8 camR,
                                                        const float* __restrict__ sigma2, int coarse, int checkOri,
                                                        int* __restrict__ matches12, int* __restrict__ stat) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const int kf = blockIdx.y, base = kfOff[kf], nl = nListed[kf], nleft2 = kfNleft[kf];
-  const uint32_t* sn = sNode + base;
-  const uint16_t* si = sIdx + base;
-  const int first = (blockIdx.x * nwaves + wave) * TRI_PER_WAVE;
-  for (int idx1 = first; idx1 < min(first + TRI_PER_WAVE, n1); ++idx1) {
-    int best = -1;
-    const int node = node1[idx1];
-    if (node >= 0 && !hasMp1[idx1]) {                              // :1036-1039 (a feature in no node is never visited)
-      const int lo = bow_lower_bound(sn, 0, nl, (uint32_t)node);
-      if (lo < nl && sn[lo] == (uint32_t)node) {
-        const int hi = bow_lower_bound(sn, lo + 1, nl, (uint32_t)node + 1u);
-        const pli_keypoint k1 = kp1[idx1];
-        const bool right1 = idx1 >= n1Left;                        // :1052
-        const float2 q1 = ray1[idx1];
-        const float r1[3] = {q1.x, q1.y, 1.f};
-        const float s1 = sigma2[k1.octave];
-        uint64_t d1[4];
-        load_desc(desc1 + (int64_t)idx1 * 32, d1);
-        unsigned long long k = ~0ull;
-        for (int t = lo + lane; t < hi; t += 64) {
-          const int idx2 = si[t];
-          uint64_t d2[4];
-          load_desc(kfDesc + (int64_t)(base + idx2) * 32, d2);
-          const int dist = hamming256(d1, d2);
-          if (dist > BOW_TH_LOW) continue;                         // :1080 (dist > bestDist: the key's minimum)
-          if (!coarse) {                                           // :1099-1132
-            const pli_keypoint k2 = kfKp[base + idx2];
-            const bool right2 = idx2 >= nleft2;                    // :1086
-            const float2 q2 = kfRay[base + idx2];
-            const float r2[3] = {q2.x, q2.y, 1.f};
-            const float* Rt = rel + ((int64_t)kf * 4 + (right1 ? 2 : 0) + (right2 ? 1 : 0)) * 12;
-            float x3[3];
-            const float z1 = kb8_triangulate_rays(right1 ? camR : camL, right2 ? camR : camL, r1, r2, k1.x, k1.y, k2.x, k2.y, Rt, Rt + 9,
-                                                  s1, sigma2[k2.octave], x3);
-            if (!(z1 > 0.0001f)) continue;                         // KannalaBrandt8.cpp:237
-          }
-          const unsigned long long kk = ((unsigned long long)dist << 32) | (0xFFFFFFFFu - (unsigned)idx2);
-          k = kk < k ? kk : k;
-        }
-        k = wave_min_u64(k);
-        if (k != ~0ull) best = (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
-      }
-    }
-    if (lane == 0) {
-      matches12[(int64_t)kf * n1 + idx1] = best;
-      if (best >= 0) {
-        atomicAdd(&stat[kf * TRI_STAT + 30], 1);
-        if (checkOri) atomicAdd(&stat[kf * TRI_STAT + bow_rot_bin(kp1[idx1].angle, kfKp[base + best].angle)], 1);
-      }
-    }
-  }
+  const int kf = blockIdx.y, base = kfOff[kf];
+  TriKb8Gate gate{hasMp1, kfKp, ray1, kfRay, rel + (int64_t)kf * 48, sigma2, camL, camR, n1Left, kfNleft[kf], base, coarse};
+  tri_match_body(kp1, desc1, node1, n1, base, kfKp, kfDesc, sNode, sIdx, nListed, checkOri, matches12, stat, gate);
 }
 
 __global__ void k_fill_f32(float* __restrict__ dst, int n, float v) {

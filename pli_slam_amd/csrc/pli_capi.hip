@@ -1713,6 +1713,47 @@ void levelTables(const pli_ctx* c, float* scale, float* sigma2, float* invSigma2
     if (invSigma2) invSigma2[l] = 1.0f / (s * s);
   }
 }
+
+// The projection searches (pli_fuse_search, pli_search_by_projection_sim3 / _reloc) predict a point's level by comparing against
+// level_ratio, nlevels - 1 thresholds that must not decrease, and sort a table into the 64 x 48 grid of its image bounds.
+bool levelRatioOk(const pli_ctx* c, const float* levelRatio) {
+  for (int n = 0; n < c->hp.nlevels - 1; ++n)
+    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return false; }
+  return true;
+}
+bool imageBoundsOk(float minX, float maxX, float minY, float maxY) {
+  if (!(maxX > minX) || !(maxY > minY)) { g_err = "empty image bounds"; return false; }
+  return true;
+}
+// their level block for the device: level_ratio, mvScaleFactors and (ntables 3: Fuse's chi-square gate) mvInvLevelSigma2
+struct LevelBlock {
+  float v[3 * MAX_LEVELS] = {};
+  LevelBlock(const pli_ctx* c, const float* levelRatio, int ntables) {
+    std::copy(levelRatio, levelRatio + std::max(c->hp.nlevels - 1, 0), v);
+    levelTables(c, v + MAX_LEVELS, nullptr, ntables == 3 ? v + 2 * MAX_LEVELS : nullptr);
+  }
+};
+// one table as the single "keyframe" of k_fuse_grid: its offset list {0, n} (the caller's object: it lives until the synchronise)
+struct OneTableOff { const int off[2]; explicit OneTableOff(int n) : off{0, n} {} };
+
+// the candidate list of one slot of pli_search_by_projection_sim3 / _reloc: 16 keys (DESIGN.md §9, Sim3 projection; the ordered
+// wave reads a list with one load, so 64 is the most; the development build can run the other widths)
+int sim3ListWidth() {
+  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) return std::min(64, std::max(1, atoi(e)));
+  return 16;
+}
+
+// the tail of the two SearchForTriangulation entry points (their plans and uploads interleave their own tables with the common ones)
+pli_status triEnd(pli_ctx* c, const KfBatch& B, int n1, ScratchBlock<pli_keypoint> dK1, ScratchBlock<pli_keypoint> dKk, ScratchBlock<int> dOff,
+                  ScratchBlock<int> dStat, ScratchBlock<int> dM, int checkOri, int32_t* matches12, int32_t* nmatches) {
+  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(B.nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
+  HIPCHK(download(c, matches12, dM, (size_t)B.nkf * n1));
+  std::vector<int> hstat((size_t)B.nkf * 32);
+  HIPCHK(download(c, hstat.data(), dStat, (size_t)B.nkf * 32));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < B.nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
+  return PLI_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3043,13 +3084,7 @@ pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, con
   LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1, dS1, n1, dOff, dKk,
          dKd, dKs, dSn, dSi, dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS, onlyStereo ? 1 : 0, coarse ? 1 : 0,
          checkOri ? 1 : 0, dM, dStat);
-  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
-  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
-  std::vector<int> hstat((size_t)nkf * 32);
-  HIPCHK(download(c, hstat.data(), dStat, (size_t)nkf * 32));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
-  return PLI_OK;
+  return triEnd(c, B, n1, dK1, dKk, dOff, dStat, dM, checkOri, matches12, nmatches);
 }
 
 pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
@@ -3143,13 +3178,7 @@ pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoi
   LAUNCH(c, "k_tri_match_kb8", k_tri_match_kb8, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1,
          (const float2*)dR1, n1, n1Left, dOff, (const int*)dNl, dKk, dKd, (const float2*)dKr, dSn, dSi, dListed, (const float*)dRel, cl, cr,
          (const float*)dLv, coarse ? 1 : 0, checkOri ? 1 : 0, dM, dStat);
-  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
-  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
-  std::vector<int> hstat((size_t)nkf * 32);
-  HIPCHK(download(c, hstat.data(), dStat, (size_t)nkf * 32));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
-  return PLI_OK;
+  return triEnd(c, B, n1, dK1, dKk, dOff, dStat, dM, checkOri, matches12, nmatches);
 }
 
 pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf, const int32_t* kfOff,
@@ -3159,10 +3188,7 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   CtxGuard guard__(c);
   if (!c || nmp < 0 || nkf < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (nkf > 0 && (!kfOff || !kfPose)) ||
       (nkf > 0 && nmp > 0 && !bestIdx)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  const int nlevels = c->hp.nlevels;
-  for (int n = 0; n < nlevels - 1; ++n)
-    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
-  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
   if (nkf == 0) return PLI_OK;
   KfBatch B;
   pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the Fuse cap", B);
@@ -3181,19 +3207,17 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   auto dKd = plan.add<uint8_t>((size_t)total * 32);
   auto dKu = plan.add<float>(total);
   auto dPose = plan.add<float>((size_t)nkf * 15);
-  auto dSkip = plan.add<uint8_t>(skip ? npairs : 0);
+  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, npairs);
   auto dLv = plan.add<float>(3 * MAX_LEVELS);               // level_ratio, mvScaleFactors, mvInvLevelSigma2
   auto dCell = plan.add<int>((size_t)nkf * (GRID_COLS * GRID_ROWS + 1));
   auto dSi = plan.add<uint16_t>(total);
   auto dSurv = plan.add<FuseSurvivor>(npairs);
   auto dNs = plan.add<int>(1);
   auto dBi = plan.add<int>(npairs);
-  auto dBd = plan.add<int>(bestDist ? npairs : 0);
+  auto dBd = plan.addIf<int>(bestDist != nullptr, npairs);
   st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  float hlv[3 * MAX_LEVELS] = {};
-  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
-  levelTables(c, hlv + MAX_LEVELS, nullptr, hlv + 2 * MAX_LEVELS);
+  const LevelBlock hlv(c, levelRatio, 3);
   HIPCHK(upload(c, dMp, mp, nmp));
   HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
   HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
@@ -3202,21 +3226,19 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   if (reprojGate) HIPCHK(upload(c, dKu, kfUright, total));
   HIPCHK(upload(c, dPose, kfPose, (size_t)nkf * 15));
   if (skip) HIPCHK(upload(c, dSkip, skip, npairs));
-  HIPCHK(upload(c, dLv, (const float*)hlv, 3 * MAX_LEVELS));
+  HIPCHK(upload(c, dLv, hlv.v, 3 * MAX_LEVELS));
   HIPCHK(hipMemsetAsync(dNs, 0, sizeof(int), c->stream));
-  const uint8_t* dSkipPtr = skip ? (const uint8_t*)dSkip : nullptr;
-  int* dBdPtr = bestDist ? (int*)dBd : nullptr;
   const float* lv = dLv;
   LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(nkf), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
-  LAUNCH(c, "k_fuse_project", k_fuse_project, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose, dSkipPtr, *cam, th,
-         lv, nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBdPtr);
+  LAUNCH(c, "k_fuse_project", k_fuse_project, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose, dSkip, *cam, th,
+         lv, c->hp.nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBd);
   // lanes per surviving pair (Fuse: 8 measured best; the development build can run the other widths)
   int lanes = 8;
   if (const char* e = DEVENV("PLI_FUSE_LANES")) lanes = atoi(e);
   const dim3 mgrid(1024);
 #define FUSE_MATCH(G)                                                                                                              \
   LAUNCH(c, "k_fuse_match", k_fuse_match<G>, mgrid, dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd, dKu, dCell, dSi, *cam,     \
-         lv + 2 * MAX_LEVELS, reprojGate ? 1 : 0, dBi, dBdPtr)
+         lv + 2 * MAX_LEVELS, reprojGate ? 1 : 0, dBi, dBd)
   if (lanes == 16) FUSE_MATCH(16);
   else if (lanes == 64) FUSE_MATCH(64);
   else FUSE_MATCH(8);
@@ -3227,10 +3249,6 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   return PLI_OK;
 }
 
-// the candidate list of one (pair, point) slot of pli_search_by_projection_sim3: 16 keys (DESIGN.md §9, Sim3 projection; the
-// ordered wave reads a list with one load, so 64 is the most; the development build can run the other widths)
-constexpr int SIM3_LIST_WIDTH = 16;
-
 pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t npair,
                                          const int32_t* kfOff, const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfPose,
                                          const uint8_t* skip, const uint8_t* occupied, const pli_fuse_camera* cam, float th,
@@ -3239,10 +3257,7 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
   CtxGuard guard__(c);
   if (!c || nmp < 0 || npair < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (npair > 0 && (!kfOff || !kfPose || !nmatches)) ||
       (projectForm != 0 && projectForm != 1)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  const int nlevels = c->hp.nlevels;
-  for (int n = 0; n < nlevels - 1; ++n)
-    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
-  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
   // bestDist <= TH_LOW * ratioHamming (ORBmatcher.cc:577): a float product, one rounding.  With no candidate the reference holds
   // bestDist = 256, bestIdx = -1 and would write vpMatched[-1] if the product reached 256
   const float limit = 50.0f * ratioHamming;
@@ -3265,8 +3280,7 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
     return PLI_OK;
   }
   HIPCHK(hipSetDevice(c->device));
-  int width = SIM3_LIST_WIDTH;
-  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) width = std::min(64, std::max(1, atoi(e)));
+  const int width = sim3ListWidth();
   const size_t nslot = (size_t)npair * nmp;
   ScratchPlan plan;
   auto dMp = plan.add<pli_fuse_point>(nmp);
@@ -3275,8 +3289,8 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
   auto dKk = plan.add<pli_keypoint>(total);
   auto dKd = plan.add<uint8_t>((size_t)total * 32);
   auto dPose = plan.add<float>((size_t)npair * 15);
-  auto dSkip = plan.add<uint8_t>(skip ? nslot : 0);
-  auto dOcc = plan.add<uint8_t>(occupied ? total : 0);
+  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, nslot);
+  auto dOcc = plan.addIf<uint8_t>(occupied != nullptr, total);
   auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
   auto dCell = plan.add<int>((size_t)npair * (GRID_COLS * GRID_ROWS + 1));
   auto dSi = plan.add<uint16_t>(total);
@@ -3284,13 +3298,11 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
   auto dKeys = plan.add<unsigned long long>(nslot * width);
   auto dCnt = plan.add<int>(nslot);
   auto dRow = plan.add<int>(total);
-  auto dBi = plan.add<int>(bestIdx ? nslot : 0);
+  auto dBi = plan.addIf<int>(bestIdx != nullptr, nslot);
   auto dNm = plan.add<int>(npair);
   st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  float hlv[2 * MAX_LEVELS] = {};
-  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
-  levelTables(c, hlv + MAX_LEVELS, nullptr, nullptr);
+  const LevelBlock hlv(c, levelRatio, 2);
   HIPCHK(upload(c, dMp, mp, nmp));
   HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
   HIPCHK(upload(c, dOff, kfOff, (size_t)npair + 1));
@@ -3299,18 +3311,15 @@ pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, c
   HIPCHK(upload(c, dPose, kfPose, (size_t)npair * 15));
   if (skip) HIPCHK(upload(c, dSkip, skip, nslot));
   if (occupied) HIPCHK(upload(c, dOcc, occupied, total));
-  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
-  const uint8_t* dSkipPtr = skip ? (const uint8_t*)dSkip : nullptr;
-  const uint8_t* dOccPtr = occupied ? (const uint8_t*)dOcc : nullptr;
-  int* dBiPtr = bestIdx ? (int*)dBi : nullptr;
+  HIPCHK(upload(c, dLv, hlv.v, 2 * MAX_LEVELS));
   const float* lv = dLv;
   LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(npair), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
-  LAUNCH(c, "k_sim3_project", k_sim3_project, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, dMp, nmp, npair, dPose, dSkipPtr, *cam,
-         th, lv, nlevels, lv + MAX_LEVELS, projectForm, dSurv, dCnt, dBiPtr);
-  LAUNCH(c, "k_sim3_candidates", k_sim3_candidates, dim3(1024), dim3(256), 0, dSurv, (int64_t)nslot, dMd, dOff, dKk, dKd, dCell, dSi, *cam,
+  LAUNCH(c, "k_sim3_project", k_sim3_project, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, dMp, nmp, npair, dPose, dSkip, *cam,
+         th, lv, c->hp.nlevels, lv + MAX_LEVELS, projectForm, dSurv, dCnt, dBi);
+  LAUNCH(c, "k_sim3_candidates", k_window_candidates<0>, dim3(1024), dim3(256), 0, dSurv, (int64_t)nslot, dMd, dOff, dKk, dKd, dCell, dSi, *cam,
          distLimit, width, dKeys, dCnt);
-  LAUNCH(c, "k_sim3_assign", k_sim3_assign, dim3(npair), dim3(64), (size_t)B.maxNk * sizeof(int), dSurv, nmp, dMd, dOff, dKk, dKd, dOccPtr,
-         dCell, dSi, *cam, distLimit, width, dKeys, dCnt, dRow, dBiPtr, dNm);
+  LAUNCH(c, "k_sim3_assign", k_sim3_assign, dim3(npair), dim3(64), (size_t)B.maxNk * sizeof(int), dSurv, nmp, dMd, dOff, dKk, dKd, dOcc,
+         dCell, dSi, *cam, distLimit, width, dKeys, dCnt, dRow, dBi, dNm);
   HIPCHK(download(c, rowPoint, dRow, total));
   if (bestIdx) HIPCHK(download(c, bestIdx, dBi, nslot));
   HIPCHK(download(c, nmatches, dNm, npair));
@@ -3326,10 +3335,7 @@ pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32
   CtxGuard guard__(c);
   if (!c || ncand < 0 || nf < 0 || !cam || !levelRatio || (ncand > 0 && (!mpOff || !pose || !nmatches)) || (nf > 0 && (!fKp || !fDesc)) ||
       (ncand > 0 && nf > 0 && !rowPoint)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  const int nlevels = c->hp.nlevels;
-  for (int n = 0; n < nlevels - 1; ++n)
-    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return PLI_ERR_INVALID; }
-  if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
   // bestDist <= ORBdist (ORBmatcher.cc:2403): with no candidate the reference holds bestDist = 256, bestIdx2 = -1 and would write
   // mvpMapPoints[-1] at 256
   if (orbDist < 0 || orbDist > 255) { g_err = "orb_dist must lie in [0, 255]"; return PLI_ERR_INVALID; }
@@ -3349,19 +3355,18 @@ pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32
     return PLI_OK;
   }
   HIPCHK(hipSetDevice(c->device));
-  int width = SIM3_LIST_WIDTH;                              // the list of one point, as pli_search_by_projection_sim3
-  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) width = std::min(64, std::max(1, atoi(e)));
+  const int width = sim3ListWidth();
   const size_t nrow = (size_t)ncand * nf;
   ScratchPlan plan;
   auto dOff = plan.add<int>((size_t)ncand + 1);
   auto dMp = plan.add<pli_fuse_point>(total);
   auto dMd = plan.add<uint8_t>((size_t)total * 32);
-  auto dMa = plan.add<float>(checkOri ? total : 0);
+  auto dMa = plan.addIf<float>(checkOri != 0, total);
   auto dPose = plan.add<float>((size_t)ncand * 15);
   auto dFoff = plan.add<int>(2);                            // the frame as the one table of k_fuse_grid: {0, nf}
   auto dKk = plan.add<pli_keypoint>(nf);
   auto dKd = plan.add<uint8_t>((size_t)nf * 32);
-  auto dOcc = plan.add<uint8_t>(occupied ? nrow : 0);
+  auto dOcc = plan.addIf<uint8_t>(occupied != nullptr, nrow);
   auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
   auto dCell = plan.add<int>(GRID_COLS * GRID_ROWS + 1);
   auto dSi = plan.add<uint16_t>(nf);
@@ -3369,35 +3374,30 @@ pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32
   auto dKeys = plan.add<unsigned long long>((size_t)total * width);
   auto dCnt = plan.add<int>(total);
   auto dRow = plan.add<int>(nrow);
-  auto dBi = plan.add<int>(bestIdx ? total : 0);
+  auto dBi = plan.addIf<int>(bestIdx != nullptr, total);
   auto dNm = plan.add<int>(ncand);
   st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  float hlv[2 * MAX_LEVELS] = {};
-  std::copy(levelRatio, levelRatio + std::max(nlevels - 1, 0), hlv);
-  levelTables(c, hlv + MAX_LEVELS, nullptr, nullptr);
-  const int fOff[2] = {0, nf};
+  const LevelBlock hlv(c, levelRatio, 2);
+  const OneTableOff fOff(nf);
   HIPCHK(upload(c, dOff, mpOff, (size_t)ncand + 1));
   HIPCHK(upload(c, dMp, mp, total));
   HIPCHK(upload(c, dMd, mpDesc, (size_t)total * 32));
   if (checkOri) HIPCHK(upload(c, dMa, mpAngle, total));
   HIPCHK(upload(c, dPose, pose, (size_t)ncand * 15));
-  HIPCHK(upload(c, dFoff, (const int*)fOff, 2));
+  HIPCHK(upload(c, dFoff, fOff.off, 2));
   HIPCHK(upload(c, dKk, fKp, nf));
   HIPCHK(upload(c, dKd, fDesc, (size_t)nf * 32));
   if (occupied) HIPCHK(upload(c, dOcc, occupied, nrow));
-  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
-  const float* dMaPtr = checkOri ? (const float*)dMa : nullptr;
-  const uint8_t* dOccPtr = occupied ? (const uint8_t*)dOcc : nullptr;
-  int* dBiPtr = bestIdx ? (int*)dBi : nullptr;
+  HIPCHK(upload(c, dLv, hlv.v, 2 * MAX_LEVELS));
   const float* lv = dLv;
   LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dFoff, dKk, *cam, dCell, dSi);
   LAUNCH(c, "k_reloc_project", k_reloc_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dMp, dOff, ncand, dPose, *cam, th, lv,
-         nlevels, lv + MAX_LEVELS, dSurv, dCnt, dBiPtr);
-  LAUNCH(c, "k_reloc_candidates", k_reloc_candidates, dim3(1024), dim3(256), 0, dSurv, (int64_t)total, dMd, dFoff, dKk, dKd, dCell, dSi,
+         c->hp.nlevels, lv + MAX_LEVELS, dSurv, dCnt, dBi);
+  LAUNCH(c, "k_reloc_candidates", k_window_candidates<1>, dim3(1024), dim3(256), 0, dSurv, (int64_t)total, dMd, dFoff, dKk, dKd, dCell, dSi,
          *cam, orbDist, width, dKeys, dCnt);
-  LAUNCH(c, "k_reloc_assign", k_reloc_assign, dim3(ncand), dim3(64), (size_t)(48 + nf) * sizeof(int), dSurv, dOff, dMd, dMaPtr, dFoff, dKk,
-         dKd, nf, dOccPtr, dCell, dSi, *cam, orbDist, width, checkOri ? 1 : 0, dKeys, dCnt, dRow, dBiPtr, dNm);
+  LAUNCH(c, "k_reloc_assign", k_reloc_assign, dim3(ncand), dim3(64), (size_t)(48 + nf) * sizeof(int), dSurv, dOff, dMd, dMa, dFoff, dKk,
+         dKd, nf, dOcc, dCell, dSi, *cam, orbDist, width, checkOri ? 1 : 0, dKeys, dCnt, dRow, dBi, dNm);
   HIPCHK(download(c, rowPoint, dRow, nrow));
   if (bestIdx) HIPCHK(download(c, bestIdx, dBi, total));
   HIPCHK(download(c, nmatches, dNm, ncand));
@@ -3417,7 +3417,7 @@ pli_status pli_search_for_initialization(pli_ctx* c, const pli_keypoint* kp1, co
   }
   if (windowSize < 0) { g_err = "window_size must not be negative"; return PLI_ERR_INVALID; }
   if (!std::isfinite(nnratio) || !(nnratio > 0.f)) { g_err = "nnratio must be finite and positive"; return PLI_ERR_INVALID; }
-  if (!(maxX > minX) || !(maxY > minY)) { g_err = "empty image bounds"; return PLI_ERR_INVALID; }
+  if (!imageBoundsOk(minX, maxX, minY, maxY)) return PLI_ERR_INVALID;
   if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "F1 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
   if (n2 > PLI_BOW_MAX_FEATURES) { g_err = "F2 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
   if (!octavesOk(c, kp1, n1, "kp1") || !octavesOk(c, kp2, n2, "kp2")) return PLI_ERR_INVALID;
@@ -3453,26 +3453,25 @@ pli_status pli_search_for_initialization(pli_ctx* c, const pli_keypoint* kp1, co
   auto dKeys = plan.add<unsigned long long>((size_t)n1 * width);
   auto dCnt = plan.add<int>(n1);
   auto dM12 = plan.add<int>(n1);
-  auto dRaw = plan.add<int>(raw12 ? n1 : 0);
+  auto dRaw = plan.addIf<int>(raw12 != nullptr, n1);
   auto dNm = plan.add<int>(1);
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   pli_fuse_camera cam = {};                                 // only the bounds are read (the 64 x 48 grid)
   cam.min_x = minX; cam.max_x = maxX; cam.min_y = minY; cam.max_y = maxY;
-  const int off2[2] = {0, n2};
-  HIPCHK(upload(c, dOff, (const int*)off2, 2));
+  const OneTableOff off2(n2);
+  HIPCHK(upload(c, dOff, off2.off, 2));
   HIPCHK(upload(c, dK1, kp1, n1));
   HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
   HIPCHK(upload(c, dPrev, prevMatched, (size_t)n1 * 2));
   HIPCHK(upload(c, dK2, kp2, n2));
   HIPCHK(upload(c, dD2, desc2, (size_t)n2 * 32));
-  int* dRawPtr = raw12 ? (int*)dRaw : nullptr;
   const float radius = (float)windowSize;                   // const float& r of GetFeaturesInArea takes the int (:726)
   LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dOff, dK2, cam, dCell, dSi);
   LAUNCH(c, "k_init_candidates", k_init_candidates, dim3((unsigned)std::min(1024, (n1 + 3) / 4)), dim3(256), 0, dK1, dD1, n1, dPrev, dK2, dD2,
          dCell, dSi, cam, radius, distLimit, width, dKeys, dCnt);
   LAUNCH(c, "k_init_assign", k_init_assign, dim3(1), dim3(64), (size_t)(48 + n2) * sizeof(int) + (size_t)n1 * sizeof(short), dK1, dD1, n1,
-         dPrev, dK2, dD2, n2, dCell, dSi, cam, radius, distLimit, width, nnratio, checkOri ? 1 : 0, dKeys, dCnt, dM12, dRawPtr, dNm);
+         dPrev, dK2, dD2, n2, dCell, dSi, cam, radius, distLimit, width, nnratio, checkOri ? 1 : 0, dKeys, dCnt, dM12, dRaw, dNm);
   HIPCHK(download(c, matches12, dM12, n1));
   if (raw12) HIPCHK(download(c, raw12, dRaw, n1));
   HIPCHK(download(c, nmatches, dNm, 1));

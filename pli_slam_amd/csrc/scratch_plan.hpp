@@ -6,6 +6,7 @@
 //   auto cnt = plan.add<int>(1);
 //   ... allocate plan.bytes(), plan.bind(base) ...       (pli_capi.hip: commitScratch)
 //   kernel(dq, cnt)                                       (a block converts to its pointer)
+//   auto skip = plan.addIf<uint8_t>(hostSkip != nullptr, n);   (an optional table: nullptr for the kernel when it was not passed)
 //
 // Not an allocator: nothing is freed and plans do not nest.  Plain C++ (no HIP, no context), so that a host compiler can test it.
 #pragma once
@@ -22,6 +23,7 @@ template <typename T>
 struct ScratchBlock {
   const ScratchPlan* plan;
   size_t off;                             // bytes from the plan's base
+  bool present = true;                    // false: an optional block that was not asked for (addIf), its pointer is null
   inline operator T*() const;             // valid once the plan is bound
 };
 
@@ -35,6 +37,13 @@ class ScratchPlan {
     total_ += (bytes + SCRATCH_ALIGN - 1) / SCRATCH_ALIGN * SCRATCH_ALIGN;
     return b;
   }
+  // an optional block, for a table that the caller may leave out: add(n) when wanted, else an empty block that converts to nullptr
+  template <typename T>
+  ScratchBlock<T> addIf(bool wanted, size_t n) {
+    ScratchBlock<T> b = add<T>(wanted ? n : 0);
+    b.present = wanted;
+    return b;
+  }
   size_t bytes() const { return total_; }
   void bind(void* base) { base_ = static_cast<uint8_t*>(base); }     // base: bytes() bytes, SCRATCH_ALIGN aligned
   uint8_t* base() const { return base_; }
@@ -45,6 +54,6 @@ class ScratchPlan {
 };
 
 template <typename T>
-inline ScratchBlock<T>::operator T*() const { return reinterpret_cast<T*>(plan->base() + off); }
+inline ScratchBlock<T>::operator T*() const { return present ? reinterpret_cast<T*>(plan->base() + off) : nullptr; }
 
 }  // namespace pli

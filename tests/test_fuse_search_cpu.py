@@ -153,7 +153,8 @@ def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=No
 
 # ---- the closed form -----------------------------------------------------------------------------------------------------------
 
-def fuse_search_fast(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=None, lr=None):
+def fuse_search_fast(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=None, lr=None, info=None):
+    """info (a dict, optional): "window_rows"[nmp], the rows inside every surviving point's window before the level gate."""
     lr = level_ratio() if lr is None else lr
     nmp, n = len(points), len(kf.x)
     best_idx = np.full(nmp, -1, np.int32)
@@ -205,6 +206,8 @@ def fuse_search_fast(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=None
         r1 = np.minimum(GRID_ROWS - 1, np.ceil(((vs - cam.min_y) + rs) * gh_inv)).astype(np.int64)
         cand = in_grid[None, :] & (px[None, :] >= c0) & (px[None, :] <= c1) & (py[None, :] >= r0) & (py[None, :] <= r1)
         cand &= (np.abs(kf.x[None, :] - us) < rs) & (np.abs(kf.y[None, :] - vs) < rs)
+        if info is not None:
+            info.setdefault("window_rows", np.zeros(nmp, np.int64))[s] = cand.sum(1)
         cand &= (octave[None, :] >= lv - 1) & (octave[None, :] <= lv)
         if reproj_gate:
             ex, ey, er = us - kf.x[None, :], vs - kf.y[None, :], ur[s, None] - kf.uright[None, :]

@@ -196,7 +196,8 @@ def reloc_survivors(points, pose, cam, th, lr=None):
     return ok, u, v, z, level, radius
 
 
-def reloc_search_fast(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, lr=None):
+def reloc_search_fast(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, lr=None, info=None):
+    """info (a dict, optional): "listed"[nmp], the keys of every point within ORBdist, owned rows included (its candidate list)."""
     points, descs = cand.points, cand.descs
     nmp, n = len(points), len(fr.x)
     best_idx = np.full(nmp, -1, np.int32)
@@ -226,6 +227,8 @@ def reloc_search_fast(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, lr=N
             if len(cols) == 0:
                 continue
             d = hamming(descs[i][None, :], fr.desc[cols]).astype(np.int64)
+            if info is not None:
+                info.setdefault("listed", np.zeros(nmp, np.int64))[i] = int((d <= int(orb_dist)).sum())
             free = (d <= int(orb_dist)) & (owner[cols] == -1)
             if not free.any():
                 continue

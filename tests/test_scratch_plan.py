@@ -83,6 +83,20 @@ int main() {
       verify(plan, seen);
     }
   }
+  {   // optional blocks: one that is wanted is a block like any other, one that is not keeps an offset of its own and gives nullptr
+    ScratchPlan plan;
+    auto a = plan.add<int>(3);
+    auto skipped = plan.addIf<uint8_t>(false, 1000);
+    auto wanted = plan.addIf<uint8_t>(true, 1000);
+    auto z = plan.add<int>(1);
+    CHECK(skipped.off == 256 && wanted.off == 512 && z.off == 512 + 1024 && plan.bytes() == 512 + 1024 + 256);
+    uint8_t* base = static_cast<uint8_t*>(std::aligned_alloc(256, plan.bytes()));
+    plan.bind(base);
+    uint8_t* s = skipped; uint8_t* w = wanted; const uint8_t* cs = skipped; int* pa = a; int* pz = z;
+    CHECK(s == nullptr && cs == nullptr && w == base + 512 && (uint8_t*)pa == base && (uint8_t*)pz == base + 512 + 1024);
+    w[999] = 1; *pz = 2;
+    std::free(base);
+  }
   if (!fails) std::printf("scratch plan: ok\n");
   return fails ? 1 : 0;
 }

@@ -153,7 +153,8 @@ def survivors(points, kf, cam, th, form, skip=None, lr=None):
     return ok, u, v, level, radius
 
 
-def sim3_search_fast(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=None, occupied=None, lr=None):
+def sim3_search_fast(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=None, occupied=None, lr=None, info=None):
+    """info (a dict, optional): "listed"[nmp], the keys of every point within the limit, owned rows included (its candidate list)."""
     nmp, n = len(points), len(kf.x)
     best_idx = np.full(nmp, -1, np.int32)
     owner = np.full(n, -1, np.int64)
@@ -183,6 +184,8 @@ def sim3_search_fast(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=Non
             if len(cols) == 0:
                 continue
             d = hamming(descs[i][None, :], kf.desc[cols]).astype(np.int64)
+            if info is not None:
+                info.setdefault("listed", np.zeros(nmp, np.int64))[i] = int((d <= limit).sum())
             free = (d <= limit) & (owner[cols] == -1)
             if not free.any():
                 continue
