@@ -4,6 +4,8 @@
 //                   generic double filters: RowFilter (left to right), SymmColumnFilter (centre, then the +-k pairs)
 //   k_lsd_resize64  resize(gaussian_img, scaled_image, Size(), SCALE, SCALE): INTER_LINEAR on doubles, float coefficients
 //   k_lsd_grad64    ll_angle: 2x2 gradient in double, modgrad (double plane), level-line angle, max gradient
+//   k_lsd_front64s  the three in one pass, a wave per strip of 64 scaled columns (the default where lsd_scale > 1)
+//   k_lsd_front64   the three in one pass per 64 x 16 tile (where the streaming form does not apply)
 // (OpenCV-3.3.1-compatible by intent: see DESIGN.md "Oracle" for what is known about each primitive.)
 #include "kernels.hpp"
 #include "device_prims.hpp"
@@ -276,6 +278,165 @@ __global__ __launch_bounds__(256) void k_lsd_front64(const uint8_t* __restrict__
   __shared__ unsigned long long wmax[4];
   if (radius == FR) lsd_front64_tile<FR>(pyr, pyrBlock, sw, sh, pitch, kern, radius, tab, dw, dh, dp, rho, rec, mg, own, maxMg, img0, flags, hot, cold, tile, rows, blur, wmax);
   else lsd_front64_tile<0>(pyr, pyrBlock, sw, sh, pitch, kern, radius, tab, dw, dh, dp, rho, rec, mg, own, maxMg, img0, flags, hot, cold, tile, rows, blur, wmax);
+}
+
+// ---------------------------------------------------------------------------
+// k_lsd_front64s: the streaming form of k_lsd_front64.  ONE WAVE owns a strip of 64 columns of the scaled image and walks down
+// `chunk` of its rows; there is no workgroup barrier and no tile.  Lane l owns source column sx0 + l of the strip's source window
+// (cw <= 64 columns, checked by the host) and scaled column x0 + l.
+//   per source row    one byte per lane (+ 6 halo bytes) staged in 72 bytes of LDS, the 7-tap row blur of the lane's column, and a
+//                     7-deep window of row-blurred doubles in registers: the column blur of the row three back.  The vertical halo
+//                     is paid once per chunk (6 rows warm the window up), not once per 16 scaled rows.
+//   per blurred row   one 64-double row of LDS, from which every lane takes the horizontal half of the resize for its scaled column
+//                     (row[sx] * a0 + row[sx + 1] * a1: the t0 / t1 of k_lsd_resize64, computed once per source row — a scaled row
+//                     reads two of them), and for the strip's 65th column (the same value in every lane).
+//   per scaled row    t0 * b0 + t1 * b1 with the row's weights from one uniform load, the right neighbour from the next lane (lane
+//                     63: the 65th column), the row above from registers: gradient, norm, angle, {cos, sin}, the stores.
+// Every expression is the tiled kernel's, with the same operands in the same order; only where an operand comes from differs, so
+// every word written equals the tiled kernel's.  Needs radius 3, sw > 6, sh > 6 (one reflection) and source rows that advance by
+// 0 or 1 per scaled row (scale >= 1): the host checks (pli_capi.hip frontStreamFits).
+// ---------------------------------------------------------------------------
+constexpr int FW_WAVES = LSD_FRONT_STREAM_WAVES;      // strips (waves) per workgroup: neighbours in x, the same rows
+
+__device__ __forceinline__ void front_wave_sync() {
+  // wave-private LDS: the LDS operations of a wave execute in order, the compiler only has to keep the order
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * FW_WAVES) void k_lsd_front64s(const uint8_t* __restrict__ pyr, int64_t pyrBlock, int sw, int sh, int pitch,
+                                                                const double* __restrict__ kern, const int* __restrict__ tab,
+                                                                int dw, int dh, int dp, double rho, float4* __restrict__ rec,
+                                                                double* __restrict__ mg, int2* __restrict__ own,
+                                                                unsigned long long* __restrict__ maxMg, int img0, int flags,
+                                                                int2* __restrict__ hot, float2* __restrict__ cold,
+                                                                int chunk /* scaled rows per wave */) {
+  __shared__ uint32_t stage[FW_WAVES][18];                 // a source row's bytes: window columns -3 .. cw + 2
+  __shared__ double blurRow[FW_WAVES][64];                 // the newest blurred row
+  const int trigF32 = flags & 1;
+  const bool packW = (flags & 2) != 0;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int x0 = (blockIdx.x * FW_WAVES + wv) * 64, y0 = blockIdx.y * chunk;
+  if (x0 >= dw || y0 >= dh) return;                        // (no barrier anywhere: a wave without a strip just leaves)
+  const int img = blockIdx.z + img0;
+  const uint8_t* src = pyr + (int64_t)img * pyrBlock;
+  // scaled rows y0 .. yl and columns x0 .. x1 (with the +1 halo of the 2x2 gradient), and the source window they read
+  const int x1 = min(x0 + 64, dw - 1), yl = min(y0 + chunk, dh - 1);
+  const int* ytab = tab + 3 * dw;                          // yofs[dh] | beta[2 * dh]
+  const int sx0 = tab[x0], sx1 = min(tab[x1] + 1, sw - 1);
+  const int cw = sx1 - sx0 + 1, tw = cw + 6;               // cw <= 64 (checked by the host)
+  const int bFirst = min(max(ytab[y0], 0), sh - 1), bLast = min(max(ytab[yl] + 1, 0), sh - 1);
+  // the lane's scaled column (pad columns: the last one, never used) and the strip's 65th
+  const int dx = min(x0 + lane, dw - 1);
+  const int sxl = tab[dx] - sx0, sxn = min(tab[dx] + 1, sw - 1) - sx0;
+  const double a0 = (double)__int_as_float(tab[dw + 2 * dx]), a1 = (double)__int_as_float(tab[dw + 2 * dx + 1]);
+  const int sxe = tab[x1] - sx0, sxen = min(tab[x1] + 1, sw - 1) - sx0;
+  const double ae0 = (double)__int_as_float(tab[dw + 2 * x1]), ae1 = (double)__int_as_float(tab[dw + 2 * x1 + 1]);
+  double k[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) k[i] = kern[i];
+  // the window leaves the image by at most 3 < sw, sh pixels: one reflection
+  auto refl = [](int p, int len) { return p < 0 ? -p : (p >= len ? 2 * len - 2 - p : p); };
+  const bool ld0 = lane < tw, ld1 = lane + 64 < tw;
+  const int c0 = ld0 ? refl(sx0 + lane - 3, sw) : 0, c1 = ld1 ? refl(sx0 + lane + 64 - 3, sw) : 0;
+  uint8_t* const stageB = reinterpret_cast<uint8_t*>(stage[wv]);
+  const uint32_t* const stageW = stage[wv];
+  double* const brow = blurRow[wv];
+  const int vLast = bLast + 3;                             // source rows enter as "virtual" rows bFirst - 3 .. bLast + 3, reflected
+  uint8_t n0, n1;                                          // the next row's bytes, loaded one row ahead
+  {
+    const uint8_t* row = src + (int64_t)refl(bFirst - 3, sh) * pitch;
+    n0 = row[c0]; n1 = row[c1];
+  }
+  double w0 = 0, w1 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0, w6 = 0;      // row-blurred rows v - 6 .. v
+  double hp = 0, hpe = 0;                                  // the resize's horizontal half of the blurred row before: own column, 65th
+  double p = 0, pR = 0;                                    // the scaled row before: own column, right neighbour
+  int dy = y0, sy = ytab[y0];
+  unsigned long long m = 0ull;
+  const int x = x0 + lane;
+  const int64_t obase = (int64_t)img * dp * dh + x;
+  auto emit = [&](int y, double norm, float a, float cx, float sn) {
+    const int64_t o = obase + (int64_t)y * dp;
+    if (rec) rec[o] = make_float4(a, cx, sn, (packW && !hot) ? tx_unclaimed_norm_word(norm) : 0.f);
+    if (hot) hot[o] = make_int2(__float_as_int(a), packW ? __float_as_int(tx_unclaimed_norm_word(norm)) : 0);
+    if (cold) cold[o] = make_float2(a == F64_NOTDEF ? F64_NOTDEF : cx, sn);
+    mg[o] = norm;
+    if (own) own[o] = make_int2(0x7FFFFFFF, 0x7FFFFFFF);
+  };
+  for (int v = bFirst - 3; v <= vLast; ++v) {
+    stageB[lane] = n0;
+    if (lane < 8) stageB[64 + lane] = n1;
+    front_wave_sync();
+    if (v < vLast) {
+      const uint8_t* row = src + (int64_t)refl(v + 1, sh) * pitch;
+      n0 = row[c0]; n1 = row[c1];
+    }
+    const uint32_t q0 = stageW[lane >> 2], q1 = stageW[(lane >> 2) + 1], q2 = stageW[(lane >> 2) + 2];
+    front_wave_sync();
+    // bytes lane .. lane + 3 and lane + 4 .. lane + 6 of the row, out of the three words that hold them
+    const uint32_t ta = (uint32_t)((((unsigned long long)q1 << 32) | q0) >> (8 * (lane & 3)));
+    const uint32_t tb = (uint32_t)((((unsigned long long)q2 << 32) | q1) >> (8 * (lane & 3)));
+    double s = k[0] * (double)(uint8_t)ta;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) s += k[j] * (double)(uint8_t)(ta >> (8 * j));
+#pragma unroll
+    for (int j = 4; j < 7; ++j) s += k[j] * (double)(uint8_t)(tb >> (8 * (j - 4)));
+    w0 = w1; w1 = w2; w2 = w3; w3 = w4; w4 = w5; w5 = w6; w6 = s;
+    if (v < bFirst + 3) continue;                          // (the window is warming up)
+    const int b = v - 3;                                   // the blurred row this source row completes
+    double bl = k[3] * w3;
+    bl += k[4] * (w4 + w2);
+    bl += k[5] * (w5 + w1);
+    bl += k[6] * (w6 + w0);
+    brow[lane] = bl;
+    front_wave_sync();
+    const double hc = brow[sxl] * a0 + brow[sxn] * a1;
+    const double hce = brow[sxe] * ae0 + brow[sxen] * ae1;
+    front_wave_sync();
+    // the scaled rows whose lower source row is b (their upper one is b - 1, or b at the image's border)
+    while (dy <= yl && min(max(sy + 1, 0), sh - 1) == b) {
+      const bool same = min(max(sy, 0), sh - 1) == b;
+      const double b0 = (double)__int_as_float(ytab[dh + 2 * dy]), b1 = (double)__int_as_float(ytab[dh + 2 * dy + 1]);
+      const double c = (same ? hc : hp) * b0 + hc * b1;
+      const double ce = (same ? hce : hpe) * b0 + hce * b1;
+      double cR = __shfl_down(c, 1, 64);
+      if (lane == 63) cR = ce;
+      if (dy > y0 && x < dp) {                             // pixel (x, dy - 1): its 2x2 neighbourhood is p pR / c cR
+        double norm = 0.0;
+        float a = F64_NOTDEF, cx = 0.f, sn = 0.f;
+        if (x < dw - 1) {
+          const double DA = cR - p;
+          const double BC = pR - c;
+          const double gx = DA + BC, gy = DA - BC;
+          norm = sqrt((gx * gx + gy * gy) / 4);
+          if (!(norm <= rho)) {
+            m = max(m, (unsigned long long)__double_as_longlong(norm));
+            a = fast_atan2_deg((float)gx, (float)(-gy));
+            sincos_of_float((float)((double)a * F64_DEG2RAD), trigF32 != 0, &sn, &cx);
+          }
+        }
+        emit(dy - 1, norm, a, cx, sn);
+      }
+      p = c; pR = cR;
+      ++dy;
+      if (dy <= yl) sy = ytab[dy];
+    }
+    hp = hc; hpe = hce;
+  }
+  if (y0 + chunk >= dh && x < dp) emit(dh - 1, 0.0, F64_NOTDEF, 0.f, 0.f);      // the image's last row: undefined pixels
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(m, o, 64); m = t > m ? t : m; }
+  if (lane == 0 && m) atomicMax(&maxMg[img], m);
+}
+
+// (self-test, pli_selftest_front_stream) the number of 4-byte words in which two planes differ
+__global__ __launch_bounds__(256) void k_count_diff_words(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, int64_t n,
+                                                          unsigned* __restrict__ count) {
+  unsigned d = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d += a[i] != b[i];
+  if (d) atomicAdd(count, d);
 }
 
 }  // namespace pli

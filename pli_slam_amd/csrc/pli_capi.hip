@@ -109,6 +109,8 @@ struct pli_ctx {
   bool lsdF64 = false; double* mg = nullptr; unsigned long long* maxMg = nullptr; double* tmp64 = nullptr; double* kern64 = nullptr;
   int* lsdTab64 = nullptr; int lsdRadius = 0;
   bool lsdFront64 = false;                   // the fused blur -> resize -> gradient pass applies (lsd_f64.hip: k_lsd_front64)
+  bool lsdFrontStream = false;               // ... in its streaming form (k_lsd_front64s), lsdFrontChunk scaled rows per wave
+  int lsdFrontChunk = 0;
   int2* hot = nullptr;                       // tile relaxation, CV_64F detector: round 1's 8-byte hot records {angle, owner word} (lsd_tile.hip)
   float2* cold = nullptr;                    // ... and the records' exact {cos, sin}: written instead of the 16-byte records when every round runs on the hot ones
   int2* own = nullptr; RxSeed* smallSeeds = nullptr; RxSeed* bigSeeds = nullptr; int bigCap = 0;
@@ -291,6 +293,82 @@ struct CtxGuard {
   } while (0)
 
 namespace {
+
+// The CV_64F front of the LSD (lsd_f64.hip).  Gaussian kernel in double (cv::getGaussianKernel(n, sigma, CV_64F)); radius 0 / kernel
+// {1} converts u8 -> double (lsd_scale 1).  Returns the radius, -1 above 3.
+int lsdGauss64(double lsdScale, double sigmaScale, double k[7]) {
+  const double sigma = (lsdScale < 1) ? (sigmaScale / lsdScale) : sigmaScale;
+  const unsigned h = lsdScale != 1 ? (unsigned)std::ceil(sigma * std::sqrt(2 * 3.0 * std::log(10.0))) : 0u;
+  if (h > 3) return -1;
+  for (int i = 0; i < 7; ++i) k[i] = 0;
+  const int n = 1 + 2 * (int)h;
+  if (h == 0) k[0] = 1.0;
+  else {
+    const double scale2X = -0.5 / (sigma * sigma);
+    double sum = 0;
+    for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; k[i] = std::exp(scale2X * x * x); sum += k[i]; }
+    sum = 1. / sum;
+    for (int i = 0; i < n; ++i) k[i] *= sum;
+  }
+  return (int)h;
+}
+
+// cv::resize coefficient tables for CV_64F (imgwarp.cpp): float weights (1 - f, f), x clamped at the borders, y not.
+// xofs[dw] | alpha[2*dw] (float bits) | yofs[dh] | beta[2*dh] (float bits); sc = 1 / lsd_scale.
+std::vector<int> buildResizeTab64(int sw, int sh, int dw, int dh, double sc) {
+  std::vector<int> t((size_t)3 * dw + 3 * dh);
+  auto fbits = [](float f) { int b; std::memcpy(&b, &f, 4); return b; };
+  for (int d = 0; d < dw; ++d) {
+    float f = (float)((d + 0.5) * sc - 0.5);
+    int sidx = cvFloorf(f);
+    f -= sidx;
+    if (sidx < 0) { f = 0; sidx = 0; }
+    if (sidx >= sw - 1) { f = 0; sidx = sw - 1; }
+    t[d] = sidx; t[dw + 2 * d] = fbits(1.f - f); t[dw + 2 * d + 1] = fbits(f);
+  }
+  for (int d = 0; d < dh; ++d) {
+    float f = (float)((d + 0.5) * sc - 0.5);
+    int sidx = cvFloorf(f);
+    f -= sidx;
+    t[3 * dw + d] = sidx; t[3 * dw + dh + 2 * d] = fbits(1.f - f); t[3 * dw + dh + 2 * d + 1] = fbits(f);
+  }
+  return t;
+}
+
+// the fused front (k_lsd_front64) stages the source window of a 64 x 16 tile of the scaled image in LDS: 64 x 20 at most
+bool frontTiledFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
+  bool fits = radius <= 3;
+  for (int x0 = 0; x0 < dw && fits; x0 += 64) {
+    const int x1 = std::min(x0 + 64, dw - 1);
+    fits = std::min(t[x1] + 1, sw - 1) - t[x0] + 1 <= 64;
+  }
+  for (int y0 = 0; y0 < dh && fits; y0 += 16) {
+    const int y1 = std::min(y0 + 16, dh - 1);
+    const int a = std::min(std::max(t[3 * dw + y0], 0), sh - 1), b = std::min(std::max(t[3 * dw + y1] + 1, 0), sh - 1);
+    fits = b - a + 1 <= 20;
+  }
+  return fits;
+}
+
+// the streaming front (k_lsd_front64s): radius 3 with one reflection at the borders, the source window of every strip of 64 (+ 1)
+// scaled columns within the wave's 64 lanes, and source rows and columns that advance by 0 or 1 per scaled one
+bool frontStreamFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
+  if (radius != 3 || sw <= 6 || sh <= 6 || dw < 1 || dh < 1) return false;
+  for (int x0 = 0; x0 < dw; x0 += 64) {
+    const int x1 = std::min(x0 + 64, dw - 1);
+    if (std::min(t[x1] + 1, sw - 1) - t[x0] + 1 > 64) return false;
+  }
+  for (int d = 1; d < dw; ++d) if (t[d] - t[d - 1] < 0 || t[d] - t[d - 1] > 1) return false;
+  for (int d = 1; d < dh; ++d) if (t[3 * dw + d] - t[3 * dw + d - 1] < 0 || t[3 * dw + d] - t[3 * dw + d - 1] > 1) return false;
+  return true;
+}
+
+// scaled rows per wave of the streaming front: each chunk enters 6 source rows to warm its window up, and a strip's chunks are what
+// fills the chip; dev switch PLI_LSD_FRONT_CHUNK (8 .. 4096)
+constexpr int LSD_FRONT_CHUNK = 64;
+int frontStreamChunk(const char* dev) {
+  return dev ? std::max(8, std::min(4096, atoi(dev))) : LSD_FRONT_CHUNK;
+}
 
 // cv::resize coefficient tables (see oracle/ocv_prims.hpp for the derivation):
 // xofs[dw] | alpha[2*dw] | yofs[dh] | beta[2*dh], all int32.
@@ -595,57 +673,21 @@ pli_status allocAll(pli_ctx* c) {
   if (c->lsdF64) {
     A(c->mg, npix * NI);
     A(c->maxMg, NI);
-    // Gaussian kernel in double (cv::getGaussianKernel(n, sigma, CV_64F)); radius 0 / kernel {1} converts u8 -> double (lsd_scale 1)
-    const double sigma = (c->cfg.lsd_scale < 1) ? (c->cfg.lsd_sigma_scale / c->cfg.lsd_scale) : c->cfg.lsd_sigma_scale;
-    const unsigned h = c->cfg.lsd_scale != 1 ? (unsigned)std::ceil(sigma * std::sqrt(2 * 3.0 * std::log(10.0))) : 0u;
-    if (h > 3) { g_err = "LSD pre-filter radius > 3 not supported"; return PLI_ERR_INVALID; }
-    c->lsdRadius = (int)h;
-    double k[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int n = 1 + 2 * (int)h;
-    if (h == 0) k[0] = 1.0;
-    else {
-      const double scale2X = -0.5 / (sigma * sigma);
-      double sum = 0;
-      for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; k[i] = std::exp(scale2X * x * x); sum += k[i]; }
-      sum = 1. / sum;
-      for (int i = 0; i < n; ++i) k[i] *= sum;
-    }
+    double k[7];
+    const int h = lsdGauss64(c->cfg.lsd_scale, c->cfg.lsd_sigma_scale, k);
+    if (h < 0) { g_err = "LSD pre-filter radius > 3 not supported"; return PLI_ERR_INVALID; }
+    c->lsdRadius = h;
     A(c->kern64, 7);
     HIPCHK(hipMemcpy(c->kern64, k, sizeof(k), hipMemcpyHostToDevice));
     if (c->cfg.lsd_scale != 1) {
       A(c->tmp64, (size_t)P.W * P.H * NI);
-      // cv::resize coefficient tables for CV_64F (imgwarp.cpp): float weights (1 - f, f), x clamped at the borders, y not
-      std::vector<int> t((size_t)3 * P.LWt + 3 * P.LH);
-      const double sc = 1. / c->cfg.lsd_scale;
-      auto fbits = [](float f) { int b; std::memcpy(&b, &f, 4); return b; };
-      for (int d = 0; d < P.LWt; ++d) {
-        float f = (float)((d + 0.5) * sc - 0.5);
-        int sidx = cvFloorf(f);
-        f -= sidx;
-        if (sidx < 0) { f = 0; sidx = 0; }
-        if (sidx >= P.W - 1) { f = 0; sidx = P.W - 1; }
-        t[d] = sidx; t[P.LWt + 2 * d] = fbits(1.f - f); t[P.LWt + 2 * d + 1] = fbits(f);
-      }
-      for (int d = 0; d < P.LH; ++d) {
-        float f = (float)((d + 0.5) * sc - 0.5);
-        int sidx = cvFloorf(f);
-        f -= sidx;
-        t[3 * P.LWt + d] = sidx; t[3 * P.LWt + P.LH + 2 * d] = fbits(1.f - f); t[3 * P.LWt + P.LH + 2 * d + 1] = fbits(f);
-      }
+      const std::vector<int> t = buildResizeTab64(P.W, P.H, P.LWt, P.LH, 1. / c->cfg.lsd_scale);
       A(c->lsdTab64, t.size());
       HIPCHK(hipMemcpy(c->lsdTab64, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-      // the fused front (k_lsd_front64) stages the source window of a 64 x 16 tile of the scaled image in LDS: 64 x 20 at most
-      bool fits = (int)h <= 3;
-      for (int x0 = 0; x0 < P.LWt && fits; x0 += 64) {
-        const int x1 = std::min(x0 + 64, P.LWt - 1);
-        fits = std::min(t[x1] + 1, P.W - 1) - t[x0] + 1 <= 64;
-      }
-      for (int y0 = 0; y0 < P.LH && fits; y0 += 16) {
-        const int y1 = std::min(y0 + 16, P.LH - 1);
-        const int a = std::min(std::max(t[3 * P.LWt + y0], 0), P.H - 1), b = std::min(std::max(t[3 * P.LWt + y1] + 1, 0), P.H - 1);
-        fits = b - a + 1 <= 20;
-      }
-      c->lsdFront64 = fits && !DEVENV("PLI_LSD_NOFUSE");
+      c->lsdFront64 = frontTiledFits(t, P.W, P.H, P.LWt, P.LH, h) && !DEVENV("PLI_LSD_NOFUSE");
+      // the streaming form (k_lsd_front64s) where its own conditions hold; dev switch PLI_LSD_FRONT_TILED: the tiled form (A/B, cross-checks)
+      c->lsdFrontStream = c->lsdFront64 && frontStreamFits(t, P.W, P.H, P.LWt, P.LH, h) && !DEVENV("PLI_LSD_FRONT_TILED");
+      c->lsdFrontChunk = frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK"));
     }
   } else {
     A(c->g2, npix * NI);
@@ -973,9 +1015,17 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     if (c->lsdFront64 && !c->debug) {
       // blur -> resize -> gradient in one pass over LDS tiles: neither double plane goes to HBM
       HIPCHK(hipMemsetAsync(c->maxMg + img0, 0, sizeof(unsigned long long) * nimg, c->stream));
+      if (c->lsdFrontStream) {
+        // one wave per strip of 64 scaled columns and chunk of rows, no tile and no barrier (both forms under one profile name)
+        const int strips = (P.LWt + 63) / 64, chunk = c->lsdFrontChunk;
+        LAUNCH(c, "k_lsd_front", k_lsd_front64s, dim3((strips + LSD_FRONT_STREAM_WAVES - 1) / LSD_FRONT_STREAM_WAVES, (P.LH + chunk - 1) / chunk, nimg),
+               dim3(64 * LSD_FRONT_STREAM_WAVES), 0, c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch, c->kern64, c->lsdTab64, P.LWt,
+               P.LH, P.LW, P.rho, recPlane, c->mg, ownPlane, c->maxMg, img0, trigF32, hotPlane, coldPlane, chunk);
+      } else {
       LAUNCH(c, "k_lsd_front", k_lsd_front64, dim3((P.LW + 63) / 64, (P.LH + 15) / 16, nimg), dim3(256), 0, c->pyr + P.lv[0].offset,
              P.pyrBlock, P.W, P.H, P.lv[0].pitch, c->kern64, c->lsdRadius, c->lsdTab64, P.LWt, P.LH, P.LW, P.rho, recPlane, c->mg, ownPlane,
              c->maxMg, img0, trigF32, hotPlane, coldPlane);
+      }
     } else {
     if (c->cfg.lsd_scale != 1) {
       LAUNCH(c, "k_blur_lsd", k_lsd_blur64, gb, dim3(256), 0, c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch,
@@ -2216,6 +2266,88 @@ pli_status pli_selftest_hot_trig(pli_ctx* c, double* max_abs_err) {
   HIPCHK(hipMemcpyAsync(&bits, c->scratch, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   std::memcpy(max_abs_err, &bits, 8);
+  return PLI_OK;
+}
+
+// The three forms of the CV_64F front pass (lsd_f64.hip) on the caller's images, compared on the device.  The geometry is the call's
+// own (any size from 1 x 1, any scale above 1), not the context's: the context lends its device, stream, rho and flags.
+pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t pack_w,
+                                     int32_t out[10]) {
+  CtxGuard guard__(c);
+  if (!c || !imgs || !out || n < 1 || n > 64 || w < 1 || h < 1 || w > 4095 || h > 4095 || !(scale > 1) || !(scale <= 4)) {
+    g_err = "bad argument";
+    return PLI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const DevParams& P = c->hp;
+  const int dw = cvRoundd(w * scale), dh = cvRoundd(h * scale), dp = (int)alignUp(dw, 16);
+  double k[7];
+  const int radius = lsdGauss64(scale, c->cfg.lsd_sigma_scale, k);
+  if (radius < 0) { g_err = "LSD pre-filter radius > 3 not supported"; return PLI_ERR_INVALID; }
+  const std::vector<int> t = buildResizeTab64(w, h, dw, dh, 1. / scale);
+  const bool tiled = frontTiledFits(t, w, h, dw, dh, radius);
+  const bool stream = tiled && frontStreamFits(t, w, h, dw, dh, radius);
+  if (!tiled) { g_err = "the fused front pass does not apply to this size"; return PLI_ERR_INVALID; }
+  const int chunk = frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK"));
+  const size_t npix = (size_t)dp * dh, srcPix = (size_t)w * h;
+  ScratchPlan plan;
+  auto dSrc = plan.add<uint8_t>(srcPix * n);
+  auto dTab = plan.add<int>(t.size());
+  auto dKern = plan.add<double>(7);
+  auto dBlur = plan.add<double>(srcPix * n);
+  auto dScaled = plan.add<double>((size_t)dw * dh * n);
+  auto dCount = plan.add<unsigned>(8);
+  // per form (0: the three kernels, 1: tiled, 2: streaming): hot, cold, mg, maxMg
+  ScratchBlock<int2> dHot[3] = {plan.add<int2>(npix * n), plan.add<int2>(npix * n), plan.add<int2>(npix * n)};
+  ScratchBlock<float2> dCold[3] = {plan.add<float2>(npix * n), plan.add<float2>(npix * n), plan.add<float2>(npix * n)};
+  ScratchBlock<double> dMg[3] = {plan.add<double>(npix * n), plan.add<double>(npix * n), plan.add<double>(npix * n)};
+  ScratchBlock<unsigned long long> dMax[3] = {plan.add<unsigned long long>(n), plan.add<unsigned long long>(n), plan.add<unsigned long long>(n)};
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  // (0xA5 everywhere first: a word that a form does not write differs from the other forms' only if they wrote it)
+  HIPCHK(hipMemsetAsync(plan.base(), 0xA5, plan.bytes(), c->stream));
+  HIPCHK(hipMemcpyAsync(dSrc, imgs, srcPix * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dTab, t.data(), t.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dKern, k, sizeof(k), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(dCount, 0, 8 * sizeof(unsigned), c->stream));
+  for (int f = 0; f < 3; ++f) HIPCHK(hipMemsetAsync(dMax[f], 0, sizeof(unsigned long long) * n, c->stream));
+  const int flags = ((c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0) | (pack_w ? 2 : 0);
+  LAUNCH(c, "k_blur_lsd", k_lsd_blur64, dim3((w + 63) / 64, (h + 15) / 16, n), dim3(256), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, radius,
+         dBlur, (int64_t)srcPix, 0);
+  LAUNCH(c, "k_resize_lsd", k_lsd_resize64, dim3((dw + 255) / 256, dh, n), dim3(256), 0, dBlur, w, h, dScaled, dw, dh, (int64_t)dw * dh, dTab, 0);
+  LAUNCH(c, "k_lsd_grad", k_lsd_grad64, dim3((dp + 255) / 256, (dh + 15) / 16, n), dim3(256), 0, dScaled, dw, dh, dp, (int64_t)dw * dh, P.rho,
+         (float4*)nullptr, dMg[0], (int2*)nullptr, dMax[0], (float*)nullptr, 0, flags, dHot[0], dCold[0]);
+  LAUNCH(c, "k_lsd_front", k_lsd_front64, dim3((dp + 63) / 64, (dh + 15) / 16, n), dim3(256), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, radius,
+         dTab, dw, dh, dp, P.rho, (float4*)nullptr, dMg[1], (int2*)nullptr, dMax[1], 0, flags, dHot[1], dCold[1]);
+  if (stream) {
+    const int strips = (dw + 63) / 64;
+    LAUNCH(c, "k_lsd_front", k_lsd_front64s, dim3((strips + LSD_FRONT_STREAM_WAVES - 1) / LSD_FRONT_STREAM_WAVES, (dh + chunk - 1) / chunk, n),
+           dim3(64 * LSD_FRONT_STREAM_WAVES), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, dTab, dw, dh, dp, P.rho, (float4*)nullptr, dMg[2],
+           (int2*)nullptr, dMax[2], 0, flags, dHot[2], dCold[2], chunk);
+  }
+  // out[0..3]: the streaming form against the tiled one; out[4..7]: against the three kernels (where the streaming form does not
+  // apply, the tiled form — what the host then runs — stands in its place in out[4..7], and out[0..3] are 0)
+  const int mine = stream ? 2 : 1;
+  auto diff = [&](const void* a, const void* b, size_t bytes, int slot) -> pli_status {
+    const int64_t words = (int64_t)(bytes / 4);
+    LAUNCH(c, "k_count_diff_words", k_count_diff_words, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0,
+           (const uint32_t*)a, (const uint32_t*)b, words, (unsigned*)dCount + slot);
+    return PLI_OK;
+  };
+  for (int ref = 0; ref < 2; ++ref) {
+    const int other = ref == 0 ? 1 : 0, base = ref == 0 ? 0 : 4;
+    if (ref == 0 && !stream) continue;
+    if ((st = diff(dHot[mine], dHot[other], npix * n * sizeof(int2), base + 0)) != PLI_OK) return st;
+    if ((st = diff(dCold[mine], dCold[other], npix * n * sizeof(float2), base + 1)) != PLI_OK) return st;
+    if ((st = diff(dMg[mine], dMg[other], npix * n * sizeof(double), base + 2)) != PLI_OK) return st;
+    if ((st = diff(dMax[mine], dMax[other], (size_t)n * sizeof(unsigned long long), base + 3)) != PLI_OK) return st;
+  }
+  unsigned counts[8];
+  HIPCHK(hipMemcpyAsync(counts, dCount, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 8; ++i) out[i] = (int32_t)std::min<unsigned>(counts[i], INT32_MAX);
+  out[8] = chunk;
+  out[9] = stream ? 1 : 0;
   return PLI_OK;
 }
 
