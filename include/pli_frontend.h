@@ -308,12 +308,14 @@ pli_status pli_selftest_hot_trig(pli_ctx* ctx, double* max_abs_err);
 /* Self-test of the LSD front pass (not a reference function): runs the three forms of the CV_64F front (csrc/lsd_f64.hip) on n
  * caller-supplied u8 images of w x h (rows of w bytes, images w * h bytes apart) at LSD scale `scale` (> 1) — the three separate kernels
  * (blur, resize, gradient), the tiled fused pass and the streaming fused pass — and compares what they write on the device.  The size
- * and the scale are the call's own (from 1 x 1 on), the context lends its device, rho and parity flags; pack_w sets the flag under
- * which the hot records carry the unclaimed-norm word.  out[0..3]: 4-byte words in which the streaming form differs from the tiled
- * one, per plane (hot, cold, norm, largest norm); out[4..7]: the same against the three kernels; out[8]: scaled rows per wave of the
- * streaming form; out[9]: 1 if the streaming form applies to this size — if not, out[0..3] are 0 and out[4..7] compare the tiled
- * form, which the library then runs.  PLI_ERR_INVALID where no fused form applies. */
-pli_status pli_selftest_front_stream(pli_ctx* ctx, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t pack_w,
+ * and the scale are the call's own (from 1 x 1 on), the context lends its device, rho and parity flags.  flags bit 0: the owner
+ * words carry the unclaimed-norm word; bit 1: the forms write the 16-byte records and the owner plane (what the schedules off the hot
+ * records take from the front pass) instead of the hot and cold planes.  out[0..3]: 4-byte words in which the streaming form differs
+ * from the tiled one, per plane (hot, cold, norm, largest norm; with bit 1: records, owner plane, norm, largest norm); out[4..7]: the
+ * same against the three kernels; out[8]: scaled rows per wave of the streaming form; out[9]: 1 if the streaming form applies to this
+ * size — if not, out[0..3] are 0 and out[4..7] compare the tiled form, which the library then runs.  PLI_ERR_INVALID where no fused
+ * form applies. */
+pli_status pli_selftest_front_stream(pli_ctx* ctx, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t flags,
                                      int32_t out[10]);
 
 /* The stereo rig of Frame::ComputeStereoMatches (Frame.cc:1005-1008: minZ = mb, maxD = mbf / minZ, depth = mbf / disparity):

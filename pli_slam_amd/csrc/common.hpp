@@ -151,6 +151,16 @@ struct TxKeys {
   int pack = 0;                     // 0: owner plane; 1: k_tx_sort writes the unclaimed words (ids); 2: the front pass wrote them (LAZY ids)
 };
 
+// what the CV_64F front pass writes per scaled pixel (lsd_f64.hip lsd_store_pixel; planes of pitch x height per image)
+struct LsdFrontPlanes {
+  float4* rec;         // or null: { angle, cos, sin, w } — w only carries the speculative grower's tags, or the packed round 1's word
+  double* mg;          // the gradient norm
+  int2* own;           // or null: the owner plane's start value
+  int2* hot;           // or null: round 1's 8-byte hot records { angle, owner word } (lsd_tile.hip)
+  float2* cold;        // or null: { cos, sin } beside the hot records when rec is not written
+  int packW;           // the owner word (rec.w where there is no hot record) = tx_unclaimed_norm_word: LAZY ids
+};
+
 // arguments of k_tx_tail (lsd_tile.hip): the rounds t >= t0 of the tile relaxation in one persistent launch
 struct TxTailArgs {
   const DevParams* Pp;

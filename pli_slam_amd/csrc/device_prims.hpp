@@ -26,6 +26,8 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   }
   return p;
 }
+// reflect101 where p leaves [0, len) by less than len: one reflection, no loop
+__device__ __forceinline__ int reflect_once(int p, int len) { return p < 0 ? -p : (p >= len ? 2 * len - 2 - p : p); }
 
 // cv::fastAtan2 (degrees, [0,360)); polynomial evaluated in the written order.
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
@@ -53,12 +55,28 @@ __device__ __forceinline__ int hamming256(const uint64_t a[4], const uint64_t b[
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// LDS that one wave has to itself (a single-wave workgroup, or a wave's own slice): the LDS operations of a wave execute in order,
+// so a write by some lanes followed by a read by others needs no s_barrier — the compiler only has to keep the order
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // wave-wide min of a 64-bit key (all lanes get the result)
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     unsigned long long t = __shfl_xor(v, o, 64);
     v = t < v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
   }
   return v;
 }

@@ -87,14 +87,6 @@ __device__ __forceinline__ double lsd_bin_coef(int maxG2, int nBins) {
   return maxG2 > 0 ? (double)(nBins - 1) / maxGrad : 0.0;
 }
 
-// LDS traffic of ONE wave is executed in order: a write by some lanes followed by a read by others needs no s_barrier,
-// only the compiler must keep the order
-__device__ __forceinline__ void lsd_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 
 // per-chunk histogram of the bins of the defined pixels
 __global__ __launch_bounds__(256) void k_lsd_hist(const int* __restrict__ g2a, int npix, int g2Thresh, int nBins,
@@ -309,9 +301,9 @@ __global__ __launch_bounds__(64) void k_lsd_scatter(const int* __restrict__ g2a,
       if (def) ord[slot] = i;
       if (rk && i < npix) rk[i] = slot;
       // single-wave block: the LDS operations of a wave execute in order (a block barrier would also wait for the stores)
-      lsd_wave_sync();
+      wave_lds_sync();
       if (def && last) base[bin] += cnt;
-      lsd_wave_sync();
+      wave_lds_sync();
     }
   }
 }
@@ -383,7 +375,7 @@ __device__ __forceinline__ void lsd_region2rect(const uint2* qs, const uint2* qg
       v2 = w;
     }
     st[0][lane] = v0; st[1][lane] = v1; st[2][lane] = v2;
-    lsd_wave_sync();
+    wave_lds_sync();
     if (lane < 3) {
       // list-order sum, eight terms per trip: the LDS reads of a trip are issued together, the adds stay in order
       const int m = (min(64, cnt - c0) + 7) & ~7;
@@ -395,7 +387,7 @@ __device__ __forceinline__ void lsd_region2rect(const uint2* qs, const uint2* qg
         for (int u = 0; u < 8; ++u) acc += a[u];
       }
     }
-    lsd_wave_sync();
+    wave_lds_sync();
   }
   // (wave-uniform f64 arithmetic costs a full wave instruction per operation: the two centroid divisions are one
   // division in lanes 0 and 1, the four end-point divisions below one division in lanes 0..3)
@@ -415,7 +407,7 @@ __device__ __forceinline__ void lsd_region2rect(const uint2* qs, const uint2* qg
       v2 = dx * dy * w;
     }
     st[0][lane] = v0; st[1][lane] = v1; st[2][lane] = v2;
-    lsd_wave_sync();
+    wave_lds_sync();
     if (lane < 3) {
       const int m = (min(64, cnt - c0) + 7) & ~7;
       for (int t = 0; t < m; t += 8) {
@@ -431,7 +423,7 @@ __device__ __forceinline__ void lsd_region2rect(const uint2* qs, const uint2* qg
         }
       }
     }
-    lsd_wave_sync();
+    wave_lds_sync();
   }
   const double Ixx = __shfl(acc, 0, 64), Iyy = __shfl(acc, 1, 64), Ixy = __shfl(acc, 2, 64);
   const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
@@ -883,13 +875,13 @@ __device__ __forceinline__ void lsd_grow_image_spec(const DevParams* __restrict_
     if (nst == 0) continue;
     LSTAT(0, 1);
     const unsigned long long tSpec = LCLOCK();
-    lsd_wave_sync();
+    wave_lds_sync();
     // ---- speculation: lane l < nst grows the region of staged seed l alone -------------------------------------
     const bool has = lane < nst;
     const int sp_l = has ? stageSp[lane] : -1;
     const float sa_l = has ? stageA[lane] : 0.f;
     const int sg_l = has ? stageG[lane] : 0;
-    lsd_wave_sync();                                     // the staging area is the region2rect scratch: read before anything writes it
+    wave_lds_sync();                                     // the staging area is the region2rect scratch: read before anything writes it
     float scos = 0.f, ssin = 0.f;
     double ang_l = 0.0;
     int spx = 0, spy = 0;
@@ -970,7 +962,7 @@ __device__ __forceinline__ void lsd_grow_image_spec(const DevParams* __restrict_
       }
     }
     auto lin = [&](int xy) -> int { return (xy >> 16) * W + (xy & 0xFFFF); };
-    lsd_wave_sync();
+    wave_lds_sync();
     LTIME(10, tSpec);
     const unsigned long long tVal = LCLOCK();
     // ---- validation: who still owns the tags of its pixels ------------------------------------------------------
@@ -1055,7 +1047,7 @@ __device__ __forceinline__ void lsd_grow_image_spec(const DevParams* __restrict_
           for (int t = 0; t < SPEC_CAP; ++t)
             if (t < scnt) { const int e = sq[t * 64 + lane]; rec[lin(e)].x = LSD_NOTDEF; qs[t] = make_uint2((unsigned)e, (unsigned)sq2[t * 64 + lane]); }
         }
-        lsd_wave_sync();
+        wave_lds_sync();
       } else {
         if (lane == __ffsll((long long)__builtin_amdgcn_ballot_w64(true)) - 1) rec[sp].x = LSD_NOTDEF;
         qs[0] = make_uint2(((unsigned)ry << 16) | (unsigned)rx, (unsigned)sg2);
@@ -1356,7 +1348,7 @@ __global__ __launch_bounds__(64) void k_lsd_rect(const DevParams* __restrict__ P
       const int off = rl_i(it.off, j), cnt = rl_i(it.cnt, j);
       const double ra = __longlong_as_double(((long long)rl_i(__double2hiint(it.reg_angle), j) << 32) |
                                              (unsigned long long)(unsigned)rl_i(__double2loint(it.reg_angle), j));
-      lsd_wave_sync();
+      wave_lds_sync();
       lsd_region2rect(nullptr, arena + off, st, cnt, ra, prec, scale, lane, seg, t0 + j, maxSeg, 0, mg, W);
     }
   }

@@ -25,13 +25,6 @@ __device__ __forceinline__ double rx_angle_diff(double a, double b) {
 constexpr int RX_RECT_GROUP_MAX = 192;
 constexpr int RX_RECT_CACHE = 4;          // chunks of a region's list whose weights stay in LDS between the passes
 
-__device__ __forceinline__ void rx_wave_sync() {
-  // single-wave workgroups: the LDS operations of a wave execute in order, the compiler only has to keep the order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // LANES lanes (a whole wave, or an aligned group of 16) compute the segment of one region; `on` = this group has one
 template <int LANES>
 __device__ __forceinline__ void rx_rect_region(bool on, const RxRect& it, const DevParams& P, const float4* __restrict__ rec,
@@ -65,9 +58,9 @@ __device__ __forceinline__ void rx_rect_region(bool on, const RxRect& it, const 
       v2 = w;
       if (c0 < RX_RECT_CACHE * LANES) { wc[c0 / LANES][lane] = w; ec[c0 / LANES][lane] = e; }
     }
-    rx_wave_sync();
+    wave_lds_sync();
     st[0][lane] = v0; st[1][lane] = v1; st[2][lane] = v2;
-    rx_wave_sync();
+    wave_lds_sync();
     if (gl < 3 && c0 < cnt) {
       // list-order sum, eight terms per trip: the LDS reads of a trip are issued together, the adds stay in order
       const int mm = (min(LANES, cnt - c0) + 7) & ~7;
@@ -97,9 +90,9 @@ __device__ __forceinline__ void rx_rect_region(bool on, const RxRect& it, const 
       v1 = dx * dx * w;
       v2 = dx * dy * w;
     }
-    rx_wave_sync();
+    wave_lds_sync();
     st[0][lane] = v0; st[1][lane] = v1; st[2][lane] = v2;
-    rx_wave_sync();
+    wave_lds_sync();
     if (gl < 3 && c0 < cnt) {
       const int mm = (min(LANES, cnt - c0) + 7) & ~7;
       for (int tt = 0; tt < mm; tt += 8) {

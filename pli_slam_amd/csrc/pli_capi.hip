@@ -66,6 +66,9 @@ constexpr int TX_SMALL_TILE_WAVES = 12000;
 
 struct ProfEntry { const char* name; hipEvent_t a, b; };
 
+// the forms of the CV_64F front pass (lsd_f64.hip): k_lsd_blur64 -> k_lsd_resize64 -> k_lsd_grad64, k_lsd_front64, k_lsd_front64s
+enum class LsdFront { Unfused, Tiled, Stream };
+
 }  // namespace
 
 struct pli_ctx {
@@ -108,9 +111,8 @@ struct pli_ctx {
   // CV_64F pipeline of the LSD front (PLI_PARITY_LSD_F64, lsd_f64.hip)
   bool lsdF64 = false; double* mg = nullptr; unsigned long long* maxMg = nullptr; double* tmp64 = nullptr; double* kern64 = nullptr;
   int* lsdTab64 = nullptr; int lsdRadius = 0;
-  bool lsdFront64 = false;                   // the fused blur -> resize -> gradient pass applies (lsd_f64.hip: k_lsd_front64)
-  bool lsdFrontStream = false;               // ... in its streaming form (k_lsd_front64s), lsdFrontChunk scaled rows per wave
-  int lsdFrontChunk = 0;
+  LsdFront lsdFront = LsdFront::Unfused;     // the form of the front pass that applies to the geometry (a debug context runs Unfused)
+  int lsdFrontChunk = 0;                     // Stream: scaled rows per wave
   int2* hot = nullptr;                       // tile relaxation, CV_64F detector: round 1's 8-byte hot records {angle, owner word} (lsd_tile.hip)
   float2* cold = nullptr;                    // ... and the records' exact {cos, sin}: written instead of the 16-byte records when every round runs on the hot ones
   int2* own = nullptr; RxSeed* smallSeeds = nullptr; RxSeed* bigSeeds = nullptr; int bigCap = 0;
@@ -335,13 +337,18 @@ std::vector<int> buildResizeTab64(int sw, int sh, int dw, int dh, double sc) {
   return t;
 }
 
+// both fused fronts give the source window of a strip of 64 (+ 1) scaled columns 64 columns: of LDS (k_lsd_front64), of lanes (k_lsd_front64s)
+bool frontStripsFit(const std::vector<int>& t, int sw, int dw) {
+  for (int x0 = 0; x0 < dw; x0 += 64) {
+    const int x1 = std::min(x0 + 64, dw - 1);
+    if (std::min(t[x1] + 1, sw - 1) - t[x0] + 1 > 64) return false;
+  }
+  return true;
+}
+
 // the fused front (k_lsd_front64) stages the source window of a 64 x 16 tile of the scaled image in LDS: 64 x 20 at most
 bool frontTiledFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
-  bool fits = radius <= 3;
-  for (int x0 = 0; x0 < dw && fits; x0 += 64) {
-    const int x1 = std::min(x0 + 64, dw - 1);
-    fits = std::min(t[x1] + 1, sw - 1) - t[x0] + 1 <= 64;
-  }
+  bool fits = radius <= 3 && frontStripsFit(t, sw, dw);
   for (int y0 = 0; y0 < dh && fits; y0 += 16) {
     const int y1 = std::min(y0 + 16, dh - 1);
     const int a = std::min(std::max(t[3 * dw + y0], 0), sh - 1), b = std::min(std::max(t[3 * dw + y1] + 1, 0), sh - 1);
@@ -350,17 +357,20 @@ bool frontTiledFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, i
   return fits;
 }
 
-// the streaming front (k_lsd_front64s): radius 3 with one reflection at the borders, the source window of every strip of 64 (+ 1)
-// scaled columns within the wave's 64 lanes, and source rows and columns that advance by 0 or 1 per scaled one
+// the streaming front (k_lsd_front64s): radius 3 with one reflection at the borders, the source window of every strip within the
+// wave's 64 lanes, and source rows and columns that advance by 0 or 1 per scaled one
 bool frontStreamFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
-  if (radius != 3 || sw <= 6 || sh <= 6 || dw < 1 || dh < 1) return false;
-  for (int x0 = 0; x0 < dw; x0 += 64) {
-    const int x1 = std::min(x0 + 64, dw - 1);
-    if (std::min(t[x1] + 1, sw - 1) - t[x0] + 1 > 64) return false;
-  }
+  if (radius != 3 || sw <= 6 || sh <= 6 || dw < 1 || dh < 1 || !frontStripsFit(t, sw, dw)) return false;
   for (int d = 1; d < dw; ++d) if (t[d] - t[d - 1] < 0 || t[d] - t[d - 1] > 1) return false;
   for (int d = 1; d < dh; ++d) if (t[3 * dw + d] - t[3 * dw + d - 1] < 0 || t[3 * dw + d] - t[3 * dw + d - 1] > 1) return false;
   return true;
+}
+
+// the form for a geometry (t: buildResizeTab64); dev switches PLI_LSD_NOFUSE: the three kernels, PLI_LSD_FRONT_TILED: the tiled form
+// where the streaming one applies (A/B, cross-checks)
+LsdFront frontForm(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
+  if (!frontTiledFits(t, sw, sh, dw, dh, radius) || DEVENV("PLI_LSD_NOFUSE")) return LsdFront::Unfused;
+  return frontStreamFits(t, sw, sh, dw, dh, radius) && !DEVENV("PLI_LSD_FRONT_TILED") ? LsdFront::Stream : LsdFront::Tiled;
 }
 
 // scaled rows per wave of the streaming front: each chunk enters 6 source rows to warm its window up, and a strip's chunks are what
@@ -368,6 +378,48 @@ bool frontStreamFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, 
 constexpr int LSD_FRONT_CHUNK = 64;
 int frontStreamChunk(const char* dev) {
   return dev ? std::max(8, std::min(4096, atoi(dev))) : LSD_FRONT_CHUNK;
+}
+
+// One call of the CV_64F front pass (lsd_f64.hip) in the given form on images img0 .. img0 + n - 1: the image's largest norm cleared,
+// then the form's kernels.  The forms share their profile names (k_lsd_front: either fused form).
+struct FrontSrc { const uint8_t* p; int64_t imgStride; int w, h, pitch; };       // u8 images
+struct FrontGeom {
+  const double* kern; int radius;       // the blur (lsdGauss64)
+  const int* tab;                       // buildResizeTab64, or null: lsd_scale 1 (Unfused only: the u8 image as doubles is the scaled image)
+  int dw, dh, dp;                       // scaled width and height, row pitch of the planes written
+  int chunk;                            // Stream: scaled rows per wave
+  double rho;
+  int trigF32;                          // PLI_PARITY_TRIG_F32_LSD
+};
+struct FrontUnfused {                   // Unfused: the double planes between its kernels (images blurStride / scaledStride apart)
+  double* blurred; int64_t blurStride;
+  double* scaled; int64_t scaledStride;       // rows of the TRUE width dw
+  float* angDbg;                        // or null: the debug plane of the angles
+};
+pli_status launchFront64(pli_ctx* c, LsdFront form, const FrontSrc& S, const FrontGeom& G, const LsdFrontPlanes& planes,
+                         unsigned long long* maxMg, int img0, int n, const FrontUnfused& U = {}) {
+  HIPCHK(hipMemsetAsync(maxMg + img0, 0, sizeof(unsigned long long) * n, c->stream));
+  if (form == LsdFront::Stream) {
+    // one wave per strip of 64 scaled columns and chunk of rows, no tile and no barrier
+    const int strips = (G.dw + 63) / 64;
+    LAUNCH(c, "k_lsd_front", k_lsd_front64s, dim3((strips + LSD_FRONT_STREAM_WAVES - 1) / LSD_FRONT_STREAM_WAVES, (G.dh + G.chunk - 1) / G.chunk, n),
+           dim3(64 * LSD_FRONT_STREAM_WAVES), 0, S.p, S.imgStride, S.w, S.h, S.pitch, G.kern, G.tab, G.dw, G.dh, G.dp, G.rho, planes, maxMg,
+           img0, G.trigF32, G.chunk);
+  } else if (form == LsdFront::Tiled) {
+    // blur -> resize -> gradient in one pass over LDS tiles: neither double plane goes to HBM
+    LAUNCH(c, "k_lsd_front", k_lsd_front64, dim3((G.dp + 63) / 64, (G.dh + 15) / 16, n), dim3(256), 0, S.p, S.imgStride, S.w, S.h, S.pitch,
+           G.kern, G.radius, G.tab, G.dw, G.dh, G.dp, G.rho, planes, maxMg, img0, G.trigF32);
+  } else {
+    // (lsd_scale 1: radius 0 and the kernel {1} — the blur writes the scaled plane itself)
+    LAUNCH(c, "k_blur_lsd", k_lsd_blur64, dim3((S.w + 63) / 64, (S.h + 15) / 16, n), dim3(256), 0, S.p, S.imgStride, S.w, S.h, S.pitch, G.kern,
+           G.radius, G.tab ? U.blurred : U.scaled, G.tab ? U.blurStride : U.scaledStride, img0);
+    if (G.tab)
+      LAUNCH(c, "k_resize_lsd", k_lsd_resize64, dim3((G.dw + 255) / 256, G.dh, n), dim3(256), 0, U.blurred, S.w, S.h, U.scaled, G.dw, G.dh,
+             U.scaledStride, G.tab, img0);
+    LAUNCH(c, "k_lsd_grad", k_lsd_grad64, dim3((G.dp + 255) / 256, (G.dh + 15) / 16, n), dim3(256), 0, U.scaled, G.dw, G.dh, G.dp, U.scaledStride,
+           G.rho, planes, maxMg, U.angDbg, img0, G.trigF32);
+  }
+  return PLI_OK;
 }
 
 // cv::resize coefficient tables (see oracle/ocv_prims.hpp for the derivation):
@@ -684,9 +736,7 @@ pli_status allocAll(pli_ctx* c) {
       const std::vector<int> t = buildResizeTab64(P.W, P.H, P.LWt, P.LH, 1. / c->cfg.lsd_scale);
       A(c->lsdTab64, t.size());
       HIPCHK(hipMemcpy(c->lsdTab64, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-      c->lsdFront64 = frontTiledFits(t, P.W, P.H, P.LWt, P.LH, h) && !DEVENV("PLI_LSD_NOFUSE");
-      // the streaming form (k_lsd_front64s) where its own conditions hold; dev switch PLI_LSD_FRONT_TILED: the tiled form (A/B, cross-checks)
-      c->lsdFrontStream = c->lsdFront64 && frontStreamFits(t, P.W, P.H, P.LWt, P.LH, h) && !DEVENV("PLI_LSD_FRONT_TILED");
+      c->lsdFront = frontForm(t, P.W, P.H, P.LWt, P.LH, h);
       c->lsdFrontChunk = frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK"));
     }
   } else {
@@ -1006,44 +1056,21 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
   int2* hotLater = hotAll ? c->hot : (int2*)nullptr;
   float4* recPlane = hotAll ? (float4*)nullptr : c->rec;         // (what the front pass writes: the 16-byte records, or the cold plane)
   float2* coldPlane = hotAll ? c->cold : (float2*)nullptr;
-  const int trigF32 = ((c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0) | (packMode == 2 ? 2 : 0);
+  const int trigF32 = (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0;
   if (c->lsdF64) {
-    // OpenCV 3.x: the detector works on the CV_64FC1 copy of the image (lsd_f64.hip).  The scaled double image lives in
-    // the grower's overflow area (same size, not in use before the growers run).
+    // OpenCV 3.x: the detector works on the CV_64FC1 copy of the image (lsd_f64.hip).  The three kernels' scaled double image lives
+    // in the grower's overflow area (same size, not in use before the growers run): rows of the TRUE width, images npix = pitch x
+    // height apart.  A debug context runs them: PLI_DBG_LSD_SCALED wants the plane.
     double* scaled64 = reinterpret_cast<double*>(c->regScratch);
-    const dim3 gb((P.W + 63) / 64, (P.H + 15) / 16, nimg);
-    if (c->lsdFront64 && !c->debug) {
-      // blur -> resize -> gradient in one pass over LDS tiles: neither double plane goes to HBM
-      HIPCHK(hipMemsetAsync(c->maxMg + img0, 0, sizeof(unsigned long long) * nimg, c->stream));
-      if (c->lsdFrontStream) {
-        // one wave per strip of 64 scaled columns and chunk of rows, no tile and no barrier (both forms under one profile name)
-        const int strips = (P.LWt + 63) / 64, chunk = c->lsdFrontChunk;
-        LAUNCH(c, "k_lsd_front", k_lsd_front64s, dim3((strips + LSD_FRONT_STREAM_WAVES - 1) / LSD_FRONT_STREAM_WAVES, (P.LH + chunk - 1) / chunk, nimg),
-               dim3(64 * LSD_FRONT_STREAM_WAVES), 0, c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch, c->kern64, c->lsdTab64, P.LWt,
-               P.LH, P.LW, P.rho, recPlane, c->mg, ownPlane, c->maxMg, img0, trigF32, hotPlane, coldPlane, chunk);
-      } else {
-      LAUNCH(c, "k_lsd_front", k_lsd_front64, dim3((P.LW + 63) / 64, (P.LH + 15) / 16, nimg), dim3(256), 0, c->pyr + P.lv[0].offset,
-             P.pyrBlock, P.W, P.H, P.lv[0].pitch, c->kern64, c->lsdRadius, c->lsdTab64, P.LWt, P.LH, P.LW, P.rho, recPlane, c->mg, ownPlane,
-             c->maxMg, img0, trigF32, hotPlane, coldPlane);
-      }
-    } else {
-    if (c->cfg.lsd_scale != 1) {
-      LAUNCH(c, "k_blur_lsd", k_lsd_blur64, gb, dim3(256), 0, c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch,
-             c->kern64, c->lsdRadius, c->tmp64, (int64_t)P.W * P.H, img0);
-      LAUNCH(c, "k_resize_lsd", k_lsd_resize64, dim3((P.LWt + 255) / 256, P.LH, nimg), dim3(256), 0, c->tmp64, P.W, P.H, scaled64, P.LWt,
-             P.LH, (int64_t)npix, c->lsdTab64, img0);
-    } else {
-      LAUNCH(c, "k_blur_lsd", k_lsd_blur64, gb, dim3(256), 0, c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch,
-             c->kern64, 0, scaled64, (int64_t)npix, img0);
-    }
-    // (the scaled double plane: rows of the TRUE width, images npix = pitch x height apart)
+    const pli_status st = launchFront64(
+        c, c->debug ? LsdFront::Unfused : c->lsdFront, FrontSrc{c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch},
+        FrontGeom{c->kern64, c->lsdRadius, c->lsdTab64, P.LWt, P.LH, P.LW, c->lsdFrontChunk, P.rho, trigF32},
+        LsdFrontPlanes{recPlane, c->mg, ownPlane, hotPlane, coldPlane, packMode == 2}, c->maxMg, img0, nimg,
+        FrontUnfused{c->tmp64, (int64_t)P.W * P.H, scaled64, (int64_t)npix, c->debug ? c->angDbg : (float*)nullptr});
+    if (st != PLI_OK) return st;
     if (c->debug && c->scaled64Dbg)                    // the plane becomes the growers' arena: keep a copy for PLI_DBG_LSD_SCALED
       HIPCHK(hipMemcpyAsync(c->scaled64Dbg + (int64_t)img0 * npix, scaled64 + (int64_t)img0 * npix, (size_t)nimg * npix * 8,
                             hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->maxMg + img0, 0, sizeof(unsigned long long) * nimg, c->stream));
-    LAUNCH(c, "k_lsd_grad", k_lsd_grad64, dim3((P.LW + 255) / 256, (P.LH + 15) / 16, nimg), dim3(256), 0, scaled64, P.LWt, P.LH, P.LW,
-           (int64_t)npix, P.rho, recPlane, c->mg, ownPlane, c->maxMg, c->debug ? c->angDbg : (float*)nullptr, img0, trigF32, hotPlane, coldPlane);
-    }
   } else {
     const uint8_t* scaled;
     int64_t sStride;
@@ -2271,7 +2298,9 @@ pli_status pli_selftest_hot_trig(pli_ctx* c, double* max_abs_err) {
 
 // The three forms of the CV_64F front pass (lsd_f64.hip) on the caller's images, compared on the device.  The geometry is the call's
 // own (any size from 1 x 1, any scale above 1), not the context's: the context lends its device, stream, rho and flags.
-pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t pack_w,
+// flags bit 0: the owner words carry the norm (LAZY ids); bit 1: the forms write the 16-byte records and the owner plane — what the
+// schedules off the hot records take from the front pass — instead of the hot and cold planes
+pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t flags,
                                      int32_t out[10]) {
   CtxGuard guard__(c);
   if (!c || !imgs || !out || n < 1 || n > 64 || w < 1 || h < 1 || w > 4095 || h > 4095 || !(scale > 1) || !(scale <= 4)) {
@@ -2297,11 +2326,13 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   auto dBlur = plan.add<double>(srcPix * n);
   auto dScaled = plan.add<double>((size_t)dw * dh * n);
   auto dCount = plan.add<unsigned>(8);
-  // per form (0: the three kernels, 1: tiled, 2: streaming): hot, cold, mg, maxMg
-  ScratchBlock<int2> dHot[3] = {plan.add<int2>(npix * n), plan.add<int2>(npix * n), plan.add<int2>(npix * n)};
-  ScratchBlock<float2> dCold[3] = {plan.add<float2>(npix * n), plan.add<float2>(npix * n), plan.add<float2>(npix * n)};
-  ScratchBlock<double> dMg[3] = {plan.add<double>(npix * n), plan.add<double>(npix * n), plan.add<double>(npix * n)};
-  ScratchBlock<unsigned long long> dMax[3] = {plan.add<unsigned long long>(n), plan.add<unsigned long long>(n), plan.add<unsigned long long>(n)};
+  // per form (in the order of LsdFront): the 16-byte records and the owner plane, or the hot and cold planes; mg, maxMg
+  const bool records = (flags & 2) != 0;
+  struct FormOut { ScratchBlock<float4> rec; ScratchBlock<int2> own, hot; ScratchBlock<float2> cold; ScratchBlock<double> mg; ScratchBlock<unsigned long long> max; };
+  std::vector<FormOut> F;
+  for (int f = 0; f < 3; ++f)
+    F.push_back({plan.addIf<float4>(records, npix * n), plan.addIf<int2>(records, npix * n), plan.addIf<int2>(!records, npix * n),
+                 plan.addIf<float2>(!records, npix * n), plan.add<double>(npix * n), plan.add<unsigned long long>(n)});
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
   // (0xA5 everywhere first: a word that a form does not write differs from the other forms' only if they wrote it)
@@ -2310,21 +2341,12 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   HIPCHK(hipMemcpyAsync(dTab, t.data(), t.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dKern, k, sizeof(k), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(dCount, 0, 8 * sizeof(unsigned), c->stream));
-  for (int f = 0; f < 3; ++f) HIPCHK(hipMemsetAsync(dMax[f], 0, sizeof(unsigned long long) * n, c->stream));
-  const int flags = ((c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0) | (pack_w ? 2 : 0);
-  LAUNCH(c, "k_blur_lsd", k_lsd_blur64, dim3((w + 63) / 64, (h + 15) / 16, n), dim3(256), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, radius,
-         dBlur, (int64_t)srcPix, 0);
-  LAUNCH(c, "k_resize_lsd", k_lsd_resize64, dim3((dw + 255) / 256, dh, n), dim3(256), 0, dBlur, w, h, dScaled, dw, dh, (int64_t)dw * dh, dTab, 0);
-  LAUNCH(c, "k_lsd_grad", k_lsd_grad64, dim3((dp + 255) / 256, (dh + 15) / 16, n), dim3(256), 0, dScaled, dw, dh, dp, (int64_t)dw * dh, P.rho,
-         (float4*)nullptr, dMg[0], (int2*)nullptr, dMax[0], (float*)nullptr, 0, flags, dHot[0], dCold[0]);
-  LAUNCH(c, "k_lsd_front", k_lsd_front64, dim3((dp + 63) / 64, (dh + 15) / 16, n), dim3(256), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, radius,
-         dTab, dw, dh, dp, P.rho, (float4*)nullptr, dMg[1], (int2*)nullptr, dMax[1], 0, flags, dHot[1], dCold[1]);
-  if (stream) {
-    const int strips = (dw + 63) / 64;
-    LAUNCH(c, "k_lsd_front", k_lsd_front64s, dim3((strips + LSD_FRONT_STREAM_WAVES - 1) / LSD_FRONT_STREAM_WAVES, (dh + chunk - 1) / chunk, n),
-           dim3(64 * LSD_FRONT_STREAM_WAVES), 0, dSrc, (int64_t)srcPix, w, h, w, dKern, dTab, dw, dh, dp, P.rho, (float4*)nullptr, dMg[2],
-           (int2*)nullptr, dMax[2], 0, flags, dHot[2], dCold[2], chunk);
-  }
+  const FrontSrc S{dSrc, (int64_t)srcPix, w, h, w};
+  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, chunk, P.rho, (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0};
+  const FrontUnfused U{dBlur, (int64_t)srcPix, dScaled, (int64_t)dw * dh, nullptr};
+  for (int f = 0; f < (stream ? 3 : 2); ++f)
+    if ((st = launchFront64(c, LsdFront(f), S, G, LsdFrontPlanes{F[f].rec, F[f].mg, F[f].own, F[f].hot, F[f].cold, flags & 1}, F[f].max, 0, n, U)) != PLI_OK)
+      return st;
   // out[0..3]: the streaming form against the tiled one; out[4..7]: against the three kernels (where the streaming form does not
   // apply, the tiled form — what the host then runs — stands in its place in out[4..7], and out[0..3] are 0)
   const int mine = stream ? 2 : 1;
@@ -2337,10 +2359,16 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   for (int ref = 0; ref < 2; ++ref) {
     const int other = ref == 0 ? 1 : 0, base = ref == 0 ? 0 : 4;
     if (ref == 0 && !stream) continue;
-    if ((st = diff(dHot[mine], dHot[other], npix * n * sizeof(int2), base + 0)) != PLI_OK) return st;
-    if ((st = diff(dCold[mine], dCold[other], npix * n * sizeof(float2), base + 1)) != PLI_OK) return st;
-    if ((st = diff(dMg[mine], dMg[other], npix * n * sizeof(double), base + 2)) != PLI_OK) return st;
-    if ((st = diff(dMax[mine], dMax[other], (size_t)n * sizeof(unsigned long long), base + 3)) != PLI_OK) return st;
+    const FormOut &A = F[mine], &B = F[other];
+    if (records) {
+      if ((st = diff(A.rec, B.rec, npix * n * sizeof(float4), base + 0)) != PLI_OK) return st;
+      if ((st = diff(A.own, B.own, npix * n * sizeof(int2), base + 1)) != PLI_OK) return st;
+    } else {
+      if ((st = diff(A.hot, B.hot, npix * n * sizeof(int2), base + 0)) != PLI_OK) return st;
+      if ((st = diff(A.cold, B.cold, npix * n * sizeof(float2), base + 1)) != PLI_OK) return st;
+    }
+    if ((st = diff(A.mg, B.mg, npix * n * sizeof(double), base + 2)) != PLI_OK) return st;
+    if ((st = diff(A.max, B.max, (size_t)n * sizeof(unsigned long long), base + 3)) != PLI_OK) return st;
   }
   unsigned counts[8];
   HIPCHK(hipMemcpyAsync(counts, dCount, sizeof(counts), hipMemcpyDeviceToHost, c->stream));

@@ -683,17 +683,18 @@ class Frontend:
         check(self.L.pli_selftest_hot_trig(self.h, C.byref(out)))
         return out.value
 
-    def selftest_front_stream(self, imgs, scale=1.2, pack_w=False):
+    def selftest_front_stream(self, imgs, scale=1.2, pack_w=False, records=False):
         """The three forms of the LSD front pass on a batch of u8 images (n, h, w), compared on the device (pli_selftest_front_stream).
 
         Returns {"vs_tiled": (hot, cold, mg, maxMg), "vs_unfused": (...), "chunk": rows per wave, "applied": bool}: counts of differing
-        4-byte words of the streaming form (of the tiled one where the streaming form does not apply) per plane."""
+        4-byte words of the streaming form (of the tiled one where the streaming form does not apply) per plane.  records: the forms
+        write the 16-byte records and the owner plane instead of the hot and cold planes, and the first two counts are theirs."""
         imgs = np.ascontiguousarray(imgs, dtype=np.uint8)
         assert imgs.ndim == 3
         n, h, w = imgs.shape
         out = (C.c_int32 * 10)()
         check(self.L.pli_selftest_front_stream(self.h, imgs.ctypes.data_as(C.POINTER(C.c_uint8)), n, w, h, float(scale),
-                                               1 if pack_w else 0, out))
+                                               (1 if pack_w else 0) | (2 if records else 0), out))
         v = [int(x) for x in out]
         return {"vs_tiled": tuple(v[0:4]), "vs_unfused": tuple(v[4:8]), "chunk": v[8], "applied": bool(v[9])}
 

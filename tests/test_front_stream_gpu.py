@@ -1,7 +1,8 @@
 """The streaming form of the LSD front pass (csrc/lsd_f64.hip: k_lsd_front64s) writes what the tiled form (k_lsd_front64) and the
 three separate kernels (k_lsd_blur64 -> k_lsd_resize64 -> k_lsd_grad64, pinned to the oracle by tests/test_gpu_parity.py) write:
 pli_selftest_front_stream runs the three on a batch of images and counts, on the device, the 4-byte words in which they differ — the
-hot records, the {cos, sin} plane, the norm plane with its pad columns, the largest norm per image.  Every count must be 0.
+hot records, the {cos, sin} plane, the norm plane with its pad columns, the largest norm per image; or, with records=True, the 16-byte
+records and the owner plane in place of the first two.  Every count must be 0.
 
 Sizes (source pixels, scale 1.2 unless stated): widths 53 / 54 / 107 / 75 give scaled widths 64 (one strip, no 65th column), 65 (a
 second strip of one pixel), 128 (two full strips, pitch = width) and 90 (pad columns 90 .. 95); the heights follow the chunk height
@@ -99,6 +100,23 @@ def test_streaming_front_other_scales(fe, chunk, photo, scale):
     w, h = 75, source_for(chunk + 1, scale, at_least=True)
     for name, imgs in batches(photo, h, w):
         check(fe, imgs, "%dx%d x%.1f %s" % (w, h, scale, name), scale=scale)
+
+
+@pytest.mark.parametrize("w", [54, 75])
+def test_forms_agree_on_records_and_owner_plane(fe, chunk, photo, w):
+    """The schedules off the hot records (16-byte-record schedules, the sequential schedule, lsd_mode 1) take the 16-byte records —
+    with the owner word in rec.w where there is no hot record — and the owner plane's start value from whichever form the context
+    chose: the forms must agree on those too.  Scaled widths 65 (a second strip of one pixel) and 90 (pad columns 90 .. 95), the
+    scaled height chunk + 1 (a chunk boundary inside the image)."""
+    h = source_for(chunk + 1)
+    assert scaled(w) == WIDTHS[w] and scaled(h) == chunk + 1
+    for name, imgs in batches(photo, h, w):
+        for pack_w in (False, True):
+            r = fe.selftest_front_stream(imgs, scale=1.2, pack_w=pack_w, records=True)
+            print("%dx%d %s" % (w, h, name), "records, pack_w", pack_w, r)
+            assert r["applied"], (name, r)
+            assert r["vs_tiled"] == ZERO, (name, pack_w, r)
+            assert r["vs_unfused"] == ZERO, (name, pack_w, r)
 
 
 def test_constant_image_has_no_defined_pixel(fe):
