@@ -318,6 +318,22 @@ pli_status pli_selftest_hot_trig(pli_ctx* ctx, double* max_abs_err);
 pli_status pli_selftest_front_stream(pli_ctx* ctx, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t flags,
                                      int32_t out[10]);
 
+/* Self-test of the LSD front pass (not a reference function): runs ONE form of the CV_64F front (csrc/lsd_f64.hip) on n caller-supplied
+ * u8 images — arguments, geometry and what the context lends as for pli_selftest_front_stream — and copies its planes to the host, for
+ * tests that compare them with an independent computation.  form: 0 the three separate kernels, 1 the tiled fused pass, 2 the
+ * streaming fused pass; PLI_ERR_INVALID where that form does not apply to the size or the blur radius (another form never stands in).
+ * All planes have rows of dp = dw rounded up to a multiple of 16 pixels (dw = cvRound(w * scale), dh = cvRound(h * scale)), images
+ * dp * dh pixels apart; `pixels` must be n * dp * dh.  flags bit 0: the owner words carry the unclaimed-norm word.  flags bit 1 clear:
+ * plane_a = the hot records (8 bytes a pixel: the bits of the float angle in degrees, the owner word), plane_b = the cold plane
+ * (two floats a pixel: cos, sin); bit 1 set: plane_a = the 16-byte records (angle, cos, sin, owner word as float bits), plane_b = the
+ * owner plane (two int32 a pixel).  norm: the gradient norm, a double a pixel; max_bits[n]: per image the bits of the largest norm
+ * above rho as a double, 0 where no pixel is above rho; scaled (form 0 only, may be null otherwise): the blurred and enlarged image,
+ * rows of dw doubles, images dw * dh apart.  The device buffers are filled with the byte 0xA5 before the form runs: a word that it
+ * does not write shows as 0xA5A5A5A5. */
+pli_status pli_selftest_front_planes(pli_ctx* ctx, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t form,
+                                     int32_t flags, int64_t pixels, void* plane_a, void* plane_b, double* norm, uint64_t* max_bits,
+                                     double* scaled);
+
 /* The stereo rig of Frame::ComputeStereoMatches (Frame.cc:1005-1008: minZ = mb, maxD = mbf / minZ, depth = mbf / disparity):
  * replaces pli_frontend_config.bf / .fx of an existing context (the extractors' constructors, which create the context in
  * the adapters, do not know the camera; the Frame does: mbf and mK(0,0)).  A no-op when the values are the ones in use. */

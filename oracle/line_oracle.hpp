@@ -29,6 +29,8 @@ struct LsdDebug {
   Img8 scaled;                       // blurred + resized image (CV_8UC1 pipeline)
   std::vector<double> scaled64;      // ... (CV_64FC1 pipeline)
   std::vector<float> angleDeg;       // fastAtan2 degrees, -1024 = NOTDEF
+  std::vector<double> modgrad;       // gradient norm (0 in the last row and column)
+  double max_grad = -1;              // largest norm above rho; <= 0: no pixel above rho
   std::vector<int> order;            // pixel index (y*W'+x) of every list entry, visiting order
   std::vector<float> segments;       // x1,y1,x2,y2 per detected segment (Vec4f), detection order
   int W = 0, H = 0;
@@ -118,6 +120,8 @@ static inline void lsdDetect(const Img8& image, const LsdParams& P, LsdDebug& D)
     }
   }
   D.angleDeg = adeg;
+  D.modgrad = modgrad;
+  D.max_grad = max_grad;
   // ordered list: bin descending, raster order inside a bin.  Covers x<W-1, y<H-1.
   const int n_bins = P.n_bins;
   double bin_coef = (max_grad > 0) ? double(n_bins - 1) / max_grad : 0;

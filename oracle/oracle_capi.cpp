@@ -167,6 +167,23 @@ int orc_get_lsd_angle(void* h, int eye, float* dst) {
   std::memcpy(dst, E.ld.lsd.angleDeg.data(), E.ld.lsd.angleDeg.size() * 4);
   return 0;
 }
+int orc_get_lsd_modgrad(void* h, int eye, double* dst) {
+  Eye& E = ((Frame*)h)->eye[eye];
+  std::memcpy(dst, E.ld.lsd.modgrad.data(), E.ld.lsd.modgrad.size() * 8);
+  return 0;
+}
+// the largest gradient norm above rho; <= 0: no pixel above rho
+double orc_get_lsd_max_grad(void* h, int eye) { return ((Frame*)h)->eye[eye].ld.lsd.max_grad; }
+// {cos, sin} the region grower adds for an accepted pixel of level-line angle deg[i] (fastAtan2 degrees), line_oracle.hpp
+// region_grow: cosOfFloat(float(deg * pi / 180), trig_f32), sinOfFloat(...); cs_sn: n pairs
+int orc_lsd_pixel_trig(const float* deg, int n, int trig_f32, float* cs_sn) {
+  for (int i = 0; i < n; ++i) {
+    const double angle = deg[i] * kDEG_TO_RADS;
+    cs_sn[2 * i] = cosOfFloat(float(angle), trig_f32 != 0);
+    cs_sn[2 * i + 1] = sinOfFloat(float(angle), trig_f32 != 0);
+  }
+  return n;
+}
 int orc_get_lsd_order(void* h, int eye, int* dst, int cap) {
   Eye& E = ((Frame*)h)->eye[eye];
   int n = (int)E.ld.lsd.order.size();

@@ -119,6 +119,8 @@ def lib():
         _lib.orc_fast_atan2.restype = C.c_float
         _lib.orc_fast_atan2.argtypes = [C.c_float, C.c_float]
         _lib.orc_cv_round.argtypes = [C.c_double]
+        _lib.orc_get_lsd_max_grad.restype = C.c_double
+        _lib.orc_get_lsd_max_grad.argtypes = [C.c_void_p, C.c_int]
     return _lib
 
 
@@ -246,6 +248,17 @@ class Frame:
         out = np.zeros((h, w), np.float32)
         self.L.orc_get_lsd_angle(self.h, eye, _p(out))
         return out
+
+    def lsd_modgrad(self, eye):
+        """The gradient norm plane of ll_angle, float64 (h, w): 0 in the last row and column."""
+        w, h = self.lsd_dims(eye)
+        out = np.zeros((h, w), np.float64)
+        self.L.orc_get_lsd_modgrad(self.h, eye, _p(out))
+        return out
+
+    def lsd_max_grad(self, eye):
+        """The largest gradient norm above rho; <= 0 where no pixel is above rho."""
+        return float(self.L.orc_get_lsd_max_grad(self.h, eye))
 
     def lsd_order(self, eye):
         n = self.L.orc_get_lsd_order(self.h, eye, None, 0)
@@ -565,6 +578,15 @@ def sincosf_selfcheck(first, last, step):
 
 def fast_atan2(y, x):
     return float(lib().orc_fast_atan2(C.c_float(y), C.c_float(x)))
+
+
+def lsd_pixel_trig(deg, trig_f32):
+    """{cos, sin} the LSD region grower adds for an accepted pixel of level-line angle `deg` (float32 degrees, any shape): float32
+    (..., 2).  line_oracle.hpp region_grow: cosOfFloat(float(deg * pi / 180), trig_f32), sinOfFloat(...)."""
+    deg = np.ascontiguousarray(deg, dtype=np.float32)
+    out = np.zeros(deg.shape + (2,), np.float32)
+    lib().orc_lsd_pixel_trig(_p(deg), int(deg.size), int(bool(trig_f32)), _p(out))
+    return out
 
 
 def cv_round(v):

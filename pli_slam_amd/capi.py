@@ -131,6 +131,8 @@ _PROTOS = {
     "pli_selftest_hot_trig": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "pli_selftest_front_stream": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                           C.POINTER(C.c_int32)]),
+    "pli_selftest_front_planes": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                          C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pli_lsd_arena_words": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pli_set_stereo_camera": (C.c_int32, [C.c_void_p, C.c_float, C.c_float]),
     "pli_last_counts": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),

@@ -2379,6 +2379,71 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   return PLI_OK;
 }
 
+// One form of the CV_64F front pass (lsd_f64.hip) on the caller's images, its planes copied out: what tests compare with the oracle.
+// Arguments and geometry as pli_selftest_front_stream; form: 0 the three kernels, 1 the tiled pass, 2 the streaming pass — the one
+// asked for or PLI_ERR_INVALID, never another in its place.  flags bit 0 / bit 1 as there: bit 1 clear, plane_a = the hot records
+// (int2), plane_b = the cold plane (float2); bit 1 set, plane_a = the 16-byte records, plane_b = the owner plane (int2).
+pli_status pli_selftest_front_planes(pli_ctx* c, const uint8_t* imgs, int32_t n, int32_t w, int32_t h, double scale, int32_t form,
+                                     int32_t flags, int64_t pixels, void* plane_a, void* plane_b, double* norm, uint64_t* max_bits,
+                                     double* scaled) {
+  CtxGuard guard__(c);
+  if (!c || !imgs || !plane_a || !plane_b || !norm || !max_bits || n < 1 || n > 64 || w < 1 || h < 1 || w > 4095 || h > 4095 ||
+      !(scale > 1) || !(scale <= 4) || form < 0 || form > 2 || (flags & ~3) || (form == 0 && !scaled)) {
+    g_err = "bad argument";
+    return PLI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const int dw = cvRoundd(w * scale), dh = cvRoundd(h * scale), dp = (int)alignUp(dw, 16);
+  const size_t npix = (size_t)dp * dh, srcPix = (size_t)w * h;
+  if (pixels != (int64_t)(npix * n)) { g_err = "the planes hold n * alignUp(dw, 16) * dh pixels"; return PLI_ERR_INVALID; }
+  double k[7];
+  const int radius = lsdGauss64(scale, c->cfg.lsd_sigma_scale, k);
+  if (radius < 0) { g_err = "LSD pre-filter radius > 3 not supported"; return PLI_ERR_INVALID; }
+  const std::vector<int> t = buildResizeTab64(w, h, dw, dh, 1. / scale);
+  const bool tiled = frontTiledFits(t, w, h, dw, dh, radius);
+  if ((form >= 1 && !tiled) || (form == 2 && !frontStreamFits(t, w, h, dw, dh, radius))) {
+    g_err = "this form of the front pass does not apply to this size";
+    return PLI_ERR_INVALID;
+  }
+  const bool records = (flags & 2) != 0, unfused = form == 0;
+  ScratchPlan plan;
+  auto dSrc = plan.add<uint8_t>(srcPix * n);
+  auto dTab = plan.add<int>(t.size());
+  auto dKern = plan.add<double>(7);
+  auto dBlur = plan.addIf<double>(unfused, srcPix * n);
+  auto dScaled = plan.addIf<double>(unfused, (size_t)dw * dh * n);
+  auto dRec = plan.addIf<float4>(records, npix * n);
+  auto dOwn = plan.addIf<int2>(records, npix * n);
+  auto dHot = plan.addIf<int2>(!records, npix * n);
+  auto dCold = plan.addIf<float2>(!records, npix * n);
+  auto dMg = plan.add<double>(npix * n);
+  auto dMax = plan.add<unsigned long long>(n);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  // (0xA5 everywhere first: a word that the form does not write shows)
+  HIPCHK(hipMemsetAsync(plan.base(), 0xA5, plan.bytes(), c->stream));
+  HIPCHK(hipMemcpyAsync(dSrc, imgs, srcPix * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dTab, t.data(), t.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dKern, k, sizeof(k), hipMemcpyHostToDevice, c->stream));
+  const FrontSrc S{dSrc, (int64_t)srcPix, w, h, w};
+  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK")), c->hp.rho,
+                    (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0};
+  const FrontUnfused U{dBlur, (int64_t)srcPix, dScaled, (int64_t)dw * dh, nullptr};
+  if ((st = launchFront64(c, LsdFront(form), S, G, LsdFrontPlanes{dRec, dMg, dOwn, dHot, dCold, flags & 1}, dMax, 0, n, U)) != PLI_OK) return st;
+  if (records) {
+    HIPCHK(hipMemcpyAsync(plane_a, dRec, npix * n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(plane_b, dOwn, npix * n * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+  } else {
+    HIPCHK(hipMemcpyAsync(plane_a, dHot, npix * n * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(plane_b, dCold, npix * n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipMemcpyAsync(norm, dMg, npix * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(max_bits, dMax, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  if (unfused) HIPCHK(hipMemcpyAsync(scaled, dScaled, (size_t)dw * dh * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 pli_status pli_lsd_round_stats(pli_ctx* c, int32_t out[4]) {
   CtxGuard guard__(c);
   if (!c || !out) { g_err = "bad argument"; return PLI_ERR_INVALID; }

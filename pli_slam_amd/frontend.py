@@ -698,6 +698,33 @@ class Frontend:
         v = [int(x) for x in out]
         return {"vs_tiled": tuple(v[0:4]), "vs_unfused": tuple(v[4:8]), "chunk": v[8], "applied": bool(v[9])}
 
+    def selftest_front_planes(self, imgs, form, scale=1.2, pack_w=False, records=False):
+        """One form of the LSD front pass (0 the three kernels, 1 tiled, 2 streaming) on a batch of u8 images (n, h, w), its planes
+        read back (pli_selftest_front_planes); PliError (PLI_ERR_INVALID) where the form does not apply to the size.
+
+        Returns arrays of shape (n, dh, dp, ..) — dp: the planes' row pitch, the scaled width dw rounded up to 16; columns dw .. dp - 1
+        are pad — under "hot" (int32 x 2: angle bits, owner word) and "cold" (float32 x 2: cos, sin), or with records=True under "rec"
+        (float32 x 4: angle, cos, sin, owner word) and "own" (int32 x 2); "norm" (float64), "max_bits" (uint64 per image: the bits of
+        the largest norm above rho, 0: none), "dw", and for form 0 "scaled" (float64 (n, dh, dw))."""
+        imgs = np.ascontiguousarray(imgs, dtype=np.uint8)
+        assert imgs.ndim == 3
+        n, h, w = imgs.shape
+        dw, dh = int(round(w * scale)), int(round(h * scale))      # (cvRound: nearest, ties to even — as Python's round)
+        dp = (dw + 15) // 16 * 16
+        a = np.zeros((n, dh, dp, 4), np.float32) if records else np.zeros((n, dh, dp, 2), np.int32)
+        b = np.zeros((n, dh, dp, 2), np.int32 if records else np.float32)
+        norm = np.zeros((n, dh, dp), np.float64)
+        max_bits = np.zeros(n, np.uint64)
+        scaled = np.zeros((n, dh, dw), np.float64) if form == 0 else None
+        check(self.L.pli_selftest_front_planes(self.h, imgs.ctypes.data_as(C.POINTER(C.c_uint8)), n, w, h, float(scale), int(form),
+                                               (1 if pack_w else 0) | (2 if records else 0), n * dh * dp, ptr(a), ptr(b), ptr(norm),
+                                               ptr(max_bits), ptr(scaled) if scaled is not None else None))
+        out = {"norm": norm, "max_bits": max_bits, "dw": dw}
+        out.update({"rec": a, "own": b} if records else {"hot": a, "cold": b})
+        if scaled is not None:
+            out["scaled"] = scaled
+        return out
+
     def sync(self):
         check(self.L.pli_ctx_sync(self.h))
 

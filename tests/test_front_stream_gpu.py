@@ -1,5 +1,8 @@
 """The streaming form of the LSD front pass (csrc/lsd_f64.hip: k_lsd_front64s) writes what the tiled form (k_lsd_front64) and the
-three separate kernels (k_lsd_blur64 -> k_lsd_resize64 -> k_lsd_grad64, pinned to the oracle by tests/test_gpu_parity.py) write:
+three separate kernels (k_lsd_blur64 -> k_lsd_resize64 -> k_lsd_grad64) write.  (Agreement only: the three forms call the same rule
+code, so a wrong rule is wrong in all of them and the counts stay 0.  tests/test_gpu_parity.py compares the three kernels' scaled and
+angle planes with the oracle on a debug context, at whole-frame sizes; what pins every form's planes to the oracle at the sizes below
+is tests/test_lsd_front_planes_gpu.py.)
 pli_selftest_front_stream runs the three on a batch of images and counts, on the device, the 4-byte words in which they differ — the
 hot records, the {cos, sin} plane, the norm plane with its pad columns, the largest norm per image; or, with records=True, the 16-byte
 records and the owner plane in place of the first two.  Every count must be 0.

@@ -12,33 +12,9 @@ import math
 import numpy as np
 import pytest
 
+from helpers_lsd_front import fast_atan2_deg, true_atan2_deg      # (A) and (B): scalars in, Python floats out
+
 PI = math.pi
-
-
-def fast_atan2_deg(y, x):
-    """Appendix A: fastAtan2(y, x) in degrees, float32 arithmetic."""
-    f = np.float32
-    p1, p3, p5, p7 = (f(0.9997878412794807 * (180 / PI)), f(-0.3258083974640975 * (180 / PI)), f(0.1555786518463281 * (180 / PI)),
-                      f(-0.04432655554792128 * (180 / PI)))
-    x, y = f(x), f(y)
-    ax, ay = abs(x), abs(y)
-    eps = f(2.220446049250313e-16)
-    if ax >= ay:
-        c = f(ay / f(ax + eps)); c2 = f(c * c)
-        a = f(f(f(f(f(f(p7 * c2) + p5) * c2) + p3) * c2 + p1) * c)
-    else:
-        c = f(ax / f(ay + eps)); c2 = f(c * c)
-        a = f(f(90.0) - f(f(f(f(f(f(p7 * c2) + p5) * c2) + p3) * c2 + p1) * c))
-    if x < 0:
-        a = f(f(180.0) - a)
-    if y < 0:
-        a = f(f(360.0) - a)
-    return float(a)
-
-
-def true_atan2_deg(y, x):
-    a = math.degrees(math.atan2(y, x))
-    return a + 360.0 if a < 0 else a
 
 
 def reflect101(i, n):
