@@ -455,7 +455,8 @@ pli_status pli_set_rectify_maps(pli_ctx* ctx, int32_t eye, const float* mapx, co
 /* --- SURVEY.md §8(f) row 4 (RGB-D front-end): Frame::ComputeStereoFromRGBD(imDepth), Frame.cc:1309-1331 ---
  * depth: CV_32F depth image registered to the left image (already scaled by mDepthMapFactor, Tracking.cc), row
  * stride in floats.  For every left keypoint of the last pli_orb_extract(eye 0): d = depth(trunc(v), trunc(u));
- * d > 0 -> mvDepth = d, mvuRight = x - bf/d, else both -1 (the rectified pipeline: mvKeysUn == mvKeys). */
+ * d > 0 -> mvDepth = d, mvuRight = x - bf/d, else both -1 (the rectified pipeline: mvKeysUn == mvKeys).
+ * Only the rows of the keypoints are written: uright and depth_out keep what they held from the keypoint count on. */
 pli_status pli_stereo_from_depth(pli_ctx* ctx, const float* depth, int64_t stride_floats, float* uright, float* depth_out,
                                  int32_t cap);
 

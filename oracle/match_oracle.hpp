@@ -683,6 +683,13 @@ static inline void stereoFromDepth(const pli_keypoint* kp, int n, const float* d
 // descent transform(feature, id, weight, nid, levelsup) (:1230-1272), and
 // transform(features, BowVector, FeatureVector, levelsup) (:1139-1208) for the ORB vocabulary's
 // TF_IDF weighting and L1 scoring (mustNormalize -> BowVector::normalize(L1), BowVector.cpp:59-81).
+// Pinned to the reference's own DBoW2 by tests/test_ref_pin_bow.py (oracle/_ref/pli_ref_bow, tests/golden/bow_ref).
+//
+// The unset node id.  The reference's set-level transform declares `NodeId nid;` uninitialised (:1163) and the per-feature
+// descent stores it only when nid_level <= 0 (:1239, the root) or at level L - levelsup (:1263).  A feature that reaches a
+// leaf above that level (a ragged tree, levelsup < L) leaves it unwritten, and the reference files the feature under whatever
+// the stack held.  This project's rule, not the reference's: such a feature's node id is 0.  transform() below and
+// orc_bow_descend preset it; the device kernel k_bow_descend starts from nid = 0.
 // ---------------------------------------------------------------------------
 struct BowVocabulary {
   struct Node { int parent = 0; std::vector<int> children; uint8_t desc[32] = {0}; double weight = 0; int word_id = -1; };

@@ -300,7 +300,10 @@ void* orc_vocab_create(int k, int L, int n, const int* parent, const uint8_t* is
 void orc_vocab_destroy(void* v) { delete (BowVocabulary*)v; }
 int orc_bow_descend(void* vv, const uint8_t* feat, int n, int levelsup, int* word, double* weight, int* node) {
   const BowVocabulary* v = (const BowVocabulary*)vv;
-  for (int i = 0; i < n; ++i) v->transformFeature(feat + (size_t)i * 32, word[i], weight[i], &node[i], levelsup);
+  for (int i = 0; i < n; ++i) {
+    node[i] = 0;                                            // the unset-node-id rule, see BowVocabulary
+    v->transformFeature(feat + (size_t)i * 32, word[i], weight[i], &node[i], levelsup);
+  }
   return n;
 }
 int orc_bow_vector(void* vv, const uint8_t* feat, int n, int levelsup, unsigned* words, double* values, int cap) {
@@ -308,6 +311,15 @@ int orc_bow_vector(void* vv, const uint8_t* feat, int n, int levelsup, unsigned*
   ((const BowVocabulary*)vv)->transform(feat, n, bow, fv, levelsup);
   int k = 0;
   for (auto& kv : bow) { if (k < cap) { words[k] = kv.first; values[k] = kv.second; } ++k; }
+  return k;
+}
+// the FeatureVector of the same call as (node, feature index) pairs: nodes ascending, indices in insertion order
+int orc_feature_vector(void* vv, const uint8_t* feat, int n, int levelsup, unsigned* nodes, unsigned* index, int cap) {
+  std::map<unsigned, double> bow; std::map<unsigned, std::vector<unsigned>> fv;
+  ((const BowVocabulary*)vv)->transform(feat, n, bow, fv, levelsup);
+  int k = 0;
+  for (auto& kv : fv)
+    for (unsigned i : kv.second) { if (k < cap) { nodes[k] = kv.first; index[k] = i; } ++k; }
   return k;
 }
 // cv::remap INTER_LINEAR of one 8U image (stereo_euroc.cc:166)

@@ -388,6 +388,14 @@ class Vocabulary:
         k = lib().orc_bow_vector(self.h, _p(feat), n, levelsup, _p(words), _p(vals), max(n, 1))
         return words[:k].copy(), vals[:k].copy()
 
+    def feature_vector(self, feat, levelsup=4):
+        """The FeatureVector of the same transform as (node, feature index) pairs, nodes ascending."""
+        feat = np.ascontiguousarray(feat, np.uint8)
+        n = feat.shape[0]
+        nodes = np.zeros(max(n, 1), np.uint32); index = np.zeros(max(n, 1), np.uint32)
+        k = lib().orc_feature_vector(self.h, _p(feat), n, levelsup, _p(nodes), _p(index), max(n, 1))
+        return nodes[:k].copy(), index[:k].copy()
+
 
 def stereo_from_depth(kp, depth, bf):
     kp = np.ascontiguousarray(kp, KEYPOINT_DT)

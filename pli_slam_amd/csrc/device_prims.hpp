@@ -10,6 +10,7 @@
 // __fdiv_rn are plain IEEE operations and rely on -ffp-contract=off to stay unfused.
 #pragma clang fp contract(off)
 #include <cfloat>
+#include <climits>
 #include <cstdint>
 #include "common.hpp"
 
@@ -17,6 +18,9 @@ namespace pli {
 
 // cvRound(float): nearest, ties to even (OpenCV uses cvtss2si).
 __device__ __forceinline__ int cv_round_f(float v) { return __float2int_rn(v); }
+// ... for a caller's values: cvtss2si answers INT_MIN for a NaN and for a value that does not fit an int, where the device's
+// conversion answers 0 and saturates.
+__device__ __forceinline__ int cv_round_f_x86(float v) { return fabsf(v) < 2147483648.f ? __float2int_rn(v) : INT_MIN; }
 
 __device__ __forceinline__ int reflect101(int p, int len) {
   if (len == 1) return 0;

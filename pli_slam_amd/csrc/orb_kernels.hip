@@ -23,7 +23,8 @@ __constant__ signed char c_orb_pattern[1024] = {
 // k_ingest: copy nframes x 2 images (arbitrary stride) into level 0 — or, when the eye has rectification
 // maps, cv::remap(src, dst, mapx, mapy, INTER_LINEAR) (BORDER_CONSTANT 0) fused into the copy
 // (the driver's rectification, Examples/Stereo/stereo_euroc.cc:166-167).  OpenCV 3.3.1 remap for 8U:
-// coordinates to 1/32 px with cvRound(map*32) (saturated to short), bilinear weights (32-fx)(32-fy)*32 ...
+// coordinates to 1/32 px with cvRound(map*32) (as x86 converts: INT_MIN for a NaN or a product that does not
+// fit an int, which lands outside the image; then saturated to short), bilinear weights (32-fx)(32-fy)*32 ...
 // as shorts summing to 2^15 — the all-in-one-pixel weight 32768 does not fit a short and initInterTab2D
 // repairs the block to {32767, 0, 0, 1} — result (sum + 2^14) >> 15.
 // ---------------------------------------------------------------------------
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void k_ingest(const uint8_t* __restrict__ left
       v[k] = 0;
       if (x4 + k >= W) continue;
       const float2 m = map[(int64_t)y * W + x4 + k];
-      const int sx = cv_round_f(__fmul_rn(m.x, 32.f)), sy = cv_round_f(__fmul_rn(m.y, 32.f));
+      const int sx = cv_round_f_x86(__fmul_rn(m.x, 32.f)), sy = cv_round_f_x86(__fmul_rn(m.y, 32.f));
       const int ix = min(max(sx >> 5, -32768), 32767), iy = min(max(sy >> 5, -32768), 32767);
       const int fx = sx & 31, fy = sy & 31;
       int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;

@@ -518,13 +518,17 @@ class Frontend:
                                                ptr(c1), ptr(c2), ptr(R), ptr(t), ptr(l2r), ptr(r2l), ptr(depth), ptr(p3d), C.byref(nm)))
         return nm.value, l2r[:nl], r2l[:nr], depth[:nl], p3d[:nl]
 
-    def stereo_from_depth(self, depth):
-        """Frame::ComputeStereoFromRGBD (Frame.cc:1309): (mvuRight, mvDepth) of the left keypoints from a float depth image."""
+    def stereo_from_depth(self, depth, stride=None):
+        """Frame::ComputeStereoFromRGBD (Frame.cc:1309): (mvuRight, mvDepth) of the left keypoints from a float depth image.
+        stride: row stride of `depth` in floats when its rows are padded ((height, stride) array, the image in the first `width`
+        columns).  Both results have kp_cap rows; the rows beyond the keypoint count are not written by the call and stay 0."""
         d = np.ascontiguousarray(depth, np.float32)
-        assert d.shape == (self.cfg.height, self.cfg.width)
+        if stride is None:
+            stride = self.cfg.width
+        assert stride >= self.cfg.width and d.shape == (self.cfg.height, stride)
         ur = np.zeros(self.kp_cap, np.float32)
         dp = np.zeros(self.kp_cap, np.float32)
-        check(self.L.pli_stereo_from_depth(self.h, ptr(d), d.shape[1], ptr(ur), ptr(dp), self.kp_cap))
+        check(self.L.pli_stereo_from_depth(self.h, ptr(d), stride, ptr(ur), ptr(dp), self.kp_cap))
         return ur, dp
 
     def set_rectify_maps(self, eye, mapx, mapy):

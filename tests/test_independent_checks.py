@@ -124,3 +124,35 @@ def test_fast_atan2_within_its_published_precision(oracle):
         ref = np.degrees(np.arctan2(float(y), float(x))) % 360.0
         d = abs(a - ref)
         assert min(d, 360 - d) <= 0.3
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 3, 4, 5])
+def test_remap_is_bilinear_interpolation_at_a_32nd_of_a_pixel(oracle, seed):
+    """cv::remap INTER_LINEAR, constant-0 border, by definition: bilinear interpolation of the zero-padded image at the map
+    coordinates rounded to 1/32 px.  Pins the algorithm and the 1/32 quantisation, not the repair of the weight table (that stays
+    with tools/pin/).  Bound: the weights (32-fx)(32-fy)*32 ... are exact in 15 bits, so the fixed-point sum is the exact value
+    and only the single rounding to 8 bits remains (0.5); the one inexact block is the all-in-one-pixel weight, repaired to
+    {32767, 0, 0, 1}, which moves the sum by at most 255/32768 before that rounding."""
+    rng = np.random.default_rng(seed)
+    H, W, pad = 40, 56, 6
+    img = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    mx = rng.uniform(-3, W + 3, (H, W)).astype(np.float32)
+    my = rng.uniform(-3, H + 3, (H, W)).astype(np.float32)
+    if seed % 2:                                                            # quarter and half pixels: zero fractions are common
+        mx, my = (np.rint(mx * 4) / 4).astype(np.float32), (np.rint(my * 4) / 4).astype(np.float32)
+    got = oracle.remap_linear(img, mx, my).astype(np.float64)
+    qx = np.rint(mx * np.float32(32)).astype(np.float64) / 32
+    qy = np.rint(my * np.float32(32)).astype(np.float64) / 32
+    x0, y0 = np.floor(qx).astype(np.int64), np.floor(qy).astype(np.int64)
+    fx, fy = qx - x0, qy - y0
+    P = np.pad(img.astype(np.float64), pad)
+    at = lambda yy, xx: P[yy + pad, xx + pad]
+    want = ((1 - fy) * ((1 - fx) * at(y0, x0) + fx * at(y0, x0 + 1)) + fy * ((1 - fx) * at(y0 + 1, x0) + fx * at(y0 + 1, x0 + 1)))
+    err = np.abs(got - want)
+    print("remap seed %d: worst |oracle - bilinear| = %.6f, zero fractions %d" % (seed, err.max(), int(((fx == 0) & (fy == 0)).sum())))
+    assert err.max() <= 0.5 + 255.0 / 32768
+    outside = (x0 >= W) | (x0 + 1 < 0) | (y0 >= H) | (y0 + 1 < 0)
+    assert outside.sum() > 50 and not got[outside].any()
+    assert (got[~outside] > 0).mean() > 0.9
+    if seed % 2:
+        assert ((fx == 0) & (fy == 0)).sum() > 50
