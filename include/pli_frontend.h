@@ -836,6 +836,57 @@ pli_status pli_search_for_initialization(pli_ctx* ctx, const pli_keypoint* kp1, 
                                          float min_x, float max_x, float min_y, float max_y, int32_t window_size, float nnratio,
                                          int32_t check_orientation, int32_t* matches12, int32_t* raw12, int32_t* nmatches);
 
+/* --- The keyframe database's place-recognition queries (KeyFrameDatabase.cc:806-1089) ---
+ * KeyFrameDatabase::DetectRelocalizationCandidates (Tracking.cc:4184) and DetectNBestCandidates (LoopClosing.cc:395) walk an
+ * inverted file of std::list<KeyFrame*> and then score every keyframe that shares enough words with DBoW2's L1Scoring::score
+ * (ScoringObject.cpp:23-68).  pli_kfdb keeps the BowVectors of the keyframes on the device instead and answers, per query and for
+ * EVERY keyframe in one launch, the three numbers those functions derive from the inverted file and the score; the ordered,
+ * stateful rest (minCommonWords, covisibility accumulation, the sort and the filters) stays on the host
+ * (adapters/orbslam_keyframe_database.hpp).
+ *
+ * A database belongs to the context it was created on (as a pli_vocab does) and must be destroyed before it; every call holds the
+ * context's lock and runs on its stream, so the tracking and loop-closing threads may call concurrently.  A keyframe lives in a
+ * SLOT: pli_kfdb_add hands out the smallest free slot id, which stays fixed until pli_kfdb_erase frees it for reuse.  The slot
+ * high-water mark is one more than the largest slot id handed out since creation or the last pli_kfdb_clear.
+ *
+ * Storage: a CSR arena on the device (per slot an offset and a count; word ids uint32_t, strictly ascending within a slot; values
+ * double).  add appends; a full arena doubles (allocate, copy device to device on the stream, free the old one).  erase leaves a
+ * hole; once the holes exceed half of the arena's words the next add rebuilds the arena from the host mirror of the live vectors. */
+typedef struct pli_kfdb pli_kfdb;
+struct pli_kfdb_stats {     /* (no typedef: the name is also the function's; write `struct pli_kfdb_stats`) */
+  int32_t slot_high_water;  /* slots a query answers for                                      */
+  int32_t live_keyframes;
+  int64_t live_words;       /* words of the live keyframes                                    */
+  int64_t arena_words;      /* words appended since the last rebuild / clear: live + holes    */
+  int64_t arena_capacity;   /* words the device arena holds before it doubles                 */
+  int32_t rebuilds;         /* since creation                                                 */
+  int32_t growths;          /* since creation                                                 */
+};
+/* waves of one query launch: min(ceil(nslots / 4), PLI_KFDB_QUERY_MAX_WAVES / 4) workgroups of 4 waves, the slots strided over them */
+#define PLI_KFDB_QUERY_MAX_WAVES 2048
+pli_status pli_kfdb_create(pli_ctx* ctx, pli_kfdb** out);
+void pli_kfdb_destroy(pli_kfdb* db);
+/* One keyframe's BowVector in map order.  PLI_ERR_INVALID: null arguments, n < 0, word ids not strictly ascending;
+ * PLI_ERR_CAPACITY: n > PLI_BOW_MAX_FEATURES (a BowVector has at most one word per feature).  n == 0 is valid.  On an error the
+ * database is unchanged. */
+pli_status pli_kfdb_add(pli_ctx* ctx, pli_kfdb* db, const uint32_t* word, const double* value, int32_t n, int32_t* slot);
+/* PLI_ERR_INVALID for a slot that is free or was never handed out. */
+pli_status pli_kfdb_erase(pli_ctx* ctx, pli_kfdb* db, int32_t slot);
+/* Frees every slot; the high-water mark returns to 0, the arena keeps its capacity. */
+pli_status pli_kfdb_clear(pli_ctx* ctx, pli_kfdb* db);
+pli_status pli_kfdb_stats(const pli_kfdb* db, struct pli_kfdb_stats* out);
+/* The query BowVector (qword strictly ascending, nq <= PLI_BOW_MAX_FEATURES else PLI_ERR_CAPACITY) against every slot below the
+ * high-water mark; nslots must equal it (PLI_ERR_INVALID otherwise: the caller's tables and the database disagree).
+ *   common[s] = the number of words slot s shares with the query (mnRelocWords / mnPlaceRecognitionWords of a fresh query);
+ *   first[s]  = the INDEX IN THE QUERY VECTOR of the first shared word, -1 without one: the reference pushes a keyframe to
+ *               lKFsSharingWords at that word, so (first, order of add) orders that list;
+ *   score[s]  = L1Scoring::score(query, keyframe) as the reference's double, bit for bit: the sum in ascending word order of
+ *               fabs(vi - wi) - fabs(vi) - fabs(wi), vi the query's value, then -sum / 2.0 (-0.0 when nothing is shared).
+ * A free slot and an empty keyframe answer 0, -1, -0.0.  nq == 0 and an empty database are valid.  Per query: one upload of
+ * 12 * nq bytes, one launch (k_kfdb_query), one download of 16 * nslots bytes. */
+pli_status pli_kfdb_query(pli_ctx* ctx, pli_kfdb* db, const uint32_t* qword, const double* qvalue, int32_t nq, int32_t nslots,
+                          int32_t* common, int32_t* first, double* score);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

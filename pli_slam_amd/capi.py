@@ -89,6 +89,16 @@ class TrackLayout(C.Structure):
                 ("kp_cap", C.c_int32), ("kl_cap", C.c_int32)]
 
 
+class KfdbStats(C.Structure):
+    """struct pli_kfdb_stats."""
+    _fields_ = [("slot_high_water", C.c_int32), ("live_keyframes", C.c_int32), ("live_words", C.c_int64),
+                ("arena_words", C.c_int64), ("arena_capacity", C.c_int64), ("rebuilds", C.c_int32), ("growths", C.c_int32)]
+
+
+BOW_MAX_FEATURES = 8192              # PLI_BOW_MAX_FEATURES
+KFDB_QUERY_MAX_WAVES = 2048          # PLI_KFDB_QUERY_MAX_WAVES
+
+
 class PliError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__("%s (%d): %s" % (ERRORS.get(status, "PLI_ERR"), status, msg))
@@ -169,6 +179,14 @@ _PROTOS = {
     "pli_vocab_destroy": (None, [C.c_void_p]),
     "pli_bow_transform": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "pli_kfdb_create": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pli_kfdb_destroy": (None, [C.c_void_p]),
+    "pli_kfdb_add": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "pli_kfdb_erase": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "pli_kfdb_clear": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "pli_kfdb_stats": (C.c_int32, [C.c_void_p, C.POINTER(KfdbStats)]),
+    "pli_kfdb_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "pli_search_by_bow": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                       C.c_void_p]),

@@ -3135,6 +3135,238 @@ pli_status pli_bow_transform(pli_ctx* c, const pli_vocab* v, const uint8_t* desc
   return PLI_OK;
 }
 
+// ---- the keyframe database (include/pli_frontend.h "place-recognition queries"; kfdb_kernels.hip) ---------------
+// The device holds a CSR arena (word / value) and a slot table; the host keeps a mirror of the live vectors (for the rebuild) and of
+// the slot table.  Every mutation ends with the stream idle, so the host vectors it copied from may change afterwards.
+struct pli_kfdb {
+  pli_ctx* ctx = nullptr;
+  uint32_t* dWord = nullptr; double* dValue = nullptr; KfdbSlot* dSlots = nullptr;
+  int64_t cap = 0, used = 0, liveWords = 0;               // arena words: capacity, appended (live + holes), live
+  int slotCap = 0, live = 0, rebuilds = 0, growths = 0;
+  std::vector<KfdbSlot> slots;                             // size = the high-water mark; count < 0: free
+  std::vector<std::vector<uint32_t>> hWord; std::vector<std::vector<double>> hValue;     // per slot, live ones
+  std::set<int> freeSlots;
+  std::vector<uint8_t> qStage; std::vector<KfdbAnswer> aStage;                         // a query's upload and download
+};
+
+namespace {
+
+constexpr int64_t KFDB_FIRST_ARENA = 1 << 14;             // words; doubles from here
+constexpr int KFDB_FIRST_SLOTS = 1024;
+
+bool ascending(const uint32_t* w, int n) {
+  for (int i = 1; i < n; ++i)
+    if (w[i] <= w[i - 1]) return false;
+  return true;
+}
+
+// what the device reads for a slot: a free slot is an empty run
+KfdbSlot deviceSlot(const KfdbSlot& s) { return KfdbSlot{s.count < 0 ? 0 : s.off, s.count < 0 ? 0 : s.count, 0}; }
+
+pli_status kfdbAllocArena(pli_kfdb* db, int64_t words, uint32_t** w, double** v) {
+  *w = nullptr; *v = nullptr;
+  HIPCHK(hipMalloc(w, (size_t)words * 4));
+  hipError_t e = hipMalloc(v, (size_t)words * 8);
+  if (e != hipSuccess) { hipFree(*w); *w = nullptr; g_err = std::string("hipMalloc (keyframe database arena): ") + hipGetErrorString(e); return PLI_ERR_HIP; }
+  return PLI_OK;
+}
+
+// the slot table holds at least n entries (doubling); the whole host table goes up again after a reallocation
+pli_status kfdbSlotTable(pli_ctx* c, pli_kfdb* db, int n) {
+  if (n <= db->slotCap) return PLI_OK;
+  int cap = db->slotCap ? db->slotCap : KFDB_FIRST_SLOTS;
+  while (cap < n) cap *= 2;
+  KfdbSlot* t = nullptr;
+  HIPCHK(hipMalloc(&t, (size_t)cap * sizeof(KfdbSlot)));
+  std::vector<KfdbSlot> img(db->slots.size());
+  for (size_t i = 0; i < img.size(); ++i) img[i] = deviceSlot(db->slots[i]);
+  hipError_t e = img.empty() ? hipSuccess : hipMemcpyAsync(t, img.data(), img.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { hipFree(t); g_err = std::string("keyframe database slot table: ") + hipGetErrorString(e); return PLI_ERR_HIP; }
+  hipFree(db->dSlots);
+  db->dSlots = t; db->slotCap = cap;
+  return PLI_OK;
+}
+
+// The arena rebuilt from the host mirror, with (word, value, n) appended for `slot`: the live vectors in slot order, no holes.
+pli_status kfdbRebuild(pli_ctx* c, pli_kfdb* db, int slot, const uint32_t* word, const double* value, int n) {
+  const int64_t total = db->liveWords + n;
+  int64_t cap = db->cap;
+  while (cap < total) cap *= 2;
+  std::vector<uint32_t> w((size_t)total);
+  std::vector<double> v((size_t)total);
+  std::vector<KfdbSlot> table(db->slots);
+  if ((int)table.size() <= slot) table.resize(slot + 1, KfdbSlot{0, -1, 0});
+  int64_t at = 0;
+  for (int s = 0; s < (int)table.size(); ++s) {
+    const bool isNew = s == slot;
+    if (!isNew && table[s].count < 0) continue;
+    const int cnt = isNew ? n : table[s].count;
+    const uint32_t* sw = isNew ? word : db->hWord[s].data();
+    const double* sv = isNew ? value : db->hValue[s].data();
+    if (cnt) { std::memcpy(&w[at], sw, (size_t)cnt * 4); std::memcpy(&v[at], sv, (size_t)cnt * 8); }
+    table[s] = KfdbSlot{at, cnt, 0};
+    at += cnt;
+  }
+  uint32_t* nw = db->dWord; double* nv = db->dValue;
+  if (cap != db->cap) {
+    pli_status st = kfdbAllocArena(db, cap, &nw, &nv);
+    if (st != PLI_OK) return st;
+  }
+  pli_status st = kfdbSlotTable(c, db, (int)table.size());
+  std::vector<KfdbSlot> img(table.size());
+  for (size_t i = 0; i < img.size(); ++i) img[i] = deviceSlot(table[i]);
+  hipError_t e = hipSuccess;
+  if (st == PLI_OK) {
+    if (total) e = hipMemcpyAsync(nw, w.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(nv, v.data(), (size_t)total * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db->dSlots, img.data(), img.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { g_err = std::string("keyframe database rebuild: ") + hipGetErrorString(e); st = PLI_ERR_HIP; }
+  }
+  if (st != PLI_OK) {
+    if (cap != db->cap) { hipFree(nw); hipFree(nv); }
+    return st;
+  }
+  if (cap != db->cap) { hipFree(db->dWord); hipFree(db->dValue); db->dWord = nw; db->dValue = nv; db->cap = cap; db->growths++; }
+  db->slots.swap(table);
+  db->used = total;
+  db->rebuilds++;
+  return PLI_OK;
+}
+
+}  // namespace
+
+pli_status pli_kfdb_create(pli_ctx* c, pli_kfdb** out) {
+  CtxGuard guard__(c);
+  if (!c || !out) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  *out = nullptr;
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<pli_kfdb, void (*)(pli_kfdb*)> db(new pli_kfdb(), pli_kfdb_destroy);
+  db->ctx = c;
+  pli_status st = kfdbAllocArena(db.get(), KFDB_FIRST_ARENA, &db->dWord, &db->dValue);
+  if (st != PLI_OK) return st;
+  db->cap = KFDB_FIRST_ARENA;
+  if ((st = kfdbSlotTable(c, db.get(), 1)) != PLI_OK) return st;
+  *out = db.release();
+  return PLI_OK;
+}
+
+void pli_kfdb_destroy(pli_kfdb* db) {
+  if (!db) return;
+  CtxGuard guard__(db->ctx);          // (recursive: pli_kfdb_create's failure path comes here with the lock held)
+  hipSetDevice(db->ctx->device);
+  hipFree(db->dWord); hipFree(db->dValue); hipFree(db->dSlots);
+  delete db;
+}
+
+pli_status pli_kfdb_add(pli_ctx* c, pli_kfdb* db, const uint32_t* word, const double* value, int32_t n, int32_t* slotOut) {
+  CtxGuard guard__(c);
+  if (!c || !db || db->ctx != c || !slotOut || n < 0 || (n > 0 && (!word || !value))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (n > PLI_BOW_MAX_FEATURES) { g_err = "a BowVector has at most PLI_BOW_MAX_FEATURES words"; return PLI_ERR_CAPACITY; }
+  if (!ascending(word, n)) { g_err = "word ids must ascend strictly"; return PLI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(c->device));
+  const int slot = db->freeSlots.empty() ? (int)db->slots.size() : *db->freeSlots.begin();
+  if (2 * (db->used - db->liveWords) > db->used) {                    // holes exceed half of the arena's words
+    pli_status st = kfdbRebuild(c, db, slot, word, value, n);
+    if (st != PLI_OK) return st;
+  } else {
+    pli_status st = kfdbSlotTable(c, db, slot + 1);
+    if (st != PLI_OK) return st;
+    if (db->used + n > db->cap) {                                      // full: double, device to device
+      int64_t cap = db->cap;
+      while (cap < db->used + n) cap *= 2;
+      uint32_t* nw; double* nv;
+      if ((st = kfdbAllocArena(db, cap, &nw, &nv)) != PLI_OK) return st;
+      hipError_t e = hipSuccess;
+      if (db->used) e = hipMemcpyAsync(nw, db->dWord, (size_t)db->used * 4, hipMemcpyDeviceToDevice, c->stream);
+      if (e == hipSuccess && db->used) e = hipMemcpyAsync(nv, db->dValue, (size_t)db->used * 8, hipMemcpyDeviceToDevice, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) { hipFree(nw); hipFree(nv); g_err = std::string("keyframe database growth: ") + hipGetErrorString(e); return PLI_ERR_HIP; }
+      hipFree(db->dWord); hipFree(db->dValue);
+      db->dWord = nw; db->dValue = nv; db->cap = cap; db->growths++;
+    }
+    const KfdbSlot entry{db->used, n, 0};
+    if (n) {
+      HIPCHK(hipMemcpyAsync(db->dWord + db->used, word, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(db->dValue + db->used, value, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(db->dSlots + slot, &entry, sizeof(entry), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (slot == (int)db->slots.size()) db->slots.push_back(entry); else db->slots[slot] = entry;
+    db->used += n;
+  }
+  if ((int)db->hWord.size() <= slot) { db->hWord.resize(slot + 1); db->hValue.resize(slot + 1); }
+  db->hWord[slot].assign(word, word + n);
+  db->hValue[slot].assign(value, value + n);
+  db->freeSlots.erase(slot);
+  db->liveWords += n; db->live++;
+  *slotOut = slot;
+  return PLI_OK;
+}
+
+pli_status pli_kfdb_erase(pli_ctx* c, pli_kfdb* db, int32_t slot) {
+  CtxGuard guard__(c);
+  if (!c || !db || db->ctx != c) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (slot < 0 || slot >= (int)db->slots.size() || db->slots[slot].count < 0) { g_err = "the slot holds no keyframe"; return PLI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(c->device));
+  const KfdbSlot empty{0, 0, 0};
+  HIPCHK(hipMemcpyAsync(db->dSlots + slot, &empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  db->liveWords -= db->slots[slot].count; db->live--;
+  db->slots[slot].count = -1;
+  std::vector<uint32_t>().swap(db->hWord[slot]);
+  std::vector<double>().swap(db->hValue[slot]);
+  db->freeSlots.insert(slot);
+  return PLI_OK;
+}
+
+pli_status pli_kfdb_clear(pli_ctx* c, pli_kfdb* db) {
+  CtxGuard guard__(c);
+  if (!c || !db || db->ctx != c) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  db->slots.clear(); db->hWord.clear(); db->hValue.clear(); db->freeSlots.clear();
+  db->used = db->liveWords = 0; db->live = 0;
+  return PLI_OK;
+}
+
+pli_status pli_kfdb_stats(const pli_kfdb* db, struct pli_kfdb_stats* out) {
+  if (!db || !out) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  CtxGuard guard__(db->ctx);
+  out->slot_high_water = (int32_t)db->slots.size(); out->live_keyframes = db->live;
+  out->live_words = db->liveWords; out->arena_words = db->used; out->arena_capacity = db->cap;
+  out->rebuilds = db->rebuilds; out->growths = db->growths;
+  return PLI_OK;
+}
+
+pli_status pli_kfdb_query(pli_ctx* c, pli_kfdb* db, const uint32_t* qword, const double* qvalue, int32_t nq, int32_t nslots,
+                          int32_t* common, int32_t* first, double* score) {
+  CtxGuard guard__(c);
+  if (!c || !db || db->ctx != c || nq < 0 || nslots < 0 || (nq > 0 && (!qword || !qvalue)) ||
+      (nslots > 0 && (!common || !first || !score))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nq > PLI_BOW_MAX_FEATURES) { g_err = "a BowVector has at most PLI_BOW_MAX_FEATURES words"; return PLI_ERR_CAPACITY; }
+  if (!ascending(qword, nq)) { g_err = "word ids must ascend strictly"; return PLI_ERR_INVALID; }
+  if (nslots != (int)db->slots.size()) { g_err = "nslots differs from the database's slot high-water mark"; return PLI_ERR_INVALID; }
+  if (nslots == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto dq = plan.add<uint8_t>((size_t)nq * 12);           // nq values (8-byte aligned), then nq word ids: one upload
+  auto da = plan.add<KfdbAnswer>(nslots);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  db->qStage.resize((size_t)nq * 12);
+  if (nq) { std::memcpy(db->qStage.data(), qvalue, (size_t)nq * 8); std::memcpy(db->qStage.data() + (size_t)nq * 8, qword, (size_t)nq * 4); }
+  db->aStage.resize(nslots);
+  HIPCHK(upload(c, dq, (const uint8_t*)db->qStage.data(), (size_t)nq * 12));
+  uint8_t* q8 = dq;
+  const int blocks = std::min((nslots + KFDB_QUERY_BLOCK / 64 - 1) / (KFDB_QUERY_BLOCK / 64), KFDB_QUERY_MAX_BLOCKS);
+  LAUNCH(c, "k_kfdb_query", k_kfdb_query, dim3(blocks), dim3(KFDB_QUERY_BLOCK), (size_t)nq * 4, (const uint32_t*)(q8 + (size_t)nq * 8),
+         (const double*)q8, nq, db->dSlots, nslots, db->dWord, db->dValue, (KfdbAnswer*)da);
+  HIPCHK(download(c, db->aStage.data(), da, (size_t)nslots));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int s = 0; s < nslots; ++s) { common[s] = db->aStage[s].common; first[s] = db->aStage[s].first; score[s] = db->aStage[s].score; }
+  return PLI_OK;
+}
+
 // ---- the searches of one item against a batch of keyframes (shared host part: KfBatch and the checks above) ----
 pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
                              const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,

@@ -236,6 +236,52 @@ class Frontend:
         check(self.L.pli_bow_transform(self.h, vocab, ptr(d), n, levelsup, ptr(word), ptr(weight), ptr(node)))
         return word, weight, node
 
+    # ---- the keyframe database (KeyFrameDatabase's place-recognition queries) ----
+    def kfdb_create(self):
+        """A keyframe database on this context's device; destroy it (kfdb_destroy) before the context."""
+        h = C.c_void_p()
+        check(self.L.pli_kfdb_create(self.h, C.byref(h)))
+        return h
+
+    def kfdb_destroy(self, db):
+        self.L.pli_kfdb_destroy(db)
+
+    def kfdb_add(self, db, word, value):
+        """KeyFrameDatabase::add of one BowVector (word ids strictly ascending, as the std::map iterates); returns its slot."""
+        w = np.ascontiguousarray(word, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(value, np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise ValueError("one value per word")
+        slot = C.c_int32(-1)
+        check(self.L.pli_kfdb_add(self.h, db, ptr(w), ptr(v), len(w), C.byref(slot)))
+        return slot.value
+
+    def kfdb_erase(self, db, slot):
+        check(self.L.pli_kfdb_erase(self.h, db, int(slot)))
+
+    def kfdb_clear(self, db):
+        check(self.L.pli_kfdb_clear(self.h, db))
+
+    def kfdb_stats(self, db):
+        """struct pli_kfdb_stats as a dict."""
+        st = capi.KfdbStats()
+        check(self.L.pli_kfdb_stats(db, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in capi.KfdbStats._fields_}
+
+    def kfdb_query(self, db, qword, qvalue, nslots=None):
+        """One query BowVector against every slot: (common int32[nslots], first int32[nslots], score float64[nslots]); first is
+        the index in the query vector of the first shared word (-1: none), score the reference's L1 score as its double.
+        nslots: the caller's idea of the slot high-water mark (default: the database's own)."""
+        w = np.ascontiguousarray(qword, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(qvalue, np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise ValueError("one value per word")
+        if nslots is None:
+            nslots = self.kfdb_stats(db)["slot_high_water"]
+        common = np.zeros(nslots, np.int32); first = np.zeros(nslots, np.int32); score = np.zeros(nslots, np.float64)
+        check(self.L.pli_kfdb_query(self.h, db, ptr(w), ptr(v), len(w), nslots, ptr(common), ptr(first), ptr(score)))
+        return common, first, score
+
     def search_by_bow(self, f_desc, f_angle, f_node, kfs, nnratio=0.75, check_orientation=True):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:269-470, F.Nleft == -1) of every keyframe of `kfs`
         against one frame, in one call.  kfs: list of (desc, angle, node, valid) per keyframe; node = the FeatureVector node that
