@@ -149,12 +149,22 @@ enum {
   /* the same choice for `cos(float(angle))` in OpenCV's lsd.cpp region_grow (inside namespace cv, no using-directive:
      the overload depends on whether the C++ <math.h> wrapper is in scope).  Default 0. */
   PLI_PARITY_TRIG_F32_LSD = 2,
-  /* ... and for `cos(direction)` in BinaryDescriptor::computeLBD (binary_descriptor_custom.cpp:1130).  Default 0. */
+  /* ... and for `cos(direction)` in BinaryDescriptor::computeLBD (binary_descriptor_custom.cpp:1130).  Default 0.
+     Measured (tests/test_ref_pin_line.py, DESIGN.md "Oracle"): compiled where it lies with GCC 11 / libstdc++, that file
+     selects the FLOAT overload (= 1), because the reference's own bitarray_custom.hpp includes <math.h>, whose C++ wrapper
+     (libstdc++ of GCC 6 and later) puts the float overloads into the global namespace; the stand-in headers' own regime
+     made no difference.  That contradicts this default, which is kept: an OpenCV 3.3.1 header set and a pre-GCC-6
+     libstdc++ (whose <math.h> is the C header: double) were not measured. */
   PLI_PARITY_TRIG_F32_LBD = 4,
   /* LineSegmentDetector on the CV_64FC1 copy of the image (OpenCV 3.0 .. 3.4: double Gaussian blur, double bilinear
      resize, double gradient) instead of the CV_8UC1 pipeline of the detector re-added in 4.5.x.  Default 1: the reference
      pins OpenCV 3.3.1 (README.md:18-20). */
-  PLI_PARITY_LSD_F64 = 8
+  PLI_PARITY_LSD_F64 = 8,
+  /* the same choice for `atan2( endPointY - startPointY, endPointX - startPointX )` of KeyLine::angle in
+     LSDDetectorC::detectImpl (LSDDetector_custom.cpp:298, two float arguments, inside namespace cv::line_descriptor):
+     1 = atan2f as glibc up to 2.40 computes it (the fdlibm float algorithm), 0 = correctly rounded
+     ((float)atan2((double)y, (double)x)).  Default 0; the same measurement as for PLI_PARITY_TRIG_F32_LBD found 1. */
+  PLI_PARITY_TRIG_F32_KEYLINE = 16
 };
 
 /* Fill `cfg` with the values of Examples/Stereo/Config/EuRoC.yaml for a w x h image

@@ -7,9 +7,9 @@
 //     under /root/reference: restated from the published algorithm, refine = 0)
 //   cv::line_descriptor::BinaryDescriptor::compute / computeLBD
 //                                                 Thirdparty/line_descriptor/src/binary_descriptor_custom.cpp:217-259,350-412,524-687,1026-1372
-// PARITY UNPINNED (no reference tests/golden vectors for this path, OpenCV not
-// runnable here).  Choices the reference leaves open, fixed here and mirrored
-// by the HIP kernels:
+// Pinned to the reference's own compiled code from the detector's output on (buildKeyLines, the cut, computeLBDLine,
+// lbdBinarise, LbdWeights: tests/test_ref_pin_line.py, oracle/Makefile target ref_line); the detector itself is PARITY
+// UNPINNED (OpenCV not runnable here).  Choices the reference leaves open, fixed here and mirrored by the HIP kernels:
 //   * LSD input: OpenCV 3.0-3.4 convert the image to CV_64FC1 first (double blur, double
 //     resize, double gradient: LsdParams::input_f64, the default — the reference pins
 //     3.3.1); the detector re-added in 4.5.x works on CV_8UC1 (u8 fixed-point 7x7
@@ -18,7 +18,9 @@
 //     bins with an unstable std::sort; the earlier linked-list version of the
 //     same file visits them in raster order).
 //   * Lineextractor's std::sort by response is unstable: equal responses keep
-//     detection order (std::stable_sort).
+//     detection order (std::stable_sort; libstdc++'s order differs above 16 lines).
+//   * atan2(float, float) of KeyLine::angle and cos / sin(float) in computeLBD are unqualified: PLI_PARITY_TRIG_F32_KEYLINE /
+//     _LBD choose the overload (a GCC 11 build of the reference selects the float ones; both default to double).
 #pragma once
 #include "ocv_prims.hpp"
 #include "../include/pli_frontend.h"
@@ -238,7 +240,7 @@ static inline void lsdDetect(const Img8& image, const LsdParams& P, LsdDebug& D)
 
 // LSDDetectorC::detectImpl (1 octave), LSDDetector_custom.cpp:264-308
 static inline void buildKeyLines(const std::vector<float>& segs, int imgW, int imgH, double min_length,
-                                 std::vector<pli_keyline>& out) {
+                                 std::vector<pli_keyline>& out, bool angleF32 = false) {
   out.clear();
   int class_counter = -1;
   for (size_t k = 0; k + 3 < segs.size(); k += 4) {
@@ -267,7 +269,8 @@ static inline void buildKeyLines(const std::vector<float>& segs, int imgW, int i
       kl.ePointInOctaveY = e[3];
       kl.lineLength = (float)length;
       kl.numOfPixels = lineIteratorCount(e[0], e[1], e[2], e[3]);
-      kl.angle = (float)std::atan2((double)(kl.endPointY - kl.startPointY), (double)(kl.endPointX - kl.startPointX));
+      // atan2( float, float ), LSDDetector_custom.cpp:298 (PLI_PARITY_TRIG_F32_KEYLINE: which overload)
+      kl.angle = atan2OfFloats(kl.endPointY - kl.startPointY, kl.endPointX - kl.startPointX, angleF32);
       kl.class_id = ++class_counter;
       kl.octave = 0;
       kl.size = (kl.endPointX - kl.startPointX) * (kl.endPointY - kl.startPointY);
@@ -449,16 +452,17 @@ struct LineExtractorCfg {
   double min_line_length = 0.025;
   LsdParams lsd;
   bool lbd_trig_f32 = false;      // PLI_PARITY_TRIG_F32_LBD
+  bool keyline_trig_f32 = false;  // PLI_PARITY_TRIG_F32_KEYLINE
 };
 
-// Lineextractor::operator(), LineExtractor.cc:31-70
-static inline void lineExtract(const Img8& img, const LineExtractorCfg& C, std::vector<pli_keyline>& keylines,
-                               std::vector<uint8_t>& descriptors, LineDebug& D) {
+// Lineextractor::operator() after the detector has returned `segs` (x1, y1, x2, y2 per segment): key lines, cut, blur,
+// Sobel and LBD, LineExtractor.cc:53-66
+static inline void lineExtractFromSegments(const Img8& img, const std::vector<float>& segs, const LineExtractorCfg& C,
+                                           std::vector<pli_keyline>& keylines, std::vector<uint8_t>& descriptors, LineDebug& D) {
   keylines.clear();
   descriptors.clear();
-  lsdDetect(img, C.lsd, D.lsd);
   double min_length = C.min_line_length * (std::min(img.w, img.h));
-  buildKeyLines(D.lsd.segments, img.w, img.h, min_length, keylines);
+  buildKeyLines(segs, img.w, img.h, min_length, keylines, C.keyline_trig_f32);
   if ((int)keylines.size() > C.lsd_nfeatures && C.lsd_nfeatures != 0) {
     std::stable_sort(keylines.begin(), keylines.end(),
                      [](const pli_keyline& a, const pli_keyline& b) { return a.response > b.response; });
@@ -479,6 +483,13 @@ static inline void lineExtract(const Img8& img, const LineExtractorCfg& C, std::
     computeLBDLine(keylines[i], D.dx.data(), D.dy.data(), img.w, img.h, Wt, des, C.lbd_trig_f32);
     lbdBinarise(des, &descriptors[i * 32]);
   }
+}
+
+// Lineextractor::operator(), LineExtractor.cc:31-70
+static inline void lineExtract(const Img8& img, const LineExtractorCfg& C, std::vector<pli_keyline>& keylines,
+                               std::vector<uint8_t>& descriptors, LineDebug& D) {
+  lsdDetect(img, C.lsd, D.lsd);
+  lineExtractFromSegments(img, D.lsd.segments, C, keylines, descriptors, D);
 }
 
 }  // namespace orc

@@ -447,4 +447,63 @@ static inline float glibcCosf(float y) {
 static inline float cosOfFloat(float a, bool f32) { return f32 ? glibcCosf(a) : (float)std::cos((double)a); }
 static inline float sinOfFloat(float a, bool f32) { return f32 ? glibcSinf(a) : (float)std::sin((double)a); }
 
+// ---------------------------------------------------------------------------------------------------------------
+// atan2f as glibc up to 2.40 computes it (sysdeps/ieee754/flt-32/e_atan2f.c over s_atanf.c, the fdlibm algorithm in float
+// arithmetic: up to about one ulp from the correctly rounded value) — what `atan2(float, float)` gives where the float
+// overload is selected (PLI_PARITY_TRIG_F32_KEYLINE).  Finite arguments only.  Checked bit for bit against this image's
+// glibc 2.35 by tests/test_oracle_kat.py.
+// ---------------------------------------------------------------------------------------------------------------
+static inline float f32of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+static inline float glibcAtanf(float x) {
+  // the decimal literals of s_atanf.c (its hexadecimal comments are those of the truncated doubles, not of these floats)
+  static const float hi[4] = {4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f};
+  static const float lo[4] = {5.0121582440e-09f, 3.7748947079e-08f, 3.4473217170e-08f, 7.5497894159e-08f};
+  static const float aT[11] = {3.3333334327e-01f, -2.0000000298e-01f, 1.4285714924e-01f, -1.1111110449e-01f, 9.0908870101e-02f, -7.6918758452e-02f,
+                               6.6610731184e-02f, -5.8335702866e-02f, 4.9768779427e-02f, -3.6531571299e-02f, 1.6285819933e-02f};
+  const int32_t hx = (int32_t)f32bits(x), ix = hx & 0x7fffffff;
+  int id;
+  if (ix >= 0x4c000000) return hx > 0 ? hi[3] + lo[3] : -hi[3] - lo[3];
+  if (ix < 0x3ee00000) {
+    if (ix < 0x31000000) return x;
+    id = -1;
+  } else {
+    x = std::fabs(x);
+    if (ix < 0x3f980000) {
+      if (ix < 0x3f300000) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }
+      else { id = 1; x = (x - 1.0f) / (x + 1.0f); }
+    } else {
+      if (ix < 0x401c0000) { id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x); }
+      else { id = 3; x = -1.0f / x; }
+    }
+  }
+  const float z = x * x, w = z * z;
+  auto A = [&](int i) { return aT[i]; };
+  const float s1 = z * (A(0) + w * (A(2) + w * (A(4) + w * (A(6) + w * (A(8) + w * A(10))))));
+  const float s2 = w * (A(1) + w * (A(3) + w * (A(5) + w * (A(7) + w * A(9)))));
+  if (id < 0) return x - x * (s1 + s2);
+  const float r = hi[id] - ((x * (s1 + s2) - lo[id]) - x);
+  return hx < 0 ? -r : r;
+}
+static inline float glibcAtan2f(float y, float x) {
+  const float tiny = 1.0e-30f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+  const int32_t hx = (int32_t)f32bits(x), hy = (int32_t)f32bits(y), ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+  if (hx == 0x3f800000) return glibcAtanf(y);
+  const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);
+  if (iy == 0) return m == 0 || m == 1 ? y : (m == 2 ? pi + tiny : -pi - tiny);
+  if (ix == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+  const int k = (iy - ix) >> 23;
+  float z;
+  if (k > 60) z = pi_o_2 + 0.5f * pi_lo;
+  else if (hx < 0 && k < -60) z = 0.0f;
+  else z = glibcAtanf(std::fabs(y / x));
+  switch (m) {
+    case 0: return z;
+    case 1: return -z;
+    case 2: return pi - (z - pi_lo);
+    default: return (z - pi_lo) - pi;
+  }
+}
+// atan2 of two floats as the call site selects it: f32 = the float overload, else double libm + cast
+static inline float atan2OfFloats(float y, float x, bool f32) { return f32 ? glibcAtan2f(y, x) : (float)std::atan2((double)y, (double)x); }
+
 }  // namespace orc

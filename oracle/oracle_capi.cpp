@@ -53,6 +53,7 @@ LineExtractorCfg lineCfg(const pli_frontend_config& c) {
   L.lsd.input_f64 = (c.parity_flags & PLI_PARITY_LSD_F64) != 0;
   L.lsd.trig_f32 = (c.parity_flags & PLI_PARITY_TRIG_F32_LSD) != 0;
   L.lbd_trig_f32 = (c.parity_flags & PLI_PARITY_TRIG_F32_LBD) != 0;
+  L.keyline_trig_f32 = (c.parity_flags & PLI_PARITY_TRIG_F32_KEYLINE) != 0;
   return L;
 }
 
@@ -139,6 +140,19 @@ int orc_line_extract(void* h, int eye, const uint8_t* img, int w, int hgt, int64
   Img8 I = wrap(img, w, hgt, stride);
   E.imgW = w; E.imgH = hgt;
   lineExtract(I, lineCfg(f->cfg), E.kls, E.ldesc, E.ld);
+  return (int)E.kls.size();
+}
+// The part of orc_line_extract after the detector, on a caller's segment list (nseg x {x1, y1, x2, y2}); the list is what
+// orc_get_lsd_segments returns afterwards.
+int orc_line_extract_from_segments(void* h, int eye, const uint8_t* img, int w, int hgt, int64_t stride, const float* segs, int nseg) {
+  Frame* f = (Frame*)h;
+  Eye& E = f->eye[eye];
+  Img8 I = wrap(img, w, hgt, stride);
+  E.imgW = w; E.imgH = hgt;
+  E.ld.lsd = LsdDebug();
+  E.ld.lsd.segments.assign(segs, segs + (size_t)nseg * 4);
+  const std::vector<float> S = E.ld.lsd.segments;
+  lineExtractFromSegments(I, S, lineCfg(f->cfg), E.kls, E.ldesc, E.ld);
   return (int)E.kls.size();
 }
 int orc_get_keylines(void* h, int eye, pli_keyline* kl, uint8_t* desc) {
@@ -531,6 +545,24 @@ long orc_sincosf_selfcheck(uint32_t first, uint32_t last, uint32_t step) {
     const uint32_t u = (uint32_t)b;
     std::memcpy(&x, &u, 4);
     if (cosf(x) != glibcCosf(x) || sinf(x) != glibcSinf(x)) ++bad;
+  }
+  return bad;
+}
+float orc_glibc_atan2f(float y, float x) { return glibcAtan2f(y, x); }
+// check of the atan2f restatement against the libm of this machine on n pseudo-random pairs of [-range, range)^2 (every 7th on a
+// grid of eighths, as differences of clamped end points often are) and on the axes: returns the number of pairs that differ
+long orc_atan2f_selfcheck(long n, float range) {
+  long bad = 0;
+  uint64_t st = 0x9E3779B97F4A7C15ull;
+  auto next = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (float)((double)(st >> 11) / 9007199254740992.0 * 2.0 - 1.0) * range; };
+  for (long i = 0; i < n; ++i) {
+    float y = next(), x = next();
+    if (i % 7 == 0) { y = std::nearbyint(y * 8) / 8; x = std::nearbyint(x * 8) / 8; }
+    if (i % 101 == 0) y = 0.f;
+    if (i % 103 == 0) x = 0.f;
+    if (i % 107 == 0) x = 1.f;
+    if (i % 109 == 0) y = -0.f;
+    if (f32bits(atan2f(y, x)) != f32bits(glibcAtan2f(y, x))) ++bad;
   }
   return bad;
 }

@@ -26,7 +26,7 @@ PROJ_QUERY_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("ur", 
 assert KEYPOINT_DT.itemsize == 24 and KEYLINE_DT.itemsize == 68 and PROJ_QUERY_DT.itemsize == 32
 
 
-PARITY_TRIG_F32_ORB, PARITY_TRIG_F32_LSD, PARITY_TRIG_F32_LBD, PARITY_LSD_F64 = 1, 2, 4, 8
+PARITY_TRIG_F32_ORB, PARITY_TRIG_F32_LSD, PARITY_TRIG_F32_LBD, PARITY_LSD_F64, PARITY_TRIG_F32_KEYLINE = 1, 2, 4, 8, 16
 
 
 class Config(C.Structure):
@@ -219,6 +219,18 @@ class Frame:
     def line_extract(self, eye, img):
         img = _u8(img)
         n = self.L.orc_line_extract(self.h, eye, _p(img), img.shape[1], img.shape[0], C.c_int64(img.strides[0]))
+        kl = np.zeros(n, KEYLINE_DT)
+        desc = np.zeros((n, 32), np.uint8)
+        if n:
+            self.L.orc_get_keylines(self.h, eye, _p(kl), _p(desc))
+        return n, kl, desc
+
+    def line_extract_from_segments(self, eye, img, segs):
+        """line_extract with the detector's output given: segs (n, 4) float32 rows of x1, y1, x2, y2."""
+        img = _u8(img)
+        segs = np.ascontiguousarray(segs, np.float32).reshape(-1, 4)
+        n = self.L.orc_line_extract_from_segments(self.h, eye, _p(img), img.shape[1], img.shape[0], C.c_int64(img.strides[0]),
+                                                  _p(segs), len(segs))
         kl = np.zeros(n, KEYLINE_DT)
         desc = np.zeros((n, 32), np.uint8)
         if n:
@@ -582,6 +594,17 @@ def sincosf_selfcheck(first, last, step):
     """Floats (by bit pattern) in [first, last) on which the sincosf restatement differs from this machine's cosf/sinf."""
     L_ = lib(); L_.orc_sincosf_selfcheck.restype = C.c_long; L_.orc_sincosf_selfcheck.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     return int(L_.orc_sincosf_selfcheck(first, last, step))
+
+
+def glibc_atan2f(y, x):
+    L_ = lib(); L_.orc_glibc_atan2f.restype = C.c_float; L_.orc_glibc_atan2f.argtypes = [C.c_float, C.c_float]
+    return float(L_.orc_glibc_atan2f(C.c_float(y), C.c_float(x)))
+
+
+def atan2f_selfcheck(n, value_range):
+    """Pairs, out of n pseudo-random ones of [-value_range, value_range)^2, on which the atan2f restatement differs from this machine's."""
+    L_ = lib(); L_.orc_atan2f_selfcheck.restype = C.c_long; L_.orc_atan2f_selfcheck.argtypes = [C.c_long, C.c_float]
+    return int(L_.orc_atan2f_selfcheck(n, value_range))
 
 
 def fast_atan2(y, x):

@@ -1,0 +1,1 @@
+#include "pli_line_shim.hpp"

@@ -154,6 +154,67 @@ __device__ __forceinline__ void sincos_of_float(float a, bool f32, float* sn, fl
   }
 }
 
+// atan2f as glibc up to 2.40 computes it (e_atan2f.c over s_atanf.c: the fdlibm algorithm in float arithmetic, every
+// operation rounded on its own; tests/test_oracle_kat.py checks the same restatement against the host libm).  Used where
+// the reference's unqualified atan2(float, float) selects the float overload (PLI_PARITY_TRIG_F32_KEYLINE).  Finite
+// arguments only.
+__device__ __forceinline__ float glibc_atanf(float x) {
+  // atanhi / atanlo of 0.5, 1, 1.5 and infinity (selected, not indexed: no private array)
+  const float hi0 = 4.6364760399e-01f, hi1 = 7.8539812565e-01f, hi2 = 9.8279368877e-01f, hi3 = 1.5707962513e+00f;
+  const float lo0 = 5.0121582440e-09f, lo1 = 3.7748947079e-08f, lo2 = 3.4473217170e-08f, lo3 = 7.5497894159e-08f;
+  const float a0 = 3.3333334327e-01f, a1 = -2.0000000298e-01f, a2 = 1.4285714924e-01f, a3 = -1.1111110449e-01f, a4 = 9.0908870101e-02f,
+              a5 = -7.6918758452e-02f, a6 = 6.6610731184e-02f, a7 = -5.8335702866e-02f, a8 = 4.9768779427e-02f, a9 = -3.6531571299e-02f,
+              a10 = 1.6285819933e-02f;
+  const int hx = __float_as_int(x), ix = hx & 0x7fffffff;
+  int id;
+  if (ix >= 0x4c000000) return hx > 0 ? __fadd_rn(hi3, lo3) : __fsub_rn(-hi3, lo3);
+  if (ix < 0x3ee00000) {
+    if (ix < 0x31000000) return x;
+    id = -1;
+  } else {
+    x = fabsf(x);
+    if (ix < 0x3f980000) {
+      if (ix < 0x3f300000) { id = 0; x = __fdiv_rn(__fsub_rn(__fmul_rn(2.0f, x), 1.0f), __fadd_rn(2.0f, x)); }
+      else { id = 1; x = __fdiv_rn(__fsub_rn(x, 1.0f), __fadd_rn(x, 1.0f)); }
+    } else {
+      if (ix < 0x401c0000) { id = 2; x = __fdiv_rn(__fsub_rn(x, 1.5f), __fadd_rn(1.0f, __fmul_rn(1.5f, x))); }
+      else { id = 3; x = __fdiv_rn(-1.0f, x); }
+    }
+  }
+  const float z = __fmul_rn(x, x), w = __fmul_rn(z, z);
+  float s1 = __fadd_rn(a8, __fmul_rn(w, a10));
+  s1 = __fadd_rn(a6, __fmul_rn(w, s1));
+  s1 = __fadd_rn(a4, __fmul_rn(w, s1));
+  s1 = __fadd_rn(a2, __fmul_rn(w, s1));
+  s1 = __fmul_rn(z, __fadd_rn(a0, __fmul_rn(w, s1)));
+  float s2 = __fadd_rn(a7, __fmul_rn(w, a9));
+  s2 = __fadd_rn(a5, __fmul_rn(w, s2));
+  s2 = __fadd_rn(a3, __fmul_rn(w, s2));
+  s2 = __fmul_rn(w, __fadd_rn(a1, __fmul_rn(w, s2)));
+  const float xs = __fmul_rn(x, __fadd_rn(s1, s2));
+  if (id < 0) return __fsub_rn(x, xs);
+  const float hi = id == 0 ? hi0 : id == 1 ? hi1 : id == 2 ? hi2 : hi3, lo = id == 0 ? lo0 : id == 1 ? lo1 : id == 2 ? lo2 : lo3;
+  const float r = __fsub_rn(hi, __fsub_rn(__fsub_rn(xs, lo), x));
+  return hx < 0 ? -r : r;
+}
+__device__ __forceinline__ float glibc_atan2f(float y, float x) {
+  const float tiny = 1.0e-30f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+  const int hx = __float_as_int(x), hy = __float_as_int(y), ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+  if (hx == 0x3f800000) return glibc_atanf(y);
+  const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);
+  if (iy == 0) return m < 2 ? y : (m == 2 ? __fadd_rn(pi, tiny) : __fsub_rn(-pi, tiny));
+  if (ix == 0) return hy < 0 ? __fsub_rn(-pi_o_2, tiny) : __fadd_rn(pi_o_2, tiny);
+  const int k = (iy - ix) >> 23;
+  float z;
+  if (k > 60) z = __fadd_rn(pi_o_2, __fmul_rn(0.5f, pi_lo));
+  else if (hx < 0 && k < -60) z = 0.0f;
+  else z = glibc_atanf(fabsf(__fdiv_rn(y, x)));
+  if (m == 0) return z;
+  if (m == 1) return -z;
+  if (m == 2) return __fsub_rn(pi, __fsub_rn(z, pi_lo));
+  return __fsub_rn(__fsub_rn(z, pi_lo), pi);
+}
+
 // (tile-sequential relaxation) the region of rank o was just stamped dirty for this round — the caller won the stamp, so this
 // runs once per region and round: its seed goes on the list of the seed's tile (at most ts * ts seeds per tile: no overflow)
 __device__ __forceinline__ void tx_dirty_append(const TxDirtyLists& DL, int img, int o) {

@@ -1396,7 +1396,9 @@ __global__ __launch_bounds__(256) void k_keylines(const DevParams* __restrict__ 
         kl.lineLength = (float)length;
         const int ix1 = cv_round_f(e0), iy1 = cv_round_f(e1), ix2 = cv_round_f(e2), iy2 = cv_round_f(e3);
         kl.numOfPixels = max(abs(ix2 - ix1), abs(iy2 - iy1)) + 1;
-        kl.angle = (float)atan2((double)__fsub_rn(e3, e1), (double)__fsub_rn(e2, e0));
+        // atan2( float, float ), LSDDetector_custom.cpp:298 (PLI_PARITY_TRIG_F32_KEYLINE: which overload)
+        kl.angle = (P.parityFlags & PLI_PARITY_TRIG_F32_KEYLINE) ? glibc_atan2f(__fsub_rn(e3, e1), __fsub_rn(e2, e0))
+                                                                 : (float)atan2((double)__fsub_rn(e3, e1), (double)__fsub_rn(e2, e0));
         kl.octave = 0;
         kl.size = __fmul_rn(__fsub_rn(e2, e0), __fsub_rn(e3, e1));
         kl.response = __fdiv_rn(kl.lineLength, (float)max(imgW, imgH));

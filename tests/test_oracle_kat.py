@@ -368,6 +368,23 @@ def test_sincosf_restatement_equals_this_machines_libm(oracle):
     assert abs(oracle.glibc_cosf(1.0) - 0.5403023) < 1e-7 and abs(oracle.glibc_sinf(2.5) - 0.5984721) < 1e-7
 
 
+def test_atan2f_restatement_equals_this_machines_libm(oracle):
+    """PLI_PARITY_TRIG_F32_KEYLINE: the restated atan2f (the fdlibm float algorithm of glibc up to 2.40) against the libm of this
+    machine, bit for bit, on two million pairs within the range of end-point differences (images up to 2048 px), the axes, x == 1
+    and signed zeros, and on a few hand values.  It is not the correctly rounded function: the sample must hold pairs where the
+    two differ, or the check would say nothing."""
+    assert oracle.atan2f_selfcheck(2000000, 2048.0) == 0
+    assert oracle.atan2f_selfcheck(200000, 3.0) == 0
+    assert oracle.glibc_atan2f(0.0, 1.0) == 0.0 and oracle.glibc_atan2f(0.0, -1.0) == float(np.float32(np.pi))
+    assert oracle.glibc_atan2f(1.0, 0.0) == float(np.float32(np.pi / 2)) and oracle.glibc_atan2f(-1.0, 0.0) == -float(np.float32(np.pi / 2))
+    rng = np.random.default_rng(5)
+    y, x = rng.uniform(-300, 300, 4000).astype(np.float32), rng.uniform(-300, 300, 4000).astype(np.float32)
+    mine = np.array([oracle.glibc_atan2f(float(a), float(b)) for a, b in zip(y, x)], np.float32)
+    exact = np.arctan2(y.astype(np.float64), x.astype(np.float64))
+    assert np.all(np.abs(mine.astype(np.float64) - exact) <= 1.5 * np.spacing(np.abs(exact).astype(np.float32)).astype(np.float64))
+    assert np.any(mine != exact.astype(np.float32))
+
+
 def test_lsd_f64_pipeline_primitives(oracle):
     """CV_64F Gaussian blur of a constant image is the constant (kernel sums to 1 within rounding); bilinear resize of a linear
     ramp stays linear in the interior with slope 1 / scale."""

@@ -14,6 +14,9 @@
 //       $R/Thirdparty/line_descriptor/src/LSDDetector_custom.cpp $R/Thirdparty/line_descriptor/src/binary_descriptor_custom.cpp \
 //       -I$R -I$R/include -I$R/Thirdparty/line_descriptor/include -I/usr/include/eigen3 `pkg-config --cflags --libs opencv`
 //
+// It is no longer the only whole-extractor pin: oracle/Makefile (targets ref_orb, ref_line) compiles the same sources where they lie
+// against stand-in headers and tests/test_ref_pin_orb.py / tests/test_ref_pin_line.py hold the oracle to what they return; those pins
+// run over OUR restatement of the OpenCV primitives, this program over the real OpenCV 3.3.1 and its header regime.
 // It has never been compiled in this repository's build image (no OpenCV, no Eigen): it is written against the reference's headers
 // (include/ORBextractor.h:53-87, include/LineExtractor.h:44-51, descriptor_custom.hpp:105-144) and kept deliberately plain.
 #include <opencv2/core/core.hpp>
