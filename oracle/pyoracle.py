@@ -358,7 +358,7 @@ def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occ
 
 
 def track_queries(last_kp, last_depth, Tlw, Tcw, fx, fy, cx, cy, bf, th, mono, scale_factors):
-    """Projection part of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:2190-2244): the pli_proj_query table."""
+    """Projection part of SearchByProjection(CurrentFrame, LastFrame, th, bMono, match12) (ORBmatcher.cc:2190-2244): the pli_proj_query table."""
     kp = np.ascontiguousarray(last_kp, KEYPOINT_DT)
     dp = np.ascontiguousarray(last_depth, np.float32)
     Tl = np.ascontiguousarray(Tlw, np.float32).reshape(12)

@@ -1,0 +1,3 @@
+// ORACLE — TEST INFRASTRUCTURE ONLY.
+// Stand-in for <opencv2/core/core.hpp>, written for this project: everything is in pli_match_shim.hpp.
+#include "pli_match_shim.hpp"

@@ -648,6 +648,20 @@ inline void triangulationGeometry(const float R1w[9], const float t1w[3], const 
   gemm(A, false, 1.0, R12, false, 3, nullptr, B);
   gemm(B, false, 1.0, K2i, false, 3, nullptr, F12);
 }
+
+// Where the two SearchByProjection(CurrentFrame, LastFrame, ...) overloads put a camera-frame point in the image, in the reference's
+// float operation order: pinholeProject = CurrentFrame.mpCamera->project(x3Dc) of the overload without match12 (ORBmatcher.cc:2002,
+// Pinhole.cpp:30-33: fx * x / z + cx); otherwise the overload with match12 (:2222-2223: fx * xc * invzc + cx, invzc = 1.0 / zc).
+inline void lastFrameProjection(float fx, float fy, float cx, float cy, float xc, float yc, float zc, float invzc, bool pinholeProject,
+                                float& u, float& v) {
+  if (pinholeProject) {
+    u = fx * xc / zc + cx;
+    v = fy * yc / zc + cy;
+  } else {
+    u = fx * xc * invzc + cx;
+    v = fy * yc * invzc + cy;
+  }
+}
 }  // namespace pli_detail
 
 // The parts of ORB_SLAM3::ORBmatcher on the hot path.  Template on the tree's Frame / MapPoint so that this header does
@@ -661,14 +675,24 @@ class PliORBmatcher {
   // ORBmatcher.cc:2495-2511 (bit-twiddling popcount over 8 x 32 bits): the same number as 4 x popcount(64)
   static int DescriptorDistance(const cv::Mat& a, const cv::Mat& b) { return pli::descriptorDistance(a.ptr<uint8_t>(), b.ptr<uint8_t>()); }
 
+  // ORBmatcher.cc:1961-2177 (Nleft == -1).  It differs from the overload below in ONE expression: it projects with
+  // CurrentFrame.mpCamera->project(x3Dc), Pinhole.cpp:30-33: fx * x / z + cx (:2002), where the other has fx * xc * invzc + cx (:2222);
+  // the two round differently (tests/golden/match_ref/frame_forms.npz: the reference's own answers tell them apart).
   int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono) {
     std::map<int, int> m;
-    return SearchByProjection(CurrentFrame, LastFrame, th, bMono, m);
+    return searchLastFrame(CurrentFrame, LastFrame, th, bMono, m, true);
   }
 
   // ORBmatcher.cc:2179-2323.  The projection (lines 2190-2244) is the reference's own cv::Mat arithmetic, run here on the host;
   // the window search, the "already taken" exclusion, TH_HIGH, the rotation histogram and ComputeThreeMaxima run on the GPU.
   int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono, std::map<int, int>& match12) {
+    return searchLastFrame(CurrentFrame, LastFrame, th, bMono, match12, false);
+  }
+
+ protected:
+  // What the two SearchByProjection(CurrentFrame, LastFrame, ...) overloads share; pinholeProject: the projection of :2002.
+  int searchLastFrame(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono, std::map<int, int>& match12,
+                      const bool pinholeProject) {
     match12.clear();
     const cv::Mat Rcw = CurrentFrame.mTcw.rowRange(0, 3).colRange(0, 3);
     const cv::Mat tcw = CurrentFrame.mTcw.rowRange(0, 3).col(3);
@@ -693,8 +717,8 @@ class PliORBmatcher {
       const float yc = x3Dc.at<float>(1);
       const float invzc = 1.0 / x3Dc.at<float>(2);
       if (invzc < 0) continue;
-      Q.u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
-      Q.v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
+      pli_detail::lastFrameProjection(CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, xc, yc, x3Dc.at<float>(2), invzc,
+                                      pinholeProject, Q.u, Q.v);
       const int nLastOctave = LastFrame.mvKeys[i].octave;
       Q.radius = th * CurrentFrame.mvScaleFactors[nLastOctave];
       if (bForward) { Q.min_level = nLastOctave; Q.max_level = -1; }
@@ -741,6 +765,7 @@ class PliORBmatcher {
     return nmatches;
   }
 
+ public:
   // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches), ORBmatcher.cc:269-470, for a frame of
   // one camera or rectified stereo (F.Nleft == -1) and a keyframe without a second camera: the node walk, TH_LOW, the ratio test,
   // the rotation histogram and ComputeThreeMaxima run on the GPU.  KeyFrameT needs N, mDescriptors, mvKeysUn, mFeatVec,

@@ -965,8 +965,9 @@ __global__ __launch_bounds__(64) void k_proj_assign_fisheye(
 
 // ---------------------------------------------------------------------------
 // Frame-to-frame track matching of a whole batch on the device tables (pli_batch_track): frame i against frame i-1.
-//   k_track_queries     the projection part of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono)
-//                       (ORBmatcher.cc:2190-2244) with LastFrame's stereo points standing for its map points
+//   k_track_queries     the projection part of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono, match12)
+//                       (ORBmatcher.cc:2190-2244: fx*xc*invzc + cx; the overload without match12 has Pinhole::project)
+//                       with LastFrame's stereo points standing for its map points
 //                       (Frame::UnprojectStereo, Frame.cc:1334-1350, as Tracking::UpdateLastFrame creates them)
 //   k_track_candidates / k_track_assign   the two-phase search above, one launch for all frame pairs
 //   k_track_lines       match(last.mDescriptors_Line, cur.mDescriptors_Line, nnr, matches_12) (LineMatcher.cpp:201-229)

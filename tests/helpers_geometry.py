@@ -1,6 +1,6 @@
 """An independent float64 restatement of the two stages that do camera geometry in floating point, CPU only, plain numpy.
 
-  * track_expect     the projection half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+  * track_expect     the projection half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono, match12)
                      (ORBmatcher.cc:2190-2244) with Frame::UnprojectStereo (Frame.cc:1334-1350) and mOw / mRwc of
                      Frame::UpdatePoseMatrices standing behind the last frame's map points;
   * fisheye_expect   KannalaBrandt8::TriangulateMatches / unproject / project / Triangulate (KannalaBrandt8.cpp:28-42,

@@ -1015,8 +1015,11 @@ def three_maxima(sizes):
     return ind, "maxima_three_kept"
 
 
-def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occupied=None):
-    """-> nmatches, best (after the rotation filter), raw (before it), exits, call_tags."""
+def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occupied=None, misread=()):
+    """-> nmatches, best (after the rotation filter), raw (before it), exits, call_tags.  misread: deliberate misreadings that
+    tests/test_ref_pin_match.py wants rejected ("min_last": of equal distances the last in walking order; "index_order": the window
+    walked in index order; "rot_trunc": the rotation bin by truncation; "th_high_strict": bestDist < TH_HIGH; "bounds_half_open":
+    a projection on mnMaxX / mnMaxY leaves)."""
     nq, ncur = len(q), len(kp)
     px, py, ingrid, gw, gh = _cells(kp, bounds)
     assigned = np.zeros(ncur, bool) if occupied is None else (np.asarray(occupied) != 0)
@@ -1031,7 +1034,11 @@ def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occ
             exits[i] = ("invalid",); continue
         if Q["u"] < minx or Q["u"] > maxx or Q["v"] < miny or Q["v"] > maxy:
             exits[i] = ("outside_bounds",); continue
+        if "bounds_half_open" in misread and (Q["u"] == maxx or Q["v"] == maxy):
+            exits[i] = ("outside_bounds",); continue
         idx = _area(Q, kp, px, py, ingrid, bounds, gw, gh, tags)
+        if idx is not None and "index_order" in misread:
+            idx = np.sort(idx)
         if idx is None or idx.size == 0:
             exits[i] = ("no_features_in_area",) + tuple(tags); continue
         if assigned[idx].any():
@@ -1046,9 +1053,11 @@ def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occ
         if cand.size == 0:
             exits[i] = ("no_candidate",) + tuple(tags); continue
         k = int(np.argmin(d))                       # first minimum in walking order; 256 can never be undercut: dist <= 256
+        if "min_last" in misread:
+            k = len(d) - 1 - int(np.argmin(d[::-1]))
         if int(d[k]) in (TH_HIGH, TH_HIGH + 1):
             tags.append("distance_eq_TH_HIGH" if int(d[k]) == TH_HIGH else "distance_eq_TH_HIGH_plus_1")
-        if int(d[k]) >= 256 or int(d[k]) > TH_HIGH:
+        if int(d[k]) >= 256 or int(d[k]) > TH_HIGH - ("th_high_strict" in misread):
             exits[i] = ("distance_above_TH_HIGH",) + tuple(tags); continue
         b = int(cand[k])
         if Q["valid"] & 2:
@@ -1067,6 +1076,8 @@ def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occ
             if float(rot) % 30.0 == 15.0:
                 tags.append("rot_at_half_bin")
             bn = int(c_round(f32(rot * f32(f32(1.0) / f32(HISTO_LENGTH)))))
+            if "rot_trunc" in misread:
+                bn = int(f32(rot * f32(f32(1.0) / f32(HISTO_LENGTH))))
             if bn == HISTO_LENGTH:
                 bn = 0
             hist[bn].append(i)
@@ -1085,8 +1096,10 @@ def search_by_projection(q, qdesc, kp, desc, uright, bounds, check_ori=True, occ
     return int((best >= 0).sum()), best, raw, exits, ctags
 
 
-def search_local_map(q, qdesc, kp, desc, uright, occupied, bounds, nnratio):
-    """-> nmatches, best, exits."""
+def search_local_map(q, qdesc, kp, desc, uright, occupied, bounds, nnratio, misread=()):
+    """-> nmatches, best, exits.  misread: deliberate misreadings that tests/test_ref_pin_match.py wants rejected ("ratio_double":
+    the ratio test in double; "ratio_any_level": the ratio test whatever the two levels; "index_order": the window walked in
+    index order; "ur_gate_ge": the right coordinate leaves at |error| >= radius; "th_high_strict": bestDist < TH_HIGH)."""
     nq, ncur = len(q), len(kp)
     px, py, ingrid, gw, gh = _cells(kp, bounds)
     taken = np.zeros(ncur, bool) if occupied is None else (np.asarray(occupied) != 0)
@@ -1098,11 +1111,15 @@ def search_local_map(q, qdesc, kp, desc, uright, occupied, bounds, nnratio):
         if not Q["valid"]:
             exits[i] = ("invalid",); continue
         idx = _area(Q, kp, px, py, ingrid, bounds, gw, gh, tags)
+        if idx is not None and "index_order" in misread:
+            idx = np.sort(idx)
         if idx is None or idx.size == 0:
             exits[i] = ("no_features_in_area",) + tuple(tags); continue
         if taken[idx].any():
             tags.append("occupied_keypoint_skipped")
         gated = _ur_gate(Q, idx, uright, tags)
+        if "ur_gate_ge" in misread:
+            gated = gated[~((uright[gated] > 0) & (np.abs((f32(Q["ur"]) - uright[gated]).astype(f32)) == f32(Q["radius"])))]
         d_all = hamming(qdesc[i][None], desc[gated]) if gated.size else np.zeros(0, np.int32)
         nk = int((d_all <= TH_HIGH).sum())
         if nk in (PROJ_K, PROJ_K + 1):
@@ -1118,13 +1135,14 @@ def search_local_map(q, qdesc, kp, desc, uright, occupied, bounds, nnratio):
             d2, l2 = 256, -1
         if d1 in (TH_HIGH, TH_HIGH + 1):
             tags.append("distance_eq_TH_HIGH" if d1 == TH_HIGH else "distance_eq_TH_HIGH_plus_1")
-        if d1 >= 256 or d1 > TH_HIGH:
+        if d1 >= 256 or d1 > TH_HIGH - ("th_high_strict" in misread):
             exits[i] = ("distance_above_TH_HIGH",) + tuple(tags); continue
         lim = f32(f32(nnratio) * f32(d2))
-        if l1 == l2:
+        fails = float(d1) > float(f32(nnratio)) * float(d2) if "ratio_double" in misread else f32(d1) > lim
+        if l1 == l2 or "ratio_any_level" in misread:
             if f32(d1) == lim:
                 tags.append("ratio_at_equality")
-            if f32(d1) > lim:
+            if fails:
                 exits[i] = ("ratio_test_failed_same_level",) + tuple(tags); continue
             tags.append("ratio_test_passed_same_level")
         else:

@@ -19,8 +19,11 @@ from test_bow_search_cpu import (F32, HISTO_LENGTH, POP8, TH_LOW, desc_with_bits
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def search_by_bow_kf(desc1, angle1, node1, valid1, desc2, angle2, node2, valid2, nnratio=0.75, check_orientation=True):
-    """The reference's control flow, scalar: returns (matches12[n1] = pKF2's feature or -1, nmatches)."""
+def search_by_bow_kf(desc1, angle1, node1, valid1, desc2, angle2, node2, valid2, nnratio=0.75, check_orientation=True, misread=()):
+    """The reference's control flow, scalar: returns (matches12[n1] = pKF2's feature or -1, nmatches).  misread: deliberate
+    misreadings that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "ratio_double": the ratio
+    test in double; "rot_trunc": the rotation bin by truncation; "th_low_inclusive": bestDist1 <= TH_LOW, as the (KF, Frame) form
+    has it)."""
     matches12 = [-1] * len(node1)
     matched2 = [False] * len(node2)
     fv1, fv2 = feature_vector(node1), feature_vector(node2)
@@ -39,15 +42,16 @@ def search_by_bow_kf(desc1, angle1, node1, valid1, desc2, angle2, node2, valid2,
                     if matched2[idx2] or not valid2[idx2]:
                         continue
                     d = distance(desc1[idx1], desc2[idx2])
-                    if d < best1:
+                    if d < best1 or ("min_le" in misread and d == best1):
                         best2, best1, best_idx2 = best1, d, idx2
                     elif d < best2:
                         best2 = d
-                if best1 < TH_LOW and F32(best1) < F32(ratio * F32(best2)):
+                passes = (float(best1) < float(ratio) * float(best2)) if "ratio_double" in misread else F32(best1) < F32(ratio * F32(best2))
+                if best1 < TH_LOW + ("th_low_inclusive" in misread) and passes:
                     matches12[idx1] = best_idx2
                     matched2[best_idx2] = True
                     if check_orientation:
-                        rot_hist[rot_bin(angle1[idx1], angle2[best_idx2])].append(idx1)
+                        rot_hist[rot_bin(angle1[idx1], angle2[best_idx2], "rot_trunc" in misread)].append(idx1)
                     nmatches += 1
             a += 1
             b += 1

@@ -31,17 +31,19 @@ def distance(a, b):
     return int(POP8[np.bitwise_xor(a, b)].sum())
 
 
-def rot_bin(angle_kf, angle_f):
-    """rot = kp.angle - Fkp.angle (+360 if negative), bin = round(rot * (1.0f / 30)), 30 -> 0 (float arithmetic)."""
+def rot_bin(angle_kf, angle_f, trunc=False):
+    """rot = kp.angle - Fkp.angle (+360 if negative), bin = round(rot * (1.0f / 30)), 30 -> 0 (float arithmetic); trunc: the
+    misreading `int bin = rot * factor`."""
     rot = F32(F32(angle_kf) - F32(angle_f))
     if rot < 0.0:
         rot = F32(rot + F32(360.0))
     x = F32(rot * F32(F32(1.0) / F32(HISTO_LENGTH)))
-    b = int(np.floor(np.float64(x) + 0.5))          # round(): half away from zero; x >= 0
+    b = int(np.floor(np.float64(x) + (0.0 if trunc else 0.5)))          # round(): half away from zero; x >= 0
     return 0 if b == HISTO_LENGTH else b
 
 
-def three_maxima(counts):
+def three_maxima(counts, tenth_of_second=False):
+    """tenth_of_second: the misreading that tests the third bin against a tenth of the SECOND."""
     max1 = max2 = max3 = 0
     ind1 = ind2 = ind3 = -1
     for i, s in enumerate(counts):
@@ -56,13 +58,16 @@ def three_maxima(counts):
     tenth = F32(F32(0.1) * F32(max1))
     if F32(max2) < tenth:
         ind2 = ind3 = -1
-    elif F32(max3) < tenth:
+    elif F32(max3) < (F32(F32(0.1) * F32(max2)) if tenth_of_second else tenth):
         ind3 = -1
     return ind1, ind2, ind3
 
 
-def search_by_bow(kf_desc, kf_angle, kf_node, kf_valid, f_desc, f_angle, f_node, nnratio=0.75, check_orientation=True):
-    """The reference's control flow, scalar: returns (matches[nf] = keyframe feature or -1, nmatches)."""
+def search_by_bow(kf_desc, kf_angle, kf_node, kf_valid, f_desc, f_angle, f_node, nnratio=0.75, check_orientation=True, misread=()):
+    """The reference's control flow, scalar: returns (matches[nf] = keyframe feature or -1, nmatches).  misread: deliberate
+    misreadings that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "ratio_double": the ratio
+    test in double; "rot_trunc": the rotation bin by truncation; "th_low_strict": bestDist1 < TH_LOW; "tenth_of_second": the 0.1
+    rule of ComputeThreeMaxima's third bin applied to the second maximum)."""
     nf = len(f_node)
     matches = [-1] * nf
     fv_kf, fv_f = feature_vector(kf_node), feature_vector(f_node)
@@ -82,14 +87,15 @@ def search_by_bow(kf_desc, kf_angle, kf_node, kf_valid, f_desc, f_angle, f_node,
                     if matches[i_f] >= 0:
                         continue
                     d = distance(kf_desc[ikf], f_desc[i_f])
-                    if d < best1:
+                    if d < best1 or ("min_le" in misread and d == best1):
                         best2, best1, best_idx = best1, d, i_f
                     elif d < best2:
                         best2 = d
-                if best1 <= TH_LOW and F32(best1) < F32(ratio * F32(best2)):
+                passes = (float(best1) < float(ratio) * float(best2)) if "ratio_double" in misread else F32(best1) < F32(ratio * F32(best2))
+                if best1 <= TH_LOW - ("th_low_strict" in misread) and passes:
                     matches[best_idx] = ikf
                     if check_orientation:
-                        rot_hist[rot_bin(kf_angle[ikf], f_angle[best_idx])].append(best_idx)
+                        rot_hist[rot_bin(kf_angle[ikf], f_angle[best_idx], "rot_trunc" in misread)].append(best_idx)
                     nmatches += 1
             a += 1
             b += 1
@@ -98,7 +104,7 @@ def search_by_bow(kf_desc, kf_angle, kf_node, kf_valid, f_desc, f_angle, f_node,
         else:
             b = bisect.bisect_left(f_keys, kf_keys[a], b)
     if check_orientation:
-        keep = three_maxima([len(h) for h in rot_hist])
+        keep = three_maxima([len(h) for h in rot_hist], "tenth_of_second" in misread)
         for i in range(HISTO_LENGTH):
             if i in keep:
                 continue

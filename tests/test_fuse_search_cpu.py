@@ -66,8 +66,10 @@ def gemm_row(R, p, t):
 
 # ---- the reference's control flow ----------------------------------------------------------------------------------------------
 
-def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=None, exits=None):
-    """-> best_idx[nmp], best_dist[nmp] for one keyframe; exits: a Counter of EXITS."""
+def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=None, exits=None, misread=()):
+    """-> best_idx[nmp], best_dist[nmp] for one keyframe; exits: a Counter of EXITS.  misread: deliberate misreadings of the
+    reference that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "octave_narrow": the octave
+    window one level wide; "th_low_strict": bestDist < TH_LOW; "image_closed": the image gate closed at mnMaxX)."""
     exits = exits if exits is not None else Counter()
     n = len(kf.x)
     gw_inv = f32(f32(GRID_COLS) / f32(cam.max_x - cam.min_x))
@@ -95,7 +97,7 @@ def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=No
             invz = f32(f32(1.0) / z)
             u = f32(f32(f32(cam.fx * x) / z) + cam.cx)
             v = f32(f32(f32(cam.fy * y) / z) + cam.cy)
-            if not (u >= cam.min_x and u < cam.max_x and v >= cam.min_y and v < cam.max_y):
+            if not (u >= cam.min_x and (u < cam.max_x or ("image_closed" in misread and u == cam.max_x)) and v >= cam.min_y and v < cam.max_y):
                 exits["not_in_image"] += 1; continue
             ur = f32(u - f32(cam.bf * invz))
             PO = (p - Ow).astype(f32)
@@ -124,7 +126,7 @@ def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=No
             bd, bi = 256, -1
             for j in idxs:
                 lev = int(kf.octave[j])
-                if lev < level - 1 or lev > level:
+                if lev < level - (0 if "octave_narrow" in misread else 1) or lev > level:
                     exits["level_gate"] += 1; continue
                 if reproj_gate:
                     ex, ey = f32(u - kf.x[j]), f32(v - kf.y[j])
@@ -140,10 +142,10 @@ def fuse_search_scalar(points, descs, kf, cam, th=3.0, reproj_gate=True, skip=No
                 d = int(hamming(descs[i], kf.desc[j]))
                 if d == bd and bi >= 0:
                     exits["tie"] += 1
-                if d < bd:
+                if d < bd or ("min_le" in misread and d == bd):
                     bd, bi = d, j
             best_dist[i] = bd
-            if bd <= TH_LOW:
+            if bd <= TH_LOW - ("th_low_strict" in misread):
                 best_idx[i] = bi
                 exits["match"] += 1
             else:

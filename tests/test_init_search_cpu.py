@@ -58,12 +58,12 @@ def points_of(t):
     return np.stack([t.x, t.y], 1).astype(f32)
 
 
-def rot_bin(a, b):
-    """:776-781"""
+def rot_bin(a, b, trunc=False):
+    """:776-781 (trunc: the misreading `int bin = rot * factor`)"""
     rot = f32(f32(a) - f32(b))
     if rot < 0.0:
         rot = f32(rot + f32(360.0))
-    b = int(c_round(f32(rot * FACTOR)))
+    b = int(f32(rot * FACTOR)) if trunc else int(c_round(f32(rot * FACTOR)))
     return 0 if b == HISTO_LENGTH else b
 
 
@@ -120,8 +120,12 @@ def features_in_area(t, grid, bounds, x, y, r, min_level, max_level):
     return out
 
 
-def init_search_scalar(t1, t2, prev, bounds=BOUNDS, window=100, nnratio=0.9, check_ori=True, exits=None):
-    """-> raw12 (vnMatches12 after the walk), matches12 (after the filter), nmatches, vbPrevMatched after the update."""
+def init_search_scalar(t1, t2, prev, bounds=BOUNDS, window=100, nnratio=0.9, check_ori=True, exits=None, misread=()):
+    """-> raw12 (vnMatches12 after the walk), matches12 (after the filter), nmatches, vbPrevMatched after the update.  misread:
+    deliberate misreadings that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "ratio_double":
+    the ratio test in double; "left_out_lt": a row is left out only when its holder is strictly closer; "rot_trunc": the rotation
+    bin by truncation; "evicted_leaves_histogram": an evicted match is taken out of rotHist; "th_low_strict":
+    bestDist < TH_LOW)."""
     exits = Counter() if exits is None else exits
     n1, n2 = len(t1.x), len(t2.x)
     nnratio = f32(nnratio)
@@ -144,18 +148,22 @@ def init_search_scalar(t1, t2, prev, bounds=BOUNDS, window=100, nnratio=0.9, che
         best, best2, best_idx = INT_MAX, INT_MAX, -1
         for i2 in idx2:
             dist = int(hamming(d1, t2.desc[i2]))
-            if matched_distance[i2] <= dist:
+            if matched_distance[i2] <= dist - ("left_out_lt" in misread):
                 exits["left_out"] += 1
                 continue
-            if dist < best:
+            if dist < best or ("min_le" in misread and dist == best):
                 best2, best, best_idx = best, dist, i2
                 exits["new_best"] += 1
             elif dist < best2:
                 best2 = dist
                 exits["new_second"] += 1
-        if best <= TH_LOW:
-            if f32(best) < f32(f32(best2) * nnratio):
+        if best <= TH_LOW - ("th_low_strict" in misread):
+            if (float(best) < float(best2) * float(nnratio)) if "ratio_double" in misread else f32(best) < f32(f32(best2) * nnratio):
                 if m21[best_idx] >= 0:
+                    if "evicted_leaves_histogram" in misread:
+                        for h in rot_hist:
+                            if m21[best_idx] in h:
+                                h.remove(m21[best_idx])
                     m12[m21[best_idx]] = -1
                     nmatches -= 1
                     exits["eviction"] += 1
@@ -164,7 +172,7 @@ def init_search_scalar(t1, t2, prev, bounds=BOUNDS, window=100, nnratio=0.9, che
                 matched_distance[best_idx] = best
                 nmatches += 1
                 if check_ori:
-                    rot_hist[rot_bin(t1.angle[i1], t2.angle[best_idx])].append(i1)
+                    rot_hist[rot_bin(t1.angle[i1], t2.angle[best_idx], "rot_trunc" in misread)].append(i1)
             else:
                 exits["ratio_rejected"] += 1
         else:

@@ -44,21 +44,24 @@ SETTINGS = ((10.0, 100), (3.0, 64))                                   # th, ORBd
 FACTOR = f32(1.0) / f32(HISTO_LENGTH)
 
 
-def rot_bin(a, b):
-    """:2410-2415"""
+def rot_bin(a, b, trunc=False):
+    """:2410-2415 (trunc: the misreading `int bin = rot * factor`)"""
     rot = f32(f32(a) - f32(b))
     if rot < 0.0:
         rot = f32(rot + f32(360.0))
-    b = int(c_round(f32(rot * FACTOR)))
+    b = int(f32(rot * FACTOR)) if trunc else int(c_round(f32(rot * FACTOR)))
     return 0 if b == HISTO_LENGTH else b
 
 
 # ---- the reference's control flow ----------------------------------------------------------------------------------------------
 
-def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, exits=None, state=None, info=None):
+def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, exits=None, state=None, info=None, misread=()):
     """-> row_point[nf] (the point that holds the row after the filter, -1 otherwise), best_idx[nmp] (before the filter),
     nmatches.  state (optional, for the exit counts): 0 = NULL, 1 = isBad(), 2 = in sAlreadyFound, 3 = taking part; the call itself
-    sees only valid = (state == 3).  info (a Counter): "behind_matched" counts the matches of points with z < 0."""
+    sees only valid = (state == 3).  info (a Counter): "behind_matched" counts the matches of points with z < 0.  misread: deliberate
+    misreadings that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "image_half_open": u >= mnMaxX
+    leaves, as KeyFrame::IsInImage has it; "rot_trunc": the rotation bin by truncation; "octave_narrow": octaves [level - 1, level];
+    "orb_dist_strict": bestDist < ORBdist)."""
     exits = exits if exits is not None else Counter()
     info = info if info is not None else Counter()
     points, descs = cand.points, cand.descs
@@ -90,7 +93,7 @@ def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, ex
             v = f32(f32(f32(cam.fy * y) / z) + cam.cy)
             if np.isnan(u) or np.isnan(v):                           # the stated deviation: a NaN leaves
                 exits["outside_x"] += 1; continue
-            if u < cam.min_x or u > cam.max_x:
+            if u < cam.min_x or u > cam.max_x or ("image_half_open" in misread and u == cam.max_x):
                 exits["outside_x"] += 1; continue
             if v < cam.min_y or v > cam.max_y:
                 exits["outside_y"] += 1; continue
@@ -100,7 +103,7 @@ def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, ex
                 exits["range"] += 1; continue
             level = predict_scale(f32(P["max_dist"] / dist3D))
             radius = f32(th * SF[level])
-            min_level, max_level = level - 1, level + 1
+            min_level, max_level = level - 1, level + (0 if "octave_narrow" in misread else 1)
             idxs, returned = [], True                                # Frame::GetFeaturesInArea
             c0 = max(0, math.floor(f32(f32(f32(u - cam.min_x) - radius) * gw_inv)))
             if c0 < GRID_COLS:
@@ -129,9 +132,9 @@ def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, ex
                 if mvp[j] is not None:
                     owned += 1; continue
                 d = int(hamming(descs[i], fr.desc[j]))
-                if d < bd:
+                if d < bd or ("min_le" in misread and d == bd):
                     bd, bi = d, j
-            if bd <= orb_dist:
+            if bd <= orb_dist - ("orb_dist_strict" in misread):
                 assert bi >= 0                                       # (the entry point refuses orb_dist = 256)
                 mvp[bi] = i
                 best_idx[i] = bi
@@ -140,7 +143,7 @@ def reloc_search_scalar(cand, fr, cam, th=10.0, orb_dist=100, check_ori=True, ex
                 if z < 0:
                     info["behind_matched"] += 1
                 if check_ori:
-                    rot_hist[rot_bin(cand.angles[i], fr.angle[bi])].append(bi)
+                    rot_hist[rot_bin(cand.angles[i], fr.angle[bi], "rot_trunc" in misread)].append(bi)
             elif bi >= 0:
                 exits["above_threshold"] += 1
             else:

@@ -49,8 +49,11 @@ def project_uv(x, y, z, cam, form):
 
 # ---- the reference's control flow ----------------------------------------------------------------------------------------------
 
-def sim3_search_scalar(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=None, occupied=None, exits=None):
-    """-> row_point[n] (the point that took the row in this call, -1 otherwise), best_idx[nmp], nmatches; one pair."""
+def sim3_search_scalar(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=None, occupied=None, exits=None, misread=()):
+    """-> row_point[n] (the point that took the row in this call, -1 otherwise), best_idx[nmp], nmatches; one pair.  misread:
+    deliberate misreadings that tests/test_ref_pin_match.py wants rejected ("min_le": <= in the running minimum; "octave_narrow":
+    the octave window one level wide; "owned_after": a row somebody owns is left out only after it has won; "image_closed": the image
+    gate closed at mnMaxX; "limit_strict": bestDist < TH_LOW * ratioHamming)."""
     exits = exits if exits is not None else Counter()
     n = len(kf.x)
     gw_inv = f32(f32(GRID_COLS) / f32(cam.max_x - cam.min_x))
@@ -78,7 +81,7 @@ def sim3_search_scalar(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=N
                 exits["behind"] += 1; continue
             u, v = project_uv(x, y, z, cam, form)
             assert u.dtype == f32 and v.dtype == f32
-            if not (u >= cam.min_x and u < cam.max_x and v >= cam.min_y and v < cam.max_y):
+            if not (u >= cam.min_x and (u < cam.max_x or ("image_closed" in misread and u == cam.max_x)) and v >= cam.min_y and v < cam.max_y):
                 exits["outside"] += 1; continue
             PO = (p - Ow).astype(f32)
             dist3D = f32(math.sqrt(float(PO[0]) ** 2 + float(PO[1]) ** 2 + float(PO[2]) ** 2))
@@ -104,15 +107,17 @@ def sim3_search_scalar(points, descs, kf, cam, th=3.0, ratio=1.0, form=0, skip=N
                 exits["empty_window"] += 1; continue
             bd, bi, owned = 256, -1, 0
             for j in idxs:
-                if matched[j] is not None:
+                if matched[j] is not None and "owned_after" not in misread:
                     owned += 1; continue
                 lev = int(kf.octave[j])
-                if lev < level - 1 or lev > level:
+                if lev < level - (0 if "octave_narrow" in misread else 1) or lev > level:
                     continue
                 d = int(hamming(descs[i], kf.desc[j]))
-                if d < bd:
+                if d < bd or ("min_le" in misread and d == bd):
                     bd, bi = d, j
-            if f32(bd) <= limit:
+            if "owned_after" in misread and bi >= 0 and matched[bi] is not None:
+                bd, bi, owned = 256, -1, 1
+            if f32(bd) < limit if "limit_strict" in misread else f32(bd) <= limit:
                 assert bi >= 0                                       # (the entry point refuses a limit of 256 or more)
                 matched[bi] = i
                 best_idx[i] = bi

@@ -60,9 +60,11 @@ def epipolar_constrain(x1, y1, x2, y2, F, unc):
     return bool(float(dsqr) < 3.84 * float(unc))
 
 
-def search_for_triangulation(t1, t2, F12, ep, only_stereo=False, coarse=False, check_orientation=False, exits=None):
+def search_for_triangulation(t1, t2, F12, ep, only_stereo=False, coarse=False, check_orientation=False, exits=None, misread=()):
     """The reference's control flow, scalar: returns (vMatches12[n1] after the rotation filter, nmatches).  `exits` (a Counter)
-    takes one count per exit of the loops."""
+    takes one count per exit of the loops.  misread: deliberate misreadings that tests/test_ref_pin_match.py wants rejected
+    ("tie_earlier": dist >= bestDist leaves, so of equal distances the earlier one stays; "th_low_strict": dist >= TH_LOW leaves;
+    "matched2_set": vbMatched2 is set when a feature of the neighbour is taken; "rot_trunc": the rotation bin by truncation)."""
     ex = exits if exits is not None else Counter()
     F = np.asarray(F12, np.float32).reshape(3, 3)
     epx, epy = F32(ep[0]), F32(ep[1])
@@ -96,7 +98,7 @@ def search_for_triangulation(t1, t2, F12, ep, only_stereo=False, coarse=False, c
                         ex["only_stereo2"] += 1
                         continue
                     dist = distance(t1.desc[idx1], t2.desc[idx2])
-                    if dist > TH_LOW or dist > best_dist:
+                    if dist > TH_LOW - ("th_low_strict" in misread) or dist > best_dist or ("tie_earlier" in misread and dist == best_dist and best_idx2 >= 0):
                         ex["th_low" if dist > TH_LOW else "worse_than_best"] += 1
                         continue
                     if not stereo1 and not stereo2:
@@ -119,11 +121,12 @@ def search_for_triangulation(t1, t2, F12, ep, only_stereo=False, coarse=False, c
                         rejected_by_line = min(rejected_by_line, dist)
                 if best_idx2 >= 0:
                     matches12[idx1] = best_idx2
+                    matched2[best_idx2] = "matched2_set" in misread
                     nmatches += 1
                     if rejected_by_line < best_dist:
                         ex["line_decided"] += 1   # a closer descriptor lost to the epipolar gate
                     if check_orientation:
-                        rot_hist[rot_bin(t1.angle[idx1], t2.angle[best_idx2])].append(idx1)
+                        rot_hist[rot_bin(t1.angle[idx1], t2.angle[best_idx2], "rot_trunc" in misread)].append(idx1)
                 else:
                     ex["no_match"] += 1
             i += 1
