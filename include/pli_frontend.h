@@ -614,6 +614,26 @@ pli_status pli_search_by_bow(pli_ctx* ctx, int32_t nkf, const int32_t* kf_off, c
                              const int32_t* f_node, int32_t nf, float nnratio, int32_t check_orientation, int32_t* matches,
                              int32_t* nmatches);
 
+/* ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) ORBmatcher.cc:269-470, the branch F.Nleft != -1 (:342-369,
+ * :403-432; a rig of two KannalaBrandt8 cameras: Tracking::TrackReferenceKeyFrame, Tracking.cc:2648 / :2708, and
+ * Relocalization, :4215), batched over keyframes like pli_search_by_bow.  Tables as there, plus f_nleft = F.Nleft: the frame's
+ * nf = F.N rows are the left camera's first.  The caller chooses the angles: kf_angle is mvKeysUn when !pKF->mpCamera2, else
+ * mvKeys / mvKeysRight by NLeft (:379-382); f_angle is F.mvKeys / F.mvKeysRight by Nleft (:386-389, :416-419).
+ * Per keyframe feature, over the still-unmatched frame features of its node in list order (:343-369): bestDist1 / bestDist2 /
+ * bestIdxF run over the candidates < f_nleft, bestDist1R / bestDist2R / bestIdxFR over the candidates >= f_nleft, both with
+ * strict <.  Then the reference's nesting as written (:373-433): only if bestDist1 <= TH_LOW, the left match is taken when
+ * (float)bestDist1 < mfNNratio * (float)bestDist2, and - whether or not it was - the right match when bestDist1R <= TH_LOW,
+ * without a ratio test (`|| true`, :405).  A right candidate of a keyframe feature that has no left candidate within TH_LOW is
+ * never taken.  Each taken match closes its frame feature to the later keyframe features, counts in nmatches and, with
+ * check_orientation, enters the rotation histogram with its own frame angle; ComputeThreeMaxima and the filter follow as in
+ * pli_search_by_bow.  matches / nmatches, caps and errors as there; f_nleft outside [0, nf] is PLI_ERR_INVALID.  With
+ * f_nleft == nf the result is pli_search_by_bow's; with f_nleft == 0 nothing is matched. */
+pli_status pli_search_by_bow_two_cameras(pli_ctx* ctx, int32_t nkf, const int32_t* kf_off, const uint8_t* kf_desc,
+                                         const float* kf_angle, const int32_t* kf_node, const uint8_t* kf_valid,
+                                         const uint8_t* f_desc, const float* f_angle, const int32_t* f_node, int32_t nf,
+                                         int32_t f_nleft, float nnratio, int32_t check_orientation, int32_t* matches,
+                                         int32_t* nmatches);
+
 /* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) ORBmatcher.cc:823-963 (NLeft == -1 on both sides: the
  * two-camera guards :858, :878 are not provided), for one keyframe pKF1 against nkf keyframes pKF2[k] in one call
  * (LoopClosing::DetectCommonRegionsFromBoW's loop, LoopClosing.cc:528-540).
@@ -737,6 +757,43 @@ pli_status pli_fuse_search(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t
                            const int32_t* kf_off, const pli_keypoint* kf_kp, const uint8_t* kf_desc, const float* kf_uright,
                            const float* kf_pose, const uint8_t* skip, const pli_fuse_camera* cam, float th,
                            const float* level_ratio, int32_t reproj_gate, int32_t* best_idx, int32_t* best_dist);
+
+/* The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) ORBmatcher.cc:1399-1609 for keyframes with two KannalaBrandt8
+ * cameras (NLeft != -1, mpCamera2 set): both values of bRight, for nmp map points against nkf keyframes, in one call
+ * (LocalMapping::SearchInNeighbors calls Fuse twice per target keyframe, LocalMapping.cc:747-748, and twice for the current one,
+ * :776-777).  mp, mp_desc, th, level_ratio and the cap of PLI_BOW_MAX_FEATURES rows per keyframe as for pli_fuse_search.
+ * Keyframe tables as for pli_search_for_triangulation_two_cameras: keyframe k owns rows kf_off[k] .. kf_off[k+1]-1 of kf_kp and
+ * kf_desc (mDescriptors), the first kf_nleft[k] of them mvKeys, the rest mvKeysRight (:1524-1526, KeyFrame.cc:912-914; pt and
+ * octave are read; NOT mvKeysUn).  kf_pose: nkf x 2 x 15 floats, left then right, each Rcw row major, tcw, Ow: GetRotation() /
+ * GetTranslation() / GetCameraCenter(), and GetRightRotation() / GetRightTranslation() / GetRightCameraCenter()
+ * (KeyFrame.cc:1343-1373) - the reference's own cv::Mat expressions, host arithmetic, as rel is for the triangulation call.
+ * cam_left / cam_right: mpCamera / mpCamera2, shared by the call.  min_x .. max_y: mnMinX .. mnMaxY, for KeyFrame::IsInImage and
+ * the 64 x 48 grids; pKF->fx .. cy and mbf are not read by this branch.  sides: bit 0 = the left camera (bRight == false), bit 1 =
+ * the right; a side that is not asked for is neither projected nor searched and its rows of the result are -1 / 256.
+ * skip: nkf x 2 x nmp, may be NULL (IsInKeyFrame(pKF) :1448 at the time of that side's call).
+ * Per (keyframe, side, point), in the reference's order: valid / skip; p3Dc = Rcw*p3Dw + tcw with that side's pose (a cv::Mat
+ * product: double accumulation, one rounding); z < 0 rejected (:1459); uv = KannalaBrandt8::project with that side's camera
+ * (KannalaBrandt8.cpp:28-42, with the conventions of pli_stereo_fisheye); IsInImage; the distance range with that side's Ow;
+ * PO.dot(Pn) < 0.5*dist3D; the level from level_ratio; radius = th * mvScaleFactors[level]; the window
+ * GetFeaturesInArea(uv.x, uv.y, radius, bRight) over that side's own grid (mGrid from the left rows, mGridRight from the right
+ * rows with camera-local indices, Frame.cc:468-481); the octave in [level-1, level]; e2 * mvInvLevelSigma2[octave] > 5.99
+ * rejected; the strict minimum of the Hamming distance in visiting order = the minimum of the key (distance, cell column, cell
+ * row, index), as for pli_fuse_search; bestDist <= TH_LOW.
+ * There is no kf_uright and no 7.8 bound: the fisheye constructor sets every mvuRight to -1 (Frame.cc:1589), and the reference
+ * reads mvuRight[idx] with the camera-local idx on a vector of Nleft entries, which is an out-of-range read for a right row
+ * >= Nleft.  An adapter must refuse a keyframe with NLeft != -1 and any mvuRight[i] >= 0.
+ * best_idx: nkf x 2 x nmp, the reference's bestIdx, a row over the keyframe's N (for the right camera the camera-local row +
+ * NLeft, :1559), -1 where there is no match.  best_dist (may be NULL): bestDist, 256 where no candidate passed the gates.
+ * Checked before anything is launched, PLI_ERR_INVALID: null pointers, sides outside 1..3, a decreasing or NaN level_ratio, empty
+ * image bounds, a decreasing kf_off, kf_nleft[k] outside [0, n_k], an octave outside [0, orb_nlevels), a keypoint coordinate or a
+ * pose value that is not finite.  PLI_ERR_CAPACITY for a keyframe with more than PLI_BOW_MAX_FEATURES rows.  nkf == 0, nmp == 0,
+ * empty keyframes, kf_nleft[k] == 0 and kf_nleft[k] == n_k are valid.  Three kernel launches, whatever nkf and nmp. */
+pli_status pli_fuse_search_two_cameras(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t* mp_desc, int32_t nmp, int32_t nkf,
+                                       const int32_t* kf_off, const int32_t* kf_nleft, const pli_keypoint* kf_kp,
+                                       const uint8_t* kf_desc, const float* kf_pose, const uint8_t* skip,
+                                       const pli_kb8_camera* cam_left, const pli_kb8_camera* cam_right, float min_x, float max_x,
+                                       float min_y, float max_y, float th, const float* level_ratio, int32_t sides,
+                                       int32_t* best_idx, int32_t* best_dist);
 
 /* Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) ORBmatcher.cc:473-586 and the
  * overload with vpPointsKFs / vpMatchedKF :588-704 (LoopClosing.cc:631, :656, :852), for ONE list of nmp map points against npair

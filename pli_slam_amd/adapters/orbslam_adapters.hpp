@@ -977,11 +977,34 @@ class PliORBmatcher {
     std::vector<int> best;
     fe->fuseSearch(pts.data(), desc.data(), nmp, nkf, T.off.data(), T.kp.data(), T.desc.data(), T.uright.data(), T.pose.data(),
                    skip.data(), T.cam, th, levelRatio, true, best);
+    fuseReplay(vpTargetKFs, vpMapPoints, best, nFused, pnResearch,
+               [&](int k, const std::vector<int>& which, const std::vector<pli_fuse_point>& p2, const std::vector<uint8_t>& d2) {
+                 std::vector<int32_t> off2(T.off.begin() + k, T.off.end());
+                 for (size_t j = off2.size(); j-- > 0;) off2[j] -= off2[0];
+                 const size_t row0 = (size_t)T.off[k];
+                 std::vector<int> b2;
+                 fe->fuseSearch(p2.data(), d2.data(), (int)which.size(), nkf - k, off2.data(), T.kp.data() + row0, T.desc.data() + row0 * 32,
+                                T.uright.data() + row0, T.pose.data() + (size_t)k * 15, nullptr, T.cam, th, levelRatio, true, b2);
+                 for (int kk = k; kk < nkf; ++kk)
+                   for (size_t j = 0; j < which.size(); ++j) best[(size_t)kk * nmp + which[j]] = b2[(size_t)(kk - k) * which.size() + j];
+               });
+  }
+
+ protected:
+  // The host half of a sequence of Fuse calls that ONE device search answered (the three rules above): view v is one call of the
+  // reference - keyframe viewKF[v], or one camera of it when a keyframe of two cameras takes two views in a row
+  // (PliORBmatcherTwoCameras) - and best (views x points) holds the search's bestIdx.  The views are replayed in order with
+  // :1572-1594; research(v, which, p2, d2) searches the points `which` (their tables p2 / d2) again against the views v..end and
+  // writes their entries of best.
+  template <class KeyFrameT, class Research>
+  void fuseReplay(const std::vector<KeyFrameT*>& viewKF, const std::vector<MapPointT*>& vpMapPoints, std::vector<int>& best,
+                  std::vector<int>& nFused, int* pnResearch, Research research) {
+    const int nview = (int)viewKF.size(), nmp = (int)vpMapPoints.size();
     std::vector<uint8_t> changed(nmp, 0);
     bool anyChanged = false;
-    for (int k = 0; k < nkf; ++k) {
-      KeyFrameT* pKF = vpTargetKFs[k];
-      if (anyChanged) {                         // the points whose descriptor a Replace changed, against the keyframes k..end
+    for (int k = 0; k < nview; ++k) {
+      KeyFrameT* pKF = viewKF[k];
+      if (anyChanged) {                         // the points whose descriptor a Replace changed, against the views k..end
         std::vector<int> which;
         std::vector<pli_fuse_point> p2;
         std::vector<uint8_t> d2;
@@ -994,14 +1017,7 @@ class PliORBmatcher {
             if (p2.back().valid) std::memcpy(&d2[at], vpMapPoints[i]->GetDescriptor().template ptr<uint8_t>(), 32);
             changed[i] = 0;
           }
-        std::vector<int32_t> off2(T.off.begin() + k, T.off.end());
-        for (size_t j = off2.size(); j-- > 0;) off2[j] -= off2[0];
-        const size_t row0 = (size_t)T.off[k];
-        std::vector<int> b2;
-        fe->fuseSearch(p2.data(), d2.data(), (int)which.size(), nkf - k, off2.data(), T.kp.data() + row0, T.desc.data() + row0 * 32,
-                       T.uright.data() + row0, T.pose.data() + (size_t)k * 15, nullptr, T.cam, th, levelRatio, true, b2);
-        for (int kk = k; kk < nkf; ++kk)
-          for (size_t j = 0; j < which.size(); ++j) best[(size_t)kk * nmp + which[j]] = b2[(size_t)(kk - k) * which.size() + j];
+        research(k, which, p2, d2);
         anyChanged = false;
         if (pnResearch) ++*pnResearch;
       }
@@ -1035,6 +1051,7 @@ class PliORBmatcher {
     }
   }
 
+ public:
   // ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint),
   // ORBmatcher.cc:1611-1733 (LoopClosing::SearchAndFuse).  The Sim3 decomposition :1620-1624 runs here (PARITY UNPINNED: OpenCV's
   // arithmetic, by the conventions DESIGN.md §9 lists - Mat::dot sums in double, sqrt of that double rounded to float; Mat / s is

@@ -1,6 +1,7 @@
 // The two SearchByProjection forms of ORB_SLAM3::ORBmatcher that run on every tracked frame, for a frame of two cameras
-// (Frame::Nleft != -1, the fisheye-stereo rig), and SearchForTriangulation for keyframes of two cameras (mpCamera2 set,
-// NLeft != -1): a matcher that is PliORBmatcher in everything else.
+// (Frame::Nleft != -1, the fisheye-stereo rig), SearchForTriangulation and Fuse(pKF, vpMapPoints, th, bRight) for keyframes of two
+// cameras (mpCamera2 set, NLeft != -1) and SearchByBoW(pKF, F, vpMapPointMatches) for such frames and keyframes: a matcher that is
+// PliORBmatcher in everything else.
 //
 //   inside the PLI-SLAM tree:  using ORBmatcher = ORB_SLAM3::PliORBmatcherTwoCameras<Frame, MapPoint>;
 //
@@ -26,6 +27,8 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
 
   using Base::SearchByProjection;            // every other form stays visible; the two below hide theirs
   using Base::SearchForTriangulation;        // likewise: both forms below hide theirs and forward to them
+  using Base::Fuse;                          // the Sim3 form stays the base's; the two forms below hide theirs
+  using Base::SearchByBoW;                   // the (KF, KF) forms stay the base's; the two (KF, F) forms below hide theirs
 
   // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono),
   // ORBmatcher.cc:1961-2177 (Tracking::TrackWithMotionModel, Tracking.cc:2961, :2969).  For CurrentFrame.Nleft != -1 the two
@@ -192,15 +195,7 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
       std::vector<uint8_t> hasMp;
       std::vector<int32_t> nleft;
     };
-    auto cameras = [](KeyFrameT* pKF, pli_kb8_camera cam[2]) {
-      if (pKF->mpCamera->size() != 8 || pKF->mpCamera2->size() != 8)
-        throw std::logic_error("SearchForTriangulation: a keyframe of two cameras needs two KannalaBrandt8 cameras (8 parameters each)");
-      for (int e = 0; e < 2; ++e) {
-        float v[8];
-        for (int i = 0; i < 8; ++i) v[i] = e ? pKF->mpCamera2->getParameter(i) : pKF->mpCamera->getParameter(i);
-        cam[e] = pli_kb8_camera{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-      }
-    };
+    auto cameras = [](KeyFrameT* pKF, pli_kb8_camera cam[2]) { kb8Cameras(pKF, cam); };
     pli_kb8_camera cam[2];
     cameras(pKF1, cam);
     auto gather = [&](KeyFrameT* pKF, Table& T, const char* what) {
@@ -253,7 +248,206 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
     });
   }
 
+  // ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight), ORBmatcher.cc:
+  // 1399-1609, for a keyframe of two KannalaBrandt8 cameras (NLeft != -1): the pose of the side (GetRotation() ... or
+  // GetRightRotation() / GetRightTranslation() / GetRightCameraCenter(), KeyFrame.cc:1343-1373) is read here, the projection with
+  // the side's camera and the window search over the side's grid run on the device (pli_fuse_search_two_cameras), :1572-1594 and
+  // the gates isBad() / IsInKeyFrame here (the base's replay).  A keyframe with NLeft == -1 goes to the base.
+  // There is no stereo bound for such a keyframe: the fisheye constructor sets every mvuRight to -1 (Frame.cc:1589), and :1533
+  // reads mvuRight[idx] with the camera-local idx, on a vector of Nleft entries - out of range for a right row >= Nleft.  So a
+  // keyframe with NLeft != -1 and any mvuRight[i] >= 0 throws std::logic_error.
+  // KeyFrameT needs, beyond what PliORBmatcher::Fuse reads: mvKeys, mvKeysRight, mpCamera / mpCamera2 (getParameter(i), size()) and
+  // the three right-pose getters.
+  template <class KeyFrameT>
+  int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0, const bool bRight = false) {
+    if (pKF->NLeft == -1) return Base::Fuse(pKF, vpMapPoints, th, bRight);
+    std::vector<int> nFused;
+    fuseTwoCameras(std::vector<KeyFrameT*>(1, pKF), vpMapPoints, th, bRight ? 2 : 1, nFused, nullptr);
+    return nFused[0];
+  }
+
+  // (not in the reference) The loop of LocalMapping::SearchInNeighbors, LocalMapping.cc:743-749 - Fuse(pKFi, vpMapPointMatches) and
+  // Fuse(pKFi, vpMapPointMatches, 3.0, true) for every target keyframe - with ONE device search for all targets and both cameras,
+  // replayed in the reference's order: keyframe k left, keyframe k right, keyframe k + 1 left, ...  nFused[2 k] and nFused[2 k + 1]
+  // are the two return values for keyframe k.  The replay and its three rules are the base's (fuseReplay): a point added to
+  // keyframe k on the left is in the keyframe when the right camera's turn comes and is skipped there (:1448).  When no target has
+  // two cameras the base's form runs (nFused[k]); targets with and without throw std::logic_error.
+  template <class KeyFrameT>
+  void Fuse(const std::vector<KeyFrameT*>& vpTargetKFs, const std::vector<MapPointT*>& vpMapPoints, const float th,
+            std::vector<int>& nFused, int* pnResearch = nullptr) {
+    int two = 0;
+    for (KeyFrameT* pKF : vpTargetKFs) two += pKF->NLeft != -1 ? 1 : 0;
+    if (two == 0) {
+      Base::Fuse(vpTargetKFs, vpMapPoints, th, nFused, pnResearch);
+      return;
+    }
+    if (two != (int)vpTargetKFs.size())
+      throw std::logic_error("Fuse: keyframes with and without a second camera (NLeft != -1) in one call are not supported");
+    fuseTwoCameras(vpTargetKFs, vpMapPoints, th, 3, nFused, pnResearch);
+  }
+
+  // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches), ORBmatcher.cc:269-470, with the
+  // two-camera text: a frame with F.Nleft != -1 goes to pli_search_by_bow_two_cameras (:342-369, :373-433; the frame's angles from
+  // mvKeys / mvKeysRight by Nleft, :386-389, :416-419); a frame of one camera against a keyframe with mpCamera2 goes to
+  // pli_search_by_bow with the keyframe's angles from mvKeys / mvKeysRight by NLeft (:379-382); anything else to the base.
+  // vpMapPointMatches is written as the reference writes it.
+  template <class KeyFrameT>
+  int SearchByBoW(KeyFrameT* pKF, FrameT& F, std::vector<MapPointT*>& vpMapPointMatches) {
+    std::vector<std::vector<MapPointT*>> matches;
+    std::vector<int> nmatches;
+    SearchByBoW(std::vector<KeyFrameT*>(1, pKF), F, matches, nmatches);
+    vpMapPointMatches.swap(matches[0]);
+    return nmatches[0];
+  }
+
+  // (not in the reference) The same for every keyframe of vpKFs in ONE device call (Tracking::Relocalization, Tracking.cc:4205-4230).
+  template <class KeyFrameT>
+  void SearchByBoW(const std::vector<KeyFrameT*>& vpKFs, FrameT& F, std::vector<std::vector<MapPointT*>>& vvpMapPointMatches,
+                   std::vector<int>& vnmatches) {
+    bool anyTwo = F.Nleft != -1;
+    for (KeyFrameT* pKF : vpKFs) anyTwo = anyTwo || pKF->mpCamera2;
+    if (!anyTwo) {
+      Base::SearchByBoW(vpKFs, F, vvpMapPointMatches, vnmatches);
+      return;
+    }
+    const int nf = F.N, nkf = (int)vpKFs.size(), nl = F.Nleft;
+    if (nl != -1 && (nl < 0 || nl > nf || (int)F.mvKeys.size() < nl || (int)F.mvKeysRight.size() < nf - nl))
+      throw std::logic_error("SearchByBoW: the frame's tables do not hold Nleft + Nright rows");
+    pli_detail::KfTable TF;
+    pli_detail::appendNodes(TF, F.mFeatVec, nf, "SearchByBoW: F.mFeatVec");
+    pli_detail::appendDescriptors(TF, F.mDescriptors, nf);
+    std::vector<float> fAngle((size_t)nf);
+    for (int i = 0; i < nf; ++i) fAngle[i] = (nl == -1 || i < nl) ? F.mvKeys[i].angle : F.mvKeysRight[i - nl].angle;   // :386-389, :416-419
+    std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
+    typename Base::BowTable T;
+    for (int k = 0; k < nkf; ++k) {
+      KeyFrameT* pKF = vpKFs[k];
+      kfPoints[k] = pKF->GetMapPointMatches();
+      if (!pKF->mpCamera2) {                                                 // mvKeysUn, :380
+        Base::bowGatherKeyFrame(pKF, kfPoints[k], "SearchByBoW: pKF->mFeatVec", T);
+        continue;
+      }
+      const int n = pKF->N, knl = pKF->NLeft;                                // mvKeys / mvKeysRight by NLeft, :381-382
+      if (knl < 0 || knl > n || (int)pKF->mvKeys.size() < knl || (int)pKF->mvKeysRight.size() < n - knl)
+        throw std::logic_error("SearchByBoW: a keyframe's tables do not hold NLeft + NRight rows");
+      pli_detail::appendNodes(T, pKF->mFeatVec, n, "SearchByBoW: pKF->mFeatVec");
+      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
+      for (int i = 0; i < n; ++i) {
+        MapPointT* pMP = kfPoints[k][i];
+        T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);
+        T.angle.push_back(i < knl ? pKF->mvKeys[i].angle : pKF->mvKeysRight[i - knl].angle);
+      }
+    }
+    std::vector<int> matches;
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("SearchByBoW");
+    if (nl != -1)
+      fe->searchByBoWTwoCameras(nkf, T.off.data(), T.desc.data(), T.angle.data(), T.node.data(), T.valid.data(), TF.desc.data(),
+                                fAngle.data(), TF.node.data(), nf, nl, this->mfNNratio, this->mbCheckOrientation, matches, vnmatches);
+    else
+      fe->searchByBoW(nkf, T.off.data(), T.desc.data(), T.angle.data(), T.node.data(), T.valid.data(), TF.desc.data(), fAngle.data(),
+                      TF.node.data(), nf, this->mfNNratio, this->mbCheckOrientation, matches, vnmatches);
+    vvpMapPointMatches.assign((size_t)nkf, std::vector<MapPointT*>((size_t)nf, static_cast<MapPointT*>(nullptr)));
+    pli_detail::forEachMatch(matches, nkf, nf, [&](int k, int i, int j) { vvpMapPointMatches[k][i] = kfPoints[k][j]; });
+  }
+
  private:
+  // mpCamera / mpCamera2 of a keyframe of two cameras: eight KannalaBrandt8 parameters each (GeometricCamera.h:77-80)
+  template <class KeyFrameT>
+  static void kb8Cameras(KeyFrameT* pKF, pli_kb8_camera cam[2]) {
+    if (!pKF->mpCamera || !pKF->mpCamera2 || pKF->mpCamera->size() != 8 || pKF->mpCamera2->size() != 8)
+      throw std::logic_error("PliORBmatcherTwoCameras: a keyframe of two cameras needs two KannalaBrandt8 cameras (8 parameters each)");
+    for (int e = 0; e < 2; ++e) {
+      float v[8];
+      for (int i = 0; i < 8; ++i) v[i] = e ? pKF->mpCamera2->getParameter(i) : pKF->mpCamera->getParameter(i);
+      cam[e] = pli_kb8_camera{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    }
+  }
+
+  // What the two Fuse forms share.  sides: 1 = the left camera of every target, 2 = the right one, 3 = both, left then right;
+  // nFused has one entry per replayed (keyframe, side).
+  template <class KeyFrameT>
+  void fuseTwoCameras(const std::vector<KeyFrameT*>& vpTargetKFs, const std::vector<MapPointT*>& vpMapPoints, const float th,
+                      const int sides, std::vector<int>& nFused, int* pnResearch) {
+    const int nkf = (int)vpTargetKFs.size(), nmp = (int)vpMapPoints.size(), per = sides == 3 ? 2 : 1;
+    nFused.assign((size_t)nkf * per, 0);
+    if (pnResearch) *pnResearch = 0;
+    if (nkf == 0) return;
+    struct Table : pli_detail::KfTable {
+      std::vector<pli_keypoint> kp;
+      std::vector<int32_t> nleft;
+      std::vector<float> pose;
+    } T;
+    pli_kb8_camera cam[2];
+    kb8Cameras(vpTargetKFs[0], cam);
+    KeyFrameT* first = vpTargetKFs[0];
+    const float bounds[4] = {(float)first->mnMinX, (float)first->mnMaxX, (float)first->mnMinY, (float)first->mnMaxY};
+    for (KeyFrameT* pKF : vpTargetKFs) {
+      const int n = pKF->N, nl = pKF->NLeft;
+      if (nl < 0 || nl > n || (int)pKF->mvKeys.size() < nl || (int)pKF->mvKeysRight.size() < n - nl || pKF->mDescriptors.rows < n)
+        throw std::logic_error("Fuse: a keyframe's tables do not hold NLeft + NRight rows");
+      for (size_t i = 0; i < pKF->mvuRight.size(); ++i)
+        if (pKF->mvuRight[i] >= 0)
+          throw std::logic_error("Fuse: a keyframe of two cameras with mvuRight >= 0 (the reference reads mvuRight out of range there)");
+      pli_kb8_camera own[2];
+      kb8Cameras(pKF, own);
+      const float b[4] = {(float)pKF->mnMinX, (float)pKF->mnMaxX, (float)pKF->mnMinY, (float)pKF->mnMaxY};
+      if (std::memcmp(own, cam, sizeof(own)) != 0 || std::memcmp(b, bounds, sizeof(b)) != 0)
+        throw std::logic_error("Fuse: the target keyframes of one call must share the cameras and the image bounds");
+      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
+      for (int i = 0; i < n; ++i) T.kp.push_back(pli_detail::keypoint(i < nl ? pKF->mvKeys[i] : pKF->mvKeysRight[i - nl]));   // :1524-1526
+      T.nleft.push_back(nl);
+      const cv::Mat R[2] = {pKF->GetRotation(), pKF->GetRightRotation()}, t[2] = {pKF->GetTranslation(), pKF->GetRightTranslation()},
+                    Ow[2] = {pKF->GetCameraCenter(), pKF->GetRightCameraCenter()};                                               // :1404-1417
+      for (int e = 0; e < 2; ++e) {
+        float pose[15];
+        for (int i = 0; i < 3; ++i) {
+          for (int j = 0; j < 3; ++j) pose[i * 3 + j] = R[e].template at<float>(i, j);
+          pose[9 + i] = t[e].template at<float>(i);
+          pose[12 + i] = Ow[e].template at<float>(i);
+        }
+        T.pose.insert(T.pose.end(), pose, pose + 15);
+      }
+    }
+    std::vector<pli_fuse_point> pts(nmp);
+    std::vector<uint8_t> desc((size_t)nmp * 32, 0), skip((size_t)nkf * 2 * nmp, 0);
+    for (int i = 0; i < nmp; ++i) {
+      MapPointT* pMP = vpMapPoints[i];
+      pts[i] = Base::fusePoint(pMP);
+      if (!pts[i].valid) continue;
+      std::memcpy(&desc[(size_t)i * 32], pMP->GetDescriptor().template ptr<uint8_t>(), 32);
+      for (int k = 0; k < nkf; ++k)
+        skip[((size_t)k * 2) * nmp + i] = skip[((size_t)k * 2 + 1) * nmp + i] = pMP->IsInKeyFrame(vpTargetKFs[k]) ? 1 : 0;
+    }
+    std::shared_ptr<pli::Frontend> fe = pli_detail::deviceContext("Fuse");
+    const std::vector<float>& levelRatio = this->fuseLevelRatio(first);
+    std::vector<int> all;
+    fe->fuseSearchTwoCameras(pts.data(), desc.data(), nmp, nkf, T.off.data(), T.nleft.data(), T.kp.data(), T.desc.data(), T.pose.data(),
+                             skip.data(), cam[0], cam[1], bounds, th, levelRatio, sides, all);
+    // the replayed views: (keyframe, side) for every side asked for, in the reference's order
+    std::vector<KeyFrameT*> viewKF;
+    std::vector<int> viewRow;                                                // the view's row of `all` (keyframe * 2 + side)
+    for (int k = 0; k < nkf; ++k)
+      for (int side = 0; side < 2; ++side)
+        if ((sides >> side) & 1) { viewKF.push_back(vpTargetKFs[k]); viewRow.push_back(k * 2 + side); }
+    std::vector<int> best(viewKF.size() * (size_t)nmp);
+    for (size_t v = 0; v < viewKF.size(); ++v)
+      std::copy(all.begin() + (size_t)viewRow[v] * nmp, all.begin() + ((size_t)viewRow[v] + 1) * nmp, best.begin() + v * nmp);
+    this->fuseReplay(viewKF, vpMapPoints, best, nFused, pnResearch,
+                     [&](int v, const std::vector<int>& which, const std::vector<pli_fuse_point>& p2, const std::vector<uint8_t>& d2) {
+                       const int k0 = viewRow[v] / 2;                        // the keyframes k0..end, the same sides
+                       std::vector<int32_t> off2(T.off.begin() + k0, T.off.end());
+                       for (size_t j = off2.size(); j-- > 0;) off2[j] -= off2[0];
+                       const size_t row0 = (size_t)T.off[k0];
+                       std::vector<int> b2;
+                       fe->fuseSearchTwoCameras(p2.data(), d2.data(), (int)which.size(), nkf - k0, off2.data(), T.nleft.data() + k0,
+                                                T.kp.data() + row0, T.desc.data() + row0 * 32, T.pose.data() + (size_t)k0 * 30, nullptr,
+                                                cam[0], cam[1], bounds, th, levelRatio, sides, b2);
+                       for (size_t vv = (size_t)v; vv < viewKF.size(); ++vv)
+                         for (size_t j = 0; j < which.size(); ++j)
+                           best[vv * nmp + which[j]] = b2[(size_t)(viewRow[vv] - 2 * k0) * which.size() + j];
+                     });
+  }
+
   // the two cameras of a frame as the library's tables: mvKeys / mvKeysRight, the two halves of mDescriptors, and per slot
   // "holds a map point with observations" (:2036-2038, :2111-2113; :89-91, :169-171)
   struct Tables {

@@ -138,6 +138,17 @@ class Frontend {
     check(pli_search_by_bow(ctx_, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, nnratio,
                             checkOrientation ? 1 : 0, matches.data(), nmatches.data()));
   }
+  // ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) ORBmatcher.cc:269-470, the branch F.Nleft != -1 (:342-369, :373-433), of nkf
+  // keyframes against one frame of two cameras (include/pli_frontend.h pli_search_by_bow_two_cameras): the frame's first fNleft
+  // rows are the left camera's; matches / nmatches as searchByBoW
+  void searchByBoWTwoCameras(int nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle, const int32_t* kfNode,
+                             const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle, const int32_t* fNode, int nf,
+                             int fNleft, float nnratio, bool checkOrientation, std::vector<int>& matches, std::vector<int>& nmatches) {
+    matches.assign((size_t)nkf * nf, -1);
+    nmatches.assign(nkf, 0);
+    check(pli_search_by_bow_two_cameras(ctx_, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, fNleft, nnratio,
+                                        checkOrientation ? 1 : 0, matches.data(), nmatches.data()));
+  }
   // ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) ORBmatcher.cc:823-963 (NLeft == -1) of one keyframe against nkf keyframes
   // (include/pli_frontend.h pli_search_by_bow_kf): matches12 (nkf x n1) = the row of keyframe k each feature of pKF1 is matched to
   // or -1, nmatches[k] = the reference's return value for keyframe k
@@ -188,6 +199,20 @@ class Frontend {
     bestIdx.assign((size_t)nkf * nmp, -1);
     check(pli_fuse_search(ctx_, mp, mpDesc, nmp, nkf, kfOff, kfKp, kfDesc, kfUright, kfPose, skip, &cam, th, levelRatio.data(),
                           reprojGate ? 1 : 0, bestIdx.data(), nullptr));
+  }
+  // The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) ORBmatcher.cc:1399-1609 for keyframes with two KannalaBrandt8
+  // cameras (NLeft != -1), both values of bRight of nkf keyframes in one call (include/pli_frontend.h pli_fuse_search_two_cameras):
+  // the tables hold the left camera's rows first (kfNleft = NLeft), kfPose = nkf x 2 x 15 (left, right), skip = nkf x 2 x nmp or
+  // null, bounds = mnMinX, mnMaxX, mnMinY, mnMaxY, sides: bit 0 = left, bit 1 = right; bestIdx (nkf x 2 x nmp) = the row over the
+  // keyframe's N or -1
+  void fuseSearchTwoCameras(const pli_fuse_point* mp, const uint8_t* mpDesc, int nmp, int nkf, const int32_t* kfOff,
+                            const int32_t* kfNleft, const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfPose,
+                            const uint8_t* skip, const pli_kb8_camera& camLeft, const pli_kb8_camera& camRight, const float bounds[4],
+                            float th, const std::vector<float>& levelRatio, int sides, std::vector<int>& bestIdx) {
+    bestIdx.assign((size_t)nkf * 2 * nmp, -1);
+    check(pli_fuse_search_two_cameras(ctx_, mp, mpDesc, nmp, nkf, kfOff, kfNleft, kfKp, kfDesc, kfPose, skip, &camLeft, &camRight,
+                                      bounds[0], bounds[1], bounds[2], bounds[3], th, levelRatio.data(), sides, bestIdx.data(),
+                                      nullptr));
   }
   // Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
   // ORBmatcher.cc:473-704 of nmp map points against npair (keyframe, Scw) pairs (include/pli_frontend.h

@@ -190,6 +190,9 @@ _PROTOS = {
     "pli_search_by_bow": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                       C.c_void_p]),
+    "pli_search_by_bow_two_cameras": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                                  C.c_void_p, C.c_void_p]),
     "pli_search_by_bow_kf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p]),
@@ -205,6 +208,10 @@ _PROTOS = {
     "pli_fuse_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FuseCamera), C.c_float, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p]),
+    "pli_fuse_search_two_cameras": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.c_void_p]),
     "pli_search_by_projection_two_cameras": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,

@@ -16,6 +16,8 @@
 //   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_tri_finish  the same for keyframes of two KannalaBrandt8 cameras (mpCamera2)
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
+//   k_fuse_grid, k_fuse_project_views, k_fuse_match<8, true>  the same search for keyframes of two KannalaBrandt8 cameras, both values of bRight
+//   k_node_sort + k_search_by_bow_two_cameras  ORBmatcher::SearchByBoW(KF,F) for a frame of two cameras (ORBmatcher.cc:342-369, :373-433)
 //   k_fuse_grid, k_sim3_project, k_window_candidates<0>, k_sim3_assign  ORBmatcher::SearchByProjection(KF, Scw, ...) (ORBmatcher.cc:473-704)
 //   k_fuse_grid, k_reloc_project, k_window_candidates<1>, k_reloc_assign  ORBmatcher::SearchByProjection(Frame, KF, sAlreadyFound, ...) (ORBmatcher.cc:2325-2447)
 //   k_fuse_grid, k_init_candidates, k_init_assign  ORBmatcher::SearchForInitialization (ORBmatcher.cc:706-821)
@@ -1255,10 +1257,14 @@ __global__ __launch_bounds__(1024) void k_node_sort(const int* __restrict__ kfOf
 // ties keep the first listed, the lowest index) are the two smallest (distance, candidate index) keys.  owner[candidate] (LDS,
 // -1 = free) takes the walking feature of an accepted match (bestDist1 <= maxDist and the ratio test); hist takes its rotation
 // bin.  wDesc / wAngle and cDesc / cAngle are the walking and the candidate side's tables.  Returns this wave's accepted matches.
+// kTwoCameras (SearchByBoW(KF, F) with F.Nleft != -1, ORBmatcher.cc:342-369, :373-433): the candidates < cNleft (the left camera's)
+// and the others keep a top-2 each; only if bestDist1 <= maxDist, the left match is taken on its ratio test and - whether or not it
+// was - the right one when bestDist1R <= maxDist, without a ratio test (`|| true`, :405).
+template <bool kTwoCameras>
 __device__ __forceinline__ int bow_walk(const uint32_t* key, int m, const uint8_t* __restrict__ wDesc, const float* __restrict__ wAngle,
                                         const uint32_t* __restrict__ sNode, const uint16_t* __restrict__ sIdx, int nListed,
                                         const uint8_t* __restrict__ cDesc, const float* __restrict__ cAngle, short* owner, int* hist,
-                                        int maxDist, float nnratio, int checkOri) {
+                                        int maxDist, float nnratio, int checkOri, int cNleft = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   int nm = 0;
   for (int c0 = wave * 64; c0 < m; c0 += nwaves * 64) {
@@ -1273,23 +1279,32 @@ __device__ __forceinline__ int bow_walk(const uint32_t* key, int m, const uint8_
         const int j = (int)(key[q] & 0xFFFFu);
         uint64_t dk[4];
         load_desc(wDesc + (int64_t)j * 32, dk);
-        WaveTop2 top;
+        WaveTop2 top, topR;
         for (int t = (int)lo + lane; t < hi; t += 64) {
           const int fi = sIdx[t];
-          if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319, :884)
+          if (owner[fi] >= 0) continue;                           // matched earlier in this call (:318-319, :345, :884)
           uint64_t df[4];
           load_desc(cDesc + (int64_t)fi * 32, df);
-          top.push(((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi);
+          const unsigned long long k = ((unsigned long long)hamming256(dk, df) << 32) | (unsigned)fi;
+          if (kTwoCameras && fi >= cNleft) topR.push(k);          // :361-368
+          else top.push(k);
         }
         const unsigned long long m1 = top.min1(), m2 = top.min2(m1);
-        if (m1 == ~0ull) continue;
+        if (m1 == ~0ull) continue;                                // (two cameras: bestDist1 == 256 > TH_LOW takes nothing, :373)
         const int bestDist1 = (int)(m1 >> 32), bestDist2 = m2 != ~0ull ? (int)(m2 >> 32) : 256;
-        if (bestDist1 <= maxDist && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
-          const int fi = (int)(m1 & 0xFFFFFFFFull);
+        auto take = [&](int fi) {
           owner[fi] = (short)j;                                   // every lane stores the same value
           ++nm;
           if (checkOri && lane == 0) atomicAdd(&hist[bow_rot_bin(wAngle[j], cAngle[fi])], 1);
-          __threadfence_block();
+        };
+        if (bestDist1 <= maxDist) {
+          bool taken = false;
+          if ((float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) { take((int)(m1 & 0xFFFFFFFFull)); taken = true; }
+          if (kTwoCameras) {
+            const unsigned long long r1 = topR.min1();
+            if (r1 != ~0ull && (int)(r1 >> 32) <= maxDist) { take((int)(r1 & 0xFFFFFFFFull)); taken = true; }      // :403-431
+          }
+          if (taken) __threadfence_block();
         }
       }
     }
@@ -1330,14 +1345,15 @@ __device__ __forceinline__ int bow_keep_bins(const int* hist, int total, int che
   return total;
 }
 
-// grid = keyframes; LDS: 48 ints + keyCap keys (a power of two >= every keyframe's feature count) + nf shorts
-__global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
-                                                       const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
-                                                       const uint8_t* __restrict__ kfValid, const uint8_t* __restrict__ fDesc,
-                                                       const float* __restrict__ fAngle, const uint32_t* __restrict__ sNode,
-                                                       const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed, int nf,
-                                                       int keyCap, float nnratio, int checkOri, int* __restrict__ matches,
-                                                       int* __restrict__ nmatchesOut) {
+// The body of k_search_by_bow and k_search_by_bow_two_cameras, by the whole block (one keyframe).
+template <bool kTwoCameras>
+__device__ __forceinline__ void search_by_bow_body(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
+                                                   const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
+                                                   const uint8_t* __restrict__ kfValid, const uint8_t* __restrict__ fDesc,
+                                                   const float* __restrict__ fAngle, const uint32_t* __restrict__ sNode,
+                                                   const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed, int nf,
+                                                   int fNleft, int keyCap, float nnratio, int checkOri, int* __restrict__ matches,
+                                                   int* __restrict__ nmatchesOut) {
   extern __shared__ __align__(16) int bowLds[];
   int* hist = bowLds;                                             // 30 bins (32 ints)
   int* misc = bowLds + 32;                                        // [0] keys, [1] matches, [2..4] the bins ComputeThreeMaxima keeps
@@ -1351,8 +1367,8 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
   __syncthreads();
   // the keyframe features that take part: map point set and not bad, listed in a node the frame lists too
   const int m = bow_collect_keys(kfNode + base, kfValid + base, nk, sNode, nfl, key, &misc[0]);
-  const int nm = bow_walk(key, m, kfDesc + (int64_t)base * 32, kfAngle + base, sNode, sIdx, nfl, fDesc, fAngle, owner, hist, BOW_TH_LOW,
-                          nnratio, checkOri);
+  const int nm = bow_walk<kTwoCameras>(key, m, kfDesc + (int64_t)base * 32, kfAngle + base, sNode, sIdx, nfl, fDesc, fAngle, owner, hist,
+                                       BOW_TH_LOW, nnratio, checkOri, fNleft);
   if (lane == 0 && nm) atomicAdd(&misc[1], nm);
   __syncthreads();
   if (tid == 0) nmatchesOut[kf] = bow_keep_bins(hist, misc[1], checkOri, misc + 2);
@@ -1367,6 +1383,35 @@ __global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ k
     }
     row[i] = j;
   }
+}
+
+// grid = keyframes; LDS: 48 ints + keyCap keys (a power of two >= every keyframe's feature count) + nf shorts
+__global__ __launch_bounds__(512) void k_search_by_bow(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
+                                                       const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
+                                                       const uint8_t* __restrict__ kfValid, const uint8_t* __restrict__ fDesc,
+                                                       const float* __restrict__ fAngle, const uint32_t* __restrict__ sNode,
+                                                       const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed, int nf,
+                                                       int keyCap, float nnratio, int checkOri, int* __restrict__ matches,
+                                                       int* __restrict__ nmatchesOut) {
+  search_by_bow_body<false>(kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, sNode, sIdx, nListed, nf, 0, keyCap, nnratio,
+                            checkOri, matches, nmatchesOut);
+}
+
+// SearchByBoW(pKF, F, vpMapPointMatches) for a frame with two cameras (F.Nleft != -1, ORBmatcher.cc:342-369, :373-433): the frame's
+// rows < fNleft are the left camera's.  The independence argument above holds unchanged: the left and the right top-2 of a keyframe
+// feature run over the still-unmatched frame features of ITS node, both matches it may take lie in that node, and "already matched"
+// is the only state, so all state stays inside one node; inside a node the keyframe features go in list order, as before.  A
+// frame feature is taken at most once (owner), by the left or by the right acceptance, so the filter and the counts are those of
+// k_search_by_bow.  Same grid and LDS.
+__global__ __launch_bounds__(512) void k_search_by_bow_two_cameras(const int* __restrict__ kfOff, const uint8_t* __restrict__ kfDesc,
+                                                                   const float* __restrict__ kfAngle, const int* __restrict__ kfNode,
+                                                                   const uint8_t* __restrict__ kfValid, const uint8_t* __restrict__ fDesc,
+                                                                   const float* __restrict__ fAngle, const uint32_t* __restrict__ sNode,
+                                                                   const uint16_t* __restrict__ sIdx, const int* __restrict__ nListed,
+                                                                   int nf, int fNleft, int keyCap, float nnratio, int checkOri,
+                                                                   int* __restrict__ matches, int* __restrict__ nmatchesOut) {
+  search_by_bow_body<true>(kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, sNode, sIdx, nListed, nf, fNleft, keyCap, nnratio,
+                           checkOri, matches, nmatchesOut);
 }
 
 // ---------------------------------------------------------------------------
@@ -1560,7 +1605,7 @@ __global__ __launch_bounds__(512) void k_search_by_bow_kf(const uint8_t* __restr
   for (int i = tid; i < nk; i += blockDim.x) owner[i] = -1;
   __syncthreads();
   const int m = bow_collect_keys(node1, valid1, n1, sn, nl, key, &misc[0]);   // :862-866
-  const int nm = bow_walk(key, m, desc1, angle1, sn, si, nl, kfDesc + (int64_t)base * 32, kfAngle + base, owner, hist, BOW_TH_LOW - 1,
+  const int nm = bow_walk<false>(key, m, desc1, angle1, sn, si, nl, kfDesc + (int64_t)base * 32, kfAngle + base, owner, hist, BOW_TH_LOW - 1,
                           nnratio, checkOri);                     // bestDist1 < TH_LOW :906
   if (lane == 0 && nm) atomicAdd(&misc[1], nm);
   __syncthreads();
@@ -1732,6 +1777,19 @@ __device__ __forceinline__ bool fuse_project_point(const pli_fuse_point& P, cons
   return project_point_tail<true>(P, T, th, levelRatio, nlevels, scaleFactor, S);
 }
 
+// the compact survivor list: ballot + popcount, one atomic per wave (every lane of the wave calls it)
+__device__ __forceinline__ void compact_survivor(bool keep, const FuseSurvivor& S, FuseSurvivor* __restrict__ surv,
+                                                 int* __restrict__ nSurv) {
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+  if (bal) {
+    const int lane = threadIdx.x & 63;
+    int first = 0;
+    if (lane == 0) first = atomicAdd(nSurv, __popcll(bal));
+    first = __shfl(first, 0, 64);
+    if (keep) surv[first + __popcll(bal & ((1ull << lane) - 1ull))] = S;
+  }
+}
+
 // grid = ceil(nkf * nmp / 256)
 __global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __restrict__ mp, int nmp, int nkf,
                                                       const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
@@ -1751,14 +1809,7 @@ __global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __re
     if (P.valid && !(skip && skip[pair]))                        // !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound
       keep = fuse_project_point<0>(P, kfPose + (int64_t)kf * 15, cam, th, levelRatio, nlevels, scaleFactor, S);
   }
-  const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
-  if (bal) {
-    const int lane = threadIdx.x & 63;
-    int first = 0;
-    if (lane == 0) first = atomicAdd(nSurv, __popcll(bal));
-    first = __shfl(first, 0, 64);
-    if (keep) surv[first + __popcll(bal & ((1ull << lane) - 1ull))] = S;
-  }
+  compact_survivor(keep, S, surv, nSurv);
 }
 
 // the minimum of a key over the G lanes of a group (G a power of two <= 64; all lanes of the wave take part)
@@ -1810,8 +1861,10 @@ __device__ __forceinline__ void cell_window_walk(const FuseSurvivor& S, int sub,
   }
 }
 
-// a fixed grid of 256-thread blocks; G lanes per survivor
-template <int G>
+// a fixed grid of 256-thread blocks; G lanes per survivor.  kViews: the tables are the camera views of two-camera keyframes
+// (k_fuse_project_views below): kfUright is not read - the gate is the monocular one, 5.99 - and the winner of a right view
+// gets its keyframe's NLeft added (:1559).
+template <int G, bool kViews>
 __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restrict__ surv, const int* __restrict__ nSurv, int nmp,
                                                     const uint8_t* __restrict__ mpDesc, const int* __restrict__ kfOff,
                                                     const pli_keypoint* __restrict__ kfKp, const uint8_t* __restrict__ kfDesc,
@@ -1835,7 +1888,7 @@ __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restri
                           [&](const pli_keypoint& k, int row) {  // the chi-square gate :1533-1557
                             if (!reprojGate) return true;
                             const float ex = __fsub_rn(S.u, k.x), ey = __fsub_rn(S.v, k.y);
-                            const float kr = kfUright[row];
+                            const float kr = kViews ? -1.f : kfUright[row];
                             float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
                             double lim = 5.99;
                             if (kr >= 0) {
@@ -1852,13 +1905,16 @@ __global__ __launch_bounds__(256) void k_fuse_match(const FuseSurvivor* __restri
       const int dist = key_dist(key);
       const int64_t pair = (int64_t)S.kf * nmp + S.mp;
       if (bestDist) bestDist[pair] = dist;
-      if (dist <= FUSE_TH_LOW) bestIdx[pair] = key_row(key);
+      // (a right view 2k + 1 starts NLeft rows after its left view 2k)
+      const int nleft = kViews && (S.kf & 1) ? kfOff[S.kf] - kfOff[S.kf - 1] : 0;
+      if (dist <= FUSE_TH_LOW) bestIdx[pair] = key_row(key) + nleft;
     }
   }
 }
-template __global__ void k_fuse_match<8>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
-template __global__ void k_fuse_match<16>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
-template __global__ void k_fuse_match<64>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<8, false>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<16, false>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<64, false>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
+template __global__ void k_fuse_match<8, true>(const FuseSurvivor*, const int*, int, const uint8_t*, const int*, const pli_keypoint*, const uint8_t*, const float*, const int*, const uint16_t*, pli_fuse_camera, const float*, int, int*, int*);
 
 // ---------------------------------------------------------------------------
 // Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
@@ -2577,6 +2633,53 @@ __global__ __launch_bounds__(256) void k_tri_match_kb8(const pli_keypoint* __res
   const int kf = blockIdx.y, base = kfOff[kf];
   TriKb8Gate gate{hasMp1, kfKp, ray1, kfRay, rel + (int64_t)kf * 48, sigma2, camL, camR, n1Left, kfNleft[kf], base, coarse};
   tri_match_body(kp1, desc1, node1, n1, base, kfKp, kfDesc, sNode, sIdx, nListed, checkOri, matches12, stat, gate);
+}
+
+// ---------------------------------------------------------------------------
+// The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (ORBmatcher.cc:1399-1609) for keyframes with two
+// KannalaBrandt8 cameras (NLeft != -1), both values of bRight of a batch of keyframes in one call (LocalMapping.cc:747-748,
+// :776-777).  A keyframe's camera is a VIEW: view 2k is keyframe k's left rows (mvKeys, the grid mGrid), view 2k + 1 its right
+// rows (mvKeysRight, mGridRight with camera-local indices, Frame.cc:468-481).  The offset list {off_k, off_k + NLeft_k, ...,
+// off_nkf} of 2 nkf + 1 entries makes every view a "keyframe" of k_fuse_grid and cell_window_walk, which run unchanged.
+//
+//   k_fuse_grid            (unchanged) the cell sort of every view.
+//   k_fuse_project_views   one thread per (view, point): Rcw * p + tcw with the view's pose (GetRotation() / GetRightRotation()
+//                          ..., KeyFrame.cc:1343-1373: host arithmetic), z < 0 (:1459), KannalaBrandt8::project with the view's
+//                          camera (kb8_project, :1470), IsInImage, then project_point_tail<true> with the view's Ow.  A view whose
+//                          side is not asked for keeps -1 / 256.  Survivors are compacted as in k_fuse_project.
+//   k_fuse_match<8, true>  the window walk with the 5.99 gate alone (every mvuRight of such a keyframe is -1, Frame.cc:1589) and
+//                          the right view's winner + NLeft (:1559).
+// Three launches per call, whatever nkf and nmp.
+// ---------------------------------------------------------------------------
+// grid = ceil(2 * nkf * nmp / 256); kfPose: nkf x 2 x 15, skip: nkf x 2 x nmp or null; sides: bit 0 = left, bit 1 = right
+__global__ __launch_bounds__(256) void k_fuse_project_views(const pli_fuse_point* __restrict__ mp, int nmp, int nkf,
+                                                            const float* __restrict__ kfPose, const uint8_t* __restrict__ skip,
+                                                            Kb8 camL, Kb8 camR, pli_fuse_camera bounds, int sides, float th,
+                                                            const float* __restrict__ levelRatio, int nlevels,
+                                                            const float* __restrict__ scaleFactor, FuseSurvivor* __restrict__ surv,
+                                                            int* __restrict__ nSurv, int* __restrict__ bestIdx,
+                                                            int* __restrict__ bestDist) {
+  const int64_t pair = (int64_t)blockIdx.x * 256 + threadIdx.x, npairs = (int64_t)2 * nkf * nmp;
+  bool keep = false;
+  FuseSurvivor S;
+  if (pair < npairs) {
+    const int view = (int)(pair / nmp), i = (int)(pair - (int64_t)view * nmp);
+    S.kf = view; S.mp = i; S.pad = 0; S.ur = 0.f;
+    bestIdx[pair] = -1;
+    if (bestDist) bestDist[pair] = 256;
+    const pli_fuse_point P = mp[i];
+    if (((sides >> (view & 1)) & 1) && P.valid && !(skip && skip[pair])) {     // !pMP, isBad(), IsInKeyFrame(pKF) :1435-1452
+      const float* T = kfPose + (int64_t)view * 15;
+      float pc[3];
+      for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);  // Rcw*p3Dw + tcw :1456
+      if (!(pc[2] < 0.0f)) {                                                   // :1459
+        kb8_project((view & 1) ? camR : camL, pc, S.u, S.v);                   // pCamera->project :1470
+        if (S.u >= bounds.min_x && S.u < bounds.max_x && S.v >= bounds.min_y && S.v < bounds.max_y)  // KeyFrame::IsInImage :1473
+          keep = project_point_tail<true>(P, T, th, levelRatio, nlevels, scaleFactor, S);
+      }
+    }
+  }
+  compact_survivor(keep, S, surv, nSurv);
 }
 
 __global__ void k_fill_f32(float* __restrict__ dst, int n, float v) {

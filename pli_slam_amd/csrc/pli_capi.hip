@@ -1774,6 +1774,20 @@ bool octavesOk(const pli_ctx* c, const pli_keypoint* kp, int64_t n, const char* 
   return true;
 }
 
+// (the two-camera searches: a keypoint's coordinates enter float arithmetic whose result picks cells and gates)
+bool finiteOk(const pli_keypoint* kp, int64_t n, const char* what) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(kp[i].x) || !std::isfinite(kp[i].y)) { g_err = std::string(what) + ": a keypoint's coordinates are not finite"; return false; }
+  return true;
+}
+
+// kf_nleft[k] = NLeft of keyframe k, inside its rows
+bool nleftOk(int32_t nkf, const int32_t* kfOff, const int32_t* kfNleft, const char* msg) {
+  for (int k = 0; k < nkf; ++k)
+    if (kfNleft[k] < 0 || kfNleft[k] > kfOff[k + 1] - kfOff[k]) { g_err = msg; return false; }
+  return true;
+}
+
 int pow2Ceil(int m) {
   int n = 1;
   while (n < m) n <<= 1;
@@ -3368,10 +3382,11 @@ pli_status pli_kfdb_query(pli_ctx* c, pli_kfdb* db, const uint32_t* qword, const
 }
 
 // ---- the searches of one item against a batch of keyframes (shared host part: KfBatch and the checks above) ----
-pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
-                             const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
-                             const int32_t* fNode, int32_t nf, float nnratio, int32_t checkOri, int32_t* matches, int32_t* nmatches) {
-  CtxGuard guard__(c);
+// pli_search_by_bow (fNleft < 0: F.Nleft == -1) and pli_search_by_bow_two_cameras (the frame's first fNleft rows are the left camera's)
+static pli_status searchByBow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
+                              const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
+                              const int32_t* fNode, int32_t nf, int32_t fNleft, float nnratio, int32_t checkOri, int32_t* matches,
+                              int32_t* nmatches) {
   if (!c || nkf < 0 || nf < 0 || (nkf > 0 && (!kfOff || !nmatches)) || (nf > 0 && (!fDesc || !fNode || (checkOri && !fAngle))) ||
       (nkf > 0 && nf > 0 && !matches)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
   if (nkf == 0) return PLI_OK;
@@ -3413,12 +3428,33 @@ pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, cons
   // the frame is one table without an offset list: every feature listed in a node (no flag, no stereo table, no stat)
   LAUNCH(c, "k_node_sort", k_node_sort, dim3(1), dim3(1024), (size_t)sortN * 6, (const int*)nullptr, nf, dFn, (const uint8_t*)nullptr, 0,
          (const uint8_t*)nullptr, 0, sortN, dSn, dSi, dListed, (int*)nullptr);
-  LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16), dOff,
-         dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
+  const size_t lds = 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16);
+  if (fNleft < 0)
+    LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), lds, dOff, dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf,
+           keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
+  else
+    LAUNCH(c, "k_search_by_bow_two_cameras", k_search_by_bow_two_cameras, dim3(nkf), dim3(512), lds, dOff, dKd, dKa, dKn, dKv, dFd, dFa,
+           dSn, dSi, dListed, nf, fNleft, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
   HIPCHK(download(c, matches, dM, (size_t)nkf * nf));
   HIPCHK(download(c, nmatches, dN, nkf));
   HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
+}
+
+pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
+                             const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
+                             const int32_t* fNode, int32_t nf, float nnratio, int32_t checkOri, int32_t* matches, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  return searchByBow(c, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, -1, nnratio, checkOri, matches, nmatches);
+}
+
+pli_status pli_search_by_bow_two_cameras(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
+                                         const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
+                                         const int32_t* fNode, int32_t nf, int32_t fNleft, float nnratio, int32_t checkOri,
+                                         int32_t* matches, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (fNleft < 0 || fNleft > nf) { g_err = "f_nleft outside [0, nf]"; return PLI_ERR_INVALID; }
+  return searchByBow(c, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, fNleft, nnratio, checkOri, matches, nmatches);
 }
 
 pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* angle1, const int32_t* node1, const uint8_t* valid1,
@@ -3562,14 +3598,8 @@ pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoi
   if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
   const int64_t total = B.total;
   if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  for (int k = 0; k < nkf; ++k)
-    if (kfNleft[k] < 0 || kfNleft[k] > kfOff[k + 1] - kfOff[k]) { g_err = "kf_nleft outside [0, the neighbour's rows]"; return PLI_ERR_INVALID; }
+  if (!nleftOk(nkf, kfOff, kfNleft, "kf_nleft outside [0, the neighbour's rows]")) return PLI_ERR_INVALID;
   // the gate projects with the coordinates and indexes mvLevelSigma2 by the octaves: the rule of pli_stereo_fisheye_tables
-  auto finiteOk = [](const pli_keypoint* kp, int64_t n, const char* what) {
-    for (int64_t i = 0; i < n; ++i)
-      if (!std::isfinite(kp[i].x) || !std::isfinite(kp[i].y)) { g_err = std::string(what) + ": a keypoint's coordinates are not finite"; return false; }
-    return true;
-  };
   if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || !finiteOk(kp1, n1, "kp1") ||
       (checkOri && !anglesOk(kp1, n1, "kp1: angle")))
     return PLI_ERR_INVALID;
@@ -3694,12 +3724,84 @@ pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* 
   if (const char* e = DEVENV("PLI_FUSE_LANES")) lanes = atoi(e);
   const dim3 mgrid(1024);
 #define FUSE_MATCH(G)                                                                                                              \
-  LAUNCH(c, "k_fuse_match", k_fuse_match<G>, mgrid, dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd, dKu, dCell, dSi, *cam,     \
+  LAUNCH(c, "k_fuse_match", (k_fuse_match<G, false>), mgrid, dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd, dKu, dCell, dSi, *cam,     \
          lv + 2 * MAX_LEVELS, reprojGate ? 1 : 0, dBi, dBd)
   if (lanes == 16) FUSE_MATCH(16);
   else if (lanes == 64) FUSE_MATCH(64);
   else FUSE_MATCH(8);
 #undef FUSE_MATCH
+  HIPCHK(download(c, bestIdx, dBi, npairs));
+  if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
+pli_status pli_fuse_search_two_cameras(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf,
+                                       const int32_t* kfOff, const int32_t* kfNleft, const pli_keypoint* kfKp, const uint8_t* kfDesc,
+                                       const float* kfPose, const uint8_t* skip, const pli_kb8_camera* camLeft,
+                                       const pli_kb8_camera* camRight, float minX, float maxX, float minY, float maxY, float th,
+                                       const float* levelRatio, int32_t sides, int32_t* bestIdx, int32_t* bestDist) {
+  CtxGuard guard__(c);
+  if (!c || nmp < 0 || nkf < 0 || !camLeft || !camRight || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) ||
+      (nkf > 0 && (!kfOff || !kfNleft || !kfPose)) || (nkf > 0 && nmp > 0 && !bestIdx)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (sides < 1 || sides > 3) { g_err = "sides: bit 0 = left, bit 1 = right, at least one"; return PLI_ERR_INVALID; }
+  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(minX, maxX, minY, maxY)) return PLI_ERR_INVALID;
+  if (nkf == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the Fuse cap", B);
+  if (st != PLI_OK) return st;
+  const int64_t total = B.total;
+  if (total > 0 && (!kfKp || !kfDesc)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (!nleftOk(nkf, kfOff, kfNleft, "kf_nleft outside [0, the keyframe's rows]")) return PLI_ERR_INVALID;
+  if (!octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
+  for (int64_t i = 0; i < (int64_t)nkf * 30; ++i)
+    if (!std::isfinite(kfPose[i])) { g_err = "kf_pose: a pose is not finite"; return PLI_ERR_INVALID; }
+  if (nmp == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const int nview = 2 * nkf;
+  const size_t npairs = (size_t)nview * nmp;
+  // view 2k = keyframe k's left rows, view 2k + 1 its right rows: one ascending offset list for k_fuse_grid and the window walk
+  std::vector<int> viewOff((size_t)nview + 1);
+  for (int k = 0; k < nkf; ++k) { viewOff[2 * k] = kfOff[k]; viewOff[2 * k + 1] = kfOff[k] + kfNleft[k]; }
+  viewOff[nview] = kfOff[nkf];
+  ScratchPlan plan;
+  auto dMp = plan.add<pli_fuse_point>(nmp);
+  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
+  auto dOff = plan.add<int>((size_t)nview + 1);
+  auto dKk = plan.add<pli_keypoint>(total);
+  auto dKd = plan.add<uint8_t>((size_t)total * 32);
+  auto dPose = plan.add<float>((size_t)nview * 15);
+  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, npairs);
+  auto dLv = plan.add<float>(3 * MAX_LEVELS);               // level_ratio, mvScaleFactors, mvInvLevelSigma2
+  auto dCell = plan.add<int>((size_t)nview * (GRID_COLS * GRID_ROWS + 1));
+  auto dSi = plan.add<uint16_t>(total);
+  auto dSurv = plan.add<FuseSurvivor>(npairs);
+  auto dNs = plan.add<int>(1);
+  auto dBi = plan.add<int>(npairs);
+  auto dBd = plan.addIf<int>(bestDist != nullptr, npairs);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  const LevelBlock hlv(c, levelRatio, 3);
+  HIPCHK(upload(c, dMp, mp, nmp));
+  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
+  HIPCHK(upload(c, dOff, (const int*)viewOff.data(), (size_t)nview + 1));
+  HIPCHK(upload(c, dKk, kfKp, total));
+  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
+  HIPCHK(upload(c, dPose, kfPose, (size_t)nview * 15));
+  if (skip) HIPCHK(upload(c, dSkip, skip, npairs));
+  HIPCHK(upload(c, dLv, hlv.v, 3 * MAX_LEVELS));
+  HIPCHK(hipMemsetAsync(dNs, 0, sizeof(int), c->stream));
+  Kb8 cl, cr;
+  memcpy(&cl, camLeft, sizeof(cl));
+  memcpy(&cr, camRight, sizeof(cr));
+  pli_fuse_camera bounds = {};                              // only the bounds are read (IsInImage, the 64 x 48 grid)
+  bounds.min_x = minX; bounds.max_x = maxX; bounds.min_y = minY; bounds.max_y = maxY;
+  const float* lv = dLv;
+  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(nview), dim3(256), 0, dOff, dKk, bounds, dCell, dSi);
+  LAUNCH(c, "k_fuse_project_views", k_fuse_project_views, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose,
+         dSkip, cl, cr, bounds, sides, th, lv, c->hp.nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBd);
+  LAUNCH(c, "k_fuse_match", (k_fuse_match<8, true>), dim3(1024), dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd,
+         (const float*)nullptr, dCell, dSi, bounds, lv + 2 * MAX_LEVELS, 1, dBi, dBd);
   HIPCHK(download(c, bestIdx, dBi, npairs));
   if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
   HIPCHK(hipStreamSynchronize(c->stream));

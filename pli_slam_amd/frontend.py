@@ -299,6 +299,27 @@ class Frontend:
                                        nnratio, int(check_orientation), ptr(matches), ptr(nmatches)))
         return matches, nmatches
 
+    def search_by_bow_two_cameras(self, kfs, f_desc, f_angle, f_node, f_nleft, nnratio=0.7, check_orientation=True):
+        """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:269-470), the branch F.Nleft != -1 (:342-369,
+        :403-432: a frame of two KannalaBrandt8 cameras), of every keyframe of `kfs` against one frame, in one call.  Tables as in
+        search_by_bow; f_nleft = F.Nleft, the frame's rows are the left camera's first; the angles are the caller's choice
+        (kf: mvKeysUn, or mvKeys / mvKeysRight by NLeft, :379-382; frame: mvKeys / mvKeysRight by Nleft, :386-389, :416-419).
+        Per keyframe feature the left candidates (< f_nleft) and the right ones keep a best and a second best each; only if
+        bestDist1 <= TH_LOW the left match is taken on its ratio test and the right one when bestDist1R <= TH_LOW, without a
+        ratio test (:373-433).  Returns (matches[nkf, nf], nmatches[nkf])."""
+        fd = np.ascontiguousarray(f_desc, np.uint8).reshape(-1, 32)
+        nf = fd.shape[0]
+        fa = np.ascontiguousarray(f_angle, np.float32).reshape(nf)
+        fn = np.ascontiguousarray(f_node, np.int32).reshape(nf)
+        nkf = len(kfs)
+        off, (kd, ka, kn, kv) = pack_keyframes(kfs, BOW_COLUMNS, "every keyframe needs one angle, node and valid flag per descriptor")
+        matches = np.full((nkf, nf), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        check(self.L.pli_search_by_bow_two_cameras(self.h, nkf, ptr(off), ptr(kd), ptr(ka), ptr(kn), ptr(kv), ptr(fd), ptr(fa),
+                                                   ptr(fn), nf, int(f_nleft), nnratio, int(check_orientation), ptr(matches),
+                                                   ptr(nmatches)))
+        return matches, nmatches
+
     def search_by_bow_kf(self, desc1, angle1, node1, valid1, kfs, nnratio=0.75, check_orientation=True):
         """ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:823-963, NLeft == -1) of keyframe 1 against every
         keyframe of `kfs`, in one call (loop closing).  desc1 / angle1 / node1 / valid1 and each (desc, angle, node, valid) of
@@ -362,6 +383,17 @@ class Frontend:
                                                               int(check_orientation), ptr(matches), ptr(nmatches)))
         return matches, nmatches
 
+    def _level_ratio(self, level_ratio):
+        """The level_ratio table of the projection searches: the caller's, or this host's (fuse_level_ratio), made once."""
+        if level_ratio is None:
+            if getattr(self, "_fuse_level_ratio", None) is None:
+                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
+            level_ratio = self._fuse_level_ratio
+        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
+        if len(level_ratio) != self.cfg.orb_nlevels - 1:
+            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        return level_ratio
+
     def fuse_search(self, points, descs, keyframes, cam, th=3.0, reproj_gate=True, skip=None, level_ratio=None):
         """The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reproj_gate=False: the Sim3
         overload :1611-1733) of the map points `points` (capi.FUSE_POINT_DT rows) with descriptors `descs` against every keyframe
@@ -381,18 +413,46 @@ class Frontend:
             skip = np.ascontiguousarray(skip, np.uint8)
             if skip.shape != (nkf, nmp):
                 raise ValueError("skip: nkf x nmp")
-        if level_ratio is None:
-            if getattr(self, "_fuse_level_ratio", None) is None:
-                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
-            level_ratio = self._fuse_level_ratio
-        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
-        if len(level_ratio) != self.cfg.orb_nlevels - 1:
-            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        level_ratio = self._level_ratio(level_ratio)
         best_idx = np.full((nkf, nmp), -1, np.int32)
         best_dist = np.full((nkf, nmp), 256, np.int32)
         check(self.L.pli_fuse_search(self.h, ptr(pts), ptr(d), nmp, nkf, ptr(off), ptr(kk), ptr(kd), ptr(ku), ptr(pose),
                                      ptr(skip), C.byref(cam), float(th), ptr(level_ratio), int(reproj_gate), ptr(best_idx),
                                      ptr(best_dist)))
+        return best_idx, best_dist
+
+    def fuse_search_two_cameras(self, points, descs, keyframes, cam_left, cam_right, bounds, th=3.0, sides=3, skip=None,
+                                level_ratio=None):
+        """The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (ORBmatcher.cc:1399-1609) for keyframes with two
+        KannalaBrandt8 cameras (NLeft != -1), both values of bRight (LocalMapping.cc:747-748, :776-777) of every keyframe of
+        `keyframes` in one call.  points / descs as in fuse_search; keyframes: list of (kp, desc, nleft, pose) - mvKeys then
+        mvKeysRight as KEYPOINT_DT rows (:1524-1526), mDescriptors, NLeft, pose = 2 x 15 floats, left then right (Rcw row major,
+        tcw, Ow; the right one from GetRightRotation() / GetRightTranslation() / GetRightCameraCenter(), KeyFrame.cc:1343-1373);
+        cam_left / cam_right: the 8 KannalaBrandt8 parameters of mpCamera / mpCamera2; bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY);
+        sides: bit 0 = left, bit 1 = right; skip: nkf x 2 x nmp, != 0 leaves a (keyframe, side, point) out (IsInKeyFrame, :1448).
+        The chi-square gate is the monocular one, 5.99 (:1555): every mvuRight of such a keyframe is -1 (Frame.cc:1589).
+        Returns (best_idx[nkf, 2, nmp]: the row over the keyframe's N - a right row is its camera-local row + NLeft, :1559 - or
+        -1, best_dist[nkf, 2, nmp])."""
+        pts = np.ascontiguousarray(points, capi.FUSE_POINT_DT).reshape(-1)
+        d = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        if len(d) != len(pts):
+            raise ValueError("every map point needs one descriptor")
+        nkf, nmp = len(keyframes), len(pts)
+        off, (kk, kd) = pack_keyframes(keyframes, FUSE_COLUMNS[:2], "every feature needs one keypoint and one descriptor")
+        nleft = np.ascontiguousarray([int(kf[2]) for kf in keyframes], np.int32).reshape(nkf)
+        pose = np.ascontiguousarray([np.asarray(kf[3], np.float32).reshape(30) for kf in keyframes], np.float32).reshape(nkf, 30)
+        cl, cr = np.ascontiguousarray(cam_left, np.float32).reshape(8), np.ascontiguousarray(cam_right, np.float32).reshape(8)
+        min_x, max_x, min_y, max_y = (float(v) for v in bounds)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint8)
+            if skip.shape != (nkf, 2, nmp):
+                raise ValueError("skip: nkf x 2 x nmp")
+        level_ratio = self._level_ratio(level_ratio)
+        best_idx = np.full((nkf, 2, nmp), -1, np.int32)
+        best_dist = np.full((nkf, 2, nmp), 256, np.int32)
+        check(self.L.pli_fuse_search_two_cameras(self.h, ptr(pts), ptr(d), nmp, nkf, ptr(off), ptr(nleft), ptr(kk), ptr(kd),
+                                                 ptr(pose), ptr(skip), ptr(cl), ptr(cr), min_x, max_x, min_y, max_y, float(th),
+                                                 ptr(level_ratio), int(sides), ptr(best_idx), ptr(best_dist)))
         return best_idx, best_dist
 
     def search_by_projection_sim3(self, points, descs, pairs, cam, th=3.0, ratio_hamming=1.0, project_form=0, skip=None,
@@ -428,13 +488,7 @@ class Frontend:
             skip = np.ascontiguousarray(skip, np.uint8)
             if skip.shape != (npair, nmp):
                 raise ValueError("skip: npair x nmp")
-        if level_ratio is None:
-            if getattr(self, "_fuse_level_ratio", None) is None:
-                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
-            level_ratio = self._fuse_level_ratio
-        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
-        if len(level_ratio) != self.cfg.orb_nlevels - 1:
-            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        level_ratio = self._level_ratio(level_ratio)
         rows = np.full(int(off[-1]), -1, np.int32)
         best_idx = np.full((npair, nmp), -1, np.int32)
         nmatches = np.zeros(npair, np.int32)
@@ -480,13 +534,7 @@ class Frontend:
                     occ[k] = o != 0
         if not isinstance(cam, capi.FuseCamera):
             cam = capi.FuseCamera(*[float(v) for v in cam])
-        if level_ratio is None:
-            if getattr(self, "_fuse_level_ratio", None) is None:
-                self._fuse_level_ratio = fuse_level_ratio(self.cfg.orb_nlevels, self.cfg.orb_scale_factor)
-            level_ratio = self._fuse_level_ratio
-        level_ratio = np.ascontiguousarray(level_ratio, np.float32)
-        if len(level_ratio) != self.cfg.orb_nlevels - 1:
-            raise ValueError("level_ratio: orb_nlevels - 1 thresholds")
+        level_ratio = self._level_ratio(level_ratio)
         rows = np.full((ncand, nf), -1, np.int32)
         best_idx = np.full(int(off[-1]), -1, np.int32)
         nmatches = np.zeros(ncand, np.int32)
