@@ -1,8 +1,8 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.
-// Stand-in for everything the reference's src/ORBmatcher.cc (and src/CameraModels/Pinhole.cpp) reaches through its headers, written
-// for this project.  oracle/Makefile force-includes this file (-include) in front of those sources, which are compiled where they
-// lie, unmodified.  It predefines the include guards of the reference's MapPoint.h, KeyFrame.h, Frame.h, Pinhole.h,
-// GeometricCamera.h and TwoViewReconstruction.h, so that those headers (and OpenCV, Eigen, g2o, Sophus, boost behind them) stay
+// Stand-in for everything the reference's src/ORBmatcher.cc (and src/CameraModels/Pinhole.cpp, src/CameraModels/KannalaBrandt8.cpp)
+// reaches through its headers, written for this project.  oracle/Makefile force-includes this file (-include) in front of those
+// sources, which are compiled where they lie, unmodified.  It predefines the include guards of the reference's MapPoint.h, KeyFrame.h,
+// Frame.h, Pinhole.h, KannalaBrandt8.h, GeometricCamera.h and TwoViewReconstruction.h, so that those headers (and OpenCV, Eigen, g2o, Sophus, boost behind them) stay
 // out, and declares classes of this project's own that carry only the members those two sources touch.  Member names and types are
 // the reference's; every body is ours.
 //
@@ -15,16 +15,26 @@
 //   * inv() of a 3 x 3 CV_32F matrix is the closed form: determinant and cofactors in double, each element
 //     (float)(cofactor * (1 / det)), all zeros for det == 0.
 //   * Mat::dot and cv::norm sum in double and return double.
+//   * s * Mat - Mat (KannalaBrandt8::Triangulate) is (float)(x * s) and then a float subtraction per element.
+//   * cv::SVD::compute (4 x 4 CV_32F), cv::hconcat, Mat::eye and the Mat / s of the two-camera functions (a float factor, see
+//     shim_detail::divisionFactorInFloat) are THIS PROJECT'S STATEMENT of OpenCV too, the same as oracle/match_oracle.hpp's.
+//   * An expression assigned to a matrix of its own size and type fills that storage (A.row(0) = ...), as OpenCV's does.
 // WHAT THE PIN THEREFORE COVERS: ORBmatcher.cc's own control flow, gates, visiting orders and scalar arithmetic, over this
 // project's statement of cv::Mat, Frame / KeyFrame::GetFeaturesInArea (restated from Frame.cc:774-843 / KeyFrame.cc:881-925 in the
 // reference's loop order: columns, then rows, then the cell's list), IsInImage, the grid assignment and MapPoint::PredictScale.
-// It does NOT cover OpenCV's own bits (gemm accumulation order, MatExpr folding, inv); those stay with tools/pin/run_pin.sh.
+// For KannalaBrandt8.cpp: its own float arithmetic, gates and the overloads its libm calls select.  Two-camera tables (NLeft != -1):
+// KeyFrame's right-pose getters are restated from KeyFrame.cc:1290-1373, KeyFrame::GetFeaturesInArea(..., bRight) from
+// KeyFrame.cc:881-925 and Frame::GetFeaturesInArea(..., bRight) from Frame.cc:774-843, both over the two grids of Frame.cc:468-481.
+// Driven for two cameras: SearchForTriangulation, SearchByBoW, Fuse and both frame SearchByProjection forms (the frame-to-frame one
+// with a one-camera last frame).
+// It does NOT cover OpenCV's own bits (gemm accumulation order, MatExpr folding, inv, the SVD); those stay with tools/pin/run_pin.sh.
 #ifndef PLI_MATCH_SHIM_HPP
 #define PLI_MATCH_SHIM_HPP
 #define MAPPOINT_H
 #define KEYFRAME_H
 #define FRAME_H
 #define CAMERAMODELS_PINHOLE_H
+#define CAMERAMODELS_KANNALABRANDT8_H
 #define CAMERAMODELS_GEOMETRICCAMERA_H
 #define TwoViewReconstruction_H
 
@@ -43,6 +53,13 @@
 #define CV_8U 0
 #define CV_32S 4
 #define CV_32F 5
+#define CV_PI 3.1415926535897932384626433832795
+
+// STANDARD MATH HEADERS.  OpenCV 3.3.1's core.hpp reaches <cmath> (cvdef.h -> fast_math.hpp) and no <math.h>; this file
+// includes <cmath> and no <math.h> either.  That decides which overload an unqualified cos(float) in the reference's
+// KannalaBrandt8.cpp selects: with <cmath> alone the global namespace holds only the C functions, so cos(float) is cos(double).
+// The `using namespace std;` below would add the float overloads, and the header chain of KannalaBrandt8.cpp has none, so
+// oracle/Makefile compiles that one file with -DPLI_MATCH_SHIM_NO_USING_STD.
 
 namespace cv {
 
@@ -64,12 +81,20 @@ struct KeyPoint {
 
 class Mat;
 
+namespace shim_detail {
+// Mat / s.  This project holds two statements of it: (float)(x * (1.0 / s)) in double (the convention above, which the Sim3 searches
+// of ORBmatcher.cc are pinned over), and x * (float)(1.0 / s) + 0.f in float (oracle/match_oracle.hpp: kb8TriangulateMatches,
+// after convertTo's float work type for CV_32F).  The driver switches the second on for the two-camera functions, whose only
+// division is the one in KannalaBrandt8::Triangulate; the single-camera cases keep the first.
+inline bool& divisionFactorInFloat() { static bool on = false; return on; }
+}  // namespace shim_detail
+
 // a lazy product / scale / transpose / inverse, evaluated when it becomes a Mat
 struct MatExpr {
   enum Kind { SCALE, GEMM, INV, ADD };
   Kind kind = SCALE;
   std::shared_ptr<Mat> a, b, c;      // SCALE: alpha * op(a); GEMM: alpha * op(a) * op(b) + beta * c; INV: inv(a); ADD: a + beta * b
-  bool ta = false, tb = false;
+  bool ta = false, tb = false, division = false;
   double alpha = 1.0, beta = 1.0;
   MatExpr t() const;
   MatExpr inv() const;
@@ -85,7 +110,9 @@ class Mat {
   Mat() {}
   Mat(int r, int c, int type) { create(r, c, type); }
   Mat(const MatExpr& e) { *this = e.eval(); }
-  Mat& operator=(const MatExpr& e) { *this = e.eval(); return *this; }
+  // an expression assigned to a matrix of its own size and type is written into that storage (A.row(0) = ... fills A)
+  Mat& operator=(const MatExpr& e);
+  static MatExpr eye(int r, int c, int type);
 
   void create(int r, int c, int type) {
     rows = r; cols = c; flags = type;
@@ -137,6 +164,16 @@ class Mat {
 
 inline double norm(const Mat& m) { return std::sqrt(m.dot(m)); }
 
+inline Mat& Mat::operator=(const MatExpr& e) {
+  const Mat v = e.eval();
+  if (data && rows == v.rows && cols == v.cols && flags == v.flags) {
+    for (int r = 0; r < rows; ++r) std::memcpy(data + (size_t)r * step, v.data + (size_t)r * v.step, (size_t)cols * elemSize());
+  } else {
+    *this = v;
+  }
+  return *this;
+}
+
 inline MatExpr MatExpr::t() const {
   if (kind == SCALE) { MatExpr e = *this; e.ta = !ta; return e; }
   return eval().t();
@@ -151,7 +188,8 @@ inline Mat MatExpr::eval() const {
     for (int i = 0; i < R; ++i)
       for (int j = 0; j < C; ++j) {
         const float v = ta ? a->at<float>(j, i) : a->at<float>(i, j);
-        out.at<float>(i, j) = alpha == 1.0 ? v : (float)((double)v * alpha);
+        if (division && shim_detail::divisionFactorInFloat()) out.at<float>(i, j) = v * (float)alpha + 0.f;
+        else out.at<float>(i, j) = alpha == 1.0 ? v : (float)((double)v * alpha);
       }
   } else if (kind == GEMM) {
     const int R = ta ? a->cols : a->rows, K = ta ? a->rows : a->cols, C = tb ? b->rows : b->cols;
@@ -223,8 +261,8 @@ inline MatExpr operator*(double s, const Mat& x) { return shim_detail::scale(shi
 inline MatExpr operator*(double s, const MatExpr& x) { return shim_detail::scale(x, s); }
 inline MatExpr operator*(const Mat& x, double s) { return shim_detail::scale(shim_detail::leaf(x), s); }
 inline MatExpr operator*(const MatExpr& x, double s) { return shim_detail::scale(x, s); }
-inline MatExpr operator/(const Mat& x, double s) { return shim_detail::scale(shim_detail::leaf(x), 1.0 / s); }
-inline MatExpr operator/(const MatExpr& x, double s) { return shim_detail::scale(x, 1.0 / s); }
+inline MatExpr operator/(const Mat& x, double s) { MatExpr e = shim_detail::scale(shim_detail::leaf(x), 1.0 / s); e.division = true; return e; }
+inline MatExpr operator/(const MatExpr& x, double s) { MatExpr e = shim_detail::scale(x, 1.0 / s); e.division = e.kind == MatExpr::SCALE; return e; }
 inline MatExpr operator-(const Mat& x) { return shim_detail::scale(shim_detail::leaf(x), -1.0); }
 inline MatExpr operator-(const MatExpr& x) { return shim_detail::scale(x, -1.0); }
 inline MatExpr operator+(const Mat& x, const Mat& y) { return shim_detail::add(shim_detail::leaf(x), shim_detail::leaf(y), 1.0); }
@@ -254,6 +292,120 @@ template <class T, class V> MatCommaInitializer_<T> operator<<(const Mat_<T>& m,
   return (ci, v);
 }
 
+inline MatExpr Mat::eye(int r, int c, int type) {
+  assert(type == CV_32F);
+  Mat m(r, c, type);
+  for (int i = 0; i < std::min(r, c); ++i) m.at<float>(i, i) = 1.f;
+  return shim_detail::leaf(m);
+}
+
+// cv::hconcat of two CV_32F matrices with equal rows
+inline void hconcat(const Mat& a, const Mat& b, Mat& dst) {
+  assert(a.rows == b.rows && a.type() == CV_32F && b.type() == CV_32F);
+  Mat m(a.rows, a.cols + b.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r) {
+    for (int c = 0; c < a.cols; ++c) m.at<float>(r, c) = a.at<float>(r, c);
+    for (int c = 0; c < b.cols; ++c) m.at<float>(r, a.cols + c) = b.at<float>(r, c);
+  }
+  dst = m;
+}
+
+inline std::ostream& operator<<(std::ostream& os, const Mat& m) {
+  for (int r = 0; r < m.rows; ++r)
+    for (int c = 0; c < m.cols; ++c) os << (c ? ", " : r ? "; " : "[") << m.at<float>(r, c);
+  return os << "]";
+}
+
+// cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) for a 4 x 4 CV_32F matrix only: THIS PROJECT'S STATEMENT of OpenCV 3.3.1's
+// one-sided Jacobi (lapack.cpp: JacobiSVDImpl_<float> on the transposed matrix; eps = 2 * FLT_EPSILON, at most 30 sweeps, the
+// rotations in float, norms and dot products in double, hypot(p, beta) as sqrt(p * p + beta * beta) in double, rows sorted by
+// singular value), the same statement as oracle/match_oracle.hpp: jacobiSvdLastVt4.  w and vt are filled; u is left empty (the
+// only caller, KannalaBrandt8::Triangulate, reads vt alone).
+struct SVD {
+  enum { MODIFY_A = 1, NO_UV = 2, FULL_UV = 4 };
+  static void compute(const Mat& A, Mat& w, Mat& u, Mat& vt, int flags = 0) {
+    if (A.rows != 4 || A.cols != 4 || A.type() != CV_32F || flags != (MODIFY_A | FULL_UV)) {
+      std::cerr << "match_shim: cv::SVD::compute is stated for 4 x 4 CV_32F with MODIFY_A | FULL_UV only" << std::endl;
+      std::abort();
+    }
+    const int n = 4;
+    float At[4][4], Vt[4][4];
+    double W[4];
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < n; ++k) At[i][k] = A.at<float>(k, i);
+    const float eps = 1.1920928955078125e-07f * 2;
+    for (int i = 0; i < n; ++i) {
+      double sd = 0;
+      for (int k = 0; k < n; ++k) { const float t = At[i][k]; sd += (double)t * t; }
+      W[i] = sd;
+      for (int k = 0; k < n; ++k) Vt[i][k] = i == k ? 1.f : 0.f;
+    }
+    for (int iter = 0; iter < 30; ++iter) {
+      bool changed = false;
+      for (int i = 0; i < n - 1; ++i)
+        for (int j = i + 1; j < n; ++j) {
+          float *Ai = At[i], *Aj = At[j];
+          double a = W[i], p = 0, b = W[j];
+          for (int k = 0; k < n; ++k) p += (double)Ai[k] * Aj[k];
+          if (std::fabs(p) <= (double)eps * std::sqrt(a * b)) continue;
+          p *= 2;
+          const double beta = a - b, gamma = std::sqrt(p * p + beta * beta);
+          float c, s;
+          if (beta < 0) {
+            const double delta = (gamma - beta) * 0.5;
+            s = (float)std::sqrt(delta / gamma);
+            c = (float)(p / (gamma * s * 2));
+          } else {
+            c = (float)std::sqrt((gamma + beta) / (gamma * 2));
+            s = (float)(p / (gamma * c * 2));
+          }
+          a = b = 0;
+          for (int k = 0; k < n; ++k) {
+            const float t0 = c * Ai[k] + s * Aj[k], t1 = -s * Ai[k] + c * Aj[k];
+            Ai[k] = t0; Aj[k] = t1;
+            a += (double)t0 * t0; b += (double)t1 * t1;
+          }
+          W[i] = a; W[j] = b;
+          changed = true;
+          float *Vi = Vt[i], *Vj = Vt[j];
+          for (int k = 0; k < n; ++k) {
+            const float t0 = c * Vi[k] + s * Vj[k], t1 = -s * Vi[k] + c * Vj[k];
+            Vi[k] = t0; Vj[k] = t1;
+          }
+        }
+      if (!changed) break;
+    }
+    for (int i = 0; i < n; ++i) {
+      double sd = 0;
+      for (int k = 0; k < n; ++k) { const float t = At[i][k]; sd += (double)t * t; }
+      W[i] = std::sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; ++i) {
+      int j = i;
+      for (int k = i + 1; k < n; ++k)
+        if (W[j] < W[k]) j = k;
+      if (i != j) {
+        std::swap(W[i], W[j]);
+        for (int k = 0; k < n; ++k) { std::swap(At[i][k], At[j][k]); std::swap(Vt[i][k], Vt[j][k]); }
+      }
+    }
+    Mat wm(4, 1, CV_32F), vm(4, 4, CV_32F);
+    for (int i = 0; i < n; ++i) {
+      wm.at<float>(i, 0) = (float)W[i];
+      for (int k = 0; k < n; ++k) vm.at<float>(i, k) = Vt[i][k];
+    }
+    w = wm; vt = vm; u = Mat();
+  }
+};
+
+// declared for KannalaBrandt8::ReconstructWithTwoViews, which no case reaches
+namespace fisheye {
+inline void undistortPoints(const std::vector<Point2f>&, std::vector<Point2f>&, const Mat&, const Mat&, const Mat&, const Mat&) {
+  std::cerr << "match_shim: cv::fisheye::undistortPoints has no stand-in" << std::endl;
+  std::abort();
+}
+}  // namespace fisheye
+
 }  // namespace cv
 
 // the few Eigen names Pinhole.cpp mentions
@@ -269,7 +421,9 @@ typedef Matrix<double, 2, 1> Vector2d;
 typedef Matrix<double, 3, 1> Vector3d;
 }  // namespace Eigen
 
+#ifndef PLI_MATCH_SHIM_NO_USING_STD
 using namespace std;      // the reference's ORBmatcher.h writes map<>, pair<> and vector<> unqualified (its header chain says this)
+#endif
 
 namespace ORB_SLAM3 {
 
@@ -300,6 +454,8 @@ class GeometricCamera {
   virtual ~GeometricCamera() {}
   virtual cv::Point2f project(const cv::Point3f& p3D) = 0;
   virtual cv::Point2f project(const cv::Mat& m3D) = 0;
+  virtual cv::Point3f unproject(const cv::Point2f& p2D) = 0;
+  virtual cv::Mat unprojectMat(const cv::Point2f& p2D) = 0;
   virtual cv::Mat toK() = 0;
   virtual bool epipolarConstrain(GeometricCamera* otherCamera, const cv::KeyPoint& kp1, const cv::KeyPoint& kp2, const cv::Mat& R12,
                                  const cv::Mat& t12, const float sigmaLevel, const float unc) = 0;
@@ -341,6 +497,43 @@ class Pinhole : public GeometricCamera {
   TwoViewReconstruction* tvr;
 };
 
+// exactly the members src/CameraModels/KannalaBrandt8.cpp defines, as include/CameraModels/KannalaBrandt8.h declares them (without
+// the serialisation); the bodies come from that file.  precision is the header's 1e-6.
+class KannalaBrandt8 final : public GeometricCamera {
+ public:
+  KannalaBrandt8(const std::vector<float> _vParameters) : GeometricCamera(_vParameters), mvLappingArea(2, 0), precision(1e-6), tvr(nullptr) {
+    assert(mvParameters.size() == 8);
+  }
+  cv::Point2f project(const cv::Point3f& p3D);
+  cv::Point2f project(const cv::Mat& m3D);
+  Eigen::Vector2d project(const Eigen::Vector3d& v3D);
+  cv::Mat projectMat(const cv::Point3f& p3D);
+  float uncertainty2(const Eigen::Matrix<double, 2, 1>& p2D);
+  cv::Point3f unproject(const cv::Point2f& p2D);
+  cv::Mat unprojectMat(const cv::Point2f& p2D);
+  cv::Mat projectJac(const cv::Point3f& p3D);
+  Eigen::Matrix<double, 2, 3> projectJac(const Eigen::Vector3d& v3D);
+  cv::Mat unprojectJac(const cv::Point2f& p2D);
+  bool ReconstructWithTwoViews(const std::vector<cv::KeyPoint>& vKeys1, const std::vector<cv::KeyPoint>& vKeys2,
+                               const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21, std::vector<cv::Point3f>& vP3D,
+                               std::vector<bool>& vbTriangulated);
+  cv::Mat toK();
+  bool epipolarConstrain(GeometricCamera* pCamera2, const cv::KeyPoint& kp1, const cv::KeyPoint& kp2, const cv::Mat& R12,
+                         const cv::Mat& t12, const float sigmaLevel, const float unc);
+  float TriangulateMatches(GeometricCamera* pCamera2, const cv::KeyPoint& kp1, const cv::KeyPoint& kp2, const cv::Mat& R12,
+                           const cv::Mat& t12, const float sigmaLevel, const float unc, cv::Mat& p3D);
+  std::vector<int> mvLappingArea;
+  bool matchAndtriangulate(const cv::KeyPoint& kp1, const cv::KeyPoint& kp2, GeometricCamera* pOther, cv::Mat& Tcw1, cv::Mat& Tcw2,
+                           const float sigmaLevel1, const float sigmaLevel2, cv::Mat& x3Dtriangulated);
+  friend std::ostream& operator<<(std::ostream& os, const KannalaBrandt8& kb);
+  friend std::istream& operator>>(std::istream& is, KannalaBrandt8& kb);
+
+ private:
+  const float precision;
+  TwoViewReconstruction* tvr;
+  void Triangulate(const cv::Point2f& p1, const cv::Point2f& p2, const cv::Mat& Tcw1, const cv::Mat& Tcw2, cv::Mat& x3D);
+};
+
 // What Frame and KeyFrame share here: the tables, the 64 x 48 grid (Frame::AssignFeaturesToGrid / PosInGrid, Frame.cc:845-855: the
 // cell is round() of the float product, features in index order) and the window walk of GetFeaturesInArea.
 class ShimTable {
@@ -362,8 +555,9 @@ class ShimTable {
   float mfGridElementWidthInv = 0, mfGridElementHeightInv = 0;
   GeometricCamera *mpCamera = nullptr, *mpCamera2 = nullptr;
   std::vector<int> mvLeftToRightMatch, mvRightToLeftMatch;
-  cv::Mat mTcw, mTrl, mRcw, mtcw, mOw;
-  std::vector<size_t> mGrid[GRID_COLS][GRID_ROWS];
+  cv::Mat mTcw, mTrl, mTlr, mRcw, mtcw, mOw;      // mTlr: 3 x 4, the right camera's pose in the left one (two-camera tables only)
+  std::vector<size_t> mGrid[GRID_COLS][GRID_ROWS], mGridRight[GRID_COLS][GRID_ROWS];
+  int nLeftRows = -1;                             // Nleft / NLeft of a two-camera table (mvKeys holds that many rows), -1 otherwise
 
   void AssignFeaturesToGrid() {
     mfGridElementWidthInv = static_cast<float>(GRID_COLS) / static_cast<float>(mnMaxX - mnMinX);
@@ -375,11 +569,28 @@ class ShimTable {
       mGrid[px][py].push_back((size_t)i);
     }
   }
+  // Frame::AssignFeaturesToGrid for a two-camera frame (Frame.cc:468-481): row i < Nleft is mvKeys[i] and goes to mGrid as i, the
+  // others are mvKeysRight[i - Nleft] and go to mGridRight under their camera-local index
+  void AssignFeaturesToGridTwoCameras(int nleft) {
+    nLeftRows = nleft;
+    mfGridElementWidthInv = static_cast<float>(GRID_COLS) / static_cast<float>(mnMaxX - mnMinX);
+    mfGridElementHeightInv = static_cast<float>(GRID_ROWS) / static_cast<float>(mnMaxY - mnMinY);
+    for (int i = 0; i < N; ++i) {
+      const cv::KeyPoint& kp = i < nleft ? mvKeys[(size_t)i] : mvKeysRight[(size_t)(i - nleft)];
+      const int px = (int)std::round((kp.pt.x - mnMinX) * mfGridElementWidthInv);
+      const int py = (int)std::round((kp.pt.y - mnMinY) * mfGridElementHeightInv);
+      if (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) continue;
+      if (i < nleft) mGrid[px][py].push_back((size_t)i);
+      else mGridRight[px][py].push_back((size_t)(i - nleft));
+    }
+  }
   bool IsInImage(const float& x, const float& y) const { return x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY; }
 
  protected:
   // levels: Frame's test (Frame.cc:809-831); KeyFrame's walk has none
-  std::vector<size_t> area(float x, float y, float r, bool levels, int minLevel, int maxLevel) const {
+  // bRight (KeyFrame.cc:909-914): the cell lists of mGridRight, the keypoints of mvKeysRight, camera-local indices
+  std::vector<size_t> area(float x, float y, float r, bool levels, int minLevel, int maxLevel, bool bRight = false) const {
+    const std::vector<cv::KeyPoint>& keys = bRight ? mvKeysRight : nLeftRows >= 0 ? mvKeys : mvKeysUn;
     std::vector<size_t> vIndices;
     const int c0 = std::max(0, (int)std::floor((x - mnMinX - r) * mfGridElementWidthInv));
     if (c0 >= GRID_COLS) return vIndices;
@@ -392,8 +603,8 @@ class ShimTable {
     const bool check = levels && (minLevel > 0 || maxLevel >= 0);
     for (int ix = c0; ix <= c1; ++ix)
       for (int iy = r0; iy <= r1; ++iy)
-        for (size_t j : mGrid[ix][iy]) {
-          const cv::KeyPoint& kp = mvKeysUn[j];
+        for (size_t j : (bRight ? mGridRight[ix][iy] : mGrid[ix][iy])) {
+          const cv::KeyPoint& kp = keys[j];
           if (check) {
             if (kp.octave < minLevel) continue;
             if (maxLevel >= 0 && kp.octave > maxLevel) continue;
@@ -409,27 +620,52 @@ class Frame : public ShimTable {
  public:
   int Nleft = -1;
   std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const int minLevel = -1, const int maxLevel = -1,
-                                        const bool bRight = false) const {
-    assert(!bRight);
-    return area(x, y, r, true, minLevel, maxLevel);
+                                        const bool bRight = false) const {      // Frame.cc:774-843
+    return area(x, y, r, true, minLevel, maxLevel, bRight);
   }
 };
 
 class KeyFrame : public ShimTable {
  public:
   int NLeft = -1;
-  std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const bool bRight = false) const {
-    assert(!bRight);
-    return area(x, y, r, false, -1, -1);
+  std::vector<size_t> GetFeaturesInArea(const float& x, const float& y, const float& r, const bool bRight = false) const {   // KeyFrame.cc:881-925
+    return area(x, y, r, false, -1, -1, bRight);
   }
   cv::Mat GetPose() { return mTcw.clone(); }
   cv::Mat GetRotation() { return mRcw.clone(); }
   cv::Mat GetTranslation() { return mtcw.clone(); }
   cv::Mat GetCameraCenter() { return mOw.clone(); }
-  cv::Mat GetRightPose() { return cv::Mat(); }
-  cv::Mat GetRightRotation() { return cv::Mat(); }
-  cv::Mat GetRightTranslation() { return cv::Mat(); }
-  cv::Mat GetRightCameraCenter() { return cv::Mat(); }
+  // KeyFrame.cc:1290-1373 restated over mRcw / mtcw / mOw (the reference reads the same blocks out of Tcw and Ow); empty without a
+  // second camera, as before
+  cv::Mat GetRightRotation() {                              // KeyFrame.cc:1354-1362
+    if (mTlr.empty()) return cv::Mat();
+    cv::Mat Rrl = mTlr.rowRange(0, 3).colRange(0, 3).t();
+    cv::Mat Rlw = mRcw.clone();
+    cv::Mat Rrw = Rrl * Rlw;
+    return Rrw.clone();
+  }
+  cv::Mat GetRightTranslation() {                           // KeyFrame.cc:1364-1373
+    if (mTlr.empty()) return cv::Mat();
+    cv::Mat Rrl = mTlr.rowRange(0, 3).colRange(0, 3).t();
+    cv::Mat tlw = mtcw.clone();
+    cv::Mat trl = -Rrl * mTlr.rowRange(0, 3).col(3);
+    cv::Mat trw = Rrl * tlw + trl;
+    return trw.clone();
+  }
+  cv::Mat GetRightPose() {                                  // KeyFrame.cc:1290-1303
+    if (mTlr.empty()) return cv::Mat();
+    cv::Mat Trw;
+    cv::hconcat(GetRightRotation(), GetRightTranslation(), Trw);
+    return Trw.clone();
+  }
+  cv::Mat GetRightCameraCenter() {                          // KeyFrame.cc:1343-1352
+    if (mTlr.empty()) return cv::Mat();
+    cv::Mat Rwl = mRcw.t();
+    cv::Mat tlr = mTlr.rowRange(0, 3).col(3);
+    cv::Mat twl = mOw.clone();
+    cv::Mat twr = Rwl * tlr + twl;
+    return twr.clone();
+  }
   std::vector<MapPoint*> GetMapPointMatches() { return mvpMapPoints; }
   std::set<MapPoint*> GetMapPoints();
   MapPoint* GetMapPoint(const size_t& idx);

@@ -1,9 +1,11 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.
-// Stand-alone driver over the reference's own src/ORBmatcher.cc, src/CameraModels/Pinhole.cpp and
+// Stand-alone driver over the reference's own src/ORBmatcher.cc, src/CameraModels/Pinhole.cpp, src/CameraModels/KannalaBrandt8.cpp and
 // Thirdparty/DBoW2/DBoW2/FeatureVector.cpp, which oracle/Makefile compiles from the reference tree (never copied) against
 // match_shim/ (pli_match_shim.hpp: what that stand-in states and what the pin therefore covers).
 //
 //   pli_ref_match CASE RESULT
+//   pli_ref_match --functions        prints the names "fn" may take, one per line (a caller asks this before it relies on a
+//                                    function that a program built from an earlier recipe does not have)
 //
 // CASE and RESULT are files of named arrays (tests/helpers_match_ref.py writes and reads them): "PLIM", int32 count, then per
 // array: int32 name length, the name, int32 type (0: uint8, 1: int32, 2: float32, 3: float64), int32 ndim, ndim x int64 extent,
@@ -19,7 +21,8 @@
 //   t<k>_*    table k, held both as a Frame and as a KeyFrame (again one array each): x, y, octave, angle, desc[n,32], uright (-1
 //             when absent), node (the FeatureVector node that lists the feature, -1: none), mp (index of its MapPoint, -1: NULL),
 //             outlier, cam (fx fy cx cy bf minX maxX minY maxY mb), sf / sigma2 / inv_sigma2 [levels], logsf, and either Tcw[4,4]
-//             or R[3,3], t[3], Ow[3]
+//             or R[3,3], t[3], Ow[3]; a two-camera table has nleft[1] (rows [0, nleft) are mvKeys, the rest mvKeysRight), kb1[8], kb2[8]
+//             (the KannalaBrandt8 parameters of mpCamera, mpCamera2) and Tlr[3,4] besides
 //   list, matched, found, points_kf, Scw, prev: the function's arguments (indices of MapPoints / tables, -1: NULL)
 // RESULT records what the caller of the reference function can see: "ret", and per function the containers named below, pointers
 // as indices.
@@ -133,8 +136,8 @@ struct World {
   std::vector<MapPoint> mps;
   std::vector<Frame> frames;
   std::vector<KeyFrame> kfs;
-  std::vector<Pinhole*> cams;
-  ~World() { for (Pinhole* c : cams) delete c; }
+  std::vector<GeometricCamera*> cams;
+  ~World() { for (GeometricCamera* c : cams) delete c; }
   MapPoint* mp(int i) { if (i >= (int)mps.size()) die("map point index out of range"); return i < 0 ? nullptr : &mps[(size_t)i]; }
   int index(MapPoint* p) const { return p ? p->index : -1; }
 };
@@ -190,6 +193,32 @@ void fillTable(const Case& c, const std::string& pre, ShimTable& T, World& W, in
     T.mtcw = matOf(c.f32(pre + "t", 3), 3, 1);
     T.mOw = matOf(c.f32(pre + "Ow", 3), 3, 1);
   }
+  if (c.has(pre + "nleft")) {
+    // a two-camera table: rows [0, nleft) are mvKeys, the rest mvKeysRight (camera-local indices); both cameras KannalaBrandt8
+    // (kb1, kb2: fx fy cx cy k0 k1 k2 k3); Tlr[3,4].  The two grids are filled when the table has image bounds.  mvuRight has
+    // Nleft entries, all -1, as Frame.cc:1589 leaves it for such a rig: Fuse reads mvuRight[idx] with the camera-local idx of
+    // EITHER camera (:1533), so a case with bRight must keep Nright <= Nleft (the reference reads past the vector otherwise).
+    const int nleft = c.i32(pre + "nleft", 1)[0];
+    if (nleft < 0 || nleft > (int)n) die("bad nleft");
+    T.mvKeysRight.assign(T.mvKeys.begin() + nleft, T.mvKeys.end());
+    T.mvKeys.resize((size_t)nleft);
+    const float *k1 = c.f32(pre + "kb1", 8), *k2 = c.f32(pre + "kb2", 8);
+    // pinhole[4] (fx fy cx cy): mpCamera is a Pinhole instead, for cases that need a projection which is exact in float
+    if (c.has(pre + "pinhole")) W.cams.push_back(new Pinhole(std::vector<float>(c.f32(pre + "pinhole", 4), c.f32(pre + "pinhole", 4) + 4)));
+    else W.cams.push_back(new KannalaBrandt8(std::vector<float>(k1, k1 + 8)));
+    T.mpCamera = W.cams.back();
+    W.cams.push_back(new KannalaBrandt8(std::vector<float>(k2, k2 + 8)));
+    T.mpCamera2 = W.cams.back();
+    T.mTlr = matOf(c.f32(pre + "Tlr", 12), 3, 4);
+    if (c.has(pre + "Trl")) T.mTrl = matOf(c.f32(pre + "Trl", 12), 3, 4);
+    T.mvuRight.assign((size_t)nleft, -1.f);
+    T.mvLeftToRightMatch.assign((size_t)nleft, -1);                  // l2r[nleft] / r2l[n - nleft]: Frame::ComputeStereoFishEyeMatches' tables
+    T.mvRightToLeftMatch.assign(n - (size_t)nleft, -1);
+    if (c.has(pre + "l2r")) T.mvLeftToRightMatch.assign(c.i32(pre + "l2r", (size_t)nleft), c.i32(pre + "l2r", (size_t)nleft) + nleft);
+    if (c.has(pre + "r2l")) T.mvRightToLeftMatch.assign(c.i32(pre + "r2l", n - (size_t)nleft), c.i32(pre + "r2l", n - (size_t)nleft) + (n - (size_t)nleft));
+    if (T.mnMaxX > T.mnMinX && T.mnMaxY > T.mnMinY) T.AssignFeaturesToGridTwoCameras(nleft);
+    return;
+  }
   Pinhole* cam1 = new Pinhole(std::vector<float>{T.fx, T.fy, T.cx, T.cy});
   W.cams.push_back(cam1);
   T.mpCamera = cam1;
@@ -224,12 +253,18 @@ void build(const Case& c, World& W) {
         P.mbTrackInView = t[0] != 0.f; P.mTrackProjX = t[1]; P.mTrackProjY = t[2]; P.mTrackProjXR = t[3]; P.mTrackDepth = t[4];
         P.mnTrackScaleLevel = (int)t[5]; P.mTrackViewCos = t[6];
       }
+      if (c.has("mp_track_r")) {     // [n,6]: mbTrackInViewR, mTrackProjXR, mTrackProjYR, mnTrackScaleLevelR, mTrackViewCosR, mTrackDepthR
+        const float* t = c.f32("mp_track_r", nmp * 6) + 6 * i;
+        P.mbTrackInViewR = t[0] != 0.f; P.mTrackProjXR = t[1]; P.mTrackProjYR = t[2]; P.mnTrackScaleLevelR = (int)t[3];
+        P.mTrackViewCosR = t[4]; P.mTrackDepthR = t[5];
+      }
     }
   }
   for (int k = 0; k < ntab; ++k) {
     const std::string pre = "t" + std::to_string(k) + "_";
     fillTable(c, pre, W.frames[(size_t)k], W, k);
     fillTable(c, pre, W.kfs[(size_t)k], W, k);
+    if (c.has(pre + "nleft")) W.frames[(size_t)k].Nleft = W.kfs[(size_t)k].NLeft = c.i32(pre + "nleft", 1)[0];
   }
   if (c.has("mp_in_kf")) {
     const unsigned char* in = c.u8("mp_in_kf", (size_t)ntab * nmp);
@@ -255,6 +290,12 @@ std::vector<int32_t> indices(const World& W, const std::vector<MapPoint*>& v) {
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 2 && std::string(argv[1]) == "--functions") {
+    for (const char* f : {"fuse", "fuse_sim3", "sim3", "sim3_kfs", "reloc", "bow", "bow_kf", "init", "tri", "frame", "local", "kb8", "tri2",
+                          "bow2", "fuse2", "local2", "frame2"})
+      std::printf("%s\n", f);
+    return 0;
+  }
   if (argc != 3) { std::fprintf(stderr, "usage: %s CASE RESULT\n", argv[0]); return 2; }
   Case c;
   c.bag = readBag(argv[1]);
@@ -271,7 +312,19 @@ int main(int argc, char** argv) {
   int ret = 0;
   auto table = [&](size_t k) { if (k >= W.kfs.size()) die("missing table"); return k; };
 
-  if (fn == "fuse") {                              // Fuse(pKF, vpMapPoints, th): params[2] = th
+  if (fn == "fuse2") {                             // Fuse(pKF, vpMapPoints, th, bRight): params[2] = th, params[3] = bRight
+    KeyFrame* pKF = &W.kfs[table(0)];
+    const bool bRight = param(3) != 0.0;
+    if (!pKF->mpCamera2) die("fuse2 needs a two-camera table");
+    if (bRight && pKF->mvKeysRight.size() > pKF->mvuRight.size()) die("fuse2 with bRight needs Nright <= Nleft (mvuRight has Nleft entries)");
+    cv::shim_detail::divisionFactorInFloat() = true;
+    const std::vector<MapPoint*> list = pointList(c, W, "list");
+    ShimLog::get().on = true;
+    ret = matcher.Fuse(pKF, list, (float)param(2), bRight);
+    ShimLog::get().on = false;
+    out["ops"] = ints(ShimLog::get().ops, {(int64_t)ShimLog::get().ops.size() / 3, 3});
+    out["kf_mp"] = ints(indices(W, pKF->mvpMapPoints));
+  } else if (fn == "fuse") {                       // Fuse(pKF, vpMapPoints, th): params[2] = th
     KeyFrame* pKF = &W.kfs[table(0)];
     const std::vector<MapPoint*> list = pointList(c, W, "list");
     ShimLog::get().on = true;
@@ -312,7 +365,8 @@ int main(int argc, char** argv) {
     const std::set<MapPoint*> sFound(found.begin(), found.end());
     ret = matcher.SearchByProjection(F, pKF, sFound, (float)param(2), (int)param(3));
     out["frame_mp"] = ints(indices(W, F.mvpMapPoints));
-  } else if (fn == "bow") {                        // SearchByBoW(pKF, F, vpMapPointMatches)
+  } else if (fn == "bow" || fn == "bow2") {        // SearchByBoW(pKF, F, vpMapPointMatches); bow2: F.Nleft != -1 (a two-camera table)
+    if (fn == "bow2" && (W.frames[table(1)].Nleft == -1 || !W.frames[table(1)].mpCamera2)) die("bow2 needs a two-camera frame");
     std::vector<MapPoint*> matches;
     ret = matcher.SearchByBoW(&W.kfs[table(0)], W.frames[table(1)], matches);
     out["matches"] = ints(indices(W, matches));
@@ -338,20 +392,92 @@ int main(int argc, char** argv) {
     out["rets"] = ints(rets);
     out["matches12"] = ints(all12, {(int64_t)rets.size(), (int64_t)n1});
     out["prev"] = floats(allPrev, {(int64_t)rets.size(), (int64_t)n1, 2});
-  } else if (fn == "tri") {                        // SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse)
+  } else if (fn == "tri" || fn == "tri2") {        // SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse);
+    // tri2: both tables carry nleft (mpCamera2 set on both keyframes)
+    if (fn == "tri2") {
+      if (!W.kfs[table(0)].mpCamera2 || !W.kfs[table(1)].mpCamera2) die("tri2 needs two-camera tables");
+      cv::shim_detail::divisionFactorInFloat() = true;
+    }
     std::vector<std::pair<size_t, size_t>> pairs;
     ret = matcher.SearchForTriangulation(&W.kfs[table(0)], &W.kfs[table(1)], cv::Mat(), pairs, param(2) != 0.0, param(3) != 0.0);
     std::vector<int32_t> flat;
     for (const auto& p : pairs) { flat.push_back((int32_t)p.first); flat.push_back((int32_t)p.second); }
     out["pairs"] = ints(flat, {(int64_t)pairs.size(), 2});
-  } else if (fn == "frame") {                      // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+    if (fn == "tri2") {
+      // not an output of the reference function: the right-pose getters of the stand-in (KeyFrame.cc:1354-1373 restated there) and
+      // the four relative poses of ORBmatcher.cc:995-1003 formed HERE over the stand-in's cv::Mat, ll lr rl rr, R12 then t12, so
+      // that the host arithmetic of the restatements and of the adapter can be held to the same bits
+      KeyFrame *k1 = &W.kfs[table(0)], *k2 = &W.kfs[table(1)];
+      std::vector<float> rel, right;
+      for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+          const cv::Mat Ra = a ? k1->GetRightRotation() : k1->GetRotation(), ta = a ? k1->GetRightTranslation() : k1->GetTranslation();
+          const cv::Mat Rb = b ? k2->GetRightRotation() : k2->GetRotation(), tb = b ? k2->GetRightTranslation() : k2->GetTranslation();
+          const cv::Mat R12 = Ra * Rb.t(), t12 = Ra * (-Rb.t() * tb) + ta;
+          for (int i = 0; i < 9; ++i) rel.push_back(R12.at<float>(i / 3, i % 3));
+          for (int i = 0; i < 3; ++i) rel.push_back(t12.at<float>(i));
+        }
+      for (KeyFrame* k : {k1, k2}) {
+        const cv::Mat R = k->GetRightRotation(), t = k->GetRightTranslation(), O = k->GetRightCameraCenter();
+        for (int i = 0; i < 9; ++i) right.push_back(R.at<float>(i / 3, i % 3));
+        for (int i = 0; i < 3; ++i) right.push_back(t.at<float>(i));
+        for (int i = 0; i < 3; ++i) right.push_back(O.at<float>(i));
+      }
+      out["rel"] = floats(rel, {4, 12});
+      out["right_poses"] = floats(right, {2, 15});
+    }
+  } else if (fn == "frame" || fn == "frame2") {    // SearchByProjection(CurrentFrame, LastFrame, th, bMono); frame2: CurrentFrame.Nleft != -1
     Frame& F = W.frames[table(0)];
+    if (fn == "frame2" && (F.Nleft == -1 || F.mTrl.empty())) die("frame2 needs a two-camera current frame with Trl");
     ret = matcher.SearchByProjection(F, W.frames[table(1)], (float)param(2), param(3) != 0.0);
     out["frame_mp"] = ints(indices(W, F.mvpMapPoints));
-  } else if (fn == "local") {                      // SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints)
+  } else if (fn == "local" || fn == "local2") {    // SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints); local2: F.Nleft != -1
     Frame& F = W.frames[table(0)];
+    if (fn == "local2" && (F.Nleft == -1 || !c.has("mp_track_r"))) die("local2 needs a two-camera frame and mp_track_r");
     ret = matcher.SearchByProjection(F, pointList(c, W, "list"), (float)param(2), param(3) != 0.0, (float)param(4));
     out["frame_mp"] = ints(indices(W, F.mvpMapPoints));
+  } else if (fn == "kb8") {                        // no matcher: the compiled KannalaBrandt8 members on tables of points, pixels and pairs
+    // cam1[8], cam2[8]: fx fy cx cy k0 k1 k2 k3; points[n,3], pixels[m,2]: project / unproject of BOTH cameras; kp1[k,2] (camera 1),
+    // kp2[k,2] (camera 2), R12[9], t12[3], sigma[k], unc[k]: cam1.TriangulateMatches(&cam2, ...) -> tri_ret[k], tri_p3d[k,3]
+    // (zeros where p3D stayed empty), and the two rays it starts from: tri_r1[k,3] = cam1.unproject(kp1), tri_r2[k,3] = cam2.unproject(kp2)
+    cv::shim_detail::divisionFactorInFloat() = true;
+    const float *c1 = c.f32("cam1", 8), *c2 = c.f32("cam2", 8);
+    KannalaBrandt8 cam1(std::vector<float>(c1, c1 + 8)), cam2(std::vector<float>(c2, c2 + 8));
+    KannalaBrandt8* cams[2] = {&cam1, &cam2};
+    const size_t n = c.len("points"), m = c.len("pixels"), k = c.len("kp1");
+    const float *pts = c.f32("points", n * 3), *pix = c.f32("pixels", m * 2);
+    for (int e = 0; e < 2; ++e) {
+      std::vector<float> proj(n * 2), unproj(m * 3);
+      for (size_t i = 0; i < n; ++i) {
+        const cv::Point2f uv = cams[e]->project(cv::Point3f(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
+        proj[2 * i] = uv.x; proj[2 * i + 1] = uv.y;
+      }
+      for (size_t i = 0; i < m; ++i) {
+        const cv::Point3f r = cams[e]->unproject(cv::Point2f(pix[2 * i], pix[2 * i + 1]));
+        unproj[3 * i] = r.x; unproj[3 * i + 1] = r.y; unproj[3 * i + 2] = r.z;
+      }
+      out[e ? "proj2" : "proj1"] = floats(proj, {(int64_t)n, 2});
+      out[e ? "unproj2" : "unproj1"] = floats(unproj, {(int64_t)m, 3});
+    }
+    const float *kp1 = c.f32("kp1", k * 2), *kp2 = c.f32("kp2", k * 2), *sigma = c.f32("sigma", k), *unc = c.f32("unc", k);
+    const cv::Mat R12 = matOf(c.f32("R12", 9), 3, 3), t12 = matOf(c.f32("t12", 3), 3, 1);
+    std::vector<float> triRet(k), triP(k * 3, 0.f), triR1(k * 3), triR2(k * 3);
+    for (size_t i = 0; i < k; ++i) {
+      cv::KeyPoint a, b;
+      a.pt = cv::Point2f(kp1[2 * i], kp1[2 * i + 1]);
+      b.pt = cv::Point2f(kp2[2 * i], kp2[2 * i + 1]);
+      const cv::Point3f r1 = cam1.unproject(a.pt), r2 = cam2.unproject(b.pt);
+      triR1[3 * i] = r1.x; triR1[3 * i + 1] = r1.y; triR1[3 * i + 2] = r1.z;
+      triR2[3 * i] = r2.x; triR2[3 * i + 1] = r2.y; triR2[3 * i + 2] = r2.z;
+      cv::Mat p3D;
+      triRet[i] = cam1.TriangulateMatches(&cam2, a, b, R12, t12, sigma[i], unc[i], p3D);
+      if (!p3D.empty())
+        for (int j = 0; j < 3; ++j) triP[3 * i + (size_t)j] = p3D.at<float>(j);
+    }
+    out["tri_ret"] = floats(triRet, {(int64_t)k});
+    out["tri_p3d"] = floats(triP, {(int64_t)k, 3});
+    out["tri_r1"] = floats(triR1, {(int64_t)k, 3});
+    out["tri_r2"] = floats(triR2, {(int64_t)k, 3});
   } else {
     die("unknown function " + fn);
   }

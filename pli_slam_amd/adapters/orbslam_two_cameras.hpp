@@ -14,6 +14,43 @@
 
 namespace ORB_SLAM3 {
 
+namespace pli_detail {
+
+// The four relative poses of ORBmatcher.cc:995-1003 for (pKF1, pKF2), the reference's own cv::Mat expressions: rel[4 x 12] = ll, lr,
+// rl, rr, each R12 row major and then t12.  Host arithmetic only (tests compile it without a device).
+template <class KeyFrameT>
+inline void relativePosesTwoCameras(KeyFrameT* pKF1, KeyFrameT* pKF2, float* rel) {
+  const cv::Mat R[4] = {pKF1->GetRotation() * pKF2->GetRotation().t(), pKF1->GetRotation() * pKF2->GetRightRotation().t(),        // :995-998
+                        pKF1->GetRightRotation() * pKF2->GetRotation().t(), pKF1->GetRightRotation() * pKF2->GetRightRotation().t()};
+  const cv::Mat t[4] = {                                                                                                           // :1000-1003
+      pKF1->GetRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetTranslation(),
+      pKF1->GetRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetTranslation(),
+      pKF1->GetRightRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetRightTranslation(),
+      pKF1->GetRightRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetRightTranslation()};
+  for (int p = 0; p < 4; ++p) {
+    float* out = rel + p * 12;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) out[i * 3 + j] = R[p].template at<float>(i, j);
+      out[9 + i] = t[p].template at<float>(i);
+    }
+  }
+}
+
+// The two poses Fuse(pKF, vpMapPoints, th, bRight) reads (:1404-1417): pose[2 x 15] = left, right, each Rcw row major, tcw, Ow.
+template <class KeyFrameT>
+inline void fusePosesTwoCameras(KeyFrameT* pKF, float* pose) {
+  const cv::Mat R[2] = {pKF->GetRotation(), pKF->GetRightRotation()}, t[2] = {pKF->GetTranslation(), pKF->GetRightTranslation()},
+                Ow[2] = {pKF->GetCameraCenter(), pKF->GetRightCameraCenter()};
+  for (int e = 0; e < 2; ++e)
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) pose[e * 15 + i * 3 + j] = R[e].template at<float>(i, j);
+      pose[e * 15 + 9 + i] = t[e].template at<float>(i);
+      pose[e * 15 + 12 + i] = Ow[e].template at<float>(i);
+    }
+}
+
+}  // namespace pli_detail
+
 // FrameT needs, beyond what PliORBmatcher reads: Nleft, Nright, mvKeys, mvKeysRight, mDescriptors (Nleft + Nright rows, the left
 // camera's first), mvpMapPoints (Nleft + Nright slots), mTrl (3 x 4, CV_32F), mpCamera (with project(cv::Mat) -> cv::Point2f),
 // mvLeftToRightMatch and mvRightToLeftMatch.  MapPointT needs mbTrackInViewR, mTrackProjXR / YR, mTrackViewCosR and
@@ -221,20 +258,7 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
     for (int k = 0; k < nkf; ++k) {
       KeyFrameT* pKF2 = vpKF2[k];
       gather(pKF2, T2, "SearchForTriangulation: pKF2->mFeatVec");
-      const cv::Mat R[4] = {pKF1->GetRotation() * pKF2->GetRotation().t(), pKF1->GetRotation() * pKF2->GetRightRotation().t(),        // :995-998
-                            pKF1->GetRightRotation() * pKF2->GetRotation().t(), pKF1->GetRightRotation() * pKF2->GetRightRotation().t()};
-      const cv::Mat t[4] = {                                                                                                           // :1000-1003
-          pKF1->GetRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetTranslation(),
-          pKF1->GetRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetTranslation(),
-          pKF1->GetRightRotation() * (-pKF2->GetRotation().t() * pKF2->GetTranslation()) + pKF1->GetRightTranslation(),
-          pKF1->GetRightRotation() * (-pKF2->GetRightRotation().t() * pKF2->GetRightTranslation()) + pKF1->GetRightTranslation()};
-      for (int p = 0; p < 4; ++p) {
-        float* out = &rel[((size_t)k * 4 + p) * 12];
-        for (int i = 0; i < 3; ++i) {
-          for (int j = 0; j < 3; ++j) out[i * 3 + j] = R[p].template at<float>(i, j);
-          out[9 + i] = t[p].template at<float>(i);
-        }
-      }
+      pli_detail::relativePosesTwoCameras(pKF1, pKF2, &rel[(size_t)k * 48]);                       // :995-1003
     }
     std::vector<int> matches;
     pli_detail::deviceContext("SearchForTriangulation")
@@ -396,17 +420,9 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
       pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
       for (int i = 0; i < n; ++i) T.kp.push_back(pli_detail::keypoint(i < nl ? pKF->mvKeys[i] : pKF->mvKeysRight[i - nl]));   // :1524-1526
       T.nleft.push_back(nl);
-      const cv::Mat R[2] = {pKF->GetRotation(), pKF->GetRightRotation()}, t[2] = {pKF->GetTranslation(), pKF->GetRightTranslation()},
-                    Ow[2] = {pKF->GetCameraCenter(), pKF->GetRightCameraCenter()};                                               // :1404-1417
-      for (int e = 0; e < 2; ++e) {
-        float pose[15];
-        for (int i = 0; i < 3; ++i) {
-          for (int j = 0; j < 3; ++j) pose[i * 3 + j] = R[e].template at<float>(i, j);
-          pose[9 + i] = t[e].template at<float>(i);
-          pose[12 + i] = Ow[e].template at<float>(i);
-        }
-        T.pose.insert(T.pose.end(), pose, pose + 15);
-      }
+      float pose[30];
+      pli_detail::fusePosesTwoCameras(pKF, pose);                                                   // :1404-1417
+      T.pose.insert(T.pose.end(), pose, pose + 30);
     }
     std::vector<pli_fuse_point> pts(nmp);
     std::vector<uint8_t> desc((size_t)nmp * 32, 0), skip((size_t)nkf * 2 * nmp, 0);
