@@ -954,6 +954,33 @@ pli_status pli_kfdb_stats(const pli_kfdb* db, struct pli_kfdb_stats* out);
 pli_status pli_kfdb_query(pli_ctx* ctx, pli_kfdb* db, const uint32_t* qword, const double* qvalue, int32_t nq, int32_t nslots,
                           int32_t* common, int32_t* first, double* score);
 
+/* --- MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:300-365) and MapLine::ComputeDistinctiveDescriptors
+ * (MapLine.cc:246-317) for a batch of features ---
+ * The reference runs it one feature at a time on the local-mapping thread (LocalMapping.cc:267-286 and :780-793,
+ * LoopClosing.cc:1012, MapPoint.cc:268, MapLine.cc:216).  A GROUP is the N descriptors (32 bytes each) that observe one feature, in
+ * the order in which the reference pushed them into vDescriptors (MapPoint.cc:319-325): group p owns rows off[p] .. off[p + 1] - 1
+ * of desc; off holds nfeat + 1 entries, off[0] == 0, non-decreasing.
+ *   D[i][j]   = the Hamming distance of rows i and j, D[i][i] = 0 (:333-343; the line form computes every pair twice,
+ *               MapLine.cc:284-293, which gives the same matrix);
+ *   median_i  = the element at index int(0.5 * (N - 1)), that is (N - 1) / 2 rounded down, of row i sorted ascending (:350-352);
+ *               the diagonal's zero is part of the row;
+ *   BestIdx   = the LOWEST i with the least median_i (:354 tests `median < BestMedian` strictly), BestMedian that value.
+ * So for N = 1 and N = 2 every median is 0 and BestIdx = 0; the largest possible median is 256 (a descriptor and its complement).
+ *   best[p]        = BestIdx within group p, -1 for an empty group (the reference returns before it touches mDescriptor, :314-315
+ *                    and :327-328);
+ *   best_median[p] = BestMedian, INT32_MAX for an empty group; may be NULL;
+ *   row_median     = off[nfeat] entries, median_i of every row (so that a test can hold every row to the reference, not only the
+ *                    winner); may be NULL.
+ * The answer is exact (integers): bit for bit the reference's.  A feature's answer depends on its own group alone, so batching
+ * changes nothing.  PLI_ERR_INVALID: off[0] != 0, a decreasing off, null off or best, a NULL desc with rows present.
+ * PLI_ERR_CAPACITY: a group of more than PLI_DISTINCTIVE_MAX_OBS rows; nothing is truncated and no output is written.  (The cap is
+ * far beyond what the reference can run: its `float Distances[N][N]` is a stack array that passes 8 MiB near N = 1450.)
+ * nfeat == 0 and off[nfeat] == 0 are valid.  Host pointers of any alignment are accepted.  One upload of the descriptors, one of
+ * off, one download; N <= 64: one launch, a wave per group; above: a workgroup per 256 rows of a group, then a launch that picks the winners. */
+#define PLI_DISTINCTIVE_MAX_OBS 2048
+pli_status pli_distinctive_descriptors(pli_ctx* ctx, const uint8_t* desc, const int32_t* off, int32_t nfeat, int32_t* best,
+                                       int32_t* best_median, int32_t* row_median);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

@@ -160,6 +160,20 @@ class Frontend {
     check(pli_search_by_bow_kf(ctx_, desc1, angle1, node1, valid1, n1, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, nnratio,
                                checkOrientation ? 1 : 0, matches12.data(), nmatches.data()));
   }
+  // MapPoint::ComputeDistinctiveDescriptors MapPoint.cc:300-365 / MapLine::ComputeDistinctiveDescriptors MapLine.cc:246-317 of
+  // off.size() - 1 features in one call (include/pli_frontend.h pli_distinctive_descriptors): feature p owns rows off[p] ..
+  // off[p + 1] of desc (32 bytes a row, in the order of the reference's vDescriptors); best[p] = BestIdx within the group (-1 for an
+  // empty group), bestMedian[p] = BestMedian; rowMedian (null: not wanted) = the median of every row
+  void distinctiveDescriptors(const std::vector<uint8_t>& desc, const std::vector<int32_t>& off, std::vector<int>& best,
+                              std::vector<int>& bestMedian, std::vector<int>* rowMedian = nullptr) {
+    if (off.empty() || desc.size() != (size_t)off.back() * 32) throw std::logic_error("distinctiveDescriptors: off and desc disagree");
+    const int nfeat = (int)off.size() - 1;
+    best.assign(nfeat, -1);
+    bestMedian.assign(nfeat, INT32_MAX);
+    if (rowMedian) rowMedian->assign(off.back(), 0);
+    check(pli_distinctive_descriptors(ctx_, desc.data(), off.data(), nfeat, best.data(), bestMedian.data(),
+                                      rowMedian ? rowMedian->data() : nullptr));
+  }
   // ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) ORBmatcher.cc:965-1206 (no second
   // cameras) of one keyframe against nkf neighbours (include/pli_frontend.h pli_search_for_triangulation): matches12 (nkf x n1) =
   // the neighbour's feature each feature of pKF1 is matched to or -1, nmatches[k] = the reference's return value for neighbour k

@@ -97,6 +97,7 @@ class KfdbStats(C.Structure):
 
 BOW_MAX_FEATURES = 8192              # PLI_BOW_MAX_FEATURES
 KFDB_QUERY_MAX_WAVES = 2048          # PLI_KFDB_QUERY_MAX_WAVES
+DISTINCTIVE_MAX_OBS = 2048           # PLI_DISTINCTIVE_MAX_OBS
 
 
 class PliError(RuntimeError):
@@ -187,6 +188,7 @@ _PROTOS = {
     "pli_kfdb_stats": (C.c_int32, [C.c_void_p, C.POINTER(KfdbStats)]),
     "pli_kfdb_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "pli_distinctive_descriptors": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pli_search_by_bow": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                       C.c_void_p]),

@@ -3381,6 +3381,79 @@ pli_status pli_kfdb_query(pli_ctx* c, pli_kfdb* db, const uint32_t* qword, const
   return PLI_OK;
 }
 
+// ---- MapPoint / MapLine::ComputeDistinctiveDescriptors for a batch of features (MapPoint.cc:300-365, MapLine.cc:246-317;
+// mapfeat_kernels.hip) ----
+// The host sorts the groups into the two size classes from `off` and cuts the large ones into chunks of rows; the callers' tables are
+// read and written with memcpy (any alignment).  One upload of the offsets, the class lists and the chunks, one of the descriptors,
+// one launch for the small class and two for the large one (where a class has groups), one download of best | best_median |
+// row_median.
+pli_status pli_distinctive_descriptors(pli_ctx* c, const uint8_t* desc, const int32_t* off, int32_t nfeat, int32_t* best,
+                                       int32_t* bestMedian, int32_t* rowMedian) {
+  CtxGuard guard__(c);
+  if (!c || nfeat < 0 || !off || (nfeat > 0 && !best)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  // meta: off (nfeat + 1), then nfeat entries with the small class's group ids from the front and the large class's from the back,
+  // then the large class's chunks
+  std::vector<int32_t> meta((size_t)nfeat * 2 + 1);
+  std::memcpy(meta.data(), off, ((size_t)nfeat + 1) * sizeof(int32_t));
+  if (meta[0] != 0) { g_err = "off[0] must be 0"; return PLI_ERR_INVALID; }
+  int nSmall = 0, nLarge = 0, maxN = 0;
+  for (int p = 0; p < nfeat; ++p) {
+    if (meta[p + 1] < meta[p]) { g_err = "off must not decrease"; return PLI_ERR_INVALID; }
+    const int n = meta[p + 1] - meta[p];
+    if (n > PLI_DISTINCTIVE_MAX_OBS) { g_err = "a feature has more observations than the cap of distinctive descriptors"; return PLI_ERR_CAPACITY; }
+    maxN = std::max(maxN, n);
+    int32_t* list = meta.data() + nfeat + 1;
+    if (n > DISTINCTIVE_WAVE_ROWS) list[nfeat - 1 - nLarge++] = p;
+    else if (n > 0) list[nSmall++] = p;
+  }
+  const int64_t total = meta[nfeat];
+  if (total > 0 && !desc) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nfeat == 0) return PLI_OK;
+  const size_t chunkAt = meta.size();
+  for (int g = 0; g < nLarge; ++g) {
+    const int p = meta[(size_t)nfeat + 1 + (nfeat - nLarge) + g], n = meta[p + 1] - meta[p];
+    for (int first = 0; first < n; first += DISTINCTIVE_BLOCK) { meta.push_back(p); meta.push_back(first); }
+  }
+  const int nChunks = (int)((meta.size() - chunkAt) / 2);
+  std::vector<int32_t> out((size_t)nfeat * 2 + (rowMedian ? total : 0));
+  if (total > 0) {
+    HIPCHK(hipSetDevice(c->device));
+    ScratchPlan plan;
+    auto dDesc = plan.add<uint8_t>((size_t)total * 32);
+    auto dMeta = plan.add<int32_t>(meta.size());
+    auto dOut = plan.add<int32_t>((size_t)nfeat * 2 + total);      // (the kernels always write row_median: the large class picks from it)
+    pli_status st = commitScratch(c, plan);
+    if (st != PLI_OK) return st;
+    HIPCHK(upload(c, dDesc, desc, (size_t)total * 32));
+    HIPCHK(upload(c, dMeta, (const int32_t*)meta.data(), meta.size()));
+    int32_t *dm = dMeta, *dout = dOut;
+    const int* dOff = dm;
+    const int* dList = dm + nfeat + 1;
+    int* dBest = dout;
+    int* dMed = dout + nfeat;
+    int* dRow = dout + (size_t)nfeat * 2;
+    const int perBlock = DISTINCTIVE_BLOCK / 64;
+    if (nSmall)
+      LAUNCH(c, "k_distinctive_wave", k_distinctive_wave, dim3(std::min((nSmall + perBlock - 1) / perBlock, DISTINCTIVE_MAX_BLOCKS)),
+             dim3(DISTINCTIVE_BLOCK), 0, (const uint8_t*)dDesc, dOff, dList, nSmall, dBest, dMed, dRow);
+    if (nLarge) {      // (LDS: the longest group's descriptors, 64 KiB at the cap)
+      static_assert(sizeof(DistinctiveChunk) == 2 * sizeof(int32_t), "a chunk is two ints of meta");
+      LAUNCH(c, "k_distinctive_block", k_distinctive_block, dim3(std::min(nChunks, DISTINCTIVE_MAX_BLOCKS)), dim3(DISTINCTIVE_BLOCK),
+             (size_t)maxN * 32, (const uint8_t*)dDesc, dOff, reinterpret_cast<const DistinctiveChunk*>(dm + chunkAt), nChunks, dRow);
+      LAUNCH(c, "k_distinctive_pick", k_distinctive_pick, dim3(std::min((nLarge + perBlock - 1) / perBlock, DISTINCTIVE_MAX_BLOCKS)),
+             dim3(DISTINCTIVE_BLOCK), 0, dOff, dList + (nfeat - nLarge), nLarge, (const int*)dRow, dBest, dMed);
+    }
+    HIPCHK(download(c, out.data(), dOut, out.size()));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  for (int p = 0; p < nfeat; ++p)
+    if (meta[p + 1] == meta[p]) { out[p] = -1; out[(size_t)nfeat + p] = INT32_MAX; }     // an empty group has no answer (:314-315, :327-328)
+  std::memcpy(best, out.data(), (size_t)nfeat * sizeof(int32_t));
+  if (bestMedian) std::memcpy(bestMedian, out.data() + nfeat, (size_t)nfeat * sizeof(int32_t));
+  if (rowMedian && total > 0) std::memcpy(rowMedian, out.data() + (size_t)nfeat * 2, (size_t)total * sizeof(int32_t));
+  return PLI_OK;
+}
+
 // ---- the searches of one item against a batch of keyframes (shared host part: KfBatch and the checks above) ----
 // pli_search_by_bow (fNleft < 0: F.Nleft == -1) and pli_search_by_bow_two_cameras (the frame's first fNleft rows are the left camera's)
 static pli_status searchByBow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,

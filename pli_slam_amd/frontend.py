@@ -282,6 +282,18 @@ class Frontend:
         check(self.L.pli_kfdb_query(self.h, db, ptr(w), ptr(v), len(w), nslots, ptr(common), ptr(first), ptr(score)))
         return common, first, score
 
+    def distinctive_descriptors(self, groups):
+        """MapPoint / MapLine::ComputeDistinctiveDescriptors (MapPoint.cc:300-365, MapLine.cc:246-317) of every feature of `groups`
+        in one call.  groups: a list of (N_p, 32) uint8 arrays, the descriptors that observe feature p in the reference's order.
+        Returns (best int32[nfeat], best_median int32[nfeat], row_median int32[total rows]): best[p] is the lowest row of group p
+        with the least lower-median distance to the group's rows (-1 for an empty group), best_median[p] that median (INT32_MAX
+        for an empty group), row_median the median of every row, the groups one after another."""
+        off, (desc,) = pack_keyframes([(g,) for g in groups], ((0, np.uint8, (32,)),), "a group is (N, 32) uint8")
+        nfeat = len(groups)
+        best = np.zeros(nfeat, np.int32); best_median = np.zeros(nfeat, np.int32); row_median = np.zeros(int(off[-1]), np.int32)
+        check(self.L.pli_distinctive_descriptors(self.h, ptr(desc), ptr(off), nfeat, ptr(best), ptr(best_median), ptr(row_median)))
+        return best, best_median, row_median
+
     def search_by_bow(self, f_desc, f_angle, f_node, kfs, nnratio=0.75, check_orientation=True):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:269-470, F.Nleft == -1) of every keyframe of `kfs`
         against one frame, in one call.  kfs: list of (desc, angle, node, valid) per keyframe; node = the FeatureVector node that
