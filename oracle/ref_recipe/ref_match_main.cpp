@@ -24,6 +24,8 @@
 //             or R[3,3], t[3], Ow[3]; a two-camera table has nleft[1] (rows [0, nleft) are mvKeys, the rest mvKeysRight), kb1[8], kb2[8]
 //             (the KannalaBrandt8 parameters of mpCamera, mpCamera2) and Tlr[3,4] besides
 //   list, matched, found, points_kf, Scw, prev: the function's arguments (indices of MapPoints / tables, -1: NULL)
+// One function runs no reference code: "area" (kp, nleft, bounds, q -> idx, start; see areaOfStandIn below) answers with the stand-in's
+// own grid assignment and GetFeaturesInArea, so that they can be held to what the reference's Frame.cc returned (pli_ref_stereo).
 // RESULT records what the caller of the reference function can see: "ret", and per function the containers named below, pointers
 // as indices.
 #include "ORBmatcher.h"
@@ -287,12 +289,50 @@ std::vector<int32_t> indices(const World& W, const std::vector<MapPoint*>& v) {
   return out;
 }
 
+// "area": no reference code at all -- the STAND-IN's own Frame::AssignFeaturesToGrid / GetFeaturesInArea (match_shim), on the case
+// format of pli_ref_stereo's function of that name (kp [n,3]: x, y, octave; nleft [1]; bounds [4]; q [m,6]: x, y, r, minLevel,
+// maxLevel, bRight -> idx, start).  tests/test_ref_pin_stereo.py holds its answers to what the reference's own Frame.cc returned.
+void areaOfStandIn(const Case& c, Bag& out) {
+  const Arr& ka = c.arr("kp", 2);
+  if (ka.shape.size() != 2 || ka.shape[1] != 3) die("area: kp must be [n,3]");
+  const size_t n = (size_t)ka.shape[0];
+  const float* k = c.f32("kp", n * 3);
+  const int nleft = c.i32("nleft", 1)[0];
+  const float* b = c.f32("bounds", 4);
+  Frame F;
+  F.N = (int)n;
+  std::vector<cv::KeyPoint> kp(n);
+  for (size_t i = 0; i < n; ++i) { kp[i].pt.x = k[3 * i]; kp[i].pt.y = k[3 * i + 1]; kp[i].octave = (int)k[3 * i + 2]; }
+  F.mnMinX = b[0]; F.mnMaxX = b[1]; F.mnMinY = b[2]; F.mnMaxY = b[3];
+  if (nleft == -1) {
+    F.mvKeysUn = kp; F.mvKeys = kp;
+    F.AssignFeaturesToGrid();
+  } else {
+    if (nleft < 0 || (size_t)nleft > n) die("area: nleft outside the table");
+    F.Nleft = nleft;
+    F.mvKeys.assign(kp.begin(), kp.begin() + nleft);
+    F.mvKeysRight.assign(kp.begin() + nleft, kp.end());
+    F.AssignFeaturesToGridTwoCameras(nleft);
+  }
+  const Arr& qa = c.arr("q", 2);
+  if (qa.shape.size() != 2 || qa.shape[1] != 6) die("area: q must be [m,6]");
+  const size_t m = (size_t)qa.shape[0];
+  const float* q = c.f32("q", m * 6);
+  std::vector<int32_t> idx, start(1, 0);
+  for (size_t i = 0; i < m; ++i) {
+    const float* r = q + 6 * i;
+    for (size_t j : F.GetFeaturesInArea(r[0], r[1], r[2], (int)r[3], (int)r[4], r[5] != 0.f)) idx.push_back((int32_t)j);
+    start.push_back((int32_t)idx.size());
+  }
+  out["idx"] = ints(idx); out["start"] = ints(start);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 2 && std::string(argv[1]) == "--functions") {
     for (const char* f : {"fuse", "fuse_sim3", "sim3", "sim3_kfs", "reloc", "bow", "bow_kf", "init", "tri", "frame", "local", "kb8", "tri2",
-                          "bow2", "fuse2", "local2", "frame2"})
+                          "bow2", "fuse2", "local2", "frame2", "area"})
       std::printf("%s\n", f);
     return 0;
   }
@@ -301,6 +341,12 @@ int main(int argc, char** argv) {
   c.bag = readBag(argv[1]);
   const Arr& fnArr = c.arr("fn", 0);
   const std::string fn(fnArr.data.begin(), fnArr.data.end());
+  if (fn == "area") {
+    Bag res;
+    areaOfStandIn(c, res);
+    writeBag(argv[2], res);
+    return 0;
+  }
   const Arr& pa = c.arr("params", 3);
   const double* params = reinterpret_cast<const double*>(pa.data.data());
   const size_t np = pa.count();

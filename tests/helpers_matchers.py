@@ -53,6 +53,11 @@ class Rules:
     octave_gate_narrow: bool = False      # only the left keypoint's own octave instead of levelL - 1 .. levelL + 1
     maxd_inclusive: bool = False          # `disparity <= maxD` instead of `<`
     nan_minmax: str = "std"               # "std": std::min / std::max ((b < a) ? b : a); "fmin": IEEE fmin / fmax
+    length_eln_sln: bool = False          # lineSegmentOverlapStereo: `length = eln - sln` instead of `eln - spn`
+    epr_from_old_spr: bool = False        # ep_r interpolated from sp_r as it was before Frame.cc:1228 overwrote it
+    hamming_to_vdistidx: bool = False     # the Hamming bestDist, not the SAD that shadows it, goes to vDistIdx
+    sort_ties_insertion: bool = False     # vDistIdx sorted by distance alone, equal distances in insertion order
+    overlap_zero_horizontal: bool = False # lineSegmentOverlapStereo gives 0, not 1, for a horizontal left line
 
 
 REF = Rules()
@@ -93,6 +98,7 @@ def stereo_points(kpL, descL, kpR, descR, pyrL, pyrR, sf, inv_sf, bf, maxD, rule
     N, Nr = len(kpL), len(kpR)
     uright = np.full(N, -1, f32); depth = np.full(N, -1, f32)
     best_idx = np.full(N, -1, np.int32); sad_out = np.full(N, -1, np.int32)
+    ham_out = np.full(N, -1, np.int32)
     exits = [()] * N
     bf, maxD, minD = f32(bf), f32(maxD), f32(0)
     nlev = len(sf)
@@ -215,6 +221,7 @@ def stereo_points(kpL, descL, kpR, descR, pyrL, pyrR, sf, inv_sf, bf, maxD, rule
             depth[iL] = f32(bf / disparity)
             uright[iL] = bestuR
             sad_out[iL] = bestS
+            ham_out[iL] = bestDist
             exits[iL] = ("matched",) + tuple(tags)
     # the median cut (Frame.cc:1140-1153) as a predicate: sorted by (SAD, index), the tail from the first SAD that is not
     # below thDist is removed -- that is every survivor whose SAD is not below thDist.
@@ -223,7 +230,10 @@ def stereo_points(kpL, descL, kpR, descR, pyrL, pyrR, sf, inv_sf, bf, maxD, rule
     M = ok.size
     ftags.add("survivors_none" if M == 0 else "survivors_one" if M == 1 else "survivors_even" if M % 2 == 0 else "survivors_odd")
     if M:      # (M == 0: vDistIdx[0] of an empty vector in the reference; project definition: nothing to cut)
-        order = sorted((int(sad_out[i]), int(i)) for i in ok)
+        key = ham_out if rules.hamming_to_vdistidx else sad_out
+        order = sorted((int(key[i]), int(i)) for i in ok)
+        if rules.sort_ties_insertion:      # insertion order is iL order: the same sequence, and the cut does not read the order
+            order = sorted(order, key=lambda o: o[0])
         med = order[(M - 1) // 2 if rules.median_low else M // 2][0]
         median = f32(med)
         thDist = f32(f32(f32(1.5) * f32(1.4)) * median)
@@ -286,6 +296,54 @@ def _smax(a, b, mode):
 def _div(a, b):
     with np.errstate(all="ignore"):
         return float(np.float64(a) / np.float64(b))
+
+
+def overlap_stereo(spl, epl, spr, epr, th, rules=REF, tags=None):
+    """Frame::lineSegmentOverlapStereo on four doubles (the rows of the two left and the two right end points)."""
+    tags = [] if tags is None else tags
+    mode = rules.nan_minmax
+    overlap = 1.0
+    if abs(epl - spl) > th:
+        sln, eln = _smin(spl, epl, mode), _smax(spl, epl, mode)
+        spn, epn = _smin(spr, epr, mode), _smax(spr, epr, mode)
+        length = eln - sln if rules.length_eln_sln else eln - spn
+        if epn < sln or spn > eln:
+            overlap = 0.0; tags.append("overlap_disjoint")
+        elif epn > eln and spn < sln:
+            overlap = eln - sln; tags.append("overlap_right_contains_left")
+        else:
+            overlap = _smin(eln, epn, mode) - _smax(sln, spn, mode); tags.append("overlap_partial")
+        if length > float(f32(0.01)):
+            overlap = _div(overlap, length)
+        else:
+            overlap = 0.0; tags.append("overlap_length_le_0.01")
+        if overlap > 1.0:
+            overlap = 1.0; tags.append("overlap_clamped_to_1")
+    else:
+        tags.append("overlap_left_horizontal")
+        if rules.overlap_zero_horizontal:
+            overlap = 0.0
+    return overlap
+
+
+def filter_disparity(splx, eplx, sprx, eprx, ratio, rules=REF, tags=None):
+    """Frame::filterLineSegmentDisparity on the four columns -> disp_s, disp_e."""
+    tags = [] if tags is None else tags
+    mode = rules.nan_minmax
+    with np.errstate(all="ignore"):
+        ds, de = float(np.float64(splx) - sprx), float(np.float64(eplx) - eprx)
+        if (ds < 0) != (de < 0) and ds == ds and de == de:
+            tags.append("disparities_of_mixed_sign")
+        if ds < 0 and de < 0:
+            tags.append("disparities_both_negative")
+        q = _div(_smin(ds, de, mode), _smax(ds, de, mode))
+        if q != q:
+            tags.append("disparity_ratio_nan")
+        elif q < 0:
+            tags.append("disparity_ratio_negative")
+        if q < float(ratio):
+            ds, de = -1.0, -1.0; tags.append("disparity_ratio_reset")
+    return ds, de
 
 
 def stereo_lines(cfg, klL, ldL, klR, ldR, W, H, rules=REF):
@@ -406,25 +464,7 @@ def stereo_lines(cfg, klL, ldL, klR, ldR, W, H, rules=REF):
         spr = [float(klR["startPointX"][j]), float(klR["startPointY"][j])]; epr = [float(klR["endPointX"][j]), float(klR["endPointY"][j])]
         th = float(cfg.line_horiz_th)
         # lineSegmentOverlapStereo(sp_l(1), ep_l(1), sp_r(1), ep_r(1))
-        overlap = 1.0
-        if abs(epl[1] - spl[1]) > th:
-            sln, eln = _smin(spl[1], epl[1], mode), _smax(spl[1], epl[1], mode)
-            spn, epn = _smin(spr[1], epr[1], mode), _smax(spr[1], epr[1], mode)
-            length = eln - spn
-            if epn < sln or spn > eln:
-                overlap = 0.0; tags.append("overlap_disjoint")
-            elif epn > eln and spn < sln:
-                overlap = eln - sln; tags.append("overlap_right_contains_left")
-            else:
-                overlap = _smin(eln, epn, mode) - _smax(sln, spn, mode); tags.append("overlap_partial")
-            if length > float(f32(0.01)):
-                overlap = overlap / length
-            else:
-                overlap = 0.0; tags.append("overlap_length_le_0.01")
-            if overlap > 1.0:
-                overlap = 1.0
-        else:
-            tags.append("overlap_left_horizontal")
+        overlap = overlap_stereo(spl[1], epl[1], spr[1], epr[1], th, rules, tags)
         if spr[1] == epr[1]:
             tags.append("right_horizontal_division_by_zero")
         # Eigen's comma initialiser evaluates the three expressions before it assigns: the first line uses the old sp_r,
@@ -432,17 +472,13 @@ def stereo_lines(cfg, klL, ldL, klR, ldR, W, H, rules=REF):
         den = spr[1] - epr[1]
         with np.errstate(all="ignore"):
             nsx = _div(np.float64(spr[0]) * (spl[1] - epr[1]) + np.float64(epr[0]) * (spr[1] - spl[1]), den)
-            spr = [nsx, spl[1]]
+            if not rules.epr_from_old_spr:
+                spr = [nsx, spl[1]]
             den = spr[1] - epr[1]
             nex = _div(np.float64(spr[0]) * (epl[1] - epr[1]) + np.float64(epr[0]) * (spr[1] - epl[1]), den)
             epr = [nex, epl[1]]
-            ds, de = float(np.float64(spl[0]) - spr[0]), float(np.float64(epl[0]) - epr[0])
-            if (ds < 0) != (de < 0) and ds == ds and de == de:
-                tags.append("disparities_of_mixed_sign")
-            if ds < 0 and de < 0:
-                tags.append("disparities_both_negative")
-            if _div(_smin(ds, de, mode), _smax(ds, de, mode)) < float(cfg.ls_min_disp_ratio):
-                ds, de = -1.0, -1.0; tags.append("disparity_ratio_reset")
+            spr = [nsx, spl[1]]
+            ds, de = filter_disparity(spl[0], epl[0], spr[0], epr[0], cfg.ls_min_disp_ratio, rules, tags)
         md = float(cfg.min_disp)
         if ds == md or de == md:
             tags.append("disp_eq_min_disp")
