@@ -12,7 +12,7 @@
 // cnt(v) >= k + 1: below it at most k entries are <= v, so sorted[k] > v; at it at least k + 1 are, so sorted[k] <= v.  The values
 // lie in [0, 256] (257 of them), so a bisection finds that v in nine steps of N comparisons each.
 //
-// The groups are independent.  The host sorts them into two size classes (pli_capi.hip: pli_distinctive_descriptors): one launch for
+// The groups are independent.  The host sorts them into two size classes (match_capi.hip: pli_distinctive_descriptors): one launch for
 // the small class, two for the large one.  Every loop below is bounded by N, by the nine steps or by a list's length, no workgroup
 // waits for another, and there are no atomics.
 #include "kernels.hpp"

@@ -1,51 +1,21 @@
 // Host side of libpli_frontend.so: context, geometry tables, stage scheduling
-// on one HIP stream, and the extern "C" entry points of include/pli_frontend.h.
+// on one HIP stream, and the extern "C" entry points of include/pli_frontend.h
+// that create a context, extract, match the context's own record or measure
+// (the stateless matcher entry points: match_capi.hip; what both share: capi_host.hpp).
 // There is no CPU fallback: without a gfx950 device every compute entry point
 // fails with PLI_ERR_NO_DEVICE.
-#include "kernels.hpp"
-#include "scratch_plan.hpp"
+#include "capi_host.hpp"
 #include <cmath>
 #include <cfloat>
 #include <algorithm>
 #include <memory>
 #include <limits>
-#include <cstdlib>
 #include <set>
-#include <string>
-#include <functional>
-#include <mutex>
-#include <atomic>
-#include <dlfcn.h>
-
-using namespace pli;
-
-// Development switches (tools/README.md "Environment switches"): schedules and kernels that were measured and shelved, test switches,
-// tuning knobs.  They are read ONLY by the development build of the library (make dev: -DPLI_DEV -> libpli_frontend_dev.so, which the dev-switch
-// tests and the tools load); in the product library DEVENV is a null constant — the variable names are not even in the binary, and a
-// stray variable in an integrator's environment cannot change a schedule.  The product reads four documented variables: PLI_ROCTX (roctx
-// ranges), PLI_SYNC_DEBUG (synchronise after every launch), PLI_TX_TAIL (= 0: no persistent kernel, include/pli_frontend.h "Sharing a
-// device") and PLI_LSD_MODE (overrides pli_frontend_config.lsd_mode).
-#ifdef PLI_DEV
-#define DEVENV(name) getenv(name)
-#else
-static inline const char* pli_no_devenv() { return nullptr; }
-#define DEVENV(name) (pli_no_devenv())
-#endif
-
-namespace {
 
 thread_local std::string g_err;
 
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e__ = (expr);                                                                 \
-    if (e__ != hipSuccess) {                                                                 \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e__);                            \
-      return PLI_ERR_HIP;                                                                    \
-    }                                                                                        \
-  } while (0)
+namespace {
 
-inline int64_t alignUp(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int cvRoundf(float v) { return (int)std::nearbyintf(v); }
 inline int cvRoundd(double v) { return (int)std::nearbyint(v); }
 inline int cvFloorf(float v) { int i = (int)v; return i - (i > v); }
@@ -64,202 +34,9 @@ constexpr int RX_AUTO_IMAGES = 2560;     // images (2 per stereo frame): 1280 fr
 // — in tile waves: 32 frames of 752x480 are 64 x 135 = 8640 waves of 64-pixel tiles, about what the chip holds at once (7168)
 constexpr int TX_SMALL_TILE_WAVES = 12000;
 
-struct ProfEntry { const char* name; hipEvent_t a, b; };
-
-// the forms of the CV_64F front pass (lsd_f64.hip): k_lsd_blur64 -> k_lsd_resize64 -> k_lsd_grad64, k_lsd_front64, k_lsd_front64s
-enum class LsdFront { Unfused, Tiled, Stream };
-
 }  // namespace
 
-struct pli_ctx {
-  // Every entry point that takes a context holds this lock for the whole call: the reference drives its four extractors
-  // from four std::threads (Frame.cc:128-135) and the adapters put them on ONE context, so concurrent calls on a context
-  // are legal and are serialised here (recursive: entry points call each other).  Different contexts run concurrently.
-  mutable std::recursive_mutex mu;
-  pli_frontend_config cfg;
-  DevParams hp;
-  DevParams* dP = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool ownStream = true;
-  // side stream: for small batches the ORB chain runs beside the line chain (fork after the ingest, join before the stereo
-  // stage); both chains are launch/latency bound there (+4 % on a single pair, +2.5 % at 32 frames, nothing from 256 frames on)
-  hipStream_t aux = nullptr;
-  hipEvent_t evFork = nullptr, evJoin = nullptr, evLbdPre = nullptr;
-  hipStream_t aux2 = nullptr;        // round 1's region2rect pass beside round 2's pass over the owner map (runLines)
-  hipEvent_t evRectFork = nullptr, evRectDone = nullptr;
-  std::function<pli_status()> sideChain;     // pli_batch_run -> runLines: enqueues the side stream's work (see pli_batch_run)
-  bool lbdPreOnSide = false;                 // the LBD's blur + Sobel of this call ran on the side stream (pli_batch_run)
-  bool syncDebug = getenv("PLI_SYNC_DEBUG") != nullptr;
-  int NI = 0;
-  pli_table_layout lay;
-  std::vector<void*> allocs;
-  // ORB
-  uint8_t *pyr = nullptr, *blur = nullptr;
-  int* resizeTab[MAX_LEVELS] = {nullptr};
-  uint32_t* cellCand = nullptr; int* cellCount = nullptr;
-  uint32_t* candAll = nullptr; unsigned short* nodeOf = nullptr; int* candCount = nullptr;
-  uint32_t* kpSel = nullptr; int* kpSelCount = nullptr;
-  BlurJob *jobOrb = nullptr, *jobLsd = nullptr, *jobLbd = nullptr;
-  int orbTiles = 0, l0Tiles = 0;
-  // LSD / LBD
-  uint8_t *tmp8 = nullptr, *lsdScaled = nullptr;
-  int64_t tmp8Stride = 0, lsdStride = 0;
-  int tmpPitch = 0;
-  int* lsdTab = nullptr;
-  float4* rec = nullptr; int* g2 = nullptr; int* maxG2 = nullptr;
-  // CV_64F pipeline of the LSD front (PLI_PARITY_LSD_F64, lsd_f64.hip)
-  bool lsdF64 = false; double* mg = nullptr; unsigned long long* maxMg = nullptr; double* tmp64 = nullptr; double* kern64 = nullptr;
-  int* lsdTab64 = nullptr; int lsdRadius = 0;
-  LsdFront lsdFront = LsdFront::Unfused;     // the form of the front pass that applies to the geometry (a debug context runs Unfused)
-  int lsdFrontChunk = 0;                     // Stream: scaled rows per wave
-  int2* hot = nullptr;                       // tile relaxation, CV_64F detector: round 1's 8-byte hot records {angle, owner word} (lsd_tile.hip)
-  float2* cold = nullptr;                    // ... and the records' exact {cos, sin}: written instead of the 16-byte records when every round runs on the hot ones
-  int2* own = nullptr; RxSeed* smallSeeds = nullptr; RxSeed* bigSeeds = nullptr; int bigCap = 0;
-  RxHand* hand = nullptr; int handCap = 0; RxRect* rects = nullptr; int rectCap = 0; int* rankOf = nullptr; int2* rgBox = nullptr; float4* rgSeg = nullptr; uint8_t* rgClean = nullptr;
-  int* rgLost = nullptr;                     // tile relaxation: round in which a region last lost a contested claim (per rank)
-  // rgDirty and rgLost hold ROUND STAMPS, and a stamp is only ever compared with a round of the call that reads it.  So the planes are not
-  // cleared per call: every call of the tile relaxation stamps with lineStampNext + t and leaves lineStampNext above everything it could
-  // have written (runLines).  Words of earlier calls, under whatever pixels, are below the base and match no round.  One counter per
-  // context (the planes are indexed by image slot; calls are ordered by the context's lock and the stream).  Zeroed when allocated and
-  // when the counter would pass INT_MAX.  Dev switch PLI_TX_STAMP0: where the counter starts.
-  int lineStampNext = 0;
-  int* tileTouch = nullptr;                  // tile relaxation: round in which a grower last claimed a pixel of the 8x8 cell
-  int* tileMin = nullptr; int* tileAct = nullptr; int* rgDirty = nullptr; int tilesW = 0, tilesH = 0; int* rxChunkCnt = nullptr; int rxChunks = 0;
-  int* lastSize = nullptr; int* arena = nullptr; int arenaCap = 0; int arenaFactor = 0;    // (arena words per scaled pixel the context got)
-  RxCtl* jrCtl = nullptr;
-  int2* txList = nullptr; int* txTileCnt = nullptr; int txTs = 64, txNtx = 0, txNty = 0;   // tile-sequential relaxation (lsd_tile.hip)
-  bool txKeys = false; int txPixBits = 0; int* txCand = nullptr; int* txCandCnt = nullptr;  // ... its key mode (region id = gradient bin | seed pixel: no ordered list)
-  int2* txDirtyList = nullptr; int* txDirtyCnt = nullptr;                                  // per tile: the seeds stamped dirty in a round
-  std::vector<RxCtl> jrHost;
-  int rxImages = 0;    // images the relaxations' buffers are sized for
-  int lsdMode = 0;     // 0 auto, 1 relaxation, 2 sequential, 3 tile-sequential relaxation (cfg.lsd_mode, or PLI_LSD_MODE)
-  bool lsdSpec = !(DEVENV("PLI_LSD_SPEC") != nullptr && atoi(DEVENV("PLI_LSD_SPEC")) == 0);  // speculative sequential grower (PLI_LSD_SPEC=0: the plain one)
-  int rxLastRounds = 0; // rounds the relaxation needed in an earlier call (the last one whose control blocks the host has seen)
-  // Rounds without a host look (the default once rxLastRounds is known): the call launches rxLastRounds + rxMargin rounds — kernels
-  // of a settled image leave at once —, k_lsd_grow_unsettled redoes, on the device, whatever image did not settle in them, and the
-  // control blocks come back asynchronously (rxSeen / evRxSeen) to be read at the start of a later call.  The call never drains the
-  // stream, so copies and kernels of neighbouring calls overlap (pli_batch_submit_host, the multi-GPU gather).
-  // the rounds t >= tail t0 of the tile relaxation run in one persistent launch (lsd_tile.hip: k_tx_tail)
-  unsigned* tailBar = nullptr;      // [0] barrier arrivals, [32] abort word
-  int* txPerm = nullptr;            // round 1: (image, tile) pairs in order of decreasing seed count (k_tx_order)
-  int tailBlocks = 0;               // resident grid: CUs x blocks per CU (from the kernel's occupancy)
-  int* txCellList = nullptr;        // rounds >= 3 of large batches: the cells with work, listed (k_tx_cells) ...
-  int* txCellCnt = nullptr;         // ... and the lists' lengths, two per round (zeroed with the control blocks)
-  bool tailLaunched = false;        // this call launched k_tx_tail ...
-  bool rxSeenTail = false;          // ... and so did the call whose control blocks are on their way to the host (rxSeen)
-  int rxMargin = 3;
-  int rxPlanned = 0;                // rounds the last call launched without looking (0: it looked)
-  int* rxSeen = nullptr;            // pinned: {state, changed, overflow, rounds} per image of the last look-free call
-  hipEvent_t evRxSeen = nullptr;
-  int rxSeenImages = 0;             // images behind rxSeen while the copy is in flight (0: nothing pending)
-  int64_t rxSlowImages = 0;         // images that took the device-side fallback so far (pli_prof_report prints it)
-  unsigned short* chunkHist = nullptr; int* chunkBase = nullptr; int* nDefined = nullptr;
-  int* order = nullptr; uint2* regScratch = nullptr; float* seg = nullptr; int* nSeg = nullptr;
-  LsdRectItem* rectItems = nullptr;          // sequential grower -> k_lsd_rect (maxSeg per image)
-  double* rectW = nullptr;                   // CV_64F pipeline: the weights of the listed pixels, beside the lists
-  double* scaled64Dbg = nullptr;             // debug copy of the CV_64F scaled image (its plane is reused as the growers' arena)
-  int nChunks = 0, maxSeg = 0;
-  int scanGroups = 0, scanChunksPerGroup = 0; int* scanGroupOff = nullptr;     // ordered-list scan of large images, in groups of chunks
-  pli_keyline* tmpKL = nullptr;
-  short2* dxy = nullptr;           // Sobel (dx, dy) of level 0, interleaved
-  LbdCoef* lbdCoef = nullptr;
-  // stereo
-  int *sad = nullptr, *bestIdx = nullptr;
-  unsigned long long* lmask = nullptr; double* ldir = nullptr; short* dmat = nullptr; int *m12 = nullptr, *m21 = nullptr;
-  // drop-in state
-  uint8_t* inStage[2] = {nullptr, nullptr};
-  float2* rectMap[2] = {nullptr, nullptr};   // per eye: (mapx, mapy) of the driver's rectification, or null
-  uint8_t* ownTable = nullptr;
-  std::vector<uint8_t> hostRec;
-  bool orbDone[2] = {false, false}, lineDone[2] = {false, false};
-  bool frameFresh = false;                   // ownTable / hostRec hold the COMPLETE record of one Frame (pli_frame_extract): the stereo
-                                             // matchers hand it out without running again; any per-call extraction ends that
-  bool pointsFresh = false;                  // ... and its mvuRight / mvDepth were computed with the CURRENT rig (pli_set_stereo_camera
-                                             // clears it: the point matcher then re-runs on the resident tables)
-  uint8_t* recPinned = nullptr;              // pinned staging of that record
-  uint8_t* pyrHost[2] = {nullptr, nullptr};  // pinned copy of an eye's pyramid block (pli_orb_pyramid_level)
-  bool pyrHostValid[2] = {false, false};     // ... is the one of the last extraction on that eye
-  int orbCount[2] = {0, 0};                  // keypoints the last pli_orb_extract(_lapping) left in each eye's table
-  int lineCount[2] = {0, 0};                 // keylines the last pli_line_extract left in each eye's table
-  int monoCount[2] = {0, 0};                 // pli_orb_extract_lapping: first lapping-area keypoint of each eye's table
-  // pipelined host entry point: two slots of device staging (images + table), H2D and D2H copy streams
-  struct HostSlot { uint8_t* dimg = nullptr; uint8_t* dtab = nullptr; size_t imgBytes = 0, tabBytes = 0;
-                    hipEvent_t h2d = nullptr, kern = nullptr, d2h = nullptr; bool busy = false; };
-  HostSlot hs[2];
-  hipStream_t sH2D = nullptr, sD2H = nullptr;
-  uint64_t hsSubmitted = 0, hsWaited = 0;
-  // generic scratch for the stateless matchers
-  void* scratch = nullptr; size_t scratchBytes = 0;
-  // debug
-  bool debug = false;
-  float* angDbg = nullptr; float* lbdFloat = nullptr;
-  // profiling
-  bool prof = false;
-  std::vector<ProfEntry> profLog;
-  std::vector<hipEvent_t> evPool;
-  size_t evNext = 0;
-
-  template <class T> pli_status dalloc(T** p, size_t n) {
-    void* q = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc(&q, n * sizeof(T)));
-    allocs.push_back(q);
-    *p = (T*)q;
-    return PLI_OK;
-  }
-  hipEvent_t ev() {
-    if (evNext == evPool.size()) {
-      hipEvent_t e;
-      hipEventCreate(&e);
-      evPool.push_back(e);
-    }
-    return evPool[evNext++];
-  }
-  void profBegin(const char* name) {
-    if (!prof) return;
-    ProfEntry pe{name, ev(), ev()};
-    hipEventRecord(pe.a, stream);
-    profLog.push_back(pe);
-  }
-  void profEnd() {
-    if (!prof) return;
-    hipEventRecord(profLog.back().b, stream);
-  }
-};
-
-// roctx ranges ("rocprofv3 counters + roctx ranges per kernel").  With PLI_ROCTX=1 in the environment every stage of a call
-// (ingest, ORB chain, line chain, the two stereo matchers, the entry points themselves) and every kernel launch is bracketed by
-// roctxRangePush / roctxRangePop, so that `rocprofv3 --kernel-trace --marker-trace` shows which call and stage a kernel belongs
-// to.  The marker library is looked up at run time (rocprofiler-sdk's, then roctracer's): no link-time dependency, nothing is
-// loaded and nothing is pushed without the switch.  pli_trace_ranges() counts the ranges pushed so far.
-struct PliRoctx {
-  int (*push)(const char*) = nullptr;
-  int (*pop)() = nullptr;
-  std::atomic<long long> pushed{0};
-  PliRoctx() {
-    const char* e = getenv("PLI_ROCTX");
-    if (!e || atoi(e) == 0) return;
-    for (const char* lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
-      void* h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
-      if (!h) continue;
-      push = reinterpret_cast<int (*)(const char*)>(dlsym(h, "roctxRangePushA"));
-      pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
-      if (push && pop) break;
-      push = nullptr; pop = nullptr;
-    }
-  }
-};
-static PliRoctx g_roctx;
-struct TraceRange {
-  bool on;
-  explicit TraceRange(const char* name) : on(g_roctx.push != nullptr) {
-    if (on) { g_roctx.push(name); g_roctx.pushed.fetch_add(1, std::memory_order_relaxed); }
-  }
-  ~TraceRange() { if (on) g_roctx.pop(); }
-  TraceRange(const TraceRange&) = delete;
-  TraceRange& operator=(const TraceRange&) = delete;
-};
+PliRoctx g_roctx;
 
 constexpr int TX_CELL_ROUNDS = 100;   // rounds of a call that can run on cell lists (two list lengths per round and image, zeroed per call)
 // the last k_tx_tail launch on every device of this process (see the launch site)
@@ -271,28 +48,6 @@ static hipEvent_t g_tailEv[TAIL_MAX_DEVICES] = {};
 // instead of stalling a second per call (include/pli_frontend.h "Sharing a device").
 static std::atomic<bool> g_tailAborted[TAIL_MAX_DEVICES] = {};       // (read without the mutex by every call: relaxed atomics)
 static bool g_tailWarned = false;
-
-struct CtxGuard {
-  const pli_ctx* c;
-  explicit CtxGuard(const pli_ctx* c_) : c(c_) { if (c) c->mu.lock(); }
-  ~CtxGuard() { if (c) c->mu.unlock(); }
-  CtxGuard(const CtxGuard&) = delete;
-  CtxGuard& operator=(const CtxGuard&) = delete;
-};
-
-#define LAUNCH(c, name, kern, grid, block, shmem, ...)                       \
-  do {                                                                       \
-    TraceRange tr__(name);                                                   \
-    (c)->profBegin(name);                                                    \
-    hipLaunchKernelGGL(kern, grid, block, shmem, (c)->stream, __VA_ARGS__);  \
-    (c)->profEnd();                                                          \
-    HIPCHK(hipGetLastError());                                               \
-    if ((c)->syncDebug) {   /* PLI_SYNC_DEBUG: find the kernel that faults */ \
-      std::fprintf(stderr, "[pli] %s ...", name);                            \
-      HIPCHK(hipStreamSynchronize((c)->stream));                             \
-      std::fprintf(stderr, " ok\n");                                         \
-    }                                                                        \
-  } while (0)
 
 namespace {
 
@@ -1654,42 +1409,6 @@ pli_status runStereoLines(pli_ctx* c, int nframes, uint8_t* table) {
   return PLI_OK;
 }
 
-pli_status ensureScratch(pli_ctx* c, size_t bytes) {
-  if (bytes <= c->scratchBytes) return PLI_OK;
-  if (c->scratch) hipFree(c->scratch);
-  c->scratch = nullptr; c->scratchBytes = 0;
-  HIPCHK(hipMalloc(&c->scratch, bytes));
-  c->scratchBytes = bytes;
-  return PLI_OK;
-}
-
-// The scratch of one call (scratch_plan.hpp): the context's grow-only buffer takes the plan's total, the plan's blocks point into it.
-pli_status commitScratch(pli_ctx* c, ScratchPlan& plan) {
-  const pli_status st = ensureScratch(c, plan.bytes());
-  if (st == PLI_OK) plan.bind(c->scratch);
-  return st;
-}
-
-// n elements from the host into a scratch block, on the context's stream (nothing when n == 0) ...
-template <typename T>
-hipError_t upload(pli_ctx* c, ScratchBlock<T> dst, const T* src, size_t n) {
-  return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream) : hipSuccess;
-}
-// ... and back (nothing for a null pointer or n == 0)
-template <typename T>
-hipError_t download(pli_ctx* c, T* dst, ScratchBlock<T> src, size_t n) {
-  return dst && n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-}
-
-// The tail of the matchers: waits for the stream and hands out the device's match counter.
-pli_status fetchCount(pli_ctx* c, const int* dcount, int32_t* nmatches) {
-  int cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, dcount, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (nmatches) *nmatches = cnt;
-  return PLI_OK;
-}
-
 // The counts block of a record (include/pli_frontend.h: pli_table_layout.off_counts), as the kernels write it.
 struct RecordCounts {
   int32_t kp[2], kl[2];                   // keypoints / keylines of eye 0, 1
@@ -1724,127 +1443,6 @@ pli_status stageImage(pli_ctx* c, int eye, const uint8_t* img, int w, int h, int
   return runIngest(c, c->inStage[0], c->inStage[1], w, 0, eye, 1);
 }
 
-// ---- the searches of one item against a batch of keyframes ------------------------
-// pli_search_by_bow, pli_search_by_bow_kf, pli_search_for_triangulation, pli_fuse_search and pli_search_by_projection_sim3 take their
-// keyframes as flat tables (pli_search_by_projection_reloc: its candidates' point lists, mp_off):
-// keyframe k is rows kf_off[k] .. kf_off[k + 1].  What they share on the host is here; every entry point checks in the same order:
-// null / negative arguments, nkf == 0 (OK), kf_off and the per-keyframe cap (kfBatch), the other side's cap, null tables for
-// total > 0, the values, the empty other side (OK, zeroed counts).
-struct KfBatch {
-  int nkf = 0;
-  const int32_t* off = nullptr;
-  int64_t total = 0;                                        // rows of all keyframes
-  int maxNk = 0;                                            // rows of the largest keyframe
-};
-
-// PLI_ERR_INVALID for a kf_off that does not start at 0 or decreases, PLI_ERR_CAPACITY (capMsg) for a keyframe above the cap
-pli_status kfBatch(int32_t nkf, const int32_t* kfOff, const char* capMsg, KfBatch& B) {
-  if (kfOff[0] != 0) { g_err = "kf_off[0] must be 0"; return PLI_ERR_INVALID; }
-  B.nkf = nkf; B.off = kfOff; B.maxNk = 0;
-  for (int k = 0; k < nkf; ++k) {
-    if (kfOff[k + 1] < kfOff[k]) { g_err = "kf_off must not decrease"; return PLI_ERR_INVALID; }
-    const int nk = kfOff[k + 1] - kfOff[k];
-    if (nk > PLI_BOW_MAX_FEATURES) { g_err = capMsg; return PLI_ERR_CAPACITY; }
-    B.maxNk = std::max(B.maxNk, nk);
-  }
-  B.total = kfOff[nkf];
-  return PLI_OK;
-}
-
-bool nodesOk(const int32_t* node, int64_t n, const char* what) {
-  for (int64_t i = 0; i < n; ++i)
-    if (node[i] < -1) { g_err = std::string(what) + ": a node id or -1"; return false; }
-  return true;
-}
-
-// (the rotation histogram's bin of an angle outside [0, 360) would be undefined in the reference, an assert)
-inline float angleOf(float a) { return a; }
-inline float angleOf(const pli_keypoint& k) { return k.angle; }
-template <class T>
-bool anglesOk(const T* p, int64_t n, const char* what) {
-  for (int64_t i = 0; i < n; ++i)
-    if (!(angleOf(p[i]) >= 0.f && angleOf(p[i]) < 360.f)) { g_err = std::string(what) + " outside [0, 360)"; return false; }
-  return true;
-}
-
-// (the octaves index the level tables: outside them the reference reads past a vector)
-bool octavesOk(const pli_ctx* c, const pli_keypoint* kp, int64_t n, const char* what) {
-  for (int64_t i = 0; i < n; ++i)
-    if (kp[i].octave < 0 || kp[i].octave >= c->hp.nlevels) { g_err = std::string(what) + ": octave outside the context's levels"; return false; }
-  return true;
-}
-
-// (the two-camera searches: a keypoint's coordinates enter float arithmetic whose result picks cells and gates)
-bool finiteOk(const pli_keypoint* kp, int64_t n, const char* what) {
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(kp[i].x) || !std::isfinite(kp[i].y)) { g_err = std::string(what) + ": a keypoint's coordinates are not finite"; return false; }
-  return true;
-}
-
-// kf_nleft[k] = NLeft of keyframe k, inside its rows
-bool nleftOk(int32_t nkf, const int32_t* kfOff, const int32_t* kfNleft, const char* msg) {
-  for (int k = 0; k < nkf; ++k)
-    if (kfNleft[k] < 0 || kfNleft[k] > kfOff[k + 1] - kfOff[k]) { g_err = msg; return false; }
-  return true;
-}
-
-int pow2Ceil(int m) {
-  int n = 1;
-  while (n < m) n <<= 1;
-  return n;
-}
-
-// mvScaleFactors, mvLevelSigma2 and mvInvLevelSigma2 = 1.0f / mvLevelSigma2 (ORBextractor.cc:420-431) as the device compares
-// against them; each a table of MAX_LEVELS floats or NULL
-void levelTables(const pli_ctx* c, float* scale, float* sigma2, float* invSigma2) {
-  for (int l = 0; l < c->hp.nlevels; ++l) {
-    const float s = c->hp.lv[l].scale;
-    if (scale) scale[l] = s;
-    if (sigma2) sigma2[l] = s * s;
-    if (invSigma2) invSigma2[l] = 1.0f / (s * s);
-  }
-}
-
-// The projection searches (pli_fuse_search, pli_search_by_projection_sim3 / _reloc) predict a point's level by comparing against
-// level_ratio, nlevels - 1 thresholds that must not decrease, and sort a table into the 64 x 48 grid of its image bounds.
-bool levelRatioOk(const pli_ctx* c, const float* levelRatio) {
-  for (int n = 0; n < c->hp.nlevels - 1; ++n)
-    if (std::isnan(levelRatio[n]) || (n > 0 && levelRatio[n] < levelRatio[n - 1])) { g_err = "level_ratio must not decrease"; return false; }
-  return true;
-}
-bool imageBoundsOk(float minX, float maxX, float minY, float maxY) {
-  if (!(maxX > minX) || !(maxY > minY)) { g_err = "empty image bounds"; return false; }
-  return true;
-}
-// their level block for the device: level_ratio, mvScaleFactors and (ntables 3: Fuse's chi-square gate) mvInvLevelSigma2
-struct LevelBlock {
-  float v[3 * MAX_LEVELS] = {};
-  LevelBlock(const pli_ctx* c, const float* levelRatio, int ntables) {
-    std::copy(levelRatio, levelRatio + std::max(c->hp.nlevels - 1, 0), v);
-    levelTables(c, v + MAX_LEVELS, nullptr, ntables == 3 ? v + 2 * MAX_LEVELS : nullptr);
-  }
-};
-// one table as the single "keyframe" of k_fuse_grid: its offset list {0, n} (the caller's object: it lives until the synchronise)
-struct OneTableOff { const int off[2]; explicit OneTableOff(int n) : off{0, n} {} };
-
-// the candidate list of one slot of pli_search_by_projection_sim3 / _reloc: 16 keys (DESIGN.md §9, Sim3 projection; the ordered
-// wave reads a list with one load, so 64 is the most; the development build can run the other widths)
-int sim3ListWidth() {
-  if (const char* e = DEVENV("PLI_SIM3_WIDTH")) return std::min(64, std::max(1, atoi(e)));
-  return 16;
-}
-
-// the tail of the two SearchForTriangulation entry points (their plans and uploads interleave their own tables with the common ones)
-pli_status triEnd(pli_ctx* c, const KfBatch& B, int n1, ScratchBlock<pli_keypoint> dK1, ScratchBlock<pli_keypoint> dKk, ScratchBlock<int> dOff,
-                  ScratchBlock<int> dStat, ScratchBlock<int> dM, int checkOri, int32_t* matches12, int32_t* nmatches) {
-  if (checkOri) LAUNCH(c, "k_tri_finish", k_tri_finish, dim3(B.nkf), dim3(256), 0, dK1, n1, dOff, dKk, dM, dStat);
-  HIPCHK(download(c, matches12, dM, (size_t)B.nkf * n1));
-  std::vector<int> hstat((size_t)B.nkf * 32);
-  HIPCHK(download(c, hstat.data(), dStat, (size_t)B.nkf * 32));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < B.nkf; ++k) nmatches[k] = hstat[(size_t)k * 32 + 30];
-  return PLI_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -2611,35 +2209,28 @@ static pli_status fisheyeCore(pli_ctx* c, bool hostTables, const pli_keypoint* k
         }
     }
   }
+  float hRt[12], hsig[MAX_LEVELS];
+  for (int i = 0; i < 9; ++i) hRt[i] = Rlr[i];
+  for (int i = 0; i < 3; ++i) hRt[9 + i] = tlr[i];
+  for (int l = 0; l < c->hp.nlevels; ++l) hsig[l] = c->hp.lv[l].scale * c->hp.lv[l].scale;      // mvLevelSigma2, ORBextractor.cc:424
+  const int sL = hostTables ? NL : 0, sR = hostTables ? NR : 0;      // rows staged from the caller's tables
   ScratchPlan plan;
   auto kidx = plan.add<int>((size_t)nq * 2);             // k_knn2: two ints per query, the indices ...
   auto kdst = plan.add<int>((size_t)nq * 2);             // ... and the distances
   auto dl2r = plan.add<int>(NL);
   auto ddepth = plan.add<float>(NL);
   auto dr2l = plan.add<int>(NR);
-  auto dp3 = plan.add<float>((size_t)std::max(NL, 1) * 3);
-  auto dRt = plan.add<float>(12);
-  auto dsig = plan.add<float>(MAX_LEVELS);
+  auto dp3 = plan.add<float>((size_t)NL * 3);
+  auto dRt = plan.in(hRt, 12);
+  auto dsig = plan.in(hsig, c->hp.nlevels);
   auto dcnt = plan.add<int>(1);
-  auto skL = plan.add<pli_keypoint>(hostTables ? NL : 0);
-  auto sdL = plan.add<uint8_t>(hostTables ? (size_t)NL * 32 : 0);
-  auto skR = plan.add<pli_keypoint>(hostTables ? NR : 0);
-  auto sdR = plan.add<uint8_t>(hostTables ? (size_t)NR * 32 : 0);
+  auto skL = plan.in(kL, sL);
+  auto sdL = plan.in(dL, (size_t)sL * 32);
+  auto skR = plan.in(kR, sR);
+  auto sdR = plan.in(dR, (size_t)sR * 32);
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  if (hostTables) {
-    HIPCHK(upload(c, skL, kL, NL));
-    HIPCHK(upload(c, sdL, dL, (size_t)NL * 32));
-    HIPCHK(upload(c, skR, kR, NR));
-    HIPCHK(upload(c, sdR, dR, (size_t)NR * 32));
-    kL = skL; dL = sdL; kR = skR; dR = sdR;
-  }
-  float hRt[12], hsig[MAX_LEVELS];
-  for (int i = 0; i < 9; ++i) hRt[i] = Rlr[i];
-  for (int i = 0; i < 3; ++i) hRt[9 + i] = tlr[i];
-  for (int l = 0; l < c->hp.nlevels; ++l) hsig[l] = c->hp.lv[l].scale * c->hp.lv[l].scale;      // mvLevelSigma2, ORBextractor.cc:424
-  HIPCHK(upload(c, dRt, hRt, 12));
-  HIPCHK(upload(c, dsig, hsig, c->hp.nlevels));
+  if (hostTables) { kL = skL; dL = sdL; kR = skR; dR = sdR; }
   HIPCHK(hipMemsetAsync(dl2r, 0xFF, (size_t)std::max(NL, 1) * 4, c->stream));
   HIPCHK(hipMemsetAsync(dr2l, 0xFF, (size_t)std::max(NR, 1) * 4, c->stream));
   HIPCHK(hipMemsetAsync(dp3, 0, (size_t)std::max(NL, 1) * 12, c->stream));
@@ -2653,10 +2244,10 @@ static pli_status fisheyeCore(pli_ctx* c, bool hostTables, const pli_keypoint* k
     LAUNCH(c, "k_fisheye_triangulate", k_fisheye_triangulate, dim3((nq + 63) / 64), dim3(64), 0, kL, kR, (const int*)kidx,
            (const int*)kdst, nq, nt, monoL, monoR, c1, c2, (const float*)dRt, (const float*)dsig, dl2r, dr2l, ddepth, dp3, dcnt);
   }
-  HIPCHK(download(c, l2r, dl2r, NL));
-  HIPCHK(download(c, r2l, dr2l, NR));
-  HIPCHK(download(c, depth, ddepth, NL));
-  HIPCHK(download(c, p3d, dp3, (size_t)NL * 3));
+  HIPCHK(download(c, l2r, dl2r));
+  HIPCHK(download(c, r2l, dr2l));
+  HIPCHK(download(c, depth, ddepth));
+  HIPCHK(download(c, p3d, dp3));
   return fetchCount(c, dcnt, nmatches);
 }
 
@@ -2719,304 +2310,6 @@ pli_status pli_stereo_match_lines(pli_ctx* c, float* disp, double* le, int32_t c
   return PLI_OK;
 }
 
-pli_status pli_descriptor_distance(pli_ctx* c, const uint8_t* a, const uint8_t* b, int32_t n, int32_t* dist) {
-  CtxGuard guard__(c);
-  if (!c || n < 0 || (n > 0 && (!a || !b || !dist))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (n == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto da = plan.add<uint8_t>((size_t)n * 32);
-  auto db = plan.add<uint8_t>((size_t)n * 32);
-  auto dd = plan.add<int>(n);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, da, a, (size_t)n * 32));
-  HIPCHK(upload(c, db, b, (size_t)n * 32));
-  LAUNCH(c, "k_distance", k_distance, dim3((n + 255) / 256), dim3(256), 0, da, db, n, dd);
-  HIPCHK(download(c, dist, dd, n));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_hamming_knn2(pli_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t* idx, int32_t* dist) {
-  CtxGuard guard__(c);
-  if (!c || nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nq == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dq = plan.add<uint8_t>((size_t)nq * 32);
-  auto dt = plan.add<uint8_t>((size_t)nt * 32);
-  auto di = plan.add<int>((size_t)nq * 2);               // k_knn2: two ints per query, the indices ...
-  auto dd = plan.add<int>((size_t)nq * 2);               // ... and the distances
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dq, q, (size_t)nq * 32));
-  HIPCHK(upload(c, dt, t, (size_t)nt * 32));
-  LAUNCH(c, "k_knn2", k_knn2, dim3(nq), dim3(64), 0, dq, nq, dt, nt, di, dd);
-  HIPCHK(download(c, idx, di, (size_t)nq * 2));
-  HIPCHK(download(c, dist, dd, (size_t)nq * 2));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-static pli_status matchDescriptors(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
-                                   bool mutual, int32_t* m12, int32_t* nmatches) {
-  if (!c || n1 < 0 || n2 < 0 || (n1 > 0 && (!d1 || !m12)) || (n2 > 0 && !d2)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nmatches) *nmatches = 0;
-  if (n1 == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dd1 = plan.add<uint8_t>((size_t)n1 * 32);
-  auto dd2 = plan.add<uint8_t>((size_t)n2 * 32);
-  auto i1 = plan.add<int>((size_t)n1 * 2);               // k_knn2: two ints per query, the indices ...
-  auto ds1 = plan.add<int>((size_t)n1 * 2);              // ... and the distances
-  auto i2 = plan.add<int>((size_t)n2 * 2);
-  auto ds2 = plan.add<int>((size_t)n2 * 2);
-  auto dm12 = plan.add<int>(n1);
-  auto dm21 = plan.add<int>(n2);
-  auto dcount = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dd1, d1, (size_t)n1 * 32));
-  HIPCHK(upload(c, dd2, d2, (size_t)n2 * 32));
-  HIPCHK(hipMemsetAsync(dcount, 0, 4, c->stream));
-  LAUNCH(c, "k_knn2", k_knn2, dim3(n1), dim3(64), 0, dd1, n1, dd2, n2, i1, ds1);
-  LAUNCH(c, "k_ratio", k_ratio, dim3((n1 + 255) / 256), dim3(256), 0, i1, ds1, n1, n2, nnr, dm12);
-  const bool lr = mutual;
-  if (lr && n2 > 0) {
-    LAUNCH(c, "k_knn2", k_knn2, dim3(n2), dim3(64), 0, dd2, n2, dd1, n1, i2, ds2);
-    LAUNCH(c, "k_ratio", k_ratio, dim3((n2 + 255) / 256), dim3(256), 0, i2, ds2, n2, n1, nnr, dm21);
-  }
-  LAUNCH(c, "k_mutual", k_mutual, dim3((n1 + 255) / 256), dim3(256), 0, dm12, (lr && n2 > 0) ? (int*)dm21 : (int*)nullptr, n1, dcount);
-  HIPCHK(download(c, m12, dm12, n1));
-  return fetchCount(c, dcount, nmatches);
-}
-
-pli_status pli_match_lines(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
-                           int32_t* m12, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  return matchDescriptors(c, d1, n1, d2, n2, nnr, c && c->cfg.best_lr_matches != 0, m12, nmatches);
-}
-
-pli_status pli_match_nnr(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
-                         int32_t* m12, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  return matchDescriptors(c, d1, n1, d2, n2, nnr, false, m12, nmatches);
-}
-
-// Both projection searches: mode 0 frame-to-frame (ORBmatcher.cc:2179-2323), mode 1 local map (:44-143).
-// Frames whose keypoints fit the LDS owner table take the two-phase form (candidates in parallel, then the ordered
-// assignment); larger ones the ordered assignment alone, owner table in global memory, which scans the frame per query.
-constexpr int PROJ_LDS_KEYPOINTS = 15360;
-
-static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
-                                   const pli_keypoint* kp, const uint8_t* desc, const float* uright, const uint8_t* occupied,
-                                   int32_t ncur, float minX, float maxX, float minY, float maxY, int32_t checkOri,
-                                   float nnratio, int32_t* best, int32_t* nmatches, int32_t* raw = nullptr) {
-  if (!c || nq < 0 || ncur < 0 || (nq > 0 && (!q || !qdesc || !best)) || (ncur > 0 && (!kp || !desc || !uright))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nmatches) *nmatches = 0;
-  if (nq == 0) return PLI_OK;
-  if (ncur >= (1 << 28)) { g_err = "too many keypoints"; return PLI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  const int nc = std::max(ncur, 1);
-  const bool ownerInLds = ncur <= PROJ_LDS_KEYPOINTS;
-  for (int i = 0; i < nq; ++i)
-    if (mode == 0 && (q[i].valid & ~3)) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
-  ScratchPlan plan;
-  auto dq = plan.add<pli_proj_query>(nq);
-  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
-  auto dk = plan.add<pli_keypoint>(ncur);
-  auto ddsc = plan.add<uint8_t>((size_t)ncur * 32);
-  auto du = plan.add<float>(ncur);
-  auto down = plan.add<int>(ownerInLds ? 0 : ncur);
-  auto dbest = plan.add<int>(nq);
-  auto draw = plan.add<int>(nq);
-  auto docc = plan.add<uint8_t>(ncur);
-  auto dkeys = plan.add<unsigned long long>(ownerInLds ? (size_t)nq * PROJ_K : 0);
-  auto dcc = plan.add<int>(ownerInLds ? nq : 0);
-  auto dcnt = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dq, q, nq));
-  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
-  HIPCHK(upload(c, dk, kp, ncur));
-  HIPCHK(upload(c, ddsc, desc, (size_t)ncur * 32));
-  HIPCHK(upload(c, du, uright, ncur));
-  if (occupied) HIPCHK(upload(c, docc, occupied, ncur));
-  const uint8_t* occ = (occupied && ncur > 0) ? (const uint8_t*)docc : (const uint8_t*)nullptr;
-  int* rawOut = (mode == 0 && raw) ? (int*)draw : (int*)nullptr;
-  if (ownerInLds) {
-    // a second-best farther than 100 / nnratio can no longer reject a best of <= 100 (ORBmatcher.cc:124-126)
-    int limit = 100;
-    if (mode == 1) limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
-    LAUNCH(c, "k_proj_candidates", k_proj_candidates, dim3(nq), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, ncur, minX, maxX, minY, maxY,
-           mode == 0 ? 1 : 0, limit, dkeys, dcc);
-    LAUNCH(c, "k_proj_assign", k_proj_assign, dim3(1), dim3(64), (size_t)nc * 4, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
-           minY, maxY, mode, checkOri, nnratio, dkeys, dcc, dbest, dcnt, rawOut);
-  } else {
-    LAUNCH(c, "k_proj_assign_scan", k_proj_assign_scan, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
-           minY, maxY, mode, checkOri, nnratio, down, dbest, dcnt, rawOut);
-  }
-  HIPCHK(download(c, best, dbest, nq));
-  if (rawOut) HIPCHK(download(c, raw, draw, nq));
-  return fetchCount(c, dcnt, nmatches);
-}
-
-pli_status pli_search_by_projection(pli_ctx* c, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
-                                    const pli_keypoint* kp, const uint8_t* desc, const float* uright,
-                                    const uint8_t* occupied, int32_t ncur,
-                                    float minX, float maxX, float minY, float maxY, int32_t checkOri,
-                                    int32_t* best, int32_t* raw, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  return projectionSearch(c, 0, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, checkOri, 0.0f, best, nmatches, raw);
-}
-
-pli_status pli_search_local_map(pli_ctx* c, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
-                                const pli_keypoint* kp, const uint8_t* desc, const float* uright,
-                                const uint8_t* occupied, int32_t ncur, float minX, float maxX, float minY, float maxY,
-                                float nnratio, int32_t* best, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  return projectionSearch(c, 1, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, 0, nnratio, best, nmatches);
-}
-
-pli_status pli_search_local_map_fisheye(pli_ctx* c, const pli_proj_query* qL, const pli_proj_query* qR, const uint8_t* qdesc,
-                                        int32_t nq, const pli_keypoint* kpL, const uint8_t* descL, const uint8_t* occL,
-                                        const int32_t* l2r, int32_t nL, const pli_keypoint* kpR, const uint8_t* descR,
-                                        const uint8_t* occR, const int32_t* r2l, int32_t nR, float minX, float maxX, float minY,
-                                        float maxY, float nnratio, int32_t* mpL, int32_t* mpR, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || nq < 0 || nL < 0 || nR < 0 || (nq > 0 && (!qL || !qR || !qdesc)) || (nL > 0 && (!kpL || !descL || !l2r || !mpL)) ||
-      (nR > 0 && (!kpR || !descR || !r2l || !mpR))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nmatches) *nmatches = 0;
-  for (int i = 0; i < nL; ++i) {
-    mpL[i] = -1;
-    if (l2r[i] < -1 || l2r[i] >= nR) { g_err = "left_to_right out of range"; return PLI_ERR_INVALID; }
-  }
-  for (int i = 0; i < nR; ++i) {
-    mpR[i] = -1;
-    if (r2l[i] < -1 || r2l[i] >= nL) { g_err = "right_to_left out of range"; return PLI_ERR_INVALID; }
-  }
-  if (nq == 0 || nL + nR == 0) return PLI_OK;
-  if (nL + nR > PROJ_LDS_KEYPOINTS) { g_err = "too many keypoints for the LDS slot tables of the fisheye local-map search"; return PLI_ERR_CAPACITY; }
-  HIPCHK(hipSetDevice(c->device));
-  const int ncM = std::max(std::max(nL, nR), 1);
-  ScratchPlan plan;
-  auto dqL = plan.add<pli_proj_query>(nq);
-  auto dqR = plan.add<pli_proj_query>(nq);
-  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
-  auto dkL = plan.add<pli_keypoint>(nL);
-  auto ddL = plan.add<uint8_t>((size_t)nL * 32);
-  auto doL = plan.add<uint8_t>(nL);
-  auto dl2r = plan.add<int>(nL);
-  auto dmpL = plan.add<int>(nL);
-  auto dkR = plan.add<pli_keypoint>(nR);
-  auto ddR = plan.add<uint8_t>((size_t)nR * 32);
-  auto doR = plan.add<uint8_t>(nR);
-  auto dr2l = plan.add<int>(nR);
-  auto dmpR = plan.add<int>(nR);
-  auto du = plan.add<float>(ncM);
-  auto dkeysL = plan.add<unsigned long long>((size_t)nq * PROJ_K);
-  auto dkeysR = plan.add<unsigned long long>((size_t)nq * PROJ_K);
-  auto dccL = plan.add<int>(nq);
-  auto dccR = plan.add<int>(nq);
-  auto dcnt = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dqL, qL, nq));
-  HIPCHK(upload(c, dqR, qR, nq));
-  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
-  HIPCHK(upload(c, dkL, kpL, nL));
-  HIPCHK(upload(c, ddL, descL, (size_t)nL * 32));
-  HIPCHK(upload(c, dl2r, l2r, nL));
-  if (occL) HIPCHK(upload(c, doL, occL, nL));
-  HIPCHK(upload(c, dkR, kpR, nR));
-  HIPCHK(upload(c, ddR, descR, (size_t)nR * 32));
-  HIPCHK(upload(c, dr2l, r2l, nR));
-  if (occR) HIPCHK(upload(c, doR, occR, nR));
-  // (the fisheye branch has no mvuRight gate: a plane of -1 switches it off in the shared candidate kernel)
-  LAUNCH(c, "k_fill_f32", k_fill_f32, dim3((ncM + 255) / 256), dim3(256), 0, du, ncM, -1.0f);
-  const int limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
-  LAUNCH(c, "k_proj_candidates", k_proj_candidates, dim3(nq), dim3(64), 0, dqL, dqd, nq, dkL, ddL, du, nL, minX, maxX, minY, maxY, 0, limit,
-         dkeysL, dccL);
-  LAUNCH(c, "k_proj_candidates", k_proj_candidates, dim3(nq), dim3(64), 0, dqR, dqd, nq, dkR, ddR, du, nR, minX, maxX, minY, maxY, 0, limit,
-         dkeysR, dccR);
-  LAUNCH(c, "k_proj_assign_fisheye", k_proj_assign_fisheye, dim3(1), dim3(64), (size_t)(nL + nR) * 4, dqL, dqR, dqd, nq, dkL, ddL,
-         (occL && nL > 0) ? (const uint8_t*)doL : (const uint8_t*)nullptr, dl2r, nL, dkR, ddR,
-         (occR && nR > 0) ? (const uint8_t*)doR : (const uint8_t*)nullptr, dr2l, nR, du, minX, maxX, minY, maxY, nnratio, dkeysL, dccL,
-         dkeysR, dccR, dmpL, dmpR, dcnt);
-  HIPCHK(download(c, mpL, dmpL, nL));
-  HIPCHK(download(c, mpR, dmpR, nR));
-  return fetchCount(c, dcnt, nmatches);
-}
-
-// SearchByProjection(CurrentFrame, LastFrame) for a current frame of two cameras (match_kernels.hip: k_proj2_*)
-pli_status pli_search_by_projection_two_cameras(pli_ctx* c, const pli_proj_query* qL, const pli_proj_query* qR, const uint8_t* qdesc,
-                                                int32_t nq, const pli_keypoint* kpL, const uint8_t* descL, const uint8_t* occL,
-                                                int32_t nL, const pli_keypoint* kpR, const uint8_t* descR, const uint8_t* occR,
-                                                int32_t nR, float minX, float maxX, float minY, float maxY, int32_t checkOri,
-                                                int32_t* bestL, int32_t* bestR, int32_t* rawL, int32_t* rawR, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || nq < 0 || nL < 0 || nR < 0 || (nq > 0 && (!qL || !qR || !qdesc || !bestL || !bestR)) || (nL > 0 && (!kpL || !descL)) ||
-      (nR > 0 && (!kpR || !descR))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nmatches) *nmatches = 0;
-  for (int i = 0; i < nq; ++i)
-    if (qL[i].valid & ~3) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
-  if ((int64_t)nL + nR > PROJ_LDS_KEYPOINTS) { g_err = "too many keypoints for the LDS owner tables of the two-camera projection search"; return PLI_ERR_CAPACITY; }
-  if (nq == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const int ncM = std::max(std::max(nL, nR), 1);
-  // both cameras' queries in one block: the left as given, then the right with the left's valid and angle (the only fields the
-  // reference takes from the last frame's row for both cameras); q2 lives until the synchronisation in fetchCount
-  std::vector<pli_proj_query> q2((size_t)2 * nq);
-  for (int i = 0; i < nq; ++i) {
-    q2[i] = qL[i];
-    pli_proj_query r = qR[i];
-    r.ur = 0.0f; r.angle = qL[i].angle; r.valid = qL[i].valid;
-    q2[(size_t)nq + i] = r;
-  }
-  ScratchPlan plan;
-  auto dq = plan.add<pli_proj_query>((size_t)2 * nq);
-  auto dqd = plan.add<uint8_t>((size_t)nq * 32);
-  auto dkL = plan.add<pli_keypoint>(nL);
-  auto ddL = plan.add<uint8_t>((size_t)nL * 32);
-  auto doL = plan.add<uint8_t>(nL);
-  auto dkR = plan.add<pli_keypoint>(nR);
-  auto ddR = plan.add<uint8_t>((size_t)nR * 32);
-  auto doR = plan.add<uint8_t>(nR);
-  auto du = plan.add<float>(ncM);
-  auto dkeys = plan.add<unsigned long long>((size_t)2 * nq * PROJ_K);
-  auto dcc = plan.add<int>((size_t)2 * nq);
-  auto dopen = plan.add<int>(nq);
-  auto draw = plan.add<int>((size_t)2 * nq);
-  auto dbest = plan.add<int>((size_t)2 * nq);
-  auto dhist = plan.add<int>(2 * 30);                    // [2][HISTO_LENGTH]
-  auto dacc = plan.add<int>(2);
-  auto dcnt = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dq, q2.data(), (size_t)2 * nq));
-  HIPCHK(upload(c, dqd, qdesc, (size_t)nq * 32));
-  HIPCHK(upload(c, dkL, kpL, nL));
-  HIPCHK(upload(c, ddL, descL, (size_t)nL * 32));
-  if (occL) HIPCHK(upload(c, doL, occL, nL));
-  HIPCHK(upload(c, dkR, kpR, nR));
-  HIPCHK(upload(c, ddR, descR, (size_t)nR * 32));
-  if (occR) HIPCHK(upload(c, doR, occR, nR));
-  LAUNCH(c, "k_fill_f32", k_fill_f32, dim3((ncM + 255) / 256), dim3(256), 0, du, ncM, -1.0f);
-  LAUNCH(c, "k_proj2_candidates", k_proj2_candidates, dim3(nq, 2), dim3(64), 0, dq, dqd, nq, dkL, ddL, nL, dkR, ddR, nR, du, minX, maxX,
-         minY, maxY, dkeys, dcc, dopen);
-  LAUNCH(c, "k_proj2_assign", k_proj2_assign, dim3(2), dim3(64), (size_t)ncM * 4, dq, dqd, nq, dkL, ddL,
-         (occL && nL > 0) ? (const uint8_t*)doL : (const uint8_t*)nullptr, nL, dkR, ddR,
-         (occR && nR > 0) ? (const uint8_t*)doR : (const uint8_t*)nullptr, nR, du, minX, maxX, minY, maxY, checkOri, dkeys, dcc, dopen,
-         draw, dhist, dacc);
-  LAUNCH(c, "k_proj2_finish", k_proj2_finish, dim3(1), dim3(64), 0, dq, nq, dkL, dkR, checkOri, draw, dhist, dacc, dbest, dcnt);
-  HIPCHK(download(c, bestL, dbest, nq));
-  HIPCHK(hipMemcpyAsync(bestR, (int*)dbest + nq, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(download(c, rawL, draw, nq));
-  if (rawR) HIPCHK(hipMemcpyAsync(rawR, (int*)draw + nq, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-  return fetchCount(c, dcnt, nmatches);
-}
-
 // ---- frame-to-frame track matching of a batch (match_kernels.hip: k_track_*) ------------------------
 static void trackLayout(const pli_ctx* c, pli_track_layout& L) {
   int64_t o = 0;
@@ -3070,1044 +2363,6 @@ pli_status pli_batch_track(pli_ctx* c, int32_t nframes, const void* table, const
   LAUNCH(c, "k_track_candidates", k_track_candidates, dim3(P.kpCap, nframes - 1), dim3(64), 0, T, tp, dq, dkeys, dcc);
   LAUNCH(c, "k_track_assign", k_track_assign, dim3(nframes - 1), dim3(64), (size_t)P.kpCap * 4, T, tp, dq, dkeys, dcc, (uint8_t*)track);
   LAUNCH(c, "k_track_lines", k_track_lines, dim3(nframes - 1), dim3(256), 0, T, tp, c->cfg.best_lr_matches != 0 ? 1 : 0, dl, (uint8_t*)track);
-  return PLI_OK;
-}
-
-// ---- bag of words (DBoW2 vocabulary tree) -------------------------------------
-struct pli_vocab {
-  int device = 0, k = 0, L = 0, nnodes = 0, nwords = 0;     // nnodes counts the root
-  int* childOff = nullptr; int* childList = nullptr; uint8_t* desc = nullptr; int* word = nullptr; double* weight = nullptr;
-};
-
-void pli_vocab_destroy(pli_vocab* v) {
-  if (!v) return;
-  hipSetDevice(v->device);
-  hipFree(v->childOff); hipFree(v->childList); hipFree(v->desc); hipFree(v->word); hipFree(v->weight);
-  delete v;
-}
-
-pli_status pli_vocab_create(pli_ctx* c, int32_t k, int32_t L, int32_t n, const int32_t* parent, const uint8_t* isLeaf,
-                            const uint8_t* desc, const double* weight, pli_vocab** out) {
-  CtxGuard guard__(c);
-  if (!c || !out || n < 1 || !parent || !isLeaf || !desc || !weight || k < 1 || L < 1) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  *out = nullptr;
-  const int N = n + 1;                                      // + root (TemplatedVocabulary.h:1387)
-  std::vector<int> cnt(N + 1, 0), off(N + 1, 0), list(n), word(N, -1);
-  std::vector<double> w(N, 0.0);
-  std::vector<uint8_t> d((size_t)N * 32, 0);
-  int nwords = 0;
-  for (int i = 0; i < n; ++i) {
-    const int nid = i + 1, pid = parent[i];
-    if (pid < 0 || pid >= nid) { g_err = "vocabulary: a node's parent must precede it"; return PLI_ERR_INVALID; }
-    cnt[pid]++;
-    std::memcpy(&d[(size_t)nid * 32], desc + (size_t)i * 32, 32);
-    w[nid] = weight[i];
-    if (isLeaf[i]) word[nid] = nwords++;                   // word ids in file order (:1421-1427)
-  }
-  for (int i = 0; i < N; ++i) off[i + 1] = off[i] + cnt[i];
-  std::vector<int> fill(off.begin(), off.end() - 1);
-  for (int i = 0; i < n; ++i) list[fill[parent[i]]++] = i + 1;   // children in file order (:1402)
-  for (int i = 1; i < N; ++i)
-    if (cnt[i] == 0 && word[i] < 0) { g_err = "vocabulary: a node without children is not flagged as a word"; return PLI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  std::unique_ptr<pli_vocab, void (*)(pli_vocab*)> v(new pli_vocab(), pli_vocab_destroy);
-  v->device = c->device; v->k = k; v->L = L; v->nnodes = N; v->nwords = nwords;
-  HIPCHK(hipMalloc(&v->childOff, (size_t)(N + 1) * 4));
-  HIPCHK(hipMalloc(&v->childList, (size_t)n * 4));
-  HIPCHK(hipMalloc(&v->desc, (size_t)N * 32));
-  HIPCHK(hipMalloc(&v->word, (size_t)N * 4));
-  HIPCHK(hipMalloc(&v->weight, (size_t)N * 8));
-  HIPCHK(hipMemcpy(v->childOff, off.data(), (size_t)(N + 1) * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(v->childList, list.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(v->desc, d.data(), (size_t)N * 32, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(v->word, word.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(v->weight, w.data(), (size_t)N * 8, hipMemcpyHostToDevice));
-  *out = v.release();
-  return PLI_OK;
-}
-
-pli_status pli_bow_transform(pli_ctx* c, const pli_vocab* v, const uint8_t* desc, int32_t n, int32_t levelsup, int32_t* wordId,
-                             double* weight, int32_t* nodeId) {
-  CtxGuard guard__(c);
-  if (!c || !v || n < 0 || (n > 0 && (!desc || !wordId || !weight || !nodeId))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (n == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dd = plan.add<uint8_t>((size_t)n * 32);
-  auto dwt = plan.add<double>(n);
-  auto dword = plan.add<int>(n);
-  auto dnode = plan.add<int>(n);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dd, desc, (size_t)n * 32));
-  LAUNCH(c, "k_bow_descend", k_bow_descend, dim3(n), dim3(64), 0, dd, n, v->childOff, v->childList, v->desc, v->word, v->weight,
-         v->L - levelsup, dword, dwt, dnode);
-  HIPCHK(download(c, wordId, dword, n));
-  HIPCHK(download(c, weight, dwt, n));
-  HIPCHK(download(c, nodeId, dnode, n));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-// ---- the keyframe database (include/pli_frontend.h "place-recognition queries"; kfdb_kernels.hip) ---------------
-// The device holds a CSR arena (word / value) and a slot table; the host keeps a mirror of the live vectors (for the rebuild) and of
-// the slot table.  Every mutation ends with the stream idle, so the host vectors it copied from may change afterwards.
-struct pli_kfdb {
-  pli_ctx* ctx = nullptr;
-  uint32_t* dWord = nullptr; double* dValue = nullptr; KfdbSlot* dSlots = nullptr;
-  int64_t cap = 0, used = 0, liveWords = 0;               // arena words: capacity, appended (live + holes), live
-  int slotCap = 0, live = 0, rebuilds = 0, growths = 0;
-  std::vector<KfdbSlot> slots;                             // size = the high-water mark; count < 0: free
-  std::vector<std::vector<uint32_t>> hWord; std::vector<std::vector<double>> hValue;     // per slot, live ones
-  std::set<int> freeSlots;
-  std::vector<uint8_t> qStage; std::vector<KfdbAnswer> aStage;                         // a query's upload and download
-};
-
-namespace {
-
-constexpr int64_t KFDB_FIRST_ARENA = 1 << 14;             // words; doubles from here
-constexpr int KFDB_FIRST_SLOTS = 1024;
-
-bool ascending(const uint32_t* w, int n) {
-  for (int i = 1; i < n; ++i)
-    if (w[i] <= w[i - 1]) return false;
-  return true;
-}
-
-// what the device reads for a slot: a free slot is an empty run
-KfdbSlot deviceSlot(const KfdbSlot& s) { return KfdbSlot{s.count < 0 ? 0 : s.off, s.count < 0 ? 0 : s.count, 0}; }
-
-pli_status kfdbAllocArena(pli_kfdb* db, int64_t words, uint32_t** w, double** v) {
-  *w = nullptr; *v = nullptr;
-  HIPCHK(hipMalloc(w, (size_t)words * 4));
-  hipError_t e = hipMalloc(v, (size_t)words * 8);
-  if (e != hipSuccess) { hipFree(*w); *w = nullptr; g_err = std::string("hipMalloc (keyframe database arena): ") + hipGetErrorString(e); return PLI_ERR_HIP; }
-  return PLI_OK;
-}
-
-// the slot table holds at least n entries (doubling); the whole host table goes up again after a reallocation
-pli_status kfdbSlotTable(pli_ctx* c, pli_kfdb* db, int n) {
-  if (n <= db->slotCap) return PLI_OK;
-  int cap = db->slotCap ? db->slotCap : KFDB_FIRST_SLOTS;
-  while (cap < n) cap *= 2;
-  KfdbSlot* t = nullptr;
-  HIPCHK(hipMalloc(&t, (size_t)cap * sizeof(KfdbSlot)));
-  std::vector<KfdbSlot> img(db->slots.size());
-  for (size_t i = 0; i < img.size(); ++i) img[i] = deviceSlot(db->slots[i]);
-  hipError_t e = img.empty() ? hipSuccess : hipMemcpyAsync(t, img.data(), img.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { hipFree(t); g_err = std::string("keyframe database slot table: ") + hipGetErrorString(e); return PLI_ERR_HIP; }
-  hipFree(db->dSlots);
-  db->dSlots = t; db->slotCap = cap;
-  return PLI_OK;
-}
-
-// The arena rebuilt from the host mirror, with (word, value, n) appended for `slot`: the live vectors in slot order, no holes.
-pli_status kfdbRebuild(pli_ctx* c, pli_kfdb* db, int slot, const uint32_t* word, const double* value, int n) {
-  const int64_t total = db->liveWords + n;
-  int64_t cap = db->cap;
-  while (cap < total) cap *= 2;
-  std::vector<uint32_t> w((size_t)total);
-  std::vector<double> v((size_t)total);
-  std::vector<KfdbSlot> table(db->slots);
-  if ((int)table.size() <= slot) table.resize(slot + 1, KfdbSlot{0, -1, 0});
-  int64_t at = 0;
-  for (int s = 0; s < (int)table.size(); ++s) {
-    const bool isNew = s == slot;
-    if (!isNew && table[s].count < 0) continue;
-    const int cnt = isNew ? n : table[s].count;
-    const uint32_t* sw = isNew ? word : db->hWord[s].data();
-    const double* sv = isNew ? value : db->hValue[s].data();
-    if (cnt) { std::memcpy(&w[at], sw, (size_t)cnt * 4); std::memcpy(&v[at], sv, (size_t)cnt * 8); }
-    table[s] = KfdbSlot{at, cnt, 0};
-    at += cnt;
-  }
-  uint32_t* nw = db->dWord; double* nv = db->dValue;
-  if (cap != db->cap) {
-    pli_status st = kfdbAllocArena(db, cap, &nw, &nv);
-    if (st != PLI_OK) return st;
-  }
-  pli_status st = kfdbSlotTable(c, db, (int)table.size());
-  std::vector<KfdbSlot> img(table.size());
-  for (size_t i = 0; i < img.size(); ++i) img[i] = deviceSlot(table[i]);
-  hipError_t e = hipSuccess;
-  if (st == PLI_OK) {
-    if (total) e = hipMemcpyAsync(nw, w.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && total) e = hipMemcpyAsync(nv, v.data(), (size_t)total * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(db->dSlots, img.data(), img.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { g_err = std::string("keyframe database rebuild: ") + hipGetErrorString(e); st = PLI_ERR_HIP; }
-  }
-  if (st != PLI_OK) {
-    if (cap != db->cap) { hipFree(nw); hipFree(nv); }
-    return st;
-  }
-  if (cap != db->cap) { hipFree(db->dWord); hipFree(db->dValue); db->dWord = nw; db->dValue = nv; db->cap = cap; db->growths++; }
-  db->slots.swap(table);
-  db->used = total;
-  db->rebuilds++;
-  return PLI_OK;
-}
-
-}  // namespace
-
-pli_status pli_kfdb_create(pli_ctx* c, pli_kfdb** out) {
-  CtxGuard guard__(c);
-  if (!c || !out) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  *out = nullptr;
-  HIPCHK(hipSetDevice(c->device));
-  std::unique_ptr<pli_kfdb, void (*)(pli_kfdb*)> db(new pli_kfdb(), pli_kfdb_destroy);
-  db->ctx = c;
-  pli_status st = kfdbAllocArena(db.get(), KFDB_FIRST_ARENA, &db->dWord, &db->dValue);
-  if (st != PLI_OK) return st;
-  db->cap = KFDB_FIRST_ARENA;
-  if ((st = kfdbSlotTable(c, db.get(), 1)) != PLI_OK) return st;
-  *out = db.release();
-  return PLI_OK;
-}
-
-void pli_kfdb_destroy(pli_kfdb* db) {
-  if (!db) return;
-  CtxGuard guard__(db->ctx);          // (recursive: pli_kfdb_create's failure path comes here with the lock held)
-  hipSetDevice(db->ctx->device);
-  hipFree(db->dWord); hipFree(db->dValue); hipFree(db->dSlots);
-  delete db;
-}
-
-pli_status pli_kfdb_add(pli_ctx* c, pli_kfdb* db, const uint32_t* word, const double* value, int32_t n, int32_t* slotOut) {
-  CtxGuard guard__(c);
-  if (!c || !db || db->ctx != c || !slotOut || n < 0 || (n > 0 && (!word || !value))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (n > PLI_BOW_MAX_FEATURES) { g_err = "a BowVector has at most PLI_BOW_MAX_FEATURES words"; return PLI_ERR_CAPACITY; }
-  if (!ascending(word, n)) { g_err = "word ids must ascend strictly"; return PLI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  const int slot = db->freeSlots.empty() ? (int)db->slots.size() : *db->freeSlots.begin();
-  if (2 * (db->used - db->liveWords) > db->used) {                    // holes exceed half of the arena's words
-    pli_status st = kfdbRebuild(c, db, slot, word, value, n);
-    if (st != PLI_OK) return st;
-  } else {
-    pli_status st = kfdbSlotTable(c, db, slot + 1);
-    if (st != PLI_OK) return st;
-    if (db->used + n > db->cap) {                                      // full: double, device to device
-      int64_t cap = db->cap;
-      while (cap < db->used + n) cap *= 2;
-      uint32_t* nw; double* nv;
-      if ((st = kfdbAllocArena(db, cap, &nw, &nv)) != PLI_OK) return st;
-      hipError_t e = hipSuccess;
-      if (db->used) e = hipMemcpyAsync(nw, db->dWord, (size_t)db->used * 4, hipMemcpyDeviceToDevice, c->stream);
-      if (e == hipSuccess && db->used) e = hipMemcpyAsync(nv, db->dValue, (size_t)db->used * 8, hipMemcpyDeviceToDevice, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { hipFree(nw); hipFree(nv); g_err = std::string("keyframe database growth: ") + hipGetErrorString(e); return PLI_ERR_HIP; }
-      hipFree(db->dWord); hipFree(db->dValue);
-      db->dWord = nw; db->dValue = nv; db->cap = cap; db->growths++;
-    }
-    const KfdbSlot entry{db->used, n, 0};
-    if (n) {
-      HIPCHK(hipMemcpyAsync(db->dWord + db->used, word, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(db->dValue + db->used, value, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(hipMemcpyAsync(db->dSlots + slot, &entry, sizeof(entry), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (slot == (int)db->slots.size()) db->slots.push_back(entry); else db->slots[slot] = entry;
-    db->used += n;
-  }
-  if ((int)db->hWord.size() <= slot) { db->hWord.resize(slot + 1); db->hValue.resize(slot + 1); }
-  db->hWord[slot].assign(word, word + n);
-  db->hValue[slot].assign(value, value + n);
-  db->freeSlots.erase(slot);
-  db->liveWords += n; db->live++;
-  *slotOut = slot;
-  return PLI_OK;
-}
-
-pli_status pli_kfdb_erase(pli_ctx* c, pli_kfdb* db, int32_t slot) {
-  CtxGuard guard__(c);
-  if (!c || !db || db->ctx != c) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (slot < 0 || slot >= (int)db->slots.size() || db->slots[slot].count < 0) { g_err = "the slot holds no keyframe"; return PLI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  const KfdbSlot empty{0, 0, 0};
-  HIPCHK(hipMemcpyAsync(db->dSlots + slot, &empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  db->liveWords -= db->slots[slot].count; db->live--;
-  db->slots[slot].count = -1;
-  std::vector<uint32_t>().swap(db->hWord[slot]);
-  std::vector<double>().swap(db->hValue[slot]);
-  db->freeSlots.insert(slot);
-  return PLI_OK;
-}
-
-pli_status pli_kfdb_clear(pli_ctx* c, pli_kfdb* db) {
-  CtxGuard guard__(c);
-  if (!c || !db || db->ctx != c) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  db->slots.clear(); db->hWord.clear(); db->hValue.clear(); db->freeSlots.clear();
-  db->used = db->liveWords = 0; db->live = 0;
-  return PLI_OK;
-}
-
-pli_status pli_kfdb_stats(const pli_kfdb* db, struct pli_kfdb_stats* out) {
-  if (!db || !out) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  CtxGuard guard__(db->ctx);
-  out->slot_high_water = (int32_t)db->slots.size(); out->live_keyframes = db->live;
-  out->live_words = db->liveWords; out->arena_words = db->used; out->arena_capacity = db->cap;
-  out->rebuilds = db->rebuilds; out->growths = db->growths;
-  return PLI_OK;
-}
-
-pli_status pli_kfdb_query(pli_ctx* c, pli_kfdb* db, const uint32_t* qword, const double* qvalue, int32_t nq, int32_t nslots,
-                          int32_t* common, int32_t* first, double* score) {
-  CtxGuard guard__(c);
-  if (!c || !db || db->ctx != c || nq < 0 || nslots < 0 || (nq > 0 && (!qword || !qvalue)) ||
-      (nslots > 0 && (!common || !first || !score))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nq > PLI_BOW_MAX_FEATURES) { g_err = "a BowVector has at most PLI_BOW_MAX_FEATURES words"; return PLI_ERR_CAPACITY; }
-  if (!ascending(qword, nq)) { g_err = "word ids must ascend strictly"; return PLI_ERR_INVALID; }
-  if (nslots != (int)db->slots.size()) { g_err = "nslots differs from the database's slot high-water mark"; return PLI_ERR_INVALID; }
-  if (nslots == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dq = plan.add<uint8_t>((size_t)nq * 12);           // nq values (8-byte aligned), then nq word ids: one upload
-  auto da = plan.add<KfdbAnswer>(nslots);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  db->qStage.resize((size_t)nq * 12);
-  if (nq) { std::memcpy(db->qStage.data(), qvalue, (size_t)nq * 8); std::memcpy(db->qStage.data() + (size_t)nq * 8, qword, (size_t)nq * 4); }
-  db->aStage.resize(nslots);
-  HIPCHK(upload(c, dq, (const uint8_t*)db->qStage.data(), (size_t)nq * 12));
-  uint8_t* q8 = dq;
-  const int blocks = std::min((nslots + KFDB_QUERY_BLOCK / 64 - 1) / (KFDB_QUERY_BLOCK / 64), KFDB_QUERY_MAX_BLOCKS);
-  LAUNCH(c, "k_kfdb_query", k_kfdb_query, dim3(blocks), dim3(KFDB_QUERY_BLOCK), (size_t)nq * 4, (const uint32_t*)(q8 + (size_t)nq * 8),
-         (const double*)q8, nq, db->dSlots, nslots, db->dWord, db->dValue, (KfdbAnswer*)da);
-  HIPCHK(download(c, db->aStage.data(), da, (size_t)nslots));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int s = 0; s < nslots; ++s) { common[s] = db->aStage[s].common; first[s] = db->aStage[s].first; score[s] = db->aStage[s].score; }
-  return PLI_OK;
-}
-
-// ---- MapPoint / MapLine::ComputeDistinctiveDescriptors for a batch of features (MapPoint.cc:300-365, MapLine.cc:246-317;
-// mapfeat_kernels.hip) ----
-// The host sorts the groups into the two size classes from `off` and cuts the large ones into chunks of rows; the callers' tables are
-// read and written with memcpy (any alignment).  One upload of the offsets, the class lists and the chunks, one of the descriptors,
-// one launch for the small class and two for the large one (where a class has groups), one download of best | best_median |
-// row_median.
-pli_status pli_distinctive_descriptors(pli_ctx* c, const uint8_t* desc, const int32_t* off, int32_t nfeat, int32_t* best,
-                                       int32_t* bestMedian, int32_t* rowMedian) {
-  CtxGuard guard__(c);
-  if (!c || nfeat < 0 || !off || (nfeat > 0 && !best)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  // meta: off (nfeat + 1), then nfeat entries with the small class's group ids from the front and the large class's from the back,
-  // then the large class's chunks
-  std::vector<int32_t> meta((size_t)nfeat * 2 + 1);
-  std::memcpy(meta.data(), off, ((size_t)nfeat + 1) * sizeof(int32_t));
-  if (meta[0] != 0) { g_err = "off[0] must be 0"; return PLI_ERR_INVALID; }
-  int nSmall = 0, nLarge = 0, maxN = 0;
-  for (int p = 0; p < nfeat; ++p) {
-    if (meta[p + 1] < meta[p]) { g_err = "off must not decrease"; return PLI_ERR_INVALID; }
-    const int n = meta[p + 1] - meta[p];
-    if (n > PLI_DISTINCTIVE_MAX_OBS) { g_err = "a feature has more observations than the cap of distinctive descriptors"; return PLI_ERR_CAPACITY; }
-    maxN = std::max(maxN, n);
-    int32_t* list = meta.data() + nfeat + 1;
-    if (n > DISTINCTIVE_WAVE_ROWS) list[nfeat - 1 - nLarge++] = p;
-    else if (n > 0) list[nSmall++] = p;
-  }
-  const int64_t total = meta[nfeat];
-  if (total > 0 && !desc) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nfeat == 0) return PLI_OK;
-  const size_t chunkAt = meta.size();
-  for (int g = 0; g < nLarge; ++g) {
-    const int p = meta[(size_t)nfeat + 1 + (nfeat - nLarge) + g], n = meta[p + 1] - meta[p];
-    for (int first = 0; first < n; first += DISTINCTIVE_BLOCK) { meta.push_back(p); meta.push_back(first); }
-  }
-  const int nChunks = (int)((meta.size() - chunkAt) / 2);
-  std::vector<int32_t> out((size_t)nfeat * 2 + (rowMedian ? total : 0));
-  if (total > 0) {
-    HIPCHK(hipSetDevice(c->device));
-    ScratchPlan plan;
-    auto dDesc = plan.add<uint8_t>((size_t)total * 32);
-    auto dMeta = plan.add<int32_t>(meta.size());
-    auto dOut = plan.add<int32_t>((size_t)nfeat * 2 + total);      // (the kernels always write row_median: the large class picks from it)
-    pli_status st = commitScratch(c, plan);
-    if (st != PLI_OK) return st;
-    HIPCHK(upload(c, dDesc, desc, (size_t)total * 32));
-    HIPCHK(upload(c, dMeta, (const int32_t*)meta.data(), meta.size()));
-    int32_t *dm = dMeta, *dout = dOut;
-    const int* dOff = dm;
-    const int* dList = dm + nfeat + 1;
-    int* dBest = dout;
-    int* dMed = dout + nfeat;
-    int* dRow = dout + (size_t)nfeat * 2;
-    const int perBlock = DISTINCTIVE_BLOCK / 64;
-    if (nSmall)
-      LAUNCH(c, "k_distinctive_wave", k_distinctive_wave, dim3(std::min((nSmall + perBlock - 1) / perBlock, DISTINCTIVE_MAX_BLOCKS)),
-             dim3(DISTINCTIVE_BLOCK), 0, (const uint8_t*)dDesc, dOff, dList, nSmall, dBest, dMed, dRow);
-    if (nLarge) {      // (LDS: the longest group's descriptors, 64 KiB at the cap)
-      static_assert(sizeof(DistinctiveChunk) == 2 * sizeof(int32_t), "a chunk is two ints of meta");
-      LAUNCH(c, "k_distinctive_block", k_distinctive_block, dim3(std::min(nChunks, DISTINCTIVE_MAX_BLOCKS)), dim3(DISTINCTIVE_BLOCK),
-             (size_t)maxN * 32, (const uint8_t*)dDesc, dOff, reinterpret_cast<const DistinctiveChunk*>(dm + chunkAt), nChunks, dRow);
-      LAUNCH(c, "k_distinctive_pick", k_distinctive_pick, dim3(std::min((nLarge + perBlock - 1) / perBlock, DISTINCTIVE_MAX_BLOCKS)),
-             dim3(DISTINCTIVE_BLOCK), 0, dOff, dList + (nfeat - nLarge), nLarge, (const int*)dRow, dBest, dMed);
-    }
-    HIPCHK(download(c, out.data(), dOut, out.size()));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  for (int p = 0; p < nfeat; ++p)
-    if (meta[p + 1] == meta[p]) { out[p] = -1; out[(size_t)nfeat + p] = INT32_MAX; }     // an empty group has no answer (:314-315, :327-328)
-  std::memcpy(best, out.data(), (size_t)nfeat * sizeof(int32_t));
-  if (bestMedian) std::memcpy(bestMedian, out.data() + nfeat, (size_t)nfeat * sizeof(int32_t));
-  if (rowMedian && total > 0) std::memcpy(rowMedian, out.data() + (size_t)nfeat * 2, (size_t)total * sizeof(int32_t));
-  return PLI_OK;
-}
-
-// ---- the searches of one item against a batch of keyframes (shared host part: KfBatch and the checks above) ----
-// pli_search_by_bow (fNleft < 0: F.Nleft == -1) and pli_search_by_bow_two_cameras (the frame's first fNleft rows are the left camera's)
-static pli_status searchByBow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
-                              const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
-                              const int32_t* fNode, int32_t nf, int32_t fNleft, float nnratio, int32_t checkOri, int32_t* matches,
-                              int32_t* nmatches) {
-  if (!c || nkf < 0 || nf < 0 || (nkf > 0 && (!kfOff || !nmatches)) || (nf > 0 && (!fDesc || !fNode || (checkOri && !fAngle))) ||
-      (nkf > 0 && nf > 0 && !matches)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the SearchByBoW cap", B);
-  if (st != PLI_OK) return st;
-  if (nf > PLI_BOW_MAX_FEATURES) { g_err = "the frame has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = B.total;
-  if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!nodesOk(kfNode, total, "kf_node") || !nodesOk(fNode, nf, "f_node")) return PLI_ERR_INVALID;
-  if (checkOri && (!anglesOk(kfAngle, total, "kf_angle") || !anglesOk(fAngle, nf, "f_angle"))) return PLI_ERR_INVALID;
-  if (nf == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dOff = plan.add<int>((size_t)nkf + 1);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dKa = plan.add<float>(total);
-  auto dKn = plan.add<int>(total);
-  auto dKv = plan.add<uint8_t>(total);
-  auto dFd = plan.add<uint8_t>((size_t)nf * 32);
-  auto dFa = plan.add<float>(nf);
-  auto dFn = plan.add<int>(nf);
-  auto dSn = plan.add<uint32_t>(nf);
-  auto dSi = plan.add<uint16_t>(nf);
-  auto dM = plan.add<int>((size_t)nkf * nf);
-  auto dN = plan.add<int>(nkf);
-  auto dListed = plan.add<int>(1);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  if (checkOri) HIPCHK(upload(c, dKa, kfAngle, total));
-  HIPCHK(upload(c, dKn, kfNode, total));
-  HIPCHK(upload(c, dKv, kfValid, total));
-  HIPCHK(upload(c, dFd, fDesc, (size_t)nf * 32));
-  if (checkOri) HIPCHK(upload(c, dFa, fAngle, nf));
-  HIPCHK(upload(c, dFn, fNode, nf));
-  const int sortN = pow2Ceil(nf), keyCap = pow2Ceil(B.maxNk);
-  // the frame is one table without an offset list: every feature listed in a node (no flag, no stereo table, no stat)
-  LAUNCH(c, "k_node_sort", k_node_sort, dim3(1), dim3(1024), (size_t)sortN * 6, (const int*)nullptr, nf, dFn, (const uint8_t*)nullptr, 0,
-         (const uint8_t*)nullptr, 0, sortN, dSn, dSi, dListed, (int*)nullptr);
-  const size_t lds = 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)nf * 2, 16);
-  if (fNleft < 0)
-    LAUNCH(c, "k_search_by_bow", k_search_by_bow, dim3(nkf), dim3(512), lds, dOff, dKd, dKa, dKn, dKv, dFd, dFa, dSn, dSi, dListed, nf,
-           keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
-  else
-    LAUNCH(c, "k_search_by_bow_two_cameras", k_search_by_bow_two_cameras, dim3(nkf), dim3(512), lds, dOff, dKd, dKa, dKn, dKv, dFd, dFa,
-           dSn, dSi, dListed, nf, fNleft, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
-  HIPCHK(download(c, matches, dM, (size_t)nkf * nf));
-  HIPCHK(download(c, nmatches, dN, nkf));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_search_by_bow(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
-                             const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
-                             const int32_t* fNode, int32_t nf, float nnratio, int32_t checkOri, int32_t* matches, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  return searchByBow(c, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, -1, nnratio, checkOri, matches, nmatches);
-}
-
-pli_status pli_search_by_bow_two_cameras(pli_ctx* c, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
-                                         const int32_t* kfNode, const uint8_t* kfValid, const uint8_t* fDesc, const float* fAngle,
-                                         const int32_t* fNode, int32_t nf, int32_t fNleft, float nnratio, int32_t checkOri,
-                                         int32_t* matches, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (fNleft < 0 || fNleft > nf) { g_err = "f_nleft outside [0, nf]"; return PLI_ERR_INVALID; }
-  return searchByBow(c, nkf, kfOff, kfDesc, kfAngle, kfNode, kfValid, fDesc, fAngle, fNode, nf, fNleft, nnratio, checkOri, matches, nmatches);
-}
-
-pli_status pli_search_by_bow_kf(pli_ctx* c, const uint8_t* desc1, const float* angle1, const int32_t* node1, const uint8_t* valid1,
-                                int32_t n1, int32_t nkf, const int32_t* kfOff, const uint8_t* kfDesc, const float* kfAngle,
-                                const int32_t* kfNode, const uint8_t* kfValid, float nnratio, int32_t checkOri, int32_t* matches12,
-                                int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!desc1 || !node1 || !valid1 || (checkOri && !angle1))) ||
-      (nkf > 0 && (!kfOff || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the SearchByBoW cap", B);
-  if (st != PLI_OK) return st;
-  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchByBoW cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = B.total;
-  if (total > 0 && (!kfDesc || !kfNode || !kfValid || (checkOri && !kfAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!nodesOk(kfNode, total, "kf_node") || !nodesOk(node1, n1, "node1")) return PLI_ERR_INVALID;
-  if (checkOri && (!anglesOk(kfAngle, total, "kf_angle") || !anglesOk(angle1, n1, "angle1"))) return PLI_ERR_INVALID;
-  if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
-  auto dA1 = plan.add<float>(n1);
-  auto dN1 = plan.add<int>(n1);
-  auto dV1 = plan.add<uint8_t>(n1);
-  auto dOff = plan.add<int>((size_t)nkf + 1);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dKa = plan.add<float>(total);
-  auto dKn = plan.add<int>(total);
-  auto dKv = plan.add<uint8_t>(total);
-  auto dSn = plan.add<uint32_t>(total);
-  auto dSi = plan.add<uint16_t>(total);
-  auto dListed = plan.add<int>(nkf);
-  auto dM = plan.add<int>((size_t)nkf * n1);
-  auto dN = plan.add<int>(nkf);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
-  if (checkOri) HIPCHK(upload(c, dA1, angle1, n1));
-  HIPCHK(upload(c, dN1, node1, n1));
-  HIPCHK(upload(c, dV1, valid1, n1));
-  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  if (checkOri) HIPCHK(upload(c, dKa, kfAngle, total));
-  HIPCHK(upload(c, dKn, kfNode, total));
-  HIPCHK(upload(c, dKv, kfValid, total));
-  const int sortCap = pow2Ceil(B.maxNk), keyCap = pow2Ceil(n1);
-  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)sortCap * 6, dOff, 0, dKn, dKv, 1, (const uint8_t*)nullptr, 0, sortCap,
-         dSn, dSi, dListed, (int*)nullptr);
-  LAUNCH(c, "k_search_by_bow_kf", k_search_by_bow_kf, dim3(nkf), dim3(512), 48 * 4 + (size_t)keyCap * 4 + alignUp((size_t)B.maxNk * 2, 16),
-         dD1, dA1, dN1, dV1, n1, dOff, dKd, dKa, dSn, dSi, dListed, keyCap, nnratio, checkOri ? 1 : 0, dM, dN);
-  HIPCHK(download(c, matches12, dM, (size_t)nkf * n1));
-  HIPCHK(download(c, nmatches, dN, nkf));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_search_for_triangulation(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
-                                        const uint8_t* hasMp1, const uint8_t* stereo1, int32_t n1, int32_t nkf, const int32_t* kfOff,
-                                        const pli_keypoint* kfKp, const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
-                                        const uint8_t* kfStereo, const float* F12, const float* ep, int32_t onlyStereo, int32_t coarse,
-                                        int32_t checkOri, int32_t* matches12, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || n1 < 0 || nkf < 0 || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1 || !stereo1)) ||
-      (nkf > 0 && (!kfOff || !F12 || !ep || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the SearchForTriangulation cap", B);
-  if (st != PLI_OK) return st;
-  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = B.total;
-  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp || !kfStereo)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || (checkOri && !anglesOk(kp1, n1, "kp1: angle"))) return PLI_ERR_INVALID;
-  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || (checkOri && !anglesOk(kfKp, total, "kf_kp: angle")))
-    return PLI_ERR_INVALID;
-  if (n1 == 0) { std::fill(nmatches, nmatches + nkf, 0); return PLI_OK; }
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dK1 = plan.add<pli_keypoint>(n1);
-  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
-  auto dN1 = plan.add<int>(n1);
-  auto dM1 = plan.add<uint8_t>(n1);
-  auto dS1 = plan.add<uint8_t>(n1);
-  auto dOff = plan.add<int>((size_t)nkf + 1);
-  auto dKk = plan.add<pli_keypoint>(total);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dKn = plan.add<int>(total);
-  auto dKm = plan.add<uint8_t>(total);
-  auto dKs = plan.add<uint8_t>(total);
-  auto dSn = plan.add<uint32_t>(total);
-  auto dSi = plan.add<uint16_t>(total);
-  auto dListed = plan.add<int>(nkf);
-  auto dF = plan.add<float>((size_t)nkf * 9);
-  auto dEp = plan.add<float>((size_t)nkf * 2);
-  auto dLv = plan.add<float>(2 * MAX_LEVELS);              // mvScaleFactors, then mvLevelSigma2
-  auto dStat = plan.add<int>((size_t)nkf * 32);            // per neighbour: 30 histogram bins, [30] the match counter
-  auto dM = plan.add<int>((size_t)nkf * n1);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  float hlv[2 * MAX_LEVELS] = {};
-  levelTables(c, hlv, hlv + MAX_LEVELS, nullptr);
-  HIPCHK(upload(c, dK1, kp1, n1));
-  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
-  HIPCHK(upload(c, dN1, node1, n1));
-  HIPCHK(upload(c, dM1, hasMp1, n1));
-  HIPCHK(upload(c, dS1, stereo1, n1));
-  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
-  HIPCHK(upload(c, dKk, kfKp, total));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  HIPCHK(upload(c, dKn, kfNode, total));
-  HIPCHK(upload(c, dKm, kfHasMp, total));
-  HIPCHK(upload(c, dKs, kfStereo, total));
-  HIPCHK(upload(c, dF, F12, (size_t)nkf * 9));
-  HIPCHK(upload(c, dEp, ep, (size_t)nkf * 2));
-  HIPCHK(upload(c, dLv, (const float*)hlv, 2 * MAX_LEVELS));
-  const int keyCap = pow2Ceil(B.maxNk);
-  const int perBlock = 4 * 4;                                            // k_tri_match: 4 waves x TRI_PER_WAVE features of pKF1
-  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, 0, dKn, dKm, 0, dKs, onlyStereo ? 1 : 0, keyCap,
-         dSn, dSi, dListed, dStat);
-  LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1, dS1, n1, dOff, dKk,
-         dKd, dKs, dSn, dSi, dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS, onlyStereo ? 1 : 0, coarse ? 1 : 0,
-         checkOri ? 1 : 0, dM, dStat);
-  return triEnd(c, B, n1, dK1, dKk, dOff, dStat, dM, checkOri, matches12, nmatches);
-}
-
-pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
-                                                    const uint8_t* hasMp1, int32_t n1, int32_t n1Left, int32_t nkf,
-                                                    const int32_t* kfOff, const int32_t* kfNleft, const pli_keypoint* kfKp,
-                                                    const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
-                                                    const pli_kb8_camera* camLeft, const pli_kb8_camera* camRight, const float* rel,
-                                                    int32_t onlyStereo, int32_t coarse, int32_t checkOri, int32_t* matches12,
-                                                    int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || n1 < 0 || nkf < 0 || !camLeft || !camRight || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1)) ||
-      (nkf > 0 && (!kfOff || !kfNleft || !rel || !nmatches)) || (nkf > 0 && n1 > 0 && !matches12)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (n1Left < 0 || n1Left > n1) { g_err = "n1_left outside [0, n1]"; return PLI_ERR_INVALID; }
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the SearchForTriangulation cap", B);
-  if (st != PLI_OK) return st;
-  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the SearchForTriangulation cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = B.total;
-  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!nleftOk(nkf, kfOff, kfNleft, "kf_nleft outside [0, the neighbour's rows]")) return PLI_ERR_INVALID;
-  // the gate projects with the coordinates and indexes mvLevelSigma2 by the octaves: the rule of pli_stereo_fisheye_tables
-  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || !finiteOk(kp1, n1, "kp1") ||
-      (checkOri && !anglesOk(kp1, n1, "kp1: angle")))
-    return PLI_ERR_INVALID;
-  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp") ||
-      (checkOri && !anglesOk(kfKp, total, "kf_kp: angle")))
-    return PLI_ERR_INVALID;
-  for (int64_t i = 0; i < (int64_t)nkf * 48; ++i)
-    if (!std::isfinite(rel[i])) { g_err = "rel: a relative pose is not finite"; return PLI_ERR_INVALID; }
-  std::fill(nmatches, nmatches + nkf, 0);
-  if (n1 == 0) return PLI_OK;
-  if (onlyStereo) {                                         // bStereo1 is false for every feature (:1041): :1043-1045 skips them all
-    std::fill(matches12, matches12 + (size_t)nkf * n1, -1);
-    return PLI_OK;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  ScratchPlan plan;
-  auto dK1 = plan.add<pli_keypoint>(n1);
-  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
-  auto dN1 = plan.add<int>(n1);
-  auto dM1 = plan.add<uint8_t>(n1);
-  auto dR1 = plan.add<float2>(n1);
-  auto dOff = plan.add<int>((size_t)nkf + 1);
-  auto dNl = plan.add<int>(nkf);
-  auto dKk = plan.add<pli_keypoint>(total);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dKn = plan.add<int>(total);
-  auto dKm = plan.add<uint8_t>(total);
-  auto dKr = plan.add<float2>(total);
-  auto dSn = plan.add<uint32_t>(total);
-  auto dSi = plan.add<uint16_t>(total);
-  auto dListed = plan.add<int>(nkf);
-  auto dRel = plan.add<float>((size_t)nkf * 48);
-  auto dLv = plan.add<float>(MAX_LEVELS);                  // mvLevelSigma2
-  auto dStat = plan.add<int>((size_t)nkf * 32);            // per neighbour: 30 histogram bins, [30] the match counter
-  auto dM = plan.add<int>((size_t)nkf * n1);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  float hlv[MAX_LEVELS] = {};
-  levelTables(c, nullptr, hlv, nullptr);
-  HIPCHK(upload(c, dK1, kp1, n1));
-  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
-  HIPCHK(upload(c, dN1, node1, n1));
-  HIPCHK(upload(c, dM1, hasMp1, n1));
-  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
-  HIPCHK(upload(c, dNl, kfNleft, nkf));
-  HIPCHK(upload(c, dKk, kfKp, total));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  HIPCHK(upload(c, dKn, kfNode, total));
-  HIPCHK(upload(c, dKm, kfHasMp, total));
-  HIPCHK(upload(c, dRel, rel, (size_t)nkf * 48));
-  HIPCHK(upload(c, dLv, (const float*)hlv, MAX_LEVELS));
-  Kb8 cl, cr;
-  memcpy(&cl, camLeft, sizeof(cl));
-  memcpy(&cr, camRight, sizeof(cr));
-  const int keyCap = pow2Ceil(B.maxNk);
-  const int perBlock = 4 * 4;                                            // k_tri_match_kb8: 4 waves x TRI_PER_WAVE features of pKF1
-  const int64_t nray = (int64_t)n1 + total;
-  if (!coarse)                                                           // (bCoarse: the gate, the only reader of the rays, does not run)
-    LAUNCH(c, "k_kb8_rays", k_kb8_rays, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, (const pli_keypoint*)dK1, n1, n1Left,
-           (const pli_keypoint*)dKk, (const int*)dOff, (const int*)dNl, nkf, cl, cr, (float2*)dR1, (float2*)dKr);
-  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, dOff, 0, dKn, dKm, 0, (const uint8_t*)nullptr, 0, keyCap,
-         dSn, dSi, dListed, dStat);
-  LAUNCH(c, "k_tri_match_kb8", k_tri_match_kb8, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, dK1, dD1, dN1, dM1,
-         (const float2*)dR1, n1, n1Left, dOff, (const int*)dNl, dKk, dKd, (const float2*)dKr, dSn, dSi, dListed, (const float*)dRel, cl, cr,
-         (const float*)dLv, coarse ? 1 : 0, checkOri ? 1 : 0, dM, dStat);
-  return triEnd(c, B, n1, dK1, dKk, dOff, dStat, dM, checkOri, matches12, nmatches);
-}
-
-pli_status pli_fuse_search(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf, const int32_t* kfOff,
-                           const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfUright, const float* kfPose,
-                           const uint8_t* skip, const pli_fuse_camera* cam, float th, const float* levelRatio, int32_t reprojGate,
-                           int32_t* bestIdx, int32_t* bestDist) {
-  CtxGuard guard__(c);
-  if (!c || nmp < 0 || nkf < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (nkf > 0 && (!kfOff || !kfPose)) ||
-      (nkf > 0 && nmp > 0 && !bestIdx)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the Fuse cap", B);
-  if (st != PLI_OK) return st;
-  const int64_t total = B.total;
-  if (total > 0 && (!kfKp || !kfDesc || (reprojGate && !kfUright))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!octavesOk(c, kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
-  if (nmp == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const size_t npairs = (size_t)nkf * nmp;
-  ScratchPlan plan;
-  auto dMp = plan.add<pli_fuse_point>(nmp);
-  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
-  auto dOff = plan.add<int>((size_t)nkf + 1);
-  auto dKk = plan.add<pli_keypoint>(total);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dKu = plan.add<float>(total);
-  auto dPose = plan.add<float>((size_t)nkf * 15);
-  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, npairs);
-  auto dLv = plan.add<float>(3 * MAX_LEVELS);               // level_ratio, mvScaleFactors, mvInvLevelSigma2
-  auto dCell = plan.add<int>((size_t)nkf * (GRID_COLS * GRID_ROWS + 1));
-  auto dSi = plan.add<uint16_t>(total);
-  auto dSurv = plan.add<FuseSurvivor>(npairs);
-  auto dNs = plan.add<int>(1);
-  auto dBi = plan.add<int>(npairs);
-  auto dBd = plan.addIf<int>(bestDist != nullptr, npairs);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  const LevelBlock hlv(c, levelRatio, 3);
-  HIPCHK(upload(c, dMp, mp, nmp));
-  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
-  HIPCHK(upload(c, dOff, kfOff, (size_t)nkf + 1));
-  HIPCHK(upload(c, dKk, kfKp, total));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  if (reprojGate) HIPCHK(upload(c, dKu, kfUright, total));
-  HIPCHK(upload(c, dPose, kfPose, (size_t)nkf * 15));
-  if (skip) HIPCHK(upload(c, dSkip, skip, npairs));
-  HIPCHK(upload(c, dLv, hlv.v, 3 * MAX_LEVELS));
-  HIPCHK(hipMemsetAsync(dNs, 0, sizeof(int), c->stream));
-  const float* lv = dLv;
-  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(nkf), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
-  LAUNCH(c, "k_fuse_project", k_fuse_project, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose, dSkip, *cam, th,
-         lv, c->hp.nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBd);
-  // lanes per surviving pair (Fuse: 8 measured best; the development build can run the other widths)
-  int lanes = 8;
-  if (const char* e = DEVENV("PLI_FUSE_LANES")) lanes = atoi(e);
-  const dim3 mgrid(1024);
-#define FUSE_MATCH(G)                                                                                                              \
-  LAUNCH(c, "k_fuse_match", (k_fuse_match<G, false>), mgrid, dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd, dKu, dCell, dSi, *cam,     \
-         lv + 2 * MAX_LEVELS, reprojGate ? 1 : 0, dBi, dBd)
-  if (lanes == 16) FUSE_MATCH(16);
-  else if (lanes == 64) FUSE_MATCH(64);
-  else FUSE_MATCH(8);
-#undef FUSE_MATCH
-  HIPCHK(download(c, bestIdx, dBi, npairs));
-  if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_fuse_search_two_cameras(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t nkf,
-                                       const int32_t* kfOff, const int32_t* kfNleft, const pli_keypoint* kfKp, const uint8_t* kfDesc,
-                                       const float* kfPose, const uint8_t* skip, const pli_kb8_camera* camLeft,
-                                       const pli_kb8_camera* camRight, float minX, float maxX, float minY, float maxY, float th,
-                                       const float* levelRatio, int32_t sides, int32_t* bestIdx, int32_t* bestDist) {
-  CtxGuard guard__(c);
-  if (!c || nmp < 0 || nkf < 0 || !camLeft || !camRight || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) ||
-      (nkf > 0 && (!kfOff || !kfNleft || !kfPose)) || (nkf > 0 && nmp > 0 && !bestIdx)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (sides < 1 || sides > 3) { g_err = "sides: bit 0 = left, bit 1 = right, at least one"; return PLI_ERR_INVALID; }
-  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(minX, maxX, minY, maxY)) return PLI_ERR_INVALID;
-  if (nkf == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(nkf, kfOff, "a keyframe has more features than the Fuse cap", B);
-  if (st != PLI_OK) return st;
-  const int64_t total = B.total;
-  if (total > 0 && (!kfKp || !kfDesc)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!nleftOk(nkf, kfOff, kfNleft, "kf_nleft outside [0, the keyframe's rows]")) return PLI_ERR_INVALID;
-  if (!octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
-  for (int64_t i = 0; i < (int64_t)nkf * 30; ++i)
-    if (!std::isfinite(kfPose[i])) { g_err = "kf_pose: a pose is not finite"; return PLI_ERR_INVALID; }
-  if (nmp == 0) return PLI_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const int nview = 2 * nkf;
-  const size_t npairs = (size_t)nview * nmp;
-  // view 2k = keyframe k's left rows, view 2k + 1 its right rows: one ascending offset list for k_fuse_grid and the window walk
-  std::vector<int> viewOff((size_t)nview + 1);
-  for (int k = 0; k < nkf; ++k) { viewOff[2 * k] = kfOff[k]; viewOff[2 * k + 1] = kfOff[k] + kfNleft[k]; }
-  viewOff[nview] = kfOff[nkf];
-  ScratchPlan plan;
-  auto dMp = plan.add<pli_fuse_point>(nmp);
-  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
-  auto dOff = plan.add<int>((size_t)nview + 1);
-  auto dKk = plan.add<pli_keypoint>(total);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dPose = plan.add<float>((size_t)nview * 15);
-  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, npairs);
-  auto dLv = plan.add<float>(3 * MAX_LEVELS);               // level_ratio, mvScaleFactors, mvInvLevelSigma2
-  auto dCell = plan.add<int>((size_t)nview * (GRID_COLS * GRID_ROWS + 1));
-  auto dSi = plan.add<uint16_t>(total);
-  auto dSurv = plan.add<FuseSurvivor>(npairs);
-  auto dNs = plan.add<int>(1);
-  auto dBi = plan.add<int>(npairs);
-  auto dBd = plan.addIf<int>(bestDist != nullptr, npairs);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  const LevelBlock hlv(c, levelRatio, 3);
-  HIPCHK(upload(c, dMp, mp, nmp));
-  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
-  HIPCHK(upload(c, dOff, (const int*)viewOff.data(), (size_t)nview + 1));
-  HIPCHK(upload(c, dKk, kfKp, total));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  HIPCHK(upload(c, dPose, kfPose, (size_t)nview * 15));
-  if (skip) HIPCHK(upload(c, dSkip, skip, npairs));
-  HIPCHK(upload(c, dLv, hlv.v, 3 * MAX_LEVELS));
-  HIPCHK(hipMemsetAsync(dNs, 0, sizeof(int), c->stream));
-  Kb8 cl, cr;
-  memcpy(&cl, camLeft, sizeof(cl));
-  memcpy(&cr, camRight, sizeof(cr));
-  pli_fuse_camera bounds = {};                              // only the bounds are read (IsInImage, the 64 x 48 grid)
-  bounds.min_x = minX; bounds.max_x = maxX; bounds.min_y = minY; bounds.max_y = maxY;
-  const float* lv = dLv;
-  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(nview), dim3(256), 0, dOff, dKk, bounds, dCell, dSi);
-  LAUNCH(c, "k_fuse_project_views", k_fuse_project_views, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, dMp, nmp, nkf, dPose,
-         dSkip, cl, cr, bounds, sides, th, lv, c->hp.nlevels, lv + MAX_LEVELS, dSurv, dNs, dBi, dBd);
-  LAUNCH(c, "k_fuse_match", (k_fuse_match<8, true>), dim3(1024), dim3(256), 0, dSurv, dNs, nmp, dMd, dOff, dKk, dKd,
-         (const float*)nullptr, dCell, dSi, bounds, lv + 2 * MAX_LEVELS, 1, dBi, dBd);
-  HIPCHK(download(c, bestIdx, dBi, npairs));
-  if (bestDist) HIPCHK(download(c, bestDist, dBd, npairs));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_search_by_projection_sim3(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nmp, int32_t npair,
-                                         const int32_t* kfOff, const pli_keypoint* kfKp, const uint8_t* kfDesc, const float* kfPose,
-                                         const uint8_t* skip, const uint8_t* occupied, const pli_fuse_camera* cam, float th,
-                                         const float* levelRatio, float ratioHamming, int32_t projectForm, int32_t* rowPoint,
-                                         int32_t* bestIdx, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || nmp < 0 || npair < 0 || !cam || !levelRatio || (nmp > 0 && (!mp || !mpDesc)) || (npair > 0 && (!kfOff || !kfPose || !nmatches)) ||
-      (projectForm != 0 && projectForm != 1)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
-  // bestDist <= TH_LOW * ratioHamming (ORBmatcher.cc:577): a float product, one rounding.  With no candidate the reference holds
-  // bestDist = 256, bestIdx = -1 and would write vpMatched[-1] if the product reached 256
-  const float limit = 50.0f * ratioHamming;
-  if (!std::isfinite(ratioHamming) || !(ratioHamming > 0.f) || !(limit < 256.0f)) {
-    g_err = "ratio_hamming must be finite, > 0 and 50 * ratio_hamming < 256";
-    return PLI_ERR_INVALID;
-  }
-  const int distLimit = (int)std::floor(limit);             // (float)d <= limit  <=>  d <= floor(limit) for the integers d < 256
-  if (npair == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(npair, kfOff, "a keyframe has more features than the projection search cap", B);
-  if (st != PLI_OK) return st;
-  const int64_t total = B.total;
-  if (total > 0 && (!kfKp || !kfDesc || !rowPoint)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!octavesOk(c, kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
-  std::fill(nmatches, nmatches + npair, 0);
-  if (nmp == 0 || total == 0) {
-    if (total > 0) std::fill(rowPoint, rowPoint + total, -1);
-    if (bestIdx) std::fill(bestIdx, bestIdx + (size_t)npair * nmp, -1);
-    return PLI_OK;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const int width = sim3ListWidth();
-  const size_t nslot = (size_t)npair * nmp;
-  ScratchPlan plan;
-  auto dMp = plan.add<pli_fuse_point>(nmp);
-  auto dMd = plan.add<uint8_t>((size_t)nmp * 32);
-  auto dOff = plan.add<int>((size_t)npair + 1);
-  auto dKk = plan.add<pli_keypoint>(total);
-  auto dKd = plan.add<uint8_t>((size_t)total * 32);
-  auto dPose = plan.add<float>((size_t)npair * 15);
-  auto dSkip = plan.addIf<uint8_t>(skip != nullptr, nslot);
-  auto dOcc = plan.addIf<uint8_t>(occupied != nullptr, total);
-  auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
-  auto dCell = plan.add<int>((size_t)npair * (GRID_COLS * GRID_ROWS + 1));
-  auto dSi = plan.add<uint16_t>(total);
-  auto dSurv = plan.add<FuseSurvivor>(nslot);
-  auto dKeys = plan.add<unsigned long long>(nslot * width);
-  auto dCnt = plan.add<int>(nslot);
-  auto dRow = plan.add<int>(total);
-  auto dBi = plan.addIf<int>(bestIdx != nullptr, nslot);
-  auto dNm = plan.add<int>(npair);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  const LevelBlock hlv(c, levelRatio, 2);
-  HIPCHK(upload(c, dMp, mp, nmp));
-  HIPCHK(upload(c, dMd, mpDesc, (size_t)nmp * 32));
-  HIPCHK(upload(c, dOff, kfOff, (size_t)npair + 1));
-  HIPCHK(upload(c, dKk, kfKp, total));
-  HIPCHK(upload(c, dKd, kfDesc, (size_t)total * 32));
-  HIPCHK(upload(c, dPose, kfPose, (size_t)npair * 15));
-  if (skip) HIPCHK(upload(c, dSkip, skip, nslot));
-  if (occupied) HIPCHK(upload(c, dOcc, occupied, total));
-  HIPCHK(upload(c, dLv, hlv.v, 2 * MAX_LEVELS));
-  const float* lv = dLv;
-  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(npair), dim3(256), 0, dOff, dKk, *cam, dCell, dSi);
-  LAUNCH(c, "k_sim3_project", k_sim3_project, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, dMp, nmp, npair, dPose, dSkip, *cam,
-         th, lv, c->hp.nlevels, lv + MAX_LEVELS, projectForm, dSurv, dCnt, dBi);
-  LAUNCH(c, "k_sim3_candidates", k_window_candidates<0>, dim3(1024), dim3(256), 0, dSurv, (int64_t)nslot, dMd, dOff, dKk, dKd, dCell, dSi, *cam,
-         distLimit, width, dKeys, dCnt);
-  LAUNCH(c, "k_sim3_assign", k_sim3_assign, dim3(npair), dim3(64), (size_t)B.maxNk * sizeof(int), dSurv, nmp, dMd, dOff, dKk, dKd, dOcc,
-         dCell, dSi, *cam, distLimit, width, dKeys, dCnt, dRow, dBi, dNm);
-  HIPCHK(download(c, rowPoint, dRow, total));
-  if (bestIdx) HIPCHK(download(c, bestIdx, dBi, nslot));
-  HIPCHK(download(c, nmatches, dNm, npair));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-pli_status pli_search_by_projection_reloc(pli_ctx* c, int32_t ncand, const int32_t* mpOff, const pli_fuse_point* mp,
-                                          const uint8_t* mpDesc, const float* mpAngle, const float* pose, const pli_keypoint* fKp,
-                                          const uint8_t* fDesc, int32_t nf, const uint8_t* occupied, const pli_fuse_camera* cam,
-                                          float th, const float* levelRatio, int32_t orbDist, int32_t checkOri, int32_t* rowPoint,
-                                          int32_t* bestIdx, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || ncand < 0 || nf < 0 || !cam || !levelRatio || (ncand > 0 && (!mpOff || !pose || !nmatches)) || (nf > 0 && (!fKp || !fDesc)) ||
-      (ncand > 0 && nf > 0 && !rowPoint)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
-  // bestDist <= ORBdist (ORBmatcher.cc:2403): with no candidate the reference holds bestDist = 256, bestIdx2 = -1 and would write
-  // mvpMapPoints[-1] at 256
-  if (orbDist < 0 || orbDist > 255) { g_err = "orb_dist must lie in [0, 255]"; return PLI_ERR_INVALID; }
-  if (ncand == 0) return PLI_OK;
-  KfBatch B;
-  pli_status st = kfBatch(ncand, mpOff, "a candidate lists more points than the projection search cap", B);
-  if (st != PLI_OK) return st;
-  if (nf > PLI_BOW_MAX_FEATURES) { g_err = "the frame has more features than the projection search cap"; return PLI_ERR_CAPACITY; }
-  const int64_t total = B.total;
-  if (total > 0 && (!mp || !mpDesc || (checkOri && !mpAngle))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
-  if (!octavesOk(c, fKp, nf, "f_kp")) return PLI_ERR_INVALID;
-  if (checkOri && (!anglesOk(mpAngle, total, "mp_angle") || !anglesOk(fKp, nf, "f_kp angle"))) return PLI_ERR_INVALID;
-  std::fill(nmatches, nmatches + ncand, 0);
-  if (total == 0 || nf == 0) {
-    if (nf > 0) std::fill(rowPoint, rowPoint + (size_t)ncand * nf, -1);
-    if (bestIdx) std::fill(bestIdx, bestIdx + total, -1);
-    return PLI_OK;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  const int width = sim3ListWidth();
-  const size_t nrow = (size_t)ncand * nf;
-  ScratchPlan plan;
-  auto dOff = plan.add<int>((size_t)ncand + 1);
-  auto dMp = plan.add<pli_fuse_point>(total);
-  auto dMd = plan.add<uint8_t>((size_t)total * 32);
-  auto dMa = plan.addIf<float>(checkOri != 0, total);
-  auto dPose = plan.add<float>((size_t)ncand * 15);
-  auto dFoff = plan.add<int>(2);                            // the frame as the one table of k_fuse_grid: {0, nf}
-  auto dKk = plan.add<pli_keypoint>(nf);
-  auto dKd = plan.add<uint8_t>((size_t)nf * 32);
-  auto dOcc = plan.addIf<uint8_t>(occupied != nullptr, nrow);
-  auto dLv = plan.add<float>(2 * MAX_LEVELS);               // level_ratio, mvScaleFactors
-  auto dCell = plan.add<int>(GRID_COLS * GRID_ROWS + 1);
-  auto dSi = plan.add<uint16_t>(nf);
-  auto dSurv = plan.add<FuseSurvivor>(total);
-  auto dKeys = plan.add<unsigned long long>((size_t)total * width);
-  auto dCnt = plan.add<int>(total);
-  auto dRow = plan.add<int>(nrow);
-  auto dBi = plan.addIf<int>(bestIdx != nullptr, total);
-  auto dNm = plan.add<int>(ncand);
-  st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  const LevelBlock hlv(c, levelRatio, 2);
-  const OneTableOff fOff(nf);
-  HIPCHK(upload(c, dOff, mpOff, (size_t)ncand + 1));
-  HIPCHK(upload(c, dMp, mp, total));
-  HIPCHK(upload(c, dMd, mpDesc, (size_t)total * 32));
-  if (checkOri) HIPCHK(upload(c, dMa, mpAngle, total));
-  HIPCHK(upload(c, dPose, pose, (size_t)ncand * 15));
-  HIPCHK(upload(c, dFoff, fOff.off, 2));
-  HIPCHK(upload(c, dKk, fKp, nf));
-  HIPCHK(upload(c, dKd, fDesc, (size_t)nf * 32));
-  if (occupied) HIPCHK(upload(c, dOcc, occupied, nrow));
-  HIPCHK(upload(c, dLv, hlv.v, 2 * MAX_LEVELS));
-  const float* lv = dLv;
-  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dFoff, dKk, *cam, dCell, dSi);
-  LAUNCH(c, "k_reloc_project", k_reloc_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dMp, dOff, ncand, dPose, *cam, th, lv,
-         c->hp.nlevels, lv + MAX_LEVELS, dSurv, dCnt, dBi);
-  LAUNCH(c, "k_reloc_candidates", k_window_candidates<1>, dim3(1024), dim3(256), 0, dSurv, (int64_t)total, dMd, dFoff, dKk, dKd, dCell, dSi,
-         *cam, orbDist, width, dKeys, dCnt);
-  LAUNCH(c, "k_reloc_assign", k_reloc_assign, dim3(ncand), dim3(64), (size_t)(48 + nf) * sizeof(int), dSurv, dOff, dMd, dMa, dFoff, dKk,
-         dKd, nf, dOcc, dCell, dSi, *cam, orbDist, width, checkOri ? 1 : 0, dKeys, dCnt, dRow, dBi, dNm);
-  HIPCHK(download(c, rowPoint, dRow, nrow));
-  if (bestIdx) HIPCHK(download(c, bestIdx, dBi, total));
-  HIPCHK(download(c, nmatches, dNm, ncand));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return PLI_OK;
-}
-
-constexpr int INIT_LIST_WIDTH = 16;
-
-pli_status pli_search_for_initialization(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, int32_t n1,
-                                         const float* prevMatched, const pli_keypoint* kp2, const uint8_t* desc2, int32_t n2,
-                                         float minX, float maxX, float minY, float maxY, int32_t windowSize, float nnratio,
-                                         int32_t checkOri, int32_t* matches12, int32_t* raw12, int32_t* nmatches) {
-  CtxGuard guard__(c);
-  if (!c || n1 < 0 || n2 < 0 || !nmatches || (n1 > 0 && (!kp1 || !desc1 || !prevMatched || !matches12)) || (n2 > 0 && (!kp2 || !desc2))) {
-    g_err = "bad argument"; return PLI_ERR_INVALID;
-  }
-  if (windowSize < 0) { g_err = "window_size must not be negative"; return PLI_ERR_INVALID; }
-  if (!std::isfinite(nnratio) || !(nnratio > 0.f)) { g_err = "nnratio must be finite and positive"; return PLI_ERR_INVALID; }
-  if (!imageBoundsOk(minX, maxX, minY, maxY)) return PLI_ERR_INVALID;
-  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "F1 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
-  if (n2 > PLI_BOW_MAX_FEATURES) { g_err = "F2 has more features than the initialisation search cap"; return PLI_ERR_CAPACITY; }
-  if (!octavesOk(c, kp1, n1, "kp1") || !octavesOk(c, kp2, n2, "kp2")) return PLI_ERR_INVALID;
-  if (checkOri && (!anglesOk(kp1, n1, "kp1 angle") || !anglesOk(kp2, n2, "kp2 angle"))) return PLI_ERR_INVALID;
-  for (int64_t i = 0; i < 2 * (int64_t)n1; ++i)
-    if (std::isnan(prevMatched[i])) { g_err = "prev_matched holds a NaN"; return PLI_ERR_INVALID; }
-  *nmatches = 0;
-  if (n1 == 0 || n2 == 0) {
-    std::fill(matches12, matches12 + n1, -1);
-    if (raw12) std::fill(raw12, raw12 + n1, -1);
-    return PLI_OK;
-  }
-  HIPCHK(hipSetDevice(c->device));
-  // The limit of the per-i1 candidate lists.  A candidate at distance d can bear on a decision in two ways only.  As a best: :760
-  // needs d <= TH_LOW.  As a second-best that rejects a best b <= TH_LOW: :762 rejects when b >= (float)d * nnratio, and with
-  // b <= 50 that needs (float)d * nnratio <= 50.0f, which is monotone in d for nnratio > 0.  A candidate above both bounds is
-  // never a best that is accepted (if it were the minimum, every other candidate would be above TH_LOW too) and as a second-best
-  // it behaves like INT_MAX: (float)d * nnratio > 50.0f >= b accepts, as does a missing second-best.  Whether it is left out by
-  // vMatchedDistance (:745) changes nothing either, and it never enters vMatchedDistance, which only holds accepted distances.
-  // So the lists keep d <= max(TH_LOW, the largest d with (float)d * nnratio <= 50.0f): 55 for 0.9.
-  int distLimit = 50;
-  while (distLimit < 256 && (float)(distLimit + 1) * nnratio <= 50.0f) ++distLimit;
-  const int width = INIT_LIST_WIDTH;
-  ScratchPlan plan;
-  auto dOff = plan.add<int>(2);                             // F2 as the one table of k_fuse_grid: {0, n2}
-  auto dK1 = plan.add<pli_keypoint>(n1);
-  auto dD1 = plan.add<uint8_t>((size_t)n1 * 32);
-  auto dPrev = plan.add<float>((size_t)n1 * 2);
-  auto dK2 = plan.add<pli_keypoint>(n2);
-  auto dD2 = plan.add<uint8_t>((size_t)n2 * 32);
-  auto dCell = plan.add<int>(GRID_COLS * GRID_ROWS + 1);
-  auto dSi = plan.add<uint16_t>(n2);
-  auto dKeys = plan.add<unsigned long long>((size_t)n1 * width);
-  auto dCnt = plan.add<int>(n1);
-  auto dM12 = plan.add<int>(n1);
-  auto dRaw = plan.addIf<int>(raw12 != nullptr, n1);
-  auto dNm = plan.add<int>(1);
-  pli_status st = commitScratch(c, plan);
-  if (st != PLI_OK) return st;
-  pli_fuse_camera cam = {};                                 // only the bounds are read (the 64 x 48 grid)
-  cam.min_x = minX; cam.max_x = maxX; cam.min_y = minY; cam.max_y = maxY;
-  const OneTableOff off2(n2);
-  HIPCHK(upload(c, dOff, off2.off, 2));
-  HIPCHK(upload(c, dK1, kp1, n1));
-  HIPCHK(upload(c, dD1, desc1, (size_t)n1 * 32));
-  HIPCHK(upload(c, dPrev, prevMatched, (size_t)n1 * 2));
-  HIPCHK(upload(c, dK2, kp2, n2));
-  HIPCHK(upload(c, dD2, desc2, (size_t)n2 * 32));
-  const float radius = (float)windowSize;                   // const float& r of GetFeaturesInArea takes the int (:726)
-  LAUNCH(c, "k_fuse_grid", k_fuse_grid, dim3(1), dim3(256), 0, dOff, dK2, cam, dCell, dSi);
-  LAUNCH(c, "k_init_candidates", k_init_candidates, dim3((unsigned)std::min(1024, (n1 + 3) / 4)), dim3(256), 0, dK1, dD1, n1, dPrev, dK2, dD2,
-         dCell, dSi, cam, radius, distLimit, width, dKeys, dCnt);
-  LAUNCH(c, "k_init_assign", k_init_assign, dim3(1), dim3(64), (size_t)(48 + n2) * sizeof(int) + (size_t)n1 * sizeof(short), dK1, dD1, n1,
-         dPrev, dK2, dD2, n2, dCell, dSi, cam, radius, distLimit, width, nnratio, checkOri ? 1 : 0, dKeys, dCnt, dM12, dRaw, dNm);
-  HIPCHK(download(c, matches12, dM12, n1));
-  if (raw12) HIPCHK(download(c, raw12, dRaw, n1));
-  HIPCHK(download(c, nmatches, dNm, 1));
-  HIPCHK(hipStreamSynchronize(c->stream));
   return PLI_OK;
 }
 

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 W, H = 752, 480
 NLEVELS = 8
 CAP = 8192                                                # PLI_BOW_MAX_FEATURES
-LIST_WIDTH = 16                                           # the candidate list of one i1 (INIT_LIST_WIDTH, pli_capi.hip)
+LIST_WIDTH = 16                                           # the candidate list of one i1 (INIT_LIST_WIDTH, match_capi.hip)
 
 
 @pytest.fixture(scope="module")

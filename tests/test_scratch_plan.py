@@ -1,6 +1,7 @@
 """pli_slam_amd/csrc/scratch_plan.hpp, the plan from which the matcher entry points carve their device scratch, is plain C++: it is
 compiled here with g++ (no HIP, no GPU) under AddressSanitizer and UBSan, bound to a host buffer of exactly plan.bytes() bytes, and every
-block is written through its own pointer for its declared length."""
+block is written through its own pointer for its declared length.  The copies that a plan records for its inputs (in / inOpt) are
+carried out with memcpy from sources of exactly the declared length, so the sanitizer guards both ends of every copy."""
 import os
 import subprocess
 
@@ -96,6 +97,49 @@ int main() {
     CHECK(s == nullptr && cs == nullptr && w == base + 512 && (uint8_t*)pa == base && (uint8_t*)pz == base + 512 + 1024);
     w[999] = 1; *pz = 2;
     std::free(base);
+  }
+  {   // inputs declared with their host source: the recorded copies, carried out with memcpy from sources of exactly the declared length
+    static int dummy = 0;
+    for (size_t n : {0, 1, 255, 256, 257, 15360}) {
+      ScratchPlan plan;
+      std::vector<uint8_t> s1(n, 0x11); std::vector<uint16_t> s2(n, 0x2222); std::vector<int> s4(n, 0x44444444);
+      std::vector<double> s8(n, 8.0); std::vector<Kp> s28(n, Kp{{1, 2, 3, 4, 5}, 6, 7});
+      auto a = plan.in(s1.data(), n);
+      auto out = plan.add<int>(n);                         // a block without a source between the inputs
+      auto b = plan.in(s2.data(), n);
+      auto c = plan.inOpt(s4.data(), n);
+      auto plain = plan.in<double>(nullptr, n);            // a null source: a plain block
+      auto d = plan.in(s8.data(), n);
+      auto absent = plan.inOpt<Kp>(nullptr, n);
+      auto e = plan.inOpt(s28.data(), n);
+      auto zero = plan.in(&dummy, 0);                      // a source, but nothing to copy
+      CHECK(a.n == n && out.n == n && b.n == n && plain.n == n && d.n == n && zero.n == 0);       // a block reports its declared count
+      CHECK(c.n == (c.present ? n : 0) && e.n == (e.present ? n : 0) && absent.n == 0);
+      CHECK(c.present == (n > 0) && e.present == (n > 0) && !absent.present && a.present && plain.present && zero.present);
+      // the list: the blocks with a source and n > 0, in the order of declaration, each for its block's declared bytes at its block
+      const struct { size_t off, bytes; const void* src; } want[5] = {{a.off, a.n * 1, s1.data()}, {b.off, b.n * 2, s2.data()},
+          {c.off, c.n * 4, s4.data()}, {d.off, d.n * 8, s8.data()}, {e.off, e.n * 28, s28.data()}};
+      const auto& copies = plan.copies();
+      CHECK(copies.size() == (n ? 5u : 0u));                // a null source or n == 0 records nothing
+      for (size_t i = 0; i < copies.size() && i < 5; ++i) {
+        CHECK(copies[i].src == want[i].src && copies[i].bytes == want[i].bytes);
+        CHECK(copies[i].off >= want[i].off && copies[i].off + copies[i].bytes <= want[i].off + want[i].bytes);
+        CHECK(i == 0 || copies[i].off >= copies[i - 1].off + copies[i - 1].bytes);
+      }
+      uint8_t* base = static_cast<uint8_t*>(std::aligned_alloc(256, plan.bytes()));       // exactly bytes(): ASan guards both ends
+      plan.bind(base);
+      for (const auto& k : copies) std::memcpy(plan.base() + k.off, k.src, k.bytes);
+      uint8_t* pa = a; uint16_t* pb = b; int* pc = c; double* pp = plain; double* pd = d; Kp* pe = e; Kp* pn = absent; int* pz = zero;
+      const Kp* cpn = absent;
+      CHECK(pa && pb && pp && pd && pz && (int*)out != nullptr);                      // in: the pointer is always valid
+      CHECK(pn == nullptr && cpn == nullptr && (pc != nullptr) == (n > 0) && (pe != nullptr) == (n > 0));
+      if (n) {
+        CHECK(!std::memcmp(pa, s1.data(), n) && !std::memcmp(pb, s2.data(), n * 2) && !std::memcmp(pc, s4.data(), n * 4));
+        CHECK(!std::memcmp(pd, s8.data(), n * 8) && !std::memcmp(pe, s28.data(), n * 28));
+        CHECK(pe[n - 1].b == 7 && (uint8_t*)(pe + n) <= base + plan.bytes());
+      }
+      std::free(base);
+    }
   }
   if (!fails) std::printf("scratch plan: ok\n");
   return fails ? 1 : 0;

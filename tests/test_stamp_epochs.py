@@ -2,7 +2,7 @@
 
 The tile relaxation keeps two planes of ROUND STAMPS per image slot (rgDirty, rgLost: one word per region id).  They are not cleared
 per call: a call stamps with `base + round`, and the base moves up with every call of the context past every round a call can write
-(pli_capi.hip: pli_ctx::lineStampNext).  A stale stamp that matched a round of a later call would regrow or carry the wrong regions,
+(capi_host.hpp: pli_ctx::lineStampNext).  A stale stamp that matched a round of a later call would regrow or carry the wrong regions,
 so every test here reuses ONE context for a sequence of calls whose images change under the slots — photographs and the hostile
 images that need many rounds among them — and compares every call, byte for byte, with the table a FRESH context writes for the same
 images, and one record per call with the oracle.
