@@ -981,6 +981,76 @@ pli_status pli_kfdb_query(pli_ctx* ctx, pli_kfdb* db, const uint32_t* qword, con
 pli_status pli_distinctive_descriptors(pli_ctx* ctx, const uint8_t* desc, const int32_t* off, int32_t nfeat, int32_t* best,
                                        int32_t* best_median, int32_t* row_median);
 
+/* --- Local-map tracking: the front of Tracking::SearchLocalPointsAndLines (Tracking.cc:3809-3883) for a frame of one camera ---
+ * pli_search_local_points covers :3809-3855 in one call: Frame::isInFrustum (Frame.cc:585-647, the branch Nleft == -1) of every
+ * local map point, the queries of ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) as
+ * ORBmatcher.cc:53-73 builds them, and that search (pli_search_local_map's kernels) on the queries where the device left them.
+ * mp / mp_desc: the nq points of mvpLocalMapPoints in list order as pli_fuse_point rows (valid == 0: skipped at :3813-3816,
+ * mnLastFrameSeen == mnId or isBad(); also a point whose max_dist is not finite and positive) and their GetDescriptor() rows.
+ * valid == PLI_LOCAL_STORED_VIEW: a point that :3813 skips (mnLastFrameSeen == mnId), is not bad, and still has mbTrackInView set
+ * from an earlier frame.  The skip only bypasses isInFrustum; SearchByProjection at :3854 walks the whole list and tests
+ * mbTrackInView (ORBmatcher.cc:53), so the reference searches such a point, in its list position, with the fields it holds.  This
+ * happens in ordinary tracking: for a frame of one camera TrackWithMotionModel's outlier loop (:2996-3004) sets mnLastFrameSeen
+ * and resets only mbTrackInViewR, and the point's row is NULL by :3770.  Such a row carries the stored fields instead of world
+ * coordinates: pos = {mTrackProjX, mTrackProjY, mTrackProjXR}, normal = {mTrackDepth, mTrackViewCos, (float)mnTrackScaleLevel}
+ * (the level in [0, orb_nlevels), else PLI_ERR_INVALID); the distance fields are not read.  Its query is built from them as from
+ * a record (the far-point gate included), its view record is all zero and it does not count in *n_in_view.
+ * pose: 15 floats, mRcw row major, mtcw, mOw (the stored values).  cam: fx .. cy of mpCamera, mbf, mnMinX .. mnMaxY.
+ * viewing_cos_limit: 0.5 at :3818.  th, far_points, th_far, nnratio: the arguments of :3854 and of ORBmatcher(0.8).
+ * level_ratio: as for pli_fuse_search.  cur_*: the frame's mvKeysUn, mDescriptors, mvuRight and "holds a map point with
+ * Observations() > 0" as for pli_search_local_map (cur_occupied may be NULL).
+ * The arithmetic is the reference's, in its order: mRcw*P + mtcw as a cv::Mat product (double accumulation, one rounding),
+ * cv::norm and Mat::dot in double, the rest float and nothing fused.  The image gate is the one written at :607-610,
+ * u < mnMinX || u > mnMaxX: closed at mnMaxX / mnMaxY (KeyFrame::IsInImage of pli_fuse_search is open there), and a NaN projection
+ * (PcZ == 0 with PcX == 0) passes it.  The viewing angle is viewCos = (float)(PO.dot(Pn) / dist) < viewing_cos_limit, compared in
+ * float (pli_fuse_search compares the dot product with 0.5 * dist in double).
+ * view[i]: what the call leaves in the map point.  A skipped point: all zero.  Otherwise proj_x / proj_y = -1 until the point
+ * passes the image gate and mTrackProjX / Y from there on, also where a later gate refuses it (:612-613); in_view = mbTrackInView;
+ * proj_xr (mTrackProjXR), depth (mTrackDepth = cv::norm(Pc)), level (mnTrackScaleLevel) and view_cos (mTrackViewCos) are written
+ * only with in_view and are 0 otherwise (the reference leaves the fields as they were).
+ * The query of point i is valid when in_view and not (far_points && depth > th_far); radius = r * mvScaleFactors[level] with
+ * r = view_cos > 0.998 ? 2.5 : 4.0 (the float against the double constant), times th when th != 1.0; octaves [level - 1, level].
+ * A point in view takes part whatever its Observations(): as for pli_search_local_map the row it takes is closed to the points
+ * behind it, so a caller with points of no observations in view replays that case itself (the adapter refuses it).
+ * best_idx2[i]: the keypoint point i took, or -1.  A query whose projection is NaN takes no keypoint: every distance test against
+ * it is false (the device closes such a query when it writes it; the view record keeps the NaN).  *n_in_view = nToMatch of :3821.
+ * The search runs whatever it is: the reference searches only when nToMatch > 0 (:3829), so with *n_in_view == 0 a caller that
+ * passed stored views ignores best_idx2 and *nmatches (the adapter does).
+ * *nmatches = the reference's return value.  Frames above 15360 keypoints take the ordered scan, as pli_search_local_map.
+ * PLI_ERR_INVALID before any device call: a null context, camera, pose or level_ratio, negative counts, null tables with rows
+ * present, empty image bounds, a decreasing level_ratio, an octave outside [0, orb_nlevels).  nq == 0 and ncur == 0 are valid. */
+#define PLI_LOCAL_STORED_VIEW 2
+typedef struct pli_local_view {   /* 32 bytes */
+  float proj_x, proj_y, proj_xr, depth, view_cos;
+  int32_t level, in_view, pad;
+} pli_local_view;
+pli_status pli_search_local_points(pli_ctx* ctx, const pli_fuse_point* mp, const uint8_t* mp_desc, int32_t nq, const float* pose,
+                                   const pli_fuse_camera* cam, float viewing_cos_limit, float th, int32_t far_points,
+                                   float th_far, float nnratio, const float* level_ratio, const pli_keypoint* cur_kp,
+                                   const uint8_t* cur_desc, const float* cur_uright, const uint8_t* cur_occupied, int32_t ncur,
+                                   pli_local_view* view, int32_t* best_idx2, int32_t* n_in_view, int32_t* nmatches);
+
+/* pli_search_local_lines covers :3862-3883: Frame::isInFrustum_l (Frame.cc:661-701) of every local map line, the ordered list
+ * mvpLocalMapLines_InFrustum, and match(mvpLocalMapLines_InFrustum, mCurrentFrame, nnr, matches_12) (LineMatcher.cpp:161, the
+ * one-way matchNNR of pli_match_nnr) on the descriptors of the lines in view.
+ * sp: nl x 3 floats, the start point of GetWorldPos() cast to float (Converter::toCvMat of sep.head(3)); valid[i] == 0: skipped at
+ * :3865-3868; desc: the GetDescriptor() rows; pose, cam as above (bf is not read); cur_desc: the n2 rows of mDescriptors_Line.
+ * Per line: mRcw*sp + mtcw, out if PcZ < 0, invz = 1.0f / PcZ, u = fx*PcX*invz + cx evaluated left to right (NOT Pinhole::project's
+ * fx*x/z + cx: the two round differently), the closed image gate of :687-690 (a NaN passes).
+ * in_view[i] (nl ints) = mbTrackInView; proj_s[i] (nl x 2 floats) = mTrackProjsX / Y where in view, else 0 (the reference leaves
+ * them as they were); in_frustum[k] = the list index of the k-th line in view, k < *n_in_view (room for nl); matches_12[k] = the
+ * frame line matched to it or -1 (room for nl; the rows from *n_in_view on are not written).  *n_in_view = nToMatch,
+ * *nmatches = match()'s return value; n2 < 2 matches nothing, as pli_match_nnr.  The list's length decides the match's launch, so
+ * the call reads the count back once between its two halves.
+ * NOT covered, and left to the caller on the fields as they stand: the reference never writes mTrackProjeX / mTrackProjeY - it
+ * reads them uninitialised for mnTrackangle (Frame.cc:698) and for the position gate of Tracking.cc:3908-3911 - so mnTrackangle
+ * and the loop :3886-3919 (mvDisparity_l, Observations(), the position gate, mvpMapLines[i2] = pML) stay on the host.
+ * PLI_ERR_INVALID before any device call: a null context, camera or pose, negative counts, null tables with rows present. */
+pli_status pli_search_local_lines(pli_ctx* ctx, const float* sp, const uint8_t* valid, const uint8_t* desc, int32_t nl,
+                                  const float* pose, const pli_fuse_camera* cam, const uint8_t* cur_desc, int32_t n2, float nnr,
+                                  int32_t* in_view, float* proj_s, int32_t* in_frustum, int32_t* matches_12,
+                                  int32_t* n_in_view, int32_t* nmatches);
+
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (bench.py / tests only).                                */
 /* ------------------------------------------------------------------------ */

@@ -348,6 +348,37 @@ class Frontend {
     check(pli_match_nnr(ctx_, desc1, n1, desc2, n2, nnr, matches12.data(), &n));
     return n;
   }
+  // Tracking.cc:3809-3855 for a frame of one camera (include/pli_frontend.h pli_search_local_points): Frame::isInFrustum of every
+  // local map point, the queries of ORBmatcher.cc:53-73 and the search, projection and queries on the device.  view[i]: what the
+  // call leaves in point i; bestIdx2[i]: the keypoint it took or -1; nInView = nToMatch.  Returns the reference's nmatches.
+  int searchLocalPoints(const std::vector<pli_fuse_point>& mp, const uint8_t* mpDesc, const float pose[15], const pli_fuse_camera& cam,
+                        float viewingCosLimit, float th, bool farPoints, float thFar, float nnratio,
+                        const std::vector<float>& levelRatio, const std::vector<pli_keypoint>& cur, const uint8_t* curDesc,
+                        const float* curURight, const uint8_t* curOccupied, std::vector<pli_local_view>& view,
+                        std::vector<int>& bestIdx2, int& nInView) {
+    view.assign(mp.size(), pli_local_view{});
+    bestIdx2.assign(mp.size(), -1);
+    int32_t n = 0, nv = 0;
+    check(pli_search_local_points(ctx_, mp.data(), mpDesc, (int)mp.size(), pose, &cam, viewingCosLimit, th, farPoints ? 1 : 0, thFar,
+                                  nnratio, levelRatio.data(), cur.data(), curDesc, curURight, curOccupied, (int)cur.size(),
+                                  view.data(), bestIdx2.data(), &nv, &n));
+    nInView = nv;
+    return n;
+  }
+  // Tracking.cc:3862-3883 (include/pli_frontend.h pli_search_local_lines): Frame::isInFrustum_l of every local map line, the list
+  // mvpLocalMapLines_InFrustum (inFrustum[k] = list index of its k-th line) and match(..., nnr, matches12) on it.  sp: nl x 3.
+  int searchLocalLines(const std::vector<float>& sp, const std::vector<uint8_t>& valid, const uint8_t* desc, const float pose[15],
+                       const pli_fuse_camera& cam, const uint8_t* curDesc, int n2, float nnr, std::vector<int>& inView,
+                       std::vector<float>& projS, std::vector<int>& inFrustum, std::vector<int>& matches12) {
+    const size_t nl = valid.size();
+    if (sp.size() != 3 * nl) throw std::logic_error("searchLocalLines: three coordinates per line");
+    inView.assign(nl, 0); projS.assign(2 * nl, 0.0f); inFrustum.assign(nl, -1); matches12.assign(nl, -1);
+    int32_t n = 0, nv = 0;
+    check(pli_search_local_lines(ctx_, sp.data(), valid.data(), desc, (int)nl, pose, &cam, curDesc, n2, nnr, inView.data(),
+                                 projS.data(), inFrustum.data(), matches12.data(), &nv, &n));
+    inFrustum.resize(nv); matches12.resize(nv);
+    return n;
+  }
   // Frame::ComputeStereoFishEyeMatches Frame.cc:1577-1618 on the Frame's own tables (mvKeys / mDescriptors / monoLeft, ...);
   // fills mvLeftToRightMatch, mvRightToLeftMatch, mvDepth, mvStereo3Dpoints (x, y, z per left keypoint) and returns nMatches
   int stereoFishEye(const std::vector<pli_keypoint>& kpLeft, const uint8_t* descLeft, int monoLeft,

@@ -31,6 +31,9 @@ PROJ_QUERY_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("ur", 
 
 FUSE_POINT_DT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist_inv", "<f4"), ("max_dist_inv", "<f4"),
                           ("max_dist", "<f4"), ("valid", "<i4")])
+LOCAL_VIEW_DT = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"),
+                          ("level", "<i4"), ("in_view", "<i4"), ("pad", "<i4")])           # pli_local_view
+LOCAL_STORED_VIEW = 2                 # PLI_LOCAL_STORED_VIEW: a FUSE_POINT_DT row that carries the fields a skipped point still holds
 
 PLI_OK = 0
 ERRORS = {-1: "PLI_ERR_INVALID", -2: "PLI_ERR_EMPTY_IMAGE", -3: "PLI_ERR_CAPACITY", -4: "PLI_ERR_HIP",
@@ -228,6 +231,13 @@ _PROTOS = {
     "pli_search_for_initialization": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_float,
                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pli_search_local_points": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(FuseCamera),
+                                            C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pli_search_local_lines": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.POINTER(FuseCamera), C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pli_prof_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "pli_prof_reset": (C.c_int32, [C.c_void_p]),
     "pli_prof_report": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int64]),

@@ -202,6 +202,39 @@ pli_status pli_hamming_knn2(pli_ctx* c, const uint8_t* q, int32_t nq, const uint
   return PLI_OK;
 }
 
+// knnMatch(k = 2), the ratio test and (mutual) the check the other way, on tables that are already on the device
+struct MatchTables {
+  ScratchBlock<uint8_t> d1, d2;
+  ScratchBlock<int> i1, ds1, i2, ds2, m12, m21, count;
+};
+// (d1 / d2 null: a block that a kernel fills)
+static MatchTables matchTables(ScratchPlan& plan, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2) {
+  MatchTables T;
+  T.d1 = plan.in(d1, (size_t)n1 * 32);
+  T.d2 = plan.in(d2, (size_t)n2 * 32);
+  T.i1 = plan.add<int>((size_t)n1 * 2);                  // k_knn2: two ints per query, the indices ...
+  T.ds1 = plan.add<int>((size_t)n1 * 2);                 // ... and the distances
+  T.i2 = plan.add<int>((size_t)n2 * 2);
+  T.ds2 = plan.add<int>((size_t)n2 * 2);
+  T.m12 = plan.add<int>(n1);
+  T.m21 = plan.add<int>(n2);
+  T.count = plan.add<int>(1);
+  return T;
+}
+// the first n1 rows of T.d1 (n1 > 0, at most as declared) against T.d2
+static pli_status matchLaunch(pli_ctx* c, const MatchTables& T, int32_t n1, int32_t n2, float nnr, bool mutual) {
+  HIPCHK(hipMemsetAsync(T.count, 0, 4, c->stream));
+  LAUNCH(c, "k_knn2", k_knn2, dim3(n1), dim3(64), 0, T.d1, n1, T.d2, n2, T.i1, T.ds1);
+  LAUNCH(c, "k_ratio", k_ratio, dim3((n1 + 255) / 256), dim3(256), 0, T.i1, T.ds1, n1, n2, nnr, T.m12);
+  const bool lr = mutual;
+  if (lr && n2 > 0) {
+    LAUNCH(c, "k_knn2", k_knn2, dim3(n2), dim3(64), 0, T.d2, n2, T.d1, n1, T.i2, T.ds2);
+    LAUNCH(c, "k_ratio", k_ratio, dim3((n2 + 255) / 256), dim3(256), 0, T.i2, T.ds2, n2, n1, nnr, T.m21);
+  }
+  LAUNCH(c, "k_mutual", k_mutual, dim3((n1 + 255) / 256), dim3(256), 0, T.m12, (lr && n2 > 0) ? (int*)T.m21 : (int*)nullptr, n1, T.count);
+  return PLI_OK;
+}
+
 static pli_status matchDescriptors(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
                                    bool mutual, int32_t* m12, int32_t* nmatches) {
   if (!c || n1 < 0 || n2 < 0 || (n1 > 0 && (!d1 || !m12)) || (n2 > 0 && !d2)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
@@ -209,28 +242,12 @@ static pli_status matchDescriptors(pli_ctx* c, const uint8_t* d1, int32_t n1, co
   if (n1 == 0) return PLI_OK;
   HIPCHK(hipSetDevice(c->device));
   ScratchPlan plan;
-  auto dd1 = plan.in(d1, (size_t)n1 * 32);
-  auto dd2 = plan.in(d2, (size_t)n2 * 32);
-  auto i1 = plan.add<int>((size_t)n1 * 2);               // k_knn2: two ints per query, the indices ...
-  auto ds1 = plan.add<int>((size_t)n1 * 2);              // ... and the distances
-  auto i2 = plan.add<int>((size_t)n2 * 2);
-  auto ds2 = plan.add<int>((size_t)n2 * 2);
-  auto dm12 = plan.add<int>(n1);
-  auto dm21 = plan.add<int>(n2);
-  auto dcount = plan.add<int>(1);
+  const MatchTables T = matchTables(plan, d1, n1, d2, n2);
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  HIPCHK(hipMemsetAsync(dcount, 0, 4, c->stream));
-  LAUNCH(c, "k_knn2", k_knn2, dim3(n1), dim3(64), 0, dd1, n1, dd2, n2, i1, ds1);
-  LAUNCH(c, "k_ratio", k_ratio, dim3((n1 + 255) / 256), dim3(256), 0, i1, ds1, n1, n2, nnr, dm12);
-  const bool lr = mutual;
-  if (lr && n2 > 0) {
-    LAUNCH(c, "k_knn2", k_knn2, dim3(n2), dim3(64), 0, dd2, n2, dd1, n1, i2, ds2);
-    LAUNCH(c, "k_ratio", k_ratio, dim3((n2 + 255) / 256), dim3(256), 0, i2, ds2, n2, n1, nnr, dm21);
-  }
-  LAUNCH(c, "k_mutual", k_mutual, dim3((n1 + 255) / 256), dim3(256), 0, dm12, (lr && n2 > 0) ? (int*)dm21 : (int*)nullptr, n1, dcount);
-  HIPCHK(download(c, m12, dm12));
-  return fetchCount(c, dcount, nmatches);
+  if ((st = matchLaunch(c, T, n1, n2, nnr, mutual)) != PLI_OK) return st;
+  HIPCHK(download(c, m12, T.m12));
+  return fetchCount(c, T.count, nmatches);
 }
 
 pli_status pli_match_lines(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_t* d2, int32_t n2, float nnr,
@@ -250,6 +267,50 @@ pli_status pli_match_nnr(pli_ctx* c, const uint8_t* d1, int32_t n1, const uint8_
 // assignment); larger ones the ordered assignment alone, owner table in global memory, which scans the frame per query.
 constexpr int PROJ_LDS_KEYPOINTS = 15360;
 
+// The tables of one search: the queries and their descriptors, the frame, the results (q null: a kernel writes the queries)
+struct ProjTables {
+  ScratchBlock<pli_proj_query> q; ScratchBlock<uint8_t> qd;
+  ScratchBlock<pli_keypoint> k; ScratchBlock<uint8_t> dsc; ScratchBlock<float> u; ScratchBlock<uint8_t> occ;
+  ScratchBlock<int> own, best, raw; ScratchBlock<unsigned long long> keys; ScratchBlock<int> cc, cnt;
+};
+static ProjTables projTables(ScratchPlan& plan, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq, const pli_keypoint* kp,
+                             const uint8_t* desc, const float* uright, const uint8_t* occupied, int32_t ncur) {
+  const bool ownerInLds = ncur <= PROJ_LDS_KEYPOINTS;
+  ProjTables T;
+  T.q = plan.in(q, nq);
+  T.qd = plan.in(qdesc, (size_t)nq * 32);
+  T.k = plan.in(kp, ncur);
+  T.dsc = plan.in(desc, (size_t)ncur * 32);
+  T.u = plan.in(uright, ncur);
+  T.own = plan.add<int>(ownerInLds ? 0 : ncur);
+  T.best = plan.add<int>(nq);
+  T.raw = plan.add<int>(nq);
+  T.occ = plan.inOpt(occupied, ncur);
+  T.keys = plan.add<unsigned long long>(ownerInLds ? (size_t)nq * PROJ_K : 0);
+  T.cc = plan.add<int>(ownerInLds ? nq : 0);
+  T.cnt = plan.add<int>(1);
+  return T;
+}
+// the search on tables that are on the device (nq > 0); T.best, T.cnt and (mode 0, wantRaw) T.raw hold the answer
+static pli_status projLaunch(pli_ctx* c, int mode, const ProjTables& T, int32_t nq, int32_t ncur, float minX, float maxX, float minY,
+                             float maxY, int32_t checkOri, float nnratio, bool wantRaw) {
+  const int nc = std::max(ncur, 1);
+  int* rawOut = (mode == 0 && wantRaw) ? (int*)T.raw : (int*)nullptr;
+  if (ncur <= PROJ_LDS_KEYPOINTS) {
+    // a second-best farther than 100 / nnratio can no longer reject a best of <= 100 (ORBmatcher.cc:124-126)
+    int limit = 100;
+    if (mode == 1) limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
+    LAUNCH(c, "k_proj_candidates", k_proj_candidates, dim3(nq), dim3(64), 0, T.q, T.qd, nq, T.k, T.dsc, T.u, ncur, minX, maxX, minY, maxY,
+           mode == 0 ? 1 : 0, limit, T.keys, T.cc);
+    LAUNCH(c, "k_proj_assign", k_proj_assign, dim3(1), dim3(64), (size_t)nc * 4, T.q, T.qd, nq, T.k, T.dsc, T.u, T.occ, ncur, minX, maxX,
+           minY, maxY, mode, checkOri, nnratio, T.keys, T.cc, T.best, T.cnt, rawOut);
+  } else {
+    LAUNCH(c, "k_proj_assign_scan", k_proj_assign_scan, dim3(1), dim3(64), 0, T.q, T.qd, nq, T.k, T.dsc, T.u, T.occ, ncur, minX, maxX,
+           minY, maxY, mode, checkOri, nnratio, T.own, T.best, T.cnt, rawOut);
+  }
+  return PLI_OK;
+}
+
 static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
                                    const pli_keypoint* kp, const uint8_t* desc, const float* uright, const uint8_t* occupied,
                                    int32_t ncur, float minX, float maxX, float minY, float maxY, int32_t checkOri,
@@ -259,41 +320,17 @@ static pli_status projectionSearch(pli_ctx* c, int mode, const pli_proj_query* q
   if (nq == 0) return PLI_OK;
   if (ncur >= (1 << 28)) { g_err = "too many keypoints"; return PLI_ERR_INVALID; }
   HIPCHK(hipSetDevice(c->device));
-  const int nc = std::max(ncur, 1);
-  const bool ownerInLds = ncur <= PROJ_LDS_KEYPOINTS;
   for (int i = 0; i < nq; ++i)
     if (mode == 0 && (q[i].valid & ~3)) { g_err = "pli_proj_query.valid: 0, 1 or 1 | PLI_PROJ_NO_OBSERVATIONS"; return PLI_ERR_INVALID; }
   ScratchPlan plan;
-  auto dq = plan.in(q, nq);
-  auto dqd = plan.in(qdesc, (size_t)nq * 32);
-  auto dk = plan.in(kp, ncur);
-  auto ddsc = plan.in(desc, (size_t)ncur * 32);
-  auto du = plan.in(uright, ncur);
-  auto down = plan.add<int>(ownerInLds ? 0 : ncur);
-  auto dbest = plan.add<int>(nq);
-  auto draw = plan.add<int>(nq);
-  auto occ = plan.inOpt(occupied, ncur);
-  auto dkeys = plan.add<unsigned long long>(ownerInLds ? (size_t)nq * PROJ_K : 0);
-  auto dcc = plan.add<int>(ownerInLds ? nq : 0);
-  auto dcnt = plan.add<int>(1);
+  const ProjTables T = projTables(plan, q, qdesc, nq, kp, desc, uright, occupied, ncur);
   pli_status st = commitScratch(c, plan);
   if (st != PLI_OK) return st;
-  int* rawOut = (mode == 0 && raw) ? (int*)draw : (int*)nullptr;
-  if (ownerInLds) {
-    // a second-best farther than 100 / nnratio can no longer reject a best of <= 100 (ORBmatcher.cc:124-126)
-    int limit = 100;
-    if (mode == 1) limit = (nnratio > 0.4f) ? std::min(255, (int)(100.0f / nnratio) + 2) : 255;
-    LAUNCH(c, "k_proj_candidates", k_proj_candidates, dim3(nq), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, ncur, minX, maxX, minY, maxY,
-           mode == 0 ? 1 : 0, limit, dkeys, dcc);
-    LAUNCH(c, "k_proj_assign", k_proj_assign, dim3(1), dim3(64), (size_t)nc * 4, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
-           minY, maxY, mode, checkOri, nnratio, dkeys, dcc, dbest, dcnt, rawOut);
-  } else {
-    LAUNCH(c, "k_proj_assign_scan", k_proj_assign_scan, dim3(1), dim3(64), 0, dq, dqd, nq, dk, ddsc, du, occ, ncur, minX, maxX,
-           minY, maxY, mode, checkOri, nnratio, down, dbest, dcnt, rawOut);
-  }
-  HIPCHK(download(c, best, dbest));
-  if (rawOut) HIPCHK(download(c, raw, draw));
-  return fetchCount(c, dcnt, nmatches);
+  const bool wantRaw = mode == 0 && raw;
+  if ((st = projLaunch(c, mode, T, nq, ncur, minX, maxX, minY, maxY, checkOri, nnratio, wantRaw)) != PLI_OK) return st;
+  HIPCHK(download(c, best, T.best));
+  if (wantRaw) HIPCHK(download(c, raw, T.raw));
+  return fetchCount(c, T.cnt, nmatches);
 }
 
 pli_status pli_search_by_projection(pli_ctx* c, const pli_proj_query* q, const uint8_t* qdesc, int32_t nq,
@@ -311,6 +348,85 @@ pli_status pli_search_local_map(pli_ctx* c, const pli_proj_query* q, const uint8
                                 float nnratio, int32_t* best, int32_t* nmatches) {
   CtxGuard guard__(c);
   return projectionSearch(c, 1, q, qdesc, nq, kp, desc, uright, occupied, ncur, minX, maxX, minY, maxY, 0, nnratio, best, nmatches);
+}
+
+// Tracking.cc:3809-3855 in one call: k_local_project writes the view records and the queries, the mode-1 search reads the queries
+// where they lie.
+pli_status pli_search_local_points(pli_ctx* c, const pli_fuse_point* mp, const uint8_t* mpDesc, int32_t nq, const float* pose,
+                                   const pli_fuse_camera* cam, float viewingCosLimit, float th, int32_t farPoints, float thFar,
+                                   float nnratio, const float* levelRatio, const pli_keypoint* kp, const uint8_t* desc,
+                                   const float* uright, const uint8_t* occupied, int32_t ncur, pli_local_view* view,
+                                   int32_t* best, int32_t* nInView, int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || nq < 0 || ncur < 0 || !pose || !cam || !levelRatio || (nq > 0 && (!mp || !mpDesc || !view || !best)) ||
+      (ncur > 0 && (!kp || !desc || !uright))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nInView) *nInView = 0;
+  if (nmatches) *nmatches = 0;
+  if (!levelRatioOk(c, levelRatio) || !imageBoundsOk(cam->min_x, cam->max_x, cam->min_y, cam->max_y)) return PLI_ERR_INVALID;
+  if (ncur >= (1 << 28)) { g_err = "too many keypoints"; return PLI_ERR_INVALID; }
+  if (!octavesOk(c, kp, ncur, "cur_kp")) return PLI_ERR_INVALID;
+  for (int i = 0; i < nq; ++i)                                // (a stored level indexes mvScaleFactors)
+    if (mp[i].valid == PLI_LOCAL_STORED_VIEW && !(mp[i].normal[2] >= 0.0f && mp[i].normal[2] < (float)c->hp.nlevels)) {
+      g_err = "a stored view's level outside [0, orb_nlevels)";
+      return PLI_ERR_INVALID;
+    }
+  if (nq == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const LevelBlock lv(c, levelRatio, 2);
+  ScratchPlan plan;
+  auto dmp = plan.in(mp, nq);
+  auto dpose = plan.in(pose, 15);
+  auto dlv = plan.in(lv.v, 2 * MAX_LEVELS);
+  auto dview = plan.add<pli_local_view>(nq);
+  auto dcnt = plan.add<int>(1);                               // the points in view
+  const ProjTables T = projTables(plan, nullptr, mpDesc, nq, kp, desc, uright, occupied, ncur);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  HIPCHK(hipMemsetAsync(dcnt, 0, 4, c->stream));
+  LAUNCH(c, "k_local_project", k_local_project, dim3((nq + 255) / 256), dim3(256), 0, dmp, nq, dpose, *cam, viewingCosLimit, th,
+         farPoints ? 1 : 0, thFar, dlv, c->hp.nlevels, dlv + MAX_LEVELS, dview, T.q, dcnt);
+  if ((st = projLaunch(c, 1, T, nq, ncur, cam->min_x, cam->max_x, cam->min_y, cam->max_y, 0, nnratio, false)) != PLI_OK) return st;
+  HIPCHK(download(c, view, dview));
+  HIPCHK(download(c, best, T.best));
+  HIPCHK(download(c, nInView, dcnt, 0, 1));
+  return fetchCount(c, T.cnt, nmatches);
+}
+
+// Tracking.cc:3862-3883 in one call: k_local_lines_project leaves the list and its descriptors, matchNNR runs on them.
+pli_status pli_search_local_lines(pli_ctx* c, const float* sp, const uint8_t* valid, const uint8_t* desc, int32_t nl,
+                                  const float* pose, const pli_fuse_camera* cam, const uint8_t* curDesc, int32_t n2, float nnr,
+                                  int32_t* inView, float* projS, int32_t* inFrustum, int32_t* matches12, int32_t* nInView,
+                                  int32_t* nmatches) {
+  CtxGuard guard__(c);
+  if (!c || nl < 0 || n2 < 0 || !pose || !cam || (nl > 0 && (!sp || !valid || !desc || !inView || !projS || !inFrustum || !matches12)) ||
+      (n2 > 0 && !curDesc)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nInView) *nInView = 0;
+  if (nmatches) *nmatches = 0;
+  if (nl == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto dsp = plan.in(sp, (size_t)nl * 3);
+  auto dvalid = plan.in(valid, nl);
+  auto ddesc = plan.in(desc, (size_t)nl * 32);
+  auto dpose = plan.in(pose, 15);
+  auto din = plan.add<int>(nl);
+  auto dproj = plan.add<float>((size_t)nl * 2);
+  auto dlist = plan.add<int>(nl);
+  const MatchTables T = matchTables(plan, nullptr, nl, curDesc, n2);      // T.d1: the descriptors of the lines in view, gathered
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  LAUNCH(c, "k_local_lines_project", k_local_lines_project, dim3(1), dim3(1024), 0, dsp, dvalid, ddesc, nl, dpose, *cam, din, dproj, dlist,
+         T.d1, T.count);
+  HIPCHK(download(c, inView, din));
+  HIPCHK(download(c, projS, dproj));
+  int n1 = 0;
+  if ((st = fetchCount(c, T.count, &n1)) != PLI_OK) return st;            // the list's length sizes the match
+  if (nInView) *nInView = n1;
+  if (n1 == 0) return PLI_OK;
+  if ((st = matchLaunch(c, T, n1, n2, nnr, false)) != PLI_OK) return st;
+  HIPCHK(download(c, inFrustum, dlist, 0, n1));
+  HIPCHK(download(c, matches12, T.m12, 0, n1));
+  return fetchCount(c, T.count, nmatches);
 }
 
 pli_status pli_search_local_map_fisheye(pli_ctx* c, const pli_proj_query* qL, const pli_proj_query* qR, const uint8_t* qdesc,

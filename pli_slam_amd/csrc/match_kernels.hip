@@ -1812,6 +1812,130 @@ __global__ __launch_bounds__(256) void k_fuse_project(const pli_fuse_point* __re
   compact_survivor(keep, S, surv, nSurv);
 }
 
+// ---------------------------------------------------------------------------
+// The front of Tracking::SearchLocalPointsAndLines (Tracking.cc:3809-3883) for a frame of one camera (Nleft == -1).
+//   k_local_project        one thread per local map point: Frame::isInFrustum (Frame.cc:585-647) in the reference's order and with
+//                          its roundings, the view record the tracker keeps, and the point's query of
+//                          ORBmatcher::SearchByProjection(F, vpMapPoints) as ORBmatcher.cc:53-73 builds it, left on the device for
+//                          k_proj_candidates / k_proj_assign.  NOT fuse_project_point: the image gate is closed at mnMaxX / mnMaxY
+//                          and lets a NaN through, the viewing angle is a float cosine against the caller's limit, and the record
+//                          keeps the projection of a point that a later gate refuses.
+//   k_local_lines_project  ONE workgroup: Frame::isInFrustum_l (Frame.cc:661-701) per local map line, then the in-view lines
+//                          compacted in list order (the order is the result: matches_12 is indexed by the position in
+//                          mvpLocalMapLines_InFrustum) with their descriptors gathered for k_knn2.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(pli_local_view) == 32, "pli_local_view layout");
+
+// grid = ceil(nq / 256); T: Rcw row major, tcw, Ow
+__global__ __launch_bounds__(256) void k_local_project(const pli_fuse_point* __restrict__ mp, int nq, const float* __restrict__ T,
+                                                       pli_fuse_camera cam, float viewCosLimit, float th, int farPoints,
+                                                       float thFar, const float* __restrict__ levelRatio, int nlevels,
+                                                       const float* __restrict__ scaleFactor, pli_local_view* __restrict__ view,
+                                                       pli_proj_query* __restrict__ q, int* __restrict__ nInView) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool inView = false;
+  if (i < nq) {
+    pli_local_view V = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0};
+    const pli_fuse_point P = mp[i];
+    // A point skipped at Tracking.cc:3813 that still carries mbTrackInView from an earlier frame (PLI_LOCAL_STORED_VIEW): isInFrustum
+    // does not run, ORBmatcher.cc:53-73 searches it with the fields it holds.  The row carries them; the record stays zero.
+    const bool stored = P.valid == PLI_LOCAL_STORED_VIEW;
+    if (stored) {
+      V.proj_x = P.pos[0]; V.proj_y = P.pos[1]; V.proj_xr = P.pos[2];
+      V.depth = P.normal[0]; V.view_cos = P.normal[1]; V.level = (int)P.normal[2];
+    } else if (P.valid) {                                          // Tracking.cc:3813-3816
+      V.proj_x = -1.0f; V.proj_y = -1.0f;                          // Frame.cc:589-590
+      float pc[3];
+      for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, P.pos, 1.0, (double)T[9 + r]);      // mRcw*P + mtcw
+      const float pcDist = (float)sqrt((double)pc[0] * (double)pc[0] + (double)pc[1] * (double)pc[1] + (double)pc[2] * (double)pc[2]);
+      const float z = pc[2];
+      const float invz = __fdiv_rn(1.0f, z);
+      if (!(z < 0.0f)) {                                           // :602
+        const float u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, pc[0]), z), cam.cx);       // Pinhole::project, Pinhole.cpp:30-33
+        const float v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, pc[1]), z), cam.cy);
+        if (!(u < cam.min_x || u > cam.max_x) && !(v < cam.min_y || v > cam.max_y)) {    // :607-610, as written: a NaN stays
+          V.proj_x = u; V.proj_y = v;                              // :612-613
+          const float po[3] = {__fsub_rn(P.pos[0], T[12]), __fsub_rn(P.pos[1], T[13]), __fsub_rn(P.pos[2], T[14])};
+          const float dist = (float)sqrt((double)po[0] * (double)po[0] + (double)po[1] * (double)po[1] + (double)po[2] * (double)po[2]);
+          if (!(dist < P.min_dist_inv || dist > P.max_dist_inv)) { // :621
+            const double dot = (double)po[0] * (double)P.normal[0] + (double)po[1] * (double)P.normal[1] + (double)po[2] * (double)P.normal[2];
+            const float viewCos = (float)(dot / (double)dist);     // :627
+            if (!(viewCos < viewCosLimit)) {                       // :629
+              const float ratio = __fdiv_rn(P.max_dist, dist);     // MapPoint::PredictScale, MapPoint.cc:449-464
+              int level = 0;
+              for (int n = 0; n < nlevels - 1; ++n) level += ratio > levelRatio[n] ? 1 : 0;
+              inView = true;
+              V.in_view = 1; V.level = level; V.depth = pcDist; V.view_cos = viewCos;
+              V.proj_xr = __fsub_rn(u, __fmul_rn(cam.bf, invz));   // :638
+            }
+          }
+        }
+      }
+    }
+    pli_proj_query Q = {0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0.0f, 0};
+    if ((inView || stored) && !(farPoints && V.depth > thFar)) {   // ORBmatcher.cc:53-57
+      float r = (double)V.view_cos > 0.998 ? 2.5f : 4.0f;          // RadiusByViewingCos :216-222
+      if (th != 1.0f) r = __fmul_rn(r, th);                        // :69-70
+      Q.u = V.proj_x; Q.v = V.proj_y; Q.ur = V.proj_xr;
+      Q.radius = __fmul_rn(r, scaleFactor[min(max(V.level, 0), nlevels - 1)]);   // :73 (a stored level: the host checked it)
+      Q.min_level = V.level - 1; Q.max_level = V.level;
+      // a NaN projection takes no keypoint (every |x - u| < r is false): the query is closed here, so that no window is derived from it
+      Q.valid = (Q.u != Q.u || Q.v != Q.v) ? 0 : 1;
+    }
+    q[i] = Q;
+    if (stored) V = pli_local_view{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0};
+    view[i] = V;
+  }
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(inView);
+  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(nInView, __popcll(bal));
+}
+
+// grid = 1, 1024 threads; sp: nl x 3 floats, gathered: room for nl rows of 32 bytes, count[0] = the lines in view
+__global__ __launch_bounds__(1024) void k_local_lines_project(const float* __restrict__ sp, const uint8_t* __restrict__ valid,
+                                                              const uint8_t* __restrict__ desc, int nl,
+                                                              const float* __restrict__ T, pli_fuse_camera cam,
+                                                              int* __restrict__ inViewOut, float* __restrict__ projS,
+                                                              int* __restrict__ inFrustum, uint8_t* __restrict__ gathered,
+                                                              int* __restrict__ count) {
+  __shared__ int waveCnt[16];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int base = 0;                                                    // in-view lines before this chunk (the same in every thread)
+  for (int first = 0; first < nl; first += 1024) {
+    const int i = first + t;
+    bool in = false;
+    float u = 0.0f, v = 0.0f;
+    if (i < nl && valid[i]) {                                      // Tracking.cc:3865-3868
+      float pc[3];
+      for (int r = 0; r < 3; ++r) pc[r] = cvmat_dot3(T + 3 * r, 1, sp + 3 * (int64_t)i, 1.0, (double)T[9 + r]);   // mRcw*sp + mtcw
+      if (!(pc[2] < 0.0f)) {                                       // Frame.cc:679
+        const float invz = __fdiv_rn(1.0f, pc[2]);
+        const float pu = __fadd_rn(__fmul_rn(__fmul_rn(cam.fx, pc[0]), invz), cam.cx);   // :684-685, left to right
+        const float pv = __fadd_rn(__fmul_rn(__fmul_rn(cam.fy, pc[1]), invz), cam.cy);
+        if (!(pu < cam.min_x || pu > cam.max_x) && !(pv < cam.min_y || pv > cam.max_y)) { in = true; u = pu; v = pv; }
+      }
+    }
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(in);
+    if (lane == 0) waveCnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, chunk = 0;
+    for (int w = 0; w < 16; ++w) { const int c = waveCnt[w]; before += w < wave ? c : 0; chunk += c; }
+    if (i < nl) {
+      inViewOut[i] = in ? 1 : 0;
+      projS[2 * (int64_t)i] = u; projS[2 * (int64_t)i + 1] = v;
+      if (in) {
+        const int k = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+        inFrustum[k] = i;
+        const uint4* s = reinterpret_cast<const uint4*>(desc + (int64_t)i * 32);
+        uint4* d = reinterpret_cast<uint4*>(gathered + (int64_t)k * 32);
+        d[0] = s[0]; d[1] = s[1];
+      }
+    }
+    base += chunk;
+    __syncthreads();                                               // waveCnt is read before the next chunk rewrites it
+  }
+  if (t == 0) count[0] = base;
+}
+
 // the minimum of a key over the G lanes of a group (G a power of two <= 64; all lanes of the wave take part)
 template <int G>
 __device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v) {

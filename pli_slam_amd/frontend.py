@@ -715,6 +715,59 @@ class Frontend:
         check(self.L.pli_match_nnr(self.h, ptr(d1), d1.shape[0], ptr(d2), d2.shape[0], nnr, ptr(m), C.byref(n)))
         return n.value, m
 
+    def search_local_points(self, points, descs, pose, cam, cur_kp, cur_desc, cur_uright, th=1.0, far_points=False, th_far=0.0,
+                            nnratio=0.8, viewing_cos_limit=0.5, cur_occupied=None, level_ratio=None):
+        """Tracking.cc:3809-3855 for a frame of one camera: Frame::isInFrustum of every local map point, the queries of
+        ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) and that search, the projection and the
+        queries on the device - see pli_search_local_points.  points: capi.FUSE_POINT_DT rows in list order (valid == 0: skipped
+        at :3813-3816; valid == capi.LOCAL_STORED_VIEW: skipped there but still mbTrackInView, searched with the fields it holds:
+        pos = mTrackProjX, Y, XR, normal = mTrackDepth, mTrackViewCos, mnTrackScaleLevel), descs their GetDescriptor() rows; pose: 15 floats (mRcw row major, mtcw, mOw); cam: capi.FuseCamera or its
+        9 values.  Returns (view: capi.LOCAL_VIEW_DT rows, best_idx2, n_in_view, nmatches)."""
+        pts = np.ascontiguousarray(points, capi.FUSE_POINT_DT).reshape(-1)
+        d = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        if len(d) != len(pts):
+            raise ValueError("every map point needs one descriptor")
+        pose = np.ascontiguousarray(pose, np.float32).reshape(15)
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        kp = np.ascontiguousarray(cur_kp, KEYPOINT_DT)
+        de = np.ascontiguousarray(cur_desc, np.uint8)
+        ur = np.ascontiguousarray(cur_uright, np.float32)
+        occ = None if cur_occupied is None else np.ascontiguousarray(cur_occupied, np.uint8)
+        level_ratio = self._level_ratio(level_ratio)
+        view = np.zeros(len(pts), capi.LOCAL_VIEW_DT)
+        best = np.full(len(pts), -1, np.int32)
+        nview, n = C.c_int32(), C.c_int32()
+        check(self.L.pli_search_local_points(self.h, ptr(pts), ptr(d), len(pts), ptr(pose), C.byref(cam), float(viewing_cos_limit),
+                                             float(th), int(bool(far_points)), float(th_far), float(nnratio), ptr(level_ratio),
+                                             ptr(kp), ptr(de), ptr(ur), ptr(occ), kp.shape[0], ptr(view), ptr(best),
+                                             C.byref(nview), C.byref(n)))
+        return view, best, nview.value, n.value
+
+    def search_local_lines(self, start_points, valid, descs, pose, cam, cur_desc, nnr):
+        """Tracking.cc:3862-3883: Frame::isInFrustum_l of every local map line, the ordered list mvpLocalMapLines_InFrustum and
+        the one-way matchNNR of its descriptors against the frame's - see pli_search_local_lines.  start_points: nl x 3 floats,
+        valid: nl (0: skipped at :3865-3868), descs: nl x 32.  Returns (in_view[nl], proj_s[nl, 2], in_frustum[k], matches_12[k],
+        nmatches) with k = the number of lines in view."""
+        sp = np.ascontiguousarray(start_points, np.float32).reshape(-1, 3)
+        va = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+        d = np.ascontiguousarray(descs, np.uint8).reshape(-1, 32)
+        if not len(sp) == len(va) == len(d):
+            raise ValueError("every map line needs a start point, a valid flag and a descriptor")
+        pose = np.ascontiguousarray(pose, np.float32).reshape(15)
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        d2 = np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, 32)
+        nl = len(sp)
+        in_view = np.zeros(nl, np.int32)
+        proj = np.zeros((nl, 2), np.float32)
+        lst = np.full(nl, -1, np.int32)
+        m = np.full(nl, -1, np.int32)
+        nview, n = C.c_int32(), C.c_int32()
+        check(self.L.pli_search_local_lines(self.h, ptr(sp), ptr(va), ptr(d), nl, ptr(pose), C.byref(cam), ptr(d2), len(d2),
+                                            float(nnr), ptr(in_view), ptr(proj), ptr(lst), ptr(m), C.byref(nview), C.byref(n)))
+        return in_view, proj, lst[:nview.value].copy(), m[:nview.value].copy(), n.value
+
     # ---- batch path ----------------------------------------------------------
     def table_bytes(self, nframes):
         return int(self.layout.record_bytes) * nframes
