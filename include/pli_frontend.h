@@ -174,6 +174,10 @@ void pli_config_default(pli_frontend_config* cfg, int32_t width, int32_t height)
 /* Capacities derived from a config (sizes of the per-eye tables). */
 int32_t pli_kp_capacity(const pli_frontend_config* cfg);   /* >= nfeatures + 3*nlevels    */
 int32_t pli_kl_capacity(const pli_frontend_config* cfg);   /* lsd_nfeatures or max_lines  */
+/* The short-segment cut of a plain (non-debug) context: a line-support region whose bounding box in the scaled image has
+ * bw^2 + bh^2 <= this value cannot yield a segment longer than min_line_length * min(width, height), so the detector computes
+ * no segment for it (the key-line tables do not change: such a segment fails the length test anyway).  -1: no cut. */
+int32_t pli_lsd_segment_box_cut(const pli_frontend_config* cfg);
 
 /* ------------------------------------------------------------------------ */
 /* Result table: one fixed-stride record per stereo frame, written on the    */
@@ -1077,7 +1081,9 @@ enum {
   PLI_DBG_LEVEL_KEYPOINTS = 4, /* arg = level; int32 count then {int32 x,y,score} after the quadtree */
   PLI_DBG_LSD_SCALED = 5,      /* u8 W'*H' (blur 0.6 + x1.2 resize)                         */
   PLI_DBG_LSD_ANGLE = 6,       /* float W'*H' degrees, -1024 = NOTDEF                       */
-  PLI_DBG_LSD_SEGMENTS = 7,    /* int32 count then float[4] x1,y1,x2,y2 in detection order  */
+  PLI_DBG_LSD_SEGMENTS = 7,    /* int32 count then float[4] x1,y1,x2,y2 in detection order: EVERY detected segment only in a
+                                  debug context (pli_debug_enable) — a plain context omits the segments that cannot pass the
+                                  length cut (pli_lsd_segment_box_cut), except on the sequential schedule, which lists them all */
   PLI_DBG_LBD_DXDY = 8,        /* int16 dx[w*h] then int16 dy[w*h]                          */
   PLI_DBG_LSD_ORDER = 9,       /* int32 count then int32 pixel index of every seed in visiting order */
   PLI_DBG_LBD_FLOAT = 10,      /* float[kl_cap][72] LBD band vector before binarisation     */

@@ -116,6 +116,7 @@ _PROTOS = {
     "pli_config_default": (None, [C.POINTER(Config), C.c_int32, C.c_int32]),
     "pli_kp_capacity": (C.c_int32, [C.POINTER(Config)]),
     "pli_kl_capacity": (C.c_int32, [C.POINTER(Config)]),
+    "pli_lsd_segment_box_cut": (C.c_int32, [C.POINTER(Config)]),
     "pli_ctx_create": (C.c_int32, [C.POINTER(Config), C.c_int32, C.POINTER(C.c_void_p)]),
     "pli_ctx_destroy": (None, [C.c_void_p]),
     "pli_last_error": (C.c_char_p, []),

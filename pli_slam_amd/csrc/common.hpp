@@ -2,6 +2,7 @@
 // gfx950 only: wave64, no CUDA compatibility paths.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -62,12 +63,40 @@ struct DevParams {
   int maxLines;
   int lsdNFeatures;
   double minLength;
+  int segBoxCut, segBoxPad;   // lsd_seg_box_cut: a region whose box has bw^2 + bh^2 <= segBoxCut gets no segment (-1: every region does)
   // stereo
   float bf, maxD;
   // line matching
   int sWs, bestLR;
   double lineSimTh, overlapTh, ratio12L, minDispRatio, minDisp, horizTh;
 };
+
+// SHORT-SEGMENT CUT (tile and lane relaxations).  k_keylines keeps a segment only if its length exceeds minLength, and a region's
+// bounding box bounds that length from above, so a region whose box is too small needs no region2rect at all.  With
+// bw = xmax - xmin, bh = ymax - ymin of the region's pixels (scaled image) and D = sqrt(bw^2 + bh^2):
+//   * region2rect's end points are centroid + l_min * dir and centroid + l_max * dir, l the projection of the integer pixel
+//     coordinates on the unit vector dir about the centroid; two projections differ by at most the distance of their pixels, so
+//     l_max - l_min <= D (the 0 both start from lies between them: the centroid is a positive-weight mean of the pixels);
+//   * + 0.5 and / scale make that D / scale; the four coordinates are then rounded to float — they stay below 16384 (lsd_seg_box_cut
+//     asks for images of at most 8192 a side), where half an ulp is at most 2^-11, so either difference moves by at most 2^-10 and the length by sqrt(2) * 2^-10 <
+//     1.4e-3, the float rounding of the length itself (1e-6) included; k_keylines' clamp into the image is coordinate-wise and
+//     never lengthens a segment.
+// Hence length <= D / scale + 1.4e-3, and a region with D <= scale * (minLength - 0.01) — a margin of seven times that budget —
+// cannot pass `length > minLength`.  D^2 is an integer: the cut is D^2 <= floor((scale * (minLength - 0.01))^2).
+// The growers skip the rect list for such a region and the emit kernels skip the region (k_tx_collect, rx_emits): both apply this
+// one predicate to the box the grower stored, so what is emitted never depends on what was skipped.  Segments that are dropped never
+// reach k_keylines' numbering, so every output table is unchanged.  -1 (no cut): minLength <= 0.01, images wider than the float
+// budget above, and debug contexts, whose PLI_DBG_LSD_SEGMENTS lists every detected segment.
+inline int lsd_seg_box_cut(double lsdScale, double minLength, int W, int H) {
+  const double d = lsdScale * (minLength - 0.01);
+  if (!(minLength - 0.01 > 0) || W > 8192 || H > 8192 || !(lsdScale * (W > H ? W : H) < 16384) || !(d * d < 1e9)) return -1;
+  return (int)std::floor(d * d);
+}
+// (bmin / bmax: the packed 16-bit (y << 16 | x) minima and maxima of a region's pixels, as the growers store them in rgBox)
+__host__ __device__ __forceinline__ bool lsd_box_can_pass(int bmin, int bmax, int T2) {
+  const int bw = (bmax & 0xFFFF) - (bmin & 0xFFFF), bh = (int)((unsigned)bmax >> 16) - (int)((unsigned)bmin >> 16);
+  return T2 < 0 || bw * bw + bh * bh > T2;             // (T2 >= 0: both sides below 2^14 scaled pixels, the sum fits)
+}
 
 // per-image control block of the LSD relaxation (lsd_relax.hip)
 // Returning atomics on one cache line serialise in its L2 channel (~40 ns each), so every hot counter has its own

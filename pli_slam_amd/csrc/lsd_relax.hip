@@ -858,15 +858,21 @@ constexpr int RX_CCHUNK = 2048;   // ranks per block
 // (the size first: it is read in rank order — by the callers, for all the ranks of a thread at once and from a clamped index: a load
 // under the lane predicate i < n is waited for at the end of its branch —, and only the ~1.5 % of the ranks whose region is large
 // enough go on to the two dependent gathers)
-__device__ __forceinline__ bool rx_emits(const int* order, const int2* own, int size, int i, int n, int minReg) {
+// (... and a region whose final box says that its segment cannot pass k_keylines' length cut is not emitted: the tile growers gave it
+// none — common.hpp "SHORT-SEGMENT CUT"; box: the image's rgBox plane, indexed by rank like the sizes)
+__device__ __forceinline__ bool rx_emits(const int* order, const int2* own, int size, int i, int n, int minReg, const int2* box, int boxCut) {
   if (i >= n) return false;
-  return size >= minReg && own[order[i]].x == i;
+  if (size < minReg || own[order[i]].x != i) return false;
+  if (boxCut < 0) return true;
+  const int2 b = box[i];
+  return lsd_box_can_pass(b.x, b.y, boxCut);
 }
 
 __global__ __launch_bounds__(256) void k_rx_count(const RxCtl* __restrict__ ctl, const int* __restrict__ orderAll,
                                                   const int* __restrict__ nDefined, const int2* __restrict__ ownAll,
                                                   const int* __restrict__ rgSizeAll, int* __restrict__ chunkCntAll,
-                                                  int nChunks, int64_t npix, int minReg, int img0) {
+                                                  int nChunks, int64_t npix, int minReg, int img0, const int2* __restrict__ rgBoxAll,
+                                                  int boxCut) {
   __shared__ int wsum[4];
   const int img = blockIdx.y + img0;
   if (ctl[img].state != 2 || ctl[img].overflow) return;
@@ -878,7 +884,8 @@ __global__ __launch_bounds__(256) void k_rx_count(const RxCtl* __restrict__ ctl,
   for (int j = 0; j < RX_CCHUNK / 256; ++j) sz[j] = rgSizeAll[img * npix + min((int)blockIdx.x * RX_CCHUNK + j * 256 + tid, max(n - 1, 0))];
 #pragma unroll
   for (int j = 0; j < RX_CCHUNK / 256; ++j)
-    cntv += rx_emits(orderAll + img * npix, ownAll + img * npix, sz[j], blockIdx.x * RX_CCHUNK + j * 256 + tid, n, minReg) ? 1 : 0;
+    cntv += rx_emits(orderAll + img * npix, ownAll + img * npix, sz[j], blockIdx.x * RX_CCHUNK + j * 256 + tid, n, minReg,
+                     rgBoxAll + img * npix, boxCut) ? 1 : 0;
   cntv = wave_sum_i32(cntv);
   if ((tid & 63) == 0) wsum[tid >> 6] = cntv;
   __syncthreads();
@@ -890,7 +897,7 @@ __global__ __launch_bounds__(256) void k_rx_emit(const RxCtl* __restrict__ ctl, 
                                                  const int* __restrict__ rgSizeAll, const float4* __restrict__ rgSegAll,
                                                  const int* __restrict__ chunkCntAll, int nChunks, int64_t npix,
                                                  int minReg, float* __restrict__ segAll, int* __restrict__ nSeg,
-                                                 int maxSeg, int img0) {
+                                                 int maxSeg, int img0, const int2* __restrict__ rgBoxAll, int boxCut) {
   __shared__ int wsum[4];
   __shared__ int sbase;
   const int img = blockIdx.y + img0;
@@ -913,7 +920,7 @@ __global__ __launch_bounds__(256) void k_rx_emit(const RxCtl* __restrict__ ctl, 
 #pragma unroll
   for (int j = 0; j < RX_CCHUNK / 256; ++j) {
     const int i = blockIdx.x * RX_CCHUNK + j * 256 + tid;
-    const bool e = rx_emits(orderAll + img * npix, ownAll + img * npix, sz[j], i, n, minReg);
+    const bool e = rx_emits(orderAll + img * npix, ownAll + img * npix, sz[j], i, n, minReg, rgBoxAll + img * npix, boxCut);
     const unsigned long long bal = __builtin_amdgcn_ballot_w64(e);
     __syncthreads();
     if (lane == 0) wsum[wv] = __popcll(bal);

@@ -1628,7 +1628,10 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
         rgSize[r & DL.rmask] = cnt;
         rgBox[r & DL.rmask] = make_int2(bmin, bmax);
       }
-      if (cnt >= minReg) {                              // the pixel list goes to k_rx_rect (region2rect)
+      // the pixel list goes to k_rx_rect (region2rect) — unless the box just stored says that the segment cannot pass k_keylines'
+      // length cut (common.hpp "SHORT-SEGMENT CUT": four regions in five; the emit kernels drop the region by the same test)
+      // (the box is wave-uniform but lives in vector registers — tx_accept_fast's v_pk_min / v_pk_max —: the compiler has to be told)
+      if (cnt >= minReg && lsd_box_can_pass(__builtin_amdgcn_readfirstlane(bmin), __builtin_amdgcn_readfirstlane(bmax), P.segBoxCut)) {
         int off = 0, slot = 0;
         if (first) {
           const unsigned long long ra = atomicAdd(&c.rectArena, (1ull << RX_ARENA_BITS) | (unsigned long long)cnt);
@@ -2261,7 +2264,8 @@ __global__ __launch_bounds__(256) void k_tx_rec_from_hot(const RxCtl* __restrict
 
 __global__ __launch_bounds__(256) void k_tx_collect(RxCtl* __restrict__ ctl, const int* __restrict__ idPlaneAll, const int2* __restrict__ ownAll,
                                                     const int* __restrict__ rgSizeAll, int64_t npix, int minReg, int* __restrict__ candAll,
-                                                    int* __restrict__ candCnt, int img0, int emitCap) {
+                                                    int* __restrict__ candCnt, int img0, int emitCap, const int2* __restrict__ rgBoxAll,
+                                                    int boxCut) {
   constexpr int CAP = 1024;           // ids a workgroup gathers in LDS before its one atomic on the image's counter
   __shared__ int s_n, s_base;
   __shared__ int s_buf[CAP];
@@ -2300,7 +2304,9 @@ __global__ __launch_bounds__(256) void k_tx_collect(RxCtl* __restrict__ ctl, con
       hits &= hits - 1u;
       const int64_t p = p1 + (j >> 2) * 1024 + tid * 4 + (j & 3);
       const int id = idPlaneAll[base + p];
-      if (id == TX_INF || ownAll[base + p].x != id) continue;
+      // (the region's final box, fetched beside its id: a region the growers gave no segment — common.hpp "SHORT-SEGMENT CUT" — is no candidate)
+      const int2 box = boxCut >= 0 ? rgBoxAll[base + p] : make_int2(0, 0);
+      if (id == TX_INF || ownAll[base + p].x != id || !lsd_box_can_pass(box.x, box.y, boxCut)) continue;
       const int at = atomicAdd(&s_n, 1);
       if (at < CAP) s_buf[at] = id;
       else {                                        // (more than CAP in one workgroup's share: straight to the image's list)

@@ -367,6 +367,8 @@ pli_status buildGeometry(pli_ctx* c) {
   P.maxLines = cfg.max_lines;
   P.lsdNFeatures = cfg.lsd_nfeatures;
   P.minLength = cfg.min_line_length * (std::min(P.W, P.H));
+  P.segBoxCut = lsd_seg_box_cut(P.lsdScale, P.minLength, P.W, P.H);     // (a plain context; pli_debug_enable switches the cut off)
+  P.segBoxPad = 0;
   P.bf = cfg.bf;
   P.maxD = cfg.stereo_maxd_inf ? std::numeric_limits<float>::infinity() : cfg.bf / (cfg.bf / cfg.fx);
   P.sWs = cfg.matching_s_ws; P.bestLR = cfg.best_lr_matches;
@@ -1325,7 +1327,8 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       int emitCap = TX_EMIT_CAP;                   // (test switch: a small list, so that images take the overflow path to the sequential grower)
       if (const char* e = DEVENV("PLI_TX_EMITCAP")) emitCap = std::max(1, std::min(TX_EMIT_CAP, atoi(e)));
       TRL(c, "k_tx_collect", k_tx_collect, dim3(std::max(1, std::min(64, (int)((npix64 + 2047) / 2048))), nimg), dim3(256), 0, c->jrCtl,
-          (const int*)c->rankOf, (const int2*)c->own, (const int*)c->lastSize, npix64, P.minRegSize, c->txCand, c->txCandCnt, img0, emitCap);
+          (const int*)c->rankOf, (const int2*)c->own, (const int*)c->lastSize, npix64, P.minRegSize, c->txCand, c->txCandCnt, img0, emitCap,
+          (const int2*)c->rgBox, P.segBoxCut);
       TRL(c, "k_tx_emit_sorted", k_tx_emit_sorted, dim3(nimg), dim3(1024), TX_EMIT_CAP * 4, (const RxCtl*)c->jrCtl, (const int*)c->txCand,
           (const int*)c->txCandCnt, (const float4*)c->rgSeg, npix64, (1 << c->txPixBits) - 1, c->seg, c->nSeg, c->maxSeg, img0, emitCap);
       // (the ordered lists of the images left to the sequential grower, decided on the device: normally none, and the three passes end at once)
@@ -1333,9 +1336,10 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       if (os != PLI_OK) return os;
     } else {
     TRL(c, "k_rx_count", k_rx_count, dim3(c->rxChunks, nimg), dim3(256), 0, c->jrCtl, c->order, c->nDefined, c->own, c->lastSize,
-           c->rxChunkCnt, c->rxChunks, npix64, P.minRegSize, img0);
+           c->rxChunkCnt, c->rxChunks, npix64, P.minRegSize, img0, (const int2*)c->rgBox, P.segBoxCut);
     TRL(c, "k_rx_emit", k_rx_emit, dim3(c->rxChunks, nimg), dim3(256), 0, c->jrCtl, c->order, c->nDefined, c->own, c->lastSize,
-           c->rgSeg, c->rxChunkCnt, c->rxChunks, npix64, P.minRegSize, c->seg, c->nSeg, c->maxSeg, img0);
+           c->rgSeg, c->rxChunkCnt, c->rxChunks, npix64, P.minRegSize, c->seg, c->nSeg, c->maxSeg, img0,
+           (const int2*)c->rgBox, P.segBoxCut);
     }
     // images that ran out of a capacity (or did not settle) take the sequential grower
     // (... which reads the 16-byte records: with every round on the hot records nobody has written them — for those images, now)
@@ -1483,6 +1487,9 @@ int32_t pli_kp_capacity(const pli_frontend_config* c) {
   return (int32_t)alignUp((int64_t)c->orb_nfeatures + extra + 8, 64);
 }
 int32_t pli_kl_capacity(const pli_frontend_config* c) { return c->lsd_nfeatures != 0 ? c->lsd_nfeatures : c->max_lines; }
+int32_t pli_lsd_segment_box_cut(const pli_frontend_config* c) {
+  return lsd_seg_box_cut(c->lsd_scale, c->min_line_length * std::min(c->width, c->height), c->width, c->height);
+}
 
 pli_status pli_ctx_create(const pli_frontend_config* cfg, int32_t device, pli_ctx** out) {
   if (!cfg || !out) { g_err = "null argument"; return PLI_ERR_INVALID; }
@@ -2420,6 +2427,9 @@ pli_status pli_debug_enable(pli_ctx* c, int32_t on) {
     if (c->lsdF64 && (st = c->dalloc(&c->scaled64Dbg, (size_t)c->hp.LW * c->hp.LH * c->NI)) != PLI_OK) return st;
   }
   c->debug = on != 0;
+  // (a debug context lists every detected segment — PLI_DBG_LSD_SEGMENTS is compared with the reference's detector there —: no short-segment cut)
+  c->hp.segBoxCut = c->debug ? -1 : lsd_seg_box_cut(c->hp.lsdScale, c->hp.minLength, c->hp.W, c->hp.H);
+  HIPCHK(hipMemcpy(c->dP, &c->hp, sizeof(DevParams), hipMemcpyHostToDevice));
   return PLI_OK;
 }
 
