@@ -799,6 +799,64 @@ pli_status pli_fuse_search_two_cameras(pli_ctx* ctx, const pli_fuse_point* mp, c
                                        float min_y, float max_y, float th, const float* level_ratio, int32_t sides,
                                        int32_t* best_idx, int32_t* best_dist);
 
+/* LocalMapping::CreateNewMapPoints from the search on (LocalMapping.cc:423-684), for keyframes of one pinhole camera (NLeft == -1,
+ * no mpCamera2: monocular, rectified stereo, RGB-D), one keyframe against nkf neighbours in one call: SearchForTriangulation
+ * (bOnlyStereo = false as at :423, mbCheckOrientation = false as the matcher of :367 is built), then per matched pair the
+ * unprojection, the ray and stereo parallax, the linear triangulation through cv::SVD::compute or KeyFrame::UnprojectStereo, the
+ * depths, both chi-square gates, the far-point gate and the scale consistency (:530-667), on the device with the cv::Mat
+ * conventions of pli_fuse_search and pli_stereo_fisheye.
+ * The reference's loop is sequential along the neighbours: a feature of pKF1 that received a map point from neighbour k
+ * (AddMapPoint :675) is skipped by the search of every later neighbour (ORBmatcher.cc:1033-1039).  That is its only coupling (no
+ * rotation histogram, vbMatched2 is never set, the neighbours are distinct keyframes), so the call evaluates every (neighbour,
+ * feature) pair on the map-point state at entry and then, per feature, keeps the FIRST neighbour in which it is matched and passes
+ * every gate; in every later neighbour it is unmatched.  The results are the sequential loop's exactly.
+ * What stays with the caller: the baseline / median-depth test :396-413 (only neighbours that pass it are sent), F12 and ep as
+ * for pli_search_for_triangulation, and :670-683 (new MapPoint, AddObservation, AddMapPoint, ...), which
+ * PliCreateNewMapPoints (adapters/orbslam_local_mapping.hpp) replays in the reference's order.
+ * Tables: kp1 / desc1 / node1 / has_mp1 and the kf_* ones as for pli_search_for_triangulation.  Per feature of either side also
+ * uright = mvuRight (the stereo flag is mvuRight >= 0), depth = mvDepth, key = mvKeys[i].pt as two floats, which
+ * KeyFrame::UnprojectStereo reads (KeyFrame.cc:937-938; NOT mvKeysUn, which everything else reads).  pose1 / kf_pose: 15 floats per
+ * keyframe as for pli_fuse_search - Rcw row major, tcw, the stored Ow; Rwc is the exact transpose and Twc's blocks are that
+ * transpose and Ow (KeyFrame::SetPose).  cam: fx, fy, cx, cy and bf = mbf are read, shared by the call: fx1..cy1 and fx2..cy2 of
+ * the reference are the same numbers here, and mpCurrentKeyFrame->mbf serves the second keyframe's stereo gate too (:641).  mb is
+ * read by the stereo parallax (:543, :545; the second one only when the first side is not stereo, `else if` at :544).
+ * far_points / th_far: mbFarPoints / mThFarPoints (:660, dist >= th_far rejects).  ratio_factor: 1.5f * mfScaleFactor, computed by
+ * the caller in float (:384).  coarse: bCoarse (:420-422).
+ * Outputs, nkf x n1 unless said: matches12 = what the reference's loop sees at neighbour k (a feature taken by an earlier neighbour
+ * is -1); nmatches[nkf] = the size of that vMatchedIndices; status = one of the codes below per pair; x3d (nkf x n1 x 3) = x3D,
+ * defined where status == PLI_NEWPT_CREATED; nnew[nkf] = the map points created per neighbour.  Two features of pKF1 may be
+ * matched to the same feature of a neighbour and both be created, as in the reference.
+ * Checked before anything is launched, PLI_ERR_INVALID: null pointers, negative counts, a decreasing kf_off, an octave outside
+ * [0, orb_nlevels), a keypoint coordinate, mvKeys coordinate, mvuRight, mvDepth or pose value that is not finite.
+ * PLI_ERR_CAPACITY for more than PLI_BOW_MAX_FEATURES rows in n1 or in a neighbour.  nkf == 0, n1 == 0 and empty neighbours are
+ * valid.  The number of kernel launches does not depend on nkf. */
+enum {
+  PLI_NEWPT_CREATED = 0,          /* :670, a map point is created                                   */
+  PLI_NEWPT_LOW_PARALLAX = 1,     /* :582, no stereo and very low parallax                          */
+  PLI_NEWPT_W_ZERO = 2,           /* :565, x3D.at<float>(3) == 0                                    */
+  PLI_NEWPT_EMPTY_UNPROJECT = 3,  /* :587, UnprojectStereo returned an empty Mat (mvDepth <= 0)     */
+  PLI_NEWPT_Z1 = 4,               /* :590, z1 <= 0                                                  */
+  PLI_NEWPT_Z2 = 5,               /* :594, z2 <= 0                                                  */
+  PLI_NEWPT_REPROJ1_MONO = 6,     /* :609, > 5.991 * sigmaSquare1                                   */
+  PLI_NEWPT_REPROJ1_STEREO = 7,   /* :621, > 7.8 * sigmaSquare1                                     */
+  PLI_NEWPT_REPROJ2_MONO = 8,     /* :635                                                           */
+  PLI_NEWPT_REPROJ2_STEREO = 9,   /* :646                                                           */
+  PLI_NEWPT_DIST_ZERO = 10,       /* :657                                                           */
+  PLI_NEWPT_FAR = 11,             /* :660                                                           */
+  PLI_NEWPT_RATIO_LOW = 12,       /* :666, ratioDist*ratioFactor < ratioOctave                      */
+  PLI_NEWPT_RATIO_HIGH = 13,      /* :666, ratioDist > ratioOctave*ratioFactor                      */
+  PLI_NEWPT_TAKEN_EARLIER = 14,   /* matched on the state at entry, but an earlier neighbour created the feature's map point */
+  PLI_NEWPT_NOT_MATCHED = 15      /* SearchForTriangulation found no pair for the feature           */
+};
+pli_status pli_create_new_map_points(pli_ctx* ctx, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                     const uint8_t* has_mp1, const float* uright1, const float* depth1, const float* key1,
+                                     int32_t n1, int32_t nkf, const int32_t* kf_off, const pli_keypoint* kf_kp,
+                                     const uint8_t* kf_desc, const int32_t* kf_node, const uint8_t* kf_has_mp,
+                                     const float* kf_uright, const float* kf_depth, const float* kf_key, const float* F12,
+                                     const float* ep, const float* pose1, const float* kf_pose, const pli_fuse_camera* cam,
+                                     float mb, int32_t coarse, int32_t far_points, float th_far, float ratio_factor,
+                                     int32_t* matches12, int32_t* nmatches, int32_t* status, float* x3d, int32_t* nnew);
+
 /* Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) ORBmatcher.cc:473-586 and the
  * overload with vpPointsKFs / vpMatchedKF :588-704 (LoopClosing.cc:631, :656, :852), for ONE list of nmp map points against npair
  * (keyframe, Scw) pairs in one call.  Unlike Fuse this search is sequential across the points of a pair: vpMatched[bestIdx] = pMP

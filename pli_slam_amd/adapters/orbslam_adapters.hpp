@@ -649,6 +649,36 @@ inline void triangulationGeometry(const float R1w[9], const float t1w[3], const 
   gemm(B, false, 1.0, K2i, false, 3, nullptr, F12);
 }
 
+// One keyframe's side of SearchForTriangulation for keyframes of one pinhole camera each, as the batch form and
+// PliCreateNewMapPoints (orbslam_local_mapping.hpp) gather it: the flat tables, and the pose and intrinsics of the keyframe
+// gathered last (triangulationGeometry reads them).
+struct TriangulationTable : KfTable {
+  std::vector<pli_keypoint> kp;
+  std::vector<uint8_t> hasMp, stereo;
+  float R[9], t[3], K[4];
+};
+// appends pKF's rows; `who` names the caller and `what` the FeatureVector in the messages.  A keyframe of two cameras is refused.
+template <class KeyFrameT>
+void gatherTriangulationTable(KeyFrameT* pKF, TriangulationTable& T, const char* who, const char* what) {
+  if (pKF->mpCamera2 || pKF->NLeft != -1)
+    throw std::logic_error(std::string(who) + ": a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
+  const int n = pKF->N;
+  appendNodes(T, pKF->mFeatVec, n, what);
+  appendDescriptors(T, pKF->mDescriptors, n);
+  for (int i = 0; i < n; ++i) {
+    T.kp.push_back(keypoint(pKF->mvKeysUn[i]));
+    T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (ORBmatcher.cc:1033-1039, :1064-1068: isBad() is not asked)
+    T.stereo.push_back(pKF->mvuRight[i] >= 0 ? 1 : 0);
+  }
+  const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), K = pKF->mpCamera->toK();
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) T.R[i * 3 + j] = R.template at<float>(i, j);
+    T.t[i] = t.template at<float>(i);
+  }
+  T.K[0] = K.template at<float>(0, 0); T.K[1] = K.template at<float>(1, 1);
+  T.K[2] = K.template at<float>(0, 2); T.K[3] = K.template at<float>(1, 2);
+}
+
 // Where the two SearchByProjection(CurrentFrame, LastFrame, ...) overloads put a camera-frame point in the image, in the reference's
 // float operation order: pinholeProject = CurrentFrame.mpCamera->project(x3Dc) of the overload without match12 (ORBmatcher.cc:2002,
 // Pinhole.cpp:30-33: fx * x / z + cx); otherwise the overload with match12 (:2222-2223: fx * xc * invzc + cx, invzc = 1.0 / zc).
@@ -869,39 +899,15 @@ class PliORBmatcher {
   void SearchForTriangulation(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2,
                               std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, std::vector<int>& vnmatches,
                               const bool bOnlyStereo, const bool bCoarse = false) {
-    struct Table : pli_detail::KfTable {
-      std::vector<pli_keypoint> kp;
-      std::vector<uint8_t> hasMp, stereo;
-      float R[9], t[3], K[4];
-    };
-    auto gather = [](KeyFrameT* pKF, Table& T, const char* what) {
-      if (pKF->mpCamera2 || pKF->NLeft != -1)
-        throw std::logic_error("SearchForTriangulation: a keyframe of two cameras (mpCamera2 set, NLeft != -1) is not supported");
-      const int n = pKF->N;
-      pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
-      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
-      for (int i = 0; i < n; ++i) {
-        T.kp.push_back(pli_detail::keypoint(pKF->mvKeysUn[i]));
-        T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
-        T.stereo.push_back(pKF->mvuRight[i] >= 0 ? 1 : 0);
-      }
-      const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), K = pKF->mpCamera->toK();
-      for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) T.R[i * 3 + j] = R.template at<float>(i, j);
-        T.t[i] = t.template at<float>(i);
-      }
-      T.K[0] = K.template at<float>(0, 0); T.K[1] = K.template at<float>(1, 1);
-      T.K[2] = K.template at<float>(0, 2); T.K[3] = K.template at<float>(1, 2);
-    };
     const int nkf = (int)vpKF2.size();
-    Table T1, T2;
-    gather(pKF1, T1, "SearchForTriangulation: pKF1->mFeatVec");
+    pli_detail::TriangulationTable T1, T2;
+    pli_detail::gatherTriangulationTable(pKF1, T1, "SearchForTriangulation", "SearchForTriangulation: pKF1->mFeatVec");
     const int n1 = pKF1->N;
     const cv::Mat Cw = pKF1->GetCameraCenter();
     const float cw[3] = {Cw.template at<float>(0), Cw.template at<float>(1), Cw.template at<float>(2)};
     std::vector<float> F12((size_t)nkf * 9 + 1), ep((size_t)nkf * 2 + 1);
     for (int k = 0; k < nkf; ++k) {
-      gather(vpKF2[k], T2, "SearchForTriangulation: pKF2->mFeatVec");
+      pli_detail::gatherTriangulationTable(vpKF2[k], T2, "SearchForTriangulation", "SearchForTriangulation: pKF2->mFeatVec");
       pli_detail::triangulationGeometry(T1.R, T1.t, cw, T1.K, T2.R, T2.t, T2.K, &F12[(size_t)k * 9], &ep[(size_t)k * 2]);
     }
     std::vector<int> matches;

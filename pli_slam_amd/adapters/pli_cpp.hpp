@@ -204,6 +204,29 @@ class Frontend {
                                                    kfNode, kfHasMp, &camLeft, &camRight, rel, onlyStereo ? 1 : 0, coarse ? 1 : 0,
                                                    checkOrientation ? 1 : 0, matches12.data(), nmatches.data()));
   }
+  // LocalMapping::CreateNewMapPoints from the search on (LocalMapping.cc:423-684, keyframes of one pinhole camera) of one keyframe
+  // against nkf neighbours (include/pli_frontend.h pli_create_new_map_points): what the reference's sequential loop sees and creates
+  // at neighbour k - matches12, status (PLI_NEWPT_*) and x3d (x 3) are nkf x n1, nmatches and nnew have nkf entries
+  struct NewMapPoints {
+    std::vector<int> matches12, nmatches, status, nnew;
+    std::vector<float> x3d;
+  };
+  void createNewMapPoints(const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1, const uint8_t* hasMp1,
+                          const float* uright1, const float* depth1, const float* key1, int n1, int nkf, const int32_t* kfOff,
+                          const pli_keypoint* kfKp, const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
+                          const float* kfUright, const float* kfDepth, const float* kfKey, const float* F12, const float* ep,
+                          const float* pose1, const float* kfPose, const pli_fuse_camera& cam, float mb, bool coarse, bool farPoints,
+                          float thFar, float ratioFactor, NewMapPoints& out) {
+    out.matches12.assign((size_t)nkf * n1, -1);
+    out.status.assign((size_t)nkf * n1, PLI_NEWPT_NOT_MATCHED);
+    out.x3d.assign((size_t)nkf * n1 * 3, 0.f);
+    out.nmatches.assign(nkf, 0);
+    out.nnew.assign(nkf, 0);
+    check(pli_create_new_map_points(ctx_, kp1, desc1, node1, hasMp1, uright1, depth1, key1, n1, nkf, kfOff, kfKp, kfDesc, kfNode,
+                                    kfHasMp, kfUright, kfDepth, kfKey, F12, ep, pose1, kfPose, &cam, mb, coarse ? 1 : 0,
+                                    farPoints ? 1 : 0, thFar, ratioFactor, out.matches12.data(), out.nmatches.data(),
+                                    out.status.data(), out.x3d.data(), out.nnew.data()));
+  }
   // The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reprojGate = false: the Sim3 overload
   // :1611-1733) of nmp map points against nkf keyframes (include/pli_frontend.h pli_fuse_search): bestIdx (nkf x nmp) = the
   // keyframe's row or -1.  levelRatio: fuseLevelRatio() of the extractor's configuration.

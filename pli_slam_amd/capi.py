@@ -35,6 +35,11 @@ LOCAL_VIEW_DT = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4
                           ("level", "<i4"), ("in_view", "<i4"), ("pad", "<i4")])           # pli_local_view
 LOCAL_STORED_VIEW = 2                 # PLI_LOCAL_STORED_VIEW: a FUSE_POINT_DT row that carries the fields a skipped point still holds
 
+# the status codes of pli_create_new_map_points (PLI_NEWPT_*), in the header's order
+NEWPT_STATUS = ("created", "low_parallax", "w_zero", "empty_unproject", "z1", "z2", "reproj1_mono", "reproj1_stereo", "reproj2_mono",
+                "reproj2_stereo", "dist_zero", "far", "ratio_low", "ratio_high", "taken_earlier", "not_matched")
+NEWPT_CREATED, NEWPT_TAKEN_EARLIER, NEWPT_NOT_MATCHED = 0, 14, 15
+
 PLI_OK = 0
 ERRORS = {-1: "PLI_ERR_INVALID", -2: "PLI_ERR_EMPTY_IMAGE", -3: "PLI_ERR_CAPACITY", -4: "PLI_ERR_HIP",
           -5: "PLI_ERR_NO_DEVICE", -6: "PLI_ERR_STATE"}
@@ -211,6 +216,11 @@ _PROTOS = {
                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                              C.c_void_p, C.c_void_p]),
+    "pli_create_new_map_points": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.POINTER(FuseCamera), C.c_float, C.c_int32, C.c_int32, C.c_float,
+                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pli_fuse_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FuseCamera), C.c_float, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p]),

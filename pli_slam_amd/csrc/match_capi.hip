@@ -69,6 +69,13 @@ bool finiteOk(const pli_keypoint* kp, int64_t n, const char* what) {
   return true;
 }
 
+// (pli_create_new_map_points: mvuRight, mvDepth, mvKeys[i].pt and the poses enter float arithmetic whose results decide gates)
+bool floatsFinite(const float* v, int64_t n, const char* what) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) { g_err = std::string(what) + ": a value is not finite"; return false; }
+  return true;
+}
+
 // kf_nleft[k] = NLeft of keyframe k, inside its rows
 bool nleftOk(int32_t nkf, const int32_t* kfOff, const int32_t* kfNleft, const char* msg) {
   for (int k = 0; k < nkf; ++k)
@@ -1137,6 +1144,92 @@ pli_status pli_search_for_triangulation_two_cameras(pli_ctx* c, const pli_keypoi
          (const float2*)dR1, n1, n1Left, T.dOff, (const int*)dNl, T.dKk, T.dKd, (const float2*)dKr, T.dSn, T.dSi, T.dListed,
          (const float*)dRel, cl, cr, (const float*)dLv, coarse ? 1 : 0, checkOri ? 1 : 0, T.dM, T.dStat);
   return triEnd(c, B, n1, T, checkOri, matches12, nmatches);
+}
+
+pli_status pli_create_new_map_points(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                     const uint8_t* hasMp1, const float* uright1, const float* depth1, const float* key1, int32_t n1,
+                                     int32_t nkf, const int32_t* kfOff, const pli_keypoint* kfKp, const uint8_t* kfDesc,
+                                     const int32_t* kfNode, const uint8_t* kfHasMp, const float* kfUright, const float* kfDepth,
+                                     const float* kfKey, const float* F12, const float* ep, const float* pose1, const float* kfPose,
+                                     const pli_fuse_camera* cam, float mb, int32_t coarse, int32_t farPoints, float thFar,
+                                     float ratioFactor, int32_t* matches12, int32_t* nmatches, int32_t* status, float* x3d,
+                                     int32_t* nnew) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || nkf < 0 || !cam || !pose1 ||
+      (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1 || !uright1 || !depth1 || !key1)) ||
+      (nkf > 0 && (!kfOff || !F12 || !ep || !kfPose || !nmatches || !nnew)) ||
+      (nkf > 0 && n1 > 0 && (!matches12 || !status || !x3d))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the CreateNewMapPoints cap", B);
+  if (st != PLI_OK) return st;
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the CreateNewMapPoints cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = B.total, npairs = (int64_t)nkf * n1;
+  // (k_newpt_list indexes a pair with an int, rounded up to its block of 256)
+  if (npairs > INT32_MAX - 256) { g_err = "nkf x n1 does not fit the pair index"; return PLI_ERR_CAPACITY; }
+  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp || !kfUright || !kfDepth || !kfKey)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || !finiteOk(kp1, n1, "kp1")) return PLI_ERR_INVALID;
+  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
+  if (!floatsFinite(uright1, n1, "uright1") || !floatsFinite(depth1, n1, "depth1") || !floatsFinite(key1, 2 * (int64_t)n1, "key1") ||
+      !floatsFinite(kfUright, total, "kf_uright") || !floatsFinite(kfDepth, total, "kf_depth") ||
+      !floatsFinite(kfKey, 2 * total, "kf_key") || !floatsFinite(pose1, 15, "pose1") ||
+      !floatsFinite(kfPose, 15 * (int64_t)nkf, "kf_pose"))
+    return PLI_ERR_INVALID;
+  std::fill(nmatches, nmatches + nkf, 0);
+  std::fill(nnew, nnew + nkf, 0);
+  if (n1 == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  float hlv[2 * MAX_LEVELS] = {};
+  levelTables(c, hlv, hlv + MAX_LEVELS, nullptr);
+  // bStereo = mvuRight >= 0 (ORBmatcher.cc:1041, :1070; LocalMapping.cc:450, :459): the flag tables of the search
+  std::vector<uint8_t> stereo1(n1), kfStereo((size_t)total);
+  for (int i = 0; i < n1; ++i) stereo1[i] = uright1[i] >= 0;
+  for (int64_t i = 0; i < total; ++i) kfStereo[i] = kfUright[i] >= 0;
+  ScratchPlan plan;
+  const TriTables T = triTables(plan, B, kp1, desc1, node1, hasMp1, n1, kfKp, kfDesc, kfNode, kfHasMp);
+  auto dS1 = plan.in(stereo1.data(), n1);
+  auto dKs = plan.in(kfStereo.data(), total);
+  auto dF = plan.in(F12, (size_t)nkf * 9);
+  auto dEp = plan.in(ep, (size_t)nkf * 2);
+  auto dLv = plan.in(hlv, 2 * MAX_LEVELS);                 // mvScaleFactors, then mvLevelSigma2
+  auto dU1 = plan.in(uright1, n1);
+  auto dZ1 = plan.in(depth1, n1);
+  auto dP1 = plan.in(key1, (size_t)n1 * 2);
+  auto dKu = plan.in(kfUright, total);
+  auto dKz = plan.in(kfDepth, total);
+  auto dKp = plan.in(kfKey, (size_t)total * 2);
+  auto dPose1 = plan.in(pose1, 15);
+  auto dKpose = plan.in(kfPose, (size_t)nkf * 15);
+  auto dList = plan.add<int>(npairs);
+  auto dCnt = plan.add<int>(1 + 2 * (size_t)nkf);          // the list's length, nmatches[nkf], nnew[nkf]
+  auto dStatus = plan.add<int>(npairs);
+  auto dX = plan.add<float>((size_t)npairs * 3);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  HIPCHK(hipMemsetAsync(dCnt, 0, (1 + 2 * (size_t)nkf) * sizeof(int), c->stream));
+  const int keyCap = pow2Ceil(B.maxNk);
+  const int perBlock = 4 * 4;                                            // k_tri_match: 4 waves x TRI_PER_WAVE features of pKF1
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, T.dOff, 0, T.dKn, T.dKm, 0, dKs, 0,
+         keyCap, T.dSn, T.dSi, T.dListed, T.dStat);
+  LAUNCH(c, "k_tri_match", k_tri_match, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, T.dK1, T.dD1, T.dN1, T.dM1, dS1, n1,
+         T.dOff, T.dKk, T.dKd, dKs, T.dSn, T.dSi, T.dListed, dF, dEp, (const float*)dLv, (const float*)dLv + MAX_LEVELS,
+         0, coarse ? 1 : 0, 0, T.dM, T.dStat);
+  int* cnt = dCnt;
+  LAUNCH(c, "k_newpt_list", k_newpt_list, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, (const int*)T.dM, (int)npairs,
+         (int*)dList, cnt, (int*)dStatus, (float*)dX);
+  const NewPtTables D = {T.dK1, dU1, dZ1, (const float2*)(float*)dP1, dPose1, n1, T.dOff, T.dKk, dKu, dKz, (const float2*)(float*)dKp,
+                         dKpose, (const float*)dLv, (const float*)dLv + MAX_LEVELS};
+  const unsigned geoBlocks = (unsigned)std::min<int64_t>((npairs + 63) / 64, 2048);
+  LAUNCH(c, "k_newpt_geometry", k_newpt_geometry, dim3(geoBlocks), dim3(64), 0, D, *cam, mb, farPoints ? 1 : 0, thFar, ratioFactor,
+         (const int*)T.dM, (const int*)dList, (const int*)cnt, (int*)dStatus, (float*)dX);
+  LAUNCH(c, "k_newpt_pick", k_newpt_pick, dim3((n1 + 255) / 256), dim3(256), 0, n1, nkf, (int*)T.dM, (int*)dStatus, cnt + 1, cnt + 1 + nkf);
+  HIPCHK(download(c, matches12, T.dM));
+  HIPCHK(download(c, status, dStatus));
+  HIPCHK(download(c, x3d, dX));
+  HIPCHK(download(c, nmatches, dCnt, 1, nkf));
+  HIPCHK(download(c, nnew, dCnt, 1 + nkf, nkf));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
 }
 
 // The tables that the projection launch of a Fuse entry point reads and writes (lv: level_ratio, then mvScaleFactors)

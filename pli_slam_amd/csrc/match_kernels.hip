@@ -14,6 +14,7 @@
 //   k_node_sort + k_search_by_bow       ORBmatcher::SearchByBoW(KF,F)        (ORBmatcher.cc:269-470)
 //   k_node_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
 //   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_tri_finish  the same for keyframes of two KannalaBrandt8 cameras (mpCamera2)
+//   k_node_sort, k_tri_match, k_newpt_list, k_newpt_geometry, k_newpt_pick  LocalMapping::CreateNewMapPoints (LocalMapping.cc:423-684)
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 //   k_fuse_grid, k_fuse_project_views, k_fuse_match<8, true>  the same search for keyframes of two KannalaBrandt8 cameras, both values of bRight
@@ -2804,6 +2805,189 @@ __global__ __launch_bounds__(256) void k_fuse_project_views(const pli_fuse_point
     }
   }
   compact_survivor(keep, S, surv, nSurv);
+}
+
+// ---------------------------------------------------------------------------
+// LocalMapping::CreateNewMapPoints from the search on (LocalMapping.cc:425-684), keyframes of one pinhole camera (NLeft == -1, no
+// mpCamera2), for one keyframe against nkf neighbours (pli_create_new_map_points).  The search is k_node_sort + k_tri_match on the
+// map-point state at entry; what the sequential loop adds is, per feature of pKF1, "the first neighbour in which it is matched and
+// passes every gate keeps it, every later neighbour does not see it" (ORBmatcher.cc:1033-1039 after AddMapPoint at :675).
+//
+//   k_newpt_list        one thread per (neighbour, feature): the matched pairs of all neighbours into one list (ballot and popcount
+//                       prefix per wave, one atomic per wave; the list's order is free, results are written at (k, i)); the
+//                       unmatched ones get their status here.
+//   k_newpt_geometry    one lane per listed pair: :530-667 operation for operation, cv::Mat arithmetic as k_tri_match_kb8 and
+//                       k_fuse_project state it (a gemm row: double accumulation, one rounding; Mat::dot and cv::norm: sequential
+//                       double; s*row - row: the rounded product, then a float subtraction; Mat / s: a multiplication by
+//                       (float)(1/s); 1.0/z: the double reciprocal rounded once; the comparisons against 5.991*sigma2, 7.8*sigma2
+//                       and 0.9998 in double; a libm call on a float: in double, rounded; the rest float in the written order).
+//   k_newpt_pick        one thread per feature of pKF1: walks the neighbours in order, the first status 0 keeps the feature, every
+//                       later matched entry becomes -1 / PLI_NEWPT_TAKEN_EARLIER; counts nmatches and nnew per neighbour.
+//
+// Kept as the reference has them: `else if(bStereo2)` at :544 (the second keyframe's stereo parallax only when the first side is
+// not stereo), mpCurrentKeyFrame->mbf in the SECOND keyframe's stereo gate (:641), fx1..cy1 for the first and fx2..cy2 for the
+// second keyframe (one pli_fuse_camera serves both here: the call shares its camera), mvKeys (not mvKeysUn) in UnprojectStereo.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_newpt_list(const int* __restrict__ matches12, int npairs, int* __restrict__ list,
+                                                    int* __restrict__ nListed, int* __restrict__ status, float* __restrict__ x3d) {
+  const int p = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const bool matched = p < npairs && matches12[p] >= 0;
+  if (p < npairs) {
+    status[p] = PLI_NEWPT_NOT_MATCHED;                    // (a listed pair: k_newpt_geometry overwrites it)
+    x3d[3 * (int64_t)p] = 0.f; x3d[3 * (int64_t)p + 1] = 0.f; x3d[3 * (int64_t)p + 2] = 0.f;
+  }
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(matched);
+  if (bal == 0) return;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(nListed, __popcll(bal));
+  base = __shfl(base, 0);
+  if (matched) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = p;
+}
+
+struct NewPtSide {                                       // one keyframe's side of a pair
+  float x, y; int octave;                                // mvKeysUn[idx]
+  float ur, depth, keyX, keyY;                           // mvuRight[idx], mvDepth[idx], mvKeys[idx].pt
+  const float* T;                                        // Rcw row major, tcw, Ow
+};
+
+// KeyFrame::UnprojectStereo (KeyFrame.cc:932-948) for z > 0: Twc.rowRange(0,3).colRange(0,3)*x3Dc + Twc.rowRange(0,3).col(3)
+__device__ __forceinline__ void newpt_unproject_stereo(const NewPtSide& S, const pli_fuse_camera& cam, float invfx, float invfy,
+                                                       float x3[3]) {
+  const float xc[3] = {__fmul_rn(__fmul_rn(__fsub_rn(S.keyX, cam.cx), S.depth), invfx),
+                       __fmul_rn(__fmul_rn(__fsub_rn(S.keyY, cam.cy), S.depth), invfy), S.depth};
+  for (int r = 0; r < 3; ++r) x3[r] = cvmat_dot3(S.T + r, 3, xc, 1.0, (double)S.T[12 + r]);
+}
+
+// the reprojection gate of one keyframe (:597-623, :625-648): 0 = passed, 1 = the monocular bound, 2 = the stereo bound.
+// mbf is mpCurrentKeyFrame's for both keyframes (:616, :641).
+__device__ __forceinline__ int newpt_reproject(const NewPtSide& S, bool stereo, const pli_fuse_camera& cam, float mbf,
+                                               const float x3[3], float z, float sigma2) {
+  const float* T = S.T;
+  const float x = (float)(((double)T[0] * x3[0] + (double)T[1] * x3[1] + (double)T[2] * x3[2]) + (double)T[9]);
+  const float y = (float)(((double)T[3] * x3[0] + (double)T[4] * x3[1] + (double)T[5] * x3[2]) + (double)T[10]);
+  const float invz = (float)(1.0 / (double)z);
+  if (!stereo) {
+    const float u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);          // Pinhole::project, Pinhole.cpp:30-33
+    const float v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+    const float ex = __fsub_rn(u, S.x), ey = __fsub_rn(v, S.y);
+    return (double)__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)) > 5.991 * (double)sigma2 ? 1 : 0;
+  }
+  const float u = __fadd_rn(__fmul_rn(__fmul_rn(cam.fx, x), invz), cam.cx);
+  const float ur = __fsub_rn(u, __fmul_rn(mbf, invz));
+  const float v = __fadd_rn(__fmul_rn(__fmul_rn(cam.fy, y), invz), cam.cy);
+  const float ex = __fsub_rn(u, S.x), ey = __fsub_rn(v, S.y), er = __fsub_rn(ur, S.ur);
+  return (double)__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er)) > 7.8 * (double)sigma2 ? 2 : 0;
+}
+
+// cv::norm(x3D - Ow) as a float
+__device__ __forceinline__ float newpt_dist(const float x3[3], const float* Ow) {
+  double s = 0;
+  for (int r = 0; r < 3; ++r) { const float d = __fsub_rn(x3[r], Ow[r]); s += (double)d * d; }
+  return (float)sqrt(s);
+}
+
+// :530-667 for one matched pair; returns the status code, x3 is written where it returns PLI_NEWPT_CREATED
+__device__ __forceinline__ int newpt_pair(const NewPtSide& S1, const NewPtSide& S2, const pli_fuse_camera& cam, float mb,
+                                          int farPoints, float thFar, float ratioFactor, const float* __restrict__ scaleFactor,
+                                          const float* __restrict__ sigma2, float x3[3]) {
+  const bool stereo1 = S1.ur >= 0, stereo2 = S2.ur >= 0;
+  const float* T1 = S1.T;
+  const float* T2 = S2.T;
+  // xn = pCamera->unprojectMat(kp.pt) (Pinhole.cpp:59-62); ray = Rwc*xn with Rwc = Rcw.t()
+  const float xn1[3] = {__fdiv_rn(__fsub_rn(S1.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S1.y, cam.cy), cam.fy), 1.f};
+  const float xn2[3] = {__fdiv_rn(__fsub_rn(S2.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S2.y, cam.cy), cam.fy), 1.f};
+  float ray1[3], ray2[3];
+  for (int r = 0; r < 3; ++r) { ray1[r] = cvmat_dot3(T1 + r, 3, xn1, 1.0, 0.0); ray2[r] = cvmat_dot3(T2 + r, 3, xn2, 1.0, 0.0); }
+  const double dot = (double)ray1[0] * ray2[0] + (double)ray1[1] * ray2[1] + (double)ray1[2] * ray2[2];
+  const double n1 = sqrt((double)ray1[0] * ray1[0] + (double)ray1[1] * ray1[1] + (double)ray1[2] * ray1[2]);
+  const double n2 = sqrt((double)ray2[0] * ray2[0] + (double)ray2[1] * ray2[1] + (double)ray2[2] * ray2[2]);
+  const float cosRays = (float)(dot / (n1 * n2));
+  float cosStereo = __fadd_rn(cosRays, 1.f);
+  float cosStereo1 = cosStereo, cosStereo2 = cosStereo;
+  if (stereo1) cosStereo1 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S1.depth)));
+  else if (stereo2) cosStereo2 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S2.depth)));
+  cosStereo = cosStereo2 < cosStereo1 ? cosStereo2 : cosStereo1;                   // min(cosParallaxStereo1, cosParallaxStereo2)
+  const float invfx = __fdiv_rn(1.0f, cam.fx), invfy = __fdiv_rn(1.0f, cam.fy);     // Frame.cc: invfx = 1.0f/fx
+  if (cosRays < cosStereo && cosRays > 0 && (stereo1 || stereo2 || (double)cosRays < 0.9998)) {
+    float At[4][4];                                       // A transposed; Tcw = [Rcw | tcw]
+    for (int b = 0; b < 4; ++b) {
+      const float t1r0 = b < 3 ? T1[b] : T1[9], t1r1 = b < 3 ? T1[3 + b] : T1[10], t1r2 = b < 3 ? T1[6 + b] : T1[11];
+      const float t2r0 = b < 3 ? T2[b] : T2[9], t2r1 = b < 3 ? T2[3 + b] : T2[10], t2r2 = b < 3 ? T2[6 + b] : T2[11];
+      At[b][0] = __fsub_rn(__fmul_rn(xn1[0], t1r2), t1r0);
+      At[b][1] = __fsub_rn(__fmul_rn(xn1[1], t1r2), t1r1);
+      At[b][2] = __fsub_rn(__fmul_rn(xn2[0], t2r2), t2r0);
+      At[b][3] = __fsub_rn(__fmul_rn(xn2[1], t2r2), t2r1);
+    }
+    float vh[4];
+    jacobi_svd_last_vt4(At, vh);
+    if (vh[3] == 0) return PLI_NEWPT_W_ZERO;
+    const float inv = (float)(1.0 / (double)vh[3]);
+    for (int r = 0; r < 3; ++r) x3[r] = __fadd_rn(__fmul_rn(vh[r], inv), 0.f);
+  } else if (stereo1 && cosStereo1 < cosStereo2) {
+    if (!(S1.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
+    newpt_unproject_stereo(S1, cam, invfx, invfy, x3);
+  } else if (stereo2 && cosStereo2 < cosStereo1) {
+    if (!(S2.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
+    newpt_unproject_stereo(S2, cam, invfx, invfy, x3);
+  } else {
+    return PLI_NEWPT_LOW_PARALLAX;
+  }
+  const float z1 = (float)(((double)T1[6] * x3[0] + (double)T1[7] * x3[1] + (double)T1[8] * x3[2]) + (double)T1[11]);
+  if (z1 <= 0) return PLI_NEWPT_Z1;
+  const float z2 = (float)(((double)T2[6] * x3[0] + (double)T2[7] * x3[1] + (double)T2[8] * x3[2]) + (double)T2[11]);
+  if (z2 <= 0) return PLI_NEWPT_Z2;
+  const float mbf = cam.bf;
+  int g = newpt_reproject(S1, stereo1, cam, mbf, x3, z1, sigma2[S1.octave]);
+  if (g) return g == 1 ? PLI_NEWPT_REPROJ1_MONO : PLI_NEWPT_REPROJ1_STEREO;
+  g = newpt_reproject(S2, stereo2, cam, mbf, x3, z2, sigma2[S2.octave]);
+  if (g) return g == 1 ? PLI_NEWPT_REPROJ2_MONO : PLI_NEWPT_REPROJ2_STEREO;
+  const float dist1 = newpt_dist(x3, T1 + 12), dist2 = newpt_dist(x3, T2 + 12);
+  if (dist1 == 0 || dist2 == 0) return PLI_NEWPT_DIST_ZERO;
+  if (farPoints && (dist1 >= thFar || dist2 >= thFar)) return PLI_NEWPT_FAR;
+  const float ratioDist = __fdiv_rn(dist2, dist1);
+  const float ratioOctave = __fdiv_rn(scaleFactor[S1.octave], scaleFactor[S2.octave]);
+  if (__fmul_rn(ratioDist, ratioFactor) < ratioOctave) return PLI_NEWPT_RATIO_LOW;
+  if (ratioDist > __fmul_rn(ratioOctave, ratioFactor)) return PLI_NEWPT_RATIO_HIGH;
+  return PLI_NEWPT_CREATED;
+}
+
+// grid-stride over the list (its length is the device's); 64 threads: the Jacobi's registers
+__global__ __launch_bounds__(64) void k_newpt_geometry(NewPtTables D, pli_fuse_camera cam, float mb, int farPoints, float thFar,
+                                                       float ratioFactor, const int* __restrict__ matches12,
+                                                       const int* __restrict__ list, const int* __restrict__ nListed,
+                                                       int* __restrict__ status, float* __restrict__ x3d) {
+  const int n = *nListed;
+  for (int e = blockIdx.x * 64 + threadIdx.x; e < n; e += gridDim.x * 64) {
+    const int p = list[e], k = p / D.n1, i = p - k * D.n1;
+    const int j = D.kfOff[k] + matches12[p];
+    const pli_keypoint a = D.kp1[i], b = D.kfKp[j];
+    const float2 ka = D.key1[i], kb = D.kfKey[j];
+    const NewPtSide S1 = {a.x, a.y, a.octave, D.ur1[i], D.depth1[i], ka.x, ka.y, D.pose1};
+    const NewPtSide S2 = {b.x, b.y, b.octave, D.kfUr[j], D.kfDepth[j], kb.x, kb.y, D.kfPose + 15 * (int64_t)k};
+    float x3[3] = {0.f, 0.f, 0.f};
+    const int st = newpt_pair(S1, S2, cam, mb, farPoints, thFar, ratioFactor, D.scaleFactor, D.sigma2, x3);
+    status[p] = st;
+    if (st == PLI_NEWPT_CREATED) { x3d[3 * (int64_t)p] = x3[0]; x3d[3 * (int64_t)p + 1] = x3[1]; x3d[3 * (int64_t)p + 2] = x3[2]; }
+  }
+}
+
+// counts: nmatches[nkf] then nnew[nkf], zeroed by the caller
+__global__ __launch_bounds__(256) void k_newpt_pick(int n1, int nkf, int* __restrict__ matches12, int* __restrict__ status,
+                                                    int* __restrict__ nmatches, int* __restrict__ nnew) {
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  bool taken = false;
+  for (int k = 0; k < nkf; ++k) {                         // (uniform over the wave: the ballots see every lane)
+    bool matched = false, created = false;
+    if (i < n1) {
+      const int64_t p = (int64_t)k * n1 + i;
+      matched = matches12[p] >= 0;
+      if (matched && taken) { matches12[p] = -1; status[p] = PLI_NEWPT_TAKEN_EARLIER; matched = false; }
+      else if (matched && status[p] == PLI_NEWPT_CREATED) { created = true; taken = true; }
+    }
+    const unsigned long long bm = __builtin_amdgcn_ballot_w64(matched), bc = __builtin_amdgcn_ballot_w64(created);
+    if (lane == 0 && bm) atomicAdd(nmatches + k, __popcll(bm));
+    if (lane == 0 && bc) atomicAdd(nnew + k, __popcll(bc));
+  }
 }
 
 __global__ void k_fill_f32(float* __restrict__ dst, int n, float v) {

@@ -94,6 +94,8 @@ def pack_keyframes(kfs, spec, what):
 
 BOW_COLUMNS = ((0, np.uint8, (32,)), (1, np.float32, ()), (2, np.int32, ()), (3, np.uint8, ()))      # desc, angle, node, valid
 TRI_COLUMNS = ((0, KEYPOINT_DT, ()), (1, np.uint8, (32,)), (2, np.int32, ()), (3, np.uint8, ()), (4, np.uint8, ()))
+# kp, desc, node, has_mp, uright, depth, mvKeys[i].pt
+NEWPT_COLUMNS = TRI_COLUMNS[:4] + ((4, np.float32, ()), (5, np.float32, ()), (6, np.float32, (2,)))
 FUSE_COLUMNS = ((0, KEYPOINT_DT, ()), (1, np.uint8, (32,)), (2, np.float32, ()))                     # kp, desc, uright
 
 
@@ -394,6 +396,38 @@ class Frontend:
                                                               ptr(cr), ptr(rel), int(only_stereo), int(coarse),
                                                               int(check_orientation), ptr(matches), ptr(nmatches)))
         return matches, nmatches
+
+    def create_new_map_points(self, kf1, kfs, cam, mb, ratio_factor, coarse=False, far_points=False, th_far=0.0):
+        """LocalMapping::CreateNewMapPoints from the search on (LocalMapping.cc:423-684, keyframes of one pinhole camera) of
+        keyframe `kf1` against every neighbour of `kfs`, in one call (include/pli_frontend.h pli_create_new_map_points).
+        kf1: (kp, desc, node, has_mp, uright, depth, key, pose) - mvKeysUn as KEYPOINT_DT rows, mDescriptors, the FeatureVector
+        node that lists a feature (-1: none), map point set, mvuRight, mvDepth, mvKeys[i].pt (n x 2), pose = 15 floats (Rcw row
+        major, tcw, Ow); kfs: list of (kp, desc, node, has_mp, uright, depth, key, pose, F12, ep) per neighbour.  cam:
+        capi.FuseCamera or its 9 values (fx, fy, cx, cy, bf are read); mb; ratio_factor = 1.5f * mfScaleFactor in float.
+        Returns (matches12[nkf, n1], nmatches[nkf], status[nkf, n1] (capi.NEWPT_*), x3d[nkf, n1, 3], nnew[nkf]): what the
+        reference's sequential loop sees and creates at neighbour k."""
+        what = "every feature needs one keypoint, descriptor, node, has_mp flag, uright, depth and mvKeys point"
+        k1, d1, n1, m1, u1, z1, p1 = pack_keyframes([kf1], NEWPT_COLUMNS, what)[1]
+        nkf = len(kfs)
+        off, (kk, kd, kn, km, ku, kz, kp) = pack_keyframes(kfs, NEWPT_COLUMNS, what)
+        pose1 = np.ascontiguousarray(kf1[7], np.float32).reshape(15)
+        pose = np.ascontiguousarray([np.asarray(kf[7], np.float32).reshape(15) for kf in kfs], np.float32).reshape(nkf, 15)
+        f12 = np.ascontiguousarray([np.asarray(kf[8], np.float32).reshape(9) for kf in kfs], np.float32).reshape(nkf, 9)
+        ep = np.ascontiguousarray([np.asarray(kf[9], np.float32).reshape(2) for kf in kfs], np.float32).reshape(nkf, 2)
+        if not isinstance(cam, capi.FuseCamera):
+            cam = capi.FuseCamera(*[float(v) for v in cam])
+        n = len(n1)
+        matches = np.full((nkf, n), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        status = np.full((nkf, n), capi.NEWPT_NOT_MATCHED, np.int32)
+        x3d = np.zeros((nkf, n, 3), np.float32)
+        nnew = np.zeros(nkf, np.int32)
+        check(self.L.pli_create_new_map_points(self.h, ptr(k1), ptr(d1), ptr(n1), ptr(m1), ptr(u1), ptr(z1), ptr(p1), n, nkf,
+                                               ptr(off), ptr(kk), ptr(kd), ptr(kn), ptr(km), ptr(ku), ptr(kz), ptr(kp), ptr(f12),
+                                               ptr(ep), ptr(pose1), ptr(pose), C.byref(cam), float(mb), int(coarse),
+                                               int(far_points), float(th_far), float(ratio_factor), ptr(matches), ptr(nmatches),
+                                               ptr(status), ptr(x3d), ptr(nnew)))
+        return matches, nmatches, status, x3d, nnew
 
     def _level_ratio(self, level_ratio):
         """The level_ratio table of the projection searches: the caller's, or this host's (fuse_level_ratio), made once."""
