@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <map>
 #include "../../include/pli_frontend.h"
@@ -190,11 +191,12 @@ struct LsdFrontPlanes {
   int packW;           // the owner word (rec.w where there is no hot record) = tx_unclaimed_norm_word: LAZY ids
 };
 
-// arguments of k_tx_tail (lsd_tile.hip): the rounds t >= t0 of the tile relaxation in one persistent launch
-struct TxTailArgs {
+// the planes of the tile relaxation (lsd_tile.hip): what every kernel of a round takes, by value — the host fills one per call
+// (runLines, pli_capi.hip) and launches with copies that differ in a field (DL without lists, the hot plane of round 1 / of the later rounds)
+struct TxRound {
   const DevParams* Pp;
   RxCtl* ctl;
-  const float4* rec;
+  const float4* rec;   // the 16-byte pixel records (the packed round 1 claims into their fourth words)
   int2* own;
   const int2* list;
   const int* tileCnt;
@@ -204,6 +206,7 @@ struct TxTailArgs {
   int* rgDirty;
   int* tileAct;
   int* tileTouch;
+  int W, H;            // the scaled image (Pp->LW, Pp->LH)
   int TW, TH;
   int* arena;
   int arenaCap;
@@ -212,13 +215,20 @@ struct TxTailArgs {
   float4* rgSeg;
   const double* mg;
   const int* rank;
-  int* rgLost;
+  int* rgLost;         // or null: the conservative round-2 rule, nobody notes the losers of contested claims
   TxDirtyLists DL;
-  int img0, nimg, t0, maxRounds;
+  int img0, nimg;
+  int2* hot;           // the hot records {angle, ..}: the growers take the angles from there (and `rec` is not read), or null
+  const float2* cold;  // ... with the exact {cos, sin} plane beside them
+};
+static_assert(std::is_trivially_copyable<TxRound>::value, "TxRound is a kernel argument");
+
+// arguments of k_tx_tail (lsd_tile.hip): the rounds t >= t0 of the tile relaxation in one persistent launch
+struct TxTailArgs {
+  TxRound R;
+  int t0, maxRounds;
   unsigned* bar;       // [0] arrivals (zeroed by the host before the launch), [32] abort word (its own line)
   int forceAbort = 0;  // test switch: behave as if the first grid barrier had timed out
-  int2* hot = nullptr; // the hot records {angle, ..}: the growers take the angles from there (and `rec` is not read), or null
-  const float2* cold = nullptr;   // ... with the exact {cos, sin} plane beside them
 };
 
 // a region in mid-growth, handed from the lane grower to the wave grower

@@ -353,11 +353,16 @@ __device__ __forceinline__ void tx_mark_dirty(int o, int t, int* __restrict__ rg
 }
 
 #ifdef PLI_DEV     // (the unfused round 2 of the dev switches PLI_TX_NOFUSE2 / PLI_TX_BOXRULE; the product's round 2 is k_tx_round2)
-__global__ __launch_bounds__(256) void k_tx_diff2(RxCtl* __restrict__ ctl, const int2* __restrict__ ownAll,
-                                                  const int* __restrict__ orderAll, const int2* __restrict__ rgBoxAll,
-                                                  int* __restrict__ rgDirtyAll, int* __restrict__ tileMinAll,
-                                                  int* __restrict__ tileActAll, int W, int H, int TW, int TH, int ts, int t,
-                                                  int img0, const int* __restrict__ rgLostAll, TxDirtyLists DL) {
+__global__ __launch_bounds__(256) void k_tx_diff2(TxRound A, int t, int* __restrict__ tileMinAll) {
+  RxCtl* __restrict__ ctl = A.ctl;
+  const int2* __restrict__ ownAll = A.own;
+  const int* __restrict__ orderAll = A.DL.order;
+  const int2* __restrict__ rgBoxAll = A.rgBox;
+  int* __restrict__ rgDirtyAll = A.rgDirty;
+  int* __restrict__ tileActAll = A.tileAct;
+  const int* __restrict__ rgLostAll = A.rgLost;           // (null: the conservative rule)
+  const int W = A.W, H = A.H, TW = A.TW, TH = A.TH, ts = A.ts, img0 = A.img0;
+  const TxDirtyLists& DL = A.DL;
   __shared__ int tmin[4];
   const int img = blockIdx.z + img0;
   RxCtl& c = ctl[img];
@@ -505,16 +510,16 @@ __device__ __forceinline__ void tx_round2_block(RxCtl* __restrict__ ctl, int2* _
   }
 }
 
+template <bool PACKED>
+__device__ __forceinline__ void tx_round2_block(const TxRound& A, int t, const float4* recPack, int keepRect) {
+  tx_round2_block<PACKED>(A.ctl, A.own, A.rank, A.DL.order, A.rgBox, A.rgDirty, A.tileAct, A.W, A.H, A.TW, A.TH, t, A.img0, A.rgLost, A.DL,
+                          A.tileTouch, recPack, keepRect, A.hot);
+}
+// (A.hot: round 1's hot records, or recPack: its 16-byte records when the owner words are packed there, or neither: the owner plane)
 // (two instances: a test of the argument inside the unrolled row loops keeps the four rows' loads from being issued together)
-__global__ __launch_bounds__(256) void k_tx_round2(RxCtl* __restrict__ ctl, int2* __restrict__ ownAll,
-                                                   const int* __restrict__ rankAll, const int* __restrict__ orderAll,
-                                                   const int2* __restrict__ rgBoxAll, int* __restrict__ rgDirtyAll,
-                                                   int* __restrict__ tileActAll, int W, int H, int TW, int TH, int t, int img0,
-                                                   const int* __restrict__ rgLostAll, TxDirtyLists DL,
-                                                   int* __restrict__ tileTouchAll, const float4* __restrict__ recPack, int keepRect,
-                                                   const int2* __restrict__ hotPack) {
-  if (recPack || hotPack) tx_round2_block<true>(ctl, ownAll, rankAll, orderAll, rgBoxAll, rgDirtyAll, tileActAll, W, H, TW, TH, t, img0, rgLostAll, DL, tileTouchAll, recPack, keepRect, hotPack);
-  else tx_round2_block<false>(ctl, ownAll, rankAll, orderAll, rgBoxAll, rgDirtyAll, tileActAll, W, H, TW, TH, t, img0, rgLostAll, DL, tileTouchAll, recPack, keepRect, hotPack);
+__global__ __launch_bounds__(256) void k_tx_round2(TxRound A, int t, const float4* __restrict__ recPack, int keepRect) {
+  if (recPack || A.hot) tx_round2_block<true>(A, t, recPack, keepRect);
+  else tx_round2_block<false>(A, t, recPack, keepRect);
 }
 // (after round 1's region2rect pass, when it ran beside k_tx_round2: the list counter of the images that are still relaxing starts round 2 at zero)
 __global__ __launch_bounds__(256) void k_tx_reset_rect(RxCtl* __restrict__ ctl, int nimg, int img0) {
@@ -529,11 +534,16 @@ __global__ __launch_bounds__(256) void k_tx_reset_rect(RxCtl* __restrict__ ctl, 
 // dependent chain neighbour owner -> rgLost -> stamp runs once per block, not once per row of cells.
 // ---------------------------------------------------------------------------
 #ifdef PLI_DEV     // (the unfused marks of the dev switch PLI_TX_NOFUSEDM; the product runs k_tx_diffmark / the cell lists)
-__global__ __launch_bounds__(256) void k_tx_mark(RxCtl* __restrict__ ctl, const int2* __restrict__ ownAll,
-                                                 const int* __restrict__ rankAll, const int2* __restrict__ rgBoxAll,
-                                                 int* __restrict__ rgDirtyAll, const int* __restrict__ tileMinAll,
-                                                 int* __restrict__ tileActAll, int W, int H, int TW, int TH, int t, int img0,
-                                                 const int* __restrict__ rgLostAll, TxDirtyLists DL) {
+__global__ __launch_bounds__(256) void k_tx_mark(TxRound A, int t, const int* __restrict__ tileMinAll) {
+  RxCtl* __restrict__ ctl = A.ctl;
+  const int2* __restrict__ ownAll = A.own;
+  const int* __restrict__ rankAll = A.rank;
+  const int2* __restrict__ rgBoxAll = A.rgBox;
+  int* __restrict__ rgDirtyAll = A.rgDirty;
+  int* __restrict__ tileActAll = A.tileAct;
+  const int* __restrict__ rgLostAll = A.rgLost;
+  const int W = A.W, H = A.H, TW = A.TW, TH = A.TH, img0 = A.img0;
+  const TxDirtyLists& DL = A.DL;
   __shared__ int s_chg[8][4];
   __shared__ int s_n;
   __shared__ unsigned short lst[2048];
@@ -676,13 +686,12 @@ __device__ __forceinline__ void tx_diffmark_block(RxCtl* ctl, const int2* ownAll
   }
 }
 
-__global__ __launch_bounds__(256) void k_tx_diffmark(RxCtl* __restrict__ ctl, const int2* __restrict__ ownAll,
-                                                     const int* __restrict__ rankAll, const int2* __restrict__ rgBoxAll,
-                                                     int* __restrict__ rgDirtyAll, int* __restrict__ tileActAll,
-                                                     const int* __restrict__ tileTouchAll, int W, int H, int TW, int TH, int t,
-                                                     int img0, const int* __restrict__ rgLostAll, TxDirtyLists DL) {
-  tx_diffmark_block(ctl, ownAll, rankAll, rgBoxAll, rgDirtyAll, tileActAll, tileTouchAll, W, H, TW, TH, t, blockIdx.x, blockIdx.y,
-                    blockIdx.z + img0, rgLostAll, DL);
+__device__ __forceinline__ void tx_diffmark_block(const TxRound& A, int t, int bx, int by, int img) {
+  tx_diffmark_block(A.ctl, A.own, A.rank, A.rgBox, A.rgDirty, A.tileAct, A.tileTouch, A.W, A.H, A.TW, A.TH, t, bx, by, img, A.rgLost, A.DL);
+}
+
+__global__ __launch_bounds__(256) void k_tx_diffmark(TxRound A, int t) {
+  tx_diffmark_block(A, t, blockIdx.x, blockIdx.y, blockIdx.z + A.img0);
 }
 
 // ---------------------------------------------------------------------------
@@ -751,11 +760,13 @@ __device__ __forceinline__ void tx_prep_block(RxCtl* ctl, int2* ownAll, const in
   }
 }
 
-__global__ __launch_bounds__(256) void k_tx_prep(RxCtl* __restrict__ ctl, int2* __restrict__ ownAll,
-                                                 const int* __restrict__ rankAll, const int* __restrict__ rgDirtyAll,
-                                                 const int* __restrict__ tileActAll, int W, int H, int TW, int TH, int t, int img0,
-                                                 int full, int* __restrict__ tileTouchAll, int rmask, int stamp) {
-  tx_prep_block(ctl, ownAll, rankAll, rgDirtyAll, tileActAll, W, H, TW, TH, t, blockIdx.x, blockIdx.y, blockIdx.z + img0, full, tileTouchAll, rmask, stamp);
+// (A.tileTouch null: the round's diff and marks were separate passes — dev schedules —, `changed` alone is the flag and no cell is stamped)
+__device__ __forceinline__ void tx_prep_block(const TxRound& A, int t, int bx, int by, int img, int full) {
+  tx_prep_block(A.ctl, A.own, A.rank, A.rgDirty, A.tileAct, A.W, A.H, A.TW, A.TH, t, bx, by, img, full, A.tileTouch, A.DL.rmask, A.DL.stamp);
+}
+
+__global__ __launch_bounds__(256) void k_tx_prep(TxRound A, int t, int full) {
+  tx_prep_block(A, t, blockIdx.x, blockIdx.y, blockIdx.z + A.img0, full);
 }
 
 // ---------------------------------------------------------------------------
@@ -841,11 +852,16 @@ __global__ __launch_bounds__(256) void k_tx_cells(RxCtl* __restrict__ ctl, const
 // (owner_{t-1} != owner_{t-2}) and the rule of k_tx_mark on their neighbours
 // (single-wave workgroups: the waves do not talk to each other, and the kernel runs beside the ORB chain — the smaller the workgroup,
 // the sooner it finds its wave slots)
-__global__ __launch_bounds__(64) void k_tx_diffmark_cells(RxCtl* __restrict__ ctl, const int2* __restrict__ ownAll, const int* __restrict__ rankAll,
-                                                           const int2* __restrict__ rgBoxAll, int* __restrict__ rgDirtyAll,
-                                                           int* __restrict__ tileActAll, int W, int H, int TW, int TH, int t, int img0,
-                                                           const int* __restrict__ rgLostAll, TxDirtyLists DL, const int* __restrict__ list,
-                                                           const int* __restrict__ cnt) {
+__global__ __launch_bounds__(64) void k_tx_diffmark_cells(TxRound A, int t, const int* __restrict__ list, const int* __restrict__ cnt) {
+  RxCtl* __restrict__ ctl = A.ctl;
+  const int2* __restrict__ ownAll = A.own;
+  const int* __restrict__ rankAll = A.rank;
+  const int2* __restrict__ rgBoxAll = A.rgBox;
+  int* __restrict__ rgDirtyAll = A.rgDirty;
+  int* __restrict__ tileActAll = A.tileAct;
+  const int* __restrict__ rgLostAll = A.rgLost;
+  const int W = A.W, H = A.H, TW = A.TW, TH = A.TH, img0 = A.img0;
+  const TxDirtyLists& DL = A.DL;
   constexpr int U = 4;
   __shared__ unsigned char slots[1][64];
   const int lane = threadIdx.x & 63, wv = 0;
@@ -920,9 +936,11 @@ __global__ __launch_bounds__(64) void k_tx_diffmark_cells(RxCtl* __restrict__ ct
 }
 
 // one wave per listed cell, four cells at a time: owner_t of the cells' pixels (k_tx_prep's rule)
-__global__ __launch_bounds__(64) void k_tx_prep_cells(const RxCtl* __restrict__ ctl, int2* __restrict__ ownAll, const int* __restrict__ rankAll,
-                                                       const int* __restrict__ rgDirtyAll, int W, int H, int TW, int TH, int t, int img0, int rmask,
-                                                       const int* __restrict__ list, const int* __restrict__ cnt, int stamp) {
+__global__ __launch_bounds__(64) void k_tx_prep_cells(TxRound A, int t, const int* __restrict__ list, const int* __restrict__ cnt) {
+  int2* __restrict__ ownAll = A.own;
+  const int* __restrict__ rankAll = A.rank;
+  const int* __restrict__ rgDirtyAll = A.rgDirty;
+  const int W = A.W, H = A.H, TW = A.TW, TH = A.TH, img0 = A.img0, rmask = A.DL.rmask, stamp = A.DL.stamp;
   constexpr int U = 4;
   const int lane = threadIdx.x & 63;
   const int il = blockIdx.y, ncell = TW * TH;
@@ -2066,6 +2084,14 @@ __device__ __forceinline__ void tx_grow_tile(const DevParams* __restrict__ Pp, R
     }
   }
 }
+// (what the kernels call: the planes from the round's record)
+template <bool SPARSE, bool SPEC = false, int GQ = TX_GQ, int PACK = 0, bool HOT = false>
+__device__ __forceinline__ void tx_grow_tile(const TxRound& A, int img, int tile, int t, int* q, int* gb, int* park,
+                                             const TxKeys* keysp = nullptr) {
+  tx_grow_tile<SPARSE, SPEC, GQ, PACK, HOT>(A.Pp, A.ctl, A.rec, A.own, A.list, A.tileCnt, A.ts, A.ntx, A.nty, A.rgSize, A.rgBox, A.rgDirty,
+                                            A.tileAct, A.TW, A.TH, A.arena, A.arenaCap, A.rects, A.rectCap, img, tile, t, A.rank, A.rgLost,
+                                            A.tileTouch, A.DL, q, gb, park, keysp, HOT ? A.hot : nullptr, HOT ? A.cold : nullptr);
+}
 
 // k_tx_order: the (image, tile) pairs of a launch of k_tx_grow in order of decreasing seed count (64 buckets of 64 seeds; inside a
 // bucket any order), by one workgroup: a histogram, its scan from the top, and a scatter with one cursor per bucket.
@@ -2086,21 +2112,11 @@ __global__ __launch_bounds__(1024) void k_tx_order(const int* __restrict__ tileC
 }
 #endif
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
-                                                const float4* __restrict__ recAll, int2* __restrict__ ownAll,
-                                                const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
-                                                int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
-                                                int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,
-                                                const int* __restrict__ tileActAll, int TW, int TH,
-                                                int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
-                                                int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL) {
-  __shared__ int q[TX_GQ];
-  __shared__ int gb[TX_BMAXBLK];
-  __shared__ int park[TX_PARK];
-  // (the tiles with the most seeds first, k_tx_order: the waves that take longest start first and the launch does not end on a few of them)
-  int img = blockIdx.y, tile = blockIdx.x;
-  if (DL.perm) {
+// Round 1, one wave per tile of every image: which (image, tile) workgroup (blockIdx.x, blockIdx.y) of the launch takes
+__device__ __forceinline__ void tx_round1_tile(const TxDirtyLists& DL, bool ordered, int& img, int& tile) {
+  img = blockIdx.y; tile = blockIdx.x;
+  if (ordered && DL.perm) {
+    // (the tiles with the most seeds first, k_tx_order: the waves that take longest start first and the launch does not end on a few of them)
     const int v = DL.perm[blockIdx.y * gridDim.x + blockIdx.x];
     img = v / (int)gridDim.x;
     tile = v - img * (int)gridDim.x;
@@ -2111,84 +2127,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     img = (k / (int)gridDim.x) * 8 + xcd;
     tile = k % (int)gridDim.x;
   }
-  tx_grow_tile<false>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll, TW, TH,
-                   arenaAll, arenaCap, rectAll, rectCap, img + img0, tile, t, rankAll, rgLostAll, tileTouchAll, DL, q, gb, park);
 }
-// round 1 with owner_1 packed into the pixel records (CV_64F detector; the host picks it, pli_capi.hip)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_p1(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
-                                                float4* recAll /* written: the claims */, int2* __restrict__ ownAll,
-                                                const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
-                                                int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
-                                                int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,
-                                                const int* __restrict__ tileActAll, int TW, int TH,
-                                                int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
-                                                int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL, TxKeys keys) {
+// PACK: owner_1 packed into the pixel records (CV_64F detector; the host picks it, pli_capi.hip) — 1: k_tx_sort wrote the unclaimed
+// words, 2: LAZY ids (key mode: the front pass wrote them, k_tx_sort touches neither the records nor the owner plane).  HOT: round 1's
+// words in the 8-byte hot records (round 6; A.hot, A.cold).  Only the plain form is launched in k_tx_order's order.
+template <int PACK, bool HOT>
+__device__ __forceinline__ void tx_grow_round1(const TxRound& A, int t, const TxKeys* keysp) {
   __shared__ int q[TX_GQ];
-  __shared__ int gb[TX_BMAXBLK];
+  __shared__ int gb[TX_BMAXBLK + (HOT ? 4 : 0)];        // (HOT: + the exact sums' three words, tx_grow_tile)
   __shared__ int park[TX_PARK];
-  int img = blockIdx.y, tile = blockIdx.x;
-  if (DL.xcdAffine) {                                     // (as in k_tx_grow)
-    const int L = blockIdx.y * gridDim.x + blockIdx.x, xcd = L & 7, k = L >> 3;
-    img = (k / (int)gridDim.x) * 8 + xcd;
-    tile = k % (int)gridDim.x;
-  }
-  tx_grow_tile<false, false, TX_GQ, 1>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll,
-                                       TW, TH, arenaAll, arenaCap, rectAll, rectCap, img + img0, tile, 1, rankAll, rgLostAll, tileTouchAll, DL,
-                                       q, gb, park);
+  int img, tile;
+  tx_round1_tile(A.DL, PACK == 0 && !HOT, img, tile);
+  tx_grow_tile<false, false, TX_GQ, PACK, HOT>(A, img + A.img0, tile, t, q, gb, park, keysp);
 }
-// ... and with LAZY ids (key mode: the front pass wrote the unclaimed words, k_tx_sort touches neither the records nor the owner plane)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_p2(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
-                                                float4* recAll /* written: the claims */, int2* __restrict__ ownAll,
-                                                const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
-                                                int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
-                                                int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,
-                                                const int* __restrict__ tileActAll, int TW, int TH,
-                                                int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
-                                                int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL, TxKeys keys) {
-  __shared__ int q[TX_GQ];
-  __shared__ int gb[TX_BMAXBLK];
-  __shared__ int park[TX_PARK];
-  int img = blockIdx.y, tile = blockIdx.x;
-  if (DL.xcdAffine) {
-    const int L = blockIdx.y * gridDim.x + blockIdx.x, xcd = L & 7, k = L >> 3;
-    img = (k / (int)gridDim.x) * 8 + xcd;
-    tile = k % (int)gridDim.x;
-  }
-  tx_grow_tile<false, false, TX_GQ, 2>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll,
-                                       TW, TH, arenaAll, arenaCap, rectAll, rectCap, img + img0, tile, 1, rankAll, rgLostAll, tileTouchAll, DL,
-                                       q, gb, park, &keys);
-}
-// ... and both with round 1's words in the 8-byte hot records (round 6; keys.hot)
-#define TX_GROW_HOT_KERNEL(NAME, PACKV)                                                                                                     \
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void NAME(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl, \
-                                                const float4* __restrict__ recAll, int2* __restrict__ ownAll,                                \
-                                                const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,                        \
-                                                int ts, int ntx, int nty, int* __restrict__ rgSizeAll,                                       \
-                                                int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,                             \
-                                                const int* __restrict__ tileActAll, int TW, int TH,                                          \
-                                                int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,                      \
-                                                int rectCap, int img0, int t, const int* __restrict__ rankAll,                               \
-                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL, TxKeys keys) { \
-  __shared__ int q[TX_GQ];                                                                                                                   \
-  __shared__ int gb[TX_BMAXBLK + 4];        /* (+ the exact sums' three words, tx_grow_tile) */                                              \
-  __shared__ int park[TX_PARK];                                                                                                              \
-  int img = blockIdx.y, tile = blockIdx.x;                                                                                                   \
-  if (DL.xcdAffine) {                                                                                                                        \
-    const int L = blockIdx.y * gridDim.x + blockIdx.x, xcd = L & 7, k = L >> 3;                                                              \
-    img = (k / (int)gridDim.x) * 8 + xcd;                                                                                                    \
-    tile = k % (int)gridDim.x;                                                                                                               \
-  }                                                                                                                                          \
-  tx_grow_tile<false, false, TX_GQ, PACKV, true>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, \
-                                                 tileActAll, TW, TH, arenaAll, arenaCap, rectAll, rectCap, img + img0, tile, 1, rankAll,      \
-                                                 rgLostAll, tileTouchAll, DL, q, gb, park, &keys, keys.hot, keys.cold);                       \
-}
-TX_GROW_HOT_KERNEL(k_tx_grow_h1, 1)
-TX_GROW_HOT_KERNEL(k_tx_grow_h2, 2)
-#undef TX_GROW_HOT_KERNEL
-#ifdef PLI_DEV     // (dev switch PLI_TX_SPEC: round 1 in the speculative lane schedule — exact, measured, slower)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_spec(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow(TxRound A, int t) { tx_grow_round1<0, false>(A, t, nullptr); }
+// (the packed forms run round 1 only: t is the constant 1 for the compiler)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_p1(TxRound A, int t, TxKeys keys) { tx_grow_round1<1, false>(A, 1, &keys); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_p2(TxRound A, int t, TxKeys keys) { tx_grow_round1<2, false>(A, 1, &keys); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_h2(TxRound A, int t, TxKeys keys) { tx_grow_round1<2, true>(A, 1, &keys); }
+// k_tx_grow_h1 — the default round 1, 40 % of a step — is the one kernel that keeps its planes as `__restrict__` KERNEL parameters.
+// On the record it was measured 0.7 % slower (16.75 -> 16.86 ms at 256 frames, five interleaved runs each, outside the parent's
+// spread; profiles/README.md): a pointer read from a by-value struct is not `noalias` for the compiler, and uniform loads behind the
+// first claim into the hot plane — fields of the parameter block in the exact test — become vector loads.  Same body, same code as before.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_h1(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
                                                 const float4* __restrict__ recAll, int2* __restrict__ ownAll,
                                                 const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
                                                 int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
@@ -2196,47 +2157,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                                 const int* __restrict__ tileActAll, int TW, int TH,
                                                 int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
                                                 int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL) {
-  __shared__ int q[TX_GQ_SPEC];
-  __shared__ int gb[TX_BMAXBLK];
-  __shared__ int park[8 * 64];
-  tx_grow_tile<false, true, TX_GQ_SPEC>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll,
-                                        TW, TH, arenaAll, arenaCap, rectAll, rectCap, blockIdx.y + img0, blockIdx.x, t, rankAll, rgLostAll,
-                                        tileTouchAll, DL, q, gb, park);
-}
-#endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_sparse(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
-                                                       const float4* __restrict__ recAll, int2* __restrict__ ownAll,
-                                                       const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
-                                                       int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
-                                                       int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,
-                                                       const int* __restrict__ tileActAll, int TW, int TH,
-                                                       int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
-                                                       int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                       int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL) {
-  __shared__ int q[TX_GQ];
-  __shared__ int gb[TX_BMAXBLK];
-  __shared__ int park[TX_PARK];
-  tx_grow_tile<true>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll, TW, TH,
-                   arenaAll, arenaCap, rectAll, rectCap, blockIdx.y + img0, blockIdx.x, t, rankAll, rgLostAll, tileTouchAll, DL, q, gb, park);
-}
-// ... on the hot records (round 6): the angle from there, the owner pair from the owner plane; recAll is not read
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_sparse_h(const DevParams* __restrict__ Pp, RxCtl* __restrict__ ctl,
-                                                       const float4* __restrict__ recAll, int2* __restrict__ ownAll,
-                                                       const int2* __restrict__ listAll, const int* __restrict__ tileCntAll,
-                                                       int ts, int ntx, int nty, int* __restrict__ rgSizeAll,
-                                                       int2* __restrict__ rgBoxAll, const int* __restrict__ rgDirtyAll,
-                                                       const int* __restrict__ tileActAll, int TW, int TH,
-                                                       int* __restrict__ arenaAll, int arenaCap, RxRect* __restrict__ rectAll,
-                                                       int rectCap, int img0, int t, const int* __restrict__ rankAll,
-                                                       int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL,
-                                                       int2* __restrict__ hotAll, const float2* __restrict__ coldAll) {
+                                                int* __restrict__ rgLostAll, int* __restrict__ tileTouchAll, TxDirtyLists DL, TxKeys keys) {
   __shared__ int q[TX_GQ];
   __shared__ int gb[TX_BMAXBLK + 4];
   __shared__ int park[TX_PARK];
-  tx_grow_tile<true, false, TX_GQ, 0, true>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll, tileActAll,
-                                            TW, TH, arenaAll, arenaCap, rectAll, rectCap, blockIdx.y + img0, blockIdx.x, t, rankAll, rgLostAll,
-                                            tileTouchAll, DL, q, gb, park, nullptr, hotAll, coldAll);
+  int img, tile;
+  tx_round1_tile(DL, false, img, tile);
+  tx_grow_tile<false, false, TX_GQ, 1, true>(Pp, ctl, recAll, ownAll, listAll, tileCntAll, ts, ntx, nty, rgSizeAll, rgBoxAll, rgDirtyAll,
+                                             tileActAll, TW, TH, arenaAll, arenaCap, rectAll, rectCap, img + img0, tile, 1, rankAll,
+                                             rgLostAll, tileTouchAll, DL, q, gb, park, &keys, keys.hot, keys.cold);
+}
+#ifdef PLI_DEV     // (dev switch PLI_TX_SPEC: round 1 in the speculative lane schedule — exact, measured, slower)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_spec(TxRound A, int t) {
+  __shared__ int q[TX_GQ_SPEC];
+  __shared__ int gb[TX_BMAXBLK];
+  __shared__ int park[8 * 64];
+  tx_grow_tile<false, true, TX_GQ_SPEC>(A, blockIdx.y + A.img0, blockIdx.x, t, q, gb, park);
+}
+#endif
+// the later rounds: the tiles with seeds to regrow
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_sparse(TxRound A, int t) {
+  __shared__ int q[TX_GQ];
+  __shared__ int gb[TX_BMAXBLK];
+  __shared__ int park[TX_PARK];
+  tx_grow_tile<true>(A, blockIdx.y + A.img0, blockIdx.x, t, q, gb, park);
+}
+// ... on the hot records (round 6): the angle from there, the owner pair from the owner plane; A.rec is not read
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_tx_grow_sparse_h(TxRound A, int t) {
+  __shared__ int q[TX_GQ];
+  __shared__ int gb[TX_BMAXBLK + 4];
+  __shared__ int park[TX_PARK];
+  tx_grow_tile<true, false, TX_GQ, 0, true>(A, blockIdx.y + A.img0, blockIdx.x, t, q, gb, park);
 }
 
 // ---------------------------------------------------------------------------
@@ -2407,7 +2358,7 @@ __device__ __forceinline__ bool tx_grid_barrier(unsigned* bar, unsigned target) 
   return s_ok != 0;
 }
 
-__global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
+__global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs T) {
   __shared__ int qs[4][TX_GQ];
   __shared__ int gbs[4][TX_BMAXBLK + 4];
   __shared__ int parks[4][TX_PARK];
@@ -2416,12 +2367,13 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
   __shared__ int ecs[4][RX_RECT_CACHE][64];
   __shared__ int s_live, s_n;
   __shared__ int s_list[256];
-  if (A.forceAbort) {                                    // (test switch: what every block does when a barrier times out)
-    if (threadIdx.x == 0) __hip_atomic_store(&A.bar[32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (T.forceAbort) {                                    // (test switch: what every block does when a barrier times out)
+    if (threadIdx.x == 0) __hip_atomic_store(&T.bar[32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
+  const TxRound& A = T.R;
   const DevParams& P = *A.Pp;
-  const int W = P.LW, H = P.LH;
+  const int W = A.W, H = A.H;
   const int64_t npix = (int64_t)W * H;
   const int tid = threadIdx.x, wv = tid >> 6;
   const int G = gridDim.x;
@@ -2436,7 +2388,7 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
   // (is there anything to do there at all?), the few that pass are listed in LDS and then run, one after the other, by the whole
   // block.  The tests cost a pass over the cell stamps; the virtual blocks that do something are spread evenly over the grid.
   unsigned epoch = 0;
-  for (int t = A.t0; t <= A.maxRounds; ++t) {
+  for (int t = T.t0; t <= T.maxRounds; ++t) {
     // ---- k_tx_diffmark: the 4 x 8 cell blocks with a cell touched in round t - 1 ----
     for (int il = blockIdx.x * 256 + tid; il < A.nimg; il += G * 256) {          // (what block (0, 0) of the kernel does for its image)
       RxCtl& c = A.ctl[A.img0 + il];
@@ -2462,12 +2414,11 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
       for (int i = 0; i < n; ++i) {
         const int64_t va = base + (int64_t)s_list[i] * G;
         const int il = (int)(va / (nbx * nbyA)), rem = (int)(va - (int64_t)il * (nbx * nbyA));
-        tx_diffmark_block(A.ctl, A.own, A.rank, A.rgBox, A.rgDirty, A.tileAct, A.tileTouch, W, H, A.TW, A.TH, t, rem % nbx, rem / nbx,
-                          A.img0 + il, A.rgLost, A.DL);
+        tx_diffmark_block(A, t, rem % nbx, rem / nbx, A.img0 + il);
         __syncthreads();                                 // (the block's LDS lists are reused by the next virtual block)
       }
     }
-    if (!tx_grid_barrier(A.bar, ++epoch * G)) return;
+    if (!tx_grid_barrier(T.bar, ++epoch * G)) return;
     // ---- k_tx_prep: the fixed point of an image whose round-t flag stayed clear; the 32 x 32 blocks with an active cell ----
     for (int il = blockIdx.x * 256 + tid; il < A.nimg; il += G * 256) {
       RxCtl& c = A.ctl[A.img0 + il];
@@ -2496,11 +2447,11 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
       for (int i = 0; i < n; ++i) {
         const int64_t va = base + (int64_t)s_list[i] * G;
         const int il = (int)(va / (nbx * nbyB)), rem = (int)(va - (int64_t)il * (nbx * nbyB));
-        tx_prep_block(A.ctl, A.own, A.rank, A.rgDirty, A.tileAct, W, H, A.TW, A.TH, t, rem % nbx, rem / nbx, A.img0 + il, 0, A.tileTouch, A.DL.rmask, A.DL.stamp);
+        tx_prep_block(A, t, rem % nbx, rem / nbx, A.img0 + il, 0);
         __syncthreads();
       }
     }
-    if (!tx_grid_barrier(A.bar, ++epoch * G)) return;
+    if (!tx_grid_barrier(T.bar, ++epoch * G)) return;
     // ---- is anybody still relaxing?  (every block counts the same control words: the answer is the same everywhere) ----
     if (tid == 0) s_live = 0;
     __syncthreads();
@@ -2520,19 +2471,13 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
       for (int i = wv; i < n; i += 4) {
         const int64_t va = base + (int64_t)s_list[i] * G;
         const int il = (int)(va / ntile);
-        if (A.hot)
-          tx_grow_tile<true, false, TX_GQ, 0, true>(A.Pp, A.ctl, A.rec, A.own, A.list, A.tileCnt, A.ts, A.ntx, A.nty, A.rgSize, A.rgBox, A.rgDirty,
-                                                    A.tileAct, A.TW, A.TH, A.arena, A.arenaCap, A.rects, A.rectCap, A.img0 + il,
-                                                    (int)(va - (int64_t)il * ntile), t, A.rank, A.rgLost, A.tileTouch, A.DL, qs[wv], gbs[wv],
-                                                    parks[wv], nullptr, A.hot, A.cold);
-        else
-        tx_grow_tile<true>(A.Pp, A.ctl, A.rec, A.own, A.list, A.tileCnt, A.ts, A.ntx, A.nty, A.rgSize, A.rgBox, A.rgDirty, A.tileAct, A.TW,
-                           A.TH, A.arena, A.arenaCap, A.rects, A.rectCap, A.img0 + il, (int)(va - (int64_t)il * ntile), t, A.rank, A.rgLost,
-                           A.tileTouch, A.DL, qs[wv], gbs[wv], parks[wv]);
+        const int tile = (int)(va - (int64_t)il * ntile);
+        if (A.hot) tx_grow_tile<true, false, TX_GQ, 0, true>(A, A.img0 + il, tile, t, qs[wv], gbs[wv], parks[wv]);
+        else tx_grow_tile<true>(A, A.img0 + il, tile, t, qs[wv], gbs[wv], parks[wv]);
       }
       __syncthreads();
     }
-    if (!tx_grid_barrier(A.bar, ++epoch * G)) return;
+    if (!tx_grid_barrier(T.bar, ++epoch * G)) return;
     // ---- k_rx_rect of the regions this round completed; the dirty lists are consumed: emptied for the next round ----
     for (int64_t v = (int64_t)blockIdx.x * 256 + tid; v < nC; v += (int64_t)G * 256) A.DL.cnt[(int64_t)A.img0 * ntile + v] = 0;
     {
@@ -2546,7 +2491,7 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs A) {
                      A.hot ? A.hot + img * npix : nullptr, A.cold ? A.cold + img * npix : nullptr);
       }
     }
-    if (!tx_grid_barrier(A.bar, ++epoch * G)) return;
+    if (!tx_grid_barrier(T.bar, ++epoch * G)) return;
   }
 }
 

@@ -800,11 +800,12 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
   int hotLevel = (packMode != 0 && c->hot != nullptr && P.prec <= 1.0 && P.alignFilter != 0) ? 2 : 0;
   if (const char* e = DEVENV("PLI_TX_HOT")) hotLevel = std::min(hotLevel, std::max(0, atoi(e)));
   if (hotLevel == 2 && (DEVENV("PLI_RX_FULL") || DEVENV("PLI_TX_NODIRTYLIST"))) hotLevel = 1;     // (dev schedules that keep to the plain later-round kernels)
-  // On the hot records the ids are SORT-WRITTEN (1) by default, in key mode too: k_tx_sort rewrites the whole 8-byte record — angle and
-  // `unclaimed | id`, full sectors — and round 1 does without the lazy-id test, ~23 of a step's ~150 vector instructions: k_tx_grow
-  // 18.6 -> 17.1 ms, k_tx_sort 2.1 -> 3.2 with 4-byte stores into the records' second words (read-modify-writes of sectors) and less
-  // with whole records (DESIGN.md 5 "Round 6").  On the 16-byte records the same trade was a wash (round 5) and lazy ids stay the
-  // default there.  Dev switch PLI_TX_PACK1 = 0 / 1 / 2.
+  // On the hot records the ids are SORT-WRITTEN (1) by default, in key mode too: k_tx_sort stores `unclaimed | id` into the second word
+  // of every 8-byte record — 4-byte stores, read-modify-writes of sectors — and round 1 does without the lazy-id test, ~23 of a step's
+  // ~150 vector instructions: k_tx_grow 18.6 -> 17.1 ms, k_tx_sort 2.1 -> 3.2.  (Rewriting the whole record, the angle with it, was
+  // measured and is slower: k_tx_sort 3.8 ms — the extra loads cost more than the partial sectors, lsd_tile.hip k_tx_sort; DESIGN.md 5
+  // "Round 6".)  On the 16-byte records the same trade was a wash (round 5) and lazy ids stay the default there.  Dev switch
+  // PLI_TX_PACK1 = 0 / 1 / 2.
   if (hotLevel != 0 && packMode == 2) packMode = 1;
   if (const char* e = DEVENV("PLI_TX_PACK1")) packMode = std::min(packCap, std::max(0, atoi(e)));
   if (packMode == 0) hotLevel = 0;
@@ -1034,6 +1035,24 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       DL.stamp = stampBase;
       if (DEVENV("PLI_TX_NODIRTYLIST")) DL.list = nullptr;             // dev: every active tile walks its whole seed list
       TxDirtyLists noDL = DL; noDL.list = nullptr;
+      // The planes of the relaxation, the one argument record of every kernel of a round (TxRound, common.hpp).  A launch that differs in
+      // a field takes a copy: `first` — round 1 and round 2's pass over the owner map read ROUND 1's hot records, the later rounds theirs.
+      const TxRound txr{c->dP, c->jrCtl, c->rec, c->own, c->txList, c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty,
+                        c->tileAct, c->tileTouch, P.LW, P.LH, c->tilesW, c->tilesH, c->arena, c->arenaCap, c->rects, c->rectCap, c->rgSeg,
+                        c->mg, c->rankOf, lostRule ? c->rgLost : (int*)nullptr, DL, img0, nimg, hotLater, coldPlane};
+      TxRound first = txr; first.hot = hotPlane;
+      // the ORB chain forks from the line chain here (pli_batch_run handed it over; where: sideForkRound below)
+      auto forkSideChain = [&]() -> pli_status {
+        auto f = std::move(c->sideChain);
+        c->sideChain = nullptr;
+        return f();
+      };
+      // region2rect of the regions a round completed, on whatever c->stream is at the call
+      auto rectPass = [&]() -> pli_status {
+        TRL(c, "k_rx_rect", k_rx_rect, dim3(rectBlocks, nimg), dim3(64), 0, c->dP, c->jrCtl, c->rec, c->arena, c->arenaCap, c->rects,
+            c->rectCap, c->rgSeg, img0, c->mg, DL.rmask, (const int2*)hotPlane, (const float2*)coldPlane);
+        return PLI_OK;
+      };
       // rounds >= 3: k_rx_diff + k_tx_mark as one kernel (k_tx_diffmark; the dev rules keep the separate passes)
       const bool fusedDM = lostRule && !fullRound2 && !DEVENV("PLI_TX_CELLRULE") && !DEVENV("PLI_TX_OLDMARK") && !DEVENV("PLI_TX_FULLDIFF") &&
                            !DEVENV("PLI_TX_NOFUSEDM");
@@ -1070,10 +1089,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
         if (useTail && t == tailT0) {
           // (the dirty counters are zero: every list of the last round was taken by its tile's wave; the barrier words were cleared
           // with the control blocks)
-          TxTailArgs ta{c->dP, c->jrCtl, c->rec, c->own, c->txList, c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty,
-                        c->tileAct, c->tileTouch, c->tilesW, c->tilesH, c->arena, c->arenaCap, c->rects, c->rectCap, c->rgSeg, c->mg,
-                        c->rankOf, c->rgLost, DL, img0, nimg, t, maxRounds, c->tailBar};
-          ta.hot = hotLater; ta.cold = coldPlane;
+          TxTailArgs ta{txr, t, maxRounds, c->tailBar};
           // (a grid barrier costs 8 us with 256 workgroups and less with fewer: a few images do not need the whole chip in the late rounds)
           // (single pair: k_tx_tail 149 us with 256 workgroups, 90 with 64)
           int tb = std::min(c->tailBlocks, std::max(64, 8 * nimg));
@@ -1102,17 +1118,14 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
         const bool fused2 = t == 2 && !fullRound2 && lostRule && !DEVENV("PLI_TX_NOFUSE2");    // (dev switch: the two passes)
         bool cellsDone = false;
         if (fused2) {
-          TRL(c, "k_tx_round2", k_tx_round2, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf, c->order,
-              c->rgBox, c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)c->rgLost, DL, c->tileTouch,
-              (pack1 && !hotPlane) ? (const float4*)c->rec : (const float4*)nullptr, rectAside ? 1 : 0, (const int2*)hotPlane);
+          TRL(c, "k_tx_round2", k_tx_round2, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, first, t,
+              (pack1 && !hotPlane) ? (const float4*)c->rec : (const float4*)nullptr, rectAside ? 1 : 0);
           if (rectAside) {                               // (round 1's region2rect pass has run beside this kernel: join, then the counter)
             HIPCHK(hipStreamWaitEvent(c->stream, c->evRectDone, 0));
             TRL(c, "k_tx_reset_rect", k_tx_reset_rect, dim3((nimg + 255) / 256), dim3(256), 0, c->jrCtl, nimg, img0);
           }
           if (c->sideChain && sideForkRound == -2) {      // (dev switch: the ORB chain forks behind round 2's pass over the owner map, before its growth)
-            auto f = std::move(c->sideChain);
-            c->sideChain = nullptr;
-            pli_status ss = f();
+            pli_status ss = forkSideChain();
             if (ss != PLI_OK) return ss;
           }
         } else if (t >= 3 && fusedDM && useCells && t < TX_CELL_ROUNDS) {
@@ -1126,19 +1139,15 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           int* cntB = c->txCellCnt + ((int64_t)2 * t + 1) * c->rxImages + img0;
           int* lst = c->txCellList + (int64_t)img0 * ncell;
           TRL(c, "k_tx_cells", k_tx_cells, lg, dim3(256), 0, c->jrCtl, (const int*)c->tileTouch, c->tileTouch, ncell, nimg, img0, t, 0, lst, cntA);
-          TRL(c, "k_tx_diffmark", k_tx_diffmark_cells, wg, dim3(64), 0, c->jrCtl, (const int2*)c->own, (const int*)c->rankOf, (const int2*)c->rgBox,
-              c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)c->rgLost, DL, (const int*)lst, (const int*)cntA);
+          TRL(c, "k_tx_diffmark", k_tx_diffmark_cells, wg, dim3(64), 0, txr, t, (const int*)lst, (const int*)cntA);
           TRL(c, "k_tx_cells", k_tx_cells, lg, dim3(256), 0, c->jrCtl, (const int*)c->tileAct, c->tileTouch, ncell, nimg, img0, t, 1, lst, cntB);
-          TRL(c, "k_tx_prep", k_tx_prep_cells, wg, dim3(64), 0, (const RxCtl*)c->jrCtl, c->own, (const int*)c->rankOf, (const int*)c->rgDirty, P.LW,
-              P.LH, c->tilesW, c->tilesH, t, img0, DL.rmask, (const int*)lst, (const int*)cntB, DL.stamp);
+          TRL(c, "k_tx_prep", k_tx_prep_cells, wg, dim3(64), 0, txr, t, (const int*)lst, (const int*)cntB);
           cellsDone = true;
         } else if (t >= 3 && fusedDM)
-          TRL(c, "k_tx_diffmark", k_tx_diffmark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf,
-              c->rgBox, c->rgDirty, c->tileAct, (const int*)c->tileTouch, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)c->rgLost, DL);
+          TRL(c, "k_tx_diffmark", k_tx_diffmark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, txr, t);
 #ifdef PLI_DEV     // (the unfused passes of the dev switches: the product's round 2 is k_tx_round2, its rounds >= 3 k_tx_diffmark or the cell lists)
         else if (t == 2 && !fullRound2)
-          TRL(c, "k_tx_diff2", k_tx_diff2, dim3((P.LW + 31) / 32, c->tilesH, nimg), dim3(256), 0, c->jrCtl, c->own, c->order, c->rgBox,
-              c->rgDirty, c->tileMin, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, ts, t, img0, lostRule ? (const int*)c->rgLost : (const int*)nullptr, DL);
+          TRL(c, "k_tx_diff2", k_tx_diff2, dim3((P.LW + 31) / 32, c->tilesH, nimg), dim3(256), 0, txr, t, c->tileMin);
         else if (t >= 2)                     // (round 1 starts from the trivial map: nothing to compare, the control block is zeroed)
           TRL(c, "k_rx_diff", k_rx_diff, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->tileMin, c->tileAct,
               P.LW, P.LH, c->tilesW, c->tilesH, t, img0,
@@ -1151,82 +1160,61 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           }
 #ifdef PLI_DEV
           else if (lostRule && t >= 3 && !DEVENV("PLI_TX_CELLRULE") && !DEVENV("PLI_TX_OLDMARK"))
-          TRL(c, "k_rx_mark", k_tx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf, c->rgBox,
-              c->rgDirty, c->tileMin, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)c->rgLost, DL);
+          TRL(c, "k_rx_mark", k_tx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, txr, t, (const int*)c->tileMin);
           else if (t >= 3 || !lostRule)
           TRL(c, "k_rx_mark", k_rx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf, c->rgBox,
               c->rgDirty, c->tileMin, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, t >= 3 ? 1 : 0,
               (lostRule && t >= 3 && !DEVENV("PLI_TX_CELLRULE")) ? (const int*)c->rgLost : (const int*)nullptr, DL);
 #endif
-          if (!fused2 && !cellsDone)
-          TRL(c, "k_tx_prep", k_tx_prep, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf,
-              c->rgDirty, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, t == 2 ? 1 : 0, fusedDM ? c->tileTouch : (int*)nullptr, DL.rmask, DL.stamp);
-          if (hotLater)
-          TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse_h, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch,
-              fullRound2 && t == 2 ? noDL : DL, hotLater, (const float2*)coldPlane);
-          else
-          TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch,
-              fullRound2 && t == 2 ? noDL : DL);
+          if (!fused2 && !cellsDone) {
+            TxRound prep = txr;                           // (after separate diff and mark passes — dev schedules — no cell stamps, one flag)
+            if (!fusedDM) prep.tileTouch = nullptr;
+            TRL(c, "k_tx_prep", k_tx_prep, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, prep, t, t == 2 ? 1 : 0);
+          }
+          TxRound grow = txr;                             // (dev: a round 2 that regrows everything walks the seed lists, not the dirty lists)
+          if (fullRound2 && t == 2) grow.DL = noDL;
+          if (hotLater) TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse_h, dim3(ntile, nimg), dim3(64), txPad, grow, t);
+          else TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse, dim3(ntile, nimg), dim3(64), txPad, grow, t);
         } else {
+          TxRound r1 = first;                             // (round 1: no dirty lists yet, every tile walks its seed list)
+          r1.DL = noDL;
           // round 1 in the speculative schedule (lanes grow the small regions of 64 alive seeds at a time, lsd_tile.hip): exact, built
           // and measured in round 3, NOT the default — 37 ms against 22 ms of the plain schedule at 256 frames (the
           // divergent per-lane accept path costs more instructions than the whole-wave steps it replaces).  Dev switch PLI_TX_SPEC=1.
 #ifdef PLI_DEV
           const bool specRound1 = lostRule && P.minRegSize >= 3 && DEVENV("PLI_TX_SPEC") && atoi(DEVENV("PLI_TX_SPEC")) != 0;
           if (specRound1)
-          TRL(c, "k_tx_grow", k_tx_grow_spec, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, noDL);
+          TRL(c, "k_tx_grow", k_tx_grow_spec, dim3(ntile, nimg), dim3(64), txPad, r1, t);
           else
 #endif
           {
           // dev switch PLI_TX_ORDER=1: the heaviest tiles first (k_tx_order).  Measured, not the default: the launch does end on fewer
           // stragglers, but consecutive workgroups no longer grow neighbouring tiles of one image and k_tx_grow goes from 23.2 to
           // 31.3 ms at 256 frames (4K: 33.1 -> 44.2 ms) — the grid order's locality is worth more than the balance
-          TxDirtyLists r1DL = noDL;
-          if ((nimg % 8) == 0 && DEVENV("PLI_TX_XCD") && atoi(DEVENV("PLI_TX_XCD")) != 0) r1DL.xcdAffine = 1;
+          if ((nimg % 8) == 0 && DEVENV("PLI_TX_XCD") && atoi(DEVENV("PLI_TX_XCD")) != 0) r1.DL.xcdAffine = 1;
 #ifdef PLI_DEV
           if (DEVENV("PLI_TX_ORDER") && atoi(DEVENV("PLI_TX_ORDER")) != 0) {
             TRL(c, "k_tx_order", k_tx_order, dim3(1), dim3(1024), 0, (const int*)c->txTileCnt, ntile, nimg, img0, c->txPerm + (int64_t)img0 * ntile);
-            r1DL.perm = c->txPerm + (int64_t)img0 * ntile;
+            r1.DL.perm = c->txPerm + (int64_t)img0 * ntile;
           }
 #endif
-          if (hotPlane && packMode == 2)
-          TRL(c, "k_tx_grow", k_tx_grow_h2, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, r1DL, keys);
-          else if (hotPlane)
-          TRL(c, "k_tx_grow", k_tx_grow_h1, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, r1DL, keys);
-          else if (packMode == 2)
-          TRL(c, "k_tx_grow", k_tx_grow_p2, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, r1DL, keys);
-          else if (packMode == 1)
-          TRL(c, "k_tx_grow", k_tx_grow_p1, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, r1DL, keys);
-          else
-          TRL(c, "k_tx_grow", k_tx_grow, dim3(ntile, nimg), dim3(64), txPad, c->dP, c->jrCtl, c->rec, c->own, c->txList,
-              c->txTileCnt, ts, c->txNtx, c->txNty, c->lastSize, c->rgBox, c->rgDirty, c->tileAct, c->tilesW, c->tilesH, c->arena,
-              c->arenaCap, c->rects, c->rectCap, img0, t, (const int*)c->rankOf, lostRule ? c->rgLost : (int*)nullptr, c->tileTouch, r1DL);
+          // (the forms with owner_1 packed into the records, 16-byte or hot, take the keys beside the planes)
+          void (*const packed)(TxRound, int, TxKeys) = (hotPlane && packMode == 2) ? k_tx_grow_h2 : packMode == 2 ? k_tx_grow_p2 :
+                                                       (!hotPlane && packMode == 1) ? k_tx_grow_p1 : nullptr;
+          if (packed) TRL(c, "k_tx_grow", packed, dim3(ntile, nimg), dim3(64), txPad, r1, t, keys);
+          else if (hotPlane)       // (the default: the one kernel with its planes as `__restrict__` parameters, lsd_tile.hip k_tx_grow_h1)
+          TRL(c, "k_tx_grow", k_tx_grow_h1, dim3(ntile, nimg), dim3(64), txPad, r1.Pp, r1.ctl, r1.rec, r1.own, r1.list, r1.tileCnt, r1.ts,
+              r1.ntx, r1.nty, r1.rgSize, r1.rgBox, (const int*)r1.rgDirty, (const int*)r1.tileAct, r1.TW, r1.TH, r1.arena, r1.arenaCap,
+              r1.rects, r1.rectCap, r1.img0, t, r1.rank, r1.rgLost, r1.tileTouch, r1.DL, keys);
+          else TRL(c, "k_tx_grow", k_tx_grow, dim3(ntile, nimg), dim3(64), txPad, r1, t);
           }
           if (c->sideChain && sideForkRound <= 1 && sideForkRound != -2) {       // (pli_batch_run: the ORB chain forks here, behind round 1)
-            auto f = std::move(c->sideChain);
-            c->sideChain = nullptr;
-            pli_status ss = f();
+            pli_status ss = forkSideChain();
             if (ss != PLI_OK) return ss;
           }
         }
         if (c->sideChain && t >= 2 && t == sideForkRound) {   // (dev switch PLI_SIDE_FORK_ROUND: ... behind the growth of a later round)
-          auto f = std::move(c->sideChain);
-          c->sideChain = nullptr;
-          pli_status ss = f();
+          pli_status ss = forkSideChain();
           if (ss != PLI_OK) return ss;
         }
         if (t == 1 && rectAside) {
@@ -1251,22 +1239,14 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           HIPCHK(hipEventRecord(c->evRectFork, mainS));
           HIPCHK(hipStreamWaitEvent(rectS, c->evRectFork, 0));
           c->stream = rectS;
-          hipError_t le = hipSuccess;
-          {
-            auto launchRect = [&]() -> pli_status {
-              TRL(c, "k_rx_rect", k_rx_rect, dim3(rectBlocks, nimg), dim3(64), 0, c->dP, c->jrCtl, c->rec, c->arena, c->arenaCap, c->rects,
-                  c->rectCap, c->rgSeg, img0, c->mg, DL.rmask, (const int2*)hotPlane, (const float2*)coldPlane);
-              return PLI_OK;
-            };
-            const pli_status rs = launchRect();
-            c->stream = mainS;
-            if (rs != PLI_OK) return rs;
-          }
-          (void)le;
+          const pli_status rs = rectPass();
+          c->stream = mainS;
+          if (rs != PLI_OK) return rs;
           HIPCHK(hipEventRecord(c->evRectDone, rectS));
-        } else
-        TRL(c, "k_rx_rect", k_rx_rect, dim3(rectBlocks, nimg), dim3(64), 0, c->dP, c->jrCtl, c->rec, c->arena, c->arenaCap, c->rects,
-            c->rectCap, c->rgSeg, img0, c->mg, DL.rmask, (const int2*)hotPlane, (const float2*)coldPlane);
+        } else {
+          const pli_status rs = rectPass();
+          if (rs != PLI_OK) return rs;
+        }
         if (trace) {
           HIPCHK(hipMemcpyAsync(c->jrHost.data(), c->jrCtl + img0, sizeof(RxCtl) * nimg, hipMemcpyDeviceToHost, c->stream));
           HIPCHK(hipStreamSynchronize(c->stream));

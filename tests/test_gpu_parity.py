@@ -1089,6 +1089,40 @@ def test_tile_relaxation_dev_switches(gpu, W, H, monkeypatch):
         assert m == want[0] and kl.tobytes() == want[1].tobytes() and np.array_equal(ld, want[2]), on
 
 
+def test_tile_relaxation_round_one_and_two_dev_schedules(gpu, monkeypatch):
+    """The shelved schedules of the tile relaxation's first two rounds give the oracle's lines: round 1 in the speculative lane
+    schedule (PLI_TX_SPEC), its workgroups in order of decreasing work (PLI_TX_ORDER) or with the tiles of an image on one XCD
+    (PLI_TX_XCD: acts on a multiple of 8 images — with the hot records, with the 16-byte packed records and with the plain owner
+    plane), and round 2 regrowing everything (PLI_TX_FULL2).  Eight small images of several tiles each way in one batch."""
+    g = gpu
+    W, H = 320, 240
+    cfg = g.capi.default_config(W, H, orb_nfeatures=300, lsd_nfeatures=0, max_frames=4, lsd_mode=3)
+    pairs = [g.synth.make_stereo_pair(77 + i, W, H) for i in range(4)]
+    imgs = np.stack([np.stack(p) for p in pairs])
+    want = []
+    for L, R in pairs:
+        fr = g.po.Frame(ocfg(g, cfg))
+        want.append((fr.line_extract(0, L), fr.line_extract(1, R)))
+        assert want[-1][0][0] > 500 and want[-1][1][0] > 500
+    switches = ("PLI_TX_SPEC", "PLI_TX_ORDER", "PLI_TX_FULL2", "PLI_TX_XCD", "PLI_TX_HOT", "PLI_TX_PACK1")
+    for env in ({}, {"PLI_TX_SPEC": "1"}, {"PLI_TX_ORDER": "1"}, {"PLI_TX_FULL2": "1"}, {"PLI_TX_XCD": "1"},
+                {"PLI_TX_XCD": "1", "PLI_TX_HOT": "0"}, {"PLI_TX_XCD": "1", "PLI_TX_PACK1": "0"}):
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        fe = g.Frontend(cfg, dev=True)
+        recs = fe.batch_run_host(imgs)
+        if not env:
+            assert fe.lsd_round_stats()[1] >= 3, fe.lsd_round_stats()      # (the kernels of the later rounds ran)
+        for f in range(4):
+            for e, k in enumerate("LR"):
+                m, kl, ld = want[f][e]
+                assert m == len(recs[f]["kl" + k]), (env, f, k, len(recs[f]["kl" + k]), m)
+                assert recs[f]["kl" + k].tobytes() == kl.tobytes(), (env, f, k)
+                assert np.array_equal(recs[f]["ldesc" + k], ld), (env, f, k)
+
+
 def test_truncation_is_flagged_not_silent(gpu):
     """A max_lines smaller than the number of segments that pass the length cut: the record carries the truncation flag and
     the per-call entry point returns PLI_ERR_CAPACITY; with room enough the flag is clear and the result is the oracle's."""
