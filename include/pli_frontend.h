@@ -857,6 +857,37 @@ pli_status pli_create_new_map_points(pli_ctx* ctx, const pli_keypoint* kp1, cons
                                      float mb, int32_t coarse, int32_t far_points, float th_far, float ratio_factor,
                                      int32_t* matches12, int32_t* nmatches, int32_t* status, float* x3d, int32_t* nnew);
 
+/* The same step for keyframes of a rig of two KannalaBrandt8 cameras (NLeft != -1, mpCamera2 set), the branch
+ * `mpCurrentKeyFrame->mpCamera2 && pKF2->mpCamera2` (LocalMapping.cc:463-528), one keyframe against nkf neighbours in one call:
+ * pli_search_for_triangulation_two_cameras (bOnlyStereo = false, no orientation check), then per matched pair :530-667 with the
+ * pose and the camera that (bRight1, bRight2) = (idx1 >= NLeft of pKF1, idx2 >= NLeft of pKF2) pick for each side, and the
+ * first-accepted-wins pick of pli_create_new_map_points, which holds here unchanged.
+ * What the branch reads: kp1 / kp2 are mvKeys[idx] or mvKeysRight[idx - NLeft], never mvKeysUn (:446-448, :454-456); bStereo1 and
+ * bStereo2 are false (:450, :459), so mvuRight's value is never used, mvDepth is not read, and the call takes no uright, depth, key, mb,
+ * bf, F12 or ep; the triangulation condition :550 is 0 < cosParallaxRays < 0.9998 and everything else PLI_NEWPT_LOW_PARALLAX;
+ * xn = unprojectMat(kp.pt) is KannalaBrandt8::unproject with z = 1; both gates project with KannalaBrandt8::project against
+ * 5.991 * sigmaSquare in double (:605-610, :632-636).  PLI_NEWPT_EMPTY_UNPROJECT, PLI_NEWPT_REPROJ1_STEREO and
+ * PLI_NEWPT_REPROJ2_STEREO cannot occur here.
+ * Tables: kp1 ... kf_has_mp, n1_left, kf_nleft, cam_left, cam_right and rel exactly as for pli_search_for_triangulation_two_cameras.
+ * pose1 (2 x 15) / kf_pose (nkf x 2 x 15): per keyframe the left side, then the right side, 15 floats each as for
+ * pli_fuse_search_two_cameras - Rcw row major, tcw, Ow: GetRotation / GetTranslation / GetCameraCenter, then GetRightRotation /
+ * GetRightTranslation / GetRightCameraCenter (GetPose / GetRightPose are the same floats; Rwc is the exact transpose).
+ * coarse, far_points, th_far, ratio_factor and the five outputs exactly as for pli_create_new_map_points.
+ * A call in which one keyframe has a second camera and another has none is out of scope (the reference falls through :463 with the
+ * poses of the previous pair); the caller refuses it.
+ * Checked before anything is launched, PLI_ERR_INVALID: null pointers, negative counts, a decreasing kf_off, n1_left outside
+ * [0, n1], a kf_nleft outside its neighbour's rows, an octave outside [0, orb_nlevels), a keypoint coordinate, rel or pose value that
+ * is not finite.  PLI_ERR_CAPACITY for more than PLI_BOW_MAX_FEATURES rows in n1 or in a neighbour, or nkf x n1 beyond the pair index.
+ * nkf == 0, n1 == 0, empty neighbours, n1_left == 0 and n1_left == n1 are valid.  Six kernel launches, whatever nkf is. */
+pli_status pli_create_new_map_points_two_cameras(pli_ctx* ctx, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                                 const uint8_t* has_mp1, int32_t n1, int32_t n1_left, int32_t nkf,
+                                                 const int32_t* kf_off, const int32_t* kf_nleft, const pli_keypoint* kf_kp,
+                                                 const uint8_t* kf_desc, const int32_t* kf_node, const uint8_t* kf_has_mp,
+                                                 const pli_kb8_camera* cam_left, const pli_kb8_camera* cam_right, const float* rel,
+                                                 const float* pose1, const float* kf_pose, int32_t coarse, int32_t far_points,
+                                                 float th_far, float ratio_factor, int32_t* matches12, int32_t* nmatches,
+                                                 int32_t* status, float* x3d, int32_t* nnew);
+
 /* Loop closing's ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) ORBmatcher.cc:473-586 and the
  * overload with vpPointsKFs / vpMatchedKF :588-704 (LoopClosing.cc:631, :656, :852), for ONE list of nmp map points against npair
  * (keyframe, Scw) pairs in one call.  Unlike Fuse this search is sequential across the points of a pair: vpMatched[bestIdx] = pMP

@@ -14,6 +14,39 @@
 
 namespace ORB_SLAM3 {
 
+namespace pli_detail {
+// :670-683 for what one device call created, in the reference's order; `if(i>0 && CheckNewKeyFrames()) return;` (:389) before
+// neighbour k > 0 is applied.  Shared by PliCreateNewMapPoints and PliCreateNewMapPointsTwoCameras.
+template <class MapPointT, class KeyFrameT, class AtlasT, class StopFn>
+int replayNewMapPoints(const pli::Frontend::NewMapPoints& out, KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs,
+                       AtlasT* mpAtlas, std::list<MapPointT*>& mlpRecentAddedMapPoints, StopFn checkNewKeyFrames) {
+  const int nkf = (int)vpNeighKFs.size(), n1 = pKF1->N;
+  int created = 0;
+  for (int k = 0; k < nkf; ++k) {
+    if (k > 0 && checkNewKeyFrames()) return created;                  // :389
+    KeyFrameT* pKF2 = vpNeighKFs[k];
+    for (int idx1 = 0; idx1 < n1; ++idx1) {                            // vMatchedIndices is vMatches12 read in index order
+      const size_t p = (size_t)k * n1 + idx1;
+      if (out.status[p] != PLI_NEWPT_CREATED) continue;
+      const int idx2 = out.matches12[p];
+      cv::Mat x3D(3, 1, CV_32F);
+      for (int r = 0; r < 3; ++r) x3D.template at<float>(r) = out.x3d[3 * p + r];
+      MapPointT* pMP = new MapPointT(x3D, pKF1, mpAtlas->GetCurrentMap());          // :670
+      pMP->AddObservation(pKF1, idx1);
+      pMP->AddObservation(pKF2, idx2);
+      pKF1->AddMapPoint(pMP, idx1);
+      pKF2->AddMapPoint(pMP, idx2);
+      pMP->ComputeDistinctiveDescriptors();
+      pMP->UpdateNormalAndDepth();
+      mpAtlas->AddMapPoint(pMP);
+      mlpRecentAddedMapPoints.push_back(pMP);
+      ++created;
+    }
+  }
+  return created;
+}
+}  // namespace pli_detail
+
 // vpNeighKFs: the neighbours that passed the baseline / median-depth test of :396-413 (it stays with the caller), in the
 // reference's order.  bCoarse: :420-422.  checkNewKeyFrames: asked before neighbour k > 0 is applied, as `if(i>0 &&
 // CheckNewKeyFrames()) return;` (:389); whatever was not applied is dropped.  First-accepted-wins is a prefix property, so the
@@ -22,7 +55,8 @@ namespace ORB_SLAM3 {
 // pKF1, mpAtlas->GetCurrentMap()), both AddObservation, both AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth,
 // mpAtlas->AddMapPoint, mlpRecentAddedMapPoints.push_back (:670-683).
 // KeyFrameT needs what PliORBmatcher::SearchForTriangulation reads, and mvKeys, mvDepth, fx, fy, cx, cy, mbf, mb, mfScaleFactor,
-// AddMapPoint(pMP, idx).  A keyframe of two cameras throws std::logic_error: the branch :463-528 is not provided.
+// AddMapPoint(pMP, idx).  A keyframe of two cameras throws std::logic_error: the branch :463-528 is
+// PliCreateNewMapPointsTwoCameras (orbslam_local_mapping_two_cameras.hpp), which forwards here when no keyframe has a second camera.
 template <class MapPointT, class KeyFrameT, class AtlasT, class StopFn>
 int PliCreateNewMapPoints(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeighKFs, AtlasT* mpAtlas,
                           std::list<MapPointT*>& mlpRecentAddedMapPoints, bool bCoarse, bool mbFarPoints, float mThFarPoints,
@@ -67,29 +101,7 @@ int PliCreateNewMapPoints(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpNeig
                            T1.key.data(), n1, nkf, T2.off.data(), T2.kp.data(), T2.desc.data(), T2.node.data(), T2.hasMp.data(),
                            T2.uright.data(), T2.depth.data(), T2.key.data(), F12.data(), ep.data(), T1.pose.data(), T2.pose.data(),
                            cam, pKF1->mb, bCoarse, mbFarPoints, mThFarPoints, ratioFactor, out);
-  int created = 0;
-  for (int k = 0; k < nkf; ++k) {
-    if (k > 0 && checkNewKeyFrames()) return created;                  // :389
-    KeyFrameT* pKF2 = vpNeighKFs[k];
-    for (int idx1 = 0; idx1 < n1; ++idx1) {                            // vMatchedIndices is vMatches12 read in index order
-      const size_t p = (size_t)k * n1 + idx1;
-      if (out.status[p] != PLI_NEWPT_CREATED) continue;
-      const int idx2 = out.matches12[p];
-      cv::Mat x3D(3, 1, CV_32F);
-      for (int r = 0; r < 3; ++r) x3D.template at<float>(r) = out.x3d[3 * p + r];
-      MapPointT* pMP = new MapPointT(x3D, pKF1, mpAtlas->GetCurrentMap());          // :670
-      pMP->AddObservation(pKF1, idx1);
-      pMP->AddObservation(pKF2, idx2);
-      pKF1->AddMapPoint(pMP, idx1);
-      pKF2->AddMapPoint(pMP, idx2);
-      pMP->ComputeDistinctiveDescriptors();
-      pMP->UpdateNormalAndDepth();
-      mpAtlas->AddMapPoint(pMP);
-      mlpRecentAddedMapPoints.push_back(pMP);
-      ++created;
-    }
-  }
-  return created;
+  return pli_detail::replayNewMapPoints(out, pKF1, vpNeighKFs, mpAtlas, mlpRecentAddedMapPoints, checkNewKeyFrames);
 }
 
 }  // namespace ORB_SLAM3

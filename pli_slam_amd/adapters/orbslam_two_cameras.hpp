@@ -1,7 +1,7 @@
 // The two SearchByProjection forms of ORB_SLAM3::ORBmatcher that run on every tracked frame, for a frame of two cameras
 // (Frame::Nleft != -1, the fisheye-stereo rig), SearchForTriangulation and Fuse(pKF, vpMapPoints, th, bRight) for keyframes of two
-// cameras (mpCamera2 set, NLeft != -1) and SearchByBoW(pKF, F, vpMapPointMatches) for such frames and keyframes: a matcher that is
-// PliORBmatcher in everything else.
+// cameras (mpCamera2 set, NLeft != -1), SearchByBoW(pKF, F, vpMapPointMatches) for such frames and keyframes and
+// SearchByBoW(pKF1, pKF2, vpMatches12) for such keyframes: a matcher that is PliORBmatcher in everything else.
 //
 //   inside the PLI-SLAM tree:  using ORBmatcher = ORB_SLAM3::PliORBmatcherTwoCameras<Frame, MapPoint>;
 //
@@ -9,6 +9,7 @@
 // hides the members below and forwards each to it when the frame or every keyframe of the call has one camera.
 #pragma once
 #include "orbslam_adapters.hpp"
+#include <algorithm>
 #include <cstring>
 #include <utility>
 
@@ -49,6 +50,44 @@ inline void fusePosesTwoCameras(KeyFrameT* pKF, float* pose) {
     }
 }
 
+// mpCamera / mpCamera2 of a keyframe of two cameras: eight KannalaBrandt8 parameters each (GeometricCamera.h:77-80)
+template <class KeyFrameT>
+inline void kb8Cameras(KeyFrameT* pKF, pli_kb8_camera cam[2]) {
+  if (!pKF->mpCamera || !pKF->mpCamera2 || pKF->mpCamera->size() != 8 || pKF->mpCamera2->size() != 8)
+    throw std::logic_error("PliORBmatcherTwoCameras: a keyframe of two cameras needs two KannalaBrandt8 cameras (8 parameters each)");
+  for (int e = 0; e < 2; ++e) {
+    float v[8];
+    for (int i = 0; i < 8; ++i) v[i] = e ? pKF->mpCamera2->getParameter(i) : pKF->mpCamera->getParameter(i);
+    cam[e] = pli_kb8_camera{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+  }
+}
+
+// The tables of SearchForTriangulation for keyframes of two cameras (the batch search and PliCreateNewMapPointsTwoCameras): a
+// keyframe's rows are mvKeys then mvKeysRight (:1048-1050, :1083-1085), its cameras must be `cam`, the call's.
+struct TwoCameraTriangulationTable : KfTable {
+  std::vector<pli_keypoint> kp;
+  std::vector<uint8_t> hasMp;
+  std::vector<int32_t> nleft;
+};
+template <class KeyFrameT>
+inline void gatherTwoCameraTriangulationTable(KeyFrameT* pKF, const pli_kb8_camera cam[2], TwoCameraTriangulationTable& T,
+                                              const std::string& who, const char* what) {
+  const int n = pKF->N, nl = pKF->NLeft;
+  if (nl < 0 || nl > n || (int)pKF->mvKeys.size() < nl || (int)pKF->mvKeysRight.size() < n - nl || pKF->mDescriptors.rows < n)
+    throw std::logic_error(who + ": a keyframe's tables do not hold NLeft + NRight rows");
+  pli_kb8_camera own[2];
+  kb8Cameras(pKF, own);
+  if (std::memcmp(own, cam, sizeof(own)) != 0)
+    throw std::logic_error(who + ": the keyframes of one call must share their camera parameters");
+  appendNodes(T, pKF->mFeatVec, n, what);
+  appendDescriptors(T, pKF->mDescriptors, n);
+  for (int i = 0; i < n; ++i) {
+    T.kp.push_back(keypoint(i < nl ? pKF->mvKeys[i] : pKF->mvKeysRight[i - nl]));      // :1048-1050, :1083-1085
+    T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
+  }
+  T.nleft.push_back(nl);
+}
+
 }  // namespace pli_detail
 
 // FrameT needs, beyond what PliORBmatcher reads: Nleft, Nright, mvKeys, mvKeysRight, mDescriptors (Nleft + Nright rows, the left
@@ -65,7 +104,7 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
   using Base::SearchByProjection;            // every other form stays visible; the two below hide theirs
   using Base::SearchForTriangulation;        // likewise: both forms below hide theirs and forward to them
   using Base::Fuse;                          // the Sim3 form stays the base's; the two forms below hide theirs
-  using Base::SearchByBoW;                   // the (KF, KF) forms stay the base's; the two (KF, F) forms below hide theirs
+  using Base::SearchByBoW;                   // the (KF, F) and the (KF, KF) forms below hide theirs and forward to them
 
   // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono),
   // ORBmatcher.cc:1961-2177 (Tracking::TrackWithMotionModel, Tracking.cc:2961, :2969).  For CurrentFrame.Nleft != -1 the two
@@ -227,29 +266,11 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
     }
     if (two != nkf + 1)     // (the reference multiplies by an empty R12 for such a pair)
       throw std::logic_error("SearchForTriangulation: keyframes with and without mpCamera2 in one call are not supported");
-    struct Table : pli_detail::KfTable {
-      std::vector<pli_keypoint> kp;
-      std::vector<uint8_t> hasMp;
-      std::vector<int32_t> nleft;
-    };
-    auto cameras = [](KeyFrameT* pKF, pli_kb8_camera cam[2]) { kb8Cameras(pKF, cam); };
+    typedef pli_detail::TwoCameraTriangulationTable Table;
     pli_kb8_camera cam[2];
-    cameras(pKF1, cam);
+    kb8Cameras(pKF1, cam);
     auto gather = [&](KeyFrameT* pKF, Table& T, const char* what) {
-      const int n = pKF->N, nl = pKF->NLeft;
-      if (nl < 0 || nl > n || (int)pKF->mvKeys.size() < nl || (int)pKF->mvKeysRight.size() < n - nl || pKF->mDescriptors.rows < n)
-        throw std::logic_error("SearchForTriangulation: a keyframe's tables do not hold NLeft + NRight rows");
-      pli_kb8_camera own[2];
-      cameras(pKF, own);
-      if (std::memcmp(own, cam, sizeof(own)) != 0)
-        throw std::logic_error("SearchForTriangulation: the keyframes of one call must share their camera parameters");
-      pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
-      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
-      for (int i = 0; i < n; ++i) {
-        T.kp.push_back(pli_detail::keypoint(i < nl ? pKF->mvKeys[i] : pKF->mvKeysRight[i - nl]));      // :1048-1050, :1083-1085
-        T.hasMp.push_back(pKF->GetMapPoint(i) ? 1 : 0);                 // (:1033-1039, :1064-1068: isBad() is not asked)
-      }
-      T.nleft.push_back(nl);
+      pli_detail::gatherTwoCameraTriangulationTable(pKF, cam, T, "SearchForTriangulation", what);
     };
     Table T1, T2;
     gather(pKF1, T1, "SearchForTriangulation: pKF1->mFeatVec");
@@ -374,18 +395,69 @@ class PliORBmatcherTwoCameras : public PliORBmatcher<FrameT, MapPointT> {
     pli_detail::forEachMatch(matches, nkf, nf, [&](int k, int i, int j) { vvpMapPointMatches[k][i] = kfPoints[k][j]; });
   }
 
- private:
-  // mpCamera / mpCamera2 of a keyframe of two cameras: eight KannalaBrandt8 parameters each (GeometricCamera.h:77-80)
+  // ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), ORBmatcher.cc:823-963
+  // (LoopClosing.cc:533), with the two-camera text: for a keyframe with NLeft != -1 a feature idx >= mvKeysUn.size() is skipped, on
+  // either side (the two `continue`s at :858-860 and :878-880), and the angles of the others come from mvKeysUn (:915).  The skipped
+  // rows enter pli_search_by_bow_kf with valid = 0 and angle 0, which is what the entry's valid tables express; the device call is
+  // the base's.  vpMatches12 has GetMapPointMatches().size() entries.  Keyframes with NLeft == -1 are gathered as the base gathers
+  // them, and a call in which every keyframe is such a one goes to the base.
   template <class KeyFrameT>
-  static void kb8Cameras(KeyFrameT* pKF, pli_kb8_camera cam[2]) {
-    if (!pKF->mpCamera || !pKF->mpCamera2 || pKF->mpCamera->size() != 8 || pKF->mpCamera2->size() != 8)
-      throw std::logic_error("PliORBmatcherTwoCameras: a keyframe of two cameras needs two KannalaBrandt8 cameras (8 parameters each)");
-    for (int e = 0; e < 2; ++e) {
-      float v[8];
-      for (int i = 0; i < 8; ++i) v[i] = e ? pKF->mpCamera2->getParameter(i) : pKF->mpCamera->getParameter(i);
-      cam[e] = pli_kb8_camera{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-    }
+  int SearchByBoW(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12) {
+    std::vector<std::vector<MapPointT*>> matches;
+    std::vector<int> nmatches;
+    SearchByBoW(pKF1, std::vector<KeyFrameT*>(1, pKF2), matches, nmatches);
+    vpMatches12.swap(matches[0]);
+    return nmatches[0];
   }
+
+  // (not in the reference) The same for every keyframe of vpKF2 in ONE device call, as the base's batch form.
+  template <class KeyFrameT>
+  void SearchByBoW(KeyFrameT* pKF1, const std::vector<KeyFrameT*>& vpKF2, std::vector<std::vector<MapPointT*>>& vvpMatches12,
+                   std::vector<int>& vnmatches) {
+    bool anyTwo = pKF1->NLeft != -1;
+    for (KeyFrameT* pKF2 : vpKF2) anyTwo = anyTwo || pKF2->NLeft != -1;
+    if (!anyTwo) {
+      Base::SearchByBoW(pKF1, vpKF2, vvpMatches12, vnmatches);
+      return;
+    }
+    typedef typename Base::BowTable BowTable;
+    auto gather = [](KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const char* what, BowTable& T) {
+      if (pKF->NLeft == -1) {
+        Base::bowGatherKeyFrame(pKF, vpMapPoints, what, T);
+        return;
+      }
+      const int n = pKF->N, nun = (int)std::min(pKF->mvKeysUn.size(), (size_t)n);
+      if ((int)vpMapPoints.size() < n || pKF->mDescriptors.rows < n)
+        throw std::logic_error("SearchByBoW: a keyframe's tables do not hold N rows");
+      pli_detail::appendNodes(T, pKF->mFeatVec, n, what);
+      pli_detail::appendDescriptors(T, pKF->mDescriptors, n);
+      for (int i = 0; i < n; ++i) {
+        MapPointT* pMP = i < nun ? vpMapPoints[i] : nullptr;           // idx >= mvKeysUn.size(): :858-860, :878-880
+        T.valid.push_back(pMP && !pMP->isBad() ? 1 : 0);
+        T.angle.push_back(i < nun ? pKF->mvKeysUn[i].angle : 0.f);     // :915
+      }
+    };
+    const int nkf = (int)vpKF2.size(), n1 = pKF1->N;
+    BowTable T1, T2;
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    gather(pKF1, vpMapPoints1, "SearchByBoW: pKF1->mFeatVec", T1);
+    std::vector<std::vector<MapPointT*>> kfPoints((size_t)nkf);
+    for (int k = 0; k < nkf; ++k) {
+      kfPoints[k] = vpKF2[k]->GetMapPointMatches();
+      gather(vpKF2[k], kfPoints[k], "SearchByBoW: pKF2->mFeatVec", T2);
+    }
+    std::vector<int> matches;
+    pli_detail::deviceContext("SearchByBoW")->searchByBoWKF(T1.desc.data(), T1.angle.data(), T1.node.data(), T1.valid.data(), n1, nkf,
+                                                           T2.off.data(), T2.desc.data(), T2.angle.data(), T2.node.data(),
+                                                           T2.valid.data(), this->mfNNratio, this->mbCheckOrientation, matches,
+                                                           vnmatches);
+    vvpMatches12.assign((size_t)nkf, std::vector<MapPointT*>(vpMapPoints1.size(), static_cast<MapPointT*>(nullptr)));
+    pli_detail::forEachMatch(matches, nkf, n1, [&](int k, int i, int j) { vvpMatches12[k][i] = kfPoints[k][j]; });   // :910
+  }
+
+ private:
+  template <class KeyFrameT>
+  static void kb8Cameras(KeyFrameT* pKF, pli_kb8_camera cam[2]) { pli_detail::kb8Cameras(pKF, cam); }
 
   // What the two Fuse forms share.  sides: 1 = the left camera of every target, 2 = the right one, 3 = both, left then right;
   // nFused has one entry per replayed (keyframe, side).

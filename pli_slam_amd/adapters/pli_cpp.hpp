@@ -227,6 +227,25 @@ class Frontend {
                                     farPoints ? 1 : 0, thFar, ratioFactor, out.matches12.data(), out.nmatches.data(),
                                     out.status.data(), out.x3d.data(), out.nnew.data()));
   }
+  // The same step for keyframes of two KannalaBrandt8 cameras (LocalMapping.cc:463-528; include/pli_frontend.h
+  // pli_create_new_map_points_two_cameras): the tables of searchForTriangulationTwoCameras, pose1 (2 x 15) and kfPose (nkf x 2 x 15)
+  // = per keyframe the left then the right side's Rcw row major, tcw, Ow
+  void createNewMapPointsTwoCameras(const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1, const uint8_t* hasMp1, int n1,
+                                    int n1Left, int nkf, const int32_t* kfOff, const int32_t* kfNleft, const pli_keypoint* kfKp,
+                                    const uint8_t* kfDesc, const int32_t* kfNode, const uint8_t* kfHasMp,
+                                    const pli_kb8_camera& camLeft, const pli_kb8_camera& camRight, const float* rel,
+                                    const float* pose1, const float* kfPose, bool coarse, bool farPoints, float thFar,
+                                    float ratioFactor, NewMapPoints& out) {
+    out.matches12.assign((size_t)nkf * n1, -1);
+    out.status.assign((size_t)nkf * n1, PLI_NEWPT_NOT_MATCHED);
+    out.x3d.assign((size_t)nkf * n1 * 3, 0.f);
+    out.nmatches.assign(nkf, 0);
+    out.nnew.assign(nkf, 0);
+    check(pli_create_new_map_points_two_cameras(ctx_, kp1, desc1, node1, hasMp1, n1, n1Left, nkf, kfOff, kfNleft, kfKp, kfDesc, kfNode,
+                                                kfHasMp, &camLeft, &camRight, rel, pose1, kfPose, coarse ? 1 : 0, farPoints ? 1 : 0,
+                                                thFar, ratioFactor, out.matches12.data(), out.nmatches.data(), out.status.data(),
+                                                out.x3d.data(), out.nnew.data()));
+  }
   // The search half of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609 without second cameras; reprojGate = false: the Sim3 overload
   // :1611-1733) of nmp map points against nkf keyframes (include/pli_frontend.h pli_fuse_search): bestIdx (nkf x nmp) = the
   // keyframe's row or -1.  levelRatio: fuseLevelRatio() of the extractor's configuration.

@@ -1232,6 +1232,89 @@ pli_status pli_create_new_map_points(pli_ctx* c, const pli_keypoint* kp1, const 
   return PLI_OK;
 }
 
+pli_status pli_create_new_map_points_two_cameras(pli_ctx* c, const pli_keypoint* kp1, const uint8_t* desc1, const int32_t* node1,
+                                                 const uint8_t* hasMp1, int32_t n1, int32_t n1Left, int32_t nkf, const int32_t* kfOff,
+                                                 const int32_t* kfNleft, const pli_keypoint* kfKp, const uint8_t* kfDesc,
+                                                 const int32_t* kfNode, const uint8_t* kfHasMp, const pli_kb8_camera* camLeft,
+                                                 const pli_kb8_camera* camRight, const float* rel, const float* pose1,
+                                                 const float* kfPose, int32_t coarse, int32_t farPoints, float thFar,
+                                                 float ratioFactor, int32_t* matches12, int32_t* nmatches, int32_t* status, float* x3d,
+                                                 int32_t* nnew) {
+  CtxGuard guard__(c);
+  if (!c || n1 < 0 || nkf < 0 || !camLeft || !camRight || !pose1 || (n1 > 0 && (!kp1 || !desc1 || !node1 || !hasMp1)) ||
+      (nkf > 0 && (!kfOff || !kfNleft || !rel || !kfPose || !nmatches || !nnew)) ||
+      (nkf > 0 && n1 > 0 && (!matches12 || !status || !x3d))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (n1Left < 0 || n1Left > n1) { g_err = "n1_left outside [0, n1]"; return PLI_ERR_INVALID; }
+  if (nkf == 0) return PLI_OK;
+  KfBatch B;
+  pli_status st = kfBatch(nkf, kfOff, "a neighbour has more features than the CreateNewMapPoints cap", B);
+  if (st != PLI_OK) return st;
+  if (n1 > PLI_BOW_MAX_FEATURES) { g_err = "pKF1 has more features than the CreateNewMapPoints cap"; return PLI_ERR_CAPACITY; }
+  const int64_t total = B.total, npairs = (int64_t)nkf * n1;
+  // (k_newpt_list indexes a pair with an int, rounded up to its block of 256)
+  if (npairs > INT32_MAX - 256) { g_err = "nkf x n1 does not fit the pair index"; return PLI_ERR_CAPACITY; }
+  if (total > 0 && (!kfKp || !kfDesc || !kfNode || !kfHasMp)) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (!nleftOk(nkf, kfOff, kfNleft, "kf_nleft outside [0, the neighbour's rows]")) return PLI_ERR_INVALID;
+  if (!nodesOk(node1, n1, "node1") || !octavesOk(c, kp1, n1, "kp1") || !finiteOk(kp1, n1, "kp1")) return PLI_ERR_INVALID;
+  if (!nodesOk(kfNode, total, "kf_node") || !octavesOk(c, kfKp, total, "kf_kp") || !finiteOk(kfKp, total, "kf_kp")) return PLI_ERR_INVALID;
+  if (!floatsFinite(rel, 48 * (int64_t)nkf, "rel") || !floatsFinite(pose1, 30, "pose1") ||
+      !floatsFinite(kfPose, 30 * (int64_t)nkf, "kf_pose"))
+    return PLI_ERR_INVALID;
+  std::fill(nmatches, nmatches + nkf, 0);
+  std::fill(nnew, nnew + nkf, 0);
+  if (n1 == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  float hlv[2 * MAX_LEVELS] = {};
+  levelTables(c, hlv, hlv + MAX_LEVELS, nullptr);
+  ScratchPlan plan;
+  const TriTables T = triTables(plan, B, kp1, desc1, node1, hasMp1, n1, kfKp, kfDesc, kfNode, kfHasMp);
+  auto dR1 = plan.add<float2>(n1);
+  auto dNl = plan.in(kfNleft, nkf);
+  auto dKr = plan.add<float2>(total);
+  auto dRel = plan.in(rel, (size_t)nkf * 48);
+  auto dLv = plan.in(hlv, 2 * MAX_LEVELS);                 // mvScaleFactors, then mvLevelSigma2
+  auto dPose1 = plan.in(pose1, 30);
+  auto dKpose = plan.in(kfPose, (size_t)nkf * 30);
+  auto dList = plan.add<int>(npairs);
+  auto dCnt = plan.add<int>(1 + 2 * (size_t)nkf);          // the list's length, nmatches[nkf], nnew[nkf]
+  auto dStatus = plan.add<int>(npairs);
+  auto dX = plan.add<float>((size_t)npairs * 3);
+  st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  HIPCHK(hipMemsetAsync(dCnt, 0, (1 + 2 * (size_t)nkf) * sizeof(int), c->stream));
+  Kb8 cl, cr;
+  memcpy(&cl, camLeft, sizeof(cl));
+  memcpy(&cr, camRight, sizeof(cr));
+  const int keyCap = pow2Ceil(B.maxNk);
+  const int perBlock = 4 * 4;                                            // k_tri_match_kb8: 4 waves x TRI_PER_WAVE features of pKF1
+  const int64_t nray = (int64_t)n1 + total;
+  const float* sigma2 = (const float*)dLv + MAX_LEVELS;
+  // (also when bCoarse: the search's gate does not run then, but the geometry reads the rays)
+  LAUNCH(c, "k_kb8_rays", k_kb8_rays, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, (const pli_keypoint*)T.dK1, n1, n1Left,
+         (const pli_keypoint*)T.dKk, (const int*)T.dOff, (const int*)dNl, nkf, cl, cr, (float2*)dR1, (float2*)dKr);
+  LAUNCH(c, "k_node_sort", k_node_sort, dim3(nkf), dim3(1024), (size_t)keyCap * 6, T.dOff, 0, T.dKn, T.dKm, 0, (const uint8_t*)nullptr, 0,
+         keyCap, T.dSn, T.dSi, T.dListed, T.dStat);
+  LAUNCH(c, "k_tri_match_kb8", k_tri_match_kb8, dim3((n1 + perBlock - 1) / perBlock, nkf), dim3(256), 0, T.dK1, T.dD1, T.dN1, T.dM1,
+         (const float2*)dR1, n1, n1Left, T.dOff, (const int*)dNl, T.dKk, T.dKd, (const float2*)dKr, T.dSn, T.dSi, T.dListed,
+         (const float*)dRel, cl, cr, sigma2, coarse ? 1 : 0, 0, T.dM, T.dStat);
+  int* cnt = dCnt;
+  LAUNCH(c, "k_newpt_list", k_newpt_list, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, (const int*)T.dM, (int)npairs,
+         (int*)dList, cnt, (int*)dStatus, (float*)dX);
+  const NewPtKb8Tables D = {T.dK1, (const float2*)dR1, dPose1, n1, n1Left, T.dOff, dNl, T.dKk, (const float2*)dKr, dKpose,
+                            (const float*)dLv, sigma2};
+  const unsigned geoBlocks = (unsigned)std::min<int64_t>((npairs + 63) / 64, 2048);
+  LAUNCH(c, "k_newpt_geometry_kb8", k_newpt_geometry_kb8, dim3(geoBlocks), dim3(64), 0, D, cl, cr, farPoints ? 1 : 0, thFar,
+         ratioFactor, (const int*)T.dM, (const int*)dList, (const int*)cnt, (int*)dStatus, (float*)dX);
+  LAUNCH(c, "k_newpt_pick", k_newpt_pick, dim3((n1 + 255) / 256), dim3(256), 0, n1, nkf, (int*)T.dM, (int*)dStatus, cnt + 1, cnt + 1 + nkf);
+  HIPCHK(download(c, matches12, T.dM));
+  HIPCHK(download(c, status, dStatus));
+  HIPCHK(download(c, x3d, dX));
+  HIPCHK(download(c, nmatches, dCnt, 1, nkf));
+  HIPCHK(download(c, nnew, dCnt, 1 + nkf, nkf));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
 // The tables that the projection launch of a Fuse entry point reads and writes (lv: level_ratio, then mvScaleFactors)
 struct FuseProjectTables {
   const pli_fuse_point* mp; const float* pose; const uint8_t* skip; const float* lv;

@@ -15,6 +15,7 @@
 //   k_node_sort, k_tri_match, k_tri_finish  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:965-1206)
 //   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_tri_finish  the same for keyframes of two KannalaBrandt8 cameras (mpCamera2)
 //   k_node_sort, k_tri_match, k_newpt_list, k_newpt_geometry, k_newpt_pick  LocalMapping::CreateNewMapPoints (LocalMapping.cc:423-684)
+//   k_kb8_rays, k_node_sort, k_tri_match_kb8, k_newpt_list, k_newpt_geometry_kb8, k_newpt_pick  the same for keyframes of two KannalaBrandt8 cameras
 //   k_node_sort + k_search_by_bow_kf    ORBmatcher::SearchByBoW(KF,KF)       (ORBmatcher.cc:823-963)
 //   k_fuse_grid, k_fuse_project, k_fuse_match  the search of ORBmatcher::Fuse (ORBmatcher.cc:1399-1609, :1611-1733)
 //   k_fuse_grid, k_fuse_project_views, k_fuse_match<8, true>  the same search for keyframes of two KannalaBrandt8 cameras, both values of bRight
@@ -2886,29 +2887,27 @@ __device__ __forceinline__ float newpt_dist(const float x3[3], const float* Ow) 
   return (float)sqrt(s);
 }
 
-// :530-667 for one matched pair; returns the status code, x3 is written where it returns PLI_NEWPT_CREATED
-__device__ __forceinline__ int newpt_pair(const NewPtSide& S1, const NewPtSide& S2, const pli_fuse_camera& cam, float mb,
-                                          int farPoints, float thFar, float ratioFactor, const float* __restrict__ scaleFactor,
-                                          const float* __restrict__ sigma2, float x3[3]) {
-  const bool stereo1 = S1.ur >= 0, stereo2 = S2.ur >= 0;
-  const float* T1 = S1.T;
-  const float* T2 = S2.T;
-  // xn = pCamera->unprojectMat(kp.pt) (Pinhole.cpp:59-62); ray = Rwc*xn with Rwc = Rcw.t()
-  const float xn1[3] = {__fdiv_rn(__fsub_rn(S1.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S1.y, cam.cy), cam.fy), 1.f};
-  const float xn2[3] = {__fdiv_rn(__fsub_rn(S2.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S2.y, cam.cy), cam.fy), 1.f};
+// :534-667 from the point where xn1, xn2 and the two poses (Rcw row major, tcw, Ow) are known, for the pinhole kernel and the
+// two-camera one: the ray cosine, the linear triangulation (A, cv::SVD::compute, w == 0, the division), z1 / z2, the distances, the
+// far gate and the scale consistency.  What differs between the two is the caller's Rule:
+//   parallax(cosRays, x3)    NEWPT_TRIANGULATE where the condition of :550 holds, NEWPT_HAVE_X3 where it wrote x3 itself
+//                            (UnprojectStereo), else the status of the exit it took;
+//   reproject(second, x3, z) the chi-square gate of the first / second keyframe (:597-623, :625-648): 0 or the status of the exit.
+// Returns the status code; x3 is meaningful where it returns PLI_NEWPT_CREATED.
+enum { NEWPT_TRIANGULATE = -1, NEWPT_HAVE_X3 = -2 };
+template <class Rule>
+__device__ __forceinline__ int newpt_from_rays(const float xn1[3], const float xn2[3], const float* T1, const float* T2, int octave1,
+                                               int octave2, int farPoints, float thFar, float ratioFactor,
+                                               const float* __restrict__ scaleFactor, const Rule& rule, float x3[3]) {
+  // ray = Rwc*xn with Rwc = Rcw.t()
   float ray1[3], ray2[3];
   for (int r = 0; r < 3; ++r) { ray1[r] = cvmat_dot3(T1 + r, 3, xn1, 1.0, 0.0); ray2[r] = cvmat_dot3(T2 + r, 3, xn2, 1.0, 0.0); }
   const double dot = (double)ray1[0] * ray2[0] + (double)ray1[1] * ray2[1] + (double)ray1[2] * ray2[2];
   const double n1 = sqrt((double)ray1[0] * ray1[0] + (double)ray1[1] * ray1[1] + (double)ray1[2] * ray1[2]);
   const double n2 = sqrt((double)ray2[0] * ray2[0] + (double)ray2[1] * ray2[1] + (double)ray2[2] * ray2[2]);
   const float cosRays = (float)(dot / (n1 * n2));
-  float cosStereo = __fadd_rn(cosRays, 1.f);
-  float cosStereo1 = cosStereo, cosStereo2 = cosStereo;
-  if (stereo1) cosStereo1 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S1.depth)));
-  else if (stereo2) cosStereo2 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S2.depth)));
-  cosStereo = cosStereo2 < cosStereo1 ? cosStereo2 : cosStereo1;                   // min(cosParallaxStereo1, cosParallaxStereo2)
-  const float invfx = __fdiv_rn(1.0f, cam.fx), invfy = __fdiv_rn(1.0f, cam.fy);     // Frame.cc: invfx = 1.0f/fx
-  if (cosRays < cosStereo && cosRays > 0 && (stereo1 || stereo2 || (double)cosRays < 0.9998)) {
+  const int how = rule.parallax(cosRays, x3);
+  if (how == NEWPT_TRIANGULATE) {
     float At[4][4];                                       // A transposed; Tcw = [Rcw | tcw]
     for (int b = 0; b < 4; ++b) {
       const float t1r0 = b < 3 ? T1[b] : T1[9], t1r1 = b < 3 ? T1[3 + b] : T1[10], t1r2 = b < 3 ? T1[6 + b] : T1[11];
@@ -2923,32 +2922,68 @@ __device__ __forceinline__ int newpt_pair(const NewPtSide& S1, const NewPtSide& 
     if (vh[3] == 0) return PLI_NEWPT_W_ZERO;
     const float inv = (float)(1.0 / (double)vh[3]);
     for (int r = 0; r < 3; ++r) x3[r] = __fadd_rn(__fmul_rn(vh[r], inv), 0.f);
-  } else if (stereo1 && cosStereo1 < cosStereo2) {
-    if (!(S1.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
-    newpt_unproject_stereo(S1, cam, invfx, invfy, x3);
-  } else if (stereo2 && cosStereo2 < cosStereo1) {
-    if (!(S2.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
-    newpt_unproject_stereo(S2, cam, invfx, invfy, x3);
-  } else {
-    return PLI_NEWPT_LOW_PARALLAX;
+  } else if (how != NEWPT_HAVE_X3) {
+    return how;
   }
   const float z1 = (float)(((double)T1[6] * x3[0] + (double)T1[7] * x3[1] + (double)T1[8] * x3[2]) + (double)T1[11]);
   if (z1 <= 0) return PLI_NEWPT_Z1;
   const float z2 = (float)(((double)T2[6] * x3[0] + (double)T2[7] * x3[1] + (double)T2[8] * x3[2]) + (double)T2[11]);
   if (z2 <= 0) return PLI_NEWPT_Z2;
-  const float mbf = cam.bf;
-  int g = newpt_reproject(S1, stereo1, cam, mbf, x3, z1, sigma2[S1.octave]);
-  if (g) return g == 1 ? PLI_NEWPT_REPROJ1_MONO : PLI_NEWPT_REPROJ1_STEREO;
-  g = newpt_reproject(S2, stereo2, cam, mbf, x3, z2, sigma2[S2.octave]);
-  if (g) return g == 1 ? PLI_NEWPT_REPROJ2_MONO : PLI_NEWPT_REPROJ2_STEREO;
+  int g = rule.reproject(false, x3, z1);
+  if (g) return g;
+  g = rule.reproject(true, x3, z2);
+  if (g) return g;
   const float dist1 = newpt_dist(x3, T1 + 12), dist2 = newpt_dist(x3, T2 + 12);
   if (dist1 == 0 || dist2 == 0) return PLI_NEWPT_DIST_ZERO;
   if (farPoints && (dist1 >= thFar || dist2 >= thFar)) return PLI_NEWPT_FAR;
   const float ratioDist = __fdiv_rn(dist2, dist1);
-  const float ratioOctave = __fdiv_rn(scaleFactor[S1.octave], scaleFactor[S2.octave]);
+  const float ratioOctave = __fdiv_rn(scaleFactor[octave1], scaleFactor[octave2]);
   if (__fmul_rn(ratioDist, ratioFactor) < ratioOctave) return PLI_NEWPT_RATIO_LOW;
   if (ratioDist > __fmul_rn(ratioOctave, ratioFactor)) return PLI_NEWPT_RATIO_HIGH;
   return PLI_NEWPT_CREATED;
+}
+
+// keyframes of one pinhole camera: the stereo parallax of :543-547 and the branches :550, :576-583; the gates of newpt_reproject
+struct NewPtPinholeRule {
+  const NewPtSide& S1; const NewPtSide& S2; const pli_fuse_camera& cam; float mb; const float* __restrict__ sigma2;
+  __device__ __forceinline__ int parallax(float cosRays, float x3[3]) const {
+    const bool stereo1 = S1.ur >= 0, stereo2 = S2.ur >= 0;
+    float cosStereo = __fadd_rn(cosRays, 1.f);
+    float cosStereo1 = cosStereo, cosStereo2 = cosStereo;
+    if (stereo1) cosStereo1 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S1.depth)));
+    else if (stereo2) cosStereo2 = (float)cos((double)__fmul_rn(2.f, (float)atan2((double)__fdiv_rn(mb, 2.f), (double)S2.depth)));
+    cosStereo = cosStereo2 < cosStereo1 ? cosStereo2 : cosStereo1;                   // min(cosParallaxStereo1, cosParallaxStereo2)
+    const float invfx = __fdiv_rn(1.0f, cam.fx), invfy = __fdiv_rn(1.0f, cam.fy);     // Frame.cc: invfx = 1.0f/fx
+    if (cosRays < cosStereo && cosRays > 0 && (stereo1 || stereo2 || (double)cosRays < 0.9998)) return NEWPT_TRIANGULATE;
+    if (stereo1 && cosStereo1 < cosStereo2) {
+      if (!(S1.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
+      newpt_unproject_stereo(S1, cam, invfx, invfy, x3);
+      return NEWPT_HAVE_X3;
+    }
+    if (stereo2 && cosStereo2 < cosStereo1) {
+      if (!(S2.depth > 0)) return PLI_NEWPT_EMPTY_UNPROJECT;
+      newpt_unproject_stereo(S2, cam, invfx, invfy, x3);
+      return NEWPT_HAVE_X3;
+    }
+    return PLI_NEWPT_LOW_PARALLAX;
+  }
+  __device__ __forceinline__ int reproject(bool second, const float x3[3], float z) const {
+    const NewPtSide& S = second ? S2 : S1;
+    const int g = newpt_reproject(S, S.ur >= 0, cam, cam.bf, x3, z, sigma2[S.octave]);
+    if (!g) return 0;
+    return second ? (g == 1 ? PLI_NEWPT_REPROJ2_MONO : PLI_NEWPT_REPROJ2_STEREO) : (g == 1 ? PLI_NEWPT_REPROJ1_MONO : PLI_NEWPT_REPROJ1_STEREO);
+  }
+};
+
+// :530-667 for one matched pair of pinhole keyframes
+__device__ __forceinline__ int newpt_pair(const NewPtSide& S1, const NewPtSide& S2, const pli_fuse_camera& cam, float mb,
+                                          int farPoints, float thFar, float ratioFactor, const float* __restrict__ scaleFactor,
+                                          const float* __restrict__ sigma2, float x3[3]) {
+  // xn = pCamera->unprojectMat(kp.pt) (Pinhole.cpp:59-62)
+  const float xn1[3] = {__fdiv_rn(__fsub_rn(S1.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S1.y, cam.cy), cam.fy), 1.f};
+  const float xn2[3] = {__fdiv_rn(__fsub_rn(S2.x, cam.cx), cam.fx), __fdiv_rn(__fsub_rn(S2.y, cam.cy), cam.fy), 1.f};
+  const NewPtPinholeRule rule = {S1, S2, cam, mb, sigma2};
+  return newpt_from_rays(xn1, xn2, S1.T, S2.T, S1.octave, S2.octave, farPoints, thFar, ratioFactor, scaleFactor, rule, x3);
 }
 
 // grid-stride over the list (its length is the device's); 64 threads: the Jacobi's registers
@@ -2966,6 +3001,56 @@ __global__ __launch_bounds__(64) void k_newpt_geometry(NewPtTables D, pli_fuse_c
     const NewPtSide S2 = {b.x, b.y, b.octave, D.kfUr[j], D.kfDepth[j], kb.x, kb.y, D.kfPose + 15 * (int64_t)k};
     float x3[3] = {0.f, 0.f, 0.f};
     const int st = newpt_pair(S1, S2, cam, mb, farPoints, thFar, ratioFactor, D.scaleFactor, D.sigma2, x3);
+    status[p] = st;
+    if (st == PLI_NEWPT_CREATED) { x3d[3 * (int64_t)p] = x3[0]; x3d[3 * (int64_t)p + 1] = x3[1]; x3d[3 * (int64_t)p + 2] = x3[2]; }
+  }
+}
+
+// The same for keyframes of two KannalaBrandt8 cameras (pli_create_new_map_points_two_cameras, LocalMapping.cc:463-528): no stereo
+// feature (bStereo1 / bStereo2 are false when mpCamera2 is set, :450, :459), so :550 is 0 < cosParallaxRays < 0.9998 and everything
+// else "no stereo and very low parallax"; both gates are KannalaBrandt8::project against 5.991 * sigmaSquare (:605-610, :632-636).
+struct NewPtKb8Rule {
+  float x1, y1, x2, y2; int octave1, octave2;             // kp1.pt / kp2.pt: mvKeys or mvKeysRight, never mvKeysUn
+  const Kb8& c1; const Kb8& c2;                           // pCamera1 / pCamera2 of the pair
+  const float* T1; const float* T2; const float* __restrict__ sigma2;
+  __device__ __forceinline__ int parallax(float cosRays, float*) const {
+    // cosParallaxStereo = cosParallaxRays + 1 is above cosParallaxRays wherever cosParallaxRays > 0
+    return cosRays > 0 && (double)cosRays < 0.9998 ? (int)NEWPT_TRIANGULATE : (int)PLI_NEWPT_LOW_PARALLAX;
+  }
+  __device__ __forceinline__ int reproject(bool second, const float x3[3], float z) const {
+    const float* T = second ? T2 : T1;
+    float pc[3];
+    pc[0] = (float)(((double)T[0] * x3[0] + (double)T[1] * x3[1] + (double)T[2] * x3[2]) + (double)T[9]);
+    pc[1] = (float)(((double)T[3] * x3[0] + (double)T[4] * x3[1] + (double)T[5] * x3[2]) + (double)T[10]);
+    pc[2] = z;
+    float u, v;
+    kb8_project(second ? c2 : c1, pc, u, v);
+    const float ex = __fsub_rn(u, second ? x2 : x1), ey = __fsub_rn(v, second ? y2 : y1);
+    if ((double)__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)) > 5.991 * (double)sigma2[second ? octave2 : octave1])
+      return second ? PLI_NEWPT_REPROJ2_MONO : PLI_NEWPT_REPROJ1_MONO;
+    return 0;
+  }
+};
+
+// one lane per listed pair, as k_newpt_geometry.  (bRight1, bRight2) = (i >= n1Left, matches12 >= kfNleft[k]) pick the 15-float
+// pose (left, then right, per keyframe) and the camera of each side; xn = unprojectMat(kp.pt) is the ray k_kb8_rays stored, z = 1.
+__global__ __launch_bounds__(64) void k_newpt_geometry_kb8(NewPtKb8Tables D, Kb8 camL, Kb8 camR, int farPoints, float thFar,
+                                                           float ratioFactor, const int* __restrict__ matches12,
+                                                           const int* __restrict__ list, const int* __restrict__ nListed,
+                                                           int* __restrict__ status, float* __restrict__ x3d) {
+  const int n = *nListed;
+  for (int e = blockIdx.x * 64 + threadIdx.x; e < n; e += gridDim.x * 64) {
+    const int p = list[e], k = p / D.n1, i = p - k * D.n1;
+    const int m = matches12[p], j = D.kfOff[k] + m;
+    const bool right1 = i >= D.n1Left, right2 = m >= D.kfNleft[k];
+    const pli_keypoint a = D.kp1[i], b = D.kfKp[j];
+    const float2 ra = D.ray1[i], rb = D.kfRay[j];
+    const float xn1[3] = {ra.x, ra.y, 1.f}, xn2[3] = {rb.x, rb.y, 1.f};
+    const float* T1 = D.pose1 + (right1 ? 15 : 0);
+    const float* T2 = D.kfPose + 30 * (int64_t)k + (right2 ? 15 : 0);
+    const NewPtKb8Rule rule = {a.x, a.y, b.x, b.y, a.octave, b.octave, right1 ? camR : camL, right2 ? camR : camL, T1, T2, D.sigma2};
+    float x3[3] = {0.f, 0.f, 0.f};
+    const int st = newpt_from_rays(xn1, xn2, T1, T2, a.octave, b.octave, farPoints, thFar, ratioFactor, D.scaleFactor, rule, x3);
     status[p] = st;
     if (st == PLI_NEWPT_CREATED) { x3d[3 * (int64_t)p] = x3[0]; x3d[3 * (int64_t)p + 1] = x3[1]; x3d[3 * (int64_t)p + 2] = x3[2]; }
   }

@@ -429,6 +429,38 @@ class Frontend:
                                                ptr(status), ptr(x3d), ptr(nnew)))
         return matches, nmatches, status, x3d, nnew
 
+    def create_new_map_points_two_cameras(self, kf1, kfs, cam_left, cam_right, ratio_factor, coarse=False, far_points=False,
+                                          th_far=0.0):
+        """LocalMapping::CreateNewMapPoints from the search on (LocalMapping.cc:423-684), the branch of keyframes with two
+        KannalaBrandt8 cameras (:463-528), of keyframe `kf1` against every neighbour of `kfs`, in one call
+        (include/pli_frontend.h pli_create_new_map_points_two_cameras).  kf1: (kp, desc, node, has_mp, nleft, pose[2, 15]) - the
+        tables of search_for_triangulation_two_cameras and per side (left, right) Rcw row major, tcw, Ow; kfs: list of
+        (kp, desc, node, has_mp, nleft, pose[2, 15], rel[4, 12]) per neighbour.  cam_left / cam_right: the 8 KannalaBrandt8
+        parameters of mpCamera / mpCamera2; ratio_factor = 1.5f * mfScaleFactor in float.
+        Returns (matches12[nkf, n1], nmatches[nkf], status[nkf, n1] (capi.NEWPT_*), x3d[nkf, n1, 3], nnew[nkf]) as
+        create_new_map_points."""
+        what = "every feature needs one keypoint, descriptor, node and has_mp flag"
+        k1, d1, n1, m1 = pack_keyframes([kf1], TRI_COLUMNS[:4], what)[1]
+        nkf = len(kfs)
+        off, (kk, kd, kn, km) = pack_keyframes(kfs, TRI_COLUMNS[:4], what)
+        nleft = np.ascontiguousarray([int(kf[4]) for kf in kfs], np.int32).reshape(nkf)
+        pose1 = np.ascontiguousarray(kf1[5], np.float32).reshape(30)
+        pose = np.ascontiguousarray([np.asarray(kf[5], np.float32).reshape(30) for kf in kfs], np.float32).reshape(nkf, 30)
+        rel = np.ascontiguousarray([np.asarray(kf[6], np.float32).reshape(48) for kf in kfs], np.float32).reshape(nkf, 48)
+        cl, cr = np.ascontiguousarray(cam_left, np.float32).reshape(8), np.ascontiguousarray(cam_right, np.float32).reshape(8)
+        n = len(n1)
+        matches = np.full((nkf, n), -1, np.int32)
+        nmatches = np.zeros(nkf, np.int32)
+        status = np.full((nkf, n), capi.NEWPT_NOT_MATCHED, np.int32)
+        x3d = np.zeros((nkf, n, 3), np.float32)
+        nnew = np.zeros(nkf, np.int32)
+        check(self.L.pli_create_new_map_points_two_cameras(self.h, ptr(k1), ptr(d1), ptr(n1), ptr(m1), n, int(kf1[4]), nkf, ptr(off),
+                                                           ptr(nleft), ptr(kk), ptr(kd), ptr(kn), ptr(km), ptr(cl), ptr(cr),
+                                                           ptr(rel), ptr(pose1), ptr(pose), int(coarse), int(far_points),
+                                                           float(th_far), float(ratio_factor), ptr(matches), ptr(nmatches),
+                                                           ptr(status), ptr(x3d), ptr(nnew)))
+        return matches, nmatches, status, x3d, nnew
+
     def _level_ratio(self, level_ratio):
         """The level_ratio table of the projection searches: the caller's, or this host's (fuse_level_ratio), made once."""
         if level_ratio is None:
