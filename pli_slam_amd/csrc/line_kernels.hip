@@ -1690,16 +1690,27 @@ __constant__ int c_lbd_comb[32][2] = {
     {4, 5}, {4, 6}, {4, 7}, {4, 8}, {5, 6}, {5, 7}, {5, 8}, {6, 7}, {6, 8}, {7, 8}};
 
 
-__global__ __launch_bounds__(64) void k_lbd(const DevParams* __restrict__ Pp, const LbdCoef* __restrict__ coef,
-                                            const short2* __restrict__ dxya,
-                                            uint8_t* __restrict__ table, int64_t recordBytes, int64_t offCounts,
-                                            int64_t offKl0, int64_t offKl1, int64_t offLd0, int64_t offLd1,
-                                            float* __restrict__ dbgFloat, int img0) {
+#if defined(LBD_DIAG_WAVES) && LBD_DIAG_WAVES >= 8      // (diagnostic builds: 64 VGPRs, for eight waves per SIMD; the product build takes 65 and seven)
+#define LBD_BOUNDS __launch_bounds__(64, 8)
+#else
+#define LBD_BOUNDS __launch_bounds__(64)
+#endif
+__global__ LBD_BOUNDS void k_lbd(const DevParams* __restrict__ Pp, const LbdCoef* __restrict__ coef,
+                                 const short2* __restrict__ dxya,
+                                 uint8_t* __restrict__ table, int64_t recordBytes, int64_t offCounts,
+                                 int64_t offKl0, int64_t offKl1, int64_t offLd0, int64_t offLd1,
+                                 float* __restrict__ dbgFloat, int img0) {
   __shared__ float rowS[63][4];      // pgdL, ngdL, pgdO, ngdO row sums (already x gaussCoefG)
   __shared__ float band[9][8];       // pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2
   __shared__ float des[72];
   const DevParams& P = *Pp;
   const int img = blockIdx.y + img0, li = blockIdx.x, lane = threadIdx.x;
+#ifdef LBD_DIAG_WAVES
+  // (diagnostic builds, make EXTRA=-DLBD_DIAG_WAVES=n, never shipped: idle LDS that leaves room for n of these single-wave workgroups
+  // per SIMD — the occupancy sweep of profiles/lbd_round2_traffic_ab.json)
+  volatile __shared__ int lbdPad[(160 * 1024 / (4 * LBD_DIAG_WAVES) - 1584 - 64) / 4];      // (volatile: a store nobody reads stays)
+  if (recordBytes < 0) lbdPad[lane] = img;
+#endif
   uint8_t* rec = table + (int64_t)(img >> 1) * recordBytes;
   const int eye = img & 1;
   const int n = reinterpret_cast<const int*>(rec + offCounts)[2 + eye];
@@ -1725,21 +1736,46 @@ __global__ __launch_bounds__(64) void k_lbd(const DevParams* __restrict__ Pp, co
     }
     float sCorX = sCorX0, sCorY = sCorY0;
     float pgdL = 0, ngdL = 0, pgdO = 0, ngdO = 0;
-    // (unrolled: the gathers of several steps are in flight together, the float sums stay in walking order)
-#pragma unroll 8
-    for (short wID = 0; wID < lengthOfLSP; wID++) {
-      short tempCor = (short)roundf(sCorX);
-      short xCor = (tempCor < 0) ? 0 : (tempCor > imageWidth) ? imageWidth : tempCor;
-      tempCor = (short)roundf(sCorY);
-      short yCor = (tempCor < 0) ? 0 : (tempCor > imageHeight) ? imageHeight : tempCor;
-      const short2 g = pdxy[(int)yCor * W + xCor];
-      const float dx = (float)g.x, dy = (float)g.y;
-      const float gDL = __fadd_rn(__fmul_rn(dx, dL0), __fmul_rn(dy, dL1));
-      const float gDO = __fadd_rn(__fmul_rn(dx, dO0), __fmul_rn(dy, dO1));
-      if (gDL > 0) pgdL = __fadd_rn(pgdL, gDL); else ngdL = __fsub_rn(ngdL, gDL);
-      if (gDO > 0) pgdO = __fadd_rn(pgdO, gDO); else ngdO = __fsub_rn(ngdO, gDO);
-      sCorX = __fadd_rn(sCorX, dL0);
-      sCorY = __fadd_rn(sCorY, dL1);
+    // Blocks of 32 steps: the block's clamped coordinates depend on nothing that is loaded, so its gathers are issued back to back
+    // and the ordered sums run behind them (the float sums stay in walking order).  A lane that walks along an image row stays on one
+    // 128-byte line for 32 steps: with the block's loads in flight together the line is asked for while it is still in the cache — with
+    // 8 in flight it was fetched four times, the other waves' lines (63 per wave and group) passing through the L1 and L2 in between.
+    // The last block ends at the wave-uniform bound nb — one code path: the steps past it load the last step's pixel again (its line is
+    // there) and leave the sums alone; a remainder of up to 16 steps takes the half block.  Straight-line code on purpose, the sums as
+    // selects: behind a branch, even a wave-uniform one, a load is sunk to its use or preceded by a wait for the loads before it.
+    auto walk = [&](auto nt, const int nb) {
+      constexpr int N = decltype(nt)::value;
+      short2 g[N];
+      int at = 0;
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        short tempCor = (short)roundf(sCorX);
+        short xCor = (tempCor < 0) ? 0 : (tempCor > imageWidth) ? imageWidth : tempCor;
+        tempCor = (short)roundf(sCorY);
+        short yCor = (tempCor < 0) ? 0 : (tempCor > imageHeight) ? imageHeight : tempCor;
+        at = k < nb ? __mul24((int)yCor, W) + xCor : at;     // (nb >= 1; 24-bit factors: a 32-bit multiply-add)
+        asm("" : "+v"(at));                                  // (opaque: or the repeated load becomes a branch around it)
+        g[k] = pdxy[at];
+        sCorX = __fadd_rn(sCorX, dL0);
+        sCorY = __fadd_rn(sCorY, dL1);
+      }
+      __builtin_amdgcn_sched_barrier(0);                     // (every load of the block before the first sum)
+#pragma unroll
+      for (int k = 0; k < N; ++k) {
+        const bool in = k < nb;
+        const float dx = (float)g[k].x, dy = (float)g[k].y;
+        const float gDL = __fadd_rn(__fmul_rn(dx, dL0), __fmul_rn(dy, dL1));
+        const float gDO = __fadd_rn(__fmul_rn(dx, dO0), __fmul_rn(dy, dO1));
+        const float pl = __fadd_rn(pgdL, gDL), nl = __fsub_rn(ngdL, gDL), po = __fadd_rn(pgdO, gDO), no = __fsub_rn(ngdO, gDO);
+        pgdL = (in && gDL > 0) ? pl : pgdL;
+        ngdL = (in && !(gDL > 0)) ? nl : ngdL;
+        pgdO = (in && gDO > 0) ? po : pgdO;
+        ngdO = (in && !(gDO > 0)) ? no : ngdO;
+      }
+    };
+    for (int left = lengthOfLSP; left > 0; left -= 32) {
+      if (left > 16) walk(std::integral_constant<int, 32>{}, min(left, 32));
+      else walk(std::integral_constant<int, 16>{}, left);
     }
     const float cg = coef->G[lane];
     rowS[lane][0] = __fmul_rn(cg, pgdL);
