@@ -87,7 +87,6 @@ struct pli_ctx {
   bool lsdF64 = false; double* mg = nullptr; unsigned long long* maxMg = nullptr; double* tmp64 = nullptr; double* kern64 = nullptr;
   int* lsdTab64 = nullptr; int lsdRadius = 0;
   LsdFront lsdFront = LsdFront::Unfused;     // the form of the front pass that applies to the geometry (a debug context runs Unfused)
-  int lsdFrontChunk = 0;                     // Stream: scaled rows per wave
   int2* hot = nullptr;                       // tile relaxation, CV_64F detector: round 1's 8-byte hot records {angle, owner word} (lsd_tile.hip)
   float2* cold = nullptr;                    // ... and the records' exact {cos, sin}: written instead of the 16-byte records when every round runs on the hot ones
   int2* own = nullptr; RxSeed* smallSeeds = nullptr; RxSeed* bigSeeds = nullptr; int bigCap = 0;

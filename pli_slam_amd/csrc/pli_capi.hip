@@ -121,19 +121,15 @@ bool frontStreamFits(const std::vector<int>& t, int sw, int sh, int dw, int dh, 
   return true;
 }
 
-// the form for a geometry (t: buildResizeTab64); dev switches PLI_LSD_NOFUSE: the three kernels, PLI_LSD_FRONT_TILED: the tiled form
-// where the streaming one applies (A/B, cross-checks)
+// the form for a geometry (t: buildResizeTab64); dev switch PLI_LSD_NOFUSE: the three kernels
 LsdFront frontForm(const std::vector<int>& t, int sw, int sh, int dw, int dh, int radius) {
   if (!frontTiledFits(t, sw, sh, dw, dh, radius) || DEVENV("PLI_LSD_NOFUSE")) return LsdFront::Unfused;
-  return frontStreamFits(t, sw, sh, dw, dh, radius) && !DEVENV("PLI_LSD_FRONT_TILED") ? LsdFront::Stream : LsdFront::Tiled;
+  return frontStreamFits(t, sw, sh, dw, dh, radius) ? LsdFront::Stream : LsdFront::Tiled;
 }
 
 // scaled rows per wave of the streaming front: each chunk enters 6 source rows to warm its window up, and a strip's chunks are what
-// fills the chip; dev switch PLI_LSD_FRONT_CHUNK (8 .. 4096)
+// fills the chip
 constexpr int LSD_FRONT_CHUNK = 64;
-int frontStreamChunk(const char* dev) {
-  return dev ? std::max(8, std::min(4096, atoi(dev))) : LSD_FRONT_CHUNK;
-}
 
 // One call of the CV_64F front pass (lsd_f64.hip) in the given form on images img0 .. img0 + n - 1: the image's largest norm cleared,
 // then the form's kernels.  The forms share their profile names (k_lsd_front: either fused form).
@@ -494,7 +490,6 @@ pli_status allocAll(pli_ctx* c) {
       A(c->lsdTab64, t.size());
       HIPCHK(hipMemcpy(c->lsdTab64, t.data(), t.size() * 4, hipMemcpyHostToDevice));
       c->lsdFront = frontForm(t, P.W, P.H, P.LWt, P.LH, h);
-      c->lsdFrontChunk = frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK"));
     }
   } else {
     A(c->g2, npix * NI);
@@ -701,7 +696,7 @@ pli_status runIngest(pli_ctx* c, const uint8_t* dl, const uint8_t* dr, int64_t s
   const DevParams& P = c->hp;
   const bool aligned16 = !c->rectMap[0] && !c->rectMap[1] && (P.W % 16) == 0 && (stride % 16) == 0 && (frameStride % 16) == 0 &&
                          (reinterpret_cast<uintptr_t>(dl) % 16) == 0 && (reinterpret_cast<uintptr_t>(dr) % 16) == 0 && (P.lv[0].pitch % 16) == 0 &&
-                         (P.pyrBlock % 16) == 0 && !DEVENV("PLI_INGEST_BYTES");
+                         (P.pyrBlock % 16) == 0;
   if (aligned16) {
     const int n16 = (P.W / 16) * P.H;
     LAUNCH(c, "k_ingest", k_ingest_copy16, dim3(std::max(1, std::min((n16 + 255) / 256, 64)), nimg), dim3(256), 0, dl, dr, stride, frameStride,
@@ -731,9 +726,8 @@ pli_status runOrb(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     int need = 0;
     for (int l = 0; l < P.nlevels; ++l) need = std::max(need, std::max(P.lv[l].nfeatures + 8, 4 * P.lv[l].nIni + 8));
     // workgroups of 1024 threads while the (level, image) workgroups do not fill the chip (4K: 32 images x 8 levels; a single pair:
-    // 16 workgroups): the passes over a level's keys are the long pole, 4x the threads on them (dev switch PLI_OCTREE_WIDE=0/1)
-    bool wide = P.nlevels * nimg <= 1024;
-    if (const char* e = DEVENV("PLI_OCTREE_WIDE")) wide = atoi(e) != 0;
+    // 16 workgroups): the passes over a level's keys are the long pole, 4x the threads on them
+    const bool wide = P.nlevels * nimg <= 1024;
     const dim3 og(P.nlevels, nimg), ob(wide ? 1024 : 256);
 #define OCTREE_LAUNCH(K) LAUNCH(c, "k_octree", K, og, ob, 0, c->dP, c->cellCand, c->cellCount, c->candAll, c->nodeOf, c->candCount, c->kpSel, c->kpSelCount, img0)
     if (need <= 320) { if (wide) OCTREE_LAUNCH(k_octree_320_w); else OCTREE_LAUNCH(k_octree_320); }
@@ -771,26 +765,46 @@ pli_status runLbdPre(pli_ctx* c, int img0, int nimg) {
   return PLI_OK;
 }
 
+// this call takes the sequential grower: asked for, or auto mode with a batch the relaxations' buffers are not meant (or not sized) for
+bool sequentialGrower(const pli_ctx* c, int nimg) {
+  return c->lsdMode == 2 || (c->lsdMode == 0 && (nimg >= RX_AUTO_IMAGES || nimg > c->rxImages));
+}
+
 pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
   TraceRange range__("pli:line chain");
   const DevParams& P = c->hp;
   const pli_table_layout& Y = c->lay;
   const int npix = P.LW * P.LH;
-  const bool sequential = c->lsdMode == 2 || (c->lsdMode == 0 && (nimg >= RX_AUTO_IMAGES || nimg > c->rxImages));
+  const bool sequential = sequentialGrower(c, nimg);
   // (the owner plane's start value: the lane relaxation takes it from the front pass; the tile relaxation's k_tx_sort writes the
   // trivial map for every pixel itself — 8 bytes per scaled pixel less for the front pass to store)
   int2* ownPlane = (sequential || c->lsdMode != 1) ? (int2*)nullptr : c->own;
+  const bool tile = !sequential && c->lsdMode != 1;      // auto below RX_AUTO_IMAGES and mode 3: the tile-sequential relaxation
+  // The tile relaxation's dev switches that choose kernels, each read here once per call (the front pass already needs keyMode, packMode
+  // and hotLevel; tests change the environment between contexts of one process, so nothing is kept across calls).
+  auto devOn = [](const char* e) { return e && atoi(e) != 0; };
+  const bool boxRule = DEVENV("PLI_TX_BOXRULE") != nullptr;         // the conservative round-2 rule
+  const bool cellRule = DEVENV("PLI_TX_CELLRULE") != nullptr;       // ... of rounds >= 3
+  const bool fullRound2 = DEVENV("PLI_TX_FULL2") != nullptr;        // regrow everything in round 2
+  const bool oldMark = DEVENV("PLI_TX_OLDMARK") != nullptr;         // k_rx_mark instead of k_tx_mark
+  const bool fullDiff = DEVENV("PLI_TX_FULLDIFF") != nullptr;       // k_rx_diff over every cell, not the touched ones
+  const bool noFuse2 = DEVENV("PLI_TX_NOFUSE2") != nullptr;         // round 2's diff and prep as two passes
+  const bool noFuseDM = DEVENV("PLI_TX_NOFUSEDM") != nullptr;       // rounds >= 3: diff and mark as two passes
+  const bool noDirtyList = DEVENV("PLI_TX_NODIRTYLIST") != nullptr; // every active tile walks its whole seed list
+  const bool specEnv = devOn(DEVENV("PLI_TX_SPEC")), orderEnv = devOn(DEVENV("PLI_TX_ORDER")), xcdEnv = devOn(DEVENV("PLI_TX_XCD"));
+  // ... and the rules they add up to, each named once
+  const bool lostRule = c->lsdMode != 1 && !boxRule;                // round 2 regrows the regions that lost a contested pixel
+  const bool fuseRound2 = lostRule && !fullRound2 && !noFuse2;      // round 2's pass over the owner map is k_tx_round2
+  // rounds >= 3: k_rx_diff + k_tx_mark as one kernel (k_tx_diffmark; the dev rules keep the separate passes)
+  const bool fusedDM = lostRule && !fullRound2 && !cellRule && !oldMark && !fullDiff && !noFuseDM;
   // key mode of the tile relaxation (lsd_tile.hip): no ordered list — it is only built, at the end, for images left to the sequential grower
-  const bool lostRule0 = c->lsdMode != 1 && DEVENV("PLI_TX_BOXRULE") == nullptr;
-  const bool keyMode = !sequential && c->lsdMode != 1 && c->txKeys && !c->debug && lostRule0 && !DEVENV("PLI_TX_FULL2") &&
-                       !DEVENV("PLI_TX_OLDMARK") && !DEVENV("PLI_TX_CELLRULE");   // (k_rx_mark, lsd_relax.hip, indexes the region planes by rank)
+  const bool keyMode = tile && c->txKeys && !c->debug && lostRule && !fullRound2 && !oldMark && !cellRule;   // (k_rx_mark, lsd_relax.hip, indexes the region planes by rank)
   // packed round 1 (lsd_tile.hip, tx_load_rec16): owner_1 lives in the fourth word of the pixel records during round 1 — one
   // 16-byte gather per neighbour instead of two.  Needs the CV_64F detector (the word is free: the gradient norms have their own
   // plane) and the default schedule (k_tx_round2 moves the result into the owner plane).  In key mode the front pass writes the
   // unclaimed words itself (2: LAZY ids), otherwise k_tx_sort does (1).  Dev switch PLI_TX_PACK1=0 / 1.
   int packMode = 0;
-  if (!sequential && c->lsdMode != 1 && c->lsdF64 && c->mg && lostRule0 && !c->debug && !DEVENV("PLI_TX_FULL2") && !DEVENV("PLI_TX_NOFUSE2") &&
-      !(DEVENV("PLI_TX_SPEC") && atoi(DEVENV("PLI_TX_SPEC")) != 0) && !(DEVENV("PLI_TX_ORDER") && atoi(DEVENV("PLI_TX_ORDER")) != 0))
+  if (tile && c->lsdF64 && c->mg && !c->debug && fuseRound2 && !specEnv && !orderEnv)
     packMode = (keyMode && P.nBins > 128) ? 2 : 1;      // (the lazy form's fixed-point bin width needs maxGrad / (nBins - 1) < 4: tests/test_lazy_ids_cpu.py)
   const int packCap = packMode;                           // (what this call could do: the choice follows the hot-record level below)
   // round 6: round 1's words in 8-byte hot records of their own (lsd_tile.hip "HOT RECORDS"); dev switch PLI_TX_HOT=0 / 1
@@ -799,7 +813,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
   // from the hot records first: k_tx_rec_from_hot); 1: round 1 only; 0: the 16-byte records everywhere (round 5's form)
   int hotLevel = (packMode != 0 && c->hot != nullptr && P.prec <= 1.0 && P.alignFilter != 0) ? 2 : 0;
   if (const char* e = DEVENV("PLI_TX_HOT")) hotLevel = std::min(hotLevel, std::max(0, atoi(e)));
-  if (hotLevel == 2 && (DEVENV("PLI_RX_FULL") || DEVENV("PLI_TX_NODIRTYLIST"))) hotLevel = 1;     // (dev schedules that keep to the plain later-round kernels)
+  if (hotLevel == 2 && noDirtyList) hotLevel = 1;     // (a dev schedule that keeps to the plain later-round kernels)
   // On the hot records the ids are SORT-WRITTEN (1) by default, in key mode too: k_tx_sort stores `unclaimed | id` into the second word
   // of every 8-byte record — 4-byte stores, read-modify-writes of sectors — and round 1 does without the lazy-id test, ~23 of a step's
   // ~150 vector instructions: k_tx_grow 18.6 -> 17.1 ms, k_tx_sort 2.1 -> 3.2.  (Rewriting the whole record, the angle with it, was
@@ -822,7 +836,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     double* scaled64 = reinterpret_cast<double*>(c->regScratch);
     const pli_status st = launchFront64(
         c, c->debug ? LsdFront::Unfused : c->lsdFront, FrontSrc{c->pyr + P.lv[0].offset, P.pyrBlock, P.W, P.H, P.lv[0].pitch},
-        FrontGeom{c->kern64, c->lsdRadius, c->lsdTab64, P.LWt, P.LH, P.LW, c->lsdFrontChunk, P.rho, trigF32},
+        FrontGeom{c->kern64, c->lsdRadius, c->lsdTab64, P.LWt, P.LH, P.LW, LSD_FRONT_CHUNK, P.rho, trigF32},
         LsdFrontPlanes{recPlane, c->mg, ownPlane, hotPlane, coldPlane, packMode == 2}, c->maxMg, img0, nimg,
         FrontUnfused{c->tmp64, (int64_t)P.W * P.H, scaled64, (int64_t)npix, c->debug ? c->angDbg : (float*)nullptr});
     if (st != PLI_OK) return st;
@@ -874,7 +888,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
   if (sequential) {
     // speculative form (line_kernels.hip: lsd_grow_image_spec): the small regions of 64 seeds at a time, one per lane
     const bool spec = c->lsdSpec && P.minRegSize >= 2;
-    const bool two = nimg >= 64 && !DEVENV("PLI_GROW_WPB1");
+    const bool two = nimg >= 64;
     // region2rect off the grower's serial chain: the spec grower leaves the pixel lists in the arena, k_lsd_rect does the segments
     LsdRectItem* items = (spec && DEVENV("PLI_LSD_RECT_OFFLOAD")) ? c->rectItems : (LsdRectItem*)nullptr;      // dev switch: measured, not a gain
     if (two && spec)
@@ -896,8 +910,10 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
 #endif
   } else {
     const bool trace = DEVENV("PLI_RX_TRACE") != nullptr;
-    const bool fullPasses = DEVENV("PLI_RX_FULL") != nullptr;      // dev: full-image bookkeeping in every round
     const bool perRound = DEVENV("PLI_RX_PROFROUNDS") != nullptr;    // profile names carry the round number
+    const char* const maxRoundsEnv = DEVENV("PLI_RX_MAXROUNDS");
+    const char* const planEnv = DEVENV("PLI_RX_PLAN");               // dev / test: a fixed number of look-free rounds (too few: the device-side fallback)
+    const char* const tailEnv = getenv("PLI_TX_TAIL");               // = 0: no persistent kernel (include/pli_frontend.h "Sharing a device")
     int curT = 0;
     auto rxn = [&](const char* n) -> const char* {
       if (!perRound) return n;
@@ -908,20 +924,9 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     };
     // incremental rank-ordered relaxation (lsd_relax.hip): rounds until every image's owner map is a fixed point
     const int64_t npix64 = (int64_t)npix;
-    int growBlocks = std::max(16, std::min(256, 2048 / nimg));
-    if (const char* e = DEVENV("PLI_JR_BLOCKS")) growBlocks = std::max(1, atoi(e));
-    int bigBlocks = std::max(64, std::min(1024, 16384 / nimg));
-    if (const char* e = DEVENV("PLI_JR_BIGBLOCKS")) bigBlocks = std::max(1, atoi(e));
-    int rectBlocks = std::max(64, std::min(2048, 32768 / nimg));
-    if (const char* e = DEVENV("PLI_RECT_BLOCKS")) rectBlocks = std::max(1, atoi(e));      // dev: waves per image of k_rx_rect
-    int bigThresh = RX_HAND;
-    if (const char* e = DEVENV("PLI_JR_BIG")) bigThresh = atoi(e);
-    int maxRounds = 96;
-    if (const char* e = DEVENV("PLI_RX_MAXROUNDS")) maxRounds = std::max(1, std::min(1 << 20, atoi(e)));
-    const float precDeg = (float)(P.prec * 180.0 / 3.14159265358979323846);
-    (void)growBlocks; (void)bigBlocks; (void)bigThresh; (void)precDeg;     // (the lane relaxation's: development build)
+    const int rectBlocks = std::max(64, std::min(2048, 32768 / nimg));      // waves per image of k_rx_rect
+    int maxRounds = maxRoundsEnv ? std::max(1, std::min(1 << 20, atoi(maxRoundsEnv))) : 96;
     if (c->rgClean) HIPCHK(hipMemsetAsync(c->rgClean + (int64_t)img0 * npix, 0, npix64 * nimg, c->stream));   // round stamps
-    const bool lostRule = c->lsdMode != 1 && DEVENV("PLI_TX_BOXRULE") == nullptr;     // dev switch: the conservative round-2 rule
     {
       // everything the relaxation wants zeroed at the start of a call, in one launch (k_zero_ranges): control blocks, the cell tables,
       // the tile relaxation's per-tile dirty counters (cleared by their consumers from then on), the barrier words of k_tx_tail and the
@@ -956,27 +961,23 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     }
     // (the rank plane was written by k_lsd_scatter)
     const dim3 raster((P.LW + 255) / 256, P.LH, nimg);
-    const bool tile = c->lsdMode != 1;      // auto below RX_AUTO_IMAGES and mode 3: the tile-sequential relaxation
     bool allDone = false;
     // what the last look-free call left behind (if its copy has arrived): how many rounds its slowest image needed
     if (c->rxSeenImages > 0 && hipEventQuery(c->evRxSeen) == hipSuccess) foldRoundStats(c);
-    if (tile && c->tailBar && c->tailBlocks == 0) {       // the resident grid of k_tx_tail: CUs x blocks per CU (-1: it does not fit)
+    if (tile && c->tailBar && c->tailBlocks == 0) {       // the resident grid of k_tx_tail: one block per CU (-1: it does not fit)
       int perCu = 0, cus = 0;
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_tx_tail, 256, 0));
       HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-      int bpc = 1;
-      if (const char* e = DEVENV("PLI_TX_TAIL_BPC")) bpc = std::max(1, atoi(e));
-      c->tailBlocks = perCu < 1 ? -1 : std::min(perCu, bpc) * std::max(1, cus);
+      c->tailBlocks = perCu < 1 ? -1 : std::max(1, cus);
     }
     c->tailLaunched = false;
     const bool tailLatched = c->device < 0 || c->device >= TAIL_MAX_DEVICES || g_tailAborted[c->device].load(std::memory_order_relaxed);   // (no chain slot for the device: no tail)
-    const bool tailPossible = tile && c->tailBar && c->tailBlocks > 0 && !tailLatched && !DEVENV("PLI_RX_PLAN") && !trace && !perRound && !DEVENV("PLI_RX_BLOCKING") &&
-                              !(getenv("PLI_TX_TAIL") && atoi(getenv("PLI_TX_TAIL")) == 0) && lostRule && !DEVENV("PLI_TX_FULL2") &&
-                              !DEVENV("PLI_TX_CELLRULE") && !DEVENV("PLI_TX_OLDMARK") && !DEVENV("PLI_TX_FULLDIFF") &&
-                              !DEVENV("PLI_TX_NOFUSEDM") && !DEVENV("PLI_TX_NODIRTYLIST");
-    const bool blocking = !tailPossible && (c->rxLastRounds == 0 || trace || DEVENV("PLI_RX_BLOCKING") != nullptr);
+    // (the tail is k_tx_diffmark's rounds on the dirty lists: fusedDM, and the lists, which a tile context allocates with the barrier words)
+    const bool tailPossible = tile && c->tailBar && c->tailBlocks > 0 && !tailLatched && !planEnv && !trace && !perRound &&
+                              !(tailEnv && atoi(tailEnv) == 0) && fusedDM && !noDirtyList;
+    const bool blocking = !tailPossible && (c->rxLastRounds == 0 || trace);
     if (!blocking && !tailPossible) maxRounds = std::min(maxRounds, c->rxLastRounds + c->rxMargin);
-    if (!blocking) if (const char* e = DEVENV("PLI_RX_PLAN")) maxRounds = std::max(1, std::min(1 << 20, atoi(e)));   // dev / test: a plan that is too short
+    if (!blocking && planEnv) maxRounds = std::max(1, std::min(1 << 20, atoi(planEnv)));   // (a plan that is too short: test_look_free_rounds_and_device_side_fallback)
     c->rxPlanned = blocking ? 0 : (tailPossible ? -1 : maxRounds);
     // The call's stamp base (pli_ctx::lineStampNext).  No round of this call is above maxRounds — the host loop below and k_tx_tail, which
     // counts its own rounds, both end there — so the next call starts maxRounds + 1 higher.  Before the counter would pass INT_MAX (once in
@@ -1014,12 +1015,18 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
     if (tile) {
       // tile-sequential relaxation (lsd_tile.hip): per-tile seed lists once, then rounds of one wave per tile
       const int ts = c->txTs, ntile = c->txNtx * c->txNty;
+      // (test switch: a wide margin sends every unclaimed pixel of the LAZY form through the double plane; the results must not change)
+      const char* const lazyMarginEnv = DEVENV("PLI_TX_LAZY_MARGIN");
+      const char* const forkRoundEnv = DEVENV("PLI_SIDE_FORK_ROUND");
+      const char* const rectAsideEnv = DEVENV("PLI_RECT_ASIDE");
+      const char* const cellsEnv = DEVENV("PLI_TX_CELLS");
+      const char* const tailT0Env = DEVENV("PLI_TX_TAIL_T0");
+      const bool tailForceAbort = DEVENV("PLI_TX_TAIL_FORCE_ABORT") != nullptr;   // test switch: the kernel leaves at once, as after a barrier timeout
       TxKeys keys{};
       if (keyMode) keys = TxKeys{c->mg, c->maxMg, P.rho, P.nBins, c->txPixBits, c->rankOf};
       const bool pack1 = packMode != 0;
       if (pack1) { keys.recPack = c->rec; keys.pack = packMode; keys.hot = hotPlane; keys.cold = coldPlane; }
-      // (test switch: a wide margin sends every unclaimed pixel of the LAZY form through the double plane; the results must not change)
-      if (const char* e = DEVENV("PLI_TX_LAZY_MARGIN")) keys.lazyMargin = std::max(4, std::min(0x3FFFFFFF, atoi(e)));
+      if (lazyMarginEnv) keys.lazyMargin = std::max(4, std::min(0x3FFFFFFF, atoi(lazyMarginEnv)));
 #ifdef PLI_DEV
       if (ts == 128)
         TRL(c, "k_tx_sort", k_tx_sort128, dim3(ntile, nimg), dim3(1024), 0, c->rankOf, c->order, c->own, c->txList,
@@ -1028,12 +1035,10 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
 #endif
         TRL(c, "k_tx_sort", k_tx_sort, dim3(ntile, nimg), dim3(256), 0, c->rankOf, c->order, c->own, c->txList,
             c->txTileCnt, P.LW, P.LH, ts, c->txNtx, c->txNty, img0, keys);
-      const bool fullRound2 = DEVENV("PLI_TX_FULL2") != nullptr;       // dev: regrow everything in round 2
-      const size_t txPad = DEVENV("PLI_TX_LDSPAD") ? (size_t)atoi(DEVENV("PLI_TX_LDSPAD")) : 0;   // dev: occupancy cap of the tile growers
       TxDirtyLists DL{c->txDirtyList, c->txDirtyCnt, c->order, ts, c->txNtx, c->txNty, P.LW, npix64};
       if (keyMode) DL.rmask = (1 << c->txPixBits) - 1;
       DL.stamp = stampBase;
-      if (DEVENV("PLI_TX_NODIRTYLIST")) DL.list = nullptr;             // dev: every active tile walks its whole seed list
+      if (noDirtyList) DL.list = nullptr;
       TxDirtyLists noDL = DL; noDL.list = nullptr;
       // The planes of the relaxation, the one argument record of every kernel of a round (TxRound, common.hpp).  A launch that differs in
       // a field takes a copy: `first` — round 1 and round 2's pass over the owner map read ROUND 1's hot records, the later rounds theirs.
@@ -1041,59 +1046,55 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
                         c->tileAct, c->tileTouch, P.LW, P.LH, c->tilesW, c->tilesH, c->arena, c->arenaCap, c->rects, c->rectCap, c->rgSeg,
                         c->mg, c->rankOf, lostRule ? c->rgLost : (int*)nullptr, DL, img0, nimg, hotLater, coldPlane};
       TxRound first = txr; first.hot = hotPlane;
-      // the ORB chain forks from the line chain here (pli_batch_run handed it over; where: sideForkRound below)
-      auto forkSideChain = [&]() -> pli_status {
-        auto f = std::move(c->sideChain);
-        c->sideChain = nullptr;
-        return f();
-      };
       // region2rect of the regions a round completed, on whatever c->stream is at the call
       auto rectPass = [&]() -> pli_status {
         TRL(c, "k_rx_rect", k_rx_rect, dim3(rectBlocks, nimg), dim3(64), 0, c->dP, c->jrCtl, c->rec, c->arena, c->arenaCap, c->rects,
             c->rectCap, c->rgSeg, img0, c->mg, DL.rmask, (const int2*)hotPlane, (const float2*)coldPlane);
         return PLI_OK;
       };
-      // rounds >= 3: k_rx_diff + k_tx_mark as one kernel (k_tx_diffmark; the dev rules keep the separate passes)
-      const bool fusedDM = lostRule && !fullRound2 && !DEVENV("PLI_TX_CELLRULE") && !DEVENV("PLI_TX_OLDMARK") && !DEVENV("PLI_TX_FULLDIFF") &&
-                           !DEVENV("PLI_TX_NOFUSEDM");
-      // rounds >= tailT0 in one persistent launch that ends by itself when every image is at its fixed point (no host look, no
-      // planned round count; dev switches: PLI_TX_TAIL=0, PLI_TX_TAIL_T0, PLI_TX_TAIL_BPC)
       // Where the deferred ORB chain forks from the line chain (pli_batch_run): behind round 1's growth up to 64 images, behind round 2's
       // pass over the owner map (-2) above — what waits in a large batch is the END of the line chain (the 1024-thread / 64 KB workgroups
       // of k_tx_emit_sorted, the gated k_lsd_scan, k_keylines find no room while the ORB chain fills every hole), so the chain should end
       // early, and k_tx_round2, which the ORB kernels stretch most, should run alone.  Same box, 256 frames, fork behind round 1 /
       // round 2's owner pass / round 2 / round 3: synthetic 45.0 / 45.0 / 45.4-45.5 / 46.2 ms, photographs 28.6 / 28.5 / 29.5 / 30.0
-      // (DESIGN.md 5 has the history).  Dev switch PLI_SIDE_FORK_ROUND.
-      const int sideForkEnv = DEVENV("PLI_SIDE_FORK_ROUND") ? atoi(DEVENV("PLI_SIDE_FORK_ROUND")) : 0;
-      const int sideForkRound = sideForkEnv ? sideForkEnv : (nimg <= 64 ? 1 : -2);
+      // (DESIGN.md 5 has the history).  Dev switch PLI_SIDE_FORK_ROUND: a round t >= 2 (behind its growth), -2, anything else round 1.
+      const int forkRoundAsked = forkRoundEnv ? atoi(forkRoundEnv) : 0;
+      const int sideForkRound = forkRoundAsked == 0 ? (nimg <= 64 ? 1 : -2) : forkRoundAsked == -2 ? -2 : std::max(1, forkRoundAsked);
+      // the ORB chain forks from the line chain behind `step` (pli_batch_run handed it over): the growth of round `step`, or round 2's owner pass (-2)
+      auto forkSideChainBehind = [&](int step) -> pli_status {
+        if (!c->sideChain || step != sideForkRound) return PLI_OK;
+        auto f = std::move(c->sideChain);
+        c->sideChain = nullptr;
+        return f();
+      };
       // (round 1's region2rect pass on a stream of its own beside k_tx_round2: the default schedule only; dev switch PLI_RECT_ASIDE=0)
       // (a single pair pays 0.06 ms for the two events and the reset launch and has nothing to overlap: from 8 images on)
       // (the ORB chain's stream when the chain is waiting to fork behind round 2 or later: idle until then)
-      const bool rectOnSide = c->sideChain && c->aux && (sideForkRound >= 2 || sideForkRound == -2) && !DEVENV("PLI_RECT_OWN_STREAM");
-      const bool rectAside = lostRule && !fullRound2 && !DEVENV("PLI_TX_NOFUSE2") && !trace && !perRound && !blocking && maxRounds >= 2 && !c->syncDebug &&
-                             (DEVENV("PLI_RECT_ASIDE") ? atoi(DEVENV("PLI_RECT_ASIDE")) != 0 : (nimg >= 8 && (rectOnSide || c->sH2D == nullptr)));
-      const bool useTail = tailPossible && fusedDM && DL.list;
+      const bool rectOnSide = c->sideChain && c->aux && sideForkRound != 1;
+      const bool rectAside = fuseRound2 && !trace && !perRound && !blocking && maxRounds >= 2 && !c->syncDebug &&
+                             (rectAsideEnv ? atoi(rectAsideEnv) != 0 : (nimg >= 8 && (rectOnSide || c->sH2D == nullptr)));
       // rounds 3 .. tail start of a large batch by cell lists (six lean launches per round instead of four that walk every block;
       // a small batch keeps the four: launches are what it pays for).  Dev switch PLI_TX_CELLS=0 / 1.
       // (measured: 256 frames of 752 x 480 +2 %, 64 of 1280 x 720 +1 %, 16 of 4K +2 %; 32 frames of 752 x 480 -4 %: a million cells is the line)
       bool useCells = fusedDM && DL.list && c->txCellList && (int64_t)c->tilesW * c->tilesH * nimg >= (1 << 20);
-      if (const char* e = DEVENV("PLI_TX_CELLS")) useCells = atoi(e) != 0 && fusedDM && DL.list && c->txCellList;
+      if (cellsEnv) useCells = atoi(cellsEnv) != 0 && fusedDM && DL.list && c->txCellList;
+      // Rounds >= tailT0 in one persistent launch that ends by itself when every image is at its fixed point (no host look, no planned
+      // round count; switches: PLI_TX_TAIL=0, PLI_TX_TAIL_T0).
       // The persistent kernel takes over at round 8 — at round 12 when the rounds before it run on cell lists: their launches are lean, and
       // a large batch still has the ORB chain on the chip around round 8, beside which the tail's 256 workgroups of 50 KB LDS, which must
       // ALL be resident, wait for their compute units (k_tx_tail 0.7 ms alone, 2.6 ms in the default line).  256 frames, same box, start
       // at 8 / 12 / 14 / 16: synthetic 46.0-46.1 / 45.7 / 45.6 / 45.6 ms, photographs 29.2-29.3 / 29.3 / 29.4 / 29.7.
       int tailT0 = useCells ? 12 : 8;
-      if (const char* e = DEVENV("PLI_TX_TAIL_T0")) tailT0 = std::max(3, atoi(e));
+      if (tailT0Env) tailT0 = std::max(3, atoi(tailT0Env));
       for (int t = 1; t <= maxRounds && !allDone; ++t) {
         curT = t;
-        if (useTail && t == tailT0) {
+        if (tailPossible && t == tailT0) {
           // (the dirty counters are zero: every list of the last round was taken by its tile's wave; the barrier words were cleared
           // with the control blocks)
           TxTailArgs ta{txr, t, maxRounds, c->tailBar};
           // (a grid barrier costs 8 us with 256 workgroups and less with fewer: a few images do not need the whole chip in the late rounds)
           // (single pair: k_tx_tail 149 us with 256 workgroups, 90 with 64)
-          int tb = std::min(c->tailBlocks, std::max(64, 8 * nimg));
-          if (const char* e = DEVENV("PLI_TX_TAIL_BLOCKS")) tb = std::max(1, std::min(c->tailBlocks, atoi(e)));     // dev switch
+          const int tb = std::min(c->tailBlocks, std::max(64, 8 * nimg));
           // k_tx_tail spins on a grid barrier, so its grid must be co-resident; the grid is sized for a device it has to itself.  Two
           // tails in flight at once (two contexts of this process on one device) could each hold a part of the other's slots and spin
           // until the barrier's timeout: tails of one process are chained per device — a tail starts when the previous one has ended.
@@ -1103,7 +1104,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
             std::lock_guard<std::mutex> lk(g_tailMu);
             hipEvent_t& ev = g_tailEv[c->device];             // (0 <= device < TAIL_MAX_DEVICES: tailPossible)
             c->tailLaunched = true;
-            ta.forceAbort = DEVENV("PLI_TX_TAIL_FORCE_ABORT") ? 1 : 0;   // test switch: the kernel leaves at once, as after a barrier timeout
+            ta.forceAbort = tailForceAbort ? 1 : 0;
             if (ev) HIPCHK(hipStreamWaitEvent(c->stream, ev, 0));
             else HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
             LAUNCH(c, "k_tx_tail", k_tx_tail, dim3(tb), dim3(256), 0, ta);
@@ -1115,7 +1116,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
         // the dev schedule that regrows everything in round 2 does not read the lists it stamped)
         if (t == 3 && DL.list && fullRound2)
           HIPCHK(hipMemsetAsync(c->txDirtyCnt + (int64_t)img0 * ntile, 0, sizeof(int) * (size_t)ntile * nimg, c->stream));
-        const bool fused2 = t == 2 && !fullRound2 && lostRule && !DEVENV("PLI_TX_NOFUSE2");    // (dev switch: the two passes)
+        const bool fused2 = t == 2 && fuseRound2;
         bool cellsDone = false;
         if (fused2) {
           TRL(c, "k_tx_round2", k_tx_round2, dim3((P.LW + 31) / 32, (P.LH + 31) / 32, nimg), dim3(256), 0, first, t,
@@ -1124,10 +1125,8 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
             HIPCHK(hipStreamWaitEvent(c->stream, c->evRectDone, 0));
             TRL(c, "k_tx_reset_rect", k_tx_reset_rect, dim3((nimg + 255) / 256), dim3(256), 0, c->jrCtl, nimg, img0);
           }
-          if (c->sideChain && sideForkRound == -2) {      // (dev switch: the ORB chain forks behind round 2's pass over the owner map, before its growth)
-            pli_status ss = forkSideChain();
-            if (ss != PLI_OK) return ss;
-          }
+          const pli_status ss = forkSideChainBehind(-2);       // (before round 2's growth)
+          if (ss != PLI_OK) return ss;
         } else if (t >= 3 && fusedDM && useCells && t < TX_CELL_ROUNDS) {
           // cell lists (lsd_tile.hip "CELL LISTS"): the cells touched in round t - 1 -> their changed pixels' marks -> the active cells
           // -> their owner words.  A list and its length per image (and round: zeroed once per call) stay on the device; a few
@@ -1151,7 +1150,7 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
         else if (t >= 2)                     // (round 1 starts from the trivial map: nothing to compare, the control block is zeroed)
           TRL(c, "k_rx_diff", k_rx_diff, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->tileMin, c->tileAct,
               P.LW, P.LH, c->tilesW, c->tilesH, t, img0,
-              (t >= 3 && !fullRound2 && !DEVENV("PLI_TX_FULLDIFF")) ? (const int*)c->tileTouch : (const int*)nullptr);
+              (t >= 3 && !fullRound2 && !fullDiff) ? (const int*)c->tileTouch : (const int*)nullptr);
 #endif
         if (t >= 3 || (t == 2 && !fullRound2)) {
           // (round 2 under the lost-pixel rule: k_tx_diff2 has stamped the regions itself, k_rx_mark would find nothing)
@@ -1159,12 +1158,12 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
             // (k_tx_diffmark has done it)
           }
 #ifdef PLI_DEV
-          else if (lostRule && t >= 3 && !DEVENV("PLI_TX_CELLRULE") && !DEVENV("PLI_TX_OLDMARK"))
+          else if (lostRule && t >= 3 && !cellRule && !oldMark)
           TRL(c, "k_rx_mark", k_tx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, txr, t, (const int*)c->tileMin);
           else if (t >= 3 || !lostRule)
           TRL(c, "k_rx_mark", k_rx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf, c->rgBox,
               c->rgDirty, c->tileMin, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, t >= 3 ? 1 : 0,
-              (lostRule && t >= 3 && !DEVENV("PLI_TX_CELLRULE")) ? (const int*)c->rgLost : (const int*)nullptr, DL);
+              (lostRule && t >= 3 && !cellRule) ? (const int*)c->rgLost : (const int*)nullptr, DL);
 #endif
           if (!fused2 && !cellsDone) {
             TxRound prep = txr;                           // (after separate diff and mark passes — dev schedules — no cell stamps, one flag)
@@ -1173,8 +1172,8 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           }
           TxRound grow = txr;                             // (dev: a round 2 that regrows everything walks the seed lists, not the dirty lists)
           if (fullRound2 && t == 2) grow.DL = noDL;
-          if (hotLater) TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse_h, dim3(ntile, nimg), dim3(64), txPad, grow, t);
-          else TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse, dim3(ntile, nimg), dim3(64), txPad, grow, t);
+          if (hotLater) TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse_h, dim3(ntile, nimg), dim3(64), 0, grow, t);
+          else TRL(c, "k_tx_grow_sparse", k_tx_grow_sparse, dim3(ntile, nimg), dim3(64), 0, grow, t);
         } else {
           TxRound r1 = first;                             // (round 1: no dirty lists yet, every tile walks its seed list)
           r1.DL = noDL;
@@ -1182,18 +1181,17 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           // and measured in round 3, NOT the default — 37 ms against 22 ms of the plain schedule at 256 frames (the
           // divergent per-lane accept path costs more instructions than the whole-wave steps it replaces).  Dev switch PLI_TX_SPEC=1.
 #ifdef PLI_DEV
-          const bool specRound1 = lostRule && P.minRegSize >= 3 && DEVENV("PLI_TX_SPEC") && atoi(DEVENV("PLI_TX_SPEC")) != 0;
-          if (specRound1)
-          TRL(c, "k_tx_grow", k_tx_grow_spec, dim3(ntile, nimg), dim3(64), txPad, r1, t);
+          if (lostRule && P.minRegSize >= 3 && specEnv)
+          TRL(c, "k_tx_grow", k_tx_grow_spec, dim3(ntile, nimg), dim3(64), 0, r1, t);
           else
 #endif
           {
           // dev switch PLI_TX_ORDER=1: the heaviest tiles first (k_tx_order).  Measured, not the default: the launch does end on fewer
           // stragglers, but consecutive workgroups no longer grow neighbouring tiles of one image and k_tx_grow goes from 23.2 to
           // 31.3 ms at 256 frames (4K: 33.1 -> 44.2 ms) — the grid order's locality is worth more than the balance
-          if ((nimg % 8) == 0 && DEVENV("PLI_TX_XCD") && atoi(DEVENV("PLI_TX_XCD")) != 0) r1.DL.xcdAffine = 1;
+          if ((nimg % 8) == 0 && xcdEnv) r1.DL.xcdAffine = 1;
 #ifdef PLI_DEV
-          if (DEVENV("PLI_TX_ORDER") && atoi(DEVENV("PLI_TX_ORDER")) != 0) {
+          if (orderEnv) {
             TRL(c, "k_tx_order", k_tx_order, dim3(1), dim3(1024), 0, (const int*)c->txTileCnt, ntile, nimg, img0, c->txPerm + (int64_t)img0 * ntile);
             r1.DL.perm = c->txPerm + (int64_t)img0 * ntile;
           }
@@ -1201,22 +1199,16 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
           // (the forms with owner_1 packed into the records, 16-byte or hot, take the keys beside the planes)
           void (*const packed)(TxRound, int, TxKeys) = (hotPlane && packMode == 2) ? k_tx_grow_h2 : packMode == 2 ? k_tx_grow_p2 :
                                                        (!hotPlane && packMode == 1) ? k_tx_grow_p1 : nullptr;
-          if (packed) TRL(c, "k_tx_grow", packed, dim3(ntile, nimg), dim3(64), txPad, r1, t, keys);
+          if (packed) TRL(c, "k_tx_grow", packed, dim3(ntile, nimg), dim3(64), 0, r1, t, keys);
           else if (hotPlane)       // (the default: the one kernel with its planes as `__restrict__` parameters, lsd_tile.hip k_tx_grow_h1)
-          TRL(c, "k_tx_grow", k_tx_grow_h1, dim3(ntile, nimg), dim3(64), txPad, r1.Pp, r1.ctl, r1.rec, r1.own, r1.list, r1.tileCnt, r1.ts,
+          TRL(c, "k_tx_grow", k_tx_grow_h1, dim3(ntile, nimg), dim3(64), 0, r1.Pp, r1.ctl, r1.rec, r1.own, r1.list, r1.tileCnt, r1.ts,
               r1.ntx, r1.nty, r1.rgSize, r1.rgBox, (const int*)r1.rgDirty, (const int*)r1.tileAct, r1.TW, r1.TH, r1.arena, r1.arenaCap,
               r1.rects, r1.rectCap, r1.img0, t, r1.rank, r1.rgLost, r1.tileTouch, r1.DL, keys);
-          else TRL(c, "k_tx_grow", k_tx_grow, dim3(ntile, nimg), dim3(64), txPad, r1, t);
-          }
-          if (c->sideChain && sideForkRound <= 1 && sideForkRound != -2) {       // (pli_batch_run: the ORB chain forks here, behind round 1)
-            pli_status ss = forkSideChain();
-            if (ss != PLI_OK) return ss;
+          else TRL(c, "k_tx_grow", k_tx_grow, dim3(ntile, nimg), dim3(64), 0, r1, t);
           }
         }
-        if (c->sideChain && t >= 2 && t == sideForkRound) {   // (dev switch PLI_SIDE_FORK_ROUND: ... behind the growth of a later round)
-          pli_status ss = forkSideChain();
-          if (ss != PLI_OK) return ss;
-        }
+        const pli_status ss = forkSideChainBehind(t);         // (pli_batch_run: behind round 1's growth by default, a later round's by the dev switch)
+        if (ss != PLI_OK) return ss;
         if (t == 1 && rectAside) {
           // Round 1's region2rect pass (gather / latency bound, 2.9 ms at 256 frames) beside round 2's pass over the owner map (bandwidth
           // bound, 2.1 ms): the two touch disjoint data — the pass reads the round's pixel lists and writes the segment plane, k_tx_round2
@@ -1262,12 +1254,15 @@ pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table) {
       g_err = "lsd_mode 1 (the lane relaxation) is a development schedule: libpli_frontend_dev.so";
       return PLI_ERR_INVALID;
 #else
+    // grid sizes of the lane growers, the size from which a region counts as large
+    const int growBlocks = std::max(16, std::min(256, 2048 / nimg)), bigBlocks = std::max(64, std::min(1024, 16384 / nimg)), bigThresh = RX_HAND;
+    const float precDeg = (float)(P.prec * 180.0 / 3.14159265358979323846);
     TRL(c, "k_rx_guess", k_rx_guess, raster, dim3(256), 0, c->rec, c->rankOf, c->own, P.LW, P.LH, precDeg, img0);
     for (int t = 1; t <= maxRounds && !allDone; ++t) {
       curT = t;
       TRL(c, "k_rx_diff", k_rx_diff, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->tileMin, c->tileAct,
              P.LW, P.LH, c->tilesW, c->tilesH, t, img0, (const int*)nullptr);
-      if (t >= 3 && !fullPasses) {
+      if (t >= 3) {
         // bookkeeping only where something happened (lsd_relax.hip)
         TRL(c, "k_rx_mark", k_rx_mark, dim3((P.LW + 31) / 32, (c->tilesH + 7) / 8, nimg), dim3(256), 0, c->jrCtl, c->own, c->rankOf, c->rgBox,
             c->rgDirty, c->tileMin, c->tileAct, P.LW, P.LH, c->tilesW, c->tilesH, t, img0, 1, (const int*)nullptr, TxDirtyLists{});
@@ -1385,7 +1380,7 @@ pli_status runStereoLines(pli_ctx* c, int nframes, uint8_t* table) {
   const pli_table_layout& Y = c->lay;
   // (many lines per frame: the pair distances by several workgroups per frame, see the kernel)
   const int cap = c->hp.klCap;
-  const int slices = (cap >= 192 && !DEVENV("PLI_STEREO_LINES_1")) ? std::max(1, std::min(64, (cap * cap) / 8192)) : 1;
+  const int slices = cap >= 192 ? std::max(1, std::min(64, (cap * cap) / 8192)) : 1;
   for (int phase = slices > 1 ? 1 : 0; phase <= (slices > 1 ? 3 : 0); ++phase)
     LAUNCH(c, "k_stereo_lines", k_stereo_lines, dim3(nframes, phase == 2 ? slices : 1), dim3(256), 0, c->dP, table, Y.record_bytes,
            Y.off_counts, Y.off_kl[0], Y.off_kl[1], Y.off_ldesc[0], Y.off_ldesc[1], Y.off_disp, Y.off_le, c->lmask, c->ldir, c->dmat,
@@ -1598,25 +1593,20 @@ pli_status pli_batch_run(pli_ctx* c, int32_t nframes, const uint8_t* dl, const u
   // 1024 frames 4213 -> 4544, 1280 frames 4830 -> 5266; from 1536 frames on the grower's blocks fill the CUs' LDS, the ORB
   // kernels wait for it and stretch the grower: 5170 -> 4287, 2048 frames 6067 -> 4942.
   static const int sideMax = DEVENV("PLI_SIDE_MAX") ? atoi(DEVENV("PLI_SIDE_MAX")) : INT_MAX;    // (dev: images below which the tile relaxation has the ORB chain beside it)
-  static const int sideSeqMax = DEVENV("PLI_SIDE_SEQ_MAX") ? atoi(DEVENV("PLI_SIDE_SEQ_MAX")) : 2560;
-  const bool seqGrower = c->lsdMode == 2 || (c->lsdMode == 0 && (nimg >= RX_AUTO_IMAGES || nimg > c->rxImages));
-  if ((seqGrower ? nimg <= sideSeqMax : nimg < sideMax) && (stages & PLI_RUN_ORB) && (stages & PLI_RUN_LINES) && !c->syncDebug) {
+  const bool seqGrower = sequentialGrower(c, nimg);
+  if ((seqGrower ? nimg <= 2560 : nimg < sideMax) && (stages & PLI_RUN_ORB) && (stages & PLI_RUN_LINES) && !c->syncDebug) {
     if (!c->aux) {
       // (the line chain is the longer one: the ORB chain beside it takes what the line kernels leave free)
       int prLow = 0, prHigh = 0;
       HIPCHK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-      if (DEVENV("PLI_SIDE_NOPRIO")) prLow = 0;            // dev switch: default priority
       HIPCHK(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prLow));
       HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&c->evLbdPre, hipEventDisableTiming));
     }
     hipStream_t main = c->stream;
-    static const bool sideStereo = DEVENV("PLI_SIDE_NOSTEREO") == nullptr;      // (dev switch)
-    static const bool sideLbd = DEVENV("PLI_SIDE_NOLBD") == nullptr;            // (dev switch)
-    static const bool sideDefer = DEVENV("PLI_SIDE_NODEFER") == nullptr;        // (dev switch)
-    stereoPointsDone = (stages & PLI_RUN_STEREO_POINTS) && sideStereo;
-    c->lbdPreOnSide = c->lsdF64 && sideLbd;
+    stereoPointsDone = (stages & PLI_RUN_STEREO_POINTS) != 0;
+    c->lbdPreOnSide = c->lsdF64;
     // the side chain: forks from the line chain where it is enqueued.  Under the tile relaxation that is right after the
     // launch of round 1 (runLines calls it): round 1 keeps the chip to itself, and the later rounds, which leave most of it
     // idle, host the ORB kernels; otherwise before the line chain starts.
@@ -1626,7 +1616,7 @@ pli_status pli_batch_run(pli_ctx* c, int32_t nframes, const uint8_t* dl, const u
       c->stream = c->aux;
       pli_status s2 = runOrb(c, 0, nimg, T);
       // (the stereo point matcher needs the ORB tables only: it stays on the side stream, off the line chain's path)
-      if (s2 == PLI_OK && (stages & PLI_RUN_STEREO_POINTS) && sideStereo) s2 = runStereoPoints(c, nframes, T);
+      if (s2 == PLI_OK && (stages & PLI_RUN_STEREO_POINTS)) s2 = runStereoPoints(c, nframes, T);
       if (s2 == PLI_OK && c->lbdPreOnSide) {
         s2 = runLbdPre(c, 0, nimg);
         if (s2 == PLI_OK) { hipError_t e_ = hipEventRecord(c->evLbdPre, c->aux); if (e_ != hipSuccess) s2 = PLI_ERR_HIP; }
@@ -1644,7 +1634,7 @@ pli_status pli_batch_run(pli_ctx* c, int32_t nframes, const uint8_t* dl, const u
     // it is 47.4 / 47.5 / 47.9 / 48.4 ms on the synthetic stream; which round it forks behind: runLines (sideForkRound).
     const int sideDeferMax = DEVENV("PLI_SIDE_DEFER_MAX") ? atoi(DEVENV("PLI_SIDE_DEFER_MAX")) : -1;   // (dev: images up to which the ORB chain starts behind round 1)
     const bool deferSide = sideDeferMax >= 0 ? nimg <= sideDeferMax : (nimg <= 64 || (nimg <= 1024 && (int64_t)c->hp.W * c->hp.H < 500000));
-    if (sideDefer && !seqGrower && c->lsdMode != 1 && deferSide) c->sideChain = sideChain;
+    if (!seqGrower && c->lsdMode != 1 && deferSide) c->sideChain = sideChain;
     else if ((st = sideChain()) != PLI_OK) { c->lbdPreOnSide = false; return st; }
     st = runLines(c, 0, nimg, T);
     if (st == PLI_OK && c->sideChain) { auto f = std::move(c->sideChain); c->sideChain = nullptr; st = f(); }   // (not taken by runLines)
@@ -1916,7 +1906,6 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   const bool tiled = frontTiledFits(t, w, h, dw, dh, radius);
   const bool stream = tiled && frontStreamFits(t, w, h, dw, dh, radius);
   if (!tiled) { g_err = "the fused front pass does not apply to this size"; return PLI_ERR_INVALID; }
-  const int chunk = frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK"));
   const size_t npix = (size_t)dp * dh, srcPix = (size_t)w * h;
   ScratchPlan plan;
   auto dSrc = plan.add<uint8_t>(srcPix * n);
@@ -1941,7 +1930,7 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   HIPCHK(hipMemcpyAsync(dKern, k, sizeof(k), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(dCount, 0, 8 * sizeof(unsigned), c->stream));
   const FrontSrc S{dSrc, (int64_t)srcPix, w, h, w};
-  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, chunk, P.rho, (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0};
+  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, LSD_FRONT_CHUNK, P.rho, (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0};
   const FrontUnfused U{dBlur, (int64_t)srcPix, dScaled, (int64_t)dw * dh, nullptr};
   for (int f = 0; f < (stream ? 3 : 2); ++f)
     if ((st = launchFront64(c, LsdFront(f), S, G, LsdFrontPlanes{F[f].rec, F[f].mg, F[f].own, F[f].hot, F[f].cold, flags & 1}, F[f].max, 0, n, U)) != PLI_OK)
@@ -1973,7 +1962,7 @@ pli_status pli_selftest_front_stream(pli_ctx* c, const uint8_t* imgs, int32_t n,
   HIPCHK(hipMemcpyAsync(counts, dCount, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int i = 0; i < 8; ++i) out[i] = (int32_t)std::min<unsigned>(counts[i], INT32_MAX);
-  out[8] = chunk;
+  out[8] = LSD_FRONT_CHUNK;
   out[9] = stream ? 1 : 0;
   return PLI_OK;
 }
@@ -2025,7 +2014,7 @@ pli_status pli_selftest_front_planes(pli_ctx* c, const uint8_t* imgs, int32_t n,
   HIPCHK(hipMemcpyAsync(dTab, t.data(), t.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(dKern, k, sizeof(k), hipMemcpyHostToDevice, c->stream));
   const FrontSrc S{dSrc, (int64_t)srcPix, w, h, w};
-  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, frontStreamChunk(DEVENV("PLI_LSD_FRONT_CHUNK")), c->hp.rho,
+  const FrontGeom G{dKern, radius, dTab, dw, dh, dp, LSD_FRONT_CHUNK, c->hp.rho,
                     (c->cfg.parity_flags & PLI_PARITY_TRIG_F32_LSD) ? 1 : 0};
   const FrontUnfused U{dBlur, (int64_t)srcPix, dScaled, (int64_t)dw * dh, nullptr};
   if ((st = launchFront64(c, LsdFront(form), S, G, LsdFrontPlanes{dRec, dMg, dOwn, dHot, dCold, flags & 1}, dMax, 0, n, U)) != PLI_OK) return st;

@@ -57,6 +57,22 @@ def test_the_product_library_reads_four_environment_variables_and_no_more():
         assert hasattr(dev, name), name
 
 
+def test_every_switch_the_library_reads_is_in_the_tools_readme_and_no_other():
+    """The table of tools/README.md ("Environment switches of the library") lists exactly the PLI_* names that the library's sources
+    pass to DEVENV( or getenv(.  The table's rows for the Python side and the C++ adapters are not the library's."""
+    csrc = os.path.join(ROOT, "pli_slam_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp")):
+            read |= set(re.findall(r'\b(?:DEVENV|getenv)\(\s*"(PLI_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    assert {"PLI_ROCTX", "PLI_SYNC_DEBUG", "PLI_TX_TAIL", "PLI_LSD_MODE"} <= read and len(read) > 40
+    doc = open(os.path.join(ROOT, "tools", "README.md")).read().split("## Environment switches of the library", 1)[1]
+    rows = [l.split("|")[1] for l in doc.splitlines() if l.startswith("| `PLI_")]
+    listed = {n for cell in rows for n in re.findall(r"PLI_[A-Z0-9_]+", cell)} - {"PLI_LIB_PATH", "PLI_FUSION_WAIT_MS"}
+    assert read - listed == set(), "read by the library, missing from tools/README.md"
+    assert listed - read == set(), "in tools/README.md, read by nothing"
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():
