@@ -840,15 +840,13 @@ __global__ __launch_bounds__(64) void k_rx_rect(const DevParams* __restrict__ Pp
                                                 const int2* __restrict__ hotAll /* or null: the hot records (regions with approximate sums) */,
                                                 const float2* __restrict__ coldAll /* or null: the exact {cos, sin} plane beside them */) {
   __shared__ double st[3][64];
-  __shared__ double wc[RX_RECT_CACHE][64];
-  __shared__ int ec[RX_RECT_CACHE][64];
   const DevParams& P = *Pp;
   const int img = blockIdx.y + img0;
   const RxCtl& c = ctl[img];
   if (c.state == 2 || c.overflow) return;
   const int64_t npix = (int64_t)P.LW * P.LH;
-  rx_rect_wave(P, c, recAll + img * npix, mgAll ? mgAll + img * npix : nullptr /* CV_64F pipeline: the gradient norm as a double plane */,
-               arenaAll + (int64_t)img * arenaCap, rectAll + (int64_t)img * rectCap, rectCap, rgSegAll + img * npix, blockIdx.x, gridDim.x, st, wc, ec, rmask,
+  rx_rect_wave<true>(P, c, recAll + img * npix, mgAll ? mgAll + img * npix : nullptr /* CV_64F pipeline: the gradient norm as a double plane */,
+               arenaAll + (int64_t)img * arenaCap, rectAll + (int64_t)img * rectCap, rectCap, rgSegAll + img * npix, blockIdx.x, gridDim.x, st, nullptr, nullptr, rmask,
                hotAll ? hotAll + img * npix : nullptr, coldAll ? coldAll + img * npix : nullptr);
 }
 

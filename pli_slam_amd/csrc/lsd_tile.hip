@@ -2358,6 +2358,9 @@ __device__ __forceinline__ bool tx_grid_barrier(unsigned* bar, unsigned target) 
   return s_ok != 0;
 }
 
+// region2rect in the tail keeps the chunk-by-chunk fetches and the LDS cache (lsd_rect.hpp, PRE = false): with the block form's 36
+// kept registers on top of the growers' 204 this kernel takes 256 VGPRs and 48 bytes of scratch, one wave per SIMD in place of two.
+constexpr bool TX_TAIL_RECT_PRE = false;
 __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs T) {
   __shared__ int qs[4][TX_GQ];
   __shared__ int gbs[4][TX_BMAXBLK + 4];
@@ -2486,7 +2489,7 @@ __global__ __launch_bounds__(256) void k_tx_tail(TxTailArgs T) {
         const int img = A.img0 + il;
         const RxCtl& c = A.ctl[img];
         if (c.state == 2 || c.overflow) continue;
-        rx_rect_wave(P, c, A.rec + img * npix, A.mg ? A.mg + img * npix : nullptr, A.arena + (int64_t)img * A.arenaCap,
+        rx_rect_wave<TX_TAIL_RECT_PRE>(P, c, A.rec + img * npix, A.mg ? A.mg + img * npix : nullptr, A.arena + (int64_t)img * A.arenaCap,
                      A.rects + (int64_t)img * A.rectCap, A.rectCap, A.rgSeg + img * npix, gw % per, per, sts[wv], wcs[wv], ecs[wv], A.DL.rmask,
                      A.hot ? A.hot + img * npix : nullptr, A.cold ? A.cold + img * npix : nullptr);
       }
