@@ -1,5 +1,6 @@
-// What the host translation units of libpli_frontend.so share (pli_capi.hip: context, extraction pipeline, measurement; match_capi.hip:
-// the stateless matcher entry points): the context, the error string, the launch and trace macros, and the scratch of one call.
+// What the host translation units of libpli_frontend.so share (pli_capi.hip: context, ingest, ORB chain, stereo stages, entry points,
+// measurement; line_chain.hip: the line chain, runLines and its stages; match_capi.hip: the stateless matcher entry points): the context,
+// the error string, the launch and trace macros, the line chain's entry points and the scratch of one call.
 // Host only.
 #pragma once
 #include "kernels.hpp"
@@ -61,9 +62,9 @@ struct pli_ctx {
   // stage); both chains are launch/latency bound there (+4 % on a single pair, +2.5 % at 32 frames, nothing from 256 frames on)
   hipStream_t aux = nullptr;
   hipEvent_t evFork = nullptr, evJoin = nullptr, evLbdPre = nullptr;
-  hipStream_t aux2 = nullptr;        // round 1's region2rect pass beside round 2's pass over the owner map (runLines)
+  hipStream_t aux2 = nullptr;        // round 1's region2rect pass beside round 2's pass over the owner map (line_chain.hip: tileRect)
   hipEvent_t evRectFork = nullptr, evRectDone = nullptr;
-  std::function<pli_status()> sideChain;     // pli_batch_run -> runLines: enqueues the side stream's work (see pli_batch_run)
+  std::function<pli_status()> sideChain;     // pli_batch_run -> relaxTile (line_chain.hip): enqueues the side stream's work (see pli_batch_run)
   bool lbdPreOnSide = false;                 // the LBD's blur + Sobel of this call ran on the side stream (pli_batch_run)
   bool syncDebug = getenv("PLI_SYNC_DEBUG") != nullptr;
   int NI = 0;
@@ -94,7 +95,7 @@ struct pli_ctx {
   int* rgLost = nullptr;                     // tile relaxation: round in which a region last lost a contested claim (per rank)
   // rgDirty and rgLost hold ROUND STAMPS, and a stamp is only ever compared with a round of the call that reads it.  So the planes are not
   // cleared per call: every call of the tile relaxation stamps with lineStampNext + t and leaves lineStampNext above everything it could
-  // have written (runLines).  Words of earlier calls, under whatever pixels, are below the base and match no round.  One counter per
+  // have written (planRelaxation, line_chain.hip).  Words of earlier calls, under whatever pixels, are below the base and match no round.  One counter per
   // context (the planes are indexed by image slot; calls are ordered by the context's lock and the stream).  Zeroed when allocated and
   // when the counter would pass INT_MAX.  Dev switch PLI_TX_STAMP0: where the counter starts.
   int lineStampNext = 0;
@@ -244,6 +245,16 @@ struct CtxGuard {
   CtxGuard& operator=(const CtxGuard&) = delete;
 };
 
+// the launches of a scope go to another stream (LAUNCH takes c->stream): the context's own is back on every way out
+struct StreamScope {
+  pli_ctx* c;
+  hipStream_t saved;
+  StreamScope(pli_ctx* c_, hipStream_t s) : c(c_), saved(c_->stream) { c->stream = s; }
+  ~StreamScope() { c->stream = saved; }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+
 #define LAUNCH(c, name, kern, grid, block, shmem, ...)                       \
   do {                                                                       \
     TraceRange tr__(name);                                                   \
@@ -257,6 +268,44 @@ struct CtxGuard {
       std::fprintf(stderr, " ok\n");                                         \
     }                                                                        \
   } while (0)
+
+// ---- the line chain (line_chain.hip) and what pli_capi.hip sizes for it or calls of it ----
+// lsd_mode auto: batches of at least this many images (2 per stereo frame) take the sequential wave grower (one wave
+// per image: work-efficient, its throughput keeps growing with the batch); below it the tile-sequential relaxation
+// (lsd_tile.hip: parallel inside an image, ~1.5x the sequential work per frame at large batches).  Measured, 752x480,
+// stereo frames/s (end of round 3, tile vs sequential): 768 frames 5489 vs 3715, 1024 frames 5440 vs 4584, 1280 frames 5497 vs 5435,
+// 1536 frames 5550 vs 5250, 1792 frames 5557 vs 5702, 2048 frames 5995 (sequential).  (Round 2: crossover at 1024 frames.)
+// The hand-over is put at 1280 frames, where the two are level: the relaxations' buffers cost 25 MB per image, and a context of
+// 1600 frames with them would take 250 of the 288 GB.
+constexpr int RX_AUTO_IMAGES = 2560;     // images (2 per stereo frame): 1280 frames
+constexpr int TX_CELL_ROUNDS = 100;   // rounds of a call that can run on cell lists (two list lengths per round and image, zeroed per call)
+// scaled rows per wave of the streaming front: each chunk enters 6 source rows to warm its window up, and a strip's chunks are what
+// fills the chip
+constexpr int LSD_FRONT_CHUNK = 64;
+
+// The arguments of launchFront64: one call of the CV_64F front pass (lsd_f64.hip) in a given form.
+struct FrontSrc { const uint8_t* p; int64_t imgStride; int w, h, pitch; };       // u8 images
+struct FrontGeom {
+  const double* kern; int radius;       // the blur (lsdGauss64)
+  const int* tab;                       // buildResizeTab64, or null: lsd_scale 1 (Unfused only: the u8 image as doubles is the scaled image)
+  int dw, dh, dp;                       // scaled width and height, row pitch of the planes written
+  int chunk;                            // Stream: scaled rows per wave
+  double rho;
+  int trigF32;                          // PLI_PARITY_TRIG_F32_LSD
+};
+struct FrontUnfused {                   // Unfused: the double planes between its kernels (images blurStride / scaledStride apart)
+  double* blurred; int64_t blurStride;
+  double* scaled; int64_t scaledStride;       // rows of the TRUE width dw
+  float* angDbg;                        // or null: the debug plane of the angles
+};
+#pragma GCC visibility push(hidden)     // (shared by the library's translation units, not exported)
+pli_status launchFront64(pli_ctx* c, LsdFront form, const FrontSrc& S, const FrontGeom& G, const LsdFrontPlanes& planes,
+                         unsigned long long* maxMg, int img0, int n, const FrontUnfused& U = {});   // (the front-pass self-tests call it too)
+pli_status runLines(pli_ctx* c, int img0, int nimg, uint8_t* table);
+pli_status runLbdPre(pli_ctx* c, int img0, int nimg);
+bool sequentialGrower(const pli_ctx* c, int nimg);
+int foldRoundStats(pli_ctx* c);
+#pragma GCC visibility pop
 
 inline pli_status ensureScratch(pli_ctx* c, size_t bytes) {
   if (bytes <= c->scratchBytes) return PLI_OK;

@@ -154,7 +154,7 @@ struct TxDirtyLists {
   int xcdAffine = 0;           // round 1: all tiles of an image on ONE XCD (workgroups go to the 8 XCDs round robin)
   int stamp = 0;               // the call's stamp base: round t stamps the per-region planes (rgDirty, rgLost) with stamp + t.  The base moves
                                // up with every call of a context past every round number a call can write, so what earlier calls left in the
-                               // planes matches no round of this one and the planes need no clear per call (pli_capi.hip: lineStampBase)
+                               // planes matches no round of this one and the planes need no clear per call (line_chain.hip: planRelaxation)
 };
 
 // "no rank / no id": what the rank plane (k_lsd_scatter) and the id plane (k_tx_sort, key mode) hold for a pixel without a level-line
@@ -192,7 +192,7 @@ struct LsdFrontPlanes {
 };
 
 // the planes of the tile relaxation (lsd_tile.hip): what every kernel of a round takes, by value — the host fills one per call
-// (runLines, pli_capi.hip) and launches with copies that differ in a field (DL without lists, the hot plane of round 1 / of the later rounds)
+// (relaxTile, line_chain.hip) and launches with copies that differ in a field (DL without lists, the hot plane of round 1 / of the later rounds)
 struct TxRound {
   const DevParams* Pp;
   RxCtl* ctl;

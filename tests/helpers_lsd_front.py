@@ -231,7 +231,7 @@ def compare(want, scaled, norm, angle, max_grad, bound=T, what=""):
 # the case list
 # ---------------------------------------------------------------------------------------------------------------------------------
 Case = namedtuple("Case", "name w h scale sigma_scale")
-DEFAULT_CHUNK = 64                                           # scaled rows per wave of the streaming form (pli_capi.hip LSD_FRONT_CHUNK)
+DEFAULT_CHUNK = 64                                           # scaled rows per wave of the streaming form (capi_host.hpp LSD_FRONT_CHUNK)
 WIDTHS = {53: 64, 54: 65, 107: 128, 75: 90}                  # source width -> scaled width at 1.2: one strip exactly; a second strip of
                                                              # one pixel; two full strips, pitch = width; pad columns 90 .. 95
 TINY = [(7, 7), (7, 6), (6, 7), (6, 6), (4, 5), (3, 3), (2, 9), (9, 2), (1, 9), (1, 1)]      # (w, h); 7 x 7: the first the streaming form takes

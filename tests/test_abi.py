@@ -73,6 +73,16 @@ def test_every_switch_the_library_reads_is_in_the_tools_readme_and_no_other():
     assert listed - read == set(), "in tools/README.md, read by nothing"
 
 
+def test_the_line_chain_reads_each_switch_in_one_place():
+    """line_chain.hip reads every environment switch once per call, at the head of the stage that needs it: each PLI_* name stands
+    in exactly one DEVENV( or getenv( of the file, so no two places can come to read a switch differently."""
+    src = open(os.path.join(ROOT, "pli_slam_amd", "csrc", "line_chain.hip")).read()
+    reads = re.findall(r'\b(?:DEVENV|getenv)\(\s*"(PLI_[A-Z0-9_]+)"', src)
+    assert len(reads) >= 20, reads
+    twice = sorted({n for n in reads if reads.count(n) > 1})
+    assert twice == [], "read in more than one place: %s" % twice
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():

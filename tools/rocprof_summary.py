@@ -59,7 +59,7 @@ def markers(path):
     for r in rs:
         kids.setdefault(r[1], []).append(r)
     print("\n# the last pli_batch_run call, as nested (host time of the launch calls, not kernel time; kernels of the side stream are")
-    print("# enqueued inside the line chain's range — the fork is in runLines)")
+    print("# enqueued inside the line chain's range — the fork is in relaxTile, line_chain.hip)")
 
     def walk(r, depth):
         print("%s%-*s %10.1f us" % ("  " * depth, 34 - 2 * depth, r[4], (r[3] - r[2]) / 1e3))
