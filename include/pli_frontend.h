@@ -486,6 +486,46 @@ pli_status pli_orb_extract_lapping(pli_ctx* ctx, int32_t eye,
                                    pli_keypoint* kp, int32_t cap, uint8_t* desc /* cap x 32 */,
                                    int32_t* n, int32_t* n_mono);
 
+/* --- single-camera Frames of a DISTORTED pinhole camera: the monocular (Frame.cc:334-448) and RGB-D (:231-331) constructors with
+ * Camera.k1 != 0 (TUM RGB-D, monocular EuRoC) ---
+ * K and mDistCoef as the constructors hold them (float).  k3 = 0 stands for a 4-coefficient mDistCoef: the term k[4]*r2 is then
+ * exactly 0, so one struct serves both. */
+typedef struct pli_pinhole_distortion { float fx, fy, cx, cy, k1, k2, p1, p2, k3; } pli_pinhole_distortion;
+
+/* Stores the camera on the context (NULL removes it) and writes bounds = {mnMinX, mnMaxX, mnMinY, mnMaxY} of
+ * Frame::ComputeImageBounds (Frame.cc:947-974): the corners (0,0), (W,0), (0,H), (W,H) of the context's size through the same
+ * device function as the keypoints, min / max of the pairs the reference takes (:962-965).  The reference's gate is kept literally
+ * (:874-878, :909-913, :949, :967-973): with k1 == 0 — whatever the other coefficients — or without a camera nothing is
+ * undistorted, bounds = {0, W, 0, H} and every "undistorted" output of the two calls below is a copy of its input.  bounds may be
+ * NULL.  Synchronous. */
+pli_status pli_set_pinhole_distortion(pli_ctx* ctx, const pli_pinhole_distortion* cam, float bounds[4]);
+
+/* cv::undistortPoints(mat, mat, K, mDistCoef, cv::Mat(), K) as Frame::UndistortKeyPoints (Frame.cc:872-905) and
+ * Frame::UndistortKeyLines (:907-945) call it, for n caller points (x, y) with the context's camera: OpenCV 3.3.1's five-step
+ * iteration in double, no convergence test (csrc/frame_kernels.hip states it; parity with a real OpenCV is unpinned).
+ * With `cell` (may be NULL): Frame::PosInGrid (:845-855) of each result against the context's bounds, as AssignFeaturesToGrid
+ * (:451-482) uses it — posX * 48 + posY, or -1 where the reference returns false.  Stateless: works on the caller's tables and
+ * leaves the context's Frame state alone.  n == 0 is valid. */
+pli_status pli_undistort_points(pli_ctx* ctx, const float* xy /* n x 2 */, int32_t n, float* xy_un /* n x 2 */, int32_t* cell /* n */);
+
+/* The front-end of ONE monocular or RGB-D Frame in one submission: what Frame::Frame (Frame.cc:334-448, :231-331) does with
+ * ExtractORB(0, imGray, lap0, lap1) and ExtractLine(0, imGray) one after the other (:360-361, :258-259), UndistortKeyPoints
+ * (:872-905), UndistortKeyLines (:907-945), ComputeStereoFromRGBD (:1309-1330; depth == NULL: monocular, mvuRight = mvDepth = -1,
+ * :384-385) and the PosInGrid of AssignFeaturesToGrid (:451-482) — image and depth up, the ORB chain beside the line chain, the
+ * lapping reorder (ORBextractor.cc:1135-1144; the monocular constructor passes {0, 1000}, the RGB-D one {0, 0}) and the rest on
+ * the device, one synchronisation.  depth: CV_32F, registered to the image, row stride in floats; it is read at the
+ * DISTORTED keypoint and mvuRight is written from the UNDISTORTED x, with the context's bf.
+ * `record` receives the frame's table record (pli_table_layout, record_bytes) with its eye-0 columns filled: kp[0], desc[0], kl[0],
+ * ldesc[0], uright, depth (every row: -1 from the keypoint count on), the counts and truncation flags; everything else in it is 0.
+ * kp_un: kp_cap x 2 floats (mvKeysUn[i].pt), kl_un: kl_cap x 4 floats (mvKeysUn_Line[i]: startPointX, startPointY, endPointX,
+ * endPointY), cell: kp_cap ints (as pli_undistort_points), rows from the counts on 0 / -1; *n_mono: the extractor's return value
+ * (monoLeft).  The context is left as after pli_orb_extract_lapping(eye 0) plus pli_line_extract(eye 0): pli_last_counts,
+ * pli_orb_pyramid_level, pli_stereo_from_depth work on this Frame; eye 1 counts as not extracted.  The record and the three
+ * columns come back through one pinned buffer.  PLI_ERR_CAPACITY as those two calls. */
+pli_status pli_frame_extract_single(pli_ctx* ctx, const uint8_t* img, int32_t w, int32_t h, int64_t stride,
+                                    int32_t lap0, int32_t lap1, const float* depth, int64_t depth_stride_floats,
+                                    void* record, float* kp_un, float* kl_un, int32_t* cell, int32_t* n_mono);
+
 /* KannalaBrandt8::mvParameters (include/CameraModels/KannalaBrandt8.h): fx, fy, cx, cy, k0..k3. */
 typedef struct pli_kb8_camera { float fx, fy, cx, cy, k0, k1, k2, k3; } pli_kb8_camera;
 

@@ -91,6 +91,12 @@ class FuseCamera(C.Structure):
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class PinholeDistortion(C.Structure):
+    """pli_pinhole_distortion: K and mDistCoef of a pinhole camera; k3 = 0 stands for a 4-coefficient mDistCoef."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float)]
+
+
 class TrackLayout(C.Structure):
     """pli_track_layout."""
     _fields_ = [("record_bytes", C.c_int64), ("off_counts", C.c_int64), ("off_best", C.c_int64), ("off_lines", C.c_int64),
@@ -159,6 +165,10 @@ _PROTOS = {
     "pli_stereo_match_points": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "pli_orb_extract_lapping": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pli_set_pinhole_distortion": (C.c_int32, [C.c_void_p, C.POINTER(PinholeDistortion), C.POINTER(C.c_float)]),
+    "pli_undistort_points": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pli_frame_extract_single": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "pli_stereo_fisheye": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pli_stereo_fisheye_tables": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

@@ -64,8 +64,8 @@ struct pli_ctx {
   hipEvent_t evFork = nullptr, evJoin = nullptr, evLbdPre = nullptr;
   hipStream_t aux2 = nullptr;        // round 1's region2rect pass beside round 2's pass over the owner map (line_chain.hip: tileRect)
   hipEvent_t evRectFork = nullptr, evRectDone = nullptr;
-  std::function<pli_status()> sideChain;     // pli_batch_run -> relaxTile (line_chain.hip): enqueues the side stream's work (see pli_batch_run)
-  bool lbdPreOnSide = false;                 // the LBD's blur + Sobel of this call ran on the side stream (pli_batch_run)
+  std::function<pli_status()> sideChain;     // runChainsBeside (pli_capi.hip) -> relaxTile (line_chain.hip): enqueues the side stream's work
+  bool lbdPreOnSide = false;                 // the LBD's blur + Sobel of this call ran on the side stream (runChainsBeside)
   bool syncDebug = getenv("PLI_SYNC_DEBUG") != nullptr;
   int NI = 0;
   pli_table_layout lay;
@@ -153,11 +153,14 @@ struct pli_ctx {
   bool pointsFresh = false;                  // ... and its mvuRight / mvDepth were computed with the CURRENT rig (pli_set_stereo_camera
                                              // clears it: the point matcher then re-runs on the resident tables)
   uint8_t* recPinned = nullptr;              // pinned staging of that record
+  size_t recPinnedBytes = 0;                 // ... where pli_frame_extract_single sized it: the record and the caller's columns behind it
   uint8_t* pyrHost[2] = {nullptr, nullptr};  // pinned copy of an eye's pyramid block (pli_orb_pyramid_level)
   bool pyrHostValid[2] = {false, false};     // ... is the one of the last extraction on that eye
   int orbCount[2] = {0, 0};                  // keypoints the last pli_orb_extract(_lapping) left in each eye's table
   int lineCount[2] = {0, 0};                 // keylines the last pli_line_extract left in each eye's table
   int monoCount[2] = {0, 0};                 // pli_orb_extract_lapping: first lapping-area keypoint of each eye's table
+  PinholeUndist pinhole{};                   // pli_set_pinhole_distortion: the camera of the single-camera Frames and its image bounds
+                                             // (no camera, or k1 == 0: on = 0 and the bounds {0, W, 0, H}; pli_ctx_create sets that)
   // pipelined host entry point: two slots of device staging (images + table), H2D and D2H copy streams
   struct HostSlot { uint8_t* dimg = nullptr; uint8_t* dtab = nullptr; size_t imgBytes = 0, tabBytes = 0;
                     hipEvent_t h2d = nullptr, kern = nullptr, d2h = nullptr; bool busy = false; };

@@ -1,4 +1,4 @@
-// Kernel prototypes (definitions in orb_kernels.hip, line_kernels.hip, match_kernels.hip, kfdb_kernels.hip, mapfeat_kernels.hip).
+// Kernel prototypes (definitions in orb_kernels.hip, line_kernels.hip, match_kernels.hip, kfdb_kernels.hip, mapfeat_kernels.hip, frame_kernels.hip).
 // Started from tools/gen_kernel_protos.py; kept by hand since (the octree instances come from a macro the script does not see; the
 // script writes a templated kernel's prototype as the ones below are written).
 #pragma once
@@ -167,6 +167,15 @@ __global__ void k_proj2_candidates(const pli_proj_query* __restrict__ q, const u
 __global__ void k_proj2_assign(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq, const pli_keypoint* __restrict__ kpL, const uint8_t* __restrict__ descL, const uint8_t* __restrict__ occL, int nL, const pli_keypoint* __restrict__ kpR, const uint8_t* __restrict__ descR, const uint8_t* __restrict__ occR, int nR, const float* __restrict__ noUright, float minX, float maxX, float minY, float maxY, int checkOri, const unsigned long long* __restrict__ candKeys, const int* __restrict__ candCount, const int* __restrict__ leftOpen, int* __restrict__ rawIdx2, int* __restrict__ hist, int* __restrict__ accepts);
 __global__ void k_proj2_finish(const pli_proj_query* __restrict__ q, int nq, const pli_keypoint* __restrict__ kpL, const pli_keypoint* __restrict__ kpR, int checkOri, const int* __restrict__ rawIdx2, const int* __restrict__ hist, const int* __restrict__ accepts, int* __restrict__ bestIdx2, int* __restrict__ nmatchesOut);
 __global__ void k_lapping_order(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc, int n, float lap0, float lap1, pli_keypoint* __restrict__ dstKp, uint8_t* __restrict__ dstDesc, int* __restrict__ monoCount);
+__global__ void k_lapping_order_counted(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc, const int* __restrict__ count, int cap, float lap0, float lap1, pli_keypoint* __restrict__ dstKp, uint8_t* __restrict__ dstDesc, int* __restrict__ monoCount);
+// single-camera Frames of a distorted pinhole camera (frame_kernels.hip): the context's camera and its image bounds, by value
+struct PinholeUndist {
+  pli_pinhole_distortion cam;
+  int on;                             // a camera is set and its k1 != 0 (the reference's gate); 0: every "undistorted" output is a copy
+  float minX, maxX, minY, maxY;       // mnMinX .. mnMaxY (ComputeImageBounds)
+};
+__global__ void k_undistort_points(PinholeUndist C, const float2* __restrict__ xy, int n, float2* __restrict__ xyUn, int* __restrict__ cell);
+__global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUndist C, const float* __restrict__ depthImg, int64_t pitch, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offKl0, int64_t offUr, int64_t offDepth, float2* __restrict__ kpUn, int* __restrict__ cell, float4* __restrict__ klUn);
 
 __global__ void k_tx_tail(TxTailArgs T);
 __global__ void k_tx_rec_from_hot(const RxCtl* __restrict__ ctl, const int2* __restrict__ hotAll, const float2* __restrict__ coldAll, float4* __restrict__ recAll, int64_t npix, int img0);

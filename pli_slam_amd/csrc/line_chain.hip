@@ -541,7 +541,7 @@ pli_status tileRectPass(pli_ctx* c, const LineCall& L, const RelaxPlan& R, const
   return PLI_OK;
 }
 
-// the ORB chain forks from the line chain behind `step` (pli_batch_run handed it over): the growth of round `step`, or round 2's owner pass (-2)
+// the ORB chain forks from the line chain behind `step` (runChainsBeside, pli_capi.hip, handed it over): the growth of round `step`, or round 2's owner pass (-2)
 pli_status forkSideChainBehind(pli_ctx* c, const TileRounds& S, int step) {
   if (!c->sideChain || step != S.sideForkRound) return PLI_OK;
   auto f = std::move(c->sideChain);
@@ -715,7 +715,7 @@ pli_status relaxTile(pli_ctx* c, const LineCall& L, RelaxPlan& R) {
                     c->tileAct, c->tileTouch, P.LW, P.LH, c->tilesW, c->tilesH, c->arena, c->arenaCap, c->rects, c->rectCap, c->rgSeg,
                     c->mg, c->rankOf, L.lostRule ? c->rgLost : (int*)nullptr, DL, img0, nimg, L.hotLater, coldPlane};
   TxRound first = txr; first.hot = hotPlane;
-  // Where the deferred ORB chain forks from the line chain (pli_batch_run): behind round 1's growth up to 64 images, behind round 2's
+  // Where the deferred ORB chain forks from the line chain (runChainsBeside, pli_capi.hip): behind round 1's growth up to 64 images, behind round 2's
   // pass over the owner map (-2) above — what waits in a large batch is the END of the line chain (the 1024-thread / 64 KB workgroups
   // of k_tx_emit_sorted, the gated k_lsd_scan, k_keylines find no room while the ORB chain fills every hole), so the chain should end
   // early, and k_tx_round2, which the ORB kernels stretch most, should run alone.  Same box, 256 frames, fork behind round 1 /
@@ -831,7 +831,7 @@ pli_status lineDescribe(pli_ctx* c, const LineCall& L, uint8_t* table) {
   LAUNCH(c, "k_keylines", k_keylines, dim3(nimg), dim3(256), 0, c->dP, c->seg, c->nSeg, c->maxSeg, c->tmpKL, table,
          Y.record_bytes, Y.off_counts, Y.off_kl[0], Y.off_kl[1], img0);
   if (c->lbdPreOnSide) {
-    HIPCHK(hipStreamWaitEvent(c->stream, c->evLbdPre, 0));   // (the blur + Sobel of the LBD ran on the side stream, see pli_batch_run)
+    HIPCHK(hipStreamWaitEvent(c->stream, c->evLbdPre, 0));   // (the blur + Sobel of the LBD ran on the side stream, see runChainsBeside in pli_capi.hip)
   } else {
     pli_status ls = runLbdPre(c, img0, nimg);
     if (ls != PLI_OK) return ls;

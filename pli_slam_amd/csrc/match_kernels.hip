@@ -3085,9 +3085,9 @@ __global__ void k_fill_f32(float* __restrict__ dst, int n, float v) {
 // with lap0 <= x <= lap1 (level-0 coordinates) fill the table from the back in visiting order, the others from the front.
 // One workgroup per image: ordered counts by block scans over chunks of 1024 keypoints; src = snapshot of the table.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_lapping_order(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc,
-                                                        int n, float lap0, float lap1, pli_keypoint* __restrict__ dstKp,
-                                                        uint8_t* __restrict__ dstDesc, int* __restrict__ monoCount) {
+__device__ __forceinline__ void lapping_order(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc,
+                                              int n, float lap0, float lap1, pli_keypoint* __restrict__ dstKp,
+                                              uint8_t* __restrict__ dstDesc, int* __restrict__ monoCount) {
   __shared__ int waveCnt[16];
   __shared__ int base;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -3116,6 +3116,21 @@ __global__ __launch_bounds__(1024) void k_lapping_order(const pli_keypoint* __re
     __syncthreads();
   }
   if (tid == 0) *monoCount = base;
+}
+
+__global__ __launch_bounds__(1024) void k_lapping_order(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc,
+                                                        int n, float lap0, float lap1, pli_keypoint* __restrict__ dstKp,
+                                                        uint8_t* __restrict__ dstDesc, int* __restrict__ monoCount) {
+  lapping_order(srcKp, srcDesc, n, lap0, lap1, dstKp, dstDesc, monoCount);
+}
+
+// ... with the keypoint count read on the device (pli_frame_extract_single: no host look between the extraction and the reorder):
+// *count, at most cap, rows of the snapshot.
+__global__ __launch_bounds__(1024) void k_lapping_order_counted(const pli_keypoint* __restrict__ srcKp, const uint8_t* __restrict__ srcDesc,
+                                                                const int* __restrict__ count, int cap, float lap0, float lap1,
+                                                                pli_keypoint* __restrict__ dstKp, uint8_t* __restrict__ dstDesc,
+                                                                int* __restrict__ monoCount) {
+  lapping_order(srcKp, srcDesc, min(*count, cap), lap0, lap1, dstKp, dstDesc, monoCount);
 }
 
 }  // namespace pli

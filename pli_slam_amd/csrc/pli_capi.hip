@@ -673,6 +673,72 @@ pli_status runStereoLines(pli_ctx* c, int nframes, uint8_t* table) {
   return PLI_OK;
 }
 
+// The ORB chain runs beside the line chain (fork after the ingest, join before whatever reads both chains' tables) except under the
+// sequential grower above 2560 images.  Measured, 752x480, frames/s without -> with: tile relaxation 32 frames 2688 -> 2847,
+// 128 frames 3711 -> 3947, 256 frames 4054 -> 4245, 512 frames 4268 -> 4379, 768 frames 4303 -> 4420; sequential grower
+// 1024 frames 4213 -> 4544, 1280 frames 4830 -> 5266; from 1536 frames on the grower's blocks fill the CUs' LDS, the ORB
+// kernels wait for it and stretch the grower: 5170 -> 4287, 2048 frames 6067 -> 4942.
+bool chainsRunBeside(const pli_ctx* c, int nimg) {
+  static const int sideMax = DEVENV("PLI_SIDE_MAX") ? atoi(DEVENV("PLI_SIDE_MAX")) : INT_MAX;    // (dev: images below which the tile relaxation has the ORB chain beside it)
+  return (sequentialGrower(c, nimg) ? nimg <= 2560 : nimg < sideMax) && !c->syncDebug;
+}
+
+// Both chains of images img0 .. img0 + nimg - 1 (ingested already) into `table`, the ORB chain on the side stream, and the join: on
+// return the context's stream has waited for the side stream.  pointFrames > 0: the stereo point matcher of that many frames behind
+// the ORB chain.  One function for pli_batch_run and pli_frame_extract_single; the caller has asked chainsRunBeside.
+pli_status runChainsBeside(pli_ctx* c, int img0, int nimg, uint8_t* T, int pointFrames) {
+  pli_status st;
+  const bool seqGrower = sequentialGrower(c, nimg);
+  if (!c->aux) {
+    // (the line chain is the longer one: the ORB chain beside it takes what the line kernels leave free)
+    int prLow = 0, prHigh = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
+    HIPCHK(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prLow));
+    HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->evLbdPre, hipEventDisableTiming));
+  }
+  hipStream_t main = c->stream;
+  c->lbdPreOnSide = c->lsdF64;
+  // the side chain: forks from the line chain where it is enqueued.  Under the tile relaxation that is right after the
+  // launch of round 1 (relaxTile, line_chain.hip, calls it): round 1 keeps the chip to itself, and the later rounds, which leave most of it
+  // idle, host the ORB kernels; otherwise before the line chain starts.
+  auto sideChain = [c, img0, nimg, pointFrames, T, main]() -> pli_status {
+    HIPCHK(hipEventRecord(c->evFork, main));
+    HIPCHK(hipStreamWaitEvent(c->aux, c->evFork, 0));
+    {
+      StreamScope onSide(c, c->aux);
+      pli_status s2 = runOrb(c, img0, nimg, T);
+      if (s2 != PLI_OK) return s2;
+      // (the stereo point matcher needs the ORB tables only: it stays on the side stream, off the line chain's path)
+      if (pointFrames > 0 && (s2 = runStereoPoints(c, pointFrames, T)) != PLI_OK) return s2;
+      if (c->lbdPreOnSide) {
+        if ((s2 = runLbdPre(c, img0, nimg)) != PLI_OK) return s2;
+        HIPCHK(hipEventRecord(c->evLbdPre, c->aux));
+      }
+    }
+    HIPCHK(hipEventRecord(c->evJoin, c->aux));
+    return PLI_OK;
+  };
+  // (measured: +1.3 % at 32 frames, +1.4 % on the 4K configuration (16 frames), +1 % on a single pair; neutral at 64 and 128
+  // frames, -0.5 % at 256, -3 % on the 720p configuration with its 2000 keypoints: up to 64 images it is)
+  // Round 5, with round 1 a tenth shorter when it has the chip to itself: 256 frames of 752 x 480 +1.9 % (47.4 -> 46.6 ms), 128 frames +2 %,
+  // 512 frames +0.3 %, 1024 frames -0.4 %; 64 frames of 1280 x 720 (2000 keypoints: a longer ORB chain) still -1.3 %.  So: up to 64
+  // images always, up to 1024 images of EuRoC-sized frames (< 0.5 M pixels).  Behind a LATER round (PLI_SIDE_FORK_ROUND = 3 / 4 / 5 / 7)
+  // it is 47.4 / 47.5 / 47.9 / 48.4 ms on the synthetic stream; which round it forks behind: relaxTile (sideForkRound).
+  const int sideDeferMax = DEVENV("PLI_SIDE_DEFER_MAX") ? atoi(DEVENV("PLI_SIDE_DEFER_MAX")) : -1;   // (dev: images up to which the ORB chain starts behind round 1)
+  const bool deferSide = sideDeferMax >= 0 ? nimg <= sideDeferMax : (nimg <= 64 || (nimg <= 1024 && (int64_t)c->hp.W * c->hp.H < 500000));
+  if (!seqGrower && c->lsdMode != 1 && deferSide) c->sideChain = sideChain;
+  else if ((st = sideChain()) != PLI_OK) { c->lbdPreOnSide = false; return st; }
+  st = runLines(c, img0, nimg, T);
+  if (st == PLI_OK && c->sideChain) { auto f = std::move(c->sideChain); c->sideChain = nullptr; st = f(); }   // (not taken by runLines)
+  c->sideChain = nullptr;
+  c->lbdPreOnSide = false;
+  if (st != PLI_OK) return st;
+  HIPCHK(hipStreamWaitEvent(main, c->evJoin, 0));
+  return PLI_OK;
+}
+
 // The counts block of a record (include/pli_frontend.h: pli_table_layout.off_counts), as the kernels write it.
 struct RecordCounts {
   int32_t kp[2], kl[2];                   // keypoints / keylines of eye 0, 1
@@ -772,6 +838,7 @@ pli_status pli_ctx_create(const pli_frontend_config* cfg, int32_t device, pli_ct
   c->cfg = *cfg;
   c->device = device;
   c->NI = 2 * cfg->max_frames;
+  c->pinhole.maxX = (float)cfg->width; c->pinhole.maxY = (float)cfg->height;     // no camera yet: the grid spans the image (pli_set_pinhole_distortion)
   st = buildGeometry(c.get());
   if (st != PLI_OK) return st;
   buildLayout(c.get());
@@ -872,62 +939,9 @@ pli_status pli_batch_run(pli_ctx* c, int32_t nframes, const uint8_t* dl, const u
   for (int e = 0; e < 2; ++e) { c->orbDone[e] = c->lineDone[e] = false; c->pyrHostValid[e] = false; }
   if ((st = runIngest(c, dl, dr, stride, frameStride, 0, nimg)) != PLI_OK) return st;
   bool stereoPointsDone = false;
-  // The ORB chain runs beside the line chain (fork after the ingest, join before the stereo matchers) except under the
-  // sequential grower above 2560 images.  Measured, 752x480, frames/s without -> with: tile relaxation 32 frames 2688 -> 2847,
-  // 128 frames 3711 -> 3947, 256 frames 4054 -> 4245, 512 frames 4268 -> 4379, 768 frames 4303 -> 4420; sequential grower
-  // 1024 frames 4213 -> 4544, 1280 frames 4830 -> 5266; from 1536 frames on the grower's blocks fill the CUs' LDS, the ORB
-  // kernels wait for it and stretch the grower: 5170 -> 4287, 2048 frames 6067 -> 4942.
-  static const int sideMax = DEVENV("PLI_SIDE_MAX") ? atoi(DEVENV("PLI_SIDE_MAX")) : INT_MAX;    // (dev: images below which the tile relaxation has the ORB chain beside it)
-  const bool seqGrower = sequentialGrower(c, nimg);
-  if ((seqGrower ? nimg <= 2560 : nimg < sideMax) && (stages & PLI_RUN_ORB) && (stages & PLI_RUN_LINES) && !c->syncDebug) {
-    if (!c->aux) {
-      // (the line chain is the longer one: the ORB chain beside it takes what the line kernels leave free)
-      int prLow = 0, prHigh = 0;
-      HIPCHK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-      HIPCHK(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prLow));
-      HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->evLbdPre, hipEventDisableTiming));
-    }
-    hipStream_t main = c->stream;
+  if ((stages & PLI_RUN_ORB) && (stages & PLI_RUN_LINES) && chainsRunBeside(c, nimg)) {
     stereoPointsDone = (stages & PLI_RUN_STEREO_POINTS) != 0;
-    c->lbdPreOnSide = c->lsdF64;
-    // the side chain: forks from the line chain where it is enqueued.  Under the tile relaxation that is right after the
-    // launch of round 1 (relaxTile, line_chain.hip, calls it): round 1 keeps the chip to itself, and the later rounds, which leave most of it
-    // idle, host the ORB kernels; otherwise before the line chain starts.
-    auto sideChain = [c, nimg, nframes, T, stages, main]() -> pli_status {
-      HIPCHK(hipEventRecord(c->evFork, main));
-      HIPCHK(hipStreamWaitEvent(c->aux, c->evFork, 0));
-      {
-        StreamScope onSide(c, c->aux);
-        pli_status s2 = runOrb(c, 0, nimg, T);
-        if (s2 != PLI_OK) return s2;
-        // (the stereo point matcher needs the ORB tables only: it stays on the side stream, off the line chain's path)
-        if ((stages & PLI_RUN_STEREO_POINTS) && (s2 = runStereoPoints(c, nframes, T)) != PLI_OK) return s2;
-        if (c->lbdPreOnSide) {
-          if ((s2 = runLbdPre(c, 0, nimg)) != PLI_OK) return s2;
-          HIPCHK(hipEventRecord(c->evLbdPre, c->aux));
-        }
-      }
-      HIPCHK(hipEventRecord(c->evJoin, c->aux));
-      return PLI_OK;
-    };
-    // (measured: +1.3 % at 32 frames, +1.4 % on the 4K configuration (16 frames), +1 % on a single pair; neutral at 64 and 128
-    // frames, -0.5 % at 256, -3 % on the 720p configuration with its 2000 keypoints: up to 64 images it is)
-    // Round 5, with round 1 a tenth shorter when it has the chip to itself: 256 frames of 752 x 480 +1.9 % (47.4 -> 46.6 ms), 128 frames +2 %,
-    // 512 frames +0.3 %, 1024 frames -0.4 %; 64 frames of 1280 x 720 (2000 keypoints: a longer ORB chain) still -1.3 %.  So: up to 64
-    // images always, up to 1024 images of EuRoC-sized frames (< 0.5 M pixels).  Behind a LATER round (PLI_SIDE_FORK_ROUND = 3 / 4 / 5 / 7)
-    // it is 47.4 / 47.5 / 47.9 / 48.4 ms on the synthetic stream; which round it forks behind: relaxTile (sideForkRound).
-    const int sideDeferMax = DEVENV("PLI_SIDE_DEFER_MAX") ? atoi(DEVENV("PLI_SIDE_DEFER_MAX")) : -1;   // (dev: images up to which the ORB chain starts behind round 1)
-    const bool deferSide = sideDeferMax >= 0 ? nimg <= sideDeferMax : (nimg <= 64 || (nimg <= 1024 && (int64_t)c->hp.W * c->hp.H < 500000));
-    if (!seqGrower && c->lsdMode != 1 && deferSide) c->sideChain = sideChain;
-    else if ((st = sideChain()) != PLI_OK) { c->lbdPreOnSide = false; return st; }
-    st = runLines(c, 0, nimg, T);
-    if (st == PLI_OK && c->sideChain) { auto f = std::move(c->sideChain); c->sideChain = nullptr; st = f(); }   // (not taken by runLines)
-    c->sideChain = nullptr;
-    c->lbdPreOnSide = false;
-    if (st != PLI_OK) return st;
-    HIPCHK(hipStreamWaitEvent(main, c->evJoin, 0));
+    if ((st = runChainsBeside(c, 0, nimg, T, stereoPointsDone ? nframes : 0)) != PLI_OK) return st;
   } else {
     if (stages & PLI_RUN_ORB) if ((st = runOrb(c, 0, nimg, T)) != PLI_OK) return st;
     if (stages & PLI_RUN_LINES) if ((st = runLines(c, 0, nimg, T)) != PLI_OK) return st;
@@ -1446,6 +1460,147 @@ pli_status pli_orb_extract_lapping(pli_ctx* c, int32_t eye, const uint8_t* img, 
   if (desc) HIPCHK(hipMemcpyAsync(desc, td, (size_t)N * 32, hipMemcpyDeviceToHost, c->stream));
   if ((st = fetchCount(c, dmono, n_mono)) != PLI_OK) return st;
   c->monoCount[eye] = *n_mono;
+  return PLI_OK;
+}
+
+// ---- single-camera Frames of a distorted pinhole camera (frame_kernels.hip) ----
+// the state without a camera: nothing is undistorted and the grid spans the image (Frame.cc:967-973)
+static void clearPinhole(pli_ctx* c) {
+  c->pinhole = PinholeUndist{};
+  c->pinhole.maxX = (float)c->cfg.width;
+  c->pinhole.maxY = (float)c->cfg.height;
+}
+
+// Frame::ComputeImageBounds (Frame.cc:947-974) and the camera of the two calls below
+pli_status pli_set_pinhole_distortion(pli_ctx* c, const pli_pinhole_distortion* cam, float bounds[4]) {
+  CtxGuard guard__(c);
+  if (!c) { g_err = "null argument"; return PLI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(c->device));
+  clearPinhole(c);
+  if (cam && cam->k1 != 0.0f) {                    // (:949 `mDistCoef.at<float>(0)!=0.0`)
+    PinholeUndist U = c->pinhole;
+    U.cam = *cam;
+    U.on = 1;
+    const float W = (float)c->cfg.width, H = (float)c->cfg.height;
+    const float2 corners[4] = {{0.f, 0.f}, {W, 0.f}, {0.f, H}, {W, H}};       // (:952-955)
+    float2 m[4];
+    ScratchPlan plan;
+    auto din = plan.in(corners, 4);
+    auto dout = plan.add<float2>(4);
+    pli_status st = commitScratch(c, plan);
+    if (st != PLI_OK) return st;
+    LAUNCH(c, "k_undistort_points", k_undistort_points, dim3(1), dim3(64), 0, U, (const float2*)din, 4, (float2*)dout, (int*)nullptr);
+    HIPCHK(download(c, m, dout));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    U.minX = std::min(m[0].x, m[2].x);             // (:962-965)
+    U.maxX = std::max(m[1].x, m[3].x);
+    U.minY = std::min(m[0].y, m[1].y);
+    U.maxY = std::max(m[2].y, m[3].y);
+    c->pinhole = U;
+  } else if (cam) {
+    c->pinhole.cam = *cam;                         // (kept for the record; with k1 == 0 nothing reads it)
+  }
+  if (bounds) { bounds[0] = c->pinhole.minX; bounds[1] = c->pinhole.maxX; bounds[2] = c->pinhole.minY; bounds[3] = c->pinhole.maxY; }
+  return PLI_OK;
+}
+
+// cv::undistortPoints of Frame::UndistortKeyPoints / UndistortKeyLines (Frame.cc:891, :931-932) and Frame::PosInGrid (:845-855) on
+// caller tables
+pli_status pli_undistort_points(pli_ctx* c, const float* xy, int32_t n, float* xyUn, int32_t* cell) {
+  CtxGuard guard__(c);
+  if (!c || n < 0 || (n > 0 && (!xy || !xyUn))) { g_err = "bad argument"; return PLI_ERR_INVALID; }
+  if (n == 0) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  ScratchPlan plan;
+  auto din = plan.in(reinterpret_cast<const float2*>(xy), (size_t)n);
+  auto dout = plan.add<float2>((size_t)n);
+  auto dcell = plan.addIf<int>(cell != nullptr, (size_t)n);
+  pli_status st = commitScratch(c, plan);
+  if (st != PLI_OK) return st;
+  LAUNCH(c, "k_undistort_points", k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, c->pinhole, (const float2*)din, (int)n,
+         (float2*)dout, (int*)dcell);
+  HIPCHK(download(c, reinterpret_cast<float2*>(xyUn), dout));
+  HIPCHK(download(c, (int*)cell, dcell));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PLI_OK;
+}
+
+// The monocular (Frame.cc:334-448) and RGB-D (:231-331) constructors' front-end in one submission: see include/pli_frontend.h.
+pli_status pli_frame_extract_single(pli_ctx* c, const uint8_t* img, int32_t w, int32_t h, int64_t stride, int32_t lap0, int32_t lap1,
+                                    const float* depth, int64_t depthStrideFloats, void* record, float* kpUn, float* klUn,
+                                    int32_t* cell, int32_t* n_mono) {
+  CtxGuard guard__(c);
+  TraceRange range__("pli_frame_extract_single");
+  if (!c || !record || !kpUn || !klUn || !cell || !n_mono) { g_err = "null argument"; return PLI_ERR_INVALID; }
+  *n_mono = 0;
+  pli_status st = checkImage(c, img, w, h, stride);
+  if (st != PLI_OK) return st;
+  if (depth && depthStrideFloats < w) { g_err = "depth stride < width"; return PLI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(c->device));
+  const int W = c->cfg.width, H = c->cfg.height;
+  const pli_table_layout& Y = c->lay;
+  const DevParams& P = c->hp;
+  // what the call stages and what it reads back: the depth image; the snapshot of the eye's table that the lapping reorder reads; the
+  // caller's three columns and the mono count, contiguous behind each other so that one copy brings them to the pinned buffer
+  const size_t kpUnBytes = (size_t)P.kpCap * sizeof(float2), klUnBytes = (size_t)P.klCap * sizeof(float4), cellBytes = (size_t)P.kpCap * 4;
+  const size_t offKl = alignUp(kpUnBytes, 16), offCell = offKl + klUnBytes, offMono = offCell + cellBytes, outBytes = offMono + 4;
+  ScratchPlan plan;
+  auto ddepth = plan.addIf<float>(depth != nullptr, (size_t)W * H);
+  auto sk = plan.add<pli_keypoint>((size_t)P.kpCap);
+  auto sd = plan.add<uint8_t>((size_t)P.kpCap * 32);
+  auto dout = plan.add<uint8_t>(outBytes);
+  if ((st = commitScratch(c, plan)) != PLI_OK) return st;
+  const size_t recBytes = (size_t)Y.record_bytes, pinnedNeed = alignUp((int64_t)recBytes, 16) + outBytes;
+  if (!c->recPinned || c->recPinnedBytes < pinnedNeed) {
+    if (c->recPinned) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipHostFree(c->recPinned)); c->recPinned = nullptr; }
+    HIPCHK(hipHostMalloc((void**)&c->recPinned, pinnedNeed, hipHostMallocDefault));
+    c->recPinnedBytes = pinnedNeed;
+  }
+  // the record starts from zeros, as pli_frame_extract's does: what it returns does not depend on an earlier Frame, and what the
+  // per-call entry points cached about eye 1 ends here (a single-camera Frame has no right eye)
+  c->frameFresh = c->pointsFresh = false;
+  for (int e = 0; e < 2; ++e) { c->orbDone[e] = c->lineDone[e] = false; c->pyrHostValid[e] = false; }
+  HIPCHK(hipMemsetAsync(c->ownTable, 0, recBytes, c->stream));
+  HIPCHK(hipMemcpy2DAsync(c->inStage[0], W, img, stride, W, H, hipMemcpyHostToDevice, c->stream));
+  if (depth)
+    HIPCHK(hipMemcpy2DAsync(ddepth, (size_t)W * 4, depth, (size_t)depthStrideFloats * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, c->stream));
+  if ((st = runIngest(c, c->inStage[0], c->inStage[1], W, 0, 0, 1)) != PLI_OK) return st;
+  if (chainsRunBeside(c, 1)) {
+    if ((st = runChainsBeside(c, 0, 1, c->ownTable, 0)) != PLI_OK) return st;
+  } else {
+    if ((st = runOrb(c, 0, 1, c->ownTable)) != PLI_OK) return st;
+    if ((st = runLines(c, 0, 1, c->ownTable)) != PLI_OK) return st;
+  }
+  // the lapping reorder (ORBextractor.cc:1135-1144) with the count read on the device; {0, 0} and every other area still go through
+  // it, as pli_orb_extract_lapping does: the order and the mono count are the kernel's
+  pli_keypoint* tk = (pli_keypoint*)(c->ownTable + Y.off_kp[0]);
+  uint8_t* td = c->ownTable + Y.off_desc[0];
+  int* dmono = reinterpret_cast<int*>((uint8_t*)dout + offMono);
+  HIPCHK(hipMemcpyAsync(sk, tk, (size_t)P.kpCap * sizeof(pli_keypoint), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(sd, td, (size_t)P.kpCap * 32, hipMemcpyDeviceToDevice, c->stream));
+  LAUNCH(c, "k_lapping_order", k_lapping_order_counted, dim3(1), dim3(1024), 0, (const pli_keypoint*)sk, (const uint8_t*)sd,
+         reinterpret_cast<const int*>(c->ownTable + Y.off_counts), P.kpCap, (float)lap0, (float)lap1, tk, td, dmono);
+  LAUNCH(c, "k_frame_single_tail", k_frame_single_tail, dim3((P.kpCap + P.klCap + 255) / 256), dim3(256), 0, c->dP, c->pinhole,
+         (const float*)ddepth, (int64_t)W, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_kl[0], Y.off_uright, Y.off_depth,
+         reinterpret_cast<float2*>((uint8_t*)dout), reinterpret_cast<int*>((uint8_t*)dout + offCell),
+         reinterpret_cast<float4*>((uint8_t*)dout + offKl));
+  uint8_t* pinOut = c->recPinned + alignUp((int64_t)recBytes, 16);
+  HIPCHK(hipMemcpyAsync(c->recPinned, c->ownTable, recBytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(pinOut, (uint8_t*)dout, outBytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::memcpy(record, c->recPinned, recBytes);
+  std::memcpy(kpUn, pinOut, kpUnBytes);
+  std::memcpy(klUn, pinOut + offKl, klUnBytes);
+  std::memcpy(cell, pinOut + offCell, cellBytes);
+  std::memcpy(n_mono, pinOut + offMono, 4);
+  RecordCounts rc;
+  std::memcpy(&rc, c->recPinned + Y.off_counts, sizeof(rc));
+  c->orbDone[0] = c->lineDone[0] = true;
+  c->orbCount[0] = rc.kp[0];
+  c->lineCount[0] = rc.kl[0];
+  c->monoCount[0] = *n_mono;
+  if (rc.kpCut[0]) { g_err = "more keypoints than kp_cap holds"; return PLI_ERR_CAPACITY; }
+  if (rc.linesCut[0]) { g_err = "more segments pass the length cut than max_lines holds: raise pli_frontend_config.max_lines"; return PLI_ERR_CAPACITY; }
   return PLI_OK;
 }
 

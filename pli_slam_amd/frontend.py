@@ -703,6 +703,59 @@ class Frontend:
         check(self.L.pli_stereo_from_depth(self.h, ptr(d), stride, ptr(ur), ptr(dp), self.kp_cap))
         return ur, dp
 
+    def set_pinhole_distortion(self, cam):
+        """The pinhole camera of the single-camera Frames (pli_set_pinhole_distortion): cam = capi.PinholeDistortion or its values
+        (fx, fy, cx, cy, k1, k2, p1, p2[, k3]); None removes it.  Returns Frame::ComputeImageBounds (Frame.cc:947-974) as float32
+        (mnMinX, mnMaxX, mnMinY, mnMaxY).  With k1 == 0, or without a camera, nothing is undistorted and the bounds are the image's."""
+        bounds = (C.c_float * 4)()
+        if cam is None:
+            check(self.L.pli_set_pinhole_distortion(self.h, None, bounds))
+        else:
+            if not isinstance(cam, capi.PinholeDistortion):
+                v = [float(x) for x in cam]
+                if len(v) not in (8, 9):
+                    raise ValueError("cam: fx, fy, cx, cy, k1, k2, p1, p2 and optionally k3")
+                cam = capi.PinholeDistortion(*(v + [0.0] * (9 - len(v))))
+            check(self.L.pli_set_pinhole_distortion(self.h, C.byref(cam), bounds))
+        return np.array(bounds, np.float32)
+
+    def undistort_points(self, xy, with_cell=True):
+        """cv::undistortPoints(mat, mat, K, mDistCoef, cv::Mat(), K) of Frame::UndistortKeyPoints / UndistortKeyLines (Frame.cc:891,
+        :931-932) with the context's camera, on caller points xy (n x 2).  Returns (xy_un float32 [n, 2], cell int32 [n] or None):
+        cell = Frame::PosInGrid (:845-855) of each result against the context's bounds, posX * 48 + posY, -1 where it is false."""
+        p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = len(p)
+        out = np.zeros((n, 2), np.float32)
+        cell = np.zeros(n, np.int32) if with_cell else None
+        check(self.L.pli_undistort_points(self.h, ptr(p), n, ptr(out), ptr(cell)))
+        return out, cell
+
+    def frame_extract_single(self, image, lapping, depth=None):
+        """pli_frame_extract_single: the front-end of one monocular (depth=None, Frame.cc:334-448) or RGB-D (:231-331) Frame in one
+        submission.  lapping: the area ExtractORB passes ((0, 1000) monocular, (0, 0) RGB-D); depth: float image, (height, stride)
+        with stride >= width.  Returns the parsed record (its eye-0 columns: kpL, descL, klL, ldescL, uright, depth, counts) plus
+        kp_un [n, 2] (mvKeysUn[i].pt), kl_un [m, 4] (mvKeysUn_Line[i]: start, end), cell [n] (as undistort_points) and n_mono (the
+        extractor's return value); "full" holds the call's buffers as written, every row.  Leaves the per-call state of eye 0 behind (pyramid_level, stereo_from_depth)."""
+        image = _u8(image)
+        d, stride = None, 0
+        if depth is not None:
+            d = np.ascontiguousarray(depth, np.float32)
+            assert d.ndim == 2 and d.shape[0] == self.cfg.height and d.shape[1] >= self.cfg.width
+            stride = d.shape[1]
+        rec = np.zeros(int(self.layout.record_bytes), np.uint8)
+        kp_un = np.zeros((self.kp_cap, 2), np.float32)
+        kl_un = np.zeros((self.kl_cap, 4), np.float32)
+        cell = np.zeros(self.kp_cap, np.int32)
+        mono = C.c_int32()
+        check(self.L.pli_frame_extract_single(self.h, ptr(image), image.shape[1], image.shape[0], image.strides[0], int(lapping[0]),
+                                              int(lapping[1]), ptr(d), stride, ptr(rec), ptr(kp_un), ptr(kl_un), ptr(cell),
+                                              C.byref(mono)))
+        out = self.parse_record(rec, 0)
+        n, m = len(out["kpL"]), len(out["klL"])
+        out.update(kp_un=kp_un[:n].copy(), kl_un=kl_un[:m].copy(), cell=cell[:n].copy(), n_mono=mono.value,
+                   full={"kp_un": kp_un, "kl_un": kl_un, "cell": cell, "record": rec})
+        return out
+
     def set_rectify_maps(self, eye, mapx, mapy):
         """cv::remap(im, imRect, M1, M2, INTER_LINEAR) of the stereo driver (stereo_euroc.cc:166) fused into the ingest;
         (None, None) removes the maps."""
