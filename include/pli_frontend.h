@@ -466,11 +466,40 @@ pli_status pli_batch_track(pli_ctx* ctx, int32_t nframes, const void* dev_table,
  * NULL, NULL removes the maps of that eye. */
 pli_status pli_set_rectify_maps(pli_ctx* ctx, int32_t eye, const float* mapx, const float* mapy);
 
+/* --- the head of Tracking::GrabImageStereo / GrabImageRGBD / GrabImageMonocular fused into the ingest ---
+ * Replaces cvtColor(mImGray, mImGray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) of Tracking.cc:889-914 (both eyes,
+ * the branch chosen by the left image), :964-977 and :1014-1027.  Afterwards every entry point that takes images —
+ * pli_orb_extract, pli_orb_extract_lapping, pli_line_extract, pli_frame_extract, pli_frame_extract_single, pli_batch_run,
+ * pli_batch_run_host, pli_batch_submit_host — reads them as interleaved 8-bit pixels of that format, 3 or 4 bytes each: w and h
+ * stay in pixels, stride and frame_stride in bytes, a stride below w * channels is PLI_ERR_INVALID.  Level 0 of the pyramid
+ * (pli_orb_pyramid_level) is the gray image and everything behind it is as before.  The gray value is OpenCV 3.3.1's C++ path
+ * RGB2Gray<uchar>: (R*4899 + G*9617 + B*1868 + 8192) >> 14, alpha ignored (parity with a real OpenCV, whose IPP builds may differ,
+ * is unpinned).  With rectification maps on an eye the COLOUR image is remapped, each channel on its own and rounded to 8 bits
+ * (the driver's cv::remap, stereo_euroc.cc:166-167), and the three results are converted, as the reference orders the two.
+ * One format for both eyes: the reference has no other.  The default is PLI_IMAGE_GRAY8, the library as it was.  Synchronises the
+ * context and resizes its image staging; PLI_ERR_INVALID for an unknown format and while a batch of pli_batch_submit_host has
+ * not been waited for.  (The pli_selftest_* calls bring geometry of their own and always read gray.) */
+typedef enum { PLI_IMAGE_GRAY8 = 0, PLI_IMAGE_RGB8, PLI_IMAGE_BGR8, PLI_IMAGE_RGBA8, PLI_IMAGE_BGRA8 } pli_image_format;
+pli_status pli_set_image_format(pli_ctx* ctx, pli_image_format fmt);
+
+/* imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) of Tracking::GrabImageRGBD (Tracking.cc:979-980) at the keypoint instead of
+ * over the frame.  Afterwards the `depth` argument of pli_stereo_from_depth and pli_frame_extract_single holds elements of `type`
+ * and the value ComputeStereoFromRGBD sees at a keypoint is
+ *   PLI_DEPTH_U16:  (float)raw * scale in float, one rounding (cvtScale16u32f with shift 0); 2 bytes per pixel go up
+ *   PLI_DEPTH_F32:  d * scale in float; scale == 1.0f hands d's own bits through
+ * The d > 0 gate and the in-image guard act on that value as before; no pass over the frame is made.  Whether a map needs a scale
+ * at all (Tracking.cc:979: fabs(factor - 1) > 1e-5 || type != CV_32F) is the caller's decision (adapters/tracking_grab.hpp).
+ * The default is PLI_DEPTH_F32, 1.0f.  PLI_ERR_INVALID for an unknown type or a scale that is not finite. */
+typedef enum { PLI_DEPTH_F32 = 0, PLI_DEPTH_U16 } pli_depth_type;
+pli_status pli_set_depth_format(pli_ctx* ctx, pli_depth_type type, float scale);
+
 /* --- SURVEY.md §8(f) row 4 (RGB-D front-end): Frame::ComputeStereoFromRGBD(imDepth), Frame.cc:1309-1331 ---
  * depth: CV_32F depth image registered to the left image (already scaled by mDepthMapFactor, Tracking.cc), row
  * stride in floats.  For every left keypoint of the last pli_orb_extract(eye 0): d = depth(trunc(v), trunc(u));
  * d > 0 -> mvDepth = d, mvuRight = x - bf/d, else both -1 (the rectified pipeline: mvKeysUn == mvKeys).
- * Only the rows of the keypoints are written: uright and depth_out keep what they held from the keypoint count on. */
+ * Only the rows of the keypoints are written: uright and depth_out keep what they held from the keypoint count on.
+ * After pli_set_depth_format(ctx, PLI_DEPTH_U16, scale) `depth` points at uint16_t (the declared const float* is cast) and
+ * stride_floats counts those elements; d is then the raw element scaled as described there, for either type. */
 pli_status pli_stereo_from_depth(pli_ctx* ctx, const float* depth, int64_t stride_floats, float* uright, float* depth_out,
                                  int32_t cap);
 
@@ -514,7 +543,10 @@ pli_status pli_undistort_points(pli_ctx* ctx, const float* xy /* n x 2 */, int32
  * :384-385) and the PosInGrid of AssignFeaturesToGrid (:451-482) — image and depth up, the ORB chain beside the line chain, the
  * lapping reorder (ORBextractor.cc:1135-1144; the monocular constructor passes {0, 1000}, the RGB-D one {0, 0}) and the rest on
  * the device, one synchronisation.  depth: CV_32F, registered to the image, row stride in floats; it is read at the
- * DISTORTED keypoint and mvuRight is written from the UNDISTORTED x, with the context's bf.
+ * DISTORTED keypoint and mvuRight is written from the UNDISTORTED x, with the context's bf.  After
+ * pli_set_depth_format(ctx, PLI_DEPTH_U16, scale) `depth` points at uint16_t (the declared const float* is cast),
+ * depth_stride_floats counts those elements and the element read is scaled as described there.  `img` is read in the format of
+ * pli_set_image_format, `stride` in bytes.
  * `record` receives the frame's table record (pli_table_layout, record_bytes) with its eye-0 columns filled: kp[0], desc[0], kl[0],
  * ldesc[0], uright, depth (every row: -1 from the keypoint count on), the counts and truncation flags; everything else in it is 0.
  * kp_un: kp_cap x 2 floats (mvKeysUn[i].pt), kl_un: kl_cap x 4 floats (mvKeysUn_Line[i]: startPointX, startPointY, endPointX,

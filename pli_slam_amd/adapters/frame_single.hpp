@@ -46,16 +46,27 @@ class PliSingleCameraFrame {
     if (imGray.empty() || imGray.type() != CV_8UC1) throw std::invalid_argument("PliSingleCameraFrame: 8-bit single-channel image expected");
     if (imDepth && (imDepth->type() != CV_32F || imDepth->rows != imGray.rows || imDepth->cols != imGray.cols))
       throw std::invalid_argument("PliSingleCameraFrame: the depth image must be CV_32F of the image's size");
+    const pli::ImageView im{imGray.data, imGray.cols, imGray.rows, (int64_t)imGray.step, 1};
+    const pli::DepthView dv{imDepth ? imDepth->data : nullptr, imGray.cols, imGray.rows, imDepth ? (int64_t)imDepth->step : 0, PLI_DEPTH_F32};
+    return extractRaw(F, im, imDepth ? &dv : nullptr, x0, x1);
+  }
+
+  // ... on the images as Tracking::GrabImageRGBD / GrabImageMonocular RECEIVE them (adapters/tracking_grab.hpp: PliGrabImage has set
+  // the context's image and depth formats to what the views hold): a colour image of 3 or 4 bytes per pixel, a raw uint16 or
+  // float depth map.  Pointers and strides go to the library as they are; the image's stride stays in bytes, the depth map's is
+  // handed over in elements of its type.  The views are the caller's word: what extract() checks about its Mats is not checked here.
+  bool extractRaw(FrameT& F, const pli::ImageView& im, const pli::DepthView* depth, int x0, int x1) {
     const pli_table_layout& Y = fe_.layout();
-    if (imDepth) fe_.setStereoCamera(F.mbf, cam_.fx);          // ComputeStereoFromRGBD divides mbf (:1327)
+    if (depth) fe_.setStereoCamera(F.mbf, cam_.fx);            // ComputeStereoFromRGBD divides mbf (:1327)
     record_.resize((size_t)Y.record_bytes);
     kpUn_.resize((size_t)Y.kp_cap * 2);
     klUn_.resize((size_t)Y.kl_cap * 4);
     cell_.resize((size_t)Y.kp_cap);
     int32_t nMono = 0;
-    pli::check(pli_frame_extract_single(fe_.handle(), imGray.data, imGray.cols, imGray.rows, (int64_t)imGray.step, x0, x1,
-                                        imDepth ? reinterpret_cast<const float*>(imDepth->data) : nullptr,
-                                        imDepth ? (int64_t)(imDepth->step / sizeof(float)) : 0, record_.data(), kpUn_.data(), klUn_.data(),
+    const int64_t depthElem = depth && depth->type == PLI_DEPTH_U16 ? (int64_t)sizeof(uint16_t) : (int64_t)sizeof(float);
+    pli::check(pli_frame_extract_single(fe_.handle(), im.data, im.cols, im.rows, im.step, x0, x1,
+                                        depth ? reinterpret_cast<const float*>(depth->data) : nullptr,
+                                        depth ? depth->step / depthElem : 0, record_.data(), kpUn_.data(), klUn_.data(),
                                         cell_.data(), &nMono));
     const uint8_t* rec = record_.data();
     const int32_t* counts = reinterpret_cast<const int32_t*>(rec + Y.off_counts);

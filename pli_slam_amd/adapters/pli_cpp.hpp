@@ -36,6 +36,12 @@ inline int descriptorDistance(const uint8_t* a, const uint8_t* b) {
   return d;
 }
 
+// An image and a depth map as their owner holds them, without an OpenCV type: what cv::Mat's data, cols, rows, step (bytes) say, the
+// bytes per pixel of the image (1: gray; 3, 4: colour in the context's pli_set_image_format) and the element type of the depth map
+// (the context's pli_set_depth_format).  adapters/tracking_grab.hpp makes them from the Mats of Tracking::GrabImage*.
+struct ImageView { const uint8_t* data; int cols, rows; int64_t step; int channels; };
+struct DepthView { const void* data; int cols, rows; int64_t step; pli_depth_type type; };
+
 // One context = the four extractors of Tracking (ORB left/right, LSD left/right) plus the stereo matchers,
 // sharing device-resident pyramids and tables (reference Tracking.cc:87-98,743-749 and Frame.cc:98-228).
 // Thread safety: every pli_* call on a context holds the context's own lock inside the library
@@ -338,6 +344,10 @@ class Frontend {
   }
   // cv::remap(im, imRect, M1, M2, INTER_LINEAR) of the stereo driver (stereo_euroc.cc:166), fused into the ingest
   void setRectifyMaps(int eye, const float* mapx, const float* mapy) { check(pli_set_rectify_maps(ctx_, eye, mapx, mapy)); }
+  // the cvtColor and the depth convertTo at the head of Tracking::GrabImage* (Tracking.cc:889-914, :979-980), fused into the ingest
+  // and into ComputeStereoFromRGBD (adapters/tracking_grab.hpp picks the arguments as the reference does)
+  void setImageFormat(pli_image_format fmt) { check(pli_set_image_format(ctx_, fmt)); }
+  void setDepthFormat(pli_depth_type type, float scale) { check(pli_set_depth_format(ctx_, type, scale)); }
   // core of ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th, ...) ORBmatcher.cc:44
   int searchLocalMap(const std::vector<pli_proj_query>& q, const uint8_t* qdesc, const std::vector<pli_keypoint>& cur,
                      const uint8_t* curDesc, const float* curURight, const uint8_t* curOccupied, float minX, float maxX,

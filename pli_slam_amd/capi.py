@@ -45,6 +45,9 @@ ERRORS = {-1: "PLI_ERR_INVALID", -2: "PLI_ERR_EMPTY_IMAGE", -3: "PLI_ERR_CAPACIT
           -5: "PLI_ERR_NO_DEVICE", -6: "PLI_ERR_STATE"}
 PARITY_TRIG_F32_ORB, PARITY_TRIG_F32_LSD, PARITY_TRIG_F32_LBD, PARITY_LSD_F64, PARITY_TRIG_F32_KEYLINE = 1, 2, 4, 8, 16
 RUN_ORB, RUN_LINES, RUN_STEREO_POINTS, RUN_STEREO_LINES, RUN_ALL = 1, 2, 4, 8, 15
+IMAGE_GRAY8, IMAGE_RGB8, IMAGE_BGR8, IMAGE_RGBA8, IMAGE_BGRA8 = range(5)       # pli_image_format
+IMAGE_CHANNELS = {IMAGE_GRAY8: 1, IMAGE_RGB8: 3, IMAGE_BGR8: 3, IMAGE_RGBA8: 4, IMAGE_BGRA8: 4}
+DEPTH_F32, DEPTH_U16 = 0, 1                                                    # pli_depth_type
 (DBG_PYRAMID_LEVEL, DBG_BLUR_LEVEL, DBG_FAST_CANDIDATES, DBG_LEVEL_KEYPOINTS, DBG_LSD_SCALED, DBG_LSD_ANGLE,
  DBG_LSD_SEGMENTS, DBG_LBD_DXDY, DBG_LSD_ORDER, DBG_LBD_FLOAT, DBG_STEREO_SAD, DBG_LSD_OWNER, DBG_LSD_SIZES) = range(1, 14)
 
@@ -135,6 +138,8 @@ _PROTOS = {
     "pli_ctx_set_stream": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "pli_ctx_sync": (C.c_int32, [C.c_void_p]),
     "pli_set_rectify_maps": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pli_set_image_format": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "pli_set_depth_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_float]),
     "pli_batch_run": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32,
                                   C.c_void_p]),
     "pli_batch_run_host": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

@@ -145,6 +145,9 @@ struct pli_ctx {
   // drop-in state
   uint8_t* inStage[2] = {nullptr, nullptr};
   float2* rectMap[2] = {nullptr, nullptr};   // per eye: (mapx, mapy) of the driver's rectification, or null
+  int imgFormat = PLI_IMAGE_GRAY8;           // pli_set_image_format: how every entry point reads its images ...
+  int imgChannels = 1;                       // ... and the bytes per pixel of that format (inStage holds W * H of them per eye)
+  DepthFormat depthFmt{0, 1.0f};             // pli_set_depth_format: the depth image of the two ComputeStereoFromRGBD kernels
   uint8_t* ownTable = nullptr;
   std::vector<uint8_t> hostRec;
   bool orbDone[2] = {false, false}, lineDone[2] = {false, false};

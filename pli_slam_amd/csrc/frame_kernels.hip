@@ -70,11 +70,12 @@ __global__ void k_undistort_points(PinholeUndist C, const float2* __restrict__ x
 // kpCap + j keyline row j; the counts come from the record, as k_stereo_from_depth reads them.
 //   keypoint i < N:  kpUn[i] = the undistorted position, cell[i] = its grid cell; with a depth image ComputeStereoFromRGBD — d at
 //                    (int)v, (int)u of the DISTORTED keypoint, mvuRight = kpU.x - bf / d in float (k_stereo_from_depth's in-image guard
-//                    kept: the reference's read outside the image is undefined) —, without one mvuRight = mvDepth = -1 (:384-385)
+//                    kept: the reference's read outside the image is undefined) —, without one mvuRight = mvDepth = -1 (:384-385);
+//                    the image is the caller's raw one, d = depth_value (kernels.hpp) of the element read
 //   keyline j < M:   klUn[j] = (startPoint, endPoint) of mvKeys_Line[j], each undistorted
 // Rows from the count on: kpUn / klUn 0, cell / mvuRight / mvDepth -1, so the caller's buffers and those two columns do not depend on
 // an earlier call.
-__global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUndist C, const float* __restrict__ depthImg, int64_t pitch,
+__global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUndist C, const void* __restrict__ depthImg, DepthFormat fmt, int64_t pitch,
                                     uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offKl0, int64_t offUr,
                                     int64_t offDepth, float2* __restrict__ kpUn, int* __restrict__ cell, float4* __restrict__ klUn) {
   const DevParams& P = *Pp;
@@ -92,7 +93,7 @@ __global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUnd
       if (depthImg) {
         const int iu = (int)kp.x, iv = (int)kp.y;
         if (iu >= 0 && iv >= 0 && iu < P.W && iv < P.H) {
-          const float d = depthImg[(int64_t)iv * pitch + iu];
+          const float d = depth_value(depthImg, fmt, (int64_t)iv * pitch + iu);
           if (d > 0) { dp = d; ur = __fsub_rn(u.x, __fdiv_rn(P.bf, d)); }
         }
       }

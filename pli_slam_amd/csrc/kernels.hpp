@@ -19,6 +19,20 @@ struct BlurJob {
 };
 struct LbdCoef { float L[21]; float G[63]; };
 
+// The depth image of ComputeStereoFromRGBD as the caller holds it (pli_set_depth_format), by value to its two kernels: the
+// imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) of Tracking.cc:979-980 is made at the keypoint, on the one element read.
+struct DepthFormat {
+  int u16;        // elements are uint16_t (PLI_DEPTH_U16), otherwise float
+  float scale;
+};
+// element i of the image as ComputeStereoFromRGBD sees it: cvtScale16u32f with shift 0 is (float)raw * scale in float, one rounding
+// (every uint16 is exact in float); a float element times 1.0f keeps its bits without the multiplication (a signalling NaN too)
+__device__ __forceinline__ float depth_value(const void* __restrict__ img, DepthFormat f, int64_t i) {
+  if (f.u16) return __fmul_rn((float)static_cast<const uint16_t*>(img)[i], f.scale);
+  const float d = static_cast<const float*>(img)[i];
+  return f.scale == 1.0f ? d : __fmul_rn(d, f.scale);
+}
+
 // k_describe blurs the window of its keypoint itself (orb_kernels.hip).  The window follows from the test pattern: a tap (x, y) is
 // rotated by the keypoint angle and each coordinate rounded, so no coordinate leaves [-n, n] for the smallest n with
 // n + 0.5 > |(x, y)| * (1 + 1e-4) (the factor covers the float cos/sin and the roundings of the products).
@@ -44,6 +58,7 @@ constexpr int LBD_BLUR_R = 2;                    // GaussianBlur 5x5 (jobLbd); k
 constexpr int PROJ_K = 64;
 __global__ void k_ingest_copy16(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t stride, int64_t frameStride, uint8_t* __restrict__ pyr, int64_t pyrBlock, int W16, int H, int pitch, int img0);
 __global__ void k_ingest(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t stride, int64_t frameStride, uint8_t* __restrict__ pyr, int64_t pyrBlock, int W, int H, int pitch, const float2* __restrict__ mapL, const float2* __restrict__ mapR, int img0);
+template <int CH> __global__ void k_ingest_colour(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t stride, int64_t frameStride, uint8_t* __restrict__ pyr, int64_t pyrBlock, int W, int H, int pitch, const float2* __restrict__ mapL, const float2* __restrict__ mapR, int img0, int c0, int c2);
 __global__ void k_resize_level(const uint8_t* __restrict__ srcBase, int64_t srcImgStride, int sw, int sh, int spitch, uint8_t* __restrict__ dstBase, int64_t dstImgStride, int dw, int dh, int dpitch, const int* __restrict__ tab, int img0);
 __global__ void k_fast_cells(const DevParams* __restrict__ Pp, const uint8_t* __restrict__ pyr, uint32_t* __restrict__ cellCand, int* __restrict__ cellCount, int img0);
 __global__ void k_octree(const DevParams* __restrict__ Pp, const uint32_t* __restrict__ cellCand, const int* __restrict__ cellCount, uint32_t* __restrict__ candAll, unsigned short* __restrict__ nodeOfAll, int* __restrict__ candCount, uint32_t* __restrict__ kpSel, int* __restrict__ kpSelCount, int img0);
@@ -112,7 +127,7 @@ __global__ void k_distance(const uint8_t* __restrict__ a, const uint8_t* __restr
 __global__ void k_knn2(const uint8_t* __restrict__ q, int nq, const uint8_t* __restrict__ t, int nt, int* __restrict__ idx, int* __restrict__ dist);
 __global__ void k_ratio(const int* __restrict__ idx, const int* __restrict__ dist, int n, int nTrain, float nnr, int* __restrict__ m);
 __global__ void k_mutual(int* __restrict__ m12, const int* __restrict__ m21, int n1, int* __restrict__ nmatches);
-__global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const float* __restrict__ depthImg, int64_t pitch, int W, int H, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offUr, int64_t offDepth);
+__global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const void* __restrict__ depthImg, DepthFormat fmt, int64_t pitch, int W, int H, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offUr, int64_t offDepth);
 __global__ void k_proj_candidates(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq, const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc, const float* __restrict__ uright, int ncur, float minX, float maxX, float minY, float maxY, int checkBounds, int distLimit, unsigned long long* __restrict__ candKeys, int* __restrict__ candCount);
 __global__ void k_proj_assign(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq, const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc, const float* __restrict__ uright, const uint8_t* __restrict__ occupied, int ncur, float minX, float maxX, float minY, float maxY, int mode, int checkOri, float nnratio, const unsigned long long* __restrict__ candKeys, const int* __restrict__ candCount, int* __restrict__ bestIdx2, int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2);
 __global__ void k_proj_assign_scan(const pli_proj_query* __restrict__ q, const uint8_t* __restrict__ qdesc, int nq, const pli_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc, const float* __restrict__ uright, const uint8_t* __restrict__ occupied, int ncur, float minX, float maxX, float minY, float maxY, int mode, int checkOri, float nnratio, int* __restrict__ owner /* ncur */, int* __restrict__ bestIdx2, int* __restrict__ nmatchesOut, int* __restrict__ rawIdx2);
@@ -175,7 +190,7 @@ struct PinholeUndist {
   float minX, maxX, minY, maxY;       // mnMinX .. mnMaxY (ComputeImageBounds)
 };
 __global__ void k_undistort_points(PinholeUndist C, const float2* __restrict__ xy, int n, float2* __restrict__ xyUn, int* __restrict__ cell);
-__global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUndist C, const float* __restrict__ depthImg, int64_t pitch, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offKl0, int64_t offUr, int64_t offDepth, float2* __restrict__ kpUn, int* __restrict__ cell, float4* __restrict__ klUn);
+__global__ void k_frame_single_tail(const DevParams* __restrict__ Pp, PinholeUndist C, const void* __restrict__ depthImg, DepthFormat fmt, int64_t pitch, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0, int64_t offKl0, int64_t offUr, int64_t offDepth, float2* __restrict__ kpUn, int* __restrict__ cell, float4* __restrict__ klUn);
 
 __global__ void k_tx_tail(TxTailArgs T);
 __global__ void k_tx_rec_from_hot(const RxCtl* __restrict__ ctl, const int2* __restrict__ hotAll, const float2* __restrict__ coldAll, float4* __restrict__ recAll, int64_t npix, int img0);

@@ -545,8 +545,9 @@ __global__ void k_mutual(int* __restrict__ m12, const int* __restrict__ m21, int
 // ---------------------------------------------------------------------------
 // Frame::ComputeStereoFromRGBD (Frame.cc:1309-1331): depth of every left keypoint from a registered float
 // depth image, mvuRight = x - bf / d.  (cv::Mat::at<float>(v, u) with float arguments truncates them.)
+// The image is the caller's raw one (float or uint16, pitch in elements): depth_value (kernels.hpp) converts the element read.
 // ---------------------------------------------------------------------------
-__global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const float* __restrict__ depthImg, int64_t pitch,
+__global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const void* __restrict__ depthImg, DepthFormat fmt, int64_t pitch,
                                     int W, int H, uint8_t* __restrict__ table, int64_t offCounts, int64_t offKp0,
                                     int64_t offUr, int64_t offDepth) {
   const DevParams& P = *Pp;
@@ -557,7 +558,7 @@ __global__ void k_stereo_from_depth(const DevParams* __restrict__ Pp, const floa
   const int u = (int)kp.x, v = (int)kp.y;
   float ur = -1.f, dp = -1.f;
   if (u >= 0 && v >= 0 && u < W && v < H) {
-    const float d = depthImg[(int64_t)v * pitch + u];
+    const float d = depth_value(depthImg, fmt, (int64_t)v * pitch + u);
     if (d > 0) { dp = d; ur = __fsub_rn(kp.x, __fdiv_rn(P.bf, d)); }
   }
   reinterpret_cast<float*>(table + offUr)[i] = ur;

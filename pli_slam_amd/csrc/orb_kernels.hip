@@ -83,6 +83,88 @@ __global__ __launch_bounds__(256) void k_ingest(const uint8_t* __restrict__ left
 }
 
 // ---------------------------------------------------------------------------
+// k_ingest_colour<CH>: k_ingest for interleaved colour images of CH = 3 or 4 bytes per pixel (pli_set_image_format) — the
+// cvtColor(mImGray, mImGray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) at the head of Tracking::GrabImageStereo /
+// RGBD / Monocular (Tracking.cc:889-914, :964-977, :1014-1027) fused into the ingest.  OpenCV 3.3.1's C++ path RGB2Gray<uchar>:
+// 14-bit coefficients R2Y = 4899, G2Y = 9617, B2Y = 1868 (they sum to 2^14) in a table of b*cb, g*cg, r*cr + 2^13 per byte value,
+// gray = (R*4899 + G*9617 + B*1868 + 8192) >> 14, the fourth byte of a 4-channel pixel not read for the value.  c0 / c2 are the
+// coefficients of bytes 0 and 2 of a pixel: (4899, 1868) for RGB / RGBA, (1868, 4899) for BGR / BGRA; byte 1 is green in all four.
+// With rectification maps the reference's order is kept: the driver remaps the COLOUR image (stereo_euroc.cc:166-167: every
+// channel by k_ingest's rule, each rounded to 8 bits), GrabImageStereo converts the result.
+// A thread makes 4 adjacent pixels and stores one uchar4, as k_ingest does.  Without maps its 4 * CH source bytes are contiguous
+// and start a multiple of 4 bytes behind the row's first: where that first byte is 4-byte aligned (a row property: base and
+// stride) they are read as 3 or 4 dwords (one 16-byte load for CH = 4 where the row allows it), otherwise — an odd base, a stride
+// that is no multiple of 4 — and for the thread that holds the row's last, partial group, byte by byte.
+// ---------------------------------------------------------------------------
+template <int CH>
+__global__ __launch_bounds__(256) void k_ingest_colour(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                       int64_t stride, int64_t frameStride, uint8_t* __restrict__ pyr,
+                                                       int64_t pyrBlock, int W, int H, int pitch,
+                                                       const float2* __restrict__ mapL, const float2* __restrict__ mapR, int img0,
+                                                       int c0, int c2) {
+  static_assert(CH == 3 || CH == 4, "interleaved pixels of 3 or 4 bytes");
+  const int img = blockIdx.z + img0;
+  const uint8_t* src = ((img & 1) ? right : left) + (int64_t)(img >> 1) * frameStride;
+  const float2* map = (img & 1) ? mapR : mapL;
+  uint8_t* dst = pyr + (int64_t)img * pyrBlock;
+  const int y = blockIdx.y;
+  const int x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (x4 >= W) return;
+  auto gray = [&](int b0, int b1, int b2) -> uint8_t { return (uint8_t)((b0 * c0 + b1 * 9617 + b2 * c2 + 8192) >> 14); };
+  uint8_t v[4] = {0, 0, 0, 0};
+  if (!map) {
+    const uint8_t* s = src + (int64_t)y * stride + (int64_t)x4 * CH;
+    if (x4 + 3 < W && (reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+      uint32_t d[CH];
+      if (CH == 4 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+        const uint4 q = *reinterpret_cast<const uint4*>(s);
+        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[CH - 1] = q.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < CH; ++k) d[k] = reinterpret_cast<const uint32_t*>(s)[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // byte j of the 4 * CH bytes is byte j & 3 of dword j >> 2 (little endian)
+        auto byteAt = [&](int j) -> int { return (int)((d[j >> 2] >> ((j & 3) * 8)) & 255u); };
+        v[k] = gray(byteAt(k * CH), byteAt(k * CH + 1), byteAt(k * CH + 2));
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k < W) v[k] = gray(s[k * CH], s[k * CH + 1], s[k * CH + 2]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (x4 + k >= W) continue;
+      const float2 m = map[(int64_t)y * W + x4 + k];
+      const int sx = cv_round_f_x86(__fmul_rn(m.x, 32.f)), sy = cv_round_f_x86(__fmul_rn(m.y, 32.f));
+      const int ix = min(max(sx >> 5, -32768), 32767), iy = min(max(sy >> 5, -32768), 32767);
+      const int fx = sx & 31, fy = sy & 31;
+      int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;
+      if ((fx | fy) == 0) { w0 = 32767; w3 = 1; }
+      if (ix >= W || ix + 1 < 0 || iy >= H || iy + 1 < 0) continue;        // fully outside: border value 0 in every channel, gray 0
+      int ch[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        auto at = [&](int xx, int yy) -> int {
+          return (xx >= 0 && yy >= 0 && xx < W && yy < H) ? (int)src[(int64_t)yy * stride + (int64_t)xx * CH + q] : 0;
+        };
+        const int sum = at(ix, iy) * w0 + at(ix + 1, iy) * w1 + at(ix, iy + 1) * w2 + at(ix + 1, iy + 1) * w3;
+        ch[q] = min(max((sum + (1 << 14)) >> 15, 0), 255);
+      }
+      v[k] = gray(ch[0], ch[1], ch[2]);
+    }
+  }
+  *reinterpret_cast<uchar4*>(dst + (int64_t)y * pitch + x4) = make_uchar4(v[0], v[1], v[2], v[3]);
+}
+template __global__ void k_ingest_colour<3>(const uint8_t* __restrict__, const uint8_t* __restrict__, int64_t, int64_t, uint8_t* __restrict__,
+                                            int64_t, int, int, int, const float2* __restrict__, const float2* __restrict__, int, int, int);
+template __global__ void k_ingest_colour<4>(const uint8_t* __restrict__, const uint8_t* __restrict__, int64_t, int64_t, uint8_t* __restrict__,
+                                            int64_t, int, int, int, const float2* __restrict__, const float2* __restrict__, int, int, int);
+
+// ---------------------------------------------------------------------------
 // k_resize_level: cv::resize INTER_LINEAR u8 (11-bit coefficients built on the
 // host exactly as OpenCV builds them).
 // tab: xofs[dw] | alpha[2*dw] (as int) | yofs[dh] | beta[2*dh]

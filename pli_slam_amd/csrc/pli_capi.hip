@@ -597,6 +597,18 @@ pli_status allocAll(pli_ctx* c) {
 pli_status runIngest(pli_ctx* c, const uint8_t* dl, const uint8_t* dr, int64_t stride, int64_t frameStride, int img0, int nimg) {
   TraceRange range__("pli:ingest");
   const DevParams& P = c->hp;
+  if (c->imgFormat != PLI_IMAGE_GRAY8) {       // (pli_set_image_format: stride and frameStride are bytes of the colour images)
+    const bool rgb = c->imgFormat == PLI_IMAGE_RGB8 || c->imgFormat == PLI_IMAGE_RGBA8;
+    const int c0 = rgb ? 4899 : 1868, c2 = rgb ? 1868 : 4899;       // the coefficients of bytes 0 and 2: R2Y and B2Y, or swapped
+    dim3 g((P.W + 1023) / 1024, P.H, nimg);
+    if (c->imgChannels == 3)
+      LAUNCH(c, "k_ingest", k_ingest_colour<3>, g, dim3(256), 0, dl, dr, stride, frameStride, c->pyr, P.pyrBlock, P.W, P.H, P.lv[0].pitch,
+             (const float2*)c->rectMap[0], (const float2*)c->rectMap[1], img0, c0, c2);
+    else
+      LAUNCH(c, "k_ingest", k_ingest_colour<4>, g, dim3(256), 0, dl, dr, stride, frameStride, c->pyr, P.pyrBlock, P.W, P.H, P.lv[0].pitch,
+             (const float2*)c->rectMap[0], (const float2*)c->rectMap[1], img0, c0, c2);
+    return PLI_OK;
+  }
   const bool aligned16 = !c->rectMap[0] && !c->rectMap[1] && (P.W % 16) == 0 && (stride % 16) == 0 && (frameStride % 16) == 0 &&
                          (reinterpret_cast<uintptr_t>(dl) % 16) == 0 && (reinterpret_cast<uintptr_t>(dr) % 16) == 0 && (P.lv[0].pitch % 16) == 0 &&
                          (P.pyrBlock % 16) == 0;
@@ -761,16 +773,22 @@ hipError_t copyColumn(pli_ctx* c, T* dst, int64_t off, int n, int per = 1) {
   return dst && n > 0 ? hipMemcpy(dst, c->ownTable + off, (size_t)n * per * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
 }
 
+// bytes of one image row as the entry points read it: the context's width times the bytes per pixel of pli_set_image_format
+inline int64_t rowBytes(const pli_ctx* c) { return (int64_t)c->cfg.width * c->imgChannels; }
+// bytes of one element of a depth image (pli_set_depth_format)
+inline size_t depthElemBytes(const pli_ctx* c) { return c->depthFmt.u16 ? sizeof(uint16_t) : sizeof(float); }
+
 pli_status checkImage(pli_ctx* c, const uint8_t* img, int w, int h, int64_t stride) {
   if (!img || w <= 0 || h <= 0) { g_err = "empty image"; return PLI_ERR_EMPTY_IMAGE; }
   if (w != c->cfg.width || h != c->cfg.height) { g_err = "image size differs from the context's"; return PLI_ERR_INVALID; }
-  if (stride < w) { g_err = "stride < width"; return PLI_ERR_INVALID; }
+  if (stride < rowBytes(c)) { g_err = "stride < width x bytes per pixel"; return PLI_ERR_INVALID; }
   return PLI_OK;
 }
 
 pli_status stageImage(pli_ctx* c, int eye, const uint8_t* img, int w, int h, int64_t stride) {
-  HIPCHK(hipMemcpy2DAsync(c->inStage[eye], w, img, stride, w, h, hipMemcpyHostToDevice, c->stream));
-  return runIngest(c, c->inStage[0], c->inStage[1], w, 0, eye, 1);
+  const size_t row = (size_t)rowBytes(c);
+  HIPCHK(hipMemcpy2DAsync(c->inStage[eye], row, img, stride, row, h, hipMemcpyHostToDevice, c->stream));
+  return runIngest(c, c->inStage[0], c->inStage[1], (int64_t)row, 0, eye, 1);
 }
 
 }  // namespace
@@ -914,6 +932,54 @@ pli_status pli_set_rectify_maps(pli_ctx* c, int32_t eye, const float* mapx, cons
   return PLI_OK;
 }
 
+pli_status pli_set_image_format(pli_ctx* c, pli_image_format fmt) {
+  CtxGuard guard__(c);
+  if (!c) { g_err = "null argument"; return PLI_ERR_INVALID; }
+  int ch = 0;
+  switch ((int)fmt) {
+    case PLI_IMAGE_GRAY8: ch = 1; break;
+    case PLI_IMAGE_RGB8: case PLI_IMAGE_BGR8: ch = 3; break;
+    case PLI_IMAGE_RGBA8: case PLI_IMAGE_BGRA8: ch = 4; break;
+    default: g_err = "unknown image format"; return PLI_ERR_INVALID;
+  }
+  if (c->hsWaited < c->hsSubmitted) { g_err = "a submitted batch is in flight: pli_batch_wait first"; return PLI_ERR_INVALID; }
+  if ((int)fmt == c->imgFormat) return PLI_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));           // kernels and copies in flight read the staging of the old format
+  if (ch != c->imgChannels) {
+    // the per-call staging: W * H pixels per eye; the slots of pli_batch_submit_host are sized again by the next submit
+    // (both new buffers first: a failed allocation leaves the context as it was)
+    uint8_t* fresh[2] = {nullptr, nullptr};
+    for (int e = 0; e < 2; ++e)
+      if (hipMalloc((void**)&fresh[e], (size_t)c->cfg.width * c->cfg.height * ch) != hipSuccess) {
+        if (fresh[0]) hipFree(fresh[0]);
+        g_err = "out of device memory for the image staging";
+        return PLI_ERR_HIP;
+      }
+    for (int e = 0; e < 2; ++e) {
+      std::replace(c->allocs.begin(), c->allocs.end(), (void*)c->inStage[e], (void*)fresh[e]);
+      hipFree(c->inStage[e]);
+      c->inStage[e] = fresh[e];
+    }
+    for (int s = 0; s < 2; ++s) {
+      if (c->hs[s].dimg) hipFree(c->hs[s].dimg);
+      c->hs[s].dimg = nullptr; c->hs[s].imgBytes = 0;
+    }
+  }
+  c->imgFormat = (int)fmt;
+  c->imgChannels = ch;
+  return PLI_OK;
+}
+
+pli_status pli_set_depth_format(pli_ctx* c, pli_depth_type type, float scale) {
+  CtxGuard guard__(c);
+  if (!c) { g_err = "null argument"; return PLI_ERR_INVALID; }
+  if ((int)type != PLI_DEPTH_F32 && (int)type != PLI_DEPTH_U16) { g_err = "unknown depth type"; return PLI_ERR_INVALID; }
+  if (!std::isfinite(scale)) { g_err = "the depth scale is not finite"; return PLI_ERR_INVALID; }
+  c->depthFmt = DepthFormat{(int)type == PLI_DEPTH_U16 ? 1 : 0, scale};      // (passed by value with each launch: nothing in flight reads it)
+  return PLI_OK;
+}
+
 pli_status pli_ctx_sync(pli_ctx* c) {
   CtxGuard guard__(c);
   if (!c) return PLI_ERR_INVALID;
@@ -927,7 +993,7 @@ pli_status pli_batch_run(pli_ctx* c, int32_t nframes, const uint8_t* dl, const u
   TraceRange range__("pli_batch_run");
   if (!c || !dl || !dr || !table) { g_err = "null argument"; return PLI_ERR_INVALID; }
   if (nframes < 1 || nframes > c->cfg.max_frames) { g_err = "nframes exceeds the context's max_frames"; return PLI_ERR_INVALID; }
-  if (stride < c->cfg.width) { g_err = "stride < width"; return PLI_ERR_INVALID; }
+  if (stride < rowBytes(c)) { g_err = "stride < width x bytes per pixel"; return PLI_ERR_INVALID; }
   if (((uintptr_t)table & 15) != 0) { g_err = "the table must be 16-byte aligned"; return PLI_ERR_INVALID; }
   HIPCHK(hipSetDevice(c->device));
   uint8_t* T = (uint8_t*)table;
@@ -957,8 +1023,9 @@ pli_status pli_batch_run_host(pli_ctx* c, int32_t nframes, const uint8_t* left, 
   TraceRange range__("pli_batch_run_host");
   if (!c || !left || !right || !table) { g_err = "null argument"; return PLI_ERR_INVALID; }
   if (nframes < 1 || nframes > c->cfg.max_frames) { g_err = "nframes exceeds the context's max_frames"; return PLI_ERR_INVALID; }
+  if (stride < rowBytes(c)) { g_err = "stride < width x bytes per pixel"; return PLI_ERR_INVALID; }
   HIPCHK(hipSetDevice(c->device));
-  const int W = c->cfg.width, H = c->cfg.height;
+  const int W = (int)rowBytes(c), H = c->cfg.height;      // (W: bytes of a staged row)
   const size_t imgBytes = (size_t)W * H;
   ScratchPlan plan;
   auto dl = plan.add<uint8_t>(2 * imgBytes * nframes);                  // the left images, then the right ones
@@ -987,7 +1054,7 @@ pli_status pli_frame_extract(pli_ctx* c, const uint8_t* left, const uint8_t* rig
   if (st != PLI_OK) return st;
   if ((st = checkImage(c, right, w, h, strideRight)) != PLI_OK) return st;
   HIPCHK(hipSetDevice(c->device));
-  const int W = c->cfg.width, H = c->cfg.height;
+  const int W = (int)rowBytes(c), H = c->cfg.height;      // (W: bytes of a staged row)
   HIPCHK(hipMemcpy2DAsync(c->inStage[0], W, left, strideLeft, W, H, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpy2DAsync(c->inStage[1], W, right, strideRight, W, H, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->ownTable, 0, (size_t)c->lay.record_bytes, c->stream));
@@ -1045,9 +1112,9 @@ pli_status pli_batch_submit_host(pli_ctx* c, int32_t nframes, const uint8_t* lef
   TraceRange range__("pli_batch_submit_host");
   if (!c || !left || !right || !table) { g_err = "null argument"; return PLI_ERR_INVALID; }
   if (nframes < 1 || nframes > c->cfg.max_frames) { g_err = "nframes exceeds the context's max_frames"; return PLI_ERR_INVALID; }
-  if (stride < c->cfg.width) { g_err = "stride < width"; return PLI_ERR_INVALID; }
+  if (stride < rowBytes(c)) { g_err = "stride < width x bytes per pixel"; return PLI_ERR_INVALID; }
   HIPCHK(hipSetDevice(c->device));
-  const int W = c->cfg.width, H = c->cfg.height;
+  const int W = (int)rowBytes(c), H = c->cfg.height;      // (W: bytes of a staged row)
   const size_t imgBytes = (size_t)W * H, tabBytes = (size_t)c->lay.record_bytes * nframes;
   if (!c->sH2D) {
     HIPCHK(hipStreamCreateWithFlags(&c->sH2D, hipStreamNonBlocking));
@@ -1415,12 +1482,13 @@ pli_status pli_stereo_from_depth(pli_ctx* c, const float* depth, int64_t strideF
   if (!c->orbDone[0]) { g_err = "pli_orb_extract must run for the left eye first"; return PLI_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
   const int W = c->cfg.width, H = c->cfg.height;
-  pli_status st = ensureScratch(c, (size_t)W * H * 4);
+  const size_t el = depthElemBytes(c);        // (pli_set_depth_format: `depth` holds floats or uint16_t, the stride counts elements)
+  pli_status st = ensureScratch(c, (size_t)W * H * el);
   if (st != PLI_OK) return st;
-  HIPCHK(hipMemcpy2DAsync(c->scratch, (size_t)W * 4, depth, (size_t)strideFloats * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpy2DAsync(c->scratch, (size_t)W * el, depth, (size_t)strideFloats * el, (size_t)W * el, H, hipMemcpyHostToDevice, c->stream));
   const pli_table_layout& Y = c->lay;
-  LAUNCH(c, "k_stereo_from_depth", k_stereo_from_depth, dim3((c->hp.kpCap + 255) / 256), dim3(256), 0, c->dP, (const float*)c->scratch,
-         (int64_t)W, W, H, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_uright, Y.off_depth);
+  LAUNCH(c, "k_stereo_from_depth", k_stereo_from_depth, dim3((c->hp.kpCap + 255) / 256), dim3(256), 0, c->dP, (const void*)c->scratch,
+         c->depthFmt, (int64_t)W, W, H, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_uright, Y.off_depth);
   RecordCounts rc;
   if ((st = readCounts(c, rc)) != PLI_OK) return st;
   const int N = rc.kp[0];
@@ -1545,7 +1613,8 @@ pli_status pli_frame_extract_single(pli_ctx* c, const uint8_t* img, int32_t w, i
   const size_t kpUnBytes = (size_t)P.kpCap * sizeof(float2), klUnBytes = (size_t)P.klCap * sizeof(float4), cellBytes = (size_t)P.kpCap * 4;
   const size_t offKl = alignUp(kpUnBytes, 16), offCell = offKl + klUnBytes, offMono = offCell + cellBytes, outBytes = offMono + 4;
   ScratchPlan plan;
-  auto ddepth = plan.addIf<float>(depth != nullptr, (size_t)W * H);
+  const size_t el = depthElemBytes(c);        // (pli_set_depth_format: `depth` holds floats or uint16_t, the stride counts elements)
+  auto ddepth = plan.addIf<uint8_t>(depth != nullptr, (size_t)W * H * el);
   auto sk = plan.add<pli_keypoint>((size_t)P.kpCap);
   auto sd = plan.add<uint8_t>((size_t)P.kpCap * 32);
   auto dout = plan.add<uint8_t>(outBytes);
@@ -1561,10 +1630,11 @@ pli_status pli_frame_extract_single(pli_ctx* c, const uint8_t* img, int32_t w, i
   c->frameFresh = c->pointsFresh = false;
   for (int e = 0; e < 2; ++e) { c->orbDone[e] = c->lineDone[e] = false; c->pyrHostValid[e] = false; }
   HIPCHK(hipMemsetAsync(c->ownTable, 0, recBytes, c->stream));
-  HIPCHK(hipMemcpy2DAsync(c->inStage[0], W, img, stride, W, H, hipMemcpyHostToDevice, c->stream));
+  const size_t row = (size_t)rowBytes(c);
+  HIPCHK(hipMemcpy2DAsync(c->inStage[0], row, img, stride, row, H, hipMemcpyHostToDevice, c->stream));
   if (depth)
-    HIPCHK(hipMemcpy2DAsync(ddepth, (size_t)W * 4, depth, (size_t)depthStrideFloats * 4, (size_t)W * 4, H, hipMemcpyHostToDevice, c->stream));
-  if ((st = runIngest(c, c->inStage[0], c->inStage[1], W, 0, 0, 1)) != PLI_OK) return st;
+    HIPCHK(hipMemcpy2DAsync(ddepth, (size_t)W * el, depth, (size_t)depthStrideFloats * el, (size_t)W * el, H, hipMemcpyHostToDevice, c->stream));
+  if ((st = runIngest(c, c->inStage[0], c->inStage[1], (int64_t)row, 0, 0, 1)) != PLI_OK) return st;
   if (chainsRunBeside(c, 1)) {
     if ((st = runChainsBeside(c, 0, 1, c->ownTable, 0)) != PLI_OK) return st;
   } else {
@@ -1581,7 +1651,7 @@ pli_status pli_frame_extract_single(pli_ctx* c, const uint8_t* img, int32_t w, i
   LAUNCH(c, "k_lapping_order", k_lapping_order_counted, dim3(1), dim3(1024), 0, (const pli_keypoint*)sk, (const uint8_t*)sd,
          reinterpret_cast<const int*>(c->ownTable + Y.off_counts), P.kpCap, (float)lap0, (float)lap1, tk, td, dmono);
   LAUNCH(c, "k_frame_single_tail", k_frame_single_tail, dim3((P.kpCap + P.klCap + 255) / 256), dim3(256), 0, c->dP, c->pinhole,
-         (const float*)ddepth, (int64_t)W, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_kl[0], Y.off_uright, Y.off_depth,
+         (const void*)(uint8_t*)ddepth, c->depthFmt, (int64_t)W, c->ownTable, Y.off_counts, Y.off_kp[0], Y.off_kl[0], Y.off_uright, Y.off_depth,
          reinterpret_cast<float2*>((uint8_t*)dout), reinterpret_cast<int*>((uint8_t*)dout + offCell),
          reinterpret_cast<float4*>((uint8_t*)dout + offKl));
   uint8_t* pinOut = c->recPinned + alignUp((int64_t)recBytes, 16);

@@ -30,6 +30,17 @@ def _u8(img):
     return img
 
 
+def _colour_u8(img, channels):
+    """An interleaved (H, W, channels) u8 image as the library reads it: pixels of `channels` adjacent bytes, rows any number of
+    bytes apart.  A view with exactly that layout (padded rows, a base at any byte) goes through as it is, anything else is copied."""
+    img = np.asarray(img)
+    if img.ndim != 3 or img.shape[2] != channels:
+        raise ValueError("(H, W, %d) u8 image expected under the image format that is set" % channels)
+    if img.dtype != np.uint8 or img.strides[2] != 1 or img.strides[1] != channels or img.strides[0] < img.shape[1] * channels:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+    return img
+
+
 PRODUCT_ENV = ("PLI_ROCTX", "PLI_SYNC_DEBUG", "PLI_TX_TAIL", "PLI_LSD_MODE")      # what libpli_frontend.so itself reads
 PYTHON_ENV = ("PLI_LIB_PATH", "PLI_USE_DEV_LIB", "PLI_FUSION_WAIT_MS")             # read by this package / the C++ adapters
 
@@ -115,6 +126,35 @@ class Frontend:
         check(self.L.pli_ctx_layout(self.h, C.byref(self.layout)))
         self.kp_cap = self.layout.kp_cap
         self.kl_cap = self.layout.kl_cap
+        self.image_format, self.channels = capi.IMAGE_GRAY8, 1
+        self.depth_type, self.depth_scale = capi.DEPTH_F32, np.float32(1)
+
+    # ---- the GrabImage conversions (Tracking.cc:889-914, :964-980, :1014-1027) on the device -------------
+    def set_image_format(self, fmt):
+        """pli_set_image_format: every image helper below then takes (H, W, 3) (capi.IMAGE_RGB8 / IMAGE_BGR8) or (H, W, 4) (IMAGE_RGBA8 /
+        IMAGE_BGRA8) u8 arrays, rows possibly padded, and level 0 of the pyramid is OpenCV 3.3.1's RGB2Gray<uchar> of them; IMAGE_GRAY8 (the
+        default) takes (H, W) arrays as before."""
+        fmt = int(fmt)
+        check(self.L.pli_set_image_format(self.h, fmt))
+        self.image_format, self.channels = fmt, capi.IMAGE_CHANNELS[fmt]
+
+    def set_depth_format(self, type, scale=1.0):
+        """pli_set_depth_format: stereo_from_depth and frame_extract_single then take uint16 depth maps (capi.DEPTH_U16) or float ones
+        (capi.DEPTH_F32) and see element * scale (float) at each keypoint: imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) without a
+        pass over the frame."""
+        type, scale = int(type), np.float32(scale)
+        check(self.L.pli_set_depth_format(self.h, type, float(scale)))
+        self.depth_type, self.depth_scale = type, scale
+
+    def _image(self, img):
+        return _u8(img) if self.channels == 1 else _colour_u8(img, self.channels)
+
+    def _depth(self, depth):
+        """The depth map as the library reads it under the depth format that is set: (height, stride >= width), contiguous."""
+        dt = np.uint16 if self.depth_type == capi.DEPTH_U16 else np.float32
+        if self.depth_type == capi.DEPTH_U16 and np.asarray(depth).dtype != np.uint16:
+            raise ValueError("uint16 depth map expected under DEPTH_U16")
+        return np.ascontiguousarray(depth, dt)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -139,7 +179,7 @@ class Frontend:
             if st != -2:
                 check(st)
             return -1, np.zeros(0, KEYPOINT_DT), np.zeros((0, 32), np.uint8)
-        image = _u8(image)
+        image = self._image(image)
         kp = np.zeros(self.kp_cap, KEYPOINT_DT)
         desc = np.zeros((self.kp_cap, 32), np.uint8)
         n = C.c_int32()
@@ -156,7 +196,7 @@ class Frontend:
 
     def line_extract(self, eye, image):
         """Lineextractor::operator(); returns (n, keylines, descriptors)."""
-        image = _u8(image)
+        image = self._image(image)
         kl = np.zeros(self.kl_cap, KEYLINE_DT)
         desc = np.zeros((self.kl_cap, 32), np.uint8)
         n = C.c_int32()
@@ -655,7 +695,7 @@ class Frontend:
     def orb_extract_lapping(self, eye, image, lapping):
         """ORBextractor::operator() with vLappingArea = lapping (ORBextractor.cc:1135-1144): (n, mono count, keypoints, descriptors);
         the table keeps the mono-first / lapping-from-the-back order for stereo_fisheye()."""
-        image = _u8(image)
+        image = self._image(image)
         kp = np.zeros(self.kp_cap, KEYPOINT_DT)
         desc = np.zeros((self.kp_cap, 32), np.uint8)
         n, mono = C.c_int32(), C.c_int32()
@@ -694,7 +734,7 @@ class Frontend:
         """Frame::ComputeStereoFromRGBD (Frame.cc:1309): (mvuRight, mvDepth) of the left keypoints from a float depth image.
         stride: row stride of `depth` in floats when its rows are padded ((height, stride) array, the image in the first `width`
         columns).  Both results have kp_cap rows; the rows beyond the keypoint count are not written by the call and stay 0."""
-        d = np.ascontiguousarray(depth, np.float32)
+        d = self._depth(depth)
         if stride is None:
             stride = self.cfg.width
         assert stride >= self.cfg.width and d.shape == (self.cfg.height, stride)
@@ -736,10 +776,10 @@ class Frontend:
         with stride >= width.  Returns the parsed record (its eye-0 columns: kpL, descL, klL, ldescL, uright, depth, counts) plus
         kp_un [n, 2] (mvKeysUn[i].pt), kl_un [m, 4] (mvKeysUn_Line[i]: start, end), cell [n] (as undistort_points) and n_mono (the
         extractor's return value); "full" holds the call's buffers as written, every row.  Leaves the per-call state of eye 0 behind (pyramid_level, stereo_from_depth)."""
-        image = _u8(image)
+        image = self._image(image)
         d, stride = None, 0
         if depth is not None:
-            d = np.ascontiguousarray(depth, np.float32)
+            d = self._depth(depth)
             assert d.ndim == 2 and d.shape[0] == self.cfg.height and d.shape[1] >= self.cfg.width
             stride = d.shape[1]
         rec = np.zeros(int(self.layout.record_bytes), np.uint8)
@@ -892,9 +932,13 @@ class Frontend:
         return int(self.layout.record_bytes) * nframes
 
     def batch_run_host(self, images, stages=capi.RUN_ALL):
-        """images: (nframes, 2, H, W) u8.  Returns the list of parsed frame records."""
+        """images: (nframes, 2, H, W) u8 ((nframes, 2, H, W, channels) under a colour image format).  Returns the list of parsed
+        frame records."""
         images = np.ascontiguousarray(images, np.uint8)
-        nf, two, H, W = images.shape
+        if images.ndim != (4 if self.channels == 1 else 5) or images.shape[4:] not in ((), (self.channels,)):
+            raise ValueError("(nframes, 2, H, W%s) u8 images expected" % ("" if self.channels == 1 else ", %d" % self.channels))
+        nf, two, H, W = images.shape[:4]
+        W *= self.channels                  # bytes of a row
         assert two == 2
         left = np.ascontiguousarray(images[:, 0])
         right = np.ascontiguousarray(images[:, 1])
@@ -908,7 +952,10 @@ class Frontend:
         stay off.  images: (nframes, H, W) u8, nframes even.  Returns one dict per frame: kp, desc, kl, ldesc — what the
         monocular Frame constructor (Frame.cc:334) extracts."""
         images = np.ascontiguousarray(images, np.uint8)
-        nf, H, W = images.shape
+        if images.ndim != (3 if self.channels == 1 else 4) or images.shape[3:] not in ((), (self.channels,)):
+            raise ValueError("(nframes, H, W%s) u8 images expected" % ("" if self.channels == 1 else ", %d" % self.channels))
+        nf, H, W = images.shape[:3]
+        W *= self.channels                  # bytes of a row
         assert nf % 2 == 0 and not (stages & (capi.RUN_STEREO_POINTS | capi.RUN_STEREO_LINES))
         table = np.zeros(self.table_bytes(nf // 2), np.uint8)
         base = images.ctypes.data
@@ -940,7 +987,7 @@ class Frontend:
     def frame_extract(self, left, right):
         """pli_frame_extract: the whole front-end of one Frame (both eyes, points and lines, the two stereo matchers) in one
         submission; returns the parsed record and leaves the per-call state behind (pyramid_level, compute_stereo_matches)."""
-        left, right = _u8(left), _u8(right)
+        left, right = self._image(left), self._image(right)
         rec = np.zeros(int(self.layout.record_bytes), np.uint8)
         check(self.L.pli_frame_extract(self.h, ptr(left), ptr(right), left.shape[1], left.shape[0], left.strides[0],
                                        right.strides[0], ptr(rec)))
@@ -1046,15 +1093,16 @@ class Frontend:
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nbytes,))
 
     def host_buffers(self, nframes):
-        """(left, right, tables): pinned (nframes, H*W) image planes and two pinned result tables."""
-        n = self.cfg.width * self.cfg.height
+        """(left, right, tables): pinned (nframes, H*W) image planes (H*W*channels bytes each under a colour image format) and two
+        pinned result tables."""
+        n = self.cfg.width * self.cfg.height * self.channels
         left = self.pinned(nframes * n).reshape(nframes, n)
         right = self.pinned(nframes * n).reshape(nframes, n)
         tables = [self.pinned(self.table_bytes(nframes)) for _ in range(2)]
         return left, right, tables
 
     def host_submit(self, nframes, left, right, table, stages=capi.RUN_ALL):
-        W, H = self.cfg.width, self.cfg.height
+        W, H = self.cfg.width * self.channels, self.cfg.height      # (W: bytes of a row)
         check(self.L.pli_batch_submit_host(self.h, nframes, ptr(left), ptr(right), W, W * H, stages, ptr(table)))
 
     def host_wait(self):
