@@ -149,6 +149,11 @@ class Mat {
     for (int r = 0; r < rows; ++r) std::memcpy(m.data + (size_t)r * m.step, data + (size_t)r * step, (size_t)cols * elemSize());
     return m;
   }
+  // into a matrix or a view of this one's size and type (Rcw.copyTo(Tcw.colRange(0, 3)))
+  void copyTo(Mat m) const {
+    assert(m.data && m.rows == rows && m.cols == cols && m.flags == flags);
+    for (int r = 0; r < rows; ++r) std::memcpy(m.data + (size_t)r * m.step, data + (size_t)r * step, (size_t)cols * elemSize());
+  }
   MatExpr t() const { MatExpr e; e.a = std::make_shared<Mat>(*this); e.ta = true; return e; }
   MatExpr inv() const { MatExpr e; e.kind = MatExpr::INV; e.a = std::make_shared<Mat>(*this); return e; }
   double dot(const Mat& m) const {
@@ -425,6 +430,24 @@ typedef Matrix<double, 3, 1> Vector3d;
 using namespace std;      // the reference's ORBmatcher.h writes map<>, pair<> and vector<> unqualified (its header chain says this)
 #endif
 
+// HOOKS for a stand-in that includes this one (map_shim/pli_map_shim.hpp, which compiles definitions cut out of the reference's
+// MapPoint.cc, MapLine.cc, Frame.cc, LocalMapping.cc and KeyFrame.cc next to ORBmatcher.cc): members added to the three classes, the value type of
+// MapPoint::mObservations, and PLI_SHIM_MAPPOINT_OWN_SCALE, under which GetMinDistanceInvariance, GetMaxDistanceInvariance and
+// PredictScale(dist, Frame*) are only declared, because the reference's own definitions are linked in.  All unset here: ref_match
+// and its fixtures see the text they always saw.
+#ifndef PLI_SHIM_OBSERVATION_T
+#define PLI_SHIM_OBSERVATION_T int
+#endif
+#ifndef PLI_SHIM_MAPPOINT_EXTRA
+#define PLI_SHIM_MAPPOINT_EXTRA
+#endif
+#ifndef PLI_SHIM_KEYFRAME_EXTRA
+#define PLI_SHIM_KEYFRAME_EXTRA
+#endif
+#ifndef PLI_SHIM_FRAME_EXTRA
+#define PLI_SHIM_FRAME_EXTRA
+#endif
+
 namespace ORB_SLAM3 {
 
 class KeyFrame;
@@ -623,6 +646,7 @@ class Frame : public ShimTable {
                                         const bool bRight = false) const {      // Frame.cc:774-843
     return area(x, y, r, true, minLevel, maxLevel, bRight);
   }
+  PLI_SHIM_FRAME_EXTRA
 };
 
 class KeyFrame : public ShimTable {
@@ -670,6 +694,7 @@ class KeyFrame : public ShimTable {
   std::set<MapPoint*> GetMapPoints();
   MapPoint* GetMapPoint(const size_t& idx);
   void AddMapPoint(MapPoint* pMP, const size_t& idx);
+  PLI_SHIM_KEYFRAME_EXTRA
 };
 
 class MapPoint {
@@ -679,7 +704,8 @@ class MapPoint {
   bool mbBad = false;
   float mMinDistInv = 0, mMaxDistInv = 0, mfMaxDistance = 0;      // the invariance bounds are stored as the getters return them
   int nObs = 0;
-  std::map<KeyFrame*, int> mObservations;
+  std::map<KeyFrame*, PLI_SHIM_OBSERVATION_T> mObservations;
+  PLI_SHIM_MAPPOINT_EXTRA
 
   bool mbTrackInView = false, mbTrackInViewR = false;
   float mTrackProjX = 0, mTrackProjY = 0, mTrackProjXR = 0, mTrackProjYR = 0, mTrackDepth = 0, mTrackDepthR = 0;
@@ -690,8 +716,14 @@ class MapPoint {
   cv::Mat GetNormal() { return mNormalVector.clone(); }
   cv::Mat GetDescriptor() { ShimLog::get().put(ShimLog::GET_DESCRIPTOR, index, 0); return mDescriptor.clone(); }
   bool isBad() { return mbBad; }
+#ifdef PLI_SHIM_MAPPOINT_OWN_SCALE
+  float GetMinDistanceInvariance();
+  float GetMaxDistanceInvariance();
+  int PredictScale(const float& currentDist, Frame* pF);
+#else
   float GetMinDistanceInvariance() { return mMinDistInv; }
   float GetMaxDistanceInvariance() { return mMaxDistInv; }
+#endif
   int Observations() { return nObs; }
   bool IsInKeyFrame(KeyFrame* pKF) { return mObservations.count(pKF) != 0; }
   int GetIndexInKeyFrame(KeyFrame* pKF) { return mObservations.count(pKF) ? mObservations[pKF] : -1; }

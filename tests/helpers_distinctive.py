@@ -3,10 +3,15 @@
 restated_point / restated_line follow the reference's statements one by one (MapPoint.cc:330-359, MapLine.cc:278-312); independent is
 the definition alone, written another way.  All three return (BestIdx, BestMedian, [median_i]) as exact integers for a group of
 N >= 1 descriptors, an (N, 32) uint8 array in the order of the reference's vDescriptors.
+
+The two restatements take `mut`, a set of deliberate misreadings that tests/test_ref_pin_map.py wants the fixtures of the reference's
+own compiled code to reject (MUTANTS): "median_half" takes the median at index N / 2, "pick_le" lets a later row with an equal
+median win (<= in the pick).
 """
 import numpy as np
 
 INT_MAX = 2147483647
+MUTANTS = ("median_half", "pick_le")
 POPCOUNT = np.array([bin(v).count("1") for v in range(256)], np.int32)
 
 
@@ -15,7 +20,7 @@ def descriptor_distance(a, b):
     return int(POPCOUNT[a ^ b].sum())
 
 
-def restated_point(group):
+def restated_point(group, mut=()):
     group = np.asarray(group, np.uint8).reshape(-1, 32)
     N = len(group)                                                        # const size_t N = vDescriptors.size();
     Distances = [[np.float32(0)] * N for _ in range(N)]                   # float Distances[N][N];
@@ -31,15 +36,15 @@ def restated_point(group):
     for i in range(N):
         vDists = [int(v) for v in Distances[i]]                           # vector<int> vDists(Distances[i], Distances[i] + N);
         vDists = sorted(vDists)
-        median = vDists[int(0.5 * (N - 1))]
+        median = vDists[N // 2 if "median_half" in mut else int(0.5 * (N - 1))]
         medians.append(median)
-        if median < BestMedian:
+        if (median <= BestMedian) if "pick_le" in mut else (median < BestMedian):
             BestMedian = median
             BestIdx = i
     return BestIdx, BestMedian, medians
 
 
-def restated_line(group):
+def restated_line(group, mut=()):
     group = np.asarray(group, np.uint8).reshape(-1, 32)
     NL = len(group)
     Distances = [[np.float32(0)] * NL for _ in range(NL)]                 # Distances.resize(NL, vector<float>(NL, 0));
@@ -54,9 +59,9 @@ def restated_line(group):
     medians = []
     for i in range(NL):
         vDists = sorted(int(v) for v in Distances[i])
-        median = vDists[int(0.5 * (NL - 1))]
+        median = vDists[NL // 2 if "median_half" in mut else int(0.5 * (NL - 1))]
         medians.append(median)
-        if median < BestMedian:
+        if (median <= BestMedian) if "pick_le" in mut else (median < BestMedian):
             BestMedian = median
             BestIdx = i
     return BestIdx, BestMedian, medians

@@ -131,9 +131,9 @@ def local_queries(view, th=1.0, far_points=False, th_far=0.0, sf=SF, points=None
 
 
 def search_local_points(points, descs, pose, kp, desc, uright, occupied, cam=CAM, th=1.0, far_points=False, th_far=0.0,
-                        nnratio=0.8, limit=0.5, exits=None, misread=()):
-    """-> view, best_idx2, n_in_view, nmatches, queries."""
-    view = is_in_frustum(points, pose, cam, limit, exits=exits, misread=misread)
+                        nnratio=0.8, limit=0.5, exits=None, misread=(), lr=None):
+    """-> view, best_idx2, n_in_view, nmatches, queries.  lr: the level_ratio table (default: test_fuse_search_cpu.level_ratio)."""
+    view = is_in_frustum(points, pose, cam, limit, lr=lr, exits=exits, misread=misread)
     q = local_queries(view, th, far_points, th_far, points=points)
     bounds = (cam.min_x, cam.max_x, cam.min_y, cam.max_y)
     n, best, _ = hm.search_local_map(q, descs, kp, desc, uright, occupied, bounds, nnratio)

@@ -202,8 +202,9 @@ def _unproject_stereo(S, cam, rules):
     return [_gemm_t(T, r, xc, T[12 + r]) for r in range(3)]
 
 
-def _reproject(S, stereo, cam, x3, z, q, tag):
+def _reproject(S, stereo, cam, x3, z, q, tag, bf_of=None):
     fx, fy, cx, cy, bf = cam
+    bf = bf if bf_of is None else F32(bf_of)
     T = S["pose"]
     x = F32(_dotd(T[0:3], x3) + float(T[9]))
     y = F32(_dotd(T[3:6], x3) + float(T[10]))
@@ -225,9 +226,15 @@ def _reproject(S, stereo, cam, x3, z, q, tag):
     return 2 if float(e2) > 7.8 * sig else 0
 
 
+MUTANTS = ("stereo2_always", "unproject_un", "far_gt", "bf_neighbour", "last_wins")
+
+
 def new_map_point_pair(S1, S2, cam=CAM, mb=MB, far=False, th_far=0.0, ratio_factor=RATIO_FACTOR, rules=(), q=None):
-    """-> (status code, x3D as 3 float32 or None).  rules: deliberate misreadings for the hand cases ("stereo2_always": the second
-    stereo parallax also when the first side is stereo, against `else if` :544; "unproject_un": mvKeysUn in UnprojectStereo).
+    """-> (status code, x3D as 3 float32 or None).  rules: deliberate misreadings for the hand cases and for the fixtures of the
+    reference's own code (MUTANTS; tests/test_ref_pin_map.py): "stereo2_always": the second stereo parallax also when the first
+    side is stereo, against `else if` :544; "unproject_un": mvKeysUn in UnprojectStereo; "far_gt": dist > mThFarPoints at :660;
+    "bf_neighbour": pKF2's mbf (S2["bf"], where a case gives the neighbour another one) in the second keyframe's stereo gate,
+    against mpCurrentKeyFrame->mbf :641; "last_wins" is closed_form's: the last accepted neighbour keeps a feature.
     q (a dict) takes the compared quantities."""
     q = q if q is not None else {}
     with np.errstate(all="ignore"):
@@ -288,7 +295,8 @@ def new_map_point_pair(S1, S2, cam=CAM, mb=MB, far=False, th_far=0.0, ratio_fact
         g = _reproject(S1, stereo1, cam, x3, z1, q, "1")
         if g:
             return CODE["reproj1_mono" if g == 1 else "reproj1_stereo"], None
-        g = _reproject(S2, stereo2, cam, x3, z2, q, "2")          # (bf is mpCurrentKeyFrame's here too, :641)
+        g = _reproject(S2, stereo2, cam, x3, z2, q, "2",          # (bf is mpCurrentKeyFrame's here too, :641)
+                       bf_of=S2.get("bf") if "bf_neighbour" in rules else None)
         if g:
             return CODE["reproj2_mono" if g == 1 else "reproj2_stereo"], None
         d1 = [F32(x3[r] - T1[12 + r]) for r in range(3)]
@@ -297,7 +305,7 @@ def new_map_point_pair(S1, S2, cam=CAM, mb=MB, far=False, th_far=0.0, ratio_fact
         q.update(dist1=float(dist1), dist2=float(dist2))
         if dist1 == 0 or dist2 == 0:
             return CODE["dist_zero"], None
-        if far and (dist1 >= th_far or dist2 >= th_far):
+        if far and ((dist1 > th_far or dist2 > th_far) if "far_gt" in rules else (dist1 >= th_far or dist2 >= th_far)):
             return CODE["far"], None
         ratio_dist = F32(dist2 / dist1)
         ratio_octave = F32(SCALE[S1["octave"]] / SCALE[S2["octave"]])
@@ -315,11 +323,19 @@ def _empty(nkf, n1):
             np.zeros((nkf, n1, 3), np.float32), np.zeros(nkf, np.int32))
 
 
+def _side2(nb, j, bf2):
+    S = side(nb.kf, j)
+    if bf2 is not None:
+        S["bf"] = bf2
+    return S
+
+
 def create_new_map_points(kf1, nbrs, cam=CAM, mb=MB, ratio_factor=RATIO_FACTOR, coarse=False, far=False, th_far=0.0, exits=None,
-                          scalar_search=False, order=None, stop_before=None):
+                          scalar_search=False, order=None, stop_before=None, mut=(), bf2=None):
     """The reference's loop.  -> (matches12[nkf, n1], nmatches[nkf], status[nkf, n1], x3d[nkf, n1, 3], nnew[nkf]).
     order (a list) takes (k, idx1, idx2, x3D) per created map point, in the order of :670-683; stop_before: CheckNewKeyFrames()
-    answers true before that neighbour (:389).  The label of an unmatched feature (taken earlier / not matched) is what the search
+    answers true before that neighbour (:389); mut: MUTANTS, passed to every pair; bf2: pKF2->mbf per neighbour where it is not the
+    current keyframe's (read by the mutant "bf_neighbour" alone).  The label of an unmatched feature (taken earlier / not matched) is what the search
     on the state at entry says, which the loop itself never asks: it is computed for the comparison only."""
     ex = exits if exits is not None else Counter()
     search = search_for_triangulation if scalar_search else search_for_triangulation_fast
@@ -341,7 +357,8 @@ def create_new_map_points(kf1, nbrs, cam=CAM, mb=MB, ratio_factor=RATIO_FACTOR, 
                 else:
                     ex["not_matched"] += 1
                 continue
-            st, x = new_map_point_pair(side(kf1, i), side(nb.kf, int(m[i])), cam, mb, far, th_far, ratio_factor)
+            st, x = new_map_point_pair(side(kf1, i), _side2(nb, int(m[i]), None if bf2 is None else bf2[k]), cam, mb, far, th_far,
+                                       ratio_factor, rules=mut)
             status[k, i] = st
             ex[STATUS[st]] += 1
             if st == CREATED:
@@ -353,20 +370,22 @@ def create_new_map_points(kf1, nbrs, cam=CAM, mb=MB, ratio_factor=RATIO_FACTOR, 
     return matches, nmatches, status, x3d, nnew
 
 
-def closed_form(kf1, nbrs, cam=CAM, mb=MB, ratio_factor=RATIO_FACTOR, coarse=False, far=False, th_far=0.0):
-    """Every (neighbour, feature) pair on the map-point state at entry, then per feature the first accepted neighbour keeps it."""
+def closed_form(kf1, nbrs, cam=CAM, mb=MB, ratio_factor=RATIO_FACTOR, coarse=False, far=False, th_far=0.0, mut=(), bf2=None):
+    """Every (neighbour, feature) pair on the map-point state at entry, then per feature the first accepted neighbour keeps it
+    (mut "last_wins": the last one; the other MUTANTS go to every pair)."""
     n1, nkf = len(kf1.t.node), len(nbrs)
     matches, nmatches, status, x3d, nnew = _empty(nkf, n1)
     for k, nb in enumerate(nbrs):
         matches[k], _ = search_for_triangulation_fast(kf1.t, nb.kf.t, nb.F12, nb.ep, False, coarse, False)
         for i in np.nonzero(matches[k] >= 0)[0]:
-            st, x = new_map_point_pair(side(kf1, i), side(nb.kf, int(matches[k, i])), cam, mb, far, th_far, ratio_factor)
+            st, x = new_map_point_pair(side(kf1, i), _side2(nb, int(matches[k, i]), None if bf2 is None else bf2[k]), cam, mb, far,
+                                       th_far, ratio_factor, rules=mut)
             status[k, i] = st
             if st == CREATED:
                 x3d[k, i] = x
     for i in range(n1):
         taken = False
-        for k in range(nkf):
+        for k in (range(nkf - 1, -1, -1) if "last_wins" in mut else range(nkf)):
             if matches[k, i] < 0:
                 continue
             if taken:
